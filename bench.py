@@ -53,6 +53,8 @@ The JSON line also carries
   others        (1 GPU, config 2) the other figures of DESIGN.md measured in this run, after the timed region: config 4's launch
                 shape, K3, the fused 4:4:4 kernel, K2, subsample_hv2 (ms, fraction of 8 TB/s), configs 3 and 5 as pipelines
                 with the host and the GPU entropy stage (Gpixel/s, threads, what binds them); each K5-verified;
+  dump_outputs  (--dump-outputs DIR) which records and positions of the last timed step's output rank 0 wrote to DIR/<name>.npy:
+                `pixels` (configs 2 / 4), `pixels_host_reader` + `pixels_gpu_reader` (config 3), `coefs` (config 5);
   cpu_baseline  the CPU restatement of the model path (oracle/hvc_oracle.c, scalar, 1 thread) timed on this
                 host on a bounded sample of the same workload.  The oracle is the checker, timed as a
                 baseline only: this leg is its only use here (parity is the job of tests/).
@@ -291,6 +293,31 @@ def expected_checksums(config, n_distinct, rank):
         return None
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: every file of one run together stays under this
+DUMP_SEED = 0x44554D50
+
+
+def dump_outputs(out_dir, name, records, specs, which, budget=DUMP_BYTES):
+    """--dump-outputs: what the timed path's last step left in `records` (device tensor [n, record stride], planes laid out by
+    `specs`; which = "plane_offset" for pixels, "coef_offset" for coefficients) written as out_dir/<name>.npy, float32 [k, m]: the
+    tight records of the batch's first and last record and of two seeded ones (the last lies furthest into the buffer), whole when
+    they fit in `budget` bytes, otherwise the same seeded sample of positions of each.  Same arguments, same inputs, same sample: two
+    builds compare output for output.  Returns what the JSON line says about the file."""
+    import torch
+    import video_coding_amd as hvc
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    n = records.shape[0]
+    rows = sorted({0, n - 1} | {int(r) for r in rng.choice(n, size=min(n, 2), replace=False)})
+    tight = hvc.hvc.tight_records(records[rows], specs, which)
+    size = tight.shape[1]
+    m = min(size, (budget - 4096) // (4 * len(rows)))   # (4096: room for the .npy header)
+    if m < size:
+        tight = tight[:, torch.from_numpy(np.sort(rng.choice(size, size=m, replace=False))).to(tight.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), tight.cpu().numpy().astype(np.float32))
+    return {"file": name + ".npy", "records": rows, "positions": "all %d" % size if m == size else "%d of %d, seeded" % (m, size)}
+
+
 def dist_env():
     """RANK / WORLD_SIZE / LOCAL_RANK as torch.distributed.run exports them (1 process = 1 GPU)."""
     return (int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")),
@@ -517,7 +544,12 @@ def parse_args(argv=None):
     ap.add_argument("--sustain-seconds", type=float, default=6.0,
                     help="after the K timed steps: this many seconds of the same step back to back, reported as "
                          "`sustained` (never part of `value`); 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the K timed steps, rank 0 writes what the last one computed to DIR/<name>.npy (float32, a "
+                         "fixed seeded sample of the batch, < 64 MB in all)")
     args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     wl = WORKLOADS[args.config]
     args.frames = args.frames or wl["frames"]
     args.distinct = args.distinct or (4 if args.config in (3, 5) else 8)
@@ -631,6 +663,9 @@ def run_files(args, rank, world, local_rank, rehearsal):
 
         dt_local = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, world, dist)
         dt = max_over_ranks(dt_local, world, dist, dev)
+        dumped = dump_outputs(args.dump_outputs, "pixels_%s_reader" % reader, d_pix.view(n, info.pixel_bytes),
+                              [dict(blocks_w=L.blocks_w, blocks_h=L.blocks_h, plane_offset=L.plane_offset) for L in info.layout[:info.n_comp]],
+                              "plane_offset", DUMP_BYTES // 2) if (args.dump_outputs and rank == 0) else None
         timed = stats[-args.steps:]
         chk = bc.verify(ctx, d_pix, info.pixel_bytes, n, "configs_c3", args.distinct)["checksum"]
         ranks_ok = all_ranks_ok(chk["verified"] is True, world, dist, dev)
@@ -654,6 +689,8 @@ def run_files(args, rank, world, local_rank, rehearsal):
             "bound": ("pcie: unstuffed segments up + GPU reader kernels" if gpu else
                       "host: Huffman thread time / threads ~ wall (%.0f ms / %d = %.0f ms)" % (e_ms, threads, e_ms / threads)),
             "k_decode_packed_algorithmic_GBps": round(n * blocks_per_frame * ALGO_BYTES_PER_BLOCK / (max(k_ms, 1e-9) * 1e-3) / 1e9, 1)}
+        if dumped:
+            readers[reader]["dump_outputs"] = dumped
     ok = all(r["ranks_verified"] == world for r in readers.values())
     if rank == 0:
         host, gpu_r = readers["host"], readers["gpu"]
@@ -726,6 +763,7 @@ def run_encode(args, rank, world, local_rank, rehearsal):
     ctx.set_profiling(True)
     dt = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, world, dist)
     dt = max_over_ranks(dt, world, dist, dev)
+    dumped = dump_outputs(args.dump_outputs, "coefs", d_coefs, specs, "coef_offset") if (args.dump_outputs and rank == 0) else None
     kernel_ms = ctx.kernel_ms_history(min(args.steps, 64))
     chk = bc.verify(ctx, hvc.hvc.tight_records(d_coefs, specs, "coef_offset"), tcfs * 2, args.frames, "configs_c5", args.distinct)["checksum"]
     ranks_ok = all_ranks_ok(chk["verified"] is True, world, dist, dev)
@@ -751,6 +789,8 @@ def run_encode(args, rank, world, local_rank, rehearsal):
                "checksum": {"kernel": "k_checksum (K5) over EVERY coefficient record", "verified": chk["verified"], "ranks_verified": ranks_ok,
                             "expected": "tests/golden/bench_checksums.json:configs_c5", "rank0": chk["distinct"]},
                "per_rank_kernel_ms": {"mean_min_max": [[round(x, 4) for x in r] for r in per_rank], "rank0_cpus": node_cpus}}
+        if dumped:
+            out["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             from oracle import orc   # (the checker, timed as the baseline only)
             frames, done, t0 = recs, 0, time.perf_counter()
@@ -844,6 +884,7 @@ def main():
 
     dt = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, world, dist)
     dt = max_over_ranks(dt, world, dist, "cpu" if rehearsal else "cuda")
+    dumped = dump_outputs(args.dump_outputs, "pixels", d_pix, specs, "plane_offset") if (args.dump_outputs and rank == 0) else None
 
     # HIP events recorded around k_decode_packed inside the timed region (one pair per launch, ring of 64)
     kernel_ms = ctx.kernel_ms_history(min(args.steps * launches, 64))
@@ -954,6 +995,8 @@ def main():
                                      "what": "k_decode_packed's event-timed launches inside the timed region, every rank's own"}
         if sustained is not None:
             out["sustained"] = sustained
+        if dumped:
+            out["dump_outputs"] = dumped
     ctx.close()
     if rank == 0:
         if world == 1 and args.config == 2 and not args.no_others and not rehearsal:

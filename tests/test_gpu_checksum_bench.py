@@ -99,15 +99,27 @@ def test_headline_launch_verifies_every_one_of_its_1024_frames():
     assert rec["roofline"]["traffic"] or rec["roofline"]["traffic_source"].startswith(("stale", "no committed"))
 
 
-def test_bench_layouts_aligned_and_tight_decode_the_same_frames():
+def test_bench_layouts_aligned_and_tight_decode_the_same_frames(tmp_path):
     """bench.py lays its resident batch out with every plane on a 64 KiB / 2 MiB boundary (hvc.layout_alignment); --tight = planes back
-    to back.  Both verify against the same golden checksums (K5 runs on the planes gathered tight), configs 2 and 5."""
-    for extra in ([], ["--config", "5"]):
-        recs = [_run_bench(extra + ["--steps", "2", "--warmup", "1", "--frames", "32", "--no-cpu-baseline", "--no-others", "--sustain-seconds", "0"] + t)
-                for t in ([], ["--tight"])]
+    to back.  Both verify against the same golden checksums (K5 runs on the planes gathered tight), configs 2 and 5; and --dump-outputs
+    writes the same file from both (config 2: whole records, whose K5 is the golden one of their distinct frame)."""
+    with open(os.path.join(GOLDEN, "bench_checksums.json")) as f:
+        golden = [int(v, 16) for v in json.load(f)["bench_config2"]["rank0"]]
+    for extra, name in (([], "pixels"), (["--config", "5"], "coefs")):
+        dirs = [str(tmp_path / ("%s%d" % (name, k))) for k in range(2)]
+        recs = [_run_bench(extra + ["--steps", "2", "--warmup", "1", "--frames", "32", "--no-cpu-baseline", "--no-others", "--sustain-seconds", "0",
+                                    "--dump-outputs", d] + t) for d, t in zip(dirs, ([], ["--tight"]))]
         assert "boundary" in recs[0]["config"]["layout"] and "tight" in recs[1]["config"]["layout"]
         assert all(r["checksum"]["verified"] is True for r in recs)
         assert recs[0]["checksum"]["rank0"] == recs[1]["checksum"]["rank0"]
+        dumps = [np.load(os.path.join(d, name + ".npy")) for d in dirs]
+        assert recs[0]["dump_outputs"] == recs[1]["dump_outputs"] and recs[0]["dump_outputs"]["records"][-1] == 31
+        assert dumps[0].dtype == np.float32 and np.array_equal(dumps[0], dumps[1])
+        assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in os.listdir(dirs[0])) <= 64_000_000
+        if name == "pixels":
+            assert recs[0]["dump_outputs"]["positions"].startswith("all ")
+            rows = recs[0]["dump_outputs"]["records"]
+            assert list(checksum_records(dumps[0].astype(np.uint8))) == [golden[r % 8] for r in rows]
 
 
 def test_bench_n_rank_path_on_one_gpu():

@@ -53,28 +53,48 @@ def test_patch_uses_only_what_the_binding_defines(tmp_path):
     assert chk.check_patch(str(p))[0] == ["coefs_pointer"]
 
 
-REF = "/root/reference"
+def patched(preimage):
+    """The patch applied to the reference as tests/golden/ocaml_patch_preimage.json pins it (made from the reference by
+    tests/golden/make_patch_preimage.py, which also runs `patch` on the reference's files): every hunk lands exactly where its
+    header says (no offset, no fuzz) on the reference's own lines, checked by their SHA-256.  Returns {path: [(line number in the
+    patched file, text)]}: the hunks' resulting lines and the fixture's anchors (reference lines outside the hunks) where the
+    patch moves them."""
+    import hashlib
+    files = chk.parse_patch(open(chk.PATCH).read())
+    assert sorted(files) == sorted(preimage["files"])
+    out = {}
+    for path, hunks in files.items():
+        ref = preimage["files"][path]
+        assert [(h["old_start"], h["old_len"]) for h in hunks] == [(w["old_start"], w["old_len"]) for w in ref["hunks"]], path
+        lines, delta, end = [], 0, 0
+        for h, want in zip(hunks, ref["hunks"]):
+            assert h["old_start"] > end and h["old_start"] + h["old_len"] - 1 <= ref["lines"], (path, h["old_start"])  # in order, inside the file
+            assert h["new_start"] == h["old_start"] + delta, (path, h["old_start"])
+            pre = "".join(ln[1:] + "\n" for ln in h["lines"] if ln[0] in " -")
+            assert hashlib.sha256(pre.encode()).hexdigest() == want["sha256"], (path, h["old_start"])
+            n = h["new_start"]
+            for ln in h["lines"]:
+                if ln[0] in " +":
+                    lines.append((n, ln[1:]))
+                    n += 1
+            end = h["old_start"] + h["old_len"] - 1
+            delta += h["new_len"] - h["old_len"]
+        for text, old in ref["anchors"].items():
+            assert not any(h["old_start"] <= old < h["old_start"] + h["old_len"] for h in hunks), (path, text)
+            lines.append((old + sum(h["new_len"] - h["old_len"] for h in hunks if h["old_start"] < old), text))
+        out[path] = sorted(lines)
+    return out
 
 
-def test_patch_applies_to_the_reference(tmp_path):
-    """integration/ocaml/hvc_backend.patch is a real unified diff against the reference's decoder.ml / decoder.mli /
-    dune / plane.mli: `patch --dry-run` accepts it, and applied it leaves the functions INTEGRATION.md names.  (The
-    reference exists in the build container only; its files are copied to a temporary directory and never travel.)"""
-    import shutil
-    import subprocess
-    import pytest
-    files = ["jpeg/model/src/decoder.ml", "jpeg/model/src/decoder.mli", "jpeg/model/src/encoder.ml", "jpeg/model/src/encoder.mli",
-             "jpeg/model/src/dune", "common/src/plane.mli"]
-    if not all(os.path.exists(os.path.join(REF, f)) for f in files):
-        pytest.skip("the reference tree is not on this machine")
-    for f in files:
-        os.makedirs(os.path.dirname(tmp_path / f), exist_ok=True)
-        shutil.copy(os.path.join(REF, f), tmp_path / f)
-    for flag in (["--dry-run"], []):
-        r = subprocess.run(["patch", "-p1", "--no-backup-if-mismatch"] + flag, stdin=open(chk.PATCH), cwd=tmp_path, capture_output=True, text=True)
-        assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout, r.stdout + r.stderr
-    ml = (tmp_path / "jpeg/model/src/decoder.ml").read_text()
-    mli = (tmp_path / "jpeg/model/src/decoder.mli").read_text()
+def test_patch_applies_to_the_reference():
+    """integration/ocaml/hvc_backend.patch is a real unified diff against the reference's decoder.ml / decoder.mli / encoder.ml /
+    encoder.mli / dune / plane.mli: it applies exactly (patched() above), and applied it leaves the functions INTEGRATION.md
+    names, in an order OCaml accepts."""
+    from conftest import golden_json
+    post = patched(golden_json("ocaml_patch_preimage.json"))
+    text = {p: "\n".join(t for _, t in lines) for p, lines in post.items()}
+    # (in `text` the lines stand in the patched file's order: the index comparisons below are line comparisons)
+    ml, mli = text["jpeg/model/src/decoder.ml"], text["jpeg/model/src/decoder.mli"]
     for name in ("let decode_gpu ", "let decode_a_frame_gpu ", "module Gpu = struct", "?(decode_block = decode_block)",
                  "module Gpu_slot = struct", "let decode_frames_gpu (hvc : Hvc.ctx) (files : Bits.t list) : Frame.t list ="):
         assert name in ml, name
@@ -82,7 +102,7 @@ def test_patch_applies_to_the_reference(tmp_path):
     assert ml.index("let get_yuv_frame decoder") < ml.index("let decode_frames_gpu") and ml.index("module Gpu = struct") < ml.index("module Gpu_slot")
     assert "val decode_gpu : Hvc.ctx -> t -> unit" in mli and "val decode_a_frame_gpu" in mli
     assert "val decode_frames_gpu : Hvc.ctx -> Bits.t list -> Frame.t list" in mli
-    enc, enci = (tmp_path / "jpeg/model/src/encoder.ml").read_text(), (tmp_path / "jpeg/model/src/encoder.mli").read_text()
+    enc, enci = text["jpeg/model/src/encoder.ml"], text["jpeg/model/src/encoder.mli"]
     for name in ("let encode_seq_with ~encode_block (t : t) =", "let encode_seq (t : t) = encode_seq_with ~encode_block t",
                  "let encode_seq_gpu (hvc : Hvc.ctx) (t : t) =", "let encode_420_gpu hvc ~frame ~quality ~writer =",
                  "let encode_420_frames_gpu (hvc : Hvc.ctx) ~quality jobs =", "module Gpu_slot = struct"):
@@ -91,8 +111,8 @@ def test_patch_applies_to_the_reference(tmp_path):
     assert "val encode_420_frames_gpu : Hvc.ctx -> quality:int -> (Frame.t * Bitstream_writer.t) list -> unit" in enci
     # the exported signature of encode_seq is the reference's own (an optional argument would not match it)
     assert "val encode_seq : t -> Block.t Sequence.t" in enci and "val encode_seq_gpu : Hvc.ctx -> t -> Block.t Sequence.t" in enci
-    assert "val plane : t -> Base_bigstring.t" in (tmp_path / "common/src/plane.mli").read_text()
-    assert "ctypes.foreign" in (tmp_path / "jpeg/model/src/dune").read_text()
+    assert "val plane : t -> Base_bigstring.t" in text["common/src/plane.mli"]
+    assert "ctypes.foreign" in text["jpeg/model/src/dune"]
     # balanced: what the patch ADDS opens and closes its own brackets, comments and modules (a cheap stand-in for the
     # parser this image does not have), hunk by hunk
     added = "\n".join(ln[1:] for ln in open(chk.PATCH).read().split("\n") if ln.startswith("+") and not ln.startswith("+++"))

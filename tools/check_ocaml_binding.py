@@ -191,6 +191,37 @@ def check_patch(patch=None, binding=None):
     return [u for u in used if u not in defined], used
 
 
+def parse_patch(text):
+    """{path: [hunk, ...]} of a unified diff, hunk = dict(old_start, old_len, new_start, new_len, lines) with `lines` the hunk's
+    body (prefix kept).  A body is read by the counts its header gives; a body that does not match them raises ValueError."""
+    files, lines, i = {}, text.split("\n"), 0
+    while i < len(lines):
+        ln = lines[i]
+        i += 1
+        if ln.startswith("+++ "):
+            path = ln[4:].split("\t")[0]
+            hunks = files.setdefault(path[2:] if path.startswith("b/") else path, [])
+        elif ln.startswith("@@ "):
+            m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", ln)
+            if not m:
+                raise ValueError("bad hunk header: " + ln)
+            h = dict(old_start=int(m.group(1)), old_len=int(m.group(2) or 1), new_start=int(m.group(3)),
+                     new_len=int(m.group(4) or 1), lines=[])
+            old = new = 0
+            while old < h["old_len"] or new < h["new_len"]:
+                body = lines[i] if i < len(lines) else None
+                if body is None or body[:1] not in (" ", "-", "+"):
+                    raise ValueError("hunk %s ends after %d old / %d new lines" % (ln, old, new))
+                old += body[0] in " -"
+                new += body[0] in " +"
+                h["lines"].append(body)
+                i += 1
+            if old != h["old_len"] or new != h["new_len"]:
+                raise ValueError("hunk %s holds %d old / %d new lines" % (ln, old, new))
+            hunks.append(h)
+    return files
+
+
 def main():
     problems, unbound, n = check()
     missing, used = check_patch()
