@@ -215,6 +215,30 @@ HVC_API int hvc_decode_frames_yuv444(hvc_ctx *ctx, const int16_t *coefs, size_t 
  * this to cross-check independent implementations at full batch sizes. */
 HVC_API int hvc_set_decode_kernel(hvc_ctx *ctx, int which);
 
+/* Which ARITHMETIC the decode entry points compute.  HVC_ARITH_MODEL (the default) is the OCaml model's decoder, bit for
+ * bit.  HVC_ARITH_HARDCAML is the reference's Hardcaml RTL decoder datapath (jpeg/hardcaml/src), bit for bit: the low 12
+ * bits of every coefficient (a 12-bit coefficient bus and DC predictor: an absolute DC is taken mod 4096), dequantisation
+ * sext12((q & 0xff) * c mod 4096), the 12-bit fixed-point matrix IDCT of dct.ml (Idct_config: ROM round(4096 * M), pass 1
+ * rounded to 4 fractional bits, pass 2 rounded and saturated to [-128, 127]), + 128.  Its output differs from the model's
+ * by a few levels (the reference's tests allow 2).  The setting is per context and applies to hvc_dequant_idct_recon,
+ * hvc_decode_frames (host and device memory), hvc_decode_frames_submit, hvc_jpeg_decode, hvc_jpeg_decode_batch and
+ * hvc_jpeg_decode_batch_gpu; hvc_last_wide_blocks reports 0 after a HARDCAML call (no block needs a fix-up).  The fused
+ * 4:4:4 entry points (hvc_decode_frames_yuv444, hvc_jpeg_decode_yuv444, hvc_jpeg_decode_batch_yuv444) have no RTL form:
+ * under HARDCAML they return HVC_E_INVALID_ARG and leave their output untouched.  The encoder ignores the setting.
+ * hvc_set_arithmetic: HVC_E_INVALID_ARG for any other value. */
+typedef enum { HVC_ARITH_MODEL = 0, HVC_ARITH_HARDCAML = 1 } hvc_arith;
+HVC_API int hvc_set_arithmetic(hvc_ctx *ctx, int arith);
+HVC_API int hvc_get_arithmetic(const hvc_ctx *ctx, int *arith);
+
+/* How far the RTL datapath strays from the model: the arguments of hvc_decode_frames, and instead of pixels one byte per
+ * block, max over its 64 pixels of |model - hardcaml| (test_decoder.ml's max_reconstructed_diff).  For frame f, component
+ * k, block (bx, by) the byte is at max_diff + f * diff_frame_stride + (blocks of the components before k) + by * blocks_w
+ * + bx; diff_frame_stride >= the frame's blocks (n_frames > 1).  max_diff lives where `where` says, as the records do.
+ * Independent of hvc_set_arithmetic.  The model's pixels are made in device scratch and never leave the GPU. */
+HVC_API int hvc_decode_frames_divergence(hvc_ctx *ctx, const int16_t *coefs, size_t coef_frame_stride,
+                                         const uint16_t *qtabs, int n_qtabs, const hvc_component *comps, int n_comp,
+                                         int n_frames, uint8_t *max_diff, size_t diff_frame_stride, int where);
+
 /* Number of blocks the last decode call on ctx routed through the wide
  * (64-bit) fix-up kernel (diagnostic; synchronises the stream). */
 HVC_API int hvc_last_wide_blocks(hvc_ctx *ctx, uint64_t *count);

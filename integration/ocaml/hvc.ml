@@ -354,6 +354,21 @@ let jpeg_entropy_decode_restart =
 
 let set_restart_markers = foreign "hvc_set_restart_markers" (ctx @-> int @-> returning int)
 
+(* the block stage's arithmetic: 0 = the model (default), 1 = the Hardcaml RTL datapath
+   int hvc_set_arithmetic(ctx, arith);  int hvc_get_arithmetic(ctx, arith) *)
+let set_arithmetic = foreign "hvc_set_arithmetic" (ctx @-> int @-> returning int)
+let get_arithmetic = foreign "hvc_get_arithmetic" (ctx @-> ptr int @-> returning int)
+
+(* int hvc_decode_frames_divergence(ctx, coefs, coef_frame_stride, qtabs, n_qtabs, comps, n_comp, n_frames,
+                                    max_diff, diff_frame_stride, where): max |model - hardcaml| per block *)
+let decode_frames_divergence =
+  foreign
+    "hvc_decode_frames_divergence"
+    ~release_runtime_lock:true
+    (ctx @-> ptr int16_t @-> size_t @-> ptr uint16_t @-> int @-> ptr Component.t @-> int @-> int
+    @-> ptr char @-> size_t @-> int @-> returning int)
+;;
+
 (* int hvc_jpeg_entropy_decode2(jpeg_a, n_a, info_a, coefs_a, status_a, jpeg_b, n_b, info_b, coefs_b, status_b):
    two files decoded in turn on the calling thread *)
 let jpeg_entropy_decode2 =

@@ -9,6 +9,15 @@
     python -m video_coding_amd oyuv convert IN.yuv WxH OUT.yuv [W2xH2] [-frames A-B] [-format 420] [-out-format F]
                                             [-src-offset X,Y]    formats 420 422 444 YUY2 UYVY YVYU
                                                                                   tools/src/oconv.ml:58-133
+    python -m video_coding_amd simulate decoder IN.jpg [-yuv OUT.yuv] [-blocks N] [-error-tolerance T]
+                                                                                  jpeg/bin/simulate.ml:54-80
+
+`simulate decoder` is the reference's decoder simulation (Test_decoder.test) computed by the Hardcaml RTL twin
+(hvc_set_arithmetic HVC_ARITH_HARDCAML) instead of a cycle simulation: -yuv writes the RTL's whole frame the way
+`model decode frame` writes the model's; for each block in decode order (the first N with -blocks) whose
+max_reconstructed_diff from the model is >= T (default 2, test_decoder.ml:27) it prints block_number,
+max_reconstructed_diff and the RTL's pixels in the reference's 2-hex-digit pixel_block form, one record per line.
+The reference's (comp ...) summary of the model's block is not printed, nor are waveforms (-waves).
 
 Every pixel goes through libhvc_jpeg.so on the GPU (there is no CPU path); output text matches the
 reference's (`print_s` of an int / a float), so jpeg/test/*.t expectations can be checked verbatim.
@@ -59,6 +68,38 @@ def model_encode_frame(a):
 
 METRICS = {"max-difference": (yuv.max_difference, str), "mean-difference": (yuv.mean_difference, yuv.float_to_string),
            "mean-square-error": (yuv.mean_square_error, yuv.float_to_string), "psnr": (yuv.psnr, yuv.float_to_string)}
+
+
+def simulate_decoder(a):
+    data = open(a.jpeg, "rb").read()
+    info, coefs = hvc.jpeg_entropy_decode(data)
+    ctx = hvc.Context(a.device)
+    try:
+        ctx.set_arithmetic("hardcaml")
+        _, pixels = ctx.jpeg_decode(data)
+        specs = [dict(blocks_w=L.blocks_w, blocks_h=L.blocks_h, qtab=L.qtab, coef_offset=L.coef_offset)
+                 for L in info.layout[:info.n_comp]]
+        diff = ctx.decode_divergence(coefs, info.coef_count, info.qtab_array(), specs, 1)[0]
+    finally:
+        ctx.close()
+    if a.yuv:
+        with open(a.yuv, "wb") as f:
+            f.write(hvc.jpeg_get_yuv_frame(info, pixels).tobytes())
+    order = hvc.decode_order_positions(info)
+    if a.blocks is not None:
+        order = order[:a.blocks]
+    ends = np.cumsum([L.blocks_w * L.blocks_h for L in info.layout[:info.n_comp]])
+    planes = info.planes(pixels)
+    for n, pos in enumerate(order):
+        d = int(diff[pos])
+        if d < a.error_tolerance:
+            continue
+        k = int(np.searchsorted(ends, pos, side="right"))
+        b = int(pos - (ends[k - 1] if k else 0))
+        bw = info.layout[k].blocks_w
+        blk = planes[k][(b // bw) * 8:(b // bw) * 8 + 8, (b % bw) * 8:(b % bw) * 8 + 8]
+        rows = " ".join("(" + " ".join("%02x" % v for v in row) + ")" for row in blk)
+        print("((block_number %d) (max_reconstructed_diff %d) (pixels (%s)))" % (n, d, rows))
 
 
 def oyuv_compare(a):
@@ -177,6 +218,15 @@ def main(argv=None):
     p.add_argument("-out-format", dest="out_format", type=format_arg, default=None)
     p.add_argument("-src-offset", dest="src_offset", type=offset_arg, default=(0, 0))
     p.set_defaults(fn=oyuv_convert)
+
+    sim = top.add_parser("simulate").add_subparsers(dest="what", required=True)
+    p = sim.add_parser("decoder", help="the Hardcaml RTL decoder's output and its divergence from the model")
+    p.add_argument("jpeg")
+    p.add_argument("-yuv", default=None)
+    p.add_argument("-blocks", type=int, default=None, help="Number of blocks to compare (decode order)")
+    p.add_argument("-error-tolerance", dest="error_tolerance", type=int, default=2,
+                   help="Allowable error in reconstructed pixels compared to the model reference")
+    p.set_defaults(fn=simulate_decoder)
 
     a = ap.parse_args(argv)
     a.fn(a)

@@ -221,6 +221,9 @@ void hvc_destroy(hvc_ctx *c) {
     if (c->d_fix_list) (void)hipFree(c->d_fix_list);
     if (c->d_in) (void)hipFree(c->d_in);
     if (c->d_out) (void)hipFree(c->d_out);
+    if (c->d_div_px) (void)hipFree(c->d_div_px);
+    if (c->d_div_in) (void)hipFree(c->d_div_in);
+    if (c->d_div_out) (void)hipFree(c->d_div_out);
     if (c->d_sums) (void)hipFree(c->d_sums);
     if (c->d_aux) (void)hipFree(c->d_aux);
     if (c->d_aux2) (void)hipFree(c->d_aux2);
@@ -416,6 +419,18 @@ int hvc_set_restart_markers(hvc_ctx *c, int honour) try {
     return HVC_OK;
 } HVC_ABI_CATCH
 
+int hvc_set_arithmetic(hvc_ctx *c, int arith) try {
+    if (!c || (arith != HVC_ARITH_MODEL && arith != HVC_ARITH_HARDCAML)) return HVC_E_INVALID_ARG;
+    c->arith = arith;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_get_arithmetic(const hvc_ctx *c, int *arith) try {
+    if (!c || !arith) return HVC_E_INVALID_ARG;
+    *arith = c->arith;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
 int hvc_set_profiling(hvc_ctx *c, int enabled) try {
     if (!c) return HVC_E_INVALID_ARG;
     c->profiling = enabled != 0;
@@ -552,7 +567,27 @@ static int upload_dcfix(hvc_ctx *c, const std::vector<unsigned> &ids, const std:
     return HVC_OK;
 }
 
-static int apply_wide_dc(hvc_ctx *c, const hvc::DecodeParams &P, const std::vector<WideFix> &wide) {
+// The twin's parameters for the geometry and records of a DecodeParams (hvc_hardcaml.h)
+static hvc::HardcamlParams hardcaml_params(const hvc::DecodeParams &P, const uint16_t *qtabs, int n_qtabs) {
+    hvc::HardcamlParams H;
+    std::memset(&H, 0, sizeof H);
+    H.coefs = P.coefs;
+    H.pixels = P.pixels;
+    H.coef_fs = P.coef_fs;
+    H.pixel_fs = P.pixel_fs;
+    H.n_frames = P.n_frames;
+    H.n_comp = P.n_comp;
+    H.tiles_per_frame = P.tiles_per_frame;
+    for (int i = 0; i < P.n_comp; i++) H.comp[i] = P.comp[i];
+    hvc::prepare_hardcaml_tables(qtabs, n_qtabs, H.qq);
+    H.dc_plane = P.dc_plane;
+    H.dc_fs = P.dc_fs;
+    return H;
+}
+
+// qtabs: the call's tables (the twin's form is made from them)
+static int apply_wide_dc(hvc_ctx *c, const hvc::DecodeParams &P, const std::vector<WideFix> &wide, const uint16_t *qtabs,
+                         int n_qtabs) {
     std::vector<unsigned> ids;
     std::vector<long long> dcs;
     for (const WideFix &w : wide) {
@@ -573,6 +608,11 @@ static int apply_wide_dc(hvc_ctx *c, const hvc::DecodeParams &P, const std::vect
     if (r) return r;
     hvc::DecodeParams Q = P;
     Q.dc_plane = nullptr; // (the list carries the DC)
+    if (c->arith == HVC_ARITH_HARDCAML) {
+        const hvc::HardcamlParams H = hardcaml_params(Q, qtabs, n_qtabs);
+        HIPCHK(c, hvc::launch_hardcaml_dcfix(H, d_count, d_ids, d_dcs, c->stream));
+        return HVC_OK;
+    }
     HIPCHK(c, hvc::launch_decode_dcfix(Q, d_count, d_ids, d_dcs, c->stream));
     return HVC_OK;
 }
@@ -735,8 +775,11 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
 
+    // HVC_ARITH_HARDCAML: the RTL twin (hvc_hardcaml.hip) in place of the model's kernels -- exact in int32 for every
+    // input, so no fix-up list and no wide kernel
+    const bool twin = c->arith == HVC_ARITH_HARDCAML;
     // fix-up list: one entry per block of a LAUNCH at most (launches follow one another on the stream, each consumes its own)
-    size_t need = (size_t)((unsigned long long)per * ids_per_frame);
+    size_t need = twin ? 0 : (size_t)((unsigned long long)per * ids_per_frame);
     if (need > c->fix_cap) {
         void *p = c->d_fix_list;
         size_t cap = c->fix_cap * sizeof(unsigned);
@@ -766,7 +809,9 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
     P.kernel_sel = (c->decode_kernel == 1 || c->decode_kernel == 3) ? c->decode_kernel : 0;
     if (wide_only) c->wide_host = (long long)((unsigned long long)n_frames * L.blocks_per_frame);
     // one launch: consumes counter fix_phase, its wide kernel clears the other one (fix_assign / fix_commit above)
+    if (twin) c->wide_host = 0;
     auto launch = [&](hvc::DecodeParams &Q, hipEvent_t k0, hipEvent_t k1) -> hipError_t {
+        if (twin) return hvc::launch_hardcaml(hardcaml_params(Q, qtabs, n_qtabs), c->stream, k0, k1);
         if (wide_only) return hvc::launch_decode_wide_only(Q, c->stream, k0, k1);
         fix_assign(c, Q);
         const hipError_t e = hvc::launch_decode(Q, c->stream, k0, k1);
@@ -791,7 +836,7 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
 
     if (where == HVC_MEM_DEVICE) {
         if (((uintptr_t)coefs & 15) || ((uintptr_t)pixels & 7)) return HVC_E_ALIGNMENT;
-        if (dc_plane && P.kernel_sel != 0) return HVC_E_INVALID_ARG;
+        if (dc_plane && P.kernel_sel != 0 && !twin) return HVC_E_INVALID_ARG;
         P.coefs = coefs;
         P.pixels = pixels;
         P.dc_plane = dc_plane;
@@ -800,7 +845,7 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
         const int slot = (int)(c->k_calls % HVC_PROF_RING);
         HIPCHK(c, launch_range(coefs, pixels, 0, n_frames, prof ? c->k0[slot] : nullptr, prof ? c->k1[slot] : nullptr));
         if (prof) c->k_calls++;
-        if (wide && !wide->empty()) return apply_wide_dc(c, P, *wide);
+        if (wide && !wide->empty()) return apply_wide_dc(c, P, *wide, qtabs, n_qtabs);
         return HVC_OK;
     }
     if (dc_plane || (wide && !wide->empty())) return HVC_E_INVALID_ARG;
@@ -839,12 +884,103 @@ int hvc_decode_frames(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const ui
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------
+// max |model - hardcaml| per block: the model's block stage into device scratch (tight planes), then the twin's compare
+// form reads those pixels back beside its own and writes one byte per block.  Frames go in chunks of at most ~256 MB of
+// model pixels.
+int hvc_decode_frames_divergence(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
+                                 const hvc_component *comps_in, int n_comp_in, int n_frames, uint8_t *max_diff,
+                                 size_t diff_fs, int where) try {
+    if (!c || n_frames < 0) return HVC_E_INVALID_ARG;
+    if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
+    int r = check_qtabs(qtabs, n_qtabs, false);
+    if (r) return r;
+    hvc_component kept[HVC_MAX_COMP];
+    int n_comp = 0;
+    if ((r = drop_empty_components(comps_in, n_comp_in, kept, &n_comp))) return r;
+    if (n_comp == 0 || n_frames == 0) return HVC_OK;
+    if (!coefs || !max_diff) return HVC_E_INVALID_ARG;
+    // the model's pixels: every plane tight (stride = blocks_w * 8), one after the other
+    hvc_component tight[HVC_MAX_COMP];
+    size_t px_fs = 0, blocks = 0;
+    int blk0[HVC_MAX_COMP];
+    for (int i = 0; i < n_comp; i++) {
+        tight[i] = kept[i];
+        tight[i].stride = (size_t)kept[i].blocks_w * 8;
+        tight[i].plane_offset = px_fs;
+        px_fs += tight[i].stride * (size_t)kept[i].blocks_h * 8;
+        blk0[i] = (int)blocks;
+        blocks += (size_t)kept[i].blocks_w * kept[i].blocks_h;
+    }
+    Layout L;
+    if ((r = make_layout(tight, n_comp, n_qtabs, L))) return r;
+    if (n_frames > 1 && (coef_fs < L.coef_span || diff_fs < blocks)) return HVC_E_INVALID_ARG;
+    if (coef_fs & 7) return HVC_E_ALIGNMENT;
+    if (where == HVC_MEM_DEVICE && ((uintptr_t)coefs & 15)) return HVC_E_ALIGNMENT;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)256 << 20) / px_fs));
+    if ((r = grow(c, &c->d_div_px, &c->div_px_cap, (size_t)chunk * px_fs))) return r;
+    const size_t cspan = ((size_t)(chunk - 1) * coef_fs + L.coef_span) * sizeof(int16_t);
+    const size_t dspan = (size_t)(chunk - 1) * diff_fs + blocks;
+    if (where == HVC_MEM_HOST) {
+        if ((r = grow(c, &c->d_div_in, &c->div_in_cap, cspan))) return r;
+        if ((r = grow(c, &c->d_div_out, &c->div_out_cap, dspan))) return r;
+    }
+    const int arith_saved = c->arith;
+    const bool prof_saved = c->profiling;
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int cnt = std::min(chunk, n_frames - f0);
+        const int16_t *d_coefs = coefs + (size_t)f0 * coef_fs;
+        uint8_t *d_diff = max_diff + (size_t)f0 * diff_fs;
+        if (where == HVC_MEM_HOST) {
+            HIPCHK(c, hipMemcpyAsync(c->d_div_in, d_coefs, ((size_t)(cnt - 1) * coef_fs + L.coef_span) * sizeof(int16_t),
+                                     hipMemcpyHostToDevice, c->stream));
+            d_coefs = (const int16_t *)c->d_div_in;
+            d_diff = (uint8_t *)c->d_div_out;
+        }
+        c->arith = HVC_ARITH_MODEL;
+        c->profiling = false;
+        r = decode_frames_impl(c, d_coefs, coef_fs, qtabs, n_qtabs, tight, n_comp, cnt, (uint8_t *)c->d_div_px, px_fs,
+                               HVC_MEM_DEVICE, nullptr, 0, nullptr);
+        c->arith = arith_saved;
+        c->profiling = prof_saved;
+        if (r) return r;
+        hvc::DecodeParams P;
+        std::memset(&P, 0, sizeof P);
+        P.coefs = d_coefs;
+        P.pixels = (uint8_t *)c->d_div_px;
+        P.coef_fs = coef_fs;
+        P.pixel_fs = px_fs;
+        P.n_frames = cnt;
+        P.n_comp = L.n_comp;
+        P.tiles_per_frame = L.tiles_per_frame;
+        for (int i = 0; i < L.n_comp; i++) P.comp[i] = L.comp[i];
+        hvc::HardcamlParams H = hardcaml_params(P, qtabs, n_qtabs);
+        H.diff = d_diff;
+        H.diff_fs = diff_fs;
+        for (int i = 0; i < n_comp; i++) H.blk0[i] = blk0[i];
+        HIPCHK(c, hvc::launch_hardcaml(H, c->stream));
+        if (where == HVC_MEM_HOST) {
+            if (cnt == 1 || diff_fs == blocks)
+                HIPCHK(c, hipMemcpyAsync(max_diff + (size_t)f0 * diff_fs, d_diff, (size_t)(cnt - 1) * diff_fs + blocks,
+                                         hipMemcpyDeviceToHost, c->stream));
+            else
+                HIPCHK(c, hipMemcpy2DAsync(max_diff + (size_t)f0 * diff_fs, diff_fs, d_diff, diff_fs, blocks, (size_t)cnt,
+                                           hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+// ---------------------------------------------------------------------------
 // 4:2:0 coefficient records -> tight 4:4:4 frames (block stage + crop + chroma upsample fused)
 int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
                               const hvc_component *comps, int n_comp, int n_frames, int width, int height, uint8_t *frames,
                               size_t frame_stride, int where, const int16_t *dc_plane, size_t dc_fs,
                               const std::vector<WideFix> *wide) {
     if (!c || !coefs || !frames || !comps || n_frames < 0) return HVC_E_INVALID_ARG;
+    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path: hvc_set_arithmetic)
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     int r = check_qtabs(qtabs, n_qtabs, false);
     if (r) return r;

@@ -62,6 +62,7 @@ static int decode_one_with_wide_dc(hvc_ctx *c, const hvc_jpeg_info *info, const 
 int hvc_jpeg_decode_yuv444(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *info, uint8_t *frame,
                            size_t frame_cap) try {
     if (!c || !jpeg || !info || !frame) return HVC_E_INVALID_ARG;
+    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path: hvc_set_arithmetic)
     hvc::RestartScope honour(c->honour_restart); // (hvc_set_restart_markers; off = the model's behaviour)
     int r = hvc_jpeg_read_header(jpeg, n, info);
     if (r) return r;
@@ -486,6 +487,7 @@ int hvc_jpeg_decode_batch(hvc_ctx *c, const uint8_t *const *jpegs, const size_t 
 int hvc_jpeg_decode_batch_yuv444(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames,
                                  int threads, int frames_per_chunk, uint8_t *frames, size_t frame_stride, int where,
                                  hvc_batch_stats *stats) try {
+    if (c && c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path: hvc_set_arithmetic)
     return decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, frames, frame_stride, where, stats,
                              true);
 } HVC_ABI_CATCH

@@ -1000,5 +1000,6 @@ static int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_
 int hvc_jpeg_decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads,
                               int frames_per_chunk, uint8_t *pixels, size_t pixel_fs, int where, int yuv444,
                               hvc_batch_stats *stats) try {
+    if (c && yuv444 && c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path)
     return decode_batch_gpu(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, yuv444 != 0);
 } HVC_ABI_CATCH

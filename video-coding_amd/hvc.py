@@ -27,7 +27,9 @@ SYMBOLS = [
     "hvc_subsample420", "hvc_subsample422", "hvc_upsample422", "hvc_crop_planes", "hvc_yuv_frame_bytes", "hvc_yuv_convert",
     "hvc_host_alloc", "hvc_host_free", "hvc_host_register", "hvc_host_unregister", "hvc_decode_frames_submit",
     "hvc_encode_frames_submit", "hvc_wait", "hvc_slot_query", "hvc_slot_last_stats", "hvc_huffman_code_tables",
+    "hvc_set_arithmetic", "hvc_get_arithmetic", "hvc_decode_frames_divergence",
 ]
+HVC_ARITH = {"model": 0, "hardcaml": 1}  # enum hvc_arith
 HVC_SLOTS = 4       # enum { HVC_SLOTS }
 HVC_E_BUSY = -12
 
@@ -153,6 +155,9 @@ def lib():
         L.hvc_jpeg_entropy_decode.argtypes = [vp, sz, ip, vp]
         L.hvc_jpeg_entropy_decode_restart.argtypes = [vp, sz, ip, vp]
         L.hvc_set_restart_markers.argtypes = [vp, i]
+        L.hvc_set_arithmetic.argtypes = [vp, i]
+        L.hvc_get_arithmetic.argtypes = [vp, C.POINTER(i)]
+        L.hvc_decode_frames_divergence.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
         L.hvc_jpeg_get_yuv_frame.argtypes = [ip, vp, vp, sz, C.POINTER(sz)]
         L.hvc_jpeg_get_cropped_planes.argtypes = [ip, vp, vp, sz, C.POINTER(sz)]
         L.hvc_jpeg_entropy_decode2.argtypes = [vp, sz, ip, vp, C.POINTER(i), vp, sz, ip, vp, C.POINTER(i)]
@@ -290,6 +295,28 @@ def spread_records(tight, specs_tight, specs, stride, which):
         n = a["blocks_w"] * a["blocks_h"] * 64
         out[:, b[which]:b[which] + n] = tight[:, a[which]:a[which] + n]
     return out
+
+
+def decode_order_positions(info):
+    """For every block in the model's decode order (decode_seq, jpeg/model/src/decoder.ml:374-397: macroblocks in raster
+    order, inside one the components in turn, inside a component its vscale x hscale blocks row by row) its index in the
+    per-frame divergence array of hvc_decode_frames_divergence (the components' blocks back to back, each plane row-major)
+    -> int64 array.  Block n of this order is the reference's block_number n (hardcaml/test/test_decoder.ml)."""
+    n = info.n_comp
+    bw = [info.comp[k].decoded_width // 8 for k in range(n)]
+    bh = [info.comp[k].decoded_height // 8 for k in range(n)]
+    blk0 = np.concatenate([[0], np.cumsum([w * h for w, h in zip(bw, bh)])])
+    h0, v0 = info.comp[0].hscale, info.comp[0].vscale
+    if n == 0 or not h0 or not v0:
+        return np.zeros(0, dtype=np.int64)
+    mbw, mbh = info.comp[0].decoded_width // (8 * h0), info.comp[0].decoded_height // (8 * v0)
+    parts = []
+    for k in range(n):
+        hs, vs = info.comp[k].hscale, info.comp[k].vscale
+        # [mbh, mbw, vs, hs] positions of this component's blocks inside each macroblock
+        my, mx, y, x = np.meshgrid(np.arange(mbh), np.arange(mbw), np.arange(vs), np.arange(hs), indexing="ij")
+        parts.append((blk0[k] + (my * vs + y) * bw[k] + mx * hs + x).reshape(mbh, mbw, vs * hs))
+    return np.concatenate(parts, axis=2).reshape(-1).astype(np.int64) if parts else np.zeros(0, dtype=np.int64)
 
 
 # -- host front end / back end (no GPU needed) ------------------------------------------------
@@ -469,6 +496,35 @@ class Context:
     def set_restart_markers(self, honour=True):
         """the extension: the context's file-level entry points honour DRI / RSTn (default off = the model's behaviour)"""
         _chk(lib().hvc_set_restart_markers(self._h, 1 if honour else 0), "hvc_set_restart_markers")
+
+    def set_arithmetic(self, arith):
+        """"model" (default: the OCaml model's decoder) | "hardcaml" (the reference's RTL decoder datapath, bit for bit):
+        the block stage of every decode entry point except the fused 4:4:4 ones, which refuse "hardcaml"."""
+        _chk(lib().hvc_set_arithmetic(self._h, HVC_ARITH[arith] if isinstance(arith, str) else int(arith)),
+             "hvc_set_arithmetic")
+
+    @property
+    def arithmetic(self):
+        v = C.c_int()
+        _chk(lib().hvc_get_arithmetic(self._h, C.byref(v)), "hvc_get_arithmetic")
+        return {b: a for a, b in HVC_ARITH.items()}.get(v.value, v.value)
+
+    def decode_divergence(self, coefs, coef_frame_stride, qtabs, comps, n_frames, max_diff=None, diff_frame_stride=None):
+        """max |model - hardcaml| per block (hvc_decode_frames_divergence) -> uint8 array [n_frames, blocks per frame]
+        (host records), or into max_diff (device records: a torch uint8 tensor of n_frames * diff_frame_stride)"""
+        ca, w1 = _addr(coefs)
+        q = np.ascontiguousarray(qtabs, dtype=np.uint16).reshape(-1, 64)
+        arr = comps if not isinstance(comps, list) else components(comps)
+        blocks = sum(a.blocks_w * a.blocks_h for a in arr)
+        stride = blocks if diff_frame_stride is None else diff_frame_stride
+        if max_diff is None:
+            assert w1 == HVC_MEM_HOST, "device records: pass a device max_diff"
+            max_diff = np.zeros((n_frames, stride), dtype=np.uint8)
+        da, w2 = _addr(max_diff)
+        assert w1 == w2
+        _chk(lib().hvc_decode_frames_divergence(self._h, ca, coef_frame_stride, q.ctypes.data, q.shape[0], arr, len(arr),
+                                                n_frames, da, stride, w1), "hvc_decode_frames_divergence")
+        return max_diff
 
     def set_decode_kernel(self, which):
         """0 packed (default) | 1 unpacked int32 | 2 int64 for every block -- identical output"""
