@@ -224,7 +224,8 @@ HVC_API int hvc_set_decode_kernel(hvc_ctx *ctx, int which);
  * hvc_decode_frames (host and device memory), hvc_decode_frames_submit, hvc_jpeg_decode, hvc_jpeg_decode_batch and
  * hvc_jpeg_decode_batch_gpu; hvc_last_wide_blocks reports 0 after a HARDCAML call (no block needs a fix-up).  The fused
  * 4:4:4 entry points (hvc_decode_frames_yuv444, hvc_jpeg_decode_yuv444, hvc_jpeg_decode_batch_yuv444) have no RTL form:
- * under HARDCAML they return HVC_E_INVALID_ARG and leave their output untouched.  The encoder ignores the setting.
+ * under HARDCAML they return HVC_E_INVALID_ARG and leave their output untouched.  The encoder ignores the setting: it has
+ * its own, hvc_set_encode_arithmetic below.
  * hvc_set_arithmetic: HVC_E_INVALID_ARG for any other value. */
 typedef enum { HVC_ARITH_MODEL = 0, HVC_ARITH_HARDCAML = 1 } hvc_arith;
 HVC_API int hvc_set_arithmetic(hvc_ctx *ctx, int arith);
@@ -236,6 +237,32 @@ HVC_API int hvc_get_arithmetic(const hvc_ctx *ctx, int *arith);
  * + bx; diff_frame_stride >= the frame's blocks (n_frames > 1).  max_diff lives where `where` says, as the records do.
  * Independent of hvc_set_arithmetic.  The model's pixels are made in device scratch and never leave the GPU. */
 HVC_API int hvc_decode_frames_divergence(hvc_ctx *ctx, const int16_t *coefs, size_t coef_frame_stride,
+                                         const uint16_t *qtabs, int n_qtabs, const hvc_component *comps, int n_comp,
+                                         int n_frames, uint8_t *max_diff, size_t diff_frame_stride, int where);
+
+/* Which arithmetic the ENCODE entry points compute, independent of hvc_set_arithmetic.  HVC_ARITH_MODEL (the default) is
+ * the OCaml model's encoder, bit for bit.  HVC_ARITH_HARDCAML is the finished half of the reference's Hardcaml RTL
+ * encoder datapath (jpeg/hardcaml/src/encoder_datapath.ml), bit for bit: p - 128, the 12-bit fixed-point matrix DCT of
+ * dct.ml (Dct_config: ROM round(4096 * F), pass 1 rounded to 4 fractional bits, pass 2 rounded and saturated to 12 bits),
+ * and quant.ml's reciprocal quantiser, q = RND(R * (4096 / t), 12) (ties away from zero) wrapped to 12 bits.  The
+ * coefficient at natural position k is divided by table[Zigzag.forward[k]] and stored at record position
+ * Zigzag.forward[k], DC absolute: the DQT table convention of the model's Encoder.quant, so that the files decode as they
+ * should (the RTL's own test bench loads its table RAM in raster order, one of the upstream datapath's unfinished parts,
+ * with its run-length and Huffman stages, which are not reproduced: the records go to this library's entropy coders).
+ * Its coefficients differ from the model's by a few levels.  The setting is per context and applies to hvc_fdct_quant,
+ * hvc_encode_frames (host and device memory), hvc_encode_frames_submit, hvc_jpeg_encode, hvc_jpeg_encode_batch,
+ * hvc_jpeg_encode_batch_gpu and the encode step of hvc_encode_frames_recon (whose decode step follows hvc_set_arithmetic).
+ * Tables are validated as before (1..255, else HVC_E_RANGE).  hvc_set_encode_arithmetic: HVC_E_INVALID_ARG for any other
+ * value, the setting unchanged. */
+HVC_API int hvc_set_encode_arithmetic(hvc_ctx *ctx, int arith);
+HVC_API int hvc_get_encode_arithmetic(const hvc_ctx *ctx, int *arith);
+
+/* How far the RTL encoder's arithmetic strays from the model: the arguments of hvc_encode_frames, and instead of records
+ * one byte per block, min(255, max over its 64 coefficients of |q_model - q_hardcaml|).  For frame f, component k, block
+ * (bx, by) the byte is at max_diff + f * diff_frame_stride + (blocks of the components before k) + by * blocks_w + bx;
+ * diff_frame_stride >= the frame's blocks (n_frames > 1).  max_diff lives where `where` says, as the pixels do.
+ * Independent of both settings.  The model's records are made in device scratch and never leave the GPU. */
+HVC_API int hvc_encode_frames_divergence(hvc_ctx *ctx, const uint8_t *pixels, size_t pixel_frame_stride,
                                          const uint16_t *qtabs, int n_qtabs, const hvc_component *comps, int n_comp,
                                          int n_frames, uint8_t *max_diff, size_t diff_frame_stride, int where);
 

@@ -369,6 +369,21 @@ let decode_frames_divergence =
     @-> ptr char @-> size_t @-> int @-> returning int)
 ;;
 
+(* the encoder's arithmetic, independent of set_arithmetic: 0 = the model (default), 1 = the Hardcaml RTL DCT + quantiser
+   int hvc_set_encode_arithmetic(ctx, arith);  int hvc_get_encode_arithmetic(ctx, arith) *)
+let set_encode_arithmetic = foreign "hvc_set_encode_arithmetic" (ctx @-> int @-> returning int)
+let get_encode_arithmetic = foreign "hvc_get_encode_arithmetic" (ctx @-> ptr int @-> returning int)
+
+(* int hvc_encode_frames_divergence(ctx, pixels, pixel_frame_stride, qtabs, n_qtabs, comps, n_comp, n_frames,
+                                    max_diff, diff_frame_stride, where): max |model - hardcaml| coefficient per block *)
+let encode_frames_divergence =
+  foreign
+    "hvc_encode_frames_divergence"
+    ~release_runtime_lock:true
+    (ctx @-> ptr char @-> size_t @-> ptr uint16_t @-> int @-> ptr Component.t @-> int @-> int
+    @-> ptr char @-> size_t @-> int @-> returning int)
+;;
+
 (* int hvc_jpeg_entropy_decode2(jpeg_a, n_a, info_a, coefs_a, status_a, jpeg_b, n_b, info_b, coefs_b, status_b):
    two files decoded in turn on the calling thread *)
 let jpeg_entropy_decode2 =

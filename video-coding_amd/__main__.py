@@ -11,6 +11,7 @@
                                                                                   tools/src/oconv.ml:58-133
     python -m video_coding_amd simulate decoder IN.jpg [-yuv OUT.yuv] [-blocks N] [-error-tolerance T]
                                                                                   jpeg/bin/simulate.ml:54-80
+    python -m video_coding_amd simulate encoder IN.yuv WxH [-chroma 420] [-quality 75] [-blocks N] [-out OUT.jpg]
 
 `simulate decoder` is the reference's decoder simulation (Test_decoder.test) computed by the Hardcaml RTL twin
 (hvc_set_arithmetic HVC_ARITH_HARDCAML) instead of a cycle simulation: -yuv writes the RTL's whole frame the way
@@ -18,6 +19,12 @@
 max_reconstructed_diff from the model is >= T (default 2, test_decoder.ml:27) it prints block_number,
 max_reconstructed_diff and the RTL's pixels in the reference's 2-hex-digit pixel_block form, one record per line.
 The reference's (comp ...) summary of the model's block is not printed, nor are waveforms (-waves).
+
+`simulate encoder` is the same for the finished half of the RTL encoder datapath (its forward DCT and quantiser,
+hvc_set_encode_arithmetic HVC_ARITH_HARDCAML): for each block in encode order (MCU-interleaved, the first N with -blocks)
+it prints ((block_number n) (max_coef_diff d)), d the largest difference of a quantised coefficient from the model's;
+-out writes the file the RTL arithmetic makes of the frame (its records through this library's entropy coder).
+`model encode frame -arithmetic hardcaml` writes that file as well.
 
 Every pixel goes through libhvc_jpeg.so on the GPU (there is no CPU path); output text matches the
 reference's (`print_s` of an int / a float), so jpeg/test/*.t expectations can be checked verbatim.
@@ -59,6 +66,7 @@ def model_encode_frame(a):
     y, u, v = yuv.read_frame(a.yuv, w, h, a.chroma)
     ctx = hvc.Context(a.device)
     try:
+        ctx.set_encode_arithmetic(a.arithmetic)
         jpg = ctx.jpeg_encode(y, u, v, w, h, a.chroma, a.quality)
     finally:
         ctx.close()
@@ -100,6 +108,31 @@ def simulate_decoder(a):
         blk = planes[k][(b // bw) * 8:(b // bw) * 8 + 8, (b % bw) * 8:(b % bw) * 8 + 8]
         rows = " ".join("(" + " ".join("%02x" % v for v in row) + ")" for row in blk)
         print("((block_number %d) (max_reconstructed_diff %d) (pixels (%s)))" % (n, d, rows))
+
+
+def simulate_encoder(a):
+    w, h = a.size
+    y, u, v = yuv.read_frame(a.yuv, w, h, a.chroma)
+    info = hvc.jpeg_encoder_layout(w, h, a.chroma, a.quality)
+    rec = hvc.encoder_pixel_record(info, y, u, v, w, h, a.chroma)
+    specs = [dict(blocks_w=L.blocks_w, blocks_h=L.blocks_h, qtab=L.qtab, coef_offset=L.coef_offset,
+                  plane_offset=L.plane_offset, stride=L.stride) for L in info.layout[:info.n_comp]]
+    ctx = hvc.Context(a.device)
+    try:
+        diff = ctx.encode_divergence(rec, info.pixel_bytes, info.qtab_array(), specs, 1)[0]
+        if a.out:
+            ctx.set_encode_arithmetic("hardcaml")
+            jpg = ctx.jpeg_encode(y, u, v, w, h, a.chroma, a.quality)
+    finally:
+        ctx.close()
+    if a.out:
+        with open(a.out, "wb") as f:
+            f.write(jpg)
+    order = hvc.decode_order_positions(info)
+    if a.blocks is not None:
+        order = order[:a.blocks]
+    for n, pos in enumerate(order):
+        print("((block_number %d) (max_coef_diff %d))" % (n, int(diff[pos])))
 
 
 def oyuv_compare(a):
@@ -197,6 +230,8 @@ def main(argv=None):
     p.add_argument("bits")
     p.add_argument("-quality", type=int, default=75)
     p.add_argument("-chroma", type=int, default=420, choices=[420, 422, 444])
+    p.add_argument("-arithmetic", default="model", choices=["model", "hardcaml"],
+                   help="hardcaml: the Hardcaml RTL encoder's DCT and quantiser (hvc_set_encode_arithmetic)")
     p.set_defaults(fn=model_encode_frame)
 
     oyuv = top.add_parser("oyuv").add_subparsers(dest="cmd", required=True)
@@ -227,6 +262,14 @@ def main(argv=None):
     p.add_argument("-error-tolerance", dest="error_tolerance", type=int, default=2,
                    help="Allowable error in reconstructed pixels compared to the model reference")
     p.set_defaults(fn=simulate_decoder)
+    p = sim.add_parser("encoder", help="the Hardcaml RTL encoder arithmetic's divergence from the model, and its file")
+    p.add_argument("yuv")
+    p.add_argument("size", type=size_arg)
+    p.add_argument("-chroma", type=int, default=420, choices=[420, 422, 444])
+    p.add_argument("-quality", type=int, default=75)
+    p.add_argument("-blocks", type=int, default=None, help="Number of blocks to compare (encode order)")
+    p.add_argument("-out", default=None, help="write the RTL arithmetic's JPEG file")
+    p.set_defaults(fn=simulate_encoder)
 
     a = ap.parse_args(argv)
     a.fn(a)

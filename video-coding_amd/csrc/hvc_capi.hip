@@ -431,6 +431,18 @@ int hvc_get_arithmetic(const hvc_ctx *c, int *arith) try {
     return HVC_OK;
 } HVC_ABI_CATCH
 
+int hvc_set_encode_arithmetic(hvc_ctx *c, int arith) try {
+    if (!c || (arith != HVC_ARITH_MODEL && arith != HVC_ARITH_HARDCAML)) return HVC_E_INVALID_ARG;
+    c->enc_arith = arith;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_get_encode_arithmetic(const hvc_ctx *c, int *arith) try {
+    if (!c || !arith) return HVC_E_INVALID_ARG;
+    *arith = c->enc_arith;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
 int hvc_set_profiling(hvc_ctx *c, int enabled) try {
     if (!c) return HVC_E_INVALID_ARG;
     c->profiling = enabled != 0;
@@ -1227,6 +1239,22 @@ int hvc_dequant_idct_recon(hvc_ctx *c, const int16_t *coefs, size_t coef_plane_s
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------
+// The encoder twin's parameters for the geometry of an EncodeParams (hvc_hardcaml.h)
+static hvc::HardcamlEncodeParams hardcaml_encode_params(const hvc::EncodeParams &P, const uint16_t *qtabs, int n_qtabs) {
+    hvc::HardcamlEncodeParams H;
+    std::memset(&H, 0, sizeof H);
+    H.pixels = P.pixels;
+    H.coefs = P.coefs;
+    H.coef_fs = P.coef_fs;
+    H.pixel_fs = P.pixel_fs;
+    H.n_frames = P.n_frames;
+    H.n_comp = P.n_comp;
+    H.tiles_per_frame = P.tiles_per_frame;
+    for (int i = 0; i < P.n_comp; i++) H.comp[i] = P.comp[i];
+    hvc::prepare_hardcaml_encode_tables(qtabs, n_qtabs, H.qr);
+    return H;
+}
+
 int hvc_encode_frames(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const uint16_t *qtabs, int n_qtabs,
                       const hvc_component *comps, int n_comp, int n_frames, int16_t *coefs, size_t coef_fs,
                       int where) try {
@@ -1258,6 +1286,10 @@ int hvc_encode_frames(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const 
     for (int i = 0; i < L.n_comp; i++) P.comp[i] = L.comp[i];
     for (int i = 0; i < n_qtabs * 64; i++) // fl((1 + 2^-16) / (4t)): see quant1 in hvc_kernels.hip
         P.qrcp[i] = (float)((1.0 + 1.0 / 65536.0) / (4.0 * (double)qtabs[i]));
+    // HVC_ARITH_HARDCAML (hvc_set_encode_arithmetic): the RTL encoder twin (hvc_hardcaml.hip) in place of k_encode
+    const bool twin = c->enc_arith == HVC_ARITH_HARDCAML;
+    hvc::HardcamlEncodeParams H;
+    if (twin) H = hardcaml_encode_params(P, qtabs, n_qtabs);
 
     // frames [f0, f0 + cnt) of the batch at d_pixels / d_coefs, in launches of `per` frames
     auto launch_range = [&](const uint8_t *d_pixels, int16_t *d_coefs, int f0, int cnt, hipEvent_t k0, hipEvent_t k1) -> hipError_t {
@@ -1266,7 +1298,17 @@ int hvc_encode_frames(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const 
             Pk.n_frames = f0 + cnt - f < per ? f0 + cnt - f : per;
             Pk.coefs = d_coefs + (size_t)f * coef_fs;
             Pk.pixels = d_pixels + (size_t)f * pixel_fs;
-            const hipError_t e = hvc::launch_encode(Pk, c->stream, f == f0 ? k0 : nullptr, f + per >= f0 + cnt ? k1 : nullptr);
+            hipEvent_t e0 = f == f0 ? k0 : nullptr, e1 = f + per >= f0 + cnt ? k1 : nullptr;
+            hipError_t e;
+            if (twin) {
+                hvc::HardcamlEncodeParams Hk = H;
+                Hk.n_frames = Pk.n_frames;
+                Hk.coefs = Pk.coefs;
+                Hk.pixels = Pk.pixels;
+                e = hvc::launch_hardcaml_encode(Hk, c->stream, e0, e1);
+            } else {
+                e = hvc::launch_encode(Pk, c->stream, e0, e1);
+            }
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
@@ -1392,6 +1434,96 @@ int hvc_fdct_quant(hvc_ctx *c, const uint8_t *plane, size_t stride, size_t plane
     if (!coef_plane_stride) coef_plane_stride = (size_t)blocks_w * blocks_h * 64;
     if (!plane_stride) plane_stride = stride * (size_t)blocks_h * 8;
     return hvc_encode_frames(c, plane, plane_stride, qtab, 1, &comp, 1, n_planes, coefs, coef_plane_stride, where);
+} HVC_ABI_CATCH
+
+// ---------------------------------------------------------------------------
+// max |model - hardcaml| per block of the encoder: the model's block stage (k_encode) into device scratch (tight
+// coefficient planes), then the encoder twin's compare form reads those records beside its own and writes one byte per
+// block.  Frames go in chunks of at most ~256 MB of model records.
+int hvc_encode_frames_divergence(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const uint16_t *qtabs, int n_qtabs,
+                                 const hvc_component *comps, int n_comp, int n_frames, uint8_t *max_diff, size_t diff_fs,
+                                 int where) try {
+    if (!c || !pixels || !max_diff || n_frames < 0) return HVC_E_INVALID_ARG;
+    if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
+    int r = check_qtabs(qtabs, n_qtabs, true);
+    if (r) return r;
+    for (int i = 0; i < n_qtabs * 64; i++) // (as hvc_encode_frames: the encoder's tables are 8-bit)
+        if (qtabs[i] > 255) return HVC_E_RANGE;
+    Layout L;
+    if ((r = make_layout(comps, n_comp, n_qtabs, L))) return r;
+    if (n_frames == 0) return HVC_OK;
+    // the model's records: the caller's pixel geometry, every coefficient plane tight, one after the other
+    hvc_component tight[HVC_MAX_COMP];
+    size_t cf = 0;
+    int blk0[HVC_MAX_COMP];
+    for (int i = 0; i < n_comp; i++) {
+        tight[i] = comps[i];
+        tight[i].coef_offset = cf;
+        blk0[i] = (int)(cf / 64);
+        cf += (size_t)comps[i].blocks_w * comps[i].blocks_h * 64;
+    }
+    const size_t blocks = cf / 64;
+    Layout T;
+    if ((r = make_layout(tight, n_comp, n_qtabs, T))) return r;
+    if (n_frames > 1 && (pixel_fs < L.pixel_span || diff_fs < blocks)) return HVC_E_INVALID_ARG;
+    if (pixel_fs & 7) return HVC_E_ALIGNMENT;
+    if (where == HVC_MEM_DEVICE && ((uintptr_t)pixels & 7)) return HVC_E_ALIGNMENT;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    const size_t rec_bytes = cf * sizeof(int16_t);
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)256 << 20) / rec_bytes));
+    if ((r = grow(c, &c->d_div_px, &c->div_px_cap, (size_t)chunk * rec_bytes))) return r;
+    const size_t pspan = (size_t)(chunk - 1) * pixel_fs + L.pixel_span;
+    const size_t dspan = (size_t)(chunk - 1) * diff_fs + blocks;
+    if (where == HVC_MEM_HOST) {
+        if ((r = grow(c, &c->d_div_in, &c->div_in_cap, pspan))) return r;
+        if ((r = grow(c, &c->d_div_out, &c->div_out_cap, dspan))) return r;
+    }
+    const int arith_saved = c->enc_arith;
+    const bool prof_saved = c->profiling;
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int cnt = std::min(chunk, n_frames - f0);
+        const uint8_t *d_pix = pixels + (size_t)f0 * pixel_fs;
+        uint8_t *d_diff = max_diff + (size_t)f0 * diff_fs;
+        if (where == HVC_MEM_HOST) {
+            HIPCHK(c, hipMemcpyAsync(c->d_div_in, d_pix, (size_t)(cnt - 1) * pixel_fs + L.pixel_span, hipMemcpyHostToDevice,
+                                     c->stream));
+            d_pix = (const uint8_t *)c->d_div_in;
+            d_diff = (uint8_t *)c->d_div_out;
+        }
+        c->enc_arith = HVC_ARITH_MODEL;
+        c->profiling = false;
+        r = hvc_encode_frames(c, d_pix, pixel_fs, qtabs, n_qtabs, tight, n_comp, cnt, (int16_t *)c->d_div_px, cf,
+                              HVC_MEM_DEVICE);
+        c->enc_arith = arith_saved;
+        c->profiling = prof_saved;
+        if (r) return r;
+        hvc::EncodeParams P;
+        std::memset(&P, 0, sizeof P);
+        P.pixels = d_pix;
+        P.coefs = (int16_t *)c->d_div_px;
+        P.coef_fs = cf;
+        P.pixel_fs = pixel_fs;
+        P.n_frames = cnt;
+        P.n_comp = T.n_comp;
+        P.tiles_per_frame = T.tiles_per_frame;
+        for (int i = 0; i < T.n_comp; i++) P.comp[i] = T.comp[i];
+        hvc::HardcamlEncodeParams H = hardcaml_encode_params(P, qtabs, n_qtabs);
+        H.diff = d_diff;
+        H.diff_fs = diff_fs;
+        for (int i = 0; i < n_comp; i++) H.blk0[i] = blk0[i];
+        HIPCHK(c, hvc::launch_hardcaml_encode(H, c->stream));
+        if (where == HVC_MEM_HOST) {
+            if (cnt == 1 || diff_fs == blocks)
+                HIPCHK(c, hipMemcpyAsync(max_diff + (size_t)f0 * diff_fs, d_diff, (size_t)(cnt - 1) * diff_fs + blocks,
+                                         hipMemcpyDeviceToHost, c->stream));
+            else
+                HIPCHK(c, hipMemcpy2DAsync(max_diff + (size_t)f0 * diff_fs, diff_fs, d_diff, diff_fs, blocks, (size_t)cnt,
+                                           hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
 } HVC_ABI_CATCH
 
 int hvc_upsample420(hvc_ctx *c, const uint8_t *src, int cw, int ch, size_t src_stride, uint8_t *dst,

@@ -48,6 +48,7 @@ struct hvc_ctx {
     bool honour_restart = false; // hvc_set_restart_markers: restart intervals honoured by the file-level entry points (an extension)
     int decode_kernel = 0; // hvc_set_decode_kernel: 0 packed (default), 1 unpacked int32, 2 int64 for every block, 3 q16
     int arith = HVC_ARITH_MODEL; // hvc_set_arithmetic: the block stage's arithmetic (HARDCAML: k_hardcaml, hvc_hardcaml.hip)
+    int enc_arith = HVC_ARITH_MODEL; // hvc_set_encode_arithmetic: the encoder's (HARDCAML: k_hardcaml_encode, hvc_hardcaml.hip)
     unsigned *d_fix_count = nullptr; // two counters, used alternately (see k_decode_wide); behind them (+ 8 bytes) the 64-bit
                                      // total of the last call's fix-up blocks over all its launches (hvc_last_wide_blocks)
     // [4], [5]: a second pair of counters, for the luma planes of the fused 4:4:4 path when they run through
@@ -63,7 +64,8 @@ struct hvc_ctx {
     size_t fix_cap = 0; // entries
     void *d_in = nullptr, *d_out = nullptr, *d_sums = nullptr, *d_aux = nullptr, *d_aux2 = nullptr;
     size_t in_cap = 0, out_cap = 0, sums_cap = 0, aux_cap = 0, aux2_cap = 0;
-    // hvc_decode_frames_divergence: the model's pixels, and (host memory calls) the records and the divergence bytes
+    // hvc_decode_frames_divergence / hvc_encode_frames_divergence: the model's output (pixels / records), and (host memory
+    // calls) the input and the divergence bytes
     void *d_div_px = nullptr, *d_div_in = nullptr, *d_div_out = nullptr;
     size_t div_px_cap = 0, div_in_cap = 0, div_out_cap = 0;
     int last_hip = 0;

@@ -28,6 +28,7 @@ SYMBOLS = [
     "hvc_host_alloc", "hvc_host_free", "hvc_host_register", "hvc_host_unregister", "hvc_decode_frames_submit",
     "hvc_encode_frames_submit", "hvc_wait", "hvc_slot_query", "hvc_slot_last_stats", "hvc_huffman_code_tables",
     "hvc_set_arithmetic", "hvc_get_arithmetic", "hvc_decode_frames_divergence",
+    "hvc_set_encode_arithmetic", "hvc_get_encode_arithmetic", "hvc_encode_frames_divergence",
 ]
 HVC_ARITH = {"model": 0, "hardcaml": 1}  # enum hvc_arith
 HVC_SLOTS = 4       # enum { HVC_SLOTS }
@@ -158,6 +159,9 @@ def lib():
         L.hvc_set_arithmetic.argtypes = [vp, i]
         L.hvc_get_arithmetic.argtypes = [vp, C.POINTER(i)]
         L.hvc_decode_frames_divergence.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
+        L.hvc_set_encode_arithmetic.argtypes = [vp, i]
+        L.hvc_get_encode_arithmetic.argtypes = [vp, C.POINTER(i)]
+        L.hvc_encode_frames_divergence.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
         L.hvc_jpeg_get_yuv_frame.argtypes = [ip, vp, vp, sz, C.POINTER(sz)]
         L.hvc_jpeg_get_cropped_planes.argtypes = [ip, vp, vp, sz, C.POINTER(sz)]
         L.hvc_jpeg_entropy_decode2.argtypes = [vp, sz, ip, vp, C.POINTER(i), vp, sz, ip, vp, C.POINTER(i)]
@@ -427,6 +431,20 @@ def jpeg_encoder_layout(width, height, chroma, quality):
     return info
 
 
+def encoder_pixel_record(info, y, u, v, width, height, chroma):
+    """the padded pixel record hvc_jpeg_encode hands its block stage (Plane.blit_available of the frame's planes into
+    zero-filled planes of jpeg_encoder_layout's geometry, encoder.ml:514-516) -> uint8 array of info.pixel_bytes"""
+    out = np.zeros(info.pixel_bytes, dtype=np.uint8)
+    cw = width if chroma == 444 else width // 2
+    ch = height // 2 if chroma == 420 else height
+    for k, (p, sw, sh) in enumerate(((y, width, height), (u, cw, ch), (v, cw, ch))):
+        L = info.layout[k]
+        bw, bh = min(sw, info.comp[k].decoded_width), min(sh, info.comp[k].decoded_height)
+        plane = out[L.plane_offset:L.plane_offset + L.stride * L.blocks_h * 8].reshape(-1, L.stride)
+        plane[:bh, :bw] = np.asarray(p, dtype=np.uint8).reshape(sh, sw)[:bh, :bw]
+    return out
+
+
 def jpeg_entropy_encode(info, coefs):
     coefs = np.ascontiguousarray(coefs, dtype=np.int16)
     assert coefs.size == info.coef_count
@@ -524,6 +542,35 @@ class Context:
         assert w1 == w2
         _chk(lib().hvc_decode_frames_divergence(self._h, ca, coef_frame_stride, q.ctypes.data, q.shape[0], arr, len(arr),
                                                 n_frames, da, stride, w1), "hvc_decode_frames_divergence")
+        return max_diff
+
+    def set_encode_arithmetic(self, arith):
+        """"model" (default: the OCaml model's encoder) | "hardcaml" (the reference's RTL encoder DCT and quantiser, bit
+        for bit): the block stage of every encode entry point.  Independent of set_arithmetic."""
+        _chk(lib().hvc_set_encode_arithmetic(self._h, HVC_ARITH[arith] if isinstance(arith, str) else int(arith)),
+             "hvc_set_encode_arithmetic")
+
+    @property
+    def encode_arithmetic(self):
+        v = C.c_int()
+        _chk(lib().hvc_get_encode_arithmetic(self._h, C.byref(v)), "hvc_get_encode_arithmetic")
+        return {b: a for a, b in HVC_ARITH.items()}.get(v.value, v.value)
+
+    def encode_divergence(self, pixels, pixel_frame_stride, qtabs, comps, n_frames, max_diff=None, diff_frame_stride=None):
+        """min(255, max |q_model - q_hardcaml|) per block (hvc_encode_frames_divergence) -> uint8 array [n_frames, blocks
+        per frame] (host pixels), or into max_diff (device pixels: a torch uint8 tensor of n_frames * diff_frame_stride)"""
+        pa, w1 = _addr(pixels)
+        q = np.ascontiguousarray(qtabs, dtype=np.uint16).reshape(-1, 64)
+        arr = comps if not isinstance(comps, list) else components(comps)
+        blocks = sum(a.blocks_w * a.blocks_h for a in arr)
+        stride = blocks if diff_frame_stride is None else diff_frame_stride
+        if max_diff is None:
+            assert w1 == HVC_MEM_HOST, "device pixels: pass a device max_diff"
+            max_diff = np.zeros((n_frames, stride), dtype=np.uint8)
+        da, w2 = _addr(max_diff)
+        assert w1 == w2
+        _chk(lib().hvc_encode_frames_divergence(self._h, pa, pixel_frame_stride, q.ctypes.data, q.shape[0], arr, len(arr),
+                                                n_frames, da, stride, w1), "hvc_encode_frames_divergence")
         return max_diff
 
     def set_decode_kernel(self, which):
