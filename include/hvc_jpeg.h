@@ -600,6 +600,48 @@ typedef struct hvc_slot_stats {
 } hvc_slot_stats;
 HVC_API int hvc_slot_last_stats(hvc_ctx *ctx, int slot, hvc_slot_stats *stats);
 
+/* Fixed-point DCT: the model's parametric Dct.Fixed_point (jpeg/model/src/dct.ml:443-482) and the precision search of
+ * jpeg/bin/dct.ml, bit for bit.  The ROM of rom_prec p is round_nearest(M * 2^p), M the static x86 forward matrix
+ * (dct.ml:255-337); the inverse uses its transpose.  T = round(C X, p - tp), Y = round(T C^T, p + tp), rounding ties away
+ * from zero (a negative shift is a left shift).  Accepted: 0 <= rom_prec <= 16, 0 <= transpose_prec <= 8, |x| <= 2048
+ * into the forward transform and |x| <= 32768 (the largest |Y| of any accepted forward call) into the inverse; anything
+ * else is HVC_E_RANGE, never a wrong result.  The float64 reference is fmul (fmul F X) F^T (dct.ml:210-218), F = M or M^T,
+ * each sum from 0.0 in order k = 0..7, no fused multiply-add.  Blocks are 64 int32 in row-major order.
+ *
+ * hvc_dct_blocks is the search's input generator, a pure function of (seed, range, block index): element j of block i
+ * is ((w * 2 range) >> 32) - range in [-range, range), w the low (j even) or high (j odd) 32 bits of the (32 i + j / 2)-th
+ * output of SplitMix64 seeded with `seed`.  Upstream draws from OCaml's Random instead; this generator makes every
+ * configuration of a search see the same blocks and any worst block reproducible from its index.  1 <= range <= 32768.
+ *
+ * hvc_dct_error_search runs blocks first_block .. first_block + n_blocks - 1 through every configuration.  FORWARD and
+ * INVERSE use the fwd_* / inv_* fields and the error of a block is max |fixed - reference| over its 64 outputs; ROUND_TRIP
+ * uses both and the error is max |x - inverse(forward(x))| (an integer).  range <= 2048 (forward, round trip) or
+ * <= 32768 (inverse).  results[i] is the largest error and the smallest block index that has it, the same for any split
+ * of the block range.  All parameters are checked before anything runs: HVC_E_RANGE and HVC_E_INVALID_ARG write nothing.
+ * cfg and results are host memory; the call blocks.
+ *
+ * hvc_dct_fixed / hvc_dct_reference: explicit blocks, `where` as elsewhere (device memory: in and out 4-byte aligned,
+ * 8-byte for doubles).  hvc_dct_fixed always waits for its range check: under HVC_MEM_DEVICE a block with an input out of
+ * range is left unwritten and the call returns HVC_E_RANGE. */
+#define HVC_DCT_FORWARD 0
+#define HVC_DCT_INVERSE 1
+#define HVC_DCT_ROUND_TRIP 2
+typedef struct hvc_dct_config {
+    int mode, fwd_rom_prec, fwd_transpose_prec, inv_rom_prec, inv_transpose_prec;
+} hvc_dct_config;
+typedef struct hvc_dct_error {
+    double max_error;
+    uint64_t worst_block;
+} hvc_dct_error;
+HVC_API int hvc_dct_rom(int rom_prec, int32_t *rom64);   /* host only: the forward ROM the kernels use */
+HVC_API int hvc_dct_matrix(double *m64);                 /* host only: the float64 matrix M */
+HVC_API int hvc_dct_blocks(uint64_t seed, int range, uint64_t first, size_t n, int32_t *out); /* host only */
+HVC_API int hvc_dct_fixed(hvc_ctx *ctx, int direction, int rom_prec, int transpose_prec, const int32_t *in, int32_t *out,
+                          size_t n_blocks, int where);
+HVC_API int hvc_dct_reference(hvc_ctx *ctx, int direction, const int32_t *in, double *out, size_t n_blocks, int where);
+HVC_API int hvc_dct_error_search(hvc_ctx *ctx, const hvc_dct_config *cfg, size_t n_cfg, uint64_t seed, int range,
+                                 uint64_t first_block, uint64_t n_blocks, hvc_dct_error *results);
+
 /* Device memory helpers so that a binding needs no HIP of its own. */
 HVC_API int hvc_device_alloc(hvc_ctx *ctx, size_t bytes, void **out);
 HVC_API int hvc_device_free(hvc_ctx *ctx, void *p);

@@ -524,6 +524,62 @@ end
 (* int hvc_slot_last_stats(ctx, slot, stats) *)
 let slot_last_stats = foreign "hvc_slot_last_stats" (ctx @-> int @-> ptr Slot_stats.t @-> returning int)
 
+(* The model's parametric fixed-point DCT (Dct.Fixed_point) and jpeg/bin/dct.ml's precision search *)
+let dct_forward = 0
+let dct_inverse = 1
+let dct_round_trip = 2
+
+module Dct_config = struct
+  type t
+
+  let t : t structure typ = structure "hvc_dct_config"
+  let mode = field t "mode" int
+  let fwd_rom_prec = field t "fwd_rom_prec" int
+  let fwd_transpose_prec = field t "fwd_transpose_prec" int
+  let inv_rom_prec = field t "inv_rom_prec" int
+  let inv_transpose_prec = field t "inv_transpose_prec" int
+  let () = seal t
+end
+
+module Dct_error = struct
+  type t
+
+  let t : t structure typ = structure "hvc_dct_error"
+  let max_error = field t "max_error" double
+  let worst_block = field t "worst_block" uint64_t
+  let () = seal t
+end
+
+(* host only: int hvc_dct_rom(rom_prec, rom64); int hvc_dct_matrix(m64); int hvc_dct_blocks(seed, range, first, n, out) *)
+let dct_rom = foreign "hvc_dct_rom" (int @-> ptr int32_t @-> returning int)
+let dct_matrix = foreign "hvc_dct_matrix" (ptr double @-> returning int)
+let dct_blocks = foreign "hvc_dct_blocks" (uint64_t @-> int @-> uint64_t @-> size_t @-> ptr int32_t @-> returning int)
+
+(* int hvc_dct_fixed(ctx, direction, rom_prec, transpose_prec, in, out, n_blocks, where);
+   int hvc_dct_reference(ctx, direction, in, out, n_blocks, where) *)
+let dct_fixed =
+  foreign
+    "hvc_dct_fixed"
+    ~release_runtime_lock:true
+    (ctx @-> int @-> int @-> int @-> ptr int32_t @-> ptr int32_t @-> size_t @-> int @-> returning int)
+;;
+
+let dct_reference =
+  foreign
+    "hvc_dct_reference"
+    ~release_runtime_lock:true
+    (ctx @-> int @-> ptr int32_t @-> ptr double @-> size_t @-> int @-> returning int)
+;;
+
+(* int hvc_dct_error_search(ctx, cfg, n_cfg, seed, range, first_block, n_blocks, results) *)
+let dct_error_search =
+  foreign
+    "hvc_dct_error_search"
+    ~release_runtime_lock:true
+    (ctx @-> ptr Dct_config.t @-> size_t @-> uint64_t @-> int @-> uint64_t @-> uint64_t @-> ptr Dct_error.t
+    @-> returning int)
+;;
+
 (* Plane.t (common/src/plane.ml:4-9) is a Base_bigstring = (char, int8_unsigned_elt, c_layout) Array1:
    its data pointer is passed zero-copy.  (Needs [Plane.plane : t -> Base_bigstring.t] exposed.) *)
 let plane_ptr (p : Hardcaml_video_common.Plane.t) =

@@ -28,6 +28,8 @@ C_TO_ML = {
     "uint8_t*": {"ptr char", "ptr uint8_t", "string"},  # Base_bigstring data / OCaml string for read-only bytes
     "char*": {"string", "ptr char"},  # a read-only C string / a buffer the callee fills
     "int*": {"ptr int"}, "size_t*": {"ptr size_t"}, "float*": {"ptr float"},
+    "int32_t*": {"ptr int32_t"}, "double*": {"ptr double"},
+    "hvc_dct_config*": {"ptr Dct_config.t"}, "hvc_dct_error*": {"ptr Dct_error.t"},
     "void*": {"ptr void"}, "void**": {"ptr (ptr void)"},
     "hvc_component*": {"ptr Component.t"}, "hvc_jpeg_info*": {"ptr Jpeg_info.t"},
     "hvc_batch_stats*": {"ptr Batch_stats.t"}, "hvc_slot_stats*": {"ptr Slot_stats.t"},

@@ -26,6 +26,17 @@ it prints ((block_number n) (max_coef_diff d)), d the largest difference of a qu
 -out writes the file the RTL arithmetic makes of the frame (its records through this library's entropy coder).
 `model encode frame -arithmetic hardcaml` writes that file as well.
 
+    python -m video_coding_amd dct {forward,inverse} [-rom-prec 12] [-transpose-prec 2] [-input-range 200] [-count 1]
+    python -m video_coding_amd dct both [-fwd-rom-prec 12] [-fwd-transpose-prec 2] [-inv-rom-prec 12]
+                                        [-inv-transpose-prec 2] [-count 1]           jpeg/bin/dct.ml:33-174
+    python -m video_coding_amd dct search [-count 10000]
+        every subcommand takes -seed S (default 0); forward, inverse and both take -block I
+
+`dct` is the reference's fixed-point DCT tool (hvc_dct_*): blocks come from the library's counter-based generator
+(hvc_dct_blocks), not OCaml's Random, so block I of seed S is the same block in every run and every configuration.
+-count 1 prints the reference's verbose fields for block 0, -block I for block I; -count N > 1 prints
+((max_error E) (worst_block I) (seed S)) over blocks 0 .. N-1.  `search` prints the reference's lines.
+
 Every pixel goes through libhvc_jpeg.so on the GPU (there is no CPU path); output text matches the
 reference's (`print_s` of an int / a float), so jpeg/test/*.t expectations can be checked verbatim.
 """
@@ -210,7 +221,112 @@ def oyuv_convert(a):
             f.write(out.tobytes())
 
 
-def main(argv=None):
+def _sexp_matrix(m, fmt):
+    return "(%s)" % " ".join("(%s)" % " ".join(fmt(v) for v in row) for row in np.asarray(m).reshape(8, 8))
+
+
+def _float(v):
+    v = float(v)
+    return repr(v) if v != int(v) or abs(v) >= 1e16 else "%d." % int(v)  # OCaml's sexp of a float: round-trips
+
+
+def _ordered_fmul(a, b):
+    """Matrix8x8.fmul (dct.ml:210-218) in float64: each sum from 0.0 in order k = 0..7, products and sums rounded apart"""
+    out = np.zeros((8, 8))
+    for k in range(8):
+        out = out + np.multiply.outer(a[:, k], b[k, :])
+    return out
+
+
+def _dct_print(fields):
+    print("(%s)" % "\n ".join("(%s %s)" % kv for kv in fields))
+
+
+def dct_one(a):
+    ctx = hvc.Context(a.device)
+    try:
+        direction = a.dct_cmd
+        if a.block is not None or a.count == 1:
+            i = a.block or 0
+            x = hvc.dct_blocks(a.seed, a.input_range, i, 1)
+            dct = ctx.dct_fixed(direction, a.rom_prec, a.transpose_prec, x)[0]
+            ref = ctx.dct_reference(direction, x)[0]
+            err = np.abs(dct.astype(np.float64) - ref)
+            _dct_print([("inputs", _sexp_matrix(x[0], str)), ("dct", _sexp_matrix(dct, str)),
+                        ("ref_dct", _sexp_matrix(ref, _float)), ("max_error", _float(err.max())),
+                        ("error", _sexp_matrix(err, _float))])
+        else:
+            cfg = (direction, a.rom_prec, a.transpose_prec, a.rom_prec, a.transpose_prec)
+            e, w = ctx.dct_error_search([cfg], a.seed, a.input_range, 0, a.count)
+            print("((max_error %s) (worst_block %d) (seed %d))" % (_float(e[0]), int(w[0]), a.seed))
+    finally:
+        ctx.close()
+
+
+def dct_both(a):
+    ctx = hvc.Context(a.device)
+    try:
+        if a.block is not None or a.count == 1:
+            i = a.block or 0
+            x = hvc.dct_blocks(a.seed, 128, i, 1)
+            fwd = ctx.dct_fixed("forward", a.fwd_rom_prec, a.fwd_transpose_prec, x)
+            fixed = ctx.dct_fixed("inverse", a.inv_rom_prec, a.inv_transpose_prec, fwd)[0]
+            m = hvc.dct_matrix()
+            ref = _ordered_fmul(_ordered_fmul(m.T, _ordered_fmul(_ordered_fmul(m, x[0].astype(np.float64)), m.T)), m)
+            _dct_print([("inputs", _sexp_matrix(x[0], str)), ("fixed_dct", _sexp_matrix(fixed, str)),
+                        ("ref_dct", _sexp_matrix(ref, _float)),
+                        ("max_ref_error", _float(np.abs(x[0] - ref).max())),
+                        ("max_fixed_error", str(int(np.abs(x[0] - fixed).max())))])
+        else:
+            cfg = ("round_trip", a.fwd_rom_prec, a.fwd_transpose_prec, a.inv_rom_prec, a.inv_transpose_prec)
+            e, w = ctx.dct_error_search([cfg], a.seed, 128, 0, a.count)
+            print("((max_error %d) (worst_block %d) (seed %d))" % (int(e[0]), int(w[0]), a.seed))
+    finally:
+        ctx.close()
+
+
+def dct_search_configs():
+    """the order of jpeg/bin/dct.ml's search: fwd_rom 8..16, fwd_tp 0..5, inv_rom 8..16, inv_tp 0..5"""
+    return [(fr, ft, ir, it) for fr in range(8, 17) for ft in range(6) for ir in range(8, 17) for it in range(6)]
+
+
+def dct_search(a):
+    tuples = dct_search_configs()
+    ctx = hvc.Context(a.device)
+    try:
+        e, _ = ctx.dct_error_search([("round_trip",) + t for t in tuples], a.seed, 128, 0, a.count)
+    finally:
+        ctx.close()
+    for t, v in zip(tuples, e):
+        print("%2i %2i %2i %2i - %i" % (t + (int(v),)))
+
+
+def dct_args(top):
+    dct = top.add_parser("dct", help="the fixed-point DCT against its float reference, and the precision search")
+    sub = dct.add_subparsers(dest="dct_cmd", required=True)
+    for name in ("forward", "inverse"):
+        p = sub.add_parser(name)
+        p.add_argument("-rom-prec", dest="rom_prec", type=int, default=12)
+        p.add_argument("-transpose-prec", dest="transpose_prec", type=int, default=2)
+        p.add_argument("-input-range", dest="input_range", type=int, default=200)
+        p.add_argument("-count", type=int, default=1)
+        p.add_argument("-block", type=int, default=None)
+        p.set_defaults(fn=dct_one)
+    p = sub.add_parser("both")
+    for d in ("fwd", "inv"):
+        p.add_argument("-%s-rom-prec" % d, dest="%s_rom_prec" % d, type=int, default=12)
+        p.add_argument("-%s-transpose-prec" % d, dest="%s_transpose_prec" % d, type=int, default=2)
+    p.add_argument("-count", type=int, default=1)
+    p.add_argument("-block", type=int, default=None)
+    p.set_defaults(fn=dct_both)
+    p = sub.add_parser("search")
+    p.add_argument("-count", type=int, default=10000)
+    p.set_defaults(fn=dct_search)
+    for p in sub.choices.values():
+        p.add_argument("-seed", type=int, default=0)
+
+
+def parser():
     ap = argparse.ArgumentParser(prog="python -m video_coding_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("-device", type=int, default=0)
@@ -271,7 +387,12 @@ def main(argv=None):
     p.add_argument("-out", default=None, help="write the RTL arithmetic's JPEG file")
     p.set_defaults(fn=simulate_encoder)
 
-    a = ap.parse_args(argv)
+    dct_args(top)
+    return ap
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
     a.fn(a)
 
 

@@ -2,8 +2,11 @@
 // device memory, host CPUs) and the block stage -- hvc_decode_frames, hvc_decode_frames_yuv444, hvc_encode_frames and
 // their single-plane forms.  Host-side plumbing only: argument checking, geometry -> kernel parameter blocks, staging
 // for host-memory callers.  The file-level entry points are in hvc_capi_jpeg.hip, hvc_capi_reader.hip, hvc_capi_files.hip;
-// what they share is hvc_ctx.h.
+// what they share is hvc_ctx.h.  At the end: the fixed-point DCT's entry points (hvc_dct_*, kernels in hvc_dct_fixed.hip).
+#include <cmath>
+
 #include "hvc_ctx.h"
+#include "hvc_dct_fixed.h"
 
 bool pin_to_ctx_cpus(const hvc_ctx *c) {
     if (!c->have_cpus) { // a pool thread may still carry an earlier call's restriction
@@ -224,6 +227,9 @@ void hvc_destroy(hvc_ctx *c) {
     if (c->d_div_px) (void)hipFree(c->d_div_px);
     if (c->d_div_in) (void)hipFree(c->d_div_in);
     if (c->d_div_out) (void)hipFree(c->d_div_out);
+    if (c->d_dct_tab) (void)hipFree(c->d_dct_tab);
+    if (c->d_dct_a) (void)hipFree(c->d_dct_a);
+    if (c->d_dct_b) (void)hipFree(c->d_dct_b);
     if (c->d_sums) (void)hipFree(c->d_sums);
     if (c->d_aux) (void)hipFree(c->d_aux);
     if (c->d_aux2) (void)hipFree(c->d_aux2);
@@ -1572,5 +1578,211 @@ int hvc_upsample420(hvc_ctx *c, const uint8_t *src, int cw, int ch, size_t src_s
         HIPCHK(c, hipMemcpy2DAsync(dst + (size_t)p * dst_ps, dst_stride, (uint8_t *)c->d_out + (size_t)p * dst_ps,
                                    dst_stride, (size_t)cw * 2, (size_t)ch * 2, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+// ---------------------------------------------------------------------------
+// The parametric fixed-point DCT and its precision search (include/hvc_jpeg.h, "Fixed-point DCT"): the host-side tables and
+// generator, and the calls that run hvc_dct_fixed.hip's kernels.
+using hvc::DctCfg;
+using hvc::DctTables;
+using hvc::DctWorst;
+
+static_assert(sizeof(hvc_dct_config) == sizeof(DctCfg), "hvc_dct_config is DctCfg");
+
+namespace {
+
+// Floating_point.Eight_point.forward_transform_matrix (dct.ml:242-253), evaluated as OCaml does
+void dct_matrix(double *m) {
+    const double n = 8.;
+    for (int row = 0; row < 8; row++)
+        for (int col = 0; col < 8; col++)
+            m[row * 8 + col] = row == 0 ? 1. / std::sqrt(n)
+                                        : std::sqrt(2. / n) * std::cos(M_PI / n * ((double)col + 0.5) * (double)row);
+}
+
+const DctTables &dct_host_tables() {
+    static DctTables t;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        dct_matrix(t.m);
+        for (int p = 0; p < hvc::DCT_N_ROMS; p++)
+            for (int i = 0; i < 64; i++) t.rom[p][i] = (int32_t)std::round(std::ldexp(t.m[i], p)); // fixed_coefs
+    });
+    return t;
+}
+
+bool prec_ok(int rom, int tp) { return rom >= 0 && rom <= HVC_DCT_ROM_PREC_MAX && tp >= 0 && tp <= HVC_DCT_TP_MAX; }
+
+// the context's copy of the tables (uploaded at its first DCT call) and the word k_dct_fixed flags range errors in
+int dct_tables(hvc_ctx *c, const DctTables **d_tab, unsigned **d_bad) {
+    if (!c->d_dct_tab) {
+        void *p = nullptr;
+        hipError_t e = hipMalloc(&p, sizeof(DctTables) + 256);
+        if (e != hipSuccess) {
+            c->last_hip = (int)e;
+            return HVC_E_OUT_OF_MEMORY;
+        }
+        e = hipMemcpy(p, &dct_host_tables(), sizeof(DctTables), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return fail_hip(c, e);
+        }
+        c->d_dct_tab = p;
+    }
+    *d_tab = (const DctTables *)c->d_dct_tab;
+    if (d_bad) *d_bad = (unsigned *)((char *)c->d_dct_tab + sizeof(DctTables));
+    return HVC_OK;
+}
+
+int check_call(hvc_ctx *c, int direction, const void *in, const void *out, size_t out_align, size_t n_blocks, int where) {
+    if (!c || !in || !out || n_blocks == 0) return HVC_E_INVALID_ARG;
+    if (direction != HVC_DCT_FORWARD && direction != HVC_DCT_INVERSE) return HVC_E_INVALID_ARG;
+    if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
+    if (n_blocks > ((size_t)1 << 31)) return HVC_E_TOO_LARGE;
+    if (where == HVC_MEM_DEVICE && (((uintptr_t)in & 3) || ((uintptr_t)out & (out_align - 1)))) return HVC_E_ALIGNMENT;
+    return HVC_OK;
+}
+
+} // namespace
+
+int hvc_dct_matrix(double *m64) try {
+    if (!m64) return HVC_E_INVALID_ARG;
+    std::memcpy(m64, dct_host_tables().m, sizeof(dct_host_tables().m));
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_dct_rom(int rom_prec, int32_t *rom64) try {
+    if (!rom64) return HVC_E_INVALID_ARG;
+    if (!prec_ok(rom_prec, 0)) return HVC_E_RANGE;
+    std::memcpy(rom64, dct_host_tables().rom[rom_prec], sizeof(dct_host_tables().rom[0]));
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_dct_blocks(uint64_t seed, int range, uint64_t first, size_t n, int32_t *out) try {
+    if (!out) return HVC_E_INVALID_ARG;
+    if (range < 1 || range > HVC_DCT_INV_IN_MAX) return HVC_E_RANGE;
+    for (size_t i = 0; i < n; i++) hvc::dct_block(seed, range, first + i, out + i * 64);
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_dct_fixed(hvc_ctx *c, int direction, int rom_prec, int transpose_prec, const int32_t *in, int32_t *out,
+                  size_t n_blocks, int where) try {
+    int r = check_call(c, direction, in, out, sizeof(int32_t), n_blocks, where);
+    if (r) return r;
+    if (!prec_ok(rom_prec, transpose_prec)) return HVC_E_RANGE;
+    const int lim = direction == HVC_DCT_INVERSE ? HVC_DCT_INV_IN_MAX : HVC_DCT_FWD_IN_MAX;
+    const size_t bytes = n_blocks * 64 * sizeof(int32_t);
+    if (where == HVC_MEM_HOST)
+        for (size_t i = 0; i < n_blocks * 64; i++)
+            if (in[i] < -lim || in[i] > lim) return HVC_E_RANGE;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    const DctTables *tab;
+    unsigned *bad;
+    if ((r = dct_tables(c, &tab, &bad))) return r;
+    const int32_t *d_in = in;
+    int32_t *d_out = out;
+    if (where == HVC_MEM_HOST) {
+        if ((r = grow(c, &c->d_dct_a, &c->dct_a_cap, bytes))) return r;
+        if ((r = grow(c, &c->d_dct_b, &c->dct_b_cap, bytes))) return r;
+        HIPCHK(c, hipMemcpyAsync(c->d_dct_a, in, bytes, hipMemcpyHostToDevice, c->stream));
+        d_in = (const int32_t *)c->d_dct_a;
+        d_out = (int32_t *)c->d_dct_b;
+    }
+    HIPCHK(c, hipMemsetAsync(bad, 0, sizeof(unsigned), c->stream));
+    HIPCHK(c, hvc::launch_dct_fixed(tab, direction == HVC_DCT_INVERSE, rom_prec, transpose_prec, d_in, d_out, n_blocks, bad,
+                                    c->stream));
+    if (where == HVC_MEM_HOST) HIPCHK(c, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    unsigned h_bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return h_bad ? HVC_E_RANGE : HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_dct_reference(hvc_ctx *c, int direction, const int32_t *in, double *out, size_t n_blocks, int where) try {
+    int r = check_call(c, direction, in, out, sizeof(double), n_blocks, where);
+    if (r) return r;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    const DctTables *tab;
+    if ((r = dct_tables(c, &tab, nullptr))) return r;
+    const size_t ibytes = n_blocks * 64 * sizeof(int32_t), obytes = n_blocks * 64 * sizeof(double);
+    const int32_t *d_in = in;
+    double *d_out = out;
+    if (where == HVC_MEM_HOST) {
+        if ((r = grow(c, &c->d_dct_a, &c->dct_a_cap, ibytes))) return r;
+        if ((r = grow(c, &c->d_dct_b, &c->dct_b_cap, obytes))) return r;
+        HIPCHK(c, hipMemcpyAsync(c->d_dct_a, in, ibytes, hipMemcpyHostToDevice, c->stream));
+        d_in = (const int32_t *)c->d_dct_a;
+        d_out = (double *)c->d_dct_b;
+    }
+    HIPCHK(c, hvc::launch_dct_reference(tab, direction == HVC_DCT_INVERSE, d_in, d_out, n_blocks, c->stream));
+    if (where == HVC_MEM_HOST) {
+        HIPCHK(c, hipMemcpyAsync(out, d_out, obytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+// Configurations go to the kernel grouped by mode (one instantiation each); the results come back in the caller's order.
+int hvc_dct_error_search(hvc_ctx *c, const hvc_dct_config *cfg, size_t n_cfg, uint64_t seed, int range,
+                         uint64_t first_block, uint64_t n_blocks, hvc_dct_error *results) try {
+    if (!c || !cfg || !results || n_cfg == 0 || n_blocks == 0) return HVC_E_INVALID_ARG;
+    if (first_block + n_blocks < first_block) return HVC_E_INVALID_ARG; // (the block range wraps)
+    if (n_cfg > (size_t)65535 * hvc::DCT_SEARCH_CFGS) return HVC_E_TOO_LARGE;
+    for (size_t i = 0; i < n_cfg; i++) {
+        const hvc_dct_config &k = cfg[i];
+        if (k.mode != HVC_DCT_FORWARD && k.mode != HVC_DCT_INVERSE && k.mode != HVC_DCT_ROUND_TRIP) return HVC_E_INVALID_ARG;
+        if (k.mode != HVC_DCT_INVERSE && !prec_ok(k.fwd_rom_prec, k.fwd_transpose_prec)) return HVC_E_RANGE;
+        if (k.mode != HVC_DCT_FORWARD && !prec_ok(k.inv_rom_prec, k.inv_transpose_prec)) return HVC_E_RANGE;
+        if (range < 1 || range > (k.mode == HVC_DCT_INVERSE ? HVC_DCT_INV_IN_MAX : HVC_DCT_FWD_IN_MAX)) return HVC_E_RANGE;
+    }
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    const DctTables *tab;
+    int r = dct_tables(c, &tab, nullptr);
+    if (r) return r;
+    std::vector<DctCfg> sorted;
+    std::vector<size_t> order; // sorted[j] is cfg[order[j]]
+    size_t start[4] = {0, 0, 0, 0};
+    for (int m = 0; m < 3; m++) {
+        start[m] = sorted.size();
+        for (size_t i = 0; i < n_cfg; i++)
+            if (cfg[i].mode == m) {
+                DctCfg d;
+                std::memcpy(&d, &cfg[i], sizeof d);
+                sorted.push_back(d);
+                order.push_back(i);
+            }
+    }
+    start[3] = n_cfg;
+    size_t slab = 0;
+    for (int m = 0; m < 3; m++) {
+        const int n = (int)(start[m + 1] - start[m]);
+        if (n) slab = std::max(slab, hvc::dct_search_grid_x(n_blocks, n) * n);
+    }
+    const size_t cfg_bytes = (n_cfg * sizeof(DctCfg) + 255) & ~(size_t)255;
+    const size_t worst_bytes = n_cfg * sizeof(DctWorst);
+    if ((r = grow(c, &c->d_dct_a, &c->dct_a_cap, cfg_bytes + worst_bytes + slab * sizeof(DctWorst)))) return r;
+    DctCfg *d_cfg = (DctCfg *)c->d_dct_a;
+    DctWorst *d_worst = (DctWorst *)((char *)c->d_dct_a + cfg_bytes);
+    DctWorst *d_slab = d_worst + n_cfg;
+    HIPCHK(c, hipMemcpyAsync(d_cfg, sorted.data(), n_cfg * sizeof(DctCfg), hipMemcpyHostToDevice, c->stream));
+    for (int m = 0; m < 3; m++) {
+        const int n = (int)(start[m + 1] - start[m]);
+        if (n)
+            HIPCHK(c, hvc::launch_dct_search(tab, m, d_cfg + start[m], n, seed, range, first_block, n_blocks, d_slab,
+                                             d_worst + start[m], c->stream));
+    }
+    std::vector<DctWorst> worst(n_cfg);
+    HIPCHK(c, hipMemcpyAsync(worst.data(), d_worst, worst_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t j = 0; j < n_cfg; j++) {
+        double e;
+        std::memcpy(&e, &worst[j].key, sizeof e);
+        results[order[j]].max_error = e;
+        results[order[j]].worst_block = worst[j].idx;
+    }
     return HVC_OK;
 } HVC_ABI_CATCH

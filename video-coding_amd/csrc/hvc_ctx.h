@@ -68,6 +68,9 @@ struct hvc_ctx {
     // calls) the input and the divergence bytes
     void *d_div_px = nullptr, *d_div_in = nullptr, *d_div_out = nullptr;
     size_t div_px_cap = 0, div_in_cap = 0, div_out_cap = 0;
+    // hvc_dct_*: the tables (uploaded at the first call) with k_dct_fixed's range flag, and two scratch buffers
+    void *d_dct_tab = nullptr, *d_dct_a = nullptr, *d_dct_b = nullptr;
+    size_t dct_a_cap = 0, dct_b_cap = 0;
     int last_hip = 0;
     // hvc_jpeg_decode_batch: copy stream + ring of pinned host / device coefficient chunks
     static constexpr int RING = 3;

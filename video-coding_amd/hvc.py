@@ -29,6 +29,7 @@ SYMBOLS = [
     "hvc_encode_frames_submit", "hvc_wait", "hvc_slot_query", "hvc_slot_last_stats", "hvc_huffman_code_tables",
     "hvc_set_arithmetic", "hvc_get_arithmetic", "hvc_decode_frames_divergence",
     "hvc_set_encode_arithmetic", "hvc_get_encode_arithmetic", "hvc_encode_frames_divergence",
+    "hvc_dct_rom", "hvc_dct_matrix", "hvc_dct_blocks", "hvc_dct_fixed", "hvc_dct_reference", "hvc_dct_error_search",
 ]
 HVC_ARITH = {"model": 0, "hardcaml": 1}  # enum hvc_arith
 HVC_SLOTS = 4       # enum { HVC_SLOTS }
@@ -162,6 +163,13 @@ def lib():
         L.hvc_set_encode_arithmetic.argtypes = [vp, i]
         L.hvc_get_encode_arithmetic.argtypes = [vp, C.POINTER(i)]
         L.hvc_encode_frames_divergence.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
+        u64 = C.c_uint64
+        L.hvc_dct_rom.argtypes = [i, vp]
+        L.hvc_dct_matrix.argtypes = [vp]
+        L.hvc_dct_blocks.argtypes = [u64, i, u64, sz, vp]
+        L.hvc_dct_fixed.argtypes = [vp, i, i, i, vp, vp, sz, i]
+        L.hvc_dct_reference.argtypes = [vp, i, vp, vp, sz, i]
+        L.hvc_dct_error_search.argtypes = [vp, C.POINTER(DctConfig), sz, u64, i, u64, u64, C.POINTER(DctError)]
         L.hvc_jpeg_get_yuv_frame.argtypes = [ip, vp, vp, sz, C.POINTER(sz)]
         L.hvc_jpeg_get_cropped_planes.argtypes = [ip, vp, vp, sz, C.POINTER(sz)]
         L.hvc_jpeg_entropy_decode2.argtypes = [vp, sz, ip, vp, C.POINTER(i), vp, sz, ip, vp, C.POINTER(i)]
@@ -241,6 +249,54 @@ def _addr(x):
     if hasattr(x, "data_ptr"):
         return x.data_ptr(), (HVC_MEM_DEVICE if x.is_cuda else HVC_MEM_HOST)
     raise TypeError(type(x))
+
+
+HVC_DCT = {"forward": 0, "inverse": 1, "round_trip": 2}   # HVC_DCT_FORWARD / _INVERSE / _ROUND_TRIP
+DCT_ROM_PREC_MAX, DCT_TP_MAX = 16, 8                      # hvc_dct_spec.h
+DCT_FWD_IN_MAX, DCT_INV_IN_MAX = 2048, 32768
+
+
+class DctConfig(C.Structure):
+    _fields_ = [("mode", C.c_int), ("fwd_rom_prec", C.c_int), ("fwd_transpose_prec", C.c_int), ("inv_rom_prec", C.c_int),
+                ("inv_transpose_prec", C.c_int)]
+
+
+class DctError(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("worst_block", C.c_uint64)]
+
+
+def _dct_direction(d):
+    return HVC_DCT[d] if isinstance(d, str) else int(d)
+
+
+def dct_rom(rom_prec):
+    """the forward ROM of rom_prec, round_nearest(M * 2^rom_prec) (hvc_dct_rom) -> int32 [8, 8]"""
+    out = np.zeros((8, 8), dtype=np.int32)
+    _chk(lib().hvc_dct_rom(int(rom_prec), out.ctypes.data), "hvc_dct_rom")
+    return out
+
+
+def dct_matrix():
+    """the float64 forward matrix M, the static x86 one of dct.ml (hvc_dct_matrix) -> float64 [8, 8]"""
+    out = np.zeros((8, 8), dtype=np.float64)
+    _chk(lib().hvc_dct_matrix(out.ctypes.data), "hvc_dct_matrix")
+    return out
+
+
+def dct_blocks(seed, range_, first, n):
+    """the search's generated blocks first .. first + n - 1 (hvc_dct_blocks) -> int32 [n, 8, 8]"""
+    out = np.zeros((n, 8, 8), dtype=np.int32)
+    _chk(lib().hvc_dct_blocks(int(seed), int(range_), int(first), int(n), out.ctypes.data), "hvc_dct_blocks")
+    return out
+
+
+def dct_configs(cfgs):
+    """[(mode, fwd_rom, fwd_tp, inv_rom, inv_tp), ...] (mode a name of HVC_DCT or its number) -> DctConfig array"""
+    arr = (DctConfig * len(cfgs))()
+    for a, c in zip(arr, cfgs):
+        a.mode = _dct_direction(c[0])
+        a.fwd_rom_prec, a.fwd_transpose_prec, a.inv_rom_prec, a.inv_transpose_prec = (int(v) for v in c[1:5])
+    return arr
 
 
 def components(specs):
@@ -543,6 +599,42 @@ class Context:
         _chk(lib().hvc_decode_frames_divergence(self._h, ca, coef_frame_stride, q.ctypes.data, q.shape[0], arr, len(arr),
                                                 n_frames, da, stride, w1), "hvc_decode_frames_divergence")
         return max_diff
+
+    def dct_fixed(self, direction, rom_prec, transpose_prec, blocks, out=None):
+        """Fixed_point.forward_transform / inverse_transform of int32 blocks [n, 8, 8] (hvc_dct_fixed): a numpy array, or a
+        torch device tensor with a device `out`.  direction "forward" | "inverse" (or 0 | 1)."""
+        ia, w1 = _addr(blocks)
+        if out is None:
+            assert w1 == HVC_MEM_HOST, "device blocks: pass a device out"
+            out = np.zeros(np.shape(blocks), dtype=np.int32)
+        oa, w2 = _addr(out)
+        assert w1 == w2
+        n = int(np.prod(tuple(blocks.shape))) // 64
+        _chk(lib().hvc_dct_fixed(self._h, _dct_direction(direction), int(rom_prec), int(transpose_prec), ia, oa, n, w1),
+             "hvc_dct_fixed")
+        return out
+
+    def dct_reference(self, direction, blocks, out=None):
+        """the float64 reference transform of int32 blocks [n, 8, 8] (hvc_dct_reference) -> float64, as dct_fixed"""
+        ia, w1 = _addr(blocks)
+        if out is None:
+            assert w1 == HVC_MEM_HOST, "device blocks: pass a device out"
+            out = np.zeros(np.shape(blocks), dtype=np.float64)
+        oa, w2 = _addr(out)
+        assert w1 == w2
+        n = int(np.prod(tuple(blocks.shape))) // 64
+        _chk(lib().hvc_dct_reference(self._h, _dct_direction(direction), ia, oa, n, w1), "hvc_dct_reference")
+        return out
+
+    def dct_error_search(self, cfgs, seed, range_, first_block, n_blocks):
+        """generated blocks first_block .. + n_blocks through every configuration (hvc_dct_error_search): cfgs as
+        dct_configs takes them -> (max_error float64 [n_cfg], worst_block uint64 [n_cfg])"""
+        arr = cfgs if isinstance(cfgs, C.Array) else dct_configs(cfgs)
+        res = (DctError * len(arr))()
+        _chk(lib().hvc_dct_error_search(self._h, arr, len(arr), int(seed), int(range_), int(first_block), int(n_blocks),
+                                        res), "hvc_dct_error_search")
+        return (np.array([r.max_error for r in res], dtype=np.float64),
+                np.array([r.worst_block for r in res], dtype=np.uint64))
 
     def set_encode_arithmetic(self, arith):
         """"model" (default: the OCaml model's encoder) | "hardcaml" (the reference's RTL encoder DCT and quantiser, bit
