@@ -507,6 +507,50 @@ HVC_API int hvc_jpeg_entropy_encode(const hvc_jpeg_info *info, const int16_t *co
 HVC_API int hvc_jpeg_encode(hvc_ctx *ctx, const uint8_t *y, const uint8_t *u, const uint8_t *v, int width,
                             int height, int chroma, int quality, uint8_t *out, size_t cap, size_t *out_len);
 
+/* ------------------------------------------------------------------------- */
+/* Per-file OPTIMISED Huffman tables (an extension: the model's encoder writes the default Annex K tables only).
+ * An hvc_huff_spec is the body of one DHT: bits[l - 1] codes of length l, then n_vals symbols (HUFFVAL).  Arrays of four
+ * are ordered DC0, DC1, AC0, AC1 (table set 0 = luma, 1 = chroma, as the default files use them).  The header keeps the
+ * default files' layout (SOI, APP0, DQT x 2, SOF0, DHT DC0, DC1, AC0, AC1, SOS); only the DHT bodies change.
+ *
+ * The tables of a file are those of ITU-T T.81 Annex K.2 over its symbol counts (DC categories; (run << 4) | size, ZRL
+ * and EOB for AC, as the scan codes them): the reserved 257th symbol with count 1; c1 the LARGEST index among the
+ * smallest non-zero counts, c2 likewise with c2 != c1; lengths limited to 16 by figure K.3; the reserved code removed
+ * from the longest length; HUFFVAL ordered by the unadjusted code size, then by symbol.  Codes are assigned canonically
+ * (tables.ml:27-45).  A DC category above 11 or an AC size above 10 is HVC_E_RANGE, as with the default tables.
+ *
+ * hvc_set_huffman_tables(ctx, HVC_HUFF_OPTIMISED) makes hvc_jpeg_encode, hvc_jpeg_encode_batch and
+ * hvc_jpeg_encode_batch_gpu write such files; it combines with hvc_set_encode_arithmetic.  HVC_HUFF_DEFAULT (the
+ * default) leaves every byte as before.  Any other value: HVC_E_INVALID_ARG, the setting unchanged. */
+typedef enum { HVC_HUFF_DEFAULT = 0, HVC_HUFF_OPTIMISED = 1 } hvc_huff_tables;
+typedef struct hvc_huff_spec {
+    uint8_t bits[16];
+    uint8_t vals[256];
+    uint16_t n_vals;
+    uint16_t pad;
+} hvc_huff_spec;
+HVC_API int hvc_set_huffman_tables(hvc_ctx *ctx, int which);
+HVC_API int hvc_get_huffman_tables(const hvc_ctx *ctx, int *which);
+/* Annex K.2 over 256 symbol counts (host, no context).  HVC_E_INVALID_ARG when every count is 0, HVC_E_RANGE when they
+ * sum past 2^62. */
+HVC_API int hvc_huffman_spec_from_counts(const uint64_t counts[256], hvc_huff_spec *out);
+/* The four optimal specs of one frame's coefficient record (the geometry of hvc_jpeg_entropy_encode). */
+HVC_API int hvc_huffman_optimal_tables(const hvc_jpeg_info *info, const int16_t *coefs, hvc_huff_spec out[4]);
+/* hvc_jpeg_header with the given DHT bodies. */
+HVC_API int hvc_jpeg_header_tables(const hvc_jpeg_info *info, const hvc_huff_spec specs[4], uint8_t *out, size_t cap,
+                                   size_t *len);
+/* hvc_jpeg_entropy_encode with the given tables: the whole file.  HVC_E_RANGE for a symbol without a code in specs;
+ * HVC_E_INVALID_ARG for a malformed spec (bits that do not sum to n_vals, a Kraft sum above 1, a repeated symbol, a DC
+ * symbol above 11). */
+HVC_API int hvc_jpeg_entropy_encode_tables(const hvc_jpeg_info *info, const hvc_huff_spec specs[4], const int16_t *coefs,
+                                           uint8_t *out, size_t cap, size_t *out_len);
+/* hvc_huffman_encode_frames with each frame's own optimal tables, counted and built on the GPU (k_huff_hist,
+ * k_huff_build, csrc/hvc_huff.hip).  specs is host memory of n_frames x 4 entries and receives each frame's tables; the
+ * segments equal hvc_jpeg_entropy_encode_tables' with them. */
+HVC_API int hvc_huffman_encode_frames_optimised(hvc_ctx *ctx, const hvc_jpeg_info *info, const int16_t *coefs,
+                                                size_t coef_frame_stride, int n_frames, uint8_t *out, size_t out_cap,
+                                                uint64_t *offsets, hvc_huff_spec *specs, int where);
+
 /* The same for a batch of equally sized frames (BASELINE config 5 end to end): frames[f] is one raw
  * planar frame as `model encode frame` reads it (Frame.input, common/src/frame.ml:72-76: the tight Y, U,
  * V planes back to back); jpegs[f] receives the file (capacity caps[f]; its length in sizes[f]), byte-

@@ -618,3 +618,58 @@ let qtab_of_int_array (q : int array) =
   Array.iteri (fun i v -> CArray.set a i (Unsigned.UInt16.of_int v)) q;
   a
 ;;
+
+(* Per-file optimised Huffman tables (an extension: Annex K.2 tables fitted to each file).  A Huff_spec is one DHT body;
+   arrays of four are ordered DC0, DC1, AC0, AC1. *)
+module Huff_spec = struct
+  type t
+
+  let t : t structure typ = structure "hvc_huff_spec"
+  let bits = field t "bits" (array 16 uint8_t)
+  let vals = field t "vals" (array 256 uint8_t)
+  let n_vals = field t "n_vals" uint16_t
+  let pad = field t "pad" uint16_t
+  let () = seal t
+end
+
+(* int hvc_set_huffman_tables(ctx, which);  int hvc_get_huffman_tables(ctx, which): 0 default, 1 optimised *)
+let set_huffman_tables = foreign "hvc_set_huffman_tables" (ctx @-> int @-> returning int)
+let get_huffman_tables = foreign "hvc_get_huffman_tables" (ctx @-> ptr int @-> returning int)
+
+(* int hvc_huffman_spec_from_counts(counts[256], out): ITU-T T.81 Annex K.2 *)
+let huffman_spec_from_counts =
+  foreign "hvc_huffman_spec_from_counts" (ptr uint64_t @-> ptr Huff_spec.t @-> returning int)
+;;
+
+(* int hvc_huffman_optimal_tables(info, coefs, out[4]) *)
+let huffman_optimal_tables =
+  foreign
+    "hvc_huffman_optimal_tables"
+    ~release_runtime_lock:true
+    (ptr Jpeg_info.t @-> ptr int16_t @-> ptr Huff_spec.t @-> returning int)
+;;
+
+(* int hvc_jpeg_header_tables(info, specs[4], out, cap, len) *)
+let jpeg_header_tables =
+  foreign
+    "hvc_jpeg_header_tables"
+    (ptr Jpeg_info.t @-> ptr Huff_spec.t @-> ptr char @-> size_t @-> ptr size_t @-> returning int)
+;;
+
+(* int hvc_jpeg_entropy_encode_tables(info, specs[4], coefs, out, cap, out_len) *)
+let jpeg_entropy_encode_tables =
+  foreign
+    "hvc_jpeg_entropy_encode_tables"
+    ~release_runtime_lock:true
+    (ptr Jpeg_info.t @-> ptr Huff_spec.t @-> ptr int16_t @-> ptr char @-> size_t @-> ptr size_t @-> returning int)
+;;
+
+(* int hvc_huffman_encode_frames_optimised(ctx, info, coefs, coef_frame_stride, n_frames, out, out_cap, offsets, specs,
+                                           where): hvc_huffman_encode_frames with each frame's own tables *)
+let huffman_encode_frames_optimised =
+  foreign
+    "hvc_huffman_encode_frames_optimised"
+    ~release_runtime_lock:true
+    (ctx @-> ptr Jpeg_info.t @-> ptr int16_t @-> size_t @-> int @-> ptr char @-> size_t @-> ptr uint64_t
+    @-> ptr Huff_spec.t @-> int @-> returning int)
+;;

@@ -30,12 +30,13 @@ C_TO_ML = {
     "int*": {"ptr int"}, "size_t*": {"ptr size_t"}, "float*": {"ptr float"},
     "int32_t*": {"ptr int32_t"}, "double*": {"ptr double"},
     "hvc_dct_config*": {"ptr Dct_config.t"}, "hvc_dct_error*": {"ptr Dct_error.t"},
+    "hvc_huff_spec*": {"ptr Huff_spec.t"},
     "void*": {"ptr void"}, "void**": {"ptr (ptr void)"},
     "hvc_component*": {"ptr Component.t"}, "hvc_jpeg_info*": {"ptr Jpeg_info.t"},
     "hvc_batch_stats*": {"ptr Batch_stats.t"}, "hvc_slot_stats*": {"ptr Slot_stats.t"},
     "uint8_t**": {"ptr (ptr char)", "ptr string"},  # const uint8_t *const *: an array of byte strings
 }
-FIELD_TO_ML = {"int": "int", "size_t": "size_t", "uint16_t": "uint16_t", "double": "double", "uint64_t": "uint64_t",
+FIELD_TO_ML = {"int": "int", "size_t": "size_t", "uint16_t": "uint16_t", "uint8_t": "uint8_t", "double": "double", "uint64_t": "uint64_t",
                "hvc_jpeg_component": "Jpeg_component.t", "hvc_component": "Component.t"}
 
 
@@ -56,6 +57,8 @@ def header_functions(text):
         if args.strip() != "void":
             for a in args.split(","):
                 a = a.strip()
+                if re.search(r"\[\d*\]$", a):  # an array parameter (`const uint64_t counts[256]`) is a pointer
+                    a = re.sub(r"\s*(\w+)\s*\[\d*\]$", r" *\1", a)
                 mm = re.match(r"(.*?)(\w+)$", a, flags=re.S)   # type, then the parameter name
                 params.append(norm_ctype(mm.group(1)))
         out[name] = (norm_ctype(ret), params)

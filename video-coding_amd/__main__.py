@@ -78,6 +78,7 @@ def model_encode_frame(a):
     ctx = hvc.Context(a.device)
     try:
         ctx.set_encode_arithmetic(a.arithmetic)
+        ctx.set_huffman_tables(a.huffman)
         jpg = ctx.jpeg_encode(y, u, v, w, h, a.chroma, a.quality)
     finally:
         ctx.close()
@@ -348,6 +349,8 @@ def parser():
     p.add_argument("-chroma", type=int, default=420, choices=[420, 422, 444])
     p.add_argument("-arithmetic", default="model", choices=["model", "hardcaml"],
                    help="hardcaml: the Hardcaml RTL encoder's DCT and quantiser (hvc_set_encode_arithmetic)")
+    p.add_argument("-huffman", default="default", choices=["default", "optimised"],
+                   help="optimised: Huffman tables fitted to the file, Annex K.2 (hvc_set_huffman_tables)")
     p.set_defaults(fn=model_encode_frame)
 
     oyuv = top.add_parser("oyuv").add_subparsers(dest="cmd", required=True)

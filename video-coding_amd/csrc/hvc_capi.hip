@@ -263,6 +263,7 @@ void hvc_destroy(hvc_ctx *c) {
         if (c->ed_seg[i]) (void)hipFree(c->ed_seg[i]);
         if (c->ed_off[i]) (void)hipFree(c->ed_off[i]);
         if (c->eh_off[i]) (void)hipHostFree(c->eh_off[i]);
+        if (c->eh_specs[i]) (void)hipHostFree(c->eh_specs[i]);
     }
     for (int i = 0; i < 4; i++)
         if (c->ev_t[i]) (void)hipEventDestroy(c->ev_t[i]);
@@ -285,6 +286,7 @@ void hvc_destroy(hvc_ctx *c) {
     if (c->d_dcfix) (void)hipFree(c->d_dcfix);
     delete c->gd_tables_host;
     if (c->hd_tables) (void)hipFree(c->hd_tables);
+    if (c->hd_opt) (void)hipFree(c->hd_opt);
     if (c->hd_lens) (void)hipFree(c->hd_lens);
     if (c->hd_meta) (void)hipFree(c->hd_meta);
     if (c->hd_bitbuf) (void)hipFree(c->hd_bitbuf);
@@ -446,6 +448,18 @@ int hvc_set_encode_arithmetic(hvc_ctx *c, int arith) try {
 int hvc_get_encode_arithmetic(const hvc_ctx *c, int *arith) try {
     if (!c || !arith) return HVC_E_INVALID_ARG;
     *arith = c->enc_arith;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_set_huffman_tables(hvc_ctx *c, int which) try {
+    if (!c || (which != HVC_HUFF_DEFAULT && which != HVC_HUFF_OPTIMISED)) return HVC_E_INVALID_ARG;
+    c->huff_tables = which;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_get_huffman_tables(const hvc_ctx *c, int *which) try {
+    if (!c || !which) return HVC_E_INVALID_ARG;
+    *which = c->huff_tables;
     return HVC_OK;
 } HVC_ABI_CATCH
 

@@ -5,13 +5,20 @@
 // ---------------------------------------------------------------------------
 // Encoder back end on the GPU: RLE + Huffman + byte stuffing of coefficient records (hvc_huff.hip)
 
-// the default code tables on the device, once per context (hvc_huff.hip reads them through HuffParams::tables)
+// the default code tables on the device, once per context (hvc_huff.hip reads them through HuffParams::tables).  The
+// context holds them only once the copy has succeeded: a failed upload is tried again by the next call.
 static int upload_enc_tables(hvc_ctx *c) {
     if (c->hd_tables) return HVC_OK;
     uint32_t t[2][16 + 256];
     hvc::default_enc_tables(t);
-    HIPCHK(c, hipMalloc((void **)&c->hd_tables, sizeof t));
-    HIPCHK(c, hipMemcpy(c->hd_tables, t, sizeof t, hipMemcpyHostToDevice));
+    unsigned *d = nullptr;
+    HIPCHK(c, hipMalloc((void **)&d, sizeof t));
+    const hipError_t e = hipMemcpy(d, t, sizeof t, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail_hip(c, e);
+    }
+    c->hd_tables = d;
     return HVC_OK;
 }
 
@@ -35,7 +42,7 @@ int hvc_huffman_code_tables(hvc_ctx *c, int table_set, int where, uint32_t *code
 // Geometry + scratch of one call.  `out` / `offsets` are device pointers (the caller's, or NULL = scratch
 // inside ctx, see huffman_scratch_out).
 int huffman_prepare(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *d_coefs, size_t coef_fs, int n_frames, uint8_t *d_out,
-                    size_t out_cap, unsigned long long *d_offsets, hvc::HuffParams &P) {
+                    size_t out_cap, unsigned long long *d_offsets, hvc::HuffParams &P, bool optimised) {
     int r = hvc_jpeg_encoder_check(info);
     if (r) return r;
     std::memset(&P, 0, sizeof P);
@@ -69,9 +76,19 @@ int huffman_prepare(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *d_coef
     const size_t words = ((size_t)bpf * 216 + 3) / 4 + 2;
     P.bitbuf_words = (words + 15) / 16 * 16;
     P.ff_stride = P.bitbuf_words / 16;
-    if ((r = upload_enc_tables(c))) return r;
-    P.tables = c->hd_tables;
     const size_t nf = (size_t)n_frames;
+    if (optimised) { // per frame: counts, code tables (both HUFF_TABLE_WORDS words), four specs
+        const size_t words = nf * hvc::HUFF_TABLE_WORDS;
+        if ((r = grow(c, &c->hd_opt, &c->hd_opt_cap, 2 * words * sizeof(unsigned) + nf * 4 * sizeof(hvc_huff_spec)))) return r;
+        P.hist = (unsigned *)c->hd_opt;
+        P.opt_tables = P.hist + words;
+        P.specs = (hvc_huff_spec *)(P.opt_tables + words);
+        P.tables = P.opt_tables;
+        P.table_stride = hvc::HUFF_TABLE_WORDS;
+    } else {
+        if ((r = upload_enc_tables(c))) return r;
+        P.tables = c->hd_tables;
+    }
     if ((r = grow(c, &c->hd_lens, &c->hd_lens_cap, nf * bpf * sizeof(unsigned)))) return r;
     if ((r = grow(c, &c->hd_meta, &c->hd_meta_cap, (4 * nf + 2 * (nf + 1) + 4) * sizeof(unsigned) + 64))) return r;
     if ((r = grow(c, &c->hd_bitbuf, &c->hd_bitbuf_cap, nf * P.bitbuf_words * sizeof(unsigned)))) return r;
@@ -102,8 +119,9 @@ int hvc_jpeg_header(const hvc_jpeg_info *info, uint8_t *out, size_t cap, size_t 
     return HVC_OK;
 } HVC_ABI_CATCH
 
-int hvc_huffman_encode_frames(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *coefs, size_t coef_fs, int n_frames,
-                              uint8_t *out, size_t out_cap, uint64_t *offsets, int where) try {
+// specs != nullptr: each frame's own optimal tables, its four specs into specs[4 f .. 4 f + 3] (host memory)
+static int huffman_encode_frames_impl(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *coefs, size_t coef_fs, int n_frames,
+                                      uint8_t *out, size_t out_cap, uint64_t *offsets, hvc_huff_spec *specs, int where) {
     if (!c || !info || !coefs || !out || !offsets || n_frames < 0 || info->n_comp != 3) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     if (n_frames == 0) {
@@ -120,28 +138,45 @@ int hvc_huffman_encode_frames(hvc_ctx *c, const hvc_jpeg_info *info, const int16
     unsigned status = 0;
     if (where == HVC_MEM_DEVICE) {
         if (((uintptr_t)coefs & 15) || ((uintptr_t)offsets & 7)) return HVC_E_ALIGNMENT;
-        if ((r = huffman_prepare(c, info, coefs, coef_fs, n_frames, out, out_cap, (unsigned long long *)offsets, P))) return r;
+        if ((r = huffman_prepare(c, info, coefs, coef_fs, n_frames, out, out_cap, (unsigned long long *)offsets, P, specs != nullptr))) return r;
         HIPCHK(c, hvc::launch_huffman_encode(P, c->stream));
         HIPCHK(c, hipMemcpyAsync(&status, P.status, sizeof status, hipMemcpyDeviceToHost, c->stream));
+        if (specs)
+            HIPCHK(c, hipMemcpyAsync(specs, P.specs, (size_t)n_frames * 4 * sizeof(hvc_huff_spec), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     } else {
         const size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + info->coef_count) * sizeof(int16_t);
         if ((r = grow(c, &c->d_in, &c->in_cap, cbytes))) return r;
         if ((r = grow(c, &c->hd_out, &c->hd_out_cap, out_cap))) return r;
-        if ((r = huffman_prepare(c, info, (const int16_t *)c->d_in, coef_fs, n_frames, (uint8_t *)c->hd_out, out_cap, nullptr, P)))
+        if ((r = huffman_prepare(c, info, (const int16_t *)c->d_in, coef_fs, n_frames, (uint8_t *)c->hd_out, out_cap, nullptr, P,
+                                   specs != nullptr)))
             return r;
         HIPCHK(c, hipMemcpyAsync(c->d_in, coefs, cbytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hvc::launch_huffman_encode(P, c->stream));
         HIPCHK(c, hipMemcpyAsync(&status, P.status, sizeof status, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(offsets, P.out_offsets, (size_t)(n_frames + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
                                  c->stream));
+        if (specs)
+            HIPCHK(c, hipMemcpyAsync(specs, P.specs, (size_t)n_frames * 4 * sizeof(hvc_huff_spec), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (!(status & 7u) && offsets[n_frames] <= out_cap)
             HIPCHK(c, hipMemcpy(out, c->hd_out, (size_t)offsets[n_frames], hipMemcpyDeviceToHost));
     }
-    if (status & 1u) return HVC_E_RANGE;       // a value the default tables have no code for
+    if (status & 1u) return HVC_E_RANGE;       // a value the tables have no code for (DC category > 11, AC size > 10)
     if (status & 6u) return HVC_E_INVALID_ARG; // out_cap too small
     return HVC_OK;
+}
+
+int hvc_huffman_encode_frames(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *coefs, size_t coef_fs, int n_frames,
+                              uint8_t *out, size_t out_cap, uint64_t *offsets, int where) try {
+    return huffman_encode_frames_impl(c, info, coefs, coef_fs, n_frames, out, out_cap, offsets, nullptr, where);
+} HVC_ABI_CATCH
+
+int hvc_huffman_encode_frames_optimised(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *coefs, size_t coef_fs,
+                                        int n_frames, uint8_t *out, size_t out_cap, uint64_t *offsets, hvc_huff_spec *specs,
+                                        int where) try {
+    if (!specs) return HVC_E_INVALID_ARG;
+    return huffman_encode_frames_impl(c, info, coefs, coef_fs, n_frames, out, out_cap, offsets, specs, where);
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------
@@ -185,9 +220,24 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
             if (!c->ev_et[i][k]) HIPCHK(c, hipEventCreate(&c->ev_et[i][k]));
         if (!c->ev_gpu[i]) HIPCHK(c, hipEventCreate(&c->ev_gpu[i]));
     }
-    std::vector<uint8_t> header;
+    std::vector<uint8_t> header_default;
+    const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // each file its own tables (hvc_set_huffman_tables)
+    if (gpu_entropy && opt) { // per slot: the chunk's specs, pinned
+        const size_t spec_bytes = (size_t)C * 4 * sizeof(hvc_huff_spec);
+        if (spec_bytes > c->e_specs_bytes) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            for (int i = 0; i < NB; i++) {
+                if (c->eh_specs[i]) (void)hipHostFree(c->eh_specs[i]);
+                c->eh_specs[i] = nullptr;
+            }
+            c->e_specs_bytes = 0;
+            for (int i = 0; i < NB; i++)
+                if (hipHostMalloc(&c->eh_specs[i], spec_bytes, hipHostMallocDefault) != hipSuccess) return HVC_E_OUT_OF_MEMORY;
+            c->e_specs_bytes = spec_bytes;
+        }
+    }
     if (gpu_entropy) {
-        hvc::jpeg_header_bytes(&info, header);
+        hvc::jpeg_header_bytes(&info, header_default);
         // per slot: packed segments on the device (capacity = the coefficient chunk: 2 bytes per sample, twice the raw
         // frames), and (C + 1) offsets + one status word, on the device and pinned
         const size_t off_bytes = ((size_t)C + 2) * sizeof(unsigned long long);
@@ -276,11 +326,15 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
                     }
                 } else if (!gpu_entropy) {
                     const int16_t *cf = (const int16_t *)c->eh_out[slot] + (size_t)(f - k * C) * info.coef_count;
-                    e = hvc_jpeg_entropy_encode(&info, cf, jpegs[f], caps[f], &sizes[f]);
+                    e = opt ? hvc::entropy_encode_optimised(&info, cf, jpegs[f], caps[f], &sizes[f])
+                            : hvc_jpeg_entropy_encode(&info, cf, jpegs[f], caps[f], &sizes[f]);
                 } else { // header + the frame's segment + EOI (complete_and_write_eoi, encoder.ml:507-510)
                     const unsigned long long *off = (const unsigned long long *)c->eh_off[slot];
                     const int fi = f - k * C;
                     const size_t seg = (size_t)(off[fi + 1] - off[fi]);
+                    std::vector<uint8_t> own; // optimised: the frame's own DHT bodies
+                    if (opt) hvc::jpeg_header_bytes(&info, own, (const hvc_huff_spec *)c->eh_specs[slot] + 4 * fi);
+                    const std::vector<uint8_t> &header = opt ? own : header_default;
                     sizes[f] = header.size() + seg + 2;
                     if (sizes[f] > caps[f]) {
                         e = HVC_E_INVALID_ARG;
@@ -360,7 +414,7 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
             } else {
                 hvc::HuffParams HP;
                 rc = huffman_prepare(c, &info, (const int16_t *)c->ed_out[slot], info.coef_count, cnt,
-                                     (uint8_t *)c->ed_seg[slot], out_bytes, (unsigned long long *)c->ed_off[slot], HP);
+                                     (uint8_t *)c->ed_seg[slot], out_bytes, (unsigned long long *)c->ed_off[slot], HP, opt);
                 if (rc) break;
                 he = hvc::launch_huffman_encode(HP, compute);
                 if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][2], compute);
@@ -370,6 +424,9 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
                                         hipMemcpyDeviceToHost, compute);
                 if (he == hipSuccess)
                     he = hipMemcpyAsync((unsigned long long *)c->eh_off[slot] + C + 1, HP.status, sizeof(unsigned),
+                                        hipMemcpyDeviceToHost, compute);
+                if (he == hipSuccess && opt) // (the context's scratch: copied before the next chunk's coder reuses it)
+                    he = hipMemcpyAsync(c->eh_specs[slot], HP.specs, (size_t)cnt * 4 * sizeof(hvc_huff_spec),
                                         hipMemcpyDeviceToHost, compute);
                 if (he == hipSuccess) he = hipEventRecord(c->ev_gpu[slot], compute);
             }

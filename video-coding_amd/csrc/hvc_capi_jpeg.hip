@@ -197,17 +197,21 @@ int hvc_jpeg_encode(hvc_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_
     c->profiling = prof_saved;
     if (r) return r;
     hvc::HuffParams P;
-    if ((r = huffman_prepare(c, &info, (const int16_t *)c->d_out, info.coef_count, 1, (uint8_t *)c->hd_out, seg_cap, nullptr, P)))
+    const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // the frame's own tables (hvc_set_huffman_tables)
+    if ((r = huffman_prepare(c, &info, (const int16_t *)c->d_out, info.coef_count, 1, (uint8_t *)c->hd_out, seg_cap, nullptr, P,
+                             opt)))
         return r;
     HIPCHK(c, hvc::launch_huffman_encode(P, c->stream));
     unsigned status = 0;
     unsigned long long off[2] = {0, 0};
+    hvc_huff_spec specs[4];
     HIPCHK(c, hipMemcpyAsync(&status, P.status, sizeof status, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(off, P.out_offsets, sizeof off, hipMemcpyDeviceToHost, c->stream));
+    if (opt) HIPCHK(c, hipMemcpyAsync(specs, P.specs, sizeof specs, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (status & 1u) return HVC_E_RANGE;
     if ((status & 6u) || off[1] > seg_cap) return HVC_E_TOO_LARGE;
-    hvc::jpeg_header_bytes(&info, header);
+    hvc::jpeg_header_bytes(&info, header, opt ? specs : nullptr);
     *out_len = header.size() + (size_t)off[1] + 2;
     if (!out || *out_len > cap) return HVC_E_INVALID_ARG;
     std::memcpy(out, header.data(), header.size());

@@ -49,6 +49,7 @@ struct hvc_ctx {
     int decode_kernel = 0; // hvc_set_decode_kernel: 0 packed (default), 1 unpacked int32, 2 int64 for every block, 3 q16
     int arith = HVC_ARITH_MODEL; // hvc_set_arithmetic: the block stage's arithmetic (HARDCAML: k_hardcaml, hvc_hardcaml.hip)
     int enc_arith = HVC_ARITH_MODEL; // hvc_set_encode_arithmetic: the encoder's (HARDCAML: k_hardcaml_encode, hvc_hardcaml.hip)
+    int huff_tables = HVC_HUFF_DEFAULT; // hvc_set_huffman_tables: the files' Huffman tables (OPTIMISED: k_huff_hist / k_huff_build)
     unsigned *d_fix_count = nullptr; // two counters, used alternately (see k_decode_wide); behind them (+ 8 bytes) the 64-bit
                                      // total of the last call's fix-up blocks over all its launches (hvc_last_wide_blocks)
     // [4], [5]: a second pair of counters, for the luma planes of the fused 4:4:4 path when they run through
@@ -86,6 +87,8 @@ struct hvc_ctx {
     hipEvent_t ev_up[RING] = {}, ev_down[RING] = {}, ev_et[RING][3] = {}, ev_gpu[RING] = {};
     void *ed_seg[RING] = {}, *ed_off[RING] = {}, *eh_off[RING] = {}; // hvc_jpeg_encode_batch_gpu: packed segments + offsets
     size_t e_seg_bytes = 0, e_off_bytes = 0;
+    void *eh_specs[RING] = {}; // ... and, with optimised tables, each frame's four specs (pinned)
+    size_t e_specs_bytes = 0;
     // hvc_jpeg_decode_batch_gpu: pinned / device rings of unstuffed segments and their index arrays
     void *gp_h_ecs[RING] = {}, *gp_d_ecs[RING] = {}, *gp_h_meta[RING] = {}, *gp_d_meta[RING] = {};
     void *gp_h_ftabs[RING] = {}, *gp_d_ftabs[RING] = {}; // ... and of per-frame Huffman tables (hvc::HdFrameTabs, PF mode)
@@ -115,6 +118,8 @@ struct hvc_ctx {
     size_t gd_ecs_cap = 0, gd_meta_cap = 0, gd_state_cap = 0, gd_tables_cap = 0, gd_coefs_cap = 0, gd_dcd_cap = 0;
     // GPU Huffman coder (hvc_huffman_encode_frames): tables + scratch, grown on demand
     unsigned *hd_tables = nullptr;
+    void *hd_opt = nullptr; // optimised tables: per-frame counts, code tables and specs (HuffParams hist / opt_tables / specs)
+    size_t hd_opt_cap = 0;
     void *hd_lens = nullptr, *hd_meta = nullptr, *hd_bitbuf = nullptr, *hd_ff = nullptr, *hd_out = nullptr;
     size_t hd_lens_cap = 0, hd_meta_cap = 0, hd_bitbuf_cap = 0, hd_ff_cap = 0, hd_out_cap = 0;
     // The asynchronous seam (hvc_capi_async.hip): one batch in flight per slot.  Uploads run on copy_stream, the block stage
@@ -351,6 +356,6 @@ inline bool is_420_scan(const hvc_jpeg_info &info) { // Y 2x2, Cb / Cr 1x1 (fram
 
 // hvc_capi_files.hip: geometry + scratch + tables of one GPU Huffman coder call (hvc_huff.hip)
 int huffman_prepare(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *d_coefs, size_t coef_fs, int n_frames, uint8_t *d_out,
-                    size_t out_cap, unsigned long long *d_offsets, hvc::HuffParams &P);
+                    size_t out_cap, unsigned long long *d_offsets, hvc::HuffParams &P, bool optimised = false);
 
 #endif

@@ -26,6 +26,7 @@
 
 #include "../../include/hvc_jpeg.h"
 #include "hvc_hdec.h"
+#include "hvc_huff.h"
 #include "hvc_kernels.h"
 #include "hvc_pool.h"
 
@@ -1268,6 +1269,21 @@ inline int bit_size(int v) { // encoder.ml:143
     return a ? 32 - __builtin_clz(a) : 0;
 }
 
+// The four DHT bodies of a file (DC0, DC1, AC0, AC1) as bits / values; specs == nullptr: the default ones.
+struct TableView {
+    const uint8_t *bits[4], *vals[4];
+};
+TableView table_view(const hvc_huff_spec *specs) {
+    if (!specs) return TableView{{K_DC_LUMA_BITS, K_DC_CHROMA_BITS, K_AC_LUMA_BITS, K_AC_CHROMA_BITS},
+                                 {K_DC_VALS, K_DC_VALS, K_AC_LUMA_VALS, K_AC_CHROMA_VALS}};
+    TableView v;
+    for (int t = 0; t < 4; t++) {
+        v.bits[t] = specs[t].bits;
+        v.vals[t] = specs[t].vals;
+    }
+    return v;
+}
+
 void put_marker(std::vector<uint8_t> &o, int code) { o.push_back(0xff); o.push_back((uint8_t)code); }
 void put16(std::vector<uint8_t> &o, int v) { o.push_back((uint8_t)(v >> 8)); o.push_back((uint8_t)v); }
 
@@ -1378,7 +1394,7 @@ void entropy_decode_wide2(const uint8_t *const data[2], const size_t n[2], const
 }
 
 // Encoder.write_headers (encoder.ml:371-418) for `info`: SOI .. SOS, appended to o
-void jpeg_header_bytes(const hvc_jpeg_info *info, std::vector<uint8_t> &o) {
+void jpeg_header_bytes(const hvc_jpeg_info *info, std::vector<uint8_t> &o, const hvc_huff_spec *specs) {
     put_marker(o, 0xd8);
     { // write_app0 "Hardcaml JPEG."
         static const char tag[] = "Hardcaml JPEG.";
@@ -1403,10 +1419,8 @@ void jpeg_header_bytes(const hvc_jpeg_info *info, std::vector<uint8_t> &o) {
         o.push_back((uint8_t)((info->comp[i].hscale << 4) | info->comp[i].vscale));
         o.push_back((uint8_t)info->layout[i].qtab);
     }
-    write_dht(o, 0, 0, K_DC_LUMA_BITS, K_DC_VALS);
-    write_dht(o, 0, 1, K_DC_CHROMA_BITS, K_DC_VALS);
-    write_dht(o, 1, 0, K_AC_LUMA_BITS, K_AC_LUMA_VALS);
-    write_dht(o, 1, 1, K_AC_CHROMA_BITS, K_AC_CHROMA_VALS);
+    const TableView tv = table_view(specs); // DC0, DC1, AC0, AC1
+    for (int t = 0; t < 4; t++) write_dht(o, t >> 1, t & 1, tv.bits[t], tv.vals[t]);
     put_marker(o, 0xda); // write_sos
     put16(o, 2 + 4 + 3 * 2);
     o.push_back(3);
@@ -1695,17 +1709,35 @@ static int prepare_gpu_decode_impl(const uint8_t *jpeg, size_t n, const ::hvc_jp
 }
 } // namespace hvc
 
-extern "C" {
+namespace {
 
-int hvc_jpeg_entropy_encode(const hvc_jpeg_info *info, const int16_t *coefs, uint8_t *out, size_t cap, size_t *out_len) try {
-    if (!info || !coefs || !out_len || info->n_comp != 3) return HVC_E_INVALID_ARG;
-    std::vector<uint8_t> o;
-    o.reserve(info->coef_count / 4 + 1024);
-    hvc::jpeg_header_bytes(info, o);
-    if (hvc_jpeg_encoder_check(info)) return HVC_E_INVALID_ARG;
-    EncTable et[2];
-    build_enc(et[0], K_DC_LUMA_BITS, K_DC_VALS, K_AC_LUMA_BITS, K_AC_LUMA_VALS);
-    build_enc(et[1], K_DC_CHROMA_BITS, K_DC_VALS, K_AC_CHROMA_BITS, K_AC_CHROMA_VALS);
+// A DHT body the coders can use: bits that sum to n_vals, a Kraft sum of at most 1, no repeated symbol, DC symbols <= 11
+bool spec_is_valid(const hvc_huff_spec &s, bool dc) {
+    unsigned total = 0, kraft = 0;
+    for (int l = 0; l < 16; l++) {
+        total += s.bits[l];
+        kraft += (unsigned)s.bits[l] << (15 - l);
+    }
+    if (total != s.n_vals || total > 256 || kraft > (1u << 16)) return false;
+    bool seen[256] = {};
+    for (unsigned k = 0; k < total; k++) {
+        const uint8_t v = s.vals[k];
+        if (seen[v] || (dc && v > 11)) return false;
+        seen[v] = true;
+    }
+    return true;
+}
+bool specs_are_valid(const hvc_huff_spec *specs) {
+    for (int t = 0; t < 4; t++)
+        if (!spec_is_valid(specs[t], t < 2)) return false;
+    return true;
+}
+
+// The scan of encode_seq (encoder.ml:476-505) over one record with the tables et[0 luma, 1 chroma], appended to o.
+// CHECK: the tables may lack a code for a symbol the record holds (optimised / caller's tables): HVC_E_RANGE then.
+// Without it, the default tables have a code for every DC category <= 11 and every AC size <= 10.
+template <bool CHECK>
+int encode_scan(const hvc_jpeg_info *info, const EncTable *et, const int16_t *coefs, std::vector<uint8_t> &o) {
     int dc_pred[3] = {0, 0, 0};
     const hvc_jpeg_component &c0 = info->comp[0];
     const int mbs_wide = c0.decoded_width / (8 * c0.hscale), mbs_high = c0.decoded_height / (8 * c0.vscale);
@@ -1729,6 +1761,7 @@ int hvc_jpeg_entropy_encode(const hvc_jpeg_info *info, const int16_t *coefs, uin
                         dc_pred[i] = q[0];
                         int size = bit_size(diff);
                         if (size > 11) return HVC_E_RANGE; // no code in the default DC tables
+                        if (CHECK && !t.dc[size].len) return HVC_E_RANGE;
                         // code and magnitude bits leave as one field (<= 16 + 11 bits); a negative value's bits are those
                         // of value - 1 (encoder.ml:155-160)
                         bw.put(t.dcf[size].hi | ((unsigned)(diff + (diff >> 31)) & t.dcf[size].mask), t.dcf[size].total);
@@ -1742,14 +1775,19 @@ int hvc_jpeg_entropy_encode(const hvc_jpeg_info *info, const int16_t *coefs, uin
                             nz &= nz - 1;
                             int run = k - prev - 1;
                             prev = k;
+                            if (CHECK && run >= 16 && !t.ac[0xf0].len) return HVC_E_RANGE;
                             while (run >= 16) { bw.put(t.acf[0xf0].hi, t.acf[0xf0].total); run -= 16; }
                             const int v = q[k];
                             size = bit_size(v);
                             if (size > 10) return HVC_E_RANGE; // no code in the default AC tables
+                            if (CHECK && !t.ac[(run << 4) | size].len) return HVC_E_RANGE;
                             const EncField e = t.acf[(run << 4) | size];
                             bw.put(e.hi | ((unsigned)(v + (v >> 31)) & e.mask), e.total);
                         }
-                        if (prev != 63) bw.put(t.acf[0].hi, t.acf[0].total);
+                        if (prev != 63) {
+                            if (CHECK && !t.ac[0].len) return HVC_E_RANGE;
+                            bw.put(t.acf[0].hi, t.acf[0].total);
+                        }
                     }
             }
         if (my + 1 == mbs_high) bw.pad_with_1s();
@@ -1757,11 +1795,179 @@ int hvc_jpeg_entropy_encode(const hvc_jpeg_info *info, const int16_t *coefs, uin
         append_stuffed(o, scratch.data(), (size_t)(bw.cur - scratch.data()));
         bw.cur = scratch.data();
     }
+    return HVC_OK;
+}
+
+// Symbol counts of one record in scan order: cnt[table set][0 DC, 1 AC][symbol].  The same symbols encode_scan codes.
+int count_symbols(const hvc_jpeg_info *info, const int16_t *coefs, uint64_t (*cnt)[2][256]) {
+    std::memset(cnt, 0, sizeof(uint64_t) * 2 * 2 * 256);
+    int dc_pred[3] = {0, 0, 0};
+    const hvc_jpeg_component &c0 = info->comp[0];
+    const int mbs_wide = c0.decoded_width / (8 * c0.hscale), mbs_high = c0.decoded_height / (8 * c0.vscale);
+    for (int my = 0; my < mbs_high; my++)
+        for (int mx = 0; mx < mbs_wide; mx++)
+            for (int i = 0; i < 3; i++) {
+                const hvc_jpeg_component &c = info->comp[i];
+                const hvc_component &L = info->layout[i];
+                uint64_t *dc = cnt[c.dc_table][0], *ac = cnt[c.dc_table][1];
+                for (int sy = 0; sy < c.vscale; sy++)
+                    for (int sx = 0; sx < c.hscale; sx++) {
+                        const int bx = mx * c.hscale + sx, by = my * c.vscale + sy;
+                        const int16_t *q = coefs + L.coef_offset + ((size_t)by * L.blocks_w + bx) * 64;
+                        const int diff = q[0] - dc_pred[i];
+                        dc_pred[i] = q[0];
+                        const int size = bit_size(diff);
+                        if (size > 11) return HVC_E_RANGE;
+                        dc[size]++;
+                        uint64_t nz = nonzero_mask(q) & ~1ull;
+                        int prev = 0;
+                        while (nz) {
+                            const int k = __builtin_ctzll(nz);
+                            nz &= nz - 1;
+                            const int run = k - prev - 1;
+                            prev = k;
+                            ac[0xf0] += (unsigned)run >> 4;
+                            const int s = bit_size(q[k]);
+                            if (s > 10) return HVC_E_RANGE;
+                            ac[((run & 15) << 4) | s]++;
+                        }
+                        if (prev != 63) ac[0]++;
+                    }
+            }
+    return HVC_OK;
+}
+
+// ITU-T T.81 Annex K.2, figures K.1 (code sizes), K.2 (BITS), K.3 (limit to 16 bits) and K.4 (HUFFVAL), with the
+// reserved 257th symbol of count 1 (tools/jpeg_opt_writer.py _optimal_lengths restates the same procedure)
+int spec_from_counts(const uint64_t *counts, hvc_huff_spec &out) {
+    uint64_t f[257], total = 0;
+    for (int i = 0; i < 256; i++) {
+        if (counts[i] > (1ull << 62) - total) return HVC_E_RANGE;
+        total += counts[i];
+        f[i] = counts[i];
+    }
+    if (!total) return HVC_E_INVALID_ARG;
+    f[256] = 1;
+    int codesize[257] = {}, others[257];
+    for (int i = 0; i < 257; i++) others[i] = -1;
+    for (;;) {
+        // c1: the largest index among the smallest non-zero counts; c2: the same with c2 != c1
+        int c1 = -1, c2 = -1;
+        uint64_t v = ~0ull;
+        for (int i = 0; i < 257; i++)
+            if (f[i] && f[i] <= v) v = f[i], c1 = i;
+        v = ~0ull;
+        for (int i = 0; i < 257; i++)
+            if (f[i] && f[i] <= v && i != c1) v = f[i], c2 = i;
+        if (c2 < 0) break;
+        f[c1] += f[c2];
+        f[c2] = 0;
+        codesize[c1]++;
+        while (others[c1] >= 0) c1 = others[c1], codesize[c1]++;
+        others[c1] = c2;
+        codesize[c2]++;
+        while (others[c2] >= 0) c2 = others[c2], codesize[c2]++;
+    }
+    int bits[260] = {}, maxlen = 0;
+    for (int i = 0; i < 257; i++)
+        if (codesize[i]) {
+            bits[codesize[i]]++;
+            if (codesize[i] > maxlen) maxlen = codesize[i];
+        }
+    for (int i = maxlen; i > 16; i--)
+        while (bits[i] > 0) {
+            int j = i - 2;
+            while (bits[j] == 0) j--;
+            bits[i] -= 2;
+            bits[i - 1]++;
+            bits[j + 1] += 2;
+            bits[j]--;
+        }
+    int i = 16;
+    while (bits[i] == 0) i--;
+    bits[i]--; // the reserved symbol's code
+    std::memset(&out, 0, sizeof out);
+    for (int l = 1; l <= 16; l++) out.bits[l - 1] = (uint8_t)bits[l];
+    int k = 0;
+    for (int l = 1; l <= maxlen; l++) // by the unadjusted code size, then by symbol
+        for (int j = 0; j < 256; j++)
+            if (codesize[j] == l) out.vals[k++] = (uint8_t)j;
+    out.n_vals = (uint16_t)k;
+    return HVC_OK;
+}
+
+} // namespace
+
+namespace hvc {
+// the file's four optimal specs (DC0, DC1, AC0, AC1)
+int optimal_specs(const hvc_jpeg_info *info, const int16_t *coefs, hvc_huff_spec *out) {
+    uint64_t cnt[2][2][256];
+    int r = count_symbols(info, coefs, cnt);
+    for (int t = 0; t < 4 && r == HVC_OK; t++) r = spec_from_counts(cnt[t & 1][t >> 1], out[t]);
+    return r;
+}
+
+// SOI .. SOS + entropy-coded segment + EOI of one record; specs == nullptr: the default tables
+int entropy_encode_file(const hvc_jpeg_info *info, const hvc_huff_spec *specs, const int16_t *coefs, uint8_t *out, size_t cap,
+                        size_t *out_len) {
+    std::vector<uint8_t> o;
+    o.reserve(info->coef_count / 4 + 1024);
+    jpeg_header_bytes(info, o, specs);
+    if (hvc_jpeg_encoder_check(info)) return HVC_E_INVALID_ARG;
+    const TableView tv = table_view(specs);
+    EncTable et[2];
+    build_enc(et[0], tv.bits[0], tv.vals[0], tv.bits[2], tv.vals[2]);
+    build_enc(et[1], tv.bits[1], tv.vals[1], tv.bits[3], tv.vals[3]);
+    const int r = specs ? encode_scan<true>(info, et, coefs, o) : encode_scan<false>(info, et, coefs, o);
+    if (r) return r;
     put_marker(o, 0xd9);
     *out_len = o.size();
     if (!out || o.size() > cap) return HVC_E_INVALID_ARG;
     std::memcpy(out, o.data(), o.size());
     return HVC_OK;
+}
+
+// the file with its own optimal tables (hvc_set_huffman_tables(HVC_HUFF_OPTIMISED) on the host coder)
+int entropy_encode_optimised(const hvc_jpeg_info *info, const int16_t *coefs, uint8_t *out, size_t cap, size_t *out_len) {
+    if (hvc_jpeg_encoder_check(info)) return HVC_E_INVALID_ARG;
+    hvc_huff_spec specs[4];
+    const int r = optimal_specs(info, coefs, specs);
+    return r ? r : entropy_encode_file(info, specs, coefs, out, cap, out_len);
+}
+} // namespace hvc
+
+extern "C" {
+
+int hvc_jpeg_entropy_encode(const hvc_jpeg_info *info, const int16_t *coefs, uint8_t *out, size_t cap, size_t *out_len) try {
+    if (!info || !coefs || !out_len || info->n_comp != 3) return HVC_E_INVALID_ARG;
+    return hvc::entropy_encode_file(info, nullptr, coefs, out, cap, out_len);
+} HVC_ABI_CATCH
+
+int hvc_huffman_spec_from_counts(const uint64_t counts[256], hvc_huff_spec *out) try {
+    if (!counts || !out) return HVC_E_INVALID_ARG;
+    return spec_from_counts(counts, *out);
+} HVC_ABI_CATCH
+
+int hvc_huffman_optimal_tables(const hvc_jpeg_info *info, const int16_t *coefs, hvc_huff_spec out[4]) try {
+    if (!info || !coefs || !out || info->n_comp != 3) return HVC_E_INVALID_ARG;
+    if (hvc_jpeg_encoder_check(info)) return HVC_E_INVALID_ARG;
+    return hvc::optimal_specs(info, coefs, out);
+} HVC_ABI_CATCH
+
+int hvc_jpeg_header_tables(const hvc_jpeg_info *info, const hvc_huff_spec specs[4], uint8_t *out, size_t cap, size_t *len) try {
+    if (!info || !specs || !len || info->n_comp != 3 || !specs_are_valid(specs)) return HVC_E_INVALID_ARG;
+    std::vector<uint8_t> o;
+    hvc::jpeg_header_bytes(info, o, specs);
+    *len = o.size();
+    if (!out || cap < o.size()) return HVC_E_INVALID_ARG;
+    std::memcpy(out, o.data(), o.size());
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_jpeg_entropy_encode_tables(const hvc_jpeg_info *info, const hvc_huff_spec specs[4], const int16_t *coefs, uint8_t *out,
+                                   size_t cap, size_t *out_len) try {
+    if (!info || !specs || !coefs || !out_len || info->n_comp != 3 || !specs_are_valid(specs)) return HVC_E_INVALID_ARG;
+    return hvc::entropy_encode_file(info, specs, coefs, out, cap, out_len);
 } HVC_ABI_CATCH
 
 // Ocompare.max_difference / total_difference / square_error (tools/src/ocompare.ml:6-47) of two

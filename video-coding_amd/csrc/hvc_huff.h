@@ -8,6 +8,8 @@
 
 #include <vector>
 
+#include "../../include/hvc_jpeg.h"
+
 namespace hvc {
 
 struct HuffComp {
@@ -26,7 +28,12 @@ struct HuffParams {
     int mbs_wide, mbs_high, blocks_per_mcu;
     unsigned blocks_per_frame;   // coded blocks = mbs_wide * mbs_high * blocks_per_mcu
     HuffComp comp[3];
-    const unsigned *tables;      // device: [2][16 dc + 256 ac], (code << 5) | length
+    const unsigned *tables;      // device: [2][16 dc + 256 ac], (code << 5) | length; frame f's at tables + f * table_stride
+    size_t table_stride;         // 0: one pair for every frame (the default tables); HUFF_TABLE_WORDS: per frame (optimised)
+    // optimised tables (hist != nullptr): k_huff_hist counts into hist, k_huff_build writes opt_tables (== tables) and specs
+    unsigned *hist;              // [n_frames][2][16 dc + 256 ac] symbol counts
+    unsigned *opt_tables;        // [n_frames][2][16 + 256]
+    hvc_huff_spec *specs;        // [n_frames][4]: DC0, DC1, AC0, AC1
     unsigned *lens;              // [n_frames][blocks_per_frame]: bit lengths in scan order, then offsets
     unsigned *frame_bits, *frame_bytes, *frame_pieces, *frame_ff;   // [n_frames]
     unsigned *bitbuf;            // [n_frames][bitbuf_words]: unstuffed segments, big-endian bit order
@@ -39,16 +46,19 @@ struct HuffParams {
     unsigned *status;            // bit 0: value without a code (HVC_E_RANGE); bit 2: out too small
 };
 
+constexpr size_t HUFF_TABLE_WORDS = 2 * (16 + 256); // one frame's two table sets
+
+// P.hist != nullptr: the frames' own tables first (k_huff_hist, k_huff_build), then the coder's passes with them
 hipError_t launch_huffman_encode(const HuffParams &P, hipStream_t s);
 
 // hvc_entropy.cpp
 void default_enc_tables(uint32_t (*out)[16 + 256]);
-
-} // namespace hvc
-
-struct hvc_jpeg_info;
-namespace hvc {
-void jpeg_header_bytes(const ::hvc_jpeg_info *info, std::vector<uint8_t> &o);
+int optimal_specs(const ::hvc_jpeg_info *info, const int16_t *coefs, hvc_huff_spec *out);
+int entropy_encode_file(const ::hvc_jpeg_info *info, const hvc_huff_spec *specs, const int16_t *coefs, uint8_t *out, size_t cap,
+                        size_t *out_len);
+int entropy_encode_optimised(const ::hvc_jpeg_info *info, const int16_t *coefs, uint8_t *out, size_t cap, size_t *out_len);
+// specs: the four DHT bodies (DC0, DC1, AC0, AC1), nullptr = the default tables
+void jpeg_header_bytes(const ::hvc_jpeg_info *info, std::vector<uint8_t> &o, const hvc_huff_spec *specs = nullptr);
 
 }
 #endif

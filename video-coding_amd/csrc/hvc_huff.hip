@@ -12,7 +12,12 @@
 //   4  k_ff_count / k_scan_u32 / k_frame_offsets / k_stuff_write: 0xFF -> 0xFF 0x00 and packing of the
 //                     frames' segments back to back
 // The bytes equal hvc_jpeg_entropy_encode's scan data (tests/test_gpu_huffman.py), hence the model's.
-// Default (Annex K) tables only, as Encoder.Parameters.c420/c422/c444 use (encoder.ml:306-349).
+// The default (Annex K) tables, as Encoder.Parameters.c420/c422/c444 use (encoder.ml:306-349), are one pair for every
+// frame.  With per-frame optimised tables (hvc_huffman_encode_frames_optimised, hvc_set_huffman_tables) two passes run
+// first, over the same walk:
+//   0a k_huff_hist    symbol counts per frame and table set (LDS bins per workgroup, one flush of the non-zero bins)
+//   0b k_huff_build   one wavefront per (frame, table): ITU-T T.81 Annex K.2 -> code table + DHT body per frame
+// and passes 1 and 3 read frame f's tables at tables + f * table_stride.
 #include <vector>
 
 #include "hvc_huff.h"
@@ -22,6 +27,7 @@ namespace hvc {
 namespace {
 
 constexpr int HT = 256; // blocks (lanes) per workgroup, one component plane tile like K1 / K3
+constexpr int HIST_GROUPS = 2048; // k_huff_hist: workgroups per launch to aim at (each walks several tiles of its frame)
 
 struct BlockPos {
     int comp, bx, by;
@@ -65,19 +71,19 @@ __device__ __forceinline__ BlockPos locate_block(const HuffParams &P, int frame,
     return r;
 }
 
-// The walk over one block, shared by the length and the emit pass.  SINK::put(code, len).
+// The walk over one block, shared by the histogram, the length and the emit pass.  It hands the sink every symbol as
+// SINK::sym(slot, magnitude, size): slot = the symbol's entry of a table set (DC category, or 16 + ((run << 4) | size) for
+// AC, 16 + 0xf0 ZRL, 16 EOB), magnitude = its size low bits (encoder.ml:155-160).
 template <class SINK>
-__device__ __forceinline__ void walk_block(const unsigned (&w)[32], int pred, const unsigned *tab /* LDS: 16 dc + 256 ac */,
-                                           SINK &sink, unsigned &err) {
+__device__ __forceinline__ void walk_block(const unsigned (&w)[32], int pred, SINK &sink, unsigned &err) {
     const int dc = (int)(short)(w[0] & 0xffffu);
     const int diff = dc - pred;
     {
         const unsigned a = (unsigned)(diff < 0 ? -diff : diff);
         const int size = a ? 32 - __clz((int)a) : 0;
         if (size > 11) err = 1; // no code in the default DC tables (the host coder returns HVC_E_RANGE)
-        const unsigned e = tab[size & 15];
         const unsigned mag = (unsigned)(diff >= 0 ? diff : diff - 1) & ((1u << size) - 1u);
-        sink.put(((e >> 5) << size) | mag, (int)(e & 31u) + size);
+        sink.sym(size & 15, mag, size);
     }
     int run = 0;
 #pragma unroll
@@ -87,34 +93,32 @@ __device__ __forceinline__ void walk_block(const unsigned (&w)[32], int pred, co
             run++;
         } else {
             while (run >= 16) { // ZRL (encoder.ml:162-187)
-                const unsigned z = tab[16 + 0xf0];
-                sink.put(z >> 5, (int)(z & 31u));
+                sink.sym(16 + 0xf0, 0u, 0);
                 run -= 16;
             }
             const unsigned a = (unsigned)(v < 0 ? -v : v);
             const int size = 32 - __clz((int)a);
             if (size > 10) err = 1; // no code in the default AC tables
-            const unsigned e = tab[16 + ((run << 4) | (size & 15))];
             const unsigned mag = (unsigned)(v >= 0 ? v : v - 1) & ((1u << size) - 1u);
-            sink.put(((e >> 5) << size) | mag, (int)(e & 31u) + size);
+            sink.sym(16 + ((run << 4) | (size & 15)), mag, size);
             run = 0;
         }
     }
-    if (run) { // EOB
-        const unsigned z = tab[16];
-        sink.put(z >> 5, (int)(z & 31u));
-    }
+    if (run) sink.sym(16, 0u, 0); // EOB
 }
 
+// the length and the emit pass look their codes up in LDS: (code << 5) | length
 struct LenSink {
+    const unsigned *tab; // LDS: 16 dc + 256 ac
     unsigned bits = 0;
-    __device__ __forceinline__ void put(unsigned, int len) { bits += (unsigned)len; }
+    __device__ __forceinline__ void sym(int slot, unsigned, int size) { bits += (tab[slot] & 31u) + (unsigned)size; }
 };
 
 // Writes a bit string at an arbitrary bit offset of a zero-initialised big-endian bit buffer.  The
 // first and the last word of the string may be shared with the neighbouring blocks: atomicOr; the
 // words in between belong to this block alone: plain stores.
 struct EmitSink {
+    const unsigned *tab;     // LDS: 16 dc + 256 ac
     unsigned *wp;            // next 32-bit word of the frame's buffer
     unsigned long long acc;  // pending bits, right-aligned
     int n;                   // number of pending bits (including the `lead` bits of the first word)
@@ -124,6 +128,10 @@ struct EmitSink {
         acc = 0;
         n = (int)(bitpos & 31u); // the leading bits of the first word are somebody else's: zeros here
         first = n != 0;
+    }
+    __device__ __forceinline__ void sym(int slot, unsigned mag, int size) {
+        const unsigned e = tab[slot];
+        put(((e >> 5) << size) | mag, (int)(e & 31u) + size);
     }
     __device__ __forceinline__ void put(unsigned code, int len) { // len <= 27
         acc = (acc << len) | code;
@@ -145,21 +153,26 @@ struct EmitSink {
     }
 };
 
-__device__ __forceinline__ void load_tables(const HuffParams &P, unsigned *lds) {
-    for (int i = threadIdx.x; i < 2 * 272; i += HT) lds[i] = P.tables[i]; // both table sets
+// the histogram pass counts symbols into the workgroup's LDS bins of the block's table set; EOB (at most one per block,
+// the symbol every block shares) is left to a wave ballot
+struct HistSink {
+    unsigned *bins; // LDS: 16 dc + 256 ac
+    bool eob = false;
+    __device__ __forceinline__ void sym(int slot, unsigned, int) {
+        if (slot == 16)
+            eob = true;
+        else
+            atomicAdd(bins + slot, 1u);
+    }
+};
+
+__device__ __forceinline__ void load_tables(const HuffParams &P, int frame, unsigned *lds) {
+    const unsigned *t = P.tables + (size_t)frame * P.table_stride; // table_stride 0: the default tables of every frame
+    for (int i = threadIdx.x; i < 2 * 272; i += HT) lds[i] = t[i]; // both table sets
 }
 
-} // namespace
-
-// pass 1 ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(HT) void k_huff_len(HuffParams P) {
-    __shared__ unsigned tabs[2 * 272];
-    load_tables(P, tabs);
-    __syncthreads();
-    const int lane = threadIdx.x, frame = blockIdx.y;
-    const BlockPos b = locate_block(P, frame, blockIdx.x, lane);
+__device__ __forceinline__ void load_block(const HuffParams &P, const BlockPos &b, unsigned (&w)[32]) {
     const uint4 *src = reinterpret_cast<const uint4 *>(P.coefs + b.coef_idx);
-    unsigned w[32];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         const uint4 t = src[j];
@@ -168,10 +181,24 @@ __global__ __launch_bounds__(HT) void k_huff_len(HuffParams P) {
         w[4 * j + 2] = t.z;
         w[4 * j + 3] = t.w;
     }
+}
+
+} // namespace
+
+// pass 1 ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(HT) void k_huff_len(HuffParams P) {
+    __shared__ unsigned tabs[2 * 272];
+    const int lane = threadIdx.x, frame = blockIdx.y;
+    load_tables(P, frame, tabs);
+    __syncthreads();
+    const BlockPos b = locate_block(P, frame, blockIdx.x, lane);
+    unsigned w[32];
+    load_block(P, b, w);
     const int pred = b.has_pred ? (int)P.coefs[b.pred_idx] : 0;
     LenSink s;
+    s.tab = tabs + 272 * P.comp[b.comp].table;
     unsigned err = 0;
-    walk_block(w, pred, tabs + 272 * P.comp[b.comp].table, s, err);
+    walk_block(w, pred, s, err);
     if (b.active) {
         P.lens[(size_t)frame * P.blocks_per_frame + b.scan] = s.bits;
         if (err) atomicOr(P.status, 1u);
@@ -181,29 +208,22 @@ __global__ __launch_bounds__(HT) void k_huff_len(HuffParams P) {
 // pass 3 ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(HT) void k_huff_emit(HuffParams P) {
     __shared__ unsigned tabs[2 * 272];
-    load_tables(P, tabs);
-    __syncthreads();
     const int lane = threadIdx.x, frame = blockIdx.y;
+    load_tables(P, frame, tabs);
+    __syncthreads();
     const BlockPos b = locate_block(P, frame, blockIdx.x, lane);
     if (!b.active) return;
     if ((size_t)((P.frame_bits[frame] + 31u) >> 5) + 1 > P.bitbuf_words) return; // flagged by k_frame_sizes
-    const uint4 *src = reinterpret_cast<const uint4 *>(P.coefs + b.coef_idx);
     unsigned w[32];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const uint4 t = src[j];
-        w[4 * j + 0] = t.x;
-        w[4 * j + 1] = t.y;
-        w[4 * j + 2] = t.z;
-        w[4 * j + 3] = t.w;
-    }
+    load_block(P, b, w);
     const int pred = b.has_pred ? (int)P.coefs[b.pred_idx] : 0;
     const size_t li = (size_t)frame * P.blocks_per_frame + b.scan;
     const unsigned bitpos = P.lens[li]; // exclusive offset after pass 2
     EmitSink s;
+    s.tab = tabs + 272 * P.comp[b.comp].table;
     s.init(P.bitbuf + (size_t)frame * P.bitbuf_words, bitpos);
     unsigned err = 0;
-    walk_block(w, pred, tabs + 272 * P.comp[b.comp].table, s, err);
+    walk_block(w, pred, s, err);
     if (b.scan == P.blocks_per_frame - 1) {
         // Bitstream_writer.flush_with_1s (bitstream_writer.ml:45-49): pad the last byte with ones
         const unsigned total = P.frame_bits[frame];
@@ -211,6 +231,172 @@ __global__ __launch_bounds__(HT) void k_huff_emit(HuffParams P) {
         if (pad) s.put((1u << pad) - 1u, pad);
     }
     s.finish();
+}
+
+// optimised tables, pass 0a: symbol counts per frame and table set.  A workgroup walks every gridDim.x-th tile of its frame
+// and counts into LDS bins; at the end it adds its non-zero bins to the frame's counters (zeroed by hipMemsetAsync).
+__global__ __launch_bounds__(HT) void k_huff_hist(HuffParams P) {
+    __shared__ unsigned bins[2 * 272];
+    const int lane = threadIdx.x, frame = blockIdx.y;
+    for (int i = lane; i < 2 * 272; i += HT) bins[i] = 0;
+    __syncthreads();
+    for (int tile = blockIdx.x; tile < P.tiles_per_frame; tile += gridDim.x) {
+        const BlockPos b = locate_block(P, frame, tile, lane);
+        HistSink s;
+        s.bins = bins + 272 * P.comp[b.comp].table; // (one component per tile: the same for the whole workgroup)
+        if (b.active) {
+            unsigned w[32];
+            load_block(P, b, w);
+            const int pred = b.has_pred ? (int)P.coefs[b.pred_idx] : 0;
+            unsigned err = 0; // (k_huff_len reports it)
+            walk_block(w, pred, s, err);
+        }
+        const unsigned long long eob = __ballot(s.eob);
+        if ((lane & 63) == 0 && eob) atomicAdd(s.bins + 16, (unsigned)__popcll(eob));
+    }
+    __syncthreads();
+    unsigned *h = P.hist + (size_t)frame * HUFF_TABLE_WORDS;
+    for (int i = lane; i < 2 * 272; i += HT)
+        if (bins[i]) atomicAdd(h + i, bins[i]);
+}
+
+namespace {
+// the two smallest keys of the wave, (lo, hi) per lane -> every lane
+__device__ __forceinline__ void wave_min2(unsigned long long &lo, unsigned long long &hi) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned long long ol = __shfl_xor(lo, o), oh = __shfl_xor(hi, o);
+        const unsigned long long nl = lo < ol ? lo : ol, mx = lo < ol ? ol : lo;
+        const unsigned long long m2 = hi < oh ? hi : oh;
+        hi = mx < m2 ? mx : m2;
+        lo = nl;
+    }
+}
+} // namespace
+
+// optimised tables, pass 0b: one wavefront per (frame, table), table = blockIdx.x: 0 DC0, 1 DC1, 2 AC0, 3 AC1.
+// ITU-T T.81 Annex K.2 as hvc_huffman_spec_from_counts computes it.  Lane l holds symbols l, l + 64, ... l + 256 (256 = the
+// reserved symbol, count 1).  Merge step: the smallest key (count << 9) | (511 - index) is c1 (the largest index among the
+// smallest counts), the next smallest c2.  Code sizes: a symbol is labelled with the root of its subtree, the one symbol
+// of it whose count is non-zero; every member of both groups gets + 1 and c2's group becomes c1's -- what K.2's `others`
+// chains do, without walking them.  Then figure K.3 on lane 0, HUFFVAL by (unadjusted size, symbol), canonical codes.
+// Counts fit in 32 bits: huffman_prepare bounds a frame at 2^32 bits, and every symbol takes at least one.
+__global__ __launch_bounds__(64) void k_huff_build(HuffParams P) {
+    __shared__ unsigned cs_s[260];   // unadjusted code sizes (257 used)
+    __shared__ int bits[64], maxlen_s, cum[18];
+    __shared__ unsigned firstcode[18];
+    __shared__ unsigned spec_w[sizeof(hvc_huff_spec) / 4];
+    const int lane = threadIdx.x, t = blockIdx.x, frame = blockIdx.y;
+    const int set = t & 1, ac = t >> 1, nsym = ac ? 256 : 16;
+    const unsigned *h = P.hist + (size_t)frame * HUFF_TABLE_WORDS + 272 * set + (ac ? 16 : 0);
+    unsigned f[5], lab[5], cs[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        const int i = lane + 64 * k;
+        f[k] = i < nsym ? h[i] : (i == 256 ? 1u : 0u);
+        lab[k] = (unsigned)i;
+        cs[k] = 0;
+    }
+    for (;;) {
+        unsigned long long lo = ~0ull, hi = ~0ull;
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            const unsigned long long key = f[k] ? ((unsigned long long)f[k] << 9) | (unsigned)(511 - (lane + 64 * k)) : ~0ull;
+            if (key < lo) {
+                hi = lo;
+                lo = key;
+            } else if (key < hi) {
+                hi = key;
+            }
+        }
+        wave_min2(lo, hi);
+        if (hi == ~0ull) break; // one tree left
+        const unsigned c1 = 511u - (unsigned)(lo & 511u), c2 = 511u - (unsigned)(hi & 511u);
+        const unsigned f2 = (unsigned)(hi >> 9);
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            const unsigned i = (unsigned)(lane + 64 * k);
+            if (lab[k] == c1 || lab[k] == c2) {
+                cs[k]++;
+                lab[k] = c1;
+            }
+            if (i == c1) f[k] += f2;
+            if (i == c2) f[k] = 0;
+        }
+    }
+    bits[lane] = 0;
+    if (lane == 0) maxlen_s = 0;
+    for (int i = lane; i < (int)(sizeof spec_w / 4); i += 64) spec_w[i] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        const int i = lane + 64 * k;
+        if (i < 257) {
+            cs_s[i] = cs[k];
+            if (cs[k]) {
+                atomicAdd(&bits[cs[k] < 63 ? cs[k] : 63], 1); // (sizes stay below 50 for 32-bit counts)
+                atomicMax(&maxlen_s, (int)cs[k]);
+            }
+        }
+    }
+    __syncthreads();
+    // HUFFVAL position of each symbol < 256: the coded symbols of smaller size, and those of equal size and smaller index
+    unsigned pos[4] = {0, 0, 0, 0};
+    for (int i = 0; i < 256; i++) {
+        const unsigned c = cs_s[i];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const unsigned mine = cs[k];
+            pos[k] += (c && (c < mine || (c == mine && i < lane + 64 * k))) ? 1u : 0u;
+        }
+    }
+    uint8_t *sb = reinterpret_cast<uint8_t *>(spec_w);
+    if (lane == 0) {
+        // figure K.3: no code longer than 16 bits; then the reserved symbol's code leaves the longest length
+        for (int i = maxlen_s < 63 ? maxlen_s : 63; i > 16; i--)
+            while (bits[i] > 0) {
+                int j = i - 2;
+                while (bits[j] == 0) j--;
+                bits[i] -= 2;
+                bits[i - 1]++;
+                bits[j + 1] += 2;
+                bits[j]--;
+            }
+        int i = 16;
+        while (bits[i] == 0) i--;
+        bits[i]--;
+        // canonical codes (tables.ml:27-45)
+        int n = 0;
+        unsigned code = 0;
+        cum[0] = 0;
+        for (int l = 1; l <= 16; l++) {
+            sb[l - 1] = (uint8_t)bits[l];
+            firstcode[l] = code;
+            n += bits[l];
+            cum[l] = n;
+            code = (code + (unsigned)bits[l]) << 1;
+        }
+        sb[offsetof(hvc_huff_spec, n_vals)] = (uint8_t)(n & 255);
+        sb[offsetof(hvc_huff_spec, n_vals) + 1] = (uint8_t)(n >> 8);
+    }
+    __syncthreads();
+    unsigned *tab = P.opt_tables + (size_t)frame * HUFF_TABLE_WORDS + 272 * set + (ac ? 16 : 0);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int i = lane + 64 * k;
+        unsigned e = 0;
+        if (cs[k] && i < 256) {
+            const int p = (int)pos[k];
+            sb[offsetof(hvc_huff_spec, vals) + p] = (uint8_t)i;
+            int l = 1;
+            while (l < 16 && p >= cum[l]) l++;
+            e = ((firstcode[l] + (unsigned)(p - cum[l - 1])) << 5) | (unsigned)l;
+        }
+        if (i < nsym) tab[i] = e;
+    }
+    __syncthreads();
+    unsigned *dst = reinterpret_cast<unsigned *>(P.specs + (size_t)frame * 4 + t);
+    for (int i = lane; i < (int)(sizeof spec_w / 4); i += 64) dst[i] = spec_w[i];
 }
 
 // pass 2 / 4b: per-frame exclusive scan of n[frame] 32-bit values (in place), total -> totals[frame].
@@ -343,6 +529,14 @@ hipError_t launch_huffman_encode(const HuffParams &P, hipStream_t s) {
     e = hipMemsetAsync(P.bitbuf, 0, (size_t)P.n_frames * P.bitbuf_words * sizeof(unsigned), s);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)P.tiles_per_frame, (unsigned)P.n_frames, 1);
+    if (P.hist) { // the frames' own tables
+        e = hipMemsetAsync(P.hist, 0, (size_t)P.n_frames * HUFF_TABLE_WORDS * sizeof(unsigned), s);
+        if (e != hipSuccess) return e;
+        int per = HIST_GROUPS / P.n_frames;
+        per = per < 1 ? 1 : (per > P.tiles_per_frame ? P.tiles_per_frame : per);
+        hipLaunchKernelGGL(k_huff_hist, dim3((unsigned)per, (unsigned)P.n_frames, 1), dim3(HT), 0, s, P);
+        hipLaunchKernelGGL(k_huff_build, dim3(4, (unsigned)P.n_frames, 1), dim3(64), 0, s, P);
+    }
     hipLaunchKernelGGL(k_huff_len, grid, dim3(HT), 0, s, P);
     hipLaunchKernelGGL(k_scan_u32, dim3((unsigned)P.n_frames), dim3(1024), 0, s, P.lens, (size_t)P.blocks_per_frame,
                        (const unsigned *)nullptr, P.blocks_per_frame, P.frame_bits);

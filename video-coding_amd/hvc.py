@@ -30,7 +30,10 @@ SYMBOLS = [
     "hvc_set_arithmetic", "hvc_get_arithmetic", "hvc_decode_frames_divergence",
     "hvc_set_encode_arithmetic", "hvc_get_encode_arithmetic", "hvc_encode_frames_divergence",
     "hvc_dct_rom", "hvc_dct_matrix", "hvc_dct_blocks", "hvc_dct_fixed", "hvc_dct_reference", "hvc_dct_error_search",
+    "hvc_set_huffman_tables", "hvc_get_huffman_tables", "hvc_huffman_spec_from_counts", "hvc_huffman_optimal_tables",
+    "hvc_jpeg_header_tables", "hvc_jpeg_entropy_encode_tables", "hvc_huffman_encode_frames_optimised",
 ]
+HVC_HUFF = {"default": 0, "optimised": 1}  # enum hvc_huff_tables
 HVC_ARITH = {"model": 0, "hardcaml": 1}  # enum hvc_arith
 HVC_SLOTS = 4       # enum { HVC_SLOTS }
 HVC_E_BUSY = -12
@@ -72,6 +75,35 @@ class JpegInfo(C.Structure):
             out.append(pixels[L.plane_offset:L.plane_offset + c.decoded_width * c.decoded_height].reshape(
                 c.decoded_height, c.decoded_width))
         return out
+
+
+class HuffSpec(C.Structure):
+    """struct hvc_huff_spec: one DHT body (bits[l - 1] codes of length l, then n_vals symbols)"""
+    _fields_ = [("bits", C.c_uint8 * 16), ("vals", C.c_uint8 * 256), ("n_vals", C.c_uint16), ("pad", C.c_uint16)]
+
+    def to_pair(self):
+        """-> (bits as a list of 16, huffval as a list)"""
+        return list(self.bits), list(self.vals[:self.n_vals])
+
+    @classmethod
+    def from_pair(cls, bits, vals):
+        s = cls()
+        bits = list(bits)
+        if len(bits) == 17:  # jpeg_opt_writer's bits[0..16] with bits[0] unused
+            bits = bits[1:]
+        for i, b in enumerate(bits):
+            s.bits[i] = b
+        for i, v in enumerate(vals):
+            s.vals[i] = v
+        s.n_vals = len(vals)
+        return s
+
+
+def huff_specs(specs):
+    """four (bits, vals) pairs or HuffSpec -> ctypes array of 4 hvc_huff_spec (DC0, DC1, AC0, AC1)"""
+    if isinstance(specs, C.Array):
+        return specs
+    return (HuffSpec * len(specs))(*[s if isinstance(s, HuffSpec) else HuffSpec.from_pair(*s) for s in specs])
 
 
 class BatchStats(C.Structure):
@@ -189,6 +221,14 @@ def lib():
         L.hvc_compare_planes.argtypes = [vp, vp, sz, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.hvc_jpeg_encoder_layout.argtypes = [i, i, i, i, ip]
         L.hvc_jpeg_entropy_encode.argtypes = [ip, vp, vp, sz, C.POINTER(sz)]
+        hs = C.POINTER(HuffSpec)
+        L.hvc_set_huffman_tables.argtypes = [vp, i]
+        L.hvc_get_huffman_tables.argtypes = [vp, C.POINTER(i)]
+        L.hvc_huffman_spec_from_counts.argtypes = [vp, hs]
+        L.hvc_huffman_optimal_tables.argtypes = [ip, vp, hs]
+        L.hvc_jpeg_header_tables.argtypes = [ip, hs, vp, sz, C.POINTER(sz)]
+        L.hvc_jpeg_entropy_encode_tables.argtypes = [ip, hs, vp, vp, sz, C.POINTER(sz)]
+        L.hvc_huffman_encode_frames_optimised.argtypes = [vp, ip, vp, sz, i, vp, sz, vp, hs, i]
         L.hvc_jpeg_encode.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, sz, C.POINTER(sz)]
         L.hvc_checksum_records.argtypes = [vp, vp, sz, sz, i, vp, i]
         L.hvc_set_host_cpus.argtypes = [vp, C.c_char_p]
@@ -473,12 +513,36 @@ def huffman_code_tables(table_set, ctx=None):
     return {"dc": dc, "ac": ac}
 
 
-def jpeg_header(info):
-    """SOI .. SOS of the file Encoder.write_headers produces for this geometry / quality"""
+def jpeg_header(info, specs=None):
+    """SOI .. SOS of the file Encoder.write_headers produces for this geometry / quality; specs: four (bits, vals) pairs
+    or HuffSpec (DC0, DC1, AC0, AC1) for the DHT bodies in place of the default tables (hvc_jpeg_header_tables)"""
     n = C.c_size_t()
-    buf = np.empty(2048, dtype=np.uint8)
-    _chk(lib().hvc_jpeg_header(C.byref(info), buf.ctypes.data, buf.size, C.byref(n)), "hvc_jpeg_header")
+    buf = np.empty(4096, dtype=np.uint8)
+    if specs is None:
+        _chk(lib().hvc_jpeg_header(C.byref(info), buf.ctypes.data, buf.size, C.byref(n)), "hvc_jpeg_header")
+    else:
+        _chk(lib().hvc_jpeg_header_tables(C.byref(info), huff_specs(specs), buf.ctypes.data, buf.size, C.byref(n)),
+             "hvc_jpeg_header_tables")
     return buf[:n.value].tobytes()
+
+
+def huffman_spec_from_counts(counts):
+    """ITU-T T.81 Annex K.2 over 256 symbol counts (hvc_huffman_spec_from_counts) -> (bits as a list of 16, huffval)"""
+    c = np.zeros(256, dtype=np.uint64)
+    c[:len(counts)] = np.asarray(counts, dtype=np.uint64)
+    s = HuffSpec()
+    _chk(lib().hvc_huffman_spec_from_counts(c.ctypes.data, C.byref(s)), "hvc_huffman_spec_from_counts")
+    return s.to_pair()
+
+
+def huffman_optimal_tables(info, coefs):
+    """the four optimal tables of one frame's coefficient record (hvc_huffman_optimal_tables): [(bits, vals)] DC0, DC1,
+    AC0, AC1"""
+    coefs = np.ascontiguousarray(coefs, dtype=np.int16)
+    assert coefs.size >= info.coef_count
+    out = (HuffSpec * 4)()
+    _chk(lib().hvc_huffman_optimal_tables(C.byref(info), coefs.ctypes.data, out), "hvc_huffman_optimal_tables")
+    return [s.to_pair() for s in out]
 
 
 def jpeg_encoder_layout(width, height, chroma, quality):
@@ -501,14 +565,22 @@ def encoder_pixel_record(info, y, u, v, width, height, chroma):
     return out
 
 
-def jpeg_entropy_encode(info, coefs):
+def jpeg_entropy_encode(info, coefs, specs=None):
+    """the whole file of one coefficient record; specs: four (bits, vals) pairs or HuffSpec (DC0, DC1, AC0, AC1) in place
+    of the default tables (hvc_jpeg_entropy_encode_tables), "optimised" for the record's own optimal ones"""
     coefs = np.ascontiguousarray(coefs, dtype=np.int16)
     assert coefs.size == info.coef_count
     cap = 8 * coefs.size + 4096  # 26 bits per coefficient at worst, every byte stuffed
     out = np.empty(cap, dtype=np.uint8)
     n = C.c_size_t()
-    _chk(lib().hvc_jpeg_entropy_encode(C.byref(info), coefs.ctypes.data, out.ctypes.data, cap, C.byref(n)),
-         "hvc_jpeg_entropy_encode")
+    if specs is None:
+        _chk(lib().hvc_jpeg_entropy_encode(C.byref(info), coefs.ctypes.data, out.ctypes.data, cap, C.byref(n)),
+             "hvc_jpeg_entropy_encode")
+    else:
+        if isinstance(specs, str) and specs == "optimised":
+            specs = huffman_optimal_tables(info, coefs)
+        _chk(lib().hvc_jpeg_entropy_encode_tables(C.byref(info), huff_specs(specs), coefs.ctypes.data, out.ctypes.data, cap,
+                                                  C.byref(n)), "hvc_jpeg_entropy_encode_tables")
     return out[:n.value].tobytes()
 
 
@@ -647,6 +719,18 @@ class Context:
         v = C.c_int()
         _chk(lib().hvc_get_encode_arithmetic(self._h, C.byref(v)), "hvc_get_encode_arithmetic")
         return {b: a for a, b in HVC_ARITH.items()}.get(v.value, v.value)
+
+    def set_huffman_tables(self, which):
+        """"default" (the Annex K tables, every byte as before) | "optimised" (each file's own Annex K.2 tables): the files of
+        jpeg_encode and jpeg_encode_batch (both coders).  Independent of set_encode_arithmetic."""
+        _chk(lib().hvc_set_huffman_tables(self._h, HVC_HUFF[which] if isinstance(which, str) else int(which)),
+             "hvc_set_huffman_tables")
+
+    @property
+    def huffman_tables(self):
+        v = C.c_int()
+        _chk(lib().hvc_get_huffman_tables(self._h, C.byref(v)), "hvc_get_huffman_tables")
+        return {b: a for a, b in HVC_HUFF.items()}.get(v.value, v.value)
 
     def encode_divergence(self, pixels, pixel_frame_stride, qtabs, comps, n_frames, max_diff=None, diff_frame_stride=None):
         """min(255, max |q_model - q_hardcaml|) per block (hvc_encode_frames_divergence) -> uint8 array [n_frames, blocks
@@ -889,6 +973,32 @@ class Context:
                                                  cap, offs.ctypes.data, 0), "hvc_huffman_encode_frames")
             o, data = offs, out
         return [data[int(o[f]):int(o[f + 1])].tobytes() for f in range(n_frames)]
+
+    def huffman_encode_frames_optimised(self, info, coefs, coef_frame_stride, n_frames, out_cap=None):
+        """hvc_huffman_encode_frames with each frame's own optimal tables, counted and built on the GPU: (list of per-frame
+        segments as bytes, list of per-frame [(bits, vals)] x 4: DC0, DC1, AC0, AC1)"""
+        ca, where = _addr(coefs)
+        cap = out_cap or (n_frames * (info.coef_count // 64) * 243 + 4096)
+        specs = (HuffSpec * max(4 * n_frames, 1))()
+        if where == 1:
+            import torch
+            out = torch.empty(cap, dtype=torch.uint8, device="cuda")
+            offs = torch.zeros(n_frames + 1, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            _chk(lib().hvc_huffman_encode_frames_optimised(self._h, C.byref(info), ca, coef_frame_stride, n_frames,
+                                                           out.data_ptr(), cap, offs.data_ptr(), specs, 1),
+                 "hvc_huffman_encode_frames_optimised")
+            o = offs.cpu().numpy()
+            data = out[:int(o[-1])].cpu().numpy()
+        else:
+            out = np.empty(cap, dtype=np.uint8)
+            offs = np.zeros(n_frames + 1, dtype=np.uint64)
+            _chk(lib().hvc_huffman_encode_frames_optimised(self._h, C.byref(info), ca, coef_frame_stride, n_frames,
+                                                           out.ctypes.data, cap, offs.ctypes.data, specs, 0),
+                 "hvc_huffman_encode_frames_optimised")
+            o, data = offs, out
+        return ([data[int(o[f]):int(o[f + 1])].tobytes() for f in range(n_frames)],
+                [[specs[4 * f + t].to_pair() for t in range(4)] for f in range(n_frames)])
 
     def jpeg_encode_batch(self, frames, width, height, chroma=420, quality=75, threads=8, frames_per_chunk=16,
                           gpu_entropy=False):
