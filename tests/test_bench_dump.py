@@ -51,6 +51,11 @@ def test_a_larger_output_is_a_fixed_seeded_sample_within_the_budget(tmp_path):
     assert all(np.isin(files[0][i], rows[i]).all() for i in range(4))   # every value is one of the record's own
 
 
+def test_full_is_off_by_default():
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    assert bench.parse_args(["--config", "3", "--full"]).full is True
+
+
 def test_steps_sets_the_timed_steps():
     assert bench.parse_args(["--steps", "7"]).steps == 7 and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
     with pytest.raises(SystemExit):

@@ -72,9 +72,9 @@ def _run_bench(args, **env):
 
 
 def test_bench_line_is_verified_against_the_golden_checksums():
-    """python bench.py (config 2, small batch): the line carries roofline + cpu_baseline + a checksum that equals
+    """python bench.py --full (config 2, small batch): the line carries roofline + cpu_baseline + a checksum that equals
     tests/golden/bench_checksums.json -- entries the CPU suite derives from the model restatement."""
-    rec = _run_bench(["--steps", "3", "--warmup", "1", "--frames", "64", "--cpu-seconds", "1", "--sustain-seconds", "0.5"])
+    rec = _run_bench(["--full", "--steps", "3", "--warmup", "1", "--frames", "64", "--cpu-seconds", "1", "--sustain-seconds", "0.5"])
     with open(os.path.join(GOLDEN, "bench_checksums.json")) as f:
         g = json.load(f)
     assert rec["checksum"]["verified"] is True and rec["checksum"]["rank0"] == g["bench_config2"]["rank0"]
@@ -87,10 +87,10 @@ def test_bench_line_is_verified_against_the_golden_checksums():
 
 
 def test_headline_launch_verifies_every_one_of_its_1024_frames():
-    """`python bench.py` at its default launch -- 1024 frames of 1080p 4:2:0 -- K5-checksums EVERY record of the
+    """`python bench.py --full` at its default launch -- 1024 frames of 1080p 4:2:0 -- K5-checksums EVERY record of the
     launch whose time is `value` (record r holds distinct frame r % 8), not the first eight; the tight layout beside the aligned
     one is timed and verified in the same run (roofline.other_layout)."""
-    rec = _run_bench(["--steps", "2", "--no-others", "--cpu-seconds", "0", "--sustain-seconds", "0.3"])
+    rec = _run_bench(["--full", "--steps", "2", "--no-others", "--cpu-seconds", "0", "--sustain-seconds", "0.3"])
     assert rec["config"]["frames_per_launch"] == 1024 and rec["config"]["baseline_config"] == 2
     assert rec["checksum"]["frames"] == 1024 and rec["checksum"]["distinct"] == 8 and rec["checksum"]["verified"] is True
     assert rec["sustained"]["output_unchanged"] is True
@@ -107,7 +107,7 @@ def test_bench_layouts_aligned_and_tight_decode_the_same_frames(tmp_path):
         golden = [int(v, 16) for v in json.load(f)["bench_config2"]["rank0"]]
     for extra, name in (([], "pixels"), (["--config", "5"], "coefs")):
         dirs = [str(tmp_path / ("%s%d" % (name, k))) for k in range(2)]
-        recs = [_run_bench(extra + ["--steps", "2", "--warmup", "1", "--frames", "32", "--no-cpu-baseline", "--no-others", "--sustain-seconds", "0",
+        recs = [_run_bench(extra + ["--full", "--steps", "2", "--warmup", "1", "--frames", "32", "--no-cpu-baseline", "--no-others", "--sustain-seconds", "0",
                                     "--dump-outputs", d] + t) for d, t in zip(dirs, ([], ["--tight"]))]
         assert "boundary" in recs[0]["config"]["layout"] and "tight" in recs[1]["config"]["layout"]
         assert all(r["checksum"]["verified"] is True for r in recs)
@@ -122,13 +122,32 @@ def test_bench_layouts_aligned_and_tight_decode_the_same_frames(tmp_path):
             assert list(checksum_records(dumps[0].astype(np.uint8))) == [golden[r % 8] for r in rows]
 
 
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """bench.py without --full: setup, warm-up, the timed steps, the --dump-outputs files and the line -- no K5 comparison, no
+    sustained run, other layout, `others` or CPU baseline.  What it dumps is what a --full run of the same command dumps, and
+    that run's output verifies against the golden checksums (configs 2, 3 and 5)."""
+    for extra, names in (([], ["pixels"]), (["--config", "5"], ["coefs"]),
+                         (["--config", "3"], ["pixels_host_reader", "pixels_gpu_reader"])):
+        dirs = [str(tmp_path / ("%s_%d" % (names[0], k))) for k in range(2)]
+        common = extra + ["--steps", "2", "--warmup", "1", "--frames", "32" if names != ["coefs"] else "16"]
+        plain = _run_bench(common + ["--dump-outputs", dirs[0]])
+        full = _run_bench(common + ["--full", "--no-cpu-baseline", "--no-others", "--sustain-seconds", "0", "--dump-outputs", dirs[1]])
+        assert not {"checksum", "sustained", "others", "cpu_baseline"} & set(plain), sorted(plain)
+        assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["steps"] == 2 and plain["warmup"] == 1
+        assert full["checksum"]["verified"] is True
+        if names == ["pixels"]:
+            assert plain["roofline"]["other_layout"] is None and "tight" in full["roofline"]["other_layout"]["layout"]
+        for name in names:
+            assert np.array_equal(np.load(os.path.join(dirs[0], name + ".npy")), np.load(os.path.join(dirs[1], name + ".npy")))
+
+
 def test_bench_n_rank_path_on_one_gpu():
     """HVC_BENCH_REHEARSAL=1 python bench.py --gpus 2, as typed: bench.py starts the two ranks itself (both on
     cuda:0, gloo for the timing closure), each decodes its own shard, both outputs are verified."""
-    rec = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "64"], HVC_BENCH_REHEARSAL="1")
+    rec = _run_bench(["--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--frames", "64"], HVC_BENCH_REHEARSAL="1")
     assert rec["n_gpus"] == 2 and "REHEARSAL" in rec["data"]
     assert rec["checksum"]["verified"] is True and rec["checksum"]["ranks_verified"] == 2
-    rec = _run_bench(["--gpus", "2", "--config", "4", "--steps", "1", "--warmup", "0", "--frames", "8", "--shard", "16"],
+    rec = _run_bench(["--gpus", "2", "--config", "4", "--full", "--steps", "1", "--warmup", "0", "--frames", "8", "--shard", "16"],
                      HVC_BENCH_REHEARSAL="1")
     assert rec["n_gpus"] == 2 and rec["config"]["baseline_config"] == 4 and rec["checksum"]["ranks_verified"] == 2
     assert rec["config"]["frames_per_gpu_per_step"] == 16 and rec["config"]["frames_per_launch"] == 8
@@ -138,11 +157,11 @@ def test_bench_four_ranks_on_one_gpu():
     """The widest rehearsal a one-GPU box allows (at most 6 processes may use its card; eight ranks are rehearsed on
     the CPU, tests/test_distributed_cpu.py): four ranks of both configurations, every rank's shard verified against
     the golden checksums of ITS rank (distinct seeds per rank)."""
-    rec = _run_bench(["--gpus", "4", "--steps", "2", "--warmup", "1", "--frames", "32", "--sustain-seconds", "0.2"],
+    rec = _run_bench(["--gpus", "4", "--full", "--steps", "2", "--warmup", "1", "--frames", "32", "--sustain-seconds", "0.2"],
                      HVC_BENCH_REHEARSAL="1")
     assert rec["n_gpus"] == 4 and rec["checksum"]["ranks_verified"] == 4 and "REHEARSAL" in rec["data"]
     assert rec["sustained"]["output_unchanged"] is True
-    rec = _run_bench(["--gpus", "4", "--config", "4", "--steps", "1", "--warmup", "0", "--frames", "8", "--shard", "16",
+    rec = _run_bench(["--gpus", "4", "--config", "4", "--full", "--steps", "1", "--warmup", "0", "--frames", "8", "--shard", "16",
                       "--sustain-seconds", "0"], HVC_BENCH_REHEARSAL="1")
     assert rec["n_gpus"] == 4 and rec["config"]["baseline_config"] == 4 and rec["checksum"]["ranks_verified"] == 4
     assert "sustained" not in rec
@@ -152,7 +171,7 @@ def test_bench_config3_and_5_one_rank_and_two():
     """bench.py --config 3 (BASELINE configs[2]: JPEG files, host Huffman || H2D || K1; the GPU reader beside it) and --config 5
     (configs[4]: the encoder's block stage), small batches: alone with their CPU baselines, and over two ranks sharing the GPU
     (the file batch split, every rank's output K5-verified, each rank on its share of the host's CPUs)."""
-    rec = _run_bench(["--config", "3", "--frames", "128", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"])
+    rec = _run_bench(["--config", "3", "--full", "--frames", "128", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"])
     assert rec["n_gpus"] == 1 and rec["scaling"] == "strong" and rec["config"]["baseline_config"] == 3
     assert "host Huffman || H2D || K1" in rec["config"]["workload"] and rec["config"]["files_total"] == 128
     for reader in ("host_reader", "gpu_reader"):
@@ -164,20 +183,20 @@ def test_bench_config3_and_5_one_rank_and_two():
     assert rf["h2d_GBps"] == rec["host_reader"]["h2d_GBps"] and rf["overlap_fraction"] == rec["host_reader"]["overlap_fraction"]
     assert rf["algorithmic_bytes_per_launch"] == rec["host_reader"]["kernel_launch_frames"] * 48960 * 192
     assert rf["traffic"] or rf["traffic_source"].startswith(("stale", "no committed"))
-    rec = _run_bench(["--gpus", "2", "--config", "3", "--frames", "128", "--steps", "2", "--warmup", "1"], HVC_BENCH_REHEARSAL="1")
+    rec = _run_bench(["--gpus", "2", "--config", "3", "--full", "--frames", "128", "--steps", "2", "--warmup", "1"], HVC_BENCH_REHEARSAL="1")
     assert rec["n_gpus"] == 2 and rec["config"]["files_per_gpu_per_step"] == 64 and "REHEARSAL" in rec["data"]
     assert rec["host_reader"]["ranks_verified"] == 2 and rec["gpu_reader"]["ranks_verified"] == 2
     walls = rec["host_reader"]["per_rank"]["wall_ms_entropy_thread_ms_sum_h2d_ms_kernel_ms_threads"]
     assert len(walls) == 2 and all(w[0] > 0 and w[4] >= 1 for w in walls)
-    rec = _run_bench(["--config", "5", "--frames", "16", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"])
+    rec = _run_bench(["--config", "5", "--full", "--frames", "16", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"])
     assert rec["config"]["baseline_config"] == 5 and rec["roofline"]["kernel"] == "k_encode" and rec["checksum"]["verified"] is True
     assert rec["cpu_baseline"]["value"] > 0 and 0 < rec["roofline"]["frac"] < 1
-    rec = _run_bench(["--gpus", "2", "--config", "5", "--frames", "16", "--steps", "2", "--warmup", "1"], HVC_BENCH_REHEARSAL="1")
+    rec = _run_bench(["--gpus", "2", "--config", "5", "--full", "--frames", "16", "--steps", "2", "--warmup", "1"], HVC_BENCH_REHEARSAL="1")
     assert rec["n_gpus"] == 2 and rec["checksum"]["ranks_verified"] == 2 and len(rec["per_rank_kernel_ms"]["mean_min_max"]) == 2
 
 
 def test_bench_fails_when_the_output_is_not_the_models(tmp_path):
-    """A run whose checksums differ from the golden ones exits non-zero and says "verified": false: here
+    """A --full run whose checksums differ from the golden ones exits non-zero and says "verified": false: here
     the golden file is swapped for one with another rank's values."""
     with open(os.path.join(GOLDEN, "bench_checksums.json")) as f:
         g = json.load(f)
@@ -186,13 +205,13 @@ def test_bench_fails_when_the_output_is_not_the_models(tmp_path):
     alt.write_text(json.dumps(g))
     e = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     e["HVC_BENCH_GOLDEN"] = str(alt)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "32",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--frames", "32",
                           "--no-cpu-baseline", "--sustain-seconds", "0"], capture_output=True, text=True, env=e, timeout=900, cwd=ROOT)
     assert out.returncode == 3, out.stdout[-2000:] + out.stderr[-2000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     assert rec["checksum"]["verified"] is False and rec["checksum"]["ranks_verified"] == 0
     # more distinct frames than the golden file holds: the line says the comparison was skipped, exit 0
-    rec = _run_bench(["--steps", "2", "--warmup", "1", "--frames", "32", "--distinct", "9", "--no-cpu-baseline", "--sustain-seconds", "0"])
+    rec = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--frames", "32", "--distinct", "9", "--no-cpu-baseline", "--sustain-seconds", "0"])
     assert rec["checksum"]["verified"] is None and rec["checksum"]["verification"].startswith("SKIPPED")
 
 
@@ -239,7 +258,7 @@ def test_bench_rccl_calls_on_one_gpu():
     e.update(HVC_BENCH_DIST_ALWAYS="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", "29551", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "64", "--no-cpu-baseline"],
+                          "--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--frames", "64", "--no-cpu-baseline"],
                          capture_output=True, text=True, env=e, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
@@ -249,7 +268,7 @@ def test_bench_rccl_calls_on_one_gpu():
                         ("29555", ["--config", "5", "--frames", "16", "--steps", "2", "--warmup", "1"])):
         out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                               "--master-addr", "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"),
-                              "--gpus", "1", "--no-cpu-baseline"] + extra, capture_output=True, text=True, env=e, timeout=900, cwd=ROOT)
+                              "--gpus", "1", "--full", "--no-cpu-baseline"] + extra, capture_output=True, text=True, env=e, timeout=900, cwd=ROOT)
         assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
         rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
         assert rec["n_gpus"] == 1 and rec["checksum"]["ranks_verified"] == 1 and "REHEARSAL" not in rec["data"]

@@ -35,8 +35,8 @@ def test_config5_at_256_frames_block_stage_and_files():
 
 def test_config4_one_gpus_whole_shard():
     """2048 frames of 4K 4:4:4 per GPU, resident when the device has the room (the line says which), 16 launches of 128 frames
-    per step: `bench.py --config 4` exits non-zero unless every distinct frame's checksum is the model's"""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "4", "--steps", "1", "--warmup", "0",
+    per step: `bench.py --config 4 --full` exits non-zero unless every distinct frame's checksum is the model's"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "4", "--full", "--steps", "1", "--warmup", "0",
                           "--no-cpu-baseline", "--sustain-seconds", "0"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

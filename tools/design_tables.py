@@ -140,7 +140,7 @@ def tables(tag):
     a, bb = o["config5_files_host_coder_256_frames"], o["config5_files_gpu_coder_256_frames"]
     t.append("| config 5 end to end (raw 4K frames → `.jpg` files), host coder / GPU coder | %.2f / **%.1f Gpixel/s** (host-bound / upload-bound), both verified byte for byte | `others` of %s |"
              % (a["Gpixel_s"], bb["Gpixel_s"], bsrc))
-    t.append("| `others` of the headline line (what the driver's own run witnesses) | config 4's launch %s, K3 %s, fused 4:4:4 %s, K2 %s, `subsample_hv2` %s; config 3 host / GPU reader %.1f / %.1f Gpixel/s; all `verified` | %s |"
+    t.append("| `others` of the headline line (`bench.py --full`) | config 4's launch %s, K3 %s, fused 4:4:4 %s, K2 %s, `subsample_hv2` %s; config 3 host / GPU reader %.1f / %.1f Gpixel/s; all `verified` | %s |"
              % (pct(o["config4_launch_128x4K444"]["frac_of_8TBps"]), pct(o["k3_encode_256x4K420"]["frac_of_8TBps"]), pct(f["frac_of_8TBps"]),
                 pct(k2["frac_of_8TBps"]), pct(s2["frac_of_8TBps"]), o["config3_host_reader_4096_files"]["Gpixel_s"],
                 o["config3_gpu_reader_4096_files"]["Gpixel_s"], bsrc))

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 K=gpurun_out/${TAG}_${WHAT}_variants.txt
 mkdir -p gpurun_out
 case $WHAT in
-  k1)  CMD="python bench.py --steps 40 --no-cpu-baseline --no-others --sustain-seconds 0"; PAT='"verified": [a-z]*\|"kernel_ms": [0-9.]*\|"frac": [0-9.]*';;
+  k1)  CMD="python bench.py --full --steps 40 --no-cpu-baseline --no-others --sustain-seconds 0"; PAT='"verified": [a-z]*\|"kernel_ms": [0-9.]*\|"frac": [0-9.]*';;
   k3)  CMD="python tools/bench_configs.py --config 5 --steps 40"; PAT='"verified": [a-z]*\|"kernel_ms": [0-9.]*\|"frac_of_8TBps": [0-9.]*';;
   444) CMD="python tools/bench_configs.py --config 7 --fused-only --steps 40"; PAT='"verified": [a-z]*\|"fused_ms": [0-9.]*\|"frac_of_8TBps": [0-9.]*';;
   *) echo "k1 | k3 | 444"; exit 1;;

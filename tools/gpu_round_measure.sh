@@ -1,8 +1,9 @@
 #!/bin/bash
 # One GPU session that produces every number DESIGN.md section 5 quotes (run via gpurun from the repo root), limited to SURVEY.md
 # section 8's rows (VERDICT r4's stop list: no single-file, small-batch, restart-interval, convert or reader-chunk figures):
-#   PART=a  the bench lines:      gpurun_out/<tag>_lines.jsonl (every JSON line, tagged with its command's name: "what"),
-#                                 <tag>_stderr.txt, <tag>_shape_ceilings.txt, <tag>_mem_ubench3.txt
+#   PART=a  the bench lines:      $OUT/<tag>_lines.jsonl (every JSON line, tagged with its command's name: "what"),
+#                                 <tag>_stderr.txt, <tag>_shape_ceilings.txt, <tag>_mem_ubench3.txt; OUT = the directory the
+#                                 session's results are collected from (required for part a; bench.py runs with --full)
 #   PART=b  the rocprofv3 passes: gpurun_out/<tag>_{decode,decode_c4,decode_c3,encode,444,wide}_rocprofv3.txt (kernel trace + PMC averages) and
 #                                 gpurun_out/traffic_<tag>.jsonl (one profiles/traffic.json entry per line)
 # The driver's own two commands (the GPU suite and smoke()) are NOT in here: they are issued as direct gpurun calls.
@@ -12,37 +13,39 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p gpurun_out
 PART=${PART:-all}
 if [ "$PART" != "b" ]; then
-python bench.py > gpurun_out/m_bench.json 2> gpurun_out/m_bench.err
-python bench.py --config 4 --no-cpu-baseline > gpurun_out/m_bench_c4.json 2> gpurun_out/m_bench_c4.err
-python bench.py --config 3 > gpurun_out/m_bench_c3.json 2> gpurun_out/m_bench_c3.err
-python bench.py --config 5 > gpurun_out/m_bench_c5.json 2> gpurun_out/m_bench_c5.err
-python bench.py --frames 4096 --steps 20 --no-cpu-baseline --no-others > gpurun_out/m_bench_f4096.json 2> /dev/null
-HVC_DECODE_KERNEL=q16 python bench.py --no-cpu-baseline --no-others --sustain-seconds 0 > gpurun_out/m_bench_q16.json 2> gpurun_out/m_bench_q16.err
+OUT=${OUT:?"set OUT to the directory the session's results are collected from"}
+mkdir -p "$OUT"
+python bench.py --full > $OUT/m_bench.json 2> $OUT/m_bench.err
+python bench.py --full --config 4 --no-cpu-baseline > $OUT/m_bench_c4.json 2> $OUT/m_bench_c4.err
+python bench.py --full --config 3 > $OUT/m_bench_c3.json 2> $OUT/m_bench_c3.err
+python bench.py --full --config 5 > $OUT/m_bench_c5.json 2> $OUT/m_bench_c5.err
+python bench.py --full --frames 4096 --steps 20 --no-cpu-baseline --no-others > $OUT/m_bench_f4096.json 2> /dev/null
+HVC_DECODE_KERNEL=q16 python bench.py --full --no-cpu-baseline --no-others --sustain-seconds 0 > $OUT/m_bench_q16.json 2> $OUT/m_bench_q16.err
 echo "bench done"
 # N-rank rehearsals on this one GPU (all ranks on cuda:0, gloo): never measurements, the lines say so
-HVC_BENCH_REHEARSAL=1 python bench.py --gpus 2 --steps 20 --no-cpu-baseline 2> gpurun_out/m_bench_rehearsal2.err | grep '^{' > gpurun_out/m_bench_rehearsal2.json
-HVC_BENCH_REHEARSAL=1 python bench.py --gpus 4 --config 4 --steps 1 --warmup 0 --frames 16 --shard 64 --no-cpu-baseline --sustain-seconds 0 2> gpurun_out/m_bench_rehearsal4_c4.err | grep '^{' > gpurun_out/m_bench_rehearsal4_c4.json
-HVC_BENCH_REHEARSAL=1 python bench.py --gpus 2 --config 3 2> gpurun_out/m_bench_rehearsal2_c3.err | grep '^{' > gpurun_out/m_bench_rehearsal2_c3.json
-HVC_BENCH_REHEARSAL=1 python bench.py --gpus 2 --config 5 --steps 10 2> gpurun_out/m_bench_rehearsal2_c5.err | grep '^{' > gpurun_out/m_bench_rehearsal2_c5.json
+HVC_BENCH_REHEARSAL=1 python bench.py --full --gpus 2 --steps 20 --no-cpu-baseline 2> $OUT/m_bench_rehearsal2.err | grep '^{' > $OUT/m_bench_rehearsal2.json
+HVC_BENCH_REHEARSAL=1 python bench.py --full --gpus 4 --config 4 --steps 1 --warmup 0 --frames 16 --shard 64 --no-cpu-baseline --sustain-seconds 0 2> $OUT/m_bench_rehearsal4_c4.err | grep '^{' > $OUT/m_bench_rehearsal4_c4.json
+HVC_BENCH_REHEARSAL=1 python bench.py --full --gpus 2 --config 3 2> $OUT/m_bench_rehearsal2_c3.err | grep '^{' > $OUT/m_bench_rehearsal2_c3.json
+HVC_BENCH_REHEARSAL=1 python bench.py --full --gpus 2 --config 5 --steps 10 2> $OUT/m_bench_rehearsal2_c5.err | grep '^{' > $OUT/m_bench_rehearsal2_c5.json
 echo "rehearsals done"
-python tools/bench_configs.py --config 7 > gpurun_out/m_c7.json 2> gpurun_out/m_c7.err                       # fused 4:4:4 against its three-launch composition
-python tools/bench_configs.py --config 2 > gpurun_out/m_k2.json 2> gpurun_out/m_k2.err                       # K2 alone
-python tools/bench_configs.py --config 10 > gpurun_out/m_sub420.json 2> gpurun_out/m_sub420.err              # subsample_hv2
-python tools/bench_configs.py --config 6 > gpurun_out/m_c6.json 2> gpurun_out/m_c6.err                       # host-buffer boundary (PCIe-inclusive)
-python tools/bench_configs.py --config 8 > gpurun_out/m_c5_files.json 2> gpurun_out/m_c5_files.err           # config 5 to files, host coder
-python tools/bench_configs.py --config 8 --gpu-entropy > gpurun_out/m_c5_files_gpu_entropy.json 2> gpurun_out/m_c5g.err
-python tools/bench_configs.py --config 9 > gpurun_out/m_huffman_gpu.json 2> gpurun_out/m_huffman_gpu.err      # GPU Huffman coder alone
-python tools/bench_configs.py --config 12 --threads 16 > gpurun_out/m_seam.json 2> gpurun_out/m_seam.err      # the asynchronous seam: pinned slots -> HBM, 4096 records
-python tools/bench_configs.py --config 12 --threads 16 --host-out --frames 2048 > gpurun_out/m_seam_host.json 2> gpurun_out/m_seam_host.err   # ... pixels back into pinned slots
-python tools/bench_configs.py --config 13 > gpurun_out/m_wide.json 2> gpurun_out/m_wide.err                  # every block through the int64 kernel
-python tools/bench_configs.py --config 13 --wide-mode dqt16 > gpurun_out/m_wide_dqt16.json 2> gpurun_out/m_wide_dqt16.err
-python tools/bench_configs.py --config 14 > gpurun_out/m_fixup.json 2> gpurun_out/m_fixup.err                 # every block through the fix-up list (adversarial)
+python tools/bench_configs.py --config 7 > $OUT/m_c7.json 2> $OUT/m_c7.err                       # fused 4:4:4 against its three-launch composition
+python tools/bench_configs.py --config 2 > $OUT/m_k2.json 2> $OUT/m_k2.err                       # K2 alone
+python tools/bench_configs.py --config 10 > $OUT/m_sub420.json 2> $OUT/m_sub420.err              # subsample_hv2
+python tools/bench_configs.py --config 6 > $OUT/m_c6.json 2> $OUT/m_c6.err                       # host-buffer boundary (PCIe-inclusive)
+python tools/bench_configs.py --config 8 > $OUT/m_c5_files.json 2> $OUT/m_c5_files.err           # config 5 to files, host coder
+python tools/bench_configs.py --config 8 --gpu-entropy > $OUT/m_c5_files_gpu_entropy.json 2> $OUT/m_c5g.err
+python tools/bench_configs.py --config 9 > $OUT/m_huffman_gpu.json 2> $OUT/m_huffman_gpu.err      # GPU Huffman coder alone
+python tools/bench_configs.py --config 12 --threads 16 > $OUT/m_seam.json 2> $OUT/m_seam.err      # the asynchronous seam: pinned slots -> HBM, 4096 records
+python tools/bench_configs.py --config 12 --threads 16 --host-out --frames 2048 > $OUT/m_seam_host.json 2> $OUT/m_seam_host.err   # ... pixels back into pinned slots
+python tools/bench_configs.py --config 13 > $OUT/m_wide.json 2> $OUT/m_wide.err                  # every block through the int64 kernel
+python tools/bench_configs.py --config 13 --wide-mode dqt16 > $OUT/m_wide_dqt16.json 2> $OUT/m_wide_dqt16.err
+python tools/bench_configs.py --config 14 > $OUT/m_fixup.json 2> $OUT/m_fixup.err                 # every block through the fix-up list (adversarial)
 echo "configs done"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -o /tmp/mem_ubench3 tools/ubench/mem_ubench3.hip 2> /dev/null
-/tmp/mem_ubench3 > gpurun_out/m_mem_ubench3.txt 2>&1 || true
-bash tools/gpu_shape_ceilings.sh > gpurun_out/m_shape_ceilings.txt 2> /dev/null || true
+/tmp/mem_ubench3 > $OUT/m_mem_ubench3.txt 2>&1 || true
+bash tools/gpu_shape_ceilings.sh > $OUT/m_shape_ceilings.txt 2> /dev/null || true
 echo "ceilings done"
-python tools/consolidate_session.py gpurun_out m ${TAG}
+python tools/consolidate_session.py $OUT m ${TAG}
 fi
 if [ "$PART" = "a" ]; then exit 0; fi
 bash tools/gpu_profile.sh ${TAG}_decode

@@ -6,7 +6,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 T=$ROOT/build/variants/libhvc_traffic.so
 [ -f $T ] || { echo "no traffic-only build"; exit 1; }
-B="--steps 40 --no-cpu-baseline --no-others --sustain-seconds 0"
+B="--steps 40"   # (a plain run: the headline step and its roofline figures alone)
 echo "# shipped library, then the traffic-only build (same loads / stores / LDS exchanges, no arithmetic), same box, same session"
 for rep in 1 2; do
   echo -n "K1 shipped      "; python bench.py $B | grep -o '"frac": [0-9.]*\|"kernel_ms": [0-9.]*' | paste - -
