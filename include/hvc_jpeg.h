@@ -551,6 +551,40 @@ HVC_API int hvc_huffman_encode_frames_optimised(hvc_ctx *ctx, const hvc_jpeg_inf
                                                 size_t coef_frame_stride, int n_frames, uint8_t *out, size_t out_cap,
                                                 uint64_t *offsets, hvc_huff_spec *specs, int where);
 
+/* ------------------------------------------------------------------------- */
+/* Files WITH RESTART INTERVALS (an extension: the model's encoder writes none; ITU-T T.81 B.2.4.4, E.1.4).  With an
+ * interval of Ri MCUs (1 .. 65535) the header carries one DRI segment (FF DD 00 04 Ri) directly in front of SOS, nothing
+ * else of its layout changes; in front of every MCU whose index m > 0 is a multiple of Ri the pending bits are padded with
+ * ones to a byte (stuffed like any other byte if it is 0xFF), the two bytes FF D0+((m / Ri - 1) mod 8) follow unstuffed and
+ * every component's DC predictor starts again at 0.  No marker stands behind the last interval.  Ri >= the number of MCUs:
+ * the DRI segment is written, no marker is, and the entropy-coded segment is the plain one.  With optimised tables the
+ * symbol counts are those of the scan as coded with the interval (the DC categories change where a predictor was reset).
+ *
+ * hvc_set_restart_interval(ctx, Ri) makes hvc_jpeg_encode, hvc_jpeg_encode_batch and hvc_jpeg_encode_batch_gpu write such
+ * files; it combines with hvc_set_huffman_tables and hvc_set_encode_arithmetic and is independent of the READER's
+ * hvc_set_restart_markers (which is what reads these files back in full).  0 (the default) leaves every byte as before.
+ * A value outside 0 .. 65535: HVC_E_INVALID_ARG, the setting unchanged. */
+HVC_API int hvc_set_restart_interval(hvc_ctx *ctx, int mcus);
+HVC_API int hvc_get_restart_interval(const hvc_ctx *ctx, int *mcus);
+/* hvc_jpeg_header / hvc_jpeg_header_tables with the interval's DRI segment; specs == NULL: the default tables. */
+HVC_API int hvc_jpeg_header_restart(const hvc_jpeg_info *info, const hvc_huff_spec *specs, int restart_interval,
+                                    uint8_t *out, size_t cap, size_t *len);
+/* hvc_jpeg_entropy_encode / hvc_jpeg_entropy_encode_tables with the interval: the whole file (host, no context).
+ * restart_interval = 0 gives their bytes. */
+HVC_API int hvc_jpeg_entropy_encode_restart(const hvc_jpeg_info *info, const hvc_huff_spec *specs, int restart_interval,
+                                            const int16_t *coefs, uint8_t *out, size_t cap, size_t *out_len);
+/* hvc_huffman_optimal_tables over the symbols of the scan as coded with the interval. */
+HVC_API int hvc_huffman_optimal_tables_restart(const hvc_jpeg_info *info, const int16_t *coefs, int restart_interval,
+                                               hvc_huff_spec out[4]);
+/* hvc_huffman_encode_frames (tables = HVC_HUFF_DEFAULT; specs is not read) or hvc_huffman_encode_frames_optimised
+ * (HVC_HUFF_OPTIMISED; specs receives n_frames x 4 entries) with the interval: the k_*_rst passes of csrc/hvc_huff.hip.
+ * The segments, markers included, equal hvc_jpeg_entropy_encode_restart's.  A frame's unstuffed segment has to stay below
+ * 2^29 bytes with its pad bits counted (HVC_E_TOO_LARGE). */
+HVC_API int hvc_huffman_encode_frames_restart(hvc_ctx *ctx, const hvc_jpeg_info *info, const int16_t *coefs,
+                                              size_t coef_frame_stride, int n_frames, int restart_interval, int tables,
+                                              uint8_t *out, size_t out_cap, uint64_t *offsets, hvc_huff_spec *specs,
+                                              int where);
+
 /* The same for a batch of equally sized frames (BASELINE config 5 end to end): frames[f] is one raw
  * planar frame as `model encode frame` reads it (Frame.input, common/src/frame.ml:72-76: the tight Y, U,
  * V planes back to back); jpegs[f] receives the file (capacity caps[f]; its length in sizes[f]), byte-

@@ -673,3 +673,42 @@ let huffman_encode_frames_optimised =
     (ctx @-> ptr Jpeg_info.t @-> ptr int16_t @-> size_t @-> int @-> ptr char @-> size_t @-> ptr uint64_t
     @-> ptr Huff_spec.t @-> int @-> returning int)
 ;;
+
+(* Restart intervals (DRI + RSTn) in the files written.
+   int hvc_set_restart_interval(ctx, mcus);  int hvc_get_restart_interval(ctx, mcus): 0 off, 1 .. 65535 MCUs *)
+let set_restart_interval = foreign "hvc_set_restart_interval" (ctx @-> int @-> returning int)
+let get_restart_interval = foreign "hvc_get_restart_interval" (ctx @-> ptr int @-> returning int)
+
+(* int hvc_jpeg_header_restart(info, specs[4] or null, restart_interval, out, cap, len) *)
+let jpeg_header_restart =
+  foreign
+    "hvc_jpeg_header_restart"
+    (ptr Jpeg_info.t @-> ptr Huff_spec.t @-> int @-> ptr char @-> size_t @-> ptr size_t @-> returning int)
+;;
+
+(* int hvc_jpeg_entropy_encode_restart(info, specs[4] or null, restart_interval, coefs, out, cap, out_len) *)
+let jpeg_entropy_encode_restart =
+  foreign
+    "hvc_jpeg_entropy_encode_restart"
+    ~release_runtime_lock:true
+    (ptr Jpeg_info.t @-> ptr Huff_spec.t @-> int @-> ptr int16_t @-> ptr char @-> size_t @-> ptr size_t
+    @-> returning int)
+;;
+
+(* int hvc_huffman_optimal_tables_restart(info, coefs, restart_interval, out[4]) *)
+let huffman_optimal_tables_restart =
+  foreign
+    "hvc_huffman_optimal_tables_restart"
+    ~release_runtime_lock:true
+    (ptr Jpeg_info.t @-> ptr int16_t @-> int @-> ptr Huff_spec.t @-> returning int)
+;;
+
+(* int hvc_huffman_encode_frames_restart(ctx, info, coefs, coef_frame_stride, n_frames, restart_interval, tables, out,
+                                         out_cap, offsets, specs, where): tables 0 default (specs null), 1 optimised *)
+let huffman_encode_frames_restart =
+  foreign
+    "hvc_huffman_encode_frames_restart"
+    ~release_runtime_lock:true
+    (ctx @-> ptr Jpeg_info.t @-> ptr int16_t @-> size_t @-> int @-> int @-> int @-> ptr char @-> size_t
+    @-> ptr uint64_t @-> ptr Huff_spec.t @-> int @-> returning int)
+;;

@@ -93,7 +93,8 @@ def long_prefixes(bits, huffval):
     return out
 
 
-def jpeg_optimised_tables(w, h, chroma, qtabs, coefs, table_sets=2, ac_shape=None, stats=None, restart_interval=0):
+def jpeg_optimised_tables(w, h, chroma, qtabs, coefs, table_sets=2, ac_shape=None, stats=None, restart_interval=0,
+                          tables=None):
     """coefs: one frame's coefficient record in the C ABI's layout (int16, component planes back to back,
     zig-zag, DC absolute) for a w x h frame of the given sampling (the encoder's geometry, encoder.ml:437-472)
     -> a baseline JPEG whose Huffman tables are the optimal ones FOR THIS FILE (table_sets = 2: luma / chroma
@@ -101,6 +102,8 @@ def jpeg_optimised_tables(w, h, chroma, qtabs, coefs, table_sets=2, ac_shape=Non
     # (ac_shape / stats: below)
     # restart_interval = Ri > 0: a DRI segment, and behind every Ri MCUs (but the last) the bits are padded with ones to a
     # byte, an RSTm marker (m = 0 ... 7 in turn) follows and the DC predictors start again at zero (ITU-T T.81 E.1.4, B.2.4.4)
+    # tables (None: the fitted ones): per table set [(bits, huffval) for DC, (bits, huffval) for AC], bits a list of 17 with
+    # bits[l] codes of length l, to write and code with in place of the tables fitted to the file
     # chroma may also be a list of (h, v) sampling factors, one per component (1..4 components, any factors 1..4): the
     # DECODER's geometry then (Decoder.init, decoder.ml:294-345: every plane = the frame rounded up to whole MCUs, scaled
     # by the component's share of the largest factors) -- samplings the model's encoder never writes but its decoder reads
@@ -162,6 +165,8 @@ def jpeg_optimised_tables(w, h, chroma, qtabs, coefs, table_sets=2, ac_shape=Non
     # receives, per table set, how many coded AC symbols sit under a prefix beyond the eighth
     specs = [[_many_prefix_lengths(freq[ts][ac]) if (ac and ac_shape == "many_prefixes") else _optimal_lengths(freq[ts][ac])
               for ac in range(2)] for ts in range(n_sets)]
+    if tables is not None:
+        specs = [[(list(tables[ts][ac][0]), list(tables[ts][ac][1])) for ac in range(2)] for ts in range(n_sets)]
     if stats is not None:
         stats["symbols_beyond_eight_prefixes"] = []
         for ts in range(n_sets):

@@ -1,7 +1,8 @@
 """Command line of the path, shaped after the two executables the reference's cram tests drive:
 
-    python -m video_coding_amd model decode frame IN.jpg [OUT.yuv] [-yuv444]      jpeg/bin/model.ml:29-45
-    python -m video_coding_amd model encode frame IN.yuv WxH OUT.jpg [-quality 75] [-chroma 420]
+    python -m video_coding_amd model decode frame IN.jpg [OUT.yuv] [-yuv444] [-restart-markers]
+                                                                                  jpeg/bin/model.ml:29-45
+    python -m video_coding_amd model encode frame IN.yuv WxH OUT.jpg [-quality 75] [-chroma 420] [-restart-interval N]
                                                                                   jpeg/bin/model.ml:86-109
     python -m video_coding_amd oyuv compare {max-difference,mean-difference,mean-square-error,psnr}
                                             {y,u,v,yuv} FILE-1 FILE-2 WxH [-format 420]
@@ -57,6 +58,8 @@ def model_decode_frame(a):
     data = open(a.bits, "rb").read()
     ctx = hvc.Context(a.device)
     try:
+        if a.restart_markers:
+            ctx.set_restart_markers(True)
         if a.yuv444:
             _, frame = ctx.jpeg_decode_yuv444(data)
             out = frame.reshape(-1)
@@ -79,6 +82,7 @@ def model_encode_frame(a):
     try:
         ctx.set_encode_arithmetic(a.arithmetic)
         ctx.set_huffman_tables(a.huffman)
+        ctx.set_restart_interval(a.restart_interval)
         jpg = ctx.jpeg_encode(y, u, v, w, h, a.chroma, a.quality)
     finally:
         ctx.close()
@@ -339,6 +343,8 @@ def parser():
     p.add_argument("bits")
     p.add_argument("yuv", nargs="?")
     p.add_argument("-yuv444", action="store_true", help="4:2:0 file straight to a 4:4:4 frame (fused kernel)")
+    p.add_argument("-restart-markers", dest="restart_markers", action="store_true",
+                   help="honour DRI + RSTn (hvc_set_restart_markers); off: the model's reading, the first interval only")
     p.set_defaults(fn=model_decode_frame)
     enc = model.add_parser("encode").add_subparsers(dest="what", required=True)
     p = enc.add_parser("frame")
@@ -351,6 +357,8 @@ def parser():
                    help="hardcaml: the Hardcaml RTL encoder's DCT and quantiser (hvc_set_encode_arithmetic)")
     p.add_argument("-huffman", default="default", choices=["default", "optimised"],
                    help="optimised: Huffman tables fitted to the file, Annex K.2 (hvc_set_huffman_tables)")
+    p.add_argument("-restart-interval", dest="restart_interval", type=int, default=0,
+                   help="N > 0: a DRI segment and an RSTn marker every N MCUs (hvc_set_restart_interval)")
     p.set_defaults(fn=model_encode_frame)
 
     oyuv = top.add_parser("oyuv").add_subparsers(dest="cmd", required=True)

@@ -291,6 +291,7 @@ void hvc_destroy(hvc_ctx *c) {
     if (c->hd_meta) (void)hipFree(c->hd_meta);
     if (c->hd_bitbuf) (void)hipFree(c->hd_bitbuf);
     if (c->hd_ff) (void)hipFree(c->hd_ff);
+    if (c->hd_ivl) (void)hipFree(c->hd_ivl);
     if (c->hd_out) (void)hipFree(c->hd_out);
     for (int i = 0; i < 3; i++)
         if (c->rd_stream[i]) (void)hipStreamDestroy(c->rd_stream[i]);
@@ -460,6 +461,18 @@ int hvc_set_huffman_tables(hvc_ctx *c, int which) try {
 int hvc_get_huffman_tables(const hvc_ctx *c, int *which) try {
     if (!c || !which) return HVC_E_INVALID_ARG;
     *which = c->huff_tables;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_set_restart_interval(hvc_ctx *c, int mcus) try {
+    if (!c || mcus < 0 || mcus > 65535) return HVC_E_INVALID_ARG;
+    c->restart_interval = mcus;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_get_restart_interval(const hvc_ctx *c, int *mcus) try {
+    if (!c || !mcus) return HVC_E_INVALID_ARG;
+    *mcus = c->restart_interval;
     return HVC_OK;
 } HVC_ABI_CATCH
 

@@ -42,7 +42,7 @@ int hvc_huffman_code_tables(hvc_ctx *c, int table_set, int where, uint32_t *code
 // Geometry + scratch of one call.  `out` / `offsets` are device pointers (the caller's, or NULL = scratch
 // inside ctx, see huffman_scratch_out).
 int huffman_prepare(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *d_coefs, size_t coef_fs, int n_frames, uint8_t *d_out,
-                    size_t out_cap, unsigned long long *d_offsets, hvc::HuffParams &P, bool optimised) {
+                    size_t out_cap, unsigned long long *d_offsets, hvc::HuffParams &P, bool optimised, int restart) {
     int r = hvc_jpeg_encoder_check(info);
     if (r) return r;
     std::memset(&P, 0, sizeof P);
@@ -67,13 +67,20 @@ int huffman_prepare(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *d_coef
     P.tiles_per_frame = tile;
     P.blocks_per_mcu = base;
     const unsigned long long bpf = (unsigned long long)P.mbs_wide * P.mbs_high * base;
-    if (bpf == 0 || bpf * 64ull * 27ull >= (1ull << 32)) return HVC_E_TOO_LARGE; // 32-bit bit offsets per frame
+    // restart intervals: a scan of a single interval (Ri >= MCUs) holds no marker and is the plain segment
+    const unsigned long long mcus = (unsigned long long)P.mbs_wide * P.mbs_high;
+    const unsigned long long n_ivl = restart > 0 && (unsigned long long)restart < mcus ? (mcus + restart - 1) / restart : 0;
+    // 32-bit bit offsets per frame (up to 7 pad bits per interval on top of the fields)
+    if (bpf == 0 || bpf * 64ull * 27ull + 7ull * n_ivl >= (1ull << 32)) return HVC_E_TOO_LARGE;
+    P.restart = n_ivl ? restart : 0;
+    P.n_intervals = (unsigned)n_ivl;
     P.blocks_per_frame = (unsigned)bpf;
     P.n_frames = n_frames;
     P.coefs = d_coefs;
     P.coef_fs = coef_fs;
     // worst case per block: 64 fields of 27 bits (216 bytes); the segment buffer is sized for it
-    const size_t words = ((size_t)bpf * 216 + 3) / 4 + 2;
+    // (+ one pad byte per interval)
+    const size_t words = ((size_t)bpf * 216 + (size_t)n_ivl + 3) / 4 + 2;
     P.bitbuf_words = (words + 15) / 16 * 16;
     P.ff_stride = P.bitbuf_words / 16;
     const size_t nf = (size_t)n_frames;
@@ -103,6 +110,10 @@ int huffman_prepare(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *d_coef
     unsigned long long *scratch_off = (unsigned long long *)(((uintptr_t)(P.frame_ff + nf) + 7) & ~(uintptr_t)7);
     P.bitbuf = (unsigned *)c->hd_bitbuf;
     P.ff = (unsigned *)c->hd_ff;
+    if (n_ivl) {
+        if ((r = grow(c, &c->hd_ivl, &c->hd_ivl_cap, nf * (size_t)n_ivl * sizeof(unsigned)))) return r;
+        P.ivl = (unsigned *)c->hd_ivl;
+    }
     P.out_offsets = d_offsets ? d_offsets : scratch_off;
     P.out = d_out;
     P.out_cap = out_cap;
@@ -121,7 +132,8 @@ int hvc_jpeg_header(const hvc_jpeg_info *info, uint8_t *out, size_t cap, size_t 
 
 // specs != nullptr: each frame's own optimal tables, its four specs into specs[4 f .. 4 f + 3] (host memory)
 static int huffman_encode_frames_impl(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *coefs, size_t coef_fs, int n_frames,
-                                      uint8_t *out, size_t out_cap, uint64_t *offsets, hvc_huff_spec *specs, int where) {
+                                      uint8_t *out, size_t out_cap, uint64_t *offsets, hvc_huff_spec *specs, int where,
+                                      int restart = 0) {
     if (!c || !info || !coefs || !out || !offsets || n_frames < 0 || info->n_comp != 3) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     if (n_frames == 0) {
@@ -138,7 +150,7 @@ static int huffman_encode_frames_impl(hvc_ctx *c, const hvc_jpeg_info *info, con
     unsigned status = 0;
     if (where == HVC_MEM_DEVICE) {
         if (((uintptr_t)coefs & 15) || ((uintptr_t)offsets & 7)) return HVC_E_ALIGNMENT;
-        if ((r = huffman_prepare(c, info, coefs, coef_fs, n_frames, out, out_cap, (unsigned long long *)offsets, P, specs != nullptr))) return r;
+        if ((r = huffman_prepare(c, info, coefs, coef_fs, n_frames, out, out_cap, (unsigned long long *)offsets, P, specs != nullptr, restart))) return r;
         HIPCHK(c, hvc::launch_huffman_encode(P, c->stream));
         HIPCHK(c, hipMemcpyAsync(&status, P.status, sizeof status, hipMemcpyDeviceToHost, c->stream));
         if (specs)
@@ -149,7 +161,7 @@ static int huffman_encode_frames_impl(hvc_ctx *c, const hvc_jpeg_info *info, con
         if ((r = grow(c, &c->d_in, &c->in_cap, cbytes))) return r;
         if ((r = grow(c, &c->hd_out, &c->hd_out_cap, out_cap))) return r;
         if ((r = huffman_prepare(c, info, (const int16_t *)c->d_in, coef_fs, n_frames, (uint8_t *)c->hd_out, out_cap, nullptr, P,
-                                   specs != nullptr)))
+                                   specs != nullptr, restart)))
             return r;
         HIPCHK(c, hipMemcpyAsync(c->d_in, coefs, cbytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hvc::launch_huffman_encode(P, c->stream));
@@ -177,6 +189,16 @@ int hvc_huffman_encode_frames_optimised(hvc_ctx *c, const hvc_jpeg_info *info, c
                                         int where) try {
     if (!specs) return HVC_E_INVALID_ARG;
     return huffman_encode_frames_impl(c, info, coefs, coef_fs, n_frames, out, out_cap, offsets, specs, where);
+} HVC_ABI_CATCH
+
+int hvc_huffman_encode_frames_restart(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *coefs, size_t coef_fs, int n_frames,
+                                      int restart_interval, int tables, uint8_t *out, size_t out_cap, uint64_t *offsets,
+                                      hvc_huff_spec *specs, int where) try {
+    if (restart_interval < 0 || restart_interval > 65535) return HVC_E_INVALID_ARG;
+    if (tables != HVC_HUFF_DEFAULT && tables != HVC_HUFF_OPTIMISED) return HVC_E_INVALID_ARG;
+    if (tables == HVC_HUFF_OPTIMISED && !specs) return HVC_E_INVALID_ARG;
+    return huffman_encode_frames_impl(c, info, coefs, coef_fs, n_frames, out, out_cap, offsets,
+                                      tables == HVC_HUFF_OPTIMISED ? specs : nullptr, where, restart_interval);
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------
@@ -222,6 +244,7 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
     }
     std::vector<uint8_t> header_default;
     const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // each file its own tables (hvc_set_huffman_tables)
+    const int ri = c->restart_interval;                    // DRI + RSTn every ri MCUs (hvc_set_restart_interval)
     if (gpu_entropy && opt) { // per slot: the chunk's specs, pinned
         const size_t spec_bytes = (size_t)C * 4 * sizeof(hvc_huff_spec);
         if (spec_bytes > c->e_specs_bytes) {
@@ -237,7 +260,7 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
         }
     }
     if (gpu_entropy) {
-        hvc::jpeg_header_bytes(&info, header_default);
+        hvc::jpeg_header_bytes(&info, header_default, nullptr, ri);
         // per slot: packed segments on the device (capacity = the coefficient chunk: 2 bytes per sample, twice the raw
         // frames), and (C + 1) offsets + one status word, on the device and pinned
         const size_t off_bytes = ((size_t)C + 2) * sizeof(unsigned long long);
@@ -326,14 +349,14 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
                     }
                 } else if (!gpu_entropy) {
                     const int16_t *cf = (const int16_t *)c->eh_out[slot] + (size_t)(f - k * C) * info.coef_count;
-                    e = opt ? hvc::entropy_encode_optimised(&info, cf, jpegs[f], caps[f], &sizes[f])
-                            : hvc_jpeg_entropy_encode(&info, cf, jpegs[f], caps[f], &sizes[f]);
+                    e = opt ? hvc::entropy_encode_optimised(&info, cf, jpegs[f], caps[f], &sizes[f], ri)
+                            : hvc::entropy_encode_file(&info, nullptr, cf, jpegs[f], caps[f], &sizes[f], ri);
                 } else { // header + the frame's segment + EOI (complete_and_write_eoi, encoder.ml:507-510)
                     const unsigned long long *off = (const unsigned long long *)c->eh_off[slot];
                     const int fi = f - k * C;
                     const size_t seg = (size_t)(off[fi + 1] - off[fi]);
                     std::vector<uint8_t> own; // optimised: the frame's own DHT bodies
-                    if (opt) hvc::jpeg_header_bytes(&info, own, (const hvc_huff_spec *)c->eh_specs[slot] + 4 * fi);
+                    if (opt) hvc::jpeg_header_bytes(&info, own, (const hvc_huff_spec *)c->eh_specs[slot] + 4 * fi, ri);
                     const std::vector<uint8_t> &header = opt ? own : header_default;
                     sizes[f] = header.size() + seg + 2;
                     if (sizes[f] > caps[f]) {
@@ -414,7 +437,7 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
             } else {
                 hvc::HuffParams HP;
                 rc = huffman_prepare(c, &info, (const int16_t *)c->ed_out[slot], info.coef_count, cnt,
-                                     (uint8_t *)c->ed_seg[slot], out_bytes, (unsigned long long *)c->ed_off[slot], HP, opt);
+                                     (uint8_t *)c->ed_seg[slot], out_bytes, (unsigned long long *)c->ed_off[slot], HP, opt, ri);
                 if (rc) break;
                 he = hvc::launch_huffman_encode(HP, compute);
                 if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][2], compute);

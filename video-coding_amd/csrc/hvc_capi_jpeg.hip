@@ -185,7 +185,9 @@ int hvc_jpeg_encode(hvc_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
     const size_t coef_bytes = info.coef_count * sizeof(int16_t);
-    const size_t seg_cap = (info.coef_count / 64) * 243 + 64; // worst case incl. stuffing
+    const int ri = c->restart_interval; // DRI + RSTn every ri MCUs (hvc_set_restart_interval)
+    const size_t n_ivl = ri ? (info.coef_count / 64 + (size_t)ri - 1) / (size_t)ri : 0; // (at most: an MCU holds >= 3 blocks)
+    const size_t seg_cap = (info.coef_count / 64) * 243 + 64 + 4 * n_ivl; // worst case incl. stuffing; a (stuffed) pad byte + marker per interval
     if ((r = grow(c, &c->d_in, &c->in_cap, info.pixel_bytes))) return r;
     if ((r = grow(c, &c->d_out, &c->out_cap, coef_bytes))) return r;
     if ((r = grow(c, &c->hd_out, &c->hd_out_cap, seg_cap))) return r;
@@ -199,7 +201,7 @@ int hvc_jpeg_encode(hvc_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_
     hvc::HuffParams P;
     const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // the frame's own tables (hvc_set_huffman_tables)
     if ((r = huffman_prepare(c, &info, (const int16_t *)c->d_out, info.coef_count, 1, (uint8_t *)c->hd_out, seg_cap, nullptr, P,
-                             opt)))
+                             opt, ri)))
         return r;
     HIPCHK(c, hvc::launch_huffman_encode(P, c->stream));
     unsigned status = 0;
@@ -211,7 +213,7 @@ int hvc_jpeg_encode(hvc_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (status & 1u) return HVC_E_RANGE;
     if ((status & 6u) || off[1] > seg_cap) return HVC_E_TOO_LARGE;
-    hvc::jpeg_header_bytes(&info, header, opt ? specs : nullptr);
+    hvc::jpeg_header_bytes(&info, header, opt ? specs : nullptr, ri);
     *out_len = header.size() + (size_t)off[1] + 2;
     if (!out || *out_len > cap) return HVC_E_INVALID_ARG;
     std::memcpy(out, header.data(), header.size());

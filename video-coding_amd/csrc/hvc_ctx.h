@@ -50,6 +50,7 @@ struct hvc_ctx {
     int arith = HVC_ARITH_MODEL; // hvc_set_arithmetic: the block stage's arithmetic (HARDCAML: k_hardcaml, hvc_hardcaml.hip)
     int enc_arith = HVC_ARITH_MODEL; // hvc_set_encode_arithmetic: the encoder's (HARDCAML: k_hardcaml_encode, hvc_hardcaml.hip)
     int huff_tables = HVC_HUFF_DEFAULT; // hvc_set_huffman_tables: the files' Huffman tables (OPTIMISED: k_huff_hist / k_huff_build)
+    int restart_interval = 0; // hvc_set_restart_interval: MCUs per restart interval of the files written, 0 = no DRI / RSTn
     unsigned *d_fix_count = nullptr; // two counters, used alternately (see k_decode_wide); behind them (+ 8 bytes) the 64-bit
                                      // total of the last call's fix-up blocks over all its launches (hvc_last_wide_blocks)
     // [4], [5]: a second pair of counters, for the luma planes of the fused 4:4:4 path when they run through
@@ -122,6 +123,8 @@ struct hvc_ctx {
     size_t hd_opt_cap = 0;
     void *hd_lens = nullptr, *hd_meta = nullptr, *hd_bitbuf = nullptr, *hd_ff = nullptr, *hd_out = nullptr;
     size_t hd_lens_cap = 0, hd_meta_cap = 0, hd_bitbuf_cap = 0, hd_ff_cap = 0, hd_out_cap = 0;
+    void *hd_ivl = nullptr; // restart intervals: bytes / byte bases per interval (HuffParams ivl)
+    size_t hd_ivl_cap = 0;
     // The asynchronous seam (hvc_capi_async.hip): one batch in flight per slot.  Uploads run on copy_stream, the block stage
     // on `stream`, downloads on down_stream; a slot's device buffers are its own (grown while the slot is free).
     struct Slot {
@@ -356,6 +359,6 @@ inline bool is_420_scan(const hvc_jpeg_info &info) { // Y 2x2, Cb / Cr 1x1 (fram
 
 // hvc_capi_files.hip: geometry + scratch + tables of one GPU Huffman coder call (hvc_huff.hip)
 int huffman_prepare(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *d_coefs, size_t coef_fs, int n_frames, uint8_t *d_out,
-                    size_t out_cap, unsigned long long *d_offsets, hvc::HuffParams &P, bool optimised = false);
+                    size_t out_cap, unsigned long long *d_offsets, hvc::HuffParams &P, bool optimised = false, int restart = 0);
 
 #endif

@@ -1394,7 +1394,7 @@ void entropy_decode_wide2(const uint8_t *const data[2], const size_t n[2], const
 }
 
 // Encoder.write_headers (encoder.ml:371-418) for `info`: SOI .. SOS, appended to o
-void jpeg_header_bytes(const hvc_jpeg_info *info, std::vector<uint8_t> &o, const hvc_huff_spec *specs) {
+void jpeg_header_bytes(const hvc_jpeg_info *info, std::vector<uint8_t> &o, const hvc_huff_spec *specs, int restart) {
     put_marker(o, 0xd8);
     { // write_app0 "Hardcaml JPEG."
         static const char tag[] = "Hardcaml JPEG.";
@@ -1421,6 +1421,11 @@ void jpeg_header_bytes(const hvc_jpeg_info *info, std::vector<uint8_t> &o, const
     }
     const TableView tv = table_view(specs); // DC0, DC1, AC0, AC1
     for (int t = 0; t < 4; t++) write_dht(o, t >> 1, t & 1, tv.bits[t], tv.vals[t]);
+    if (restart > 0) { // DRI (ITU-T T.81 B.2.4.4), the extension of hvc_set_restart_interval: directly in front of SOS
+        put_marker(o, 0xdd);
+        put16(o, 4);
+        put16(o, restart);
+    }
     put_marker(o, 0xda); // write_sos
     put16(o, 2 + 4 + 3 * 2);
     o.push_back(3);
@@ -1736,9 +1741,12 @@ bool specs_are_valid(const hvc_huff_spec *specs) {
 // The scan of encode_seq (encoder.ml:476-505) over one record with the tables et[0 luma, 1 chroma], appended to o.
 // CHECK: the tables may lack a code for a symbol the record holds (optimised / caller's tables): HVC_E_RANGE then.
 // Without it, the default tables have a code for every DC category <= 11 and every AC size <= 10.
+// restart = Ri > 0: in front of every MCU whose index m > 0 is a multiple of Ri the bits are padded with ones to a byte,
+// RST((m / Ri - 1) mod 8) follows unstuffed and the predictors start again at zero (ITU-T T.81 B.2.4.4, E.1.4)
 template <bool CHECK>
-int encode_scan(const hvc_jpeg_info *info, const EncTable *et, const int16_t *coefs, std::vector<uint8_t> &o) {
+int encode_scan(const hvc_jpeg_info *info, const EncTable *et, const int16_t *coefs, std::vector<uint8_t> &o, int restart) {
     int dc_pred[3] = {0, 0, 0};
+    unsigned mcu = 0;
     const hvc_jpeg_component &c0 = info->comp[0];
     const int mbs_wide = c0.decoded_width / (8 * c0.hscale), mbs_high = c0.decoded_height / (8 * c0.vscale);
     int per_mcu = 0;
@@ -1747,7 +1755,14 @@ int encode_scan(const hvc_jpeg_info *info, const EncTable *et, const int16_t *co
     std::vector<uint8_t> scratch((size_t)mbs_wide * (size_t)per_mcu * 216 + 64);
     BitWriter bw(scratch.data());
     for (int my = 0; my < mbs_high; my++) {
-        for (int mx = 0; mx < mbs_wide; mx++)
+        for (int mx = 0; mx < mbs_wide; mx++, mcu++) {
+            if (restart > 0 && mcu && mcu % (unsigned)restart == 0) {
+                bw.pad_with_1s(); // (the pad byte is stuffed like any other; the marker is not)
+                append_stuffed(o, scratch.data(), (size_t)(bw.cur - scratch.data()));
+                bw.cur = scratch.data();
+                put_marker(o, 0xd0 + (int)((mcu / (unsigned)restart - 1u) & 7u));
+                dc_pred[0] = dc_pred[1] = dc_pred[2] = 0;
+            }
             for (int i = 0; i < 3; i++) {
                 const hvc_jpeg_component &c = info->comp[i];
                 const hvc_component &L = info->layout[i];
@@ -1790,6 +1805,7 @@ int encode_scan(const hvc_jpeg_info *info, const EncTable *et, const int16_t *co
                         }
                     }
             }
+        }
         if (my + 1 == mbs_high) bw.pad_with_1s();
         // the row's complete bytes leave; the byte in progress stays in the accumulator
         append_stuffed(o, scratch.data(), (size_t)(bw.cur - scratch.data()));
@@ -1799,13 +1815,15 @@ int encode_scan(const hvc_jpeg_info *info, const EncTable *et, const int16_t *co
 }
 
 // Symbol counts of one record in scan order: cnt[table set][0 DC, 1 AC][symbol].  The same symbols encode_scan codes.
-int count_symbols(const hvc_jpeg_info *info, const int16_t *coefs, uint64_t (*cnt)[2][256]) {
+int count_symbols(const hvc_jpeg_info *info, const int16_t *coefs, uint64_t (*cnt)[2][256], int restart) {
     std::memset(cnt, 0, sizeof(uint64_t) * 2 * 2 * 256);
     int dc_pred[3] = {0, 0, 0};
+    unsigned mcu = 0;
     const hvc_jpeg_component &c0 = info->comp[0];
     const int mbs_wide = c0.decoded_width / (8 * c0.hscale), mbs_high = c0.decoded_height / (8 * c0.vscale);
     for (int my = 0; my < mbs_high; my++)
-        for (int mx = 0; mx < mbs_wide; mx++)
+        for (int mx = 0; mx < mbs_wide; mx++, mcu++) {
+            if (restart > 0 && mcu % (unsigned)restart == 0) dc_pred[0] = dc_pred[1] = dc_pred[2] = 0; // a new interval
             for (int i = 0; i < 3; i++) {
                 const hvc_jpeg_component &c = info->comp[i];
                 const hvc_component &L = info->layout[i];
@@ -1834,6 +1852,7 @@ int count_symbols(const hvc_jpeg_info *info, const int16_t *coefs, uint64_t (*cn
                         if (prev != 63) ac[0]++;
                     }
             }
+        }
     return HVC_OK;
 }
 
@@ -1900,25 +1919,25 @@ int spec_from_counts(const uint64_t *counts, hvc_huff_spec &out) {
 
 namespace hvc {
 // the file's four optimal specs (DC0, DC1, AC0, AC1)
-int optimal_specs(const hvc_jpeg_info *info, const int16_t *coefs, hvc_huff_spec *out) {
+int optimal_specs(const hvc_jpeg_info *info, const int16_t *coefs, hvc_huff_spec *out, int restart) {
     uint64_t cnt[2][2][256];
-    int r = count_symbols(info, coefs, cnt);
+    int r = count_symbols(info, coefs, cnt, restart);
     for (int t = 0; t < 4 && r == HVC_OK; t++) r = spec_from_counts(cnt[t & 1][t >> 1], out[t]);
     return r;
 }
 
 // SOI .. SOS + entropy-coded segment + EOI of one record; specs == nullptr: the default tables
 int entropy_encode_file(const hvc_jpeg_info *info, const hvc_huff_spec *specs, const int16_t *coefs, uint8_t *out, size_t cap,
-                        size_t *out_len) {
+                        size_t *out_len, int restart) {
     std::vector<uint8_t> o;
     o.reserve(info->coef_count / 4 + 1024);
-    jpeg_header_bytes(info, o, specs);
+    jpeg_header_bytes(info, o, specs, restart);
     if (hvc_jpeg_encoder_check(info)) return HVC_E_INVALID_ARG;
     const TableView tv = table_view(specs);
     EncTable et[2];
     build_enc(et[0], tv.bits[0], tv.vals[0], tv.bits[2], tv.vals[2]);
     build_enc(et[1], tv.bits[1], tv.vals[1], tv.bits[3], tv.vals[3]);
-    const int r = specs ? encode_scan<true>(info, et, coefs, o) : encode_scan<false>(info, et, coefs, o);
+    const int r = specs ? encode_scan<true>(info, et, coefs, o, restart) : encode_scan<false>(info, et, coefs, o, restart);
     if (r) return r;
     put_marker(o, 0xd9);
     *out_len = o.size();
@@ -1928,11 +1947,12 @@ int entropy_encode_file(const hvc_jpeg_info *info, const hvc_huff_spec *specs, c
 }
 
 // the file with its own optimal tables (hvc_set_huffman_tables(HVC_HUFF_OPTIMISED) on the host coder)
-int entropy_encode_optimised(const hvc_jpeg_info *info, const int16_t *coefs, uint8_t *out, size_t cap, size_t *out_len) {
+int entropy_encode_optimised(const hvc_jpeg_info *info, const int16_t *coefs, uint8_t *out, size_t cap, size_t *out_len,
+                             int restart) {
     if (hvc_jpeg_encoder_check(info)) return HVC_E_INVALID_ARG;
     hvc_huff_spec specs[4];
-    const int r = optimal_specs(info, coefs, specs);
-    return r ? r : entropy_encode_file(info, specs, coefs, out, cap, out_len);
+    const int r = optimal_specs(info, coefs, specs, restart);
+    return r ? r : entropy_encode_file(info, specs, coefs, out, cap, out_len, restart);
 }
 } // namespace hvc
 
@@ -1968,6 +1988,34 @@ int hvc_jpeg_entropy_encode_tables(const hvc_jpeg_info *info, const hvc_huff_spe
                                    size_t cap, size_t *out_len) try {
     if (!info || !specs || !coefs || !out_len || info->n_comp != 3 || !specs_are_valid(specs)) return HVC_E_INVALID_ARG;
     return hvc::entropy_encode_file(info, specs, coefs, out, cap, out_len);
+} HVC_ABI_CATCH
+
+// The restart-interval extension (hvc_set_restart_interval) without a context.  specs == NULL: the default tables.
+int hvc_jpeg_header_restart(const hvc_jpeg_info *info, const hvc_huff_spec *specs, int restart_interval, uint8_t *out, size_t cap,
+                            size_t *len) try {
+    if (!info || !len || info->n_comp != 3 || restart_interval < 0 || restart_interval > 65535) return HVC_E_INVALID_ARG;
+    if (specs && !specs_are_valid(specs)) return HVC_E_INVALID_ARG;
+    std::vector<uint8_t> o;
+    hvc::jpeg_header_bytes(info, o, specs, restart_interval);
+    *len = o.size();
+    if (!out || cap < o.size()) return HVC_E_INVALID_ARG;
+    std::memcpy(out, o.data(), o.size());
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_jpeg_entropy_encode_restart(const hvc_jpeg_info *info, const hvc_huff_spec *specs, int restart_interval,
+                                    const int16_t *coefs, uint8_t *out, size_t cap, size_t *out_len) try {
+    if (!info || !coefs || !out_len || info->n_comp != 3 || restart_interval < 0 || restart_interval > 65535)
+        return HVC_E_INVALID_ARG;
+    if (specs && !specs_are_valid(specs)) return HVC_E_INVALID_ARG;
+    return hvc::entropy_encode_file(info, specs, coefs, out, cap, out_len, restart_interval);
+} HVC_ABI_CATCH
+
+int hvc_huffman_optimal_tables_restart(const hvc_jpeg_info *info, const int16_t *coefs, int restart_interval,
+                                       hvc_huff_spec out[4]) try {
+    if (!info || !coefs || !out || info->n_comp != 3 || restart_interval < 0 || restart_interval > 65535) return HVC_E_INVALID_ARG;
+    if (hvc_jpeg_encoder_check(info)) return HVC_E_INVALID_ARG;
+    return hvc::optimal_specs(info, coefs, out, restart_interval);
 } HVC_ABI_CATCH
 
 // Ocompare.max_difference / total_difference / square_error (tools/src/ocompare.ml:6-47) of two

@@ -44,21 +44,28 @@ struct HuffParams {
     uint8_t *out;
     unsigned long long out_cap;
     unsigned *status;            // bit 0: value without a code (HVC_E_RANGE); bit 2: out too small
+    // restart intervals (hvc_set_restart_interval; 0 = none, and nothing below is read)
+    int restart;                 // Ri: MCUs per interval
+    unsigned n_intervals;        // per frame: ceil(MCUs / Ri)
+    unsigned *ivl;               // [n_frames][n_intervals]: bytes per interval, then their byte bases in the unstuffed segment
 };
 
 constexpr size_t HUFF_TABLE_WORDS = 2 * (16 + 256); // one frame's two table sets
 
-// P.hist != nullptr: the frames' own tables first (k_huff_hist, k_huff_build), then the coder's passes with them
+// P.hist != nullptr: the frames' own tables first (k_huff_hist, k_huff_build), then the coder's passes with them.
+// P.restart > 0: the *_rst instantiations of the passes, plus k_ivl_bytes and one more scan (hvc_huff.hip)
 hipError_t launch_huffman_encode(const HuffParams &P, hipStream_t s);
 
 // hvc_entropy.cpp
 void default_enc_tables(uint32_t (*out)[16 + 256]);
-int optimal_specs(const ::hvc_jpeg_info *info, const int16_t *coefs, hvc_huff_spec *out);
+// restart: the restart interval in MCUs (hvc_set_restart_interval), 0 = none
+int optimal_specs(const ::hvc_jpeg_info *info, const int16_t *coefs, hvc_huff_spec *out, int restart = 0);
 int entropy_encode_file(const ::hvc_jpeg_info *info, const hvc_huff_spec *specs, const int16_t *coefs, uint8_t *out, size_t cap,
-                        size_t *out_len);
-int entropy_encode_optimised(const ::hvc_jpeg_info *info, const int16_t *coefs, uint8_t *out, size_t cap, size_t *out_len);
+                        size_t *out_len, int restart = 0);
+int entropy_encode_optimised(const ::hvc_jpeg_info *info, const int16_t *coefs, uint8_t *out, size_t cap, size_t *out_len,
+                             int restart = 0);
 // specs: the four DHT bodies (DC0, DC1, AC0, AC1), nullptr = the default tables
-void jpeg_header_bytes(const ::hvc_jpeg_info *info, std::vector<uint8_t> &o, const hvc_huff_spec *specs = nullptr);
+void jpeg_header_bytes(const ::hvc_jpeg_info *info, std::vector<uint8_t> &o, const hvc_huff_spec *specs = nullptr, int restart = 0);
 
 }
 #endif

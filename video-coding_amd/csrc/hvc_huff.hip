@@ -18,6 +18,15 @@
 //   0a k_huff_hist    symbol counts per frame and table set (LDS bins per workgroup, one flush of the non-zero bins)
 //   0b k_huff_build   one wavefront per (frame, table): ITU-T T.81 Annex K.2 -> code table + DHT body per frame
 // and passes 1 and 3 read frame f's tables at tables + f * table_stride.
+// With a restart interval Ri (hvc_set_restart_interval; ITU-T T.81 B.2.4.4, E.1.4) the frame is cut every Ri MCUs: each
+// interval starts on a byte, with no DC predictor, behind an RSTn marker.  The passes above run as their *_rst twins
+// (the same bodies, template <bool RST>; the plain kernels are the RST = false instantiations, unchanged), and
+//   2b k_ivl_bytes    one interval per lane: its bytes = ceil(bits / 8) from the bit offsets of pass 2; a second
+//                     k_scan_u32 gives every interval's byte base in the unstuffed segment
+// follows pass 2.  Pass 3 writes a block at 8 * base[interval] + its offset inside the interval and pads every
+// interval's last block with ones.  The markers never enter the bit buffer (they must not be stuffed): behind pass 4a
+// k_ff_marks adds 2 bytes per interval boundary to the count of the piece that holds the boundary, so the scan leaves
+// room for them, and pass 4d's byte-wise path writes FF Dn when it crosses one.
 #include <vector>
 
 #include "hvc_huff.h"
@@ -33,11 +42,13 @@ struct BlockPos {
     int comp, bx, by;
     bool active;
     unsigned scan;     // index of the block in scan order inside its frame
+    unsigned mcu;      // index of its MCU (read by the RST passes only)
     size_t coef_idx;   // int16 element index of the block's coefficients
     size_t pred_idx;   // ... of the block whose DC is the predictor (valid when has_pred)
     bool has_pred;
 };
 
+template <bool RST>
 __device__ __forceinline__ BlockPos locate_block(const HuffParams &P, int frame, int tile, int lane) {
     BlockPos r;
     int c = 0;
@@ -63,6 +74,9 @@ __device__ __forceinline__ BlockPos locate_block(const HuffParams &P, int frame,
     const int hv = K.h * K.v;
     const int ord = (my * P.mbs_wide + mx) * hv + sy * K.h + sx;
     r.has_pred = ord > 0;
+    r.mcu = (unsigned)(my * P.mbs_wide + mx);
+    // a component has no predictor at its first block of a restart interval
+    if (RST && sy == 0 && sx == 0 && r.mcu % (unsigned)P.restart == 0) r.has_pred = false;
     const int po = r.has_pred ? ord - 1 : 0;
     const int pm = po / hv, pr = po - pm * hv;
     const int psy = pr / K.h, psx = pr - psy * K.h;
@@ -186,12 +200,14 @@ __device__ __forceinline__ void load_block(const HuffParams &P, const BlockPos &
 } // namespace
 
 // pass 1 ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(HT) void k_huff_len(HuffParams P) {
+namespace {
+template <bool RST>
+__device__ __forceinline__ void huff_len_body(const HuffParams &P) {
     __shared__ unsigned tabs[2 * 272];
     const int lane = threadIdx.x, frame = blockIdx.y;
     load_tables(P, frame, tabs);
     __syncthreads();
-    const BlockPos b = locate_block(P, frame, blockIdx.x, lane);
+    const BlockPos b = locate_block<RST>(P, frame, blockIdx.x, lane);
     unsigned w[32];
     load_block(P, b, w);
     const int pred = b.has_pred ? (int)P.coefs[b.pred_idx] : 0;
@@ -204,27 +220,44 @@ __global__ __launch_bounds__(HT) void k_huff_len(HuffParams P) {
         if (err) atomicOr(P.status, 1u);
     }
 }
+} // namespace
+__global__ __launch_bounds__(HT) void k_huff_len(HuffParams P) { huff_len_body<false>(P); }
+__global__ __launch_bounds__(HT) void k_huff_len_rst(HuffParams P) { huff_len_body<true>(P); }
 
 // pass 3 ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(HT) void k_huff_emit(HuffParams P) {
+namespace {
+template <bool RST>
+__device__ __forceinline__ void huff_emit_body(const HuffParams &P) {
     __shared__ unsigned tabs[2 * 272];
     const int lane = threadIdx.x, frame = blockIdx.y;
     load_tables(P, frame, tabs);
     __syncthreads();
-    const BlockPos b = locate_block(P, frame, blockIdx.x, lane);
+    const BlockPos b = locate_block<RST>(P, frame, blockIdx.x, lane);
     if (!b.active) return;
     if ((size_t)((P.frame_bits[frame] + 31u) >> 5) + 1 > P.bitbuf_words) return; // flagged by k_frame_sizes
     unsigned w[32];
     load_block(P, b, w);
     const int pred = b.has_pred ? (int)P.coefs[b.pred_idx] : 0;
     const size_t li = (size_t)frame * P.blocks_per_frame + b.scan;
-    const unsigned bitpos = P.lens[li]; // exclusive offset after pass 2
+    unsigned bitpos = P.lens[li]; // exclusive offset after pass 2
+    const unsigned per_ivl = RST ? (unsigned)P.restart * (unsigned)P.blocks_per_mcu : 0u; // blocks per interval
+    if (RST) { // the interval's byte base (pass 2b) + the block's offset inside its interval
+        const unsigned j = b.mcu / (unsigned)P.restart;
+        bitpos = 8u * P.ivl[(size_t)frame * P.n_intervals + j] + (bitpos - P.lens[li - b.scan + j * per_ivl]);
+    }
     EmitSink s;
     s.tab = tabs + 272 * P.comp[b.comp].table;
     s.init(P.bitbuf + (size_t)frame * P.bitbuf_words, bitpos);
     unsigned err = 0;
     walk_block(w, pred, s, err);
-    if (b.scan == P.blocks_per_frame - 1) {
+    if (RST) {
+        // the last block of every interval pads to a byte with ones (T.81 B.2.4.4 in front of RSTn, flush_with_1s at the
+        // end); the sink's pending bits say where in its byte the block ended (words are whole bytes)
+        if (b.scan + 1 == P.blocks_per_frame || (b.scan + 1) % per_ivl == 0) {
+            const int pad = (8 - (s.n & 7)) & 7;
+            if (pad) s.put((1u << pad) - 1u, pad);
+        }
+    } else if (b.scan == P.blocks_per_frame - 1) {
         // Bitstream_writer.flush_with_1s (bitstream_writer.ml:45-49): pad the last byte with ones
         const unsigned total = P.frame_bits[frame];
         const int pad = (int)((8u - (total & 7u)) & 7u);
@@ -232,16 +265,21 @@ __global__ __launch_bounds__(HT) void k_huff_emit(HuffParams P) {
     }
     s.finish();
 }
+} // namespace
+__global__ __launch_bounds__(HT) void k_huff_emit(HuffParams P) { huff_emit_body<false>(P); }
+__global__ __launch_bounds__(HT) void k_huff_emit_rst(HuffParams P) { huff_emit_body<true>(P); }
 
 // optimised tables, pass 0a: symbol counts per frame and table set.  A workgroup walks every gridDim.x-th tile of its frame
 // and counts into LDS bins; at the end it adds its non-zero bins to the frame's counters (zeroed by hipMemsetAsync).
-__global__ __launch_bounds__(HT) void k_huff_hist(HuffParams P) {
+namespace {
+template <bool RST>
+__device__ __forceinline__ void huff_hist_body(const HuffParams &P) {
     __shared__ unsigned bins[2 * 272];
     const int lane = threadIdx.x, frame = blockIdx.y;
     for (int i = lane; i < 2 * 272; i += HT) bins[i] = 0;
     __syncthreads();
     for (int tile = blockIdx.x; tile < P.tiles_per_frame; tile += gridDim.x) {
-        const BlockPos b = locate_block(P, frame, tile, lane);
+        const BlockPos b = locate_block<RST>(P, frame, tile, lane);
         HistSink s;
         s.bins = bins + 272 * P.comp[b.comp].table; // (one component per tile: the same for the whole workgroup)
         if (b.active) {
@@ -259,6 +297,9 @@ __global__ __launch_bounds__(HT) void k_huff_hist(HuffParams P) {
     for (int i = lane; i < 2 * 272; i += HT)
         if (bins[i]) atomicAdd(h + i, bins[i]);
 }
+} // namespace
+__global__ __launch_bounds__(HT) void k_huff_hist(HuffParams P) { huff_hist_body<false>(P); }
+__global__ __launch_bounds__(HT) void k_huff_hist_rst(HuffParams P) { huff_hist_body<true>(P); }
 
 namespace {
 // the two smallest keys of the wave, (lo, hi) per lane -> every lane
@@ -451,6 +492,45 @@ __global__ void k_frame_sizes(HuffParams P) {
     if ((size_t)((bits + 31u) >> 5) + 1 > P.bitbuf_words) atomicOr(P.status, 2u); // cannot happen: worst case sized
 }
 
+// restart intervals, pass 2b: bytes of every interval from the frame-wide bit offsets of pass 2; one interval per lane
+__global__ __launch_bounds__(256) void k_ivl_bytes(HuffParams P) {
+    const int frame = blockIdx.y;
+    const unsigned j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= P.n_intervals) return;
+    const unsigned per_ivl = (unsigned)P.restart * (unsigned)P.blocks_per_mcu;
+    const unsigned *l = P.lens + (size_t)frame * P.blocks_per_frame;
+    const unsigned first = j * per_ivl, next = first + per_ivl;
+    const unsigned end = next < P.blocks_per_frame ? l[next] : P.frame_bits[frame];
+    P.ivl[(size_t)frame * P.n_intervals + j] = (end - l[first] + 7u) >> 3;
+}
+
+// ... and behind the scan over them (frame_bytes = the sum): the padded segment's bits and pieces
+__global__ void k_frame_sizes_rst(HuffParams P) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= P.n_frames) return;
+    const unsigned bytes = P.frame_bytes[f];
+    P.frame_bits[f] = bytes * 8u; // (huffman_prepare bounds it below 2^32)
+    P.frame_pieces[f] = (bytes + 63u) >> 6;
+    if ((size_t)((bytes + 3u) >> 2) + 1 > P.bitbuf_words) atomicOr(P.status, 2u); // cannot happen: worst case sized
+}
+
+namespace {
+// the first interval j in [1, n) whose byte base is >= key (n when there is none): base[1 ..] is strictly increasing,
+// every interval holding at least one byte
+__device__ __forceinline__ unsigned ivl_lower_bound(const unsigned *base, unsigned n, unsigned key) {
+    unsigned lo = 1, hi = n;
+    while (lo < hi) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (base[mid] < key)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+} // namespace
+
 // pass 4a: number of 0xFF bytes in every 64-byte piece
 __global__ __launch_bounds__(256) void k_ff_count(HuffParams P) {
     const int frame = blockIdx.y;
@@ -474,6 +554,17 @@ __global__ __launch_bounds__(256) void k_ff_count(HuffParams P) {
     P.ff[(size_t)frame * P.ff_stride + piece] = cnt;
 }
 
+// restart intervals, pass 4a: behind k_ff_count (left as it is), + 2 for every interval boundary inside the piece (the
+// marker in front of the interval's first byte)
+__global__ __launch_bounds__(256) void k_ff_marks(HuffParams P) {
+    const int frame = blockIdx.y;
+    const unsigned piece = blockIdx.x * 256u + threadIdx.x;
+    if (piece >= P.frame_pieces[frame]) return;
+    const unsigned *base = P.ivl + (size_t)frame * P.n_intervals;
+    const unsigned marks = ivl_lower_bound(base, P.n_intervals, piece * 64u + 64u) - ivl_lower_bound(base, P.n_intervals, piece * 64u);
+    if (marks) P.ff[(size_t)frame * P.ff_stride + piece] += 2u * marks;
+}
+
 // pass 4c: offsets of the frames' stuffed segments inside the packed output (n_frames is small)
 __global__ void k_frame_offsets(HuffParams P) {
     if (blockIdx.x || threadIdx.x) return;
@@ -486,8 +577,12 @@ __global__ void k_frame_offsets(HuffParams P) {
     if (off > P.out_cap) atomicOr(P.status, 4u);
 }
 
-// pass 4d: copy with stuffing; one 64-byte piece per lane
-__global__ __launch_bounds__(256) void k_stuff_write(HuffParams P) {
+// pass 4d: copy with stuffing; one 64-byte piece per lane.  RST: ff counts the markers' bytes too, so the straight copy
+// is taken by pieces without an 0xFF and without a boundary, and the byte-wise path writes FF Dn in front of every
+// interval's first byte (D0 + (j - 1) mod 8 in front of interval j)
+namespace {
+template <bool RST>
+__device__ __forceinline__ void stuff_write_body(const HuffParams &P) {
     const int frame = blockIdx.y;
     const unsigned piece = blockIdx.x * 256u + threadIdx.x;
     if (piece >= P.frame_pieces[frame]) return;
@@ -515,11 +610,52 @@ __global__ __launch_bounds__(256) void k_stuff_write(HuffParams P) {
         }
         return;
     }
+    const unsigned *base = RST ? P.ivl + (size_t)frame * P.n_intervals : nullptr;
+    unsigned jb = RST ? ivl_lower_bound(base, P.n_intervals, piece * 64u) : 0u;
+    unsigned nextb = RST && jb < P.n_intervals ? base[jb] - piece * 64u : ~0u; // the next boundary, relative to the piece
     for (unsigned i = 0; i < n; i++) {
+        if (RST && i == nextb) {
+            *dst++ = 0xff;
+            *dst++ = (uint8_t)(0xd0u + ((jb - 1u) & 7u));
+            jb++;
+            nextb = jb < P.n_intervals ? base[jb] - piece * 64u : ~0u;
+        }
         const uint8_t v = src[i];
         *dst++ = v;
         if (v == 0xff) *dst++ = 0;
     }
+}
+} // namespace
+__global__ __launch_bounds__(256) void k_stuff_write(HuffParams P) { stuff_write_body<false>(P); }
+__global__ __launch_bounds__(256) void k_stuff_write_rst(HuffParams P) { stuff_write_body<true>(P); }
+
+// the passes with a restart interval (the memsets of status and bitbuf are the caller's, launch_huffman_encode)
+static hipError_t launch_huffman_encode_rst(const HuffParams &P, const dim3 grid, hipStream_t s) {
+    if (P.hist) {
+        const hipError_t e = hipMemsetAsync(P.hist, 0, (size_t)P.n_frames * HUFF_TABLE_WORDS * sizeof(unsigned), s);
+        if (e != hipSuccess) return e;
+        int per = HIST_GROUPS / P.n_frames;
+        per = per < 1 ? 1 : (per > P.tiles_per_frame ? P.tiles_per_frame : per);
+        hipLaunchKernelGGL(k_huff_hist_rst, dim3((unsigned)per, (unsigned)P.n_frames, 1), dim3(HT), 0, s, P);
+        hipLaunchKernelGGL(k_huff_build, dim3(4, (unsigned)P.n_frames, 1), dim3(64), 0, s, P);
+    }
+    hipLaunchKernelGGL(k_huff_len_rst, grid, dim3(HT), 0, s, P);
+    hipLaunchKernelGGL(k_scan_u32, dim3((unsigned)P.n_frames), dim3(1024), 0, s, P.lens, (size_t)P.blocks_per_frame,
+                       (const unsigned *)nullptr, P.blocks_per_frame, P.frame_bits);
+    hipLaunchKernelGGL(k_ivl_bytes, dim3((P.n_intervals + 255u) / 256u, (unsigned)P.n_frames, 1), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_scan_u32, dim3((unsigned)P.n_frames), dim3(1024), 0, s, P.ivl, (size_t)P.n_intervals,
+                       (const unsigned *)nullptr, P.n_intervals, P.frame_bytes);
+    hipLaunchKernelGGL(k_frame_sizes_rst, dim3((unsigned)((P.n_frames + 63) / 64)), dim3(64), 0, s, P);
+    hipLaunchKernelGGL(k_huff_emit_rst, grid, dim3(HT), 0, s, P);
+    const unsigned max_pieces = (unsigned)((P.bitbuf_words * 4 + 63) / 64);
+    const dim3 pgrid((max_pieces + 255u) / 256u, (unsigned)P.n_frames, 1);
+    hipLaunchKernelGGL(k_ff_count, pgrid, dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_ff_marks, pgrid, dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_scan_u32, dim3((unsigned)P.n_frames), dim3(1024), 0, s, P.ff, P.ff_stride,
+                       (const unsigned *)P.frame_pieces, 0u, P.frame_ff);
+    hipLaunchKernelGGL(k_frame_offsets, dim3(1), dim3(1), 0, s, P);
+    hipLaunchKernelGGL(k_stuff_write_rst, pgrid, dim3(256), 0, s, P);
+    return hipGetLastError();
 }
 
 hipError_t launch_huffman_encode(const HuffParams &P, hipStream_t s) {
@@ -529,6 +665,7 @@ hipError_t launch_huffman_encode(const HuffParams &P, hipStream_t s) {
     e = hipMemsetAsync(P.bitbuf, 0, (size_t)P.n_frames * P.bitbuf_words * sizeof(unsigned), s);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)P.tiles_per_frame, (unsigned)P.n_frames, 1);
+    if (P.restart > 0) return launch_huffman_encode_rst(P, grid, s);
     if (P.hist) { // the frames' own tables
         e = hipMemsetAsync(P.hist, 0, (size_t)P.n_frames * HUFF_TABLE_WORDS * sizeof(unsigned), s);
         if (e != hipSuccess) return e;

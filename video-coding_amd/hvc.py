@@ -32,6 +32,8 @@ SYMBOLS = [
     "hvc_dct_rom", "hvc_dct_matrix", "hvc_dct_blocks", "hvc_dct_fixed", "hvc_dct_reference", "hvc_dct_error_search",
     "hvc_set_huffman_tables", "hvc_get_huffman_tables", "hvc_huffman_spec_from_counts", "hvc_huffman_optimal_tables",
     "hvc_jpeg_header_tables", "hvc_jpeg_entropy_encode_tables", "hvc_huffman_encode_frames_optimised",
+    "hvc_set_restart_interval", "hvc_get_restart_interval", "hvc_jpeg_header_restart", "hvc_jpeg_entropy_encode_restart",
+    "hvc_huffman_optimal_tables_restart", "hvc_huffman_encode_frames_restart",
 ]
 HVC_HUFF = {"default": 0, "optimised": 1}  # enum hvc_huff_tables
 HVC_ARITH = {"model": 0, "hardcaml": 1}  # enum hvc_arith
@@ -229,6 +231,12 @@ def lib():
         L.hvc_jpeg_header_tables.argtypes = [ip, hs, vp, sz, C.POINTER(sz)]
         L.hvc_jpeg_entropy_encode_tables.argtypes = [ip, hs, vp, vp, sz, C.POINTER(sz)]
         L.hvc_huffman_encode_frames_optimised.argtypes = [vp, ip, vp, sz, i, vp, sz, vp, hs, i]
+        L.hvc_set_restart_interval.argtypes = [vp, i]
+        L.hvc_get_restart_interval.argtypes = [vp, C.POINTER(i)]
+        L.hvc_jpeg_header_restart.argtypes = [ip, hs, i, vp, sz, C.POINTER(sz)]
+        L.hvc_jpeg_entropy_encode_restart.argtypes = [ip, hs, i, vp, vp, sz, C.POINTER(sz)]
+        L.hvc_huffman_optimal_tables_restart.argtypes = [ip, vp, i, hs]
+        L.hvc_huffman_encode_frames_restart.argtypes = [vp, ip, vp, sz, i, i, i, vp, sz, vp, hs, i]
         L.hvc_jpeg_encode.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, sz, C.POINTER(sz)]
         L.hvc_checksum_records.argtypes = [vp, vp, sz, sz, i, vp, i]
         L.hvc_set_host_cpus.argtypes = [vp, C.c_char_p]
@@ -513,12 +521,16 @@ def huffman_code_tables(table_set, ctx=None):
     return {"dc": dc, "ac": ac}
 
 
-def jpeg_header(info, specs=None):
+def jpeg_header(info, specs=None, restart_interval=0):
     """SOI .. SOS of the file Encoder.write_headers produces for this geometry / quality; specs: four (bits, vals) pairs
-    or HuffSpec (DC0, DC1, AC0, AC1) for the DHT bodies in place of the default tables (hvc_jpeg_header_tables)"""
+    or HuffSpec (DC0, DC1, AC0, AC1) for the DHT bodies in place of the default tables (hvc_jpeg_header_tables);
+    restart_interval: with the DRI segment of that many MCUs in front of SOS (hvc_jpeg_header_restart)"""
     n = C.c_size_t()
     buf = np.empty(4096, dtype=np.uint8)
-    if specs is None:
+    if restart_interval:
+        _chk(lib().hvc_jpeg_header_restart(C.byref(info), None if specs is None else huff_specs(specs), int(restart_interval),
+                                           buf.ctypes.data, buf.size, C.byref(n)), "hvc_jpeg_header_restart")
+    elif specs is None:
         _chk(lib().hvc_jpeg_header(C.byref(info), buf.ctypes.data, buf.size, C.byref(n)), "hvc_jpeg_header")
     else:
         _chk(lib().hvc_jpeg_header_tables(C.byref(info), huff_specs(specs), buf.ctypes.data, buf.size, C.byref(n)),
@@ -535,13 +547,17 @@ def huffman_spec_from_counts(counts):
     return s.to_pair()
 
 
-def huffman_optimal_tables(info, coefs):
+def huffman_optimal_tables(info, coefs, restart_interval=0):
     """the four optimal tables of one frame's coefficient record (hvc_huffman_optimal_tables): [(bits, vals)] DC0, DC1,
-    AC0, AC1"""
+    AC0, AC1; restart_interval: over the symbols of the scan cut every so many MCUs (hvc_huffman_optimal_tables_restart)"""
     coefs = np.ascontiguousarray(coefs, dtype=np.int16)
     assert coefs.size >= info.coef_count
     out = (HuffSpec * 4)()
-    _chk(lib().hvc_huffman_optimal_tables(C.byref(info), coefs.ctypes.data, out), "hvc_huffman_optimal_tables")
+    if restart_interval:
+        _chk(lib().hvc_huffman_optimal_tables_restart(C.byref(info), coefs.ctypes.data, int(restart_interval), out),
+             "hvc_huffman_optimal_tables_restart")
+    else:
+        _chk(lib().hvc_huffman_optimal_tables(C.byref(info), coefs.ctypes.data, out), "hvc_huffman_optimal_tables")
     return [s.to_pair() for s in out]
 
 
@@ -565,15 +581,31 @@ def encoder_pixel_record(info, y, u, v, width, height, chroma):
     return out
 
 
-def jpeg_entropy_encode(info, coefs, specs=None):
+def restart_slack(info, restart_interval):
+    """bytes a restart interval adds to a file at most: 3 per interval (pad byte + marker) and the 6 of DRI"""
+    if not restart_interval:
+        return 0
+    c0 = info.comp[0]
+    mcus = (c0.decoded_width // (8 * max(c0.hscale, 1))) * (c0.decoded_height // (8 * max(c0.vscale, 1)))
+    return 3 * -(-mcus // int(restart_interval)) + 6
+
+
+def jpeg_entropy_encode(info, coefs, specs=None, restart_interval=0):
     """the whole file of one coefficient record; specs: four (bits, vals) pairs or HuffSpec (DC0, DC1, AC0, AC1) in place
-    of the default tables (hvc_jpeg_entropy_encode_tables), "optimised" for the record's own optimal ones"""
+    of the default tables (hvc_jpeg_entropy_encode_tables), "optimised" for the record's own optimal ones;
+    restart_interval: DRI + an RSTn marker every so many MCUs (hvc_jpeg_entropy_encode_restart)"""
     coefs = np.ascontiguousarray(coefs, dtype=np.int16)
     assert coefs.size == info.coef_count
-    cap = 8 * coefs.size + 4096  # 26 bits per coefficient at worst, every byte stuffed
+    cap = 8 * coefs.size + 4096 + restart_slack(info, restart_interval)  # 26 bits per coefficient at worst, every byte stuffed
     out = np.empty(cap, dtype=np.uint8)
     n = C.c_size_t()
-    if specs is None:
+    if restart_interval:
+        if isinstance(specs, str) and specs == "optimised":
+            specs = huffman_optimal_tables(info, coefs, restart_interval)
+        _chk(lib().hvc_jpeg_entropy_encode_restart(C.byref(info), None if specs is None else huff_specs(specs),
+                                                   int(restart_interval), coefs.ctypes.data, out.ctypes.data, cap, C.byref(n)),
+             "hvc_jpeg_entropy_encode_restart")
+    elif specs is None:
         _chk(lib().hvc_jpeg_entropy_encode(C.byref(info), coefs.ctypes.data, out.ctypes.data, cap, C.byref(n)),
              "hvc_jpeg_entropy_encode")
     else:
@@ -725,6 +757,18 @@ class Context:
         jpeg_encode and jpeg_encode_batch (both coders).  Independent of set_encode_arithmetic."""
         _chk(lib().hvc_set_huffman_tables(self._h, HVC_HUFF[which] if isinstance(which, str) else int(which)),
              "hvc_set_huffman_tables")
+
+    def set_restart_interval(self, mcus):
+        """0 (default: no DRI, no RSTn, every byte as before) | 1 .. 65535: the files of jpeg_encode and jpeg_encode_batch
+        (both coders) carry a DRI segment and an RSTn marker every `mcus` MCUs.  Independent of set_huffman_tables,
+        set_encode_arithmetic and the reader's set_restart_markers."""
+        _chk(lib().hvc_set_restart_interval(self._h, int(mcus)), "hvc_set_restart_interval")
+
+    @property
+    def restart_interval(self):
+        v = C.c_int()
+        _chk(lib().hvc_get_restart_interval(self._h, C.byref(v)), "hvc_get_restart_interval")
+        return v.value
 
     @property
     def huffman_tables(self):
@@ -919,7 +963,7 @@ class Context:
     def jpeg_encode(self, y, u, v, width, height, chroma=420, quality=75):
         """Encoder.encode_420/422/444 ~frame ~quality -> jpeg bytes"""
         y, u, v = (np.ascontiguousarray(p, dtype=np.uint8) for p in (y, u, v))
-        cap = 4 * width * height + 65536
+        cap = 4 * width * height + 65536 + self._restart_slack(width, height)
         out = np.empty(cap, dtype=np.uint8)
         n = C.c_size_t()
         _chk(lib().hvc_jpeg_encode(self._h, y.ctypes.data, u.ctypes.data, v.ctypes.data, width, height, chroma, quality,
@@ -952,9 +996,17 @@ class Context:
                                                C.byref(used)), "hvc_jpeg_entropy_decode_gpu")
         return info, out, used.value
 
-    def huffman_encode_frames(self, info, coefs, coef_frame_stride, n_frames, out_cap=None):
+    def _restart_slack(self, width, height):
+        """what the context's restart interval adds to a file of this size at most (see restart_slack)"""
+        ri = self.restart_interval
+        return 3 * -(-(-(-width // 8) * -(-height // 8)) // ri) + 6 if ri else 0
+
+    def huffman_encode_frames(self, info, coefs, coef_frame_stride, n_frames, out_cap=None, restart_interval=0):
         """Encoder back end on the GPU: (list of per-frame entropy-coded segments as bytes).  coefs: host
-        int16 array or device tensor holding n_frames records."""
+        int16 array or device tensor holding n_frames records.  restart_interval: an RSTn marker every so many MCUs
+        (hvc_huffman_encode_frames_restart with the default tables)"""
+        if restart_interval:
+            return self._huffman_encode_frames_restart(info, coefs, coef_frame_stride, n_frames, out_cap, restart_interval, False)[0]
         ca, where = _addr(coefs)
         cap = out_cap or (n_frames * (info.coef_count // 64) * 243 + 4096)
         if where == 1:
@@ -974,9 +1026,38 @@ class Context:
             o, data = offs, out
         return [data[int(o[f]):int(o[f + 1])].tobytes() for f in range(n_frames)]
 
-    def huffman_encode_frames_optimised(self, info, coefs, coef_frame_stride, n_frames, out_cap=None):
+    def _huffman_encode_frames_restart(self, info, coefs, coef_frame_stride, n_frames, out_cap, restart_interval, optimised):
+        """hvc_huffman_encode_frames_restart -> (segments, per-frame specs or None)"""
+        ca, where = _addr(coefs)
+        cap = out_cap or (n_frames * ((info.coef_count // 64) * 243 + restart_slack(info, restart_interval)) + 4096)
+        specs = (HuffSpec * max(4 * n_frames, 1))() if optimised else None
+        tables = HVC_HUFF["optimised" if optimised else "default"]
+        if where == 1:
+            import torch
+            out = torch.empty(cap, dtype=torch.uint8, device="cuda")
+            offs = torch.zeros(n_frames + 1, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            _chk(lib().hvc_huffman_encode_frames_restart(self._h, C.byref(info), ca, coef_frame_stride, n_frames,
+                                                         int(restart_interval), tables, out.data_ptr(), cap, offs.data_ptr(),
+                                                         specs, 1), "hvc_huffman_encode_frames_restart")
+            o = offs.cpu().numpy()
+            data = out[:int(o[-1])].cpu().numpy()
+        else:
+            out = np.empty(cap, dtype=np.uint8)
+            offs = np.zeros(n_frames + 1, dtype=np.uint64)
+            _chk(lib().hvc_huffman_encode_frames_restart(self._h, C.byref(info), ca, coef_frame_stride, n_frames,
+                                                         int(restart_interval), tables, out.ctypes.data, cap, offs.ctypes.data,
+                                                         specs, 0), "hvc_huffman_encode_frames_restart")
+            o, data = offs, out
+        return ([data[int(o[f]):int(o[f + 1])].tobytes() for f in range(n_frames)],
+                [[specs[4 * f + t].to_pair() for t in range(4)] for f in range(n_frames)] if optimised else None)
+
+    def huffman_encode_frames_optimised(self, info, coefs, coef_frame_stride, n_frames, out_cap=None, restart_interval=0):
         """hvc_huffman_encode_frames with each frame's own optimal tables, counted and built on the GPU: (list of per-frame
-        segments as bytes, list of per-frame [(bits, vals)] x 4: DC0, DC1, AC0, AC1)"""
+        segments as bytes, list of per-frame [(bits, vals)] x 4: DC0, DC1, AC0, AC1).  restart_interval: an RSTn marker
+        every so many MCUs, the tables those of the scan so cut (hvc_huffman_encode_frames_restart)"""
+        if restart_interval:
+            return self._huffman_encode_frames_restart(info, coefs, coef_frame_stride, n_frames, out_cap, restart_interval, True)
         ca, where = _addr(coefs)
         cap = out_cap or (n_frames * (info.coef_count // 64) * 243 + 4096)
         specs = (HuffSpec * max(4 * n_frames, 1))()
@@ -1013,7 +1094,7 @@ class Context:
         for a in arrs:
             if a.size < need:
                 raise ValueError("frame shorter than %d bytes" % need)
-        cap = 4 * width * height + 65536
+        cap = 4 * width * height + 65536 + self._restart_slack(width, height)
         outs = [np.empty(cap, dtype=np.uint8) for _ in range(n)]
         fp = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
         op = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
