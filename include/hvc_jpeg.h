@@ -605,6 +605,86 @@ HVC_API int hvc_jpeg_encode_batch_gpu(hvc_ctx *ctx, const uint8_t *const *frames
                                       uint8_t *const *jpegs, const size_t *caps, size_t *sizes,
                                       hvc_batch_stats *stats);
 
+/* ------------------------------------------------------------------------- */
+/* RGB (an extension: the model never upsamples and never converts; csrc/hvc_rgb.hip).  "The RGB image of a file" is
+ *   1. the block stage's decoded planes, as hvc_decode_frames writes them, under whichever arithmetic hvc_set_arithmetic
+ *      names (the colour pass is a pass of its own, so unlike the fused 4:4:4 path it takes the Hardcaml setting as well);
+ *   2. full-size chroma as `oyuv convert ... 444` makes it: Planar_444.supersample_hv2 (4:2:0), supersample_h2 (4:2:2),
+ *      nothing (4:4:4) -- the arithmetic of hvc_upsample420 / hvc_upsample422 -- of the top-left chroma_w x chroma_h window
+ *      of the chroma planes, chroma_w = ceil(width / 2) (4:2:0, 4:2:2), chroma_h = ceil(height / 2) (4:2:0); the last column
+ *      and row of THAT WINDOW are the ones repeated, and the top-left width x height of the result is used.  For even sizes
+ *      this is hvc_decode_frames_yuv444's frame; odd sizes use the one extra chroma column / row the decoded plane holds;
+ *   3. libjpeg's 16-bit fixed-point form of the JFIF matrix (ITU-T T.871), >> arithmetic, cb = Cb - 128, cr = Cr - 128:
+ *          R = clamp(Y + ((  91881 * cr              + 32768) >> 16))
+ *          G = clamp(Y + (( -22554 * cb - 46802 * cr + 32768) >> 16))
+ *          B = clamp(Y + (( 116130 * cb              + 32768) >> 16))              clamp = to 0 .. 255
+ *      and the way back (every output is in 0 .. 255 for every input: no clamp)
+ *          Y  = ( 19595 * R + 38470 * G +  7471 * B               + 32768) >> 16
+ *          Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
+ *          Cr = ( 32768 * R - 27439 * G -  5329 * B + (128 << 16) + 32767) >> 16
+ *      followed by Planar_444.subsample_hv2 (4:2:0) / subsample_h2 (4:2:2) of the full-size Cb and Cr planes (the arithmetic
+ *      of hvc_subsample420 / hvc_subsample422).  A one-component file is grey: R = G = B = Y.
+ * Steps 2 and 3 are one kernel in either direction; the full-size chroma planes exist in registers only.  tools/rgb_reference.py
+ * is the same definition in numpy.  Three components are ALWAYS read as Y, Cb, Cr: no Adobe APP14 transform flag, no CMYK.
+ *
+ * Layouts: HVC_RGB_INTERLEAVED is R G B R G B ..., 3 bytes per pixel ([H, W, 3]); HVC_RGB_PLANAR three width x height planes
+ * R, G, B ([3, H, W]).  rgb_row_stride: bytes per row (>= 3 * width interleaved, >= width planar; 0 = tight); planar planes
+ * are rgb_row_stride * height apart; rgb_frame_stride: bytes from frame to frame (0 = tight).  Bytes between rows and frames
+ * are never written.  `sampling` is HVC_YUV_420 / 422 / 444 or HVC_YUV_400 (luma only: comps[0] alone is read or written);
+ * hvc_yuv_frame_bytes and hvc_yuv_convert keep refusing HVC_YUV_400.  `where`, streams and staging as everywhere else
+ * (HVC_MEM_DEVICE: enqueued on ctx's stream, returns at once; host memory goes through context scratch and the call blocks).
+ * A width, height or n_frames of 0: HVC_OK, nothing written.
+ *
+ * hvc_yuv_to_rgb      steps 2 + 3 on planes that are already there (pixel records of hvc_decode_frames, or raw frames):
+ *                     comps[i].plane_offset / .stride place the planes of frame f at yuv + f * yuv_frame_stride, chroma_w x
+ *                     chroma_h are the valid chroma samples.  HVC_E_INVALID_ARG unless 2 * chroma_w >= width (4:4:4: chroma_w
+ *                     >= width), 2 * chroma_h >= height for 4:2:0 (else chroma_h >= height), every stride holds its window,
+ *                     and (components that name their blocks) the window lies inside blocks_w * 8 x blocks_h * 8.
+ * hvc_rgb_to_yuv      the way back into planes at the offsets and strides of comps (the encoder's padded pixel record, or a
+ *                     raw frame); only the frame's own samples are written, padding stays the caller's.  Keeps the encoder's
+ *                     rule: even width for 4:2:2 and 4:2:0, even height for 4:2:0 (Yuv.assert_is_420 / _422), else
+ *                     HVC_E_INVALID_ARG.
+ * hvc_decode_frames_rgb  coefficient records -> RGB: hvc_decode_frames into context scratch (tight planes; comps' blocks_w,
+ *                     blocks_h, qtab and coef_offset are used, plane_offset / stride ignored), then the colour pass with
+ *                     chroma_w = ceil(width / 2) ...; the planes never leave the GPU.  n_comp is 3 (1 for HVC_YUV_400);
+ *                     the windows must lie inside the decoded planes.  Honours hvc_set_arithmetic and hvc_set_decode_kernel;
+ *                     hvc_last_wide_blocks counts as after hvc_decode_frames.
+ * hvc_jpeg_decode_rgb    hvc_jpeg_decode + colour, one file, host memory: rgb receives the image (rgb_cap >= its bytes).
+ *                     The sampling follows from the RATIOS of the scan's sampling factors: three components, luma twice the
+ *                     chroma both ways -> 4:2:0, in width only -> 4:2:2, all equal -> 4:4:4, one component -> grey.  Anything
+ *                     else (4:1:1, 4:4:0, two or four components): HVC_E_INVALID_ARG, output untouched.  Honours
+ *                     hvc_set_arithmetic, hvc_set_restart_markers and hvc_set_decode_kernel; blocks that go through the int64
+ *                     fix-up and DCs beyond int16 come out as the model's pixels, as in hvc_jpeg_decode.
+ * hvc_jpeg_decode_batch_rgb  a batch of files of one geometry: hvc_jpeg_decode_batch (gpu_reader = 0) or
+ *                     hvc_jpeg_decode_batch_gpu (gpu_reader != 0) with its planes in context scratch, and the colour pass from
+ *                     there to rgb (host or device) on the same stream.  The pipelines run unchanged; the colour pass follows a
+ *                     PART of the batch (at most ~4 GB of planes, i.e. some 1300 frames of 1080p), not each ring chunk, so the
+ *                     scratch is a part's planes.  stats: the pipelines' sums over the parts; wall_ms includes the colour pass.
+ * hvc_jpeg_encode_rgb    hvc_jpeg_encode of the converted planes, byte for byte (chroma 420, 422 or 444; a monochrome encoder
+ *                     stays out of scope); honours hvc_set_huffman_tables, hvc_set_restart_interval and
+ *                     hvc_set_encode_arithmetic.  The image is uploaded as it is and converted on the GPU.
+ * Parameter lists are the issue's; none was adjusted. */
+enum { HVC_YUV_400 = 400 }; /* luma only; beside HVC_YUV_420 / 422 / 444 */
+typedef enum { HVC_RGB_INTERLEAVED = 0, HVC_RGB_PLANAR = 1 } hvc_rgb_layout;
+HVC_API int hvc_yuv_to_rgb(hvc_ctx *ctx, const uint8_t *yuv, size_t yuv_frame_stride, const hvc_component *comps, int sampling,
+                           int width, int height, int chroma_w, int chroma_h, int n_frames, uint8_t *rgb,
+                           size_t rgb_row_stride, size_t rgb_frame_stride, int layout, int where);
+HVC_API int hvc_rgb_to_yuv(hvc_ctx *ctx, const uint8_t *rgb, size_t rgb_row_stride, size_t rgb_frame_stride, int layout,
+                           int width, int height, int sampling, int n_frames, uint8_t *yuv, size_t yuv_frame_stride,
+                           const hvc_component *comps, int where);
+HVC_API int hvc_decode_frames_rgb(hvc_ctx *ctx, const int16_t *coefs, size_t coef_frame_stride, const uint16_t *qtabs,
+                                  int n_qtabs, const hvc_component *comps, int n_comp, int sampling, int n_frames, int width,
+                                  int height, uint8_t *rgb, size_t rgb_row_stride, size_t rgb_frame_stride, int layout,
+                                  int where);
+HVC_API int hvc_jpeg_decode_rgb(hvc_ctx *ctx, const uint8_t *jpeg, size_t n, hvc_jpeg_info *info, uint8_t *rgb,
+                                size_t rgb_cap, size_t rgb_row_stride, int layout);
+HVC_API int hvc_jpeg_decode_batch_rgb(hvc_ctx *ctx, const uint8_t *const *jpegs, const size_t *sizes, int n_frames,
+                                      int threads, int frames_per_chunk, int gpu_reader, uint8_t *rgb,
+                                      size_t rgb_row_stride, size_t rgb_frame_stride, int layout, int where,
+                                      hvc_batch_stats *stats);
+HVC_API int hvc_jpeg_encode_rgb(hvc_ctx *ctx, const uint8_t *rgb, size_t rgb_row_stride, int layout, int width, int height,
+                                int chroma, int quality, uint8_t *out, size_t cap, size_t *out_len);
+
 /* K5 (no counterpart in the reference): what a benchmark or a pipeline produced, said in
  * 64 bits per record without bringing the records back.  For r < n_records
  *     sums[r] = SUM_i (byte_i + 1) * ((2 i + 1) * 0x9E3779B97F4A7C15)   mod 2^64,  i = byte index in record r

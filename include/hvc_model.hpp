@@ -242,6 +242,19 @@ inline Frame decode_a_frame(Ctx &ctx, const std::string &bits) { /* decoder.ml:4
     return d.get_yuv_frame();
 }
 
+/* An extension (the model never converts to RGB): the file's RGB image, width x height x 3 bytes R G B R G B ...
+ * (hvc_jpeg_decode_rgb: full-size chroma as `oyuv convert ... 444` makes it, then the JFIF matrix). */
+inline std::vector<uint8_t> decode_a_frame_rgb(Ctx &ctx, const std::string &bits, int *width = nullptr, int *height = nullptr) {
+    hvc_jpeg_info info = Header::decode(bits).info;
+    std::vector<uint8_t> rgb((size_t)3 * info.width * info.height + 1); /* (+ 1: a frame without a sample still has a pointer) */
+    check(hvc_jpeg_decode_rgb(ctx.get(), reinterpret_cast<const uint8_t *>(bits.data()), bits.size(), &info, rgb.data(), rgb.size(), 0,
+                              HVC_RGB_INTERLEAVED), "Decoder.decode_a_frame_rgb");
+    rgb.resize((size_t)3 * info.width * info.height);
+    if (width) *width = info.width;
+    if (height) *height = info.height;
+    return rgb;
+}
+
 /* List.map ~f:decode_a_frame through the ABI's asynchronous seam -- the compiled twin of the OCaml patch's
  * Decoder.decode_frames_gpu (integration/ocaml/hvc_backend.patch): two slots, each with a pinned coefficient
  * record and a pinned pixel record that grow with the largest frame; while the GPU works on file k (upload, block stage,

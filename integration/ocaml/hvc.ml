@@ -712,3 +712,62 @@ let huffman_encode_frames_restart =
     (ctx @-> ptr Jpeg_info.t @-> ptr int16_t @-> size_t @-> int @-> int @-> int @-> ptr char @-> size_t
     @-> ptr uint64_t @-> ptr Huff_spec.t @-> int @-> returning int)
 ;;
+
+(* RGB (an extension: JFIF colour conversion fused with the chroma resampling; include/hvc_jpeg.h, RGB).
+   sampling 420 | 422 | 444 | 400 (luma only); layout 0 interleaved ([H, W, 3]), 1 planar ([3, H, W]); strides of 0 = tight.
+   int hvc_yuv_to_rgb(ctx, yuv, yuv_frame_stride, comps, sampling, width, height, chroma_w, chroma_h, n_frames, rgb,
+                      rgb_row_stride, rgb_frame_stride, layout, where) *)
+let yuv_to_rgb =
+  foreign
+    "hvc_yuv_to_rgb"
+    ~release_runtime_lock:true
+    (ctx @-> ptr char @-> size_t @-> ptr Component.t @-> int @-> int @-> int @-> int @-> int @-> int @-> ptr char
+    @-> size_t @-> size_t @-> int @-> int @-> returning int)
+;;
+
+(* int hvc_rgb_to_yuv(ctx, rgb, rgb_row_stride, rgb_frame_stride, layout, width, height, sampling, n_frames, yuv,
+                      yuv_frame_stride, comps, where) *)
+let rgb_to_yuv =
+  foreign
+    "hvc_rgb_to_yuv"
+    ~release_runtime_lock:true
+    (ctx @-> ptr char @-> size_t @-> size_t @-> int @-> int @-> int @-> int @-> int @-> ptr char @-> size_t
+    @-> ptr Component.t @-> int @-> returning int)
+;;
+
+(* int hvc_decode_frames_rgb(ctx, coefs, coef_frame_stride, qtabs, n_qtabs, comps, n_comp, sampling, n_frames, width,
+                             height, rgb, rgb_row_stride, rgb_frame_stride, layout, where) *)
+let decode_frames_rgb =
+  foreign
+    "hvc_decode_frames_rgb"
+    ~release_runtime_lock:true
+    (ctx @-> ptr int16_t @-> size_t @-> ptr uint16_t @-> int @-> ptr Component.t @-> int @-> int @-> int @-> int
+    @-> int @-> ptr char @-> size_t @-> size_t @-> int @-> int @-> returning int)
+;;
+
+(* int hvc_jpeg_decode_rgb(ctx, jpeg, n, info, rgb, rgb_cap, rgb_row_stride, layout) *)
+let jpeg_decode_rgb =
+  foreign
+    "hvc_jpeg_decode_rgb"
+    ~release_runtime_lock:true
+    (ctx @-> string @-> size_t @-> ptr Jpeg_info.t @-> ptr char @-> size_t @-> size_t @-> int @-> returning int)
+;;
+
+(* int hvc_jpeg_decode_batch_rgb(ctx, jpegs, sizes, n_frames, threads, frames_per_chunk, gpu_reader, rgb, rgb_row_stride,
+                                 rgb_frame_stride, layout, where, stats) *)
+let jpeg_decode_batch_rgb =
+  foreign
+    "hvc_jpeg_decode_batch_rgb"
+    ~release_runtime_lock:true
+    (ctx @-> ptr string @-> ptr size_t @-> int @-> int @-> int @-> int @-> ptr char @-> size_t @-> size_t @-> int
+    @-> int @-> ptr Batch_stats.t @-> returning int)
+;;
+
+(* int hvc_jpeg_encode_rgb(ctx, rgb, rgb_row_stride, layout, width, height, chroma, quality, out, cap, out_len) *)
+let jpeg_encode_rgb =
+  foreign
+    "hvc_jpeg_encode_rgb"
+    ~release_runtime_lock:true
+    (ctx @-> ptr char @-> size_t @-> int @-> int @-> int @-> int @-> int @-> ptr char @-> size_t @-> ptr size_t
+    @-> returning int)
+;;

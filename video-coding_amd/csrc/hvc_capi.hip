@@ -929,6 +929,65 @@ int hvc_decode_frames(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const ui
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------
+// Coefficient records -> RGB images: the block stage into the context's scratch (every plane tight: stride = blocks_w * 8),
+// then the colour pass (hvc_rgb.hip) from there, on the same stream; frames go in parts of at most ~4 GB of planes.
+int hvc_decode_frames_rgb(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs, const hvc_component *comps,
+                          int n_comp, int sampling, int n_frames, int width, int height, uint8_t *rgb, size_t rgb_row_stride,
+                          size_t rgb_frame_stride, int layout, int where) try {
+    RgbImage im;
+    bool nothing = false;
+    if (!coefs || !qtabs || !comps || !rgb) return HVC_E_INVALID_ARG;
+    int r = rgb_check_args(c, sampling, width, height, n_frames, layout, where, rgb_row_stride, rgb_frame_stride, im, nothing);
+    if (r) return r;
+    if (n_comp != (sampling == HVC_YUV_400 ? 1 : 3)) return HVC_E_INVALID_ARG;
+    if ((r = check_qtabs(qtabs, n_qtabs, false))) return r;
+    if (nothing) return HVC_OK;
+    int cw, ch;
+    rgb_chroma_window(sampling, width, height, cw, ch);
+    hvc_component tight[HVC_MAX_COMP];
+    size_t px_fs = 0, coef_span = 0;
+    for (int k = 0; k < n_comp; k++) { // the window inside the decoded planes
+        if (comps[k].blocks_w < 1 || comps[k].blocks_h < 1) return HVC_E_INVALID_ARG;
+        if ((k ? cw : width) > 8 * comps[k].blocks_w || (k ? ch : height) > 8 * comps[k].blocks_h) return HVC_E_INVALID_ARG;
+        tight[k] = comps[k];
+        tight[k].stride = (size_t)comps[k].blocks_w * 8;
+        tight[k].plane_offset = px_fs;
+        px_fs += tight[k].stride * (size_t)comps[k].blocks_h * 8;
+        coef_span = std::max(coef_span, comps[k].coef_offset + (size_t)comps[k].blocks_w * comps[k].blocks_h * 64);
+    }
+    if (n_frames > 1 && coef_fs < coef_span) return HVC_E_INVALID_ARG;
+    if (coef_fs & 7) return HVC_E_ALIGNMENT;
+    if (where == HVC_MEM_DEVICE && ((uintptr_t)coefs & 15)) return HVC_E_ALIGNMENT;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    const int part = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)4 << 30) / px_fs));
+    if ((r = grow(c, &c->d_aux, &c->aux_cap, (size_t)part * px_fs))) return r;
+    const int16_t *d_coefs = coefs;
+    uint8_t *d_rgb = rgb;
+    if (where == HVC_MEM_HOST) {
+        const size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + coef_span) * sizeof(int16_t);
+        if ((r = grow(c, &c->d_in, &c->in_cap, cbytes))) return r;
+        if ((r = grow(c, &c->d_aux2, &c->aux2_cap, rgb_bytes(im, n_frames)))) return r;
+        HIPCHK(c, hipMemcpyAsync(c->d_in, coefs, cbytes, hipMemcpyHostToDevice, c->stream));
+        d_coefs = (const int16_t *)c->d_in;
+        d_rgb = (uint8_t *)c->d_aux2;
+    }
+    for (int f0 = 0; f0 < n_frames; f0 += part) {
+        const int cnt = std::min(part, n_frames - f0);
+        if ((r = decode_frames_impl(c, d_coefs + (size_t)f0 * coef_fs, coef_fs, qtabs, n_qtabs, tight, n_comp, cnt, (uint8_t *)c->d_aux, px_fs,
+                                    HVC_MEM_DEVICE, nullptr, 0)))
+            return r;
+        HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, px_fs, tight, sampling, width, height, cw, ch, cnt,
+                                    d_rgb + (size_t)f0 * im.frame_stride, im, c->stream));
+    }
+    if (where == HVC_MEM_HOST) {
+        HIPCHK(c, rgb_download(d_rgb, rgb, im, n_frames, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+// ---------------------------------------------------------------------------
 // max |model - hardcaml| per block: the model's block stage into device scratch (tight planes), then the twin's compare
 // form reads those pixels back beside its own and writes one byte per block.  Frames go in chunks of at most ~256 MB of
 // model pixels.

@@ -1,4 +1,5 @@
-// hvc_capi_jpeg.hip -- files through the C ABI: one at a time (hvc_jpeg_decode, hvc_jpeg_decode_yuv444, hvc_jpeg_encode) and
+// hvc_capi_jpeg.hip -- files through the C ABI: one at a time (hvc_jpeg_decode, hvc_jpeg_decode_yuv444, hvc_jpeg_decode_rgb,
+// hvc_jpeg_encode, hvc_jpeg_encode_rgb) and
 // BASELINE's configuration 3, the batch pipeline with the Huffman reader on the host (hvc_jpeg_decode_batch).
 #include "hvc_ctx.h"
 
@@ -155,7 +156,96 @@ int hvc_jpeg_decode(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *in
                              info->n_comp, 1, pixels, info->pixel_bytes, HVC_MEM_HOST);
 } HVC_ABI_CATCH
 
+// hvc_jpeg_decode with the colour pass behind the block stage: the planes stay in device scratch (c->d_aux), the image is
+// made in c->d_aux2 and only its bytes come back.
+int hvc_jpeg_decode_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *info, uint8_t *rgb, size_t rgb_cap, size_t rgb_row_stride,
+                        int layout) try {
+    if (!c || !jpeg || !info || !rgb) return HVC_E_INVALID_ARG;
+    hvc::RestartScope honour(c->honour_restart); // (hvc_set_restart_markers; off = the model's behaviour)
+    int r = hvc_jpeg_read_header(jpeg, n, info);
+    if (r) return r;
+    const int sampling = rgb_sampling_of(*info);
+    RgbImage im;
+    if (!sampling || !rgb_image(layout, info->width, info->height, rgb_row_stride, 0, im)) return HVC_E_INVALID_ARG;
+    if (rgb_cap < rgb_bytes(im, 1)) return HVC_E_INVALID_ARG;
+    if (info->width == 0 || info->height == 0 || info->pixel_bytes == 0) // a frame without a sample: the file is still read as the model reads it
+        return hvc_jpeg_entropy_decode(jpeg, n, info, nullptr);
+    int cw, ch;
+    rgb_chroma_window(sampling, info->width, info->height, cw, ch);
+    {
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+        if ((r = grow(c, &c->d_aux, &c->aux_cap, info->pixel_bytes))) return r;
+        if ((r = grow(c, &c->d_aux2, &c->aux2_cap, rgb_bytes(im, 1)))) return r;
+    }
+    auto colour = [&]() -> int { // planes at c->d_aux -> the caller's image
+        HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, info->pixel_bytes, info->layout, sampling, info->width, info->height, cw, ch, 1,
+                                    (uint8_t *)c->d_aux2, im, c->stream));
+        HIPCHK(c, rgb_download((const uint8_t *)c->d_aux2, rgb, im, 1, c->stream));
+        return HVC_OK;
+    };
+    int on_gpu = 0;
+    AfterReader after;
+    auto block_stage = [&]() -> int { // coefficient record on the device, enqueued behind the reader at once
+        DeviceGuard g(c->device);
+        const int e = decode_frames_impl(c, (const int16_t *)c->gd_coefs, info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
+                                         info->n_comp, 1, (uint8_t *)c->d_aux, info->pixel_bytes, HVC_MEM_DEVICE, after.dc_plane, after.dc_fs);
+        return e ? e : colour();
+    };
+    after.enqueue = block_stage;
+    if ((r = single_frame_coefs_on_device(c, jpeg, n, info, &on_gpu, &after))) return r;
+    if (on_gpu) {
+        if (after.speculated) return HVC_OK; // (the reader's one synchronisation covered the download)
+        DeviceGuard g(c->device);
+        if ((r = block_stage())) return r;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return HVC_OK;
+    }
+    std::vector<int16_t> coefs;
+    try {
+        coefs.resize(info->coef_count);
+    } catch (const std::bad_alloc &) {
+        return HVC_E_OUT_OF_MEMORY;
+    }
+    std::vector<hvc::WideDc> wide;
+    std::vector<WideFix> fix;
+    if ((r = hvc::entropy_decode_wide(jpeg, n, info, coefs.data(), wide))) return r;
+    try {
+        for (const hvc::WideDc &w : wide) fix.push_back(WideFix{0, w.block, w.dc});
+    } catch (const std::bad_alloc &) {
+        return HVC_E_OUT_OF_MEMORY;
+    }
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    const size_t cb = info->coef_count * sizeof(int16_t);
+    if ((r = grow(c, &c->d_in, &c->in_cap, cb))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_in, coefs.data(), cb, hipMemcpyHostToDevice, c->stream));
+    const bool prof_saved = c->profiling;
+    c->profiling = false;
+    r = decode_frames_impl(c, (const int16_t *)c->d_in, info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout, info->n_comp, 1,
+                           (uint8_t *)c->d_aux, info->pixel_bytes, HVC_MEM_DEVICE, nullptr, 0, &fix);
+    c->profiling = prof_saved;
+    if (r) return r;
+    if ((r = colour())) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+} HVC_ABI_CATCH
+
 // Encoder.encode_420/422/444 (encoder.ml:512-541)
+
+// The device half of hvc_jpeg_encode / hvc_jpeg_encode_rgb: scratch for one frame (padded planes c->d_in, records c->d_out,
+// segment c->hd_out), and, once the padded planes are at c->d_in, forward block stage, Huffman coder, header + segment + EOI.
+static int encode_scratch(hvc_ctx *c, const hvc_jpeg_info &info, size_t *seg_cap) {
+    const size_t coef_bytes = info.coef_count * sizeof(int16_t);
+    const int ri = c->restart_interval; // DRI + RSTn every ri MCUs (hvc_set_restart_interval)
+    const size_t n_ivl = ri ? (info.coef_count / 64 + (size_t)ri - 1) / (size_t)ri : 0; // (at most: an MCU holds >= 3 blocks)
+    *seg_cap = (info.coef_count / 64) * 243 + 64 + 4 * n_ivl; // worst case incl. stuffing; a (stuffed) pad byte + marker per interval
+    int r;
+    if ((r = grow(c, &c->d_in, &c->in_cap, info.pixel_bytes))) return r;
+    if ((r = grow(c, &c->d_out, &c->out_cap, coef_bytes))) return r;
+    return grow(c, &c->hd_out, &c->hd_out_cap, *seg_cap);
+}
+static int encode_padded_on_device(hvc_ctx *c, const hvc_jpeg_info &info, size_t seg_cap, uint8_t *out, size_t cap, size_t *out_len);
 
 int hvc_jpeg_encode(hvc_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v, int width, int height, int chroma,
                     int quality, uint8_t *out, size_t cap, size_t *out_len) try {
@@ -164,7 +254,7 @@ int hvc_jpeg_encode(hvc_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_
     int r = hvc_jpeg_encoder_layout(width, height, chroma, quality, &info);
     if (r) return r;
     if ((r = hvc_jpeg_encoder_check(&info))) return r; // the model raises for this geometry
-    std::vector<uint8_t> planes, header;
+    std::vector<uint8_t> planes;
     try {
         planes.assign(info.pixel_bytes, 0); // Plane.create is zero-filled (plane.ml:11-17)
     } catch (const std::bad_alloc &) {
@@ -184,14 +274,16 @@ int hvc_jpeg_encode(hvc_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_
     // forward block stage and Huffman coder both on the device; only the entropy-coded segment comes back
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    const size_t coef_bytes = info.coef_count * sizeof(int16_t);
-    const int ri = c->restart_interval; // DRI + RSTn every ri MCUs (hvc_set_restart_interval)
-    const size_t n_ivl = ri ? (info.coef_count / 64 + (size_t)ri - 1) / (size_t)ri : 0; // (at most: an MCU holds >= 3 blocks)
-    const size_t seg_cap = (info.coef_count / 64) * 243 + 64 + 4 * n_ivl; // worst case incl. stuffing; a (stuffed) pad byte + marker per interval
-    if ((r = grow(c, &c->d_in, &c->in_cap, info.pixel_bytes))) return r;
-    if ((r = grow(c, &c->d_out, &c->out_cap, coef_bytes))) return r;
-    if ((r = grow(c, &c->hd_out, &c->hd_out_cap, seg_cap))) return r;
+    size_t seg_cap = 0;
+    if ((r = encode_scratch(c, info, &seg_cap))) return r;
     HIPCHK(c, hipMemcpyAsync(c->d_in, planes.data(), info.pixel_bytes, hipMemcpyHostToDevice, c->stream));
+    return encode_padded_on_device(c, info, seg_cap, out, cap, out_len);
+} HVC_ABI_CATCH
+
+static int encode_padded_on_device(hvc_ctx *c, const hvc_jpeg_info &info, size_t seg_cap, uint8_t *out, size_t cap, size_t *out_len) {
+    int r;
+    std::vector<uint8_t> header;
+    const int ri = c->restart_interval;
     const bool prof_saved = c->profiling;
     c->profiling = false;
     r = hvc_encode_frames(c, (const uint8_t *)c->d_in, info.pixel_bytes, &info.qtabs[0][0], info.n_qtabs, info.layout, 3, 1,
@@ -221,6 +313,31 @@ int hvc_jpeg_encode(hvc_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_
     out[header.size() + off[1]] = 0xff; // complete_and_write_eoi (encoder.ml:507-510)
     out[header.size() + off[1] + 1] = 0xd9;
     return HVC_OK;
+}
+
+// hvc_jpeg_encode of the planes the colour pass makes of an RGB image: the image goes up as it is, k_rgb_to_ycc writes the
+// frame's samples into zeroed padded planes (Plane.create + blit_available), the rest is hvc_jpeg_encode's.
+int hvc_jpeg_encode_rgb(hvc_ctx *c, const uint8_t *rgb, size_t rgb_row_stride, int layout, int width, int height, int chroma, int quality,
+                        uint8_t *out, size_t cap, size_t *out_len) try {
+    if (!c || !rgb || !out_len) return HVC_E_INVALID_ARG;
+    hvc_jpeg_info info;
+    int r = hvc_jpeg_encoder_layout(width, height, chroma, quality, &info);
+    if (r) return r;
+    if ((r = hvc_jpeg_encoder_check(&info))) return r; // the model raises for this geometry
+    if (((chroma == 420 || chroma == 422) && (width & 1)) || (chroma == 420 && (height & 1))) return HVC_E_INVALID_ARG; // Yuv.assert_is_420 / _422
+    RgbImage im;
+    if (!rgb_image(layout, width, height, rgb_row_stride, 0, im)) return HVC_E_INVALID_ARG;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    size_t seg_cap = 0;
+    if ((r = encode_scratch(c, info, &seg_cap))) return r;
+    const size_t in_bytes = rgb_bytes(im, 1);
+    if ((r = grow(c, &c->d_aux2, &c->aux2_cap, in_bytes))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_aux2, rgb, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_in, 0, info.pixel_bytes, c->stream));
+    HIPCHK(c, rgb_to_ycc_device((const uint8_t *)c->d_aux2, im, width, height, chroma, 1, (uint8_t *)c->d_in, info.pixel_bytes, info.layout,
+                                c->stream));
+    return encode_padded_on_device(c, info, seg_cap, out, cap, out_len);
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------
@@ -496,4 +613,62 @@ int hvc_jpeg_decode_batch_yuv444(hvc_ctx *c, const uint8_t *const *jpegs, const 
     if (c && c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path: hvc_set_arithmetic)
     return decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, frames, frame_stride, where, stats,
                              true);
+} HVC_ABI_CATCH
+
+// hvc_jpeg_decode_batch_rgb: the batch pipelines as they are (host reader or GPU reader, whichever `gpu_reader` names), their
+// planes into the context's scratch instead of the caller's memory, and the colour pass (hvc_rgb.hip) from there to where the
+// output goes, on the same stream -- in parts of at most ~4 GB of planes, so that the scratch stays bounded whatever the batch.
+int hvc_jpeg_decode_batch_rgb(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads, int frames_per_chunk,
+                              int gpu_reader, uint8_t *rgb, size_t rgb_row_stride, size_t rgb_frame_stride, int layout, int where,
+                              hvc_batch_stats *stats) try {
+    if (!c || !jpegs || !sizes || !rgb || n_frames < 0) return HVC_E_INVALID_ARG;
+    if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_frames == 0) return HVC_OK;
+    if (!jpegs[0]) return HVC_E_INVALID_ARG;
+    hvc_jpeg_info info0;
+    int r = hvc_jpeg_read_header(jpegs[0], sizes[0], &info0);
+    if (r) return r;
+    const int sampling = rgb_sampling_of(info0);
+    RgbImage im;
+    if (!sampling || !rgb_image(layout, info0.width, info0.height, rgb_row_stride, rgb_frame_stride, im)) return HVC_E_INVALID_ARG;
+    const bool empty = info0.width == 0 || info0.height == 0 || info0.pixel_bytes == 0;
+    int cw, ch;
+    rgb_chroma_window(sampling, info0.width, info0.height, cw, ch);
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    const size_t px_fs = info0.pixel_bytes;
+    const int part = empty ? n_frames : (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)4 << 30) / px_fs));
+    if ((r = grow(c, &c->d_aux, &c->aux_cap, empty ? 8 : (size_t)part * px_fs))) return r;
+    uint8_t *d_rgb = rgb;
+    if (where == HVC_MEM_HOST && !empty) {
+        if ((r = grow(c, &c->d_aux2, &c->aux2_cap, rgb_bytes(im, part)))) return r;
+        d_rgb = (uint8_t *)c->d_aux2;
+    }
+    const auto wall0 = std::chrono::steady_clock::now();
+    for (int f0 = 0; f0 < n_frames; f0 += part) {
+        const int cnt = std::min(part, n_frames - f0);
+        hvc_batch_stats ps;
+        r = gpu_reader ? hvc_jpeg_decode_batch_gpu(c, jpegs + f0, sizes + f0, cnt, threads, frames_per_chunk, (uint8_t *)c->d_aux, px_fs,
+                                                   HVC_MEM_DEVICE, 0, &ps)
+                       : hvc_jpeg_decode_batch(c, jpegs + f0, sizes + f0, cnt, threads, frames_per_chunk, (uint8_t *)c->d_aux, px_fs,
+                                               HVC_MEM_DEVICE, &ps);
+        if (r) return r;
+        if (stats) {
+            stats->entropy_ms_sum += ps.entropy_ms_sum, stats->h2d_ms_sum += ps.h2d_ms_sum, stats->kernel_ms_sum += ps.kernel_ms_sum;
+            stats->d2h_ms_sum += ps.d2h_ms_sum, stats->host_prep_ms_sum += ps.host_prep_ms_sum;
+            stats->chunks += ps.chunks, stats->threads = ps.threads, stats->frames_per_chunk = ps.frames_per_chunk;
+            stats->coef_bytes += ps.coef_bytes;
+        }
+        if (empty) continue;
+        uint8_t *out = where == HVC_MEM_HOST ? d_rgb : d_rgb + (size_t)f0 * im.frame_stride;
+        HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, px_fs, info0.layout, sampling, info0.width, info0.height, cw, ch, cnt, out, im,
+                                    c->stream));
+        if (where == HVC_MEM_HOST) {
+            HIPCHK(c, rgb_download(out, rgb + (size_t)f0 * im.frame_stride, im, cnt, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+    }
+    if (stats) stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    return HVC_OK;
 } HVC_ABI_CATCH

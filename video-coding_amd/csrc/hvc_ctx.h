@@ -4,6 +4,7 @@
 //   hvc_capi_jpeg.hip    files: one at a time (hvc_jpeg_decode, hvc_jpeg_encode) and the batch pipeline with the host reader
 //   hvc_capi_reader.hip  the GPU Huffman reader's entry point and the batch pipeline built on it
 //   hvc_capi_files.hip   the GPU Huffman coder's entry point and the batch pipelines that write files
+//   hvc_rgb.hip          the RGB colour pass (kernels and launches; its entry points live with their families in the files above)
 //   hvc_capi_async.hip   pinned host memory and the slots of the asynchronous seam (hvc_decode_frames_submit / hvc_wait)
 #ifndef HVC_CTX_H
 #define HVC_CTX_H
@@ -356,6 +357,26 @@ inline bool is_420_scan(const hvc_jpeg_info &info) { // Y 2x2, Cb / Cr 1x1 (fram
     return info.n_comp == 3 && info.comp[0].hscale == 2 && info.comp[0].vscale == 2 && info.comp[1].hscale == 1 &&
            info.comp[1].vscale == 1 && info.comp[2].hscale == 1 && info.comp[2].vscale == 1;
 }
+
+// hvc_rgb.hip: the colour pass (k_ycc_to_rgb / k_rgb_to_ycc) on device memory, for the entry points that end or begin with it
+struct RgbImage { // an RGB image as the caller laid it out (hvc_rgb_layout; strides of 0 resolved to tight)
+    int layout = 0;
+    size_t row_bytes = 0, rows = 0; // what a row holds, rows from the first to the last (planar: 3 * height, the planes follow one another)
+    size_t row_stride = 0, frame_stride = 0;
+};
+bool rgb_image(int layout, int width, int height, size_t row_stride, size_t frame_stride, RgbImage &im); // false: a bad layout or stride
+size_t rgb_bytes(const RgbImage &im, int n_frames); // from the first byte of frame 0 to the last byte written
+int rgb_sampling_of(const hvc_jpeg_info &info);     // HVC_YUV_420 / 422 / 444 / 400 by the scan's sampling factors, 0 = none of them
+void rgb_chroma_window(int sampling, int width, int height, int &cw, int &ch); // ceil(width / 2) x ceil(height / 2) for 4:2:0, ...
+hipError_t ycc_to_rgb_device(const uint8_t *d_yuv, size_t yuv_fs, const hvc_component *comps, int sampling, int width, int height, int cw,
+                             int ch, int n_frames, uint8_t *d_rgb, const RgbImage &im, hipStream_t s);
+hipError_t rgb_to_ycc_device(const uint8_t *d_rgb, const RgbImage &im, int width, int height, int sampling, int n_frames, uint8_t *d_yuv,
+                             size_t yuv_fs, const hvc_component *comps, hipStream_t s);
+size_t rgb_yuv_span(const hvc_component *comps, int sampling, int w, int h, int cw, int ch); // bytes of a frame record the pass touches
+// the arguments every RGB entry point shares; HVC_OK with nothing = true: a width, height or n_frames of 0
+int rgb_check_args(const hvc_ctx *c, int sampling, int width, int height, int n_frames, int layout, int where, size_t rgb_row_stride,
+                   size_t rgb_frame_stride, RgbImage &im, bool &nothing);
+hipError_t rgb_download(const uint8_t *d_rgb, uint8_t *h_rgb, const RgbImage &im, int n_frames, hipStream_t s); // only the bytes written
 
 // hvc_capi_files.hip: geometry + scratch + tables of one GPU Huffman coder call (hvc_huff.hip)
 int huffman_prepare(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *d_coefs, size_t coef_fs, int n_frames, uint8_t *d_out,

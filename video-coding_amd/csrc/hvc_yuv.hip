@@ -589,4 +589,82 @@ int hvc_yuv_convert(hvc_ctx *c, const uint8_t *src, int src_format, int src_w, i
     return HVC_OK;
 } HVC_ABI_CATCH
 
+// ---- RGB: the chroma resampling above fused with JFIF colour conversion (k_ycc_to_rgb / k_rgb_to_ycc, hvc_rgb.hip)
+int hvc_yuv_to_rgb(hvc_ctx *c, const uint8_t *yuv, size_t yuv_fs, const hvc_component *comps, int sampling, int width, int height,
+                   int chroma_w, int chroma_h, int n_frames, uint8_t *rgb, size_t rgb_row_stride, size_t rgb_frame_stride, int layout,
+                   int where) try {
+    RgbImage im;
+    bool nothing = false;
+    if (!yuv || !comps || !rgb) return HVC_E_INVALID_ARG;
+    int r = rgb_check_args(c, sampling, width, height, n_frames, layout, where, rgb_row_stride, rgb_frame_stride, im, nothing);
+    if (r) return r;
+    const bool grey = sampling == HVC_YUV_400;
+    int need_cw, need_ch;
+    rgb_chroma_window(sampling, width, height, need_cw, need_ch);
+    if (!grey && (chroma_w < need_cw || chroma_h < need_ch)) return HVC_E_INVALID_ARG; // 2 cw >= width (4:2:0: 2 ch >= height)
+    if (grey) chroma_w = chroma_h = 0;
+    if (nothing) return HVC_OK;
+    // the window inside the planes: rows long enough and, where the components say how many blocks they hold, inside those
+    for (int k = 0; k < (grey ? 1 : 3); k++) {
+        const int pw = k ? chroma_w : width, ph = k ? chroma_h : height;
+        if (comps[k].stride < (size_t)pw) return HVC_E_INVALID_ARG;
+        if (comps[k].blocks_w > 0 && comps[k].blocks_h > 0 && (pw > 8 * comps[k].blocks_w || ph > 8 * comps[k].blocks_h)) return HVC_E_INVALID_ARG;
+    }
+    const size_t span = rgb_yuv_span(comps, sampling, width, height, chroma_w, chroma_h);
+    if (n_frames > 1 && yuv_fs < span) return HVC_E_INVALID_ARG;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    if (where == HVC_MEM_DEVICE) {
+        HIPCHK(c, ycc_to_rgb_device(yuv, yuv_fs, comps, sampling, width, height, chroma_w, chroma_h, n_frames, rgb, im, c->stream));
+        return HVC_OK;
+    }
+    const size_t in_bytes = (size_t)(n_frames - 1) * yuv_fs + span;
+    if ((r = grow(c, &c->d_in, &c->in_cap, in_bytes))) return r;
+    if ((r = grow(c, &c->d_out, &c->out_cap, rgb_bytes(im, n_frames)))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_in, yuv, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_in, yuv_fs, comps, sampling, width, height, chroma_w, chroma_h, n_frames,
+                                (uint8_t *)c->d_out, im, c->stream));
+    HIPCHK(c, rgb_download((const uint8_t *)c->d_out, rgb, im, n_frames, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_rgb_to_yuv(hvc_ctx *c, const uint8_t *rgb, size_t rgb_row_stride, size_t rgb_frame_stride, int layout, int width, int height,
+                   int sampling, int n_frames, uint8_t *yuv, size_t yuv_fs, const hvc_component *comps, int where) try {
+    RgbImage im;
+    bool nothing = false;
+    if (!rgb || !yuv || !comps) return HVC_E_INVALID_ARG;
+    int r = rgb_check_args(c, sampling, width, height, n_frames, layout, where, rgb_row_stride, rgb_frame_stride, im, nothing);
+    if (r) return r;
+    // the encoder's rule (Yuv.assert_is_420 / _422, tools/src/yuv.ml:90-116)
+    if ((sampling == HVC_YUV_420 || sampling == HVC_YUV_422) && (width & 1)) return HVC_E_INVALID_ARG;
+    if (sampling == HVC_YUV_420 && (height & 1)) return HVC_E_INVALID_ARG;
+    if (nothing) return HVC_OK;
+    const bool grey = sampling == HVC_YUV_400;
+    const int cw = sampling == HVC_YUV_444 ? width : width / 2, ch = sampling == HVC_YUV_420 ? height / 2 : height;
+    for (int k = 0; k < (grey ? 1 : 3); k++)
+        if (comps[k].stride < (size_t)(k ? cw : width)) return HVC_E_INVALID_ARG;
+    const size_t span = rgb_yuv_span(comps, sampling, width, height, cw, ch);
+    if (n_frames > 1 && yuv_fs < span) return HVC_E_INVALID_ARG;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    if (where == HVC_MEM_DEVICE) {
+        HIPCHK(c, rgb_to_ycc_device(rgb, im, width, height, sampling, n_frames, yuv, yuv_fs, comps, c->stream));
+        return HVC_OK;
+    }
+    const size_t in_bytes = rgb_bytes(im, n_frames), out_bytes = (size_t)(n_frames - 1) * yuv_fs + span;
+    if ((r = grow(c, &c->d_in, &c->in_cap, in_bytes))) return r;
+    if ((r = grow(c, &c->d_out, &c->out_cap, out_bytes))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_in, rgb, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, rgb_to_ycc_device((const uint8_t *)c->d_in, im, width, height, sampling, n_frames, (uint8_t *)c->d_out, yuv_fs, comps, c->stream));
+    for (int f = 0; f < n_frames; f++) // (only the frame's own samples: padding stays the caller's)
+        for (int k = 0; k < (grey ? 1 : 3); k++) {
+            const size_t at = (size_t)f * yuv_fs + comps[k].plane_offset;
+            HIPCHK(c, hipMemcpy2DAsync(yuv + at, comps[k].stride, (const uint8_t *)c->d_out + at, comps[k].stride, (size_t)(k ? cw : width),
+                                       (size_t)(k ? ch : height), hipMemcpyDeviceToHost, c->stream));
+        }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+} HVC_ABI_CATCH
+
 } // extern "C"

@@ -34,7 +34,11 @@ SYMBOLS = [
     "hvc_jpeg_header_tables", "hvc_jpeg_entropy_encode_tables", "hvc_huffman_encode_frames_optimised",
     "hvc_set_restart_interval", "hvc_get_restart_interval", "hvc_jpeg_header_restart", "hvc_jpeg_entropy_encode_restart",
     "hvc_huffman_optimal_tables_restart", "hvc_huffman_encode_frames_restart",
+    "hvc_yuv_to_rgb", "hvc_rgb_to_yuv", "hvc_decode_frames_rgb", "hvc_jpeg_decode_rgb", "hvc_jpeg_decode_batch_rgb",
+    "hvc_jpeg_encode_rgb",
 ]
+HVC_RGB = {"interleaved": 0, "planar": 1}  # enum hvc_rgb_layout: [H, W, 3] / [3, H, W]
+HVC_YUV_400 = 400   # luma only, beside 420 / 422 / 444
 HVC_HUFF = {"default": 0, "optimised": 1}  # enum hvc_huff_tables
 HVC_ARITH = {"model": 0, "hardcaml": 1}  # enum hvc_arith
 HVC_SLOTS = 4       # enum { HVC_SLOTS }
@@ -238,6 +242,13 @@ def lib():
         L.hvc_huffman_optimal_tables_restart.argtypes = [ip, vp, i, hs]
         L.hvc_huffman_encode_frames_restart.argtypes = [vp, ip, vp, sz, i, i, i, vp, sz, vp, hs, i]
         L.hvc_jpeg_encode.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, sz, C.POINTER(sz)]
+        L.hvc_yuv_to_rgb.argtypes = [vp, vp, sz, C.POINTER(Component), i, i, i, i, i, i, vp, sz, sz, i, i]
+        L.hvc_rgb_to_yuv.argtypes = [vp, vp, sz, sz, i, i, i, i, i, vp, sz, C.POINTER(Component), i]
+        L.hvc_decode_frames_rgb.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, i, i, i, vp, sz, sz, i, i]
+        L.hvc_jpeg_decode_rgb.argtypes = [vp, vp, sz, ip, vp, sz, sz, i]
+        L.hvc_jpeg_decode_batch_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, i, i, vp, sz, sz, i, i,
+                                                C.POINTER(BatchStats)]
+        L.hvc_jpeg_encode_rgb.argtypes = [vp, vp, sz, i, i, i, i, i, vp, sz, C.POINTER(sz)]
         L.hvc_checksum_records.argtypes = [vp, vp, sz, sz, i, vp, i]
         L.hvc_set_host_cpus.argtypes = [vp, C.c_char_p]
         L.hvc_get_host_cpus.argtypes = [vp, C.c_char_p, sz, C.POINTER(i)]
@@ -281,6 +292,20 @@ def kernel_source_id():
     except OSError:
         return None
     return h.hexdigest()[:12]
+
+
+def _rgb_layout(layout):
+    return HVC_RGB[layout] if isinstance(layout, str) else int(layout)
+
+
+def rgb_shape(layout, width, height):
+    """the shape of one tight image: (h, w, 3) interleaved, (3, h, w) planar"""
+    return (3, height, width) if _rgb_layout(layout) == 1 else (height, width, 3)
+
+
+def rgb_chroma_window(sampling, width, height):
+    """the chroma samples the RGB image of a width x height frame reads: ceil halves (include/hvc_jpeg.h, RGB)"""
+    return (width if sampling == 444 else (width + 1) // 2, (height + 1) // 2 if sampling == 420 else height)
 
 
 def _chk(code, what=""):
@@ -968,6 +993,76 @@ class Context:
         n = C.c_size_t()
         _chk(lib().hvc_jpeg_encode(self._h, y.ctypes.data, u.ctypes.data, v.ctypes.data, width, height, chroma, quality,
                                    out.ctypes.data, cap, C.byref(n)), "hvc_jpeg_encode")
+        return out[:n.value].tobytes()
+
+    # -- RGB (JFIF colour conversion fused with the chroma resampling; include/hvc_jpeg.h, RGB) ---------------
+    def yuv_to_rgb(self, yuv, comps, sampling, width, height, rgb, chroma_size=None, n_frames=1, yuv_frame_stride=0,
+                   layout="interleaved", rgb_row_stride=0, rgb_frame_stride=0):
+        """planes that are already there -> RGB (hvc_yuv_to_rgb).  yuv / rgb: numpy arrays or torch CUDA tensors; comps
+        place the planes (plane_offset, stride); sampling 420 | 422 | 444 | 400; chroma_size: the valid chroma samples
+        (default: the ceil halves the image needs)."""
+        ya, w1 = _addr(yuv)
+        ra, w2 = _addr(rgb)
+        assert w1 == w2
+        arr = comps if not isinstance(comps, list) else components(comps)
+        cw, ch = chroma_size or rgb_chroma_window(sampling, width, height)
+        _chk(lib().hvc_yuv_to_rgb(self._h, ya, yuv_frame_stride, arr, sampling, width, height, cw, ch, n_frames, ra,
+                                  rgb_row_stride, rgb_frame_stride, _rgb_layout(layout), w1), "hvc_yuv_to_rgb")
+
+    def rgb_to_yuv(self, rgb, width, height, sampling, yuv, comps, n_frames=1, yuv_frame_stride=0, layout="interleaved",
+                   rgb_row_stride=0, rgb_frame_stride=0):
+        """RGB -> planes at the offsets and strides of comps (hvc_rgb_to_yuv); only the frame's own samples are written"""
+        ra, w1 = _addr(rgb)
+        ya, w2 = _addr(yuv)
+        assert w1 == w2
+        arr = comps if not isinstance(comps, list) else components(comps)
+        _chk(lib().hvc_rgb_to_yuv(self._h, ra, rgb_row_stride, rgb_frame_stride, _rgb_layout(layout), width, height, sampling,
+                                  n_frames, ya, yuv_frame_stride, arr, w1), "hvc_rgb_to_yuv")
+
+    def decode_frames_rgb(self, coefs, coef_frame_stride, qtabs, comps, sampling, n_frames, width, height, rgb,
+                          layout="interleaved", rgb_row_stride=0, rgb_frame_stride=0):
+        """coefficient records -> RGB images: block stage into context scratch, then the colour pass (hvc_decode_frames_rgb)"""
+        ca, w1 = _addr(coefs)
+        ra, w2 = _addr(rgb)
+        assert w1 == w2
+        q = np.ascontiguousarray(qtabs, dtype=np.uint16).reshape(-1, 64)
+        arr = comps if not isinstance(comps, list) else components(comps)
+        _chk(lib().hvc_decode_frames_rgb(self._h, ca, coef_frame_stride, q.ctypes.data, q.shape[0], arr, len(arr), sampling,
+                                         n_frames, width, height, ra, rgb_row_stride, rgb_frame_stride, _rgb_layout(layout), w1),
+             "hvc_decode_frames_rgb")
+
+    def jpeg_decode_rgb(self, data: bytes, layout="interleaved"):
+        """one file -> (info, uint8 [h, w, 3] (interleaved) or [3, h, w] (planar))"""
+        info = jpeg_read_header(data)
+        out = np.zeros(rgb_shape(layout, info.width, info.height), dtype=np.uint8)
+        _chk(lib().hvc_jpeg_decode_rgb(self._h, data, len(data), C.byref(info), out.ctypes.data, out.size, 0,
+                                       _rgb_layout(layout)), "hvc_jpeg_decode_rgb")
+        return info, out
+
+    def jpeg_decode_batch_rgb(self, jpegs, rgb, layout="interleaved", threads=8, frames_per_chunk=0, gpu_entropy=False,
+                              rgb_row_stride=0, rgb_frame_stride=0):
+        """a batch of files of one geometry -> RGB images in rgb (numpy: host, torch CUDA tensor: device), e.g.
+        [n, h, w, 3] / [n, 3, h, w] uint8; gpu_entropy: the Huffman reader on the GPU as well.  Returns BatchStats."""
+        n = len(jpegs)
+        ptrs = (C.c_void_p * max(n, 1))(*[C.cast(C.c_char_p(j), C.c_void_p) for j in jpegs])
+        sizes = (C.c_size_t * max(n, 1))(*[len(j) for j in jpegs])
+        ra, where = _addr(rgb)
+        st = BatchStats()
+        _chk(lib().hvc_jpeg_decode_batch_rgb(self._h, ptrs, sizes, n, threads, frames_per_chunk, 1 if gpu_entropy else 0, ra,
+                                             rgb_row_stride, rgb_frame_stride, _rgb_layout(layout), where, C.byref(st)),
+             "hvc_jpeg_decode_batch_rgb")
+        return st
+
+    def jpeg_encode_rgb(self, rgb, chroma=420, quality=75, layout="interleaved", width=None, height=None):
+        """an RGB image ([h, w, 3] or, planar, [3, h, w]; uint8) -> jpeg bytes: hvc_jpeg_encode of the converted planes"""
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if width is None:
+            height, width = (rgb.shape[1], rgb.shape[2]) if _rgb_layout(layout) == 1 else (rgb.shape[0], rgb.shape[1])
+        cap = 4 * width * height + 65536 + self._restart_slack(width, height)
+        out = np.empty(cap, dtype=np.uint8)
+        n = C.c_size_t()
+        _chk(lib().hvc_jpeg_encode_rgb(self._h, rgb.ctypes.data, 0, _rgb_layout(layout), width, height, chroma, quality,
+                                       out.ctypes.data, cap, C.byref(n)), "hvc_jpeg_encode_rgb")
         return out[:n.value].tobytes()
 
     def jpeg_entropy_decode_gpu(self, jpegs, device=False):
