@@ -612,18 +612,25 @@ static int upload_dcfix(hvc_ctx *c, const std::vector<unsigned> &ids, const std:
     return HVC_OK;
 }
 
+// What DecodeParams, EncodeParams, HardcamlParams and HardcamlEncodeParams share: everything else zero, the geometry from
+// G -- a Layout, or another of these structs
+template <class Params, class Geometry>
+static void fill_geometry(Params &P, const Geometry &G, size_t coef_fs, size_t pixel_fs, int n_frames) {
+    std::memset(&P, 0, sizeof P);
+    P.coef_fs = coef_fs;
+    P.pixel_fs = pixel_fs;
+    P.n_frames = n_frames;
+    P.n_comp = G.n_comp;
+    P.tiles_per_frame = G.tiles_per_frame;
+    for (int i = 0; i < G.n_comp; i++) P.comp[i] = G.comp[i];
+}
+
 // The twin's parameters for the geometry and records of a DecodeParams (hvc_hardcaml.h)
 static hvc::HardcamlParams hardcaml_params(const hvc::DecodeParams &P, const uint16_t *qtabs, int n_qtabs) {
     hvc::HardcamlParams H;
-    std::memset(&H, 0, sizeof H);
+    fill_geometry(H, P, P.coef_fs, P.pixel_fs, P.n_frames);
     H.coefs = P.coefs;
     H.pixels = P.pixels;
-    H.coef_fs = P.coef_fs;
-    H.pixel_fs = P.pixel_fs;
-    H.n_frames = P.n_frames;
-    H.n_comp = P.n_comp;
-    H.tiles_per_frame = P.tiles_per_frame;
-    for (int i = 0; i < P.n_comp; i++) H.comp[i] = P.comp[i];
     hvc::prepare_hardcaml_tables(qtabs, n_qtabs, H.qq);
     H.dc_plane = P.dc_plane;
     H.dc_fs = P.dc_fs;
@@ -632,7 +639,7 @@ static hvc::HardcamlParams hardcaml_params(const hvc::DecodeParams &P, const uin
 
 // qtabs: the call's tables (the twin's form is made from them)
 static int apply_wide_dc(hvc_ctx *c, const hvc::DecodeParams &P, const std::vector<WideFix> &wide, const uint16_t *qtabs,
-                         int n_qtabs) {
+                         int n_qtabs, int arith) {
     std::vector<unsigned> ids;
     std::vector<long long> dcs;
     for (const WideFix &w : wide) {
@@ -653,7 +660,7 @@ static int apply_wide_dc(hvc_ctx *c, const hvc::DecodeParams &P, const std::vect
     if (r) return r;
     hvc::DecodeParams Q = P;
     Q.dc_plane = nullptr; // (the list carries the DC)
-    if (c->arith == HVC_ARITH_HARDCAML) {
+    if (arith == HVC_ARITH_HARDCAML) {
         const hvc::HardcamlParams H = hardcaml_params(Q, qtabs, n_qtabs);
         HIPCHK(c, hvc::launch_hardcaml_dcfix(H, d_count, d_ids, d_dcs, c->stream));
         return HVC_OK;
@@ -740,15 +747,20 @@ static RecordRun record_run(const hvc_component *comps, int n_comp, bool pixels)
 RecordRun pixel_run(const hvc_component *comps, int n_comp) { return record_run(comps, n_comp, true); }
 RecordRun coef_run(const hvc_component *comps, int n_comp) { return record_run(comps, n_comp, false); }
 
+// One stretch of `len` bytes per frame, `first` bytes into records `fs` bytes apart that lie alike at d_base and h_base,
+// frames [f0, f0 + cnt), device -> host: one copy if the stretches touch (or there is one), else one 2D copy
+static hipError_t copy_run_d2h(const uint8_t *d_base, uint8_t *h_base, size_t first, size_t len, size_t fs, int f0, int cnt,
+                               hipStream_t st) {
+    const size_t off = (size_t)f0 * fs + first;
+    if (cnt == 1 || fs == len)
+        return hipMemcpyAsync(h_base + off, d_base + off, (size_t)(cnt - 1) * fs + len, hipMemcpyDeviceToHost, st);
+    return hipMemcpy2DAsync(h_base + off, fs, d_base + off, fs, len, (size_t)cnt, hipMemcpyDeviceToHost, st);
+}
+
 hipError_t download_pixels(const hvc_component *comps, int n_comp, const RecordRun &run, int f0, int cnt, size_t fs,
                            const uint8_t *d_base, uint8_t *h_base, hipStream_t st) {
     if (cnt <= 0) return hipSuccess;
-    if (run.len) {
-        const size_t off = (size_t)f0 * fs + run.first;
-        if (cnt == 1 || fs == run.len)
-            return hipMemcpyAsync(h_base + off, d_base + off, (size_t)(cnt - 1) * fs + run.len, hipMemcpyDeviceToHost, st);
-        return hipMemcpy2DAsync(h_base + off, fs, d_base + off, fs, run.len, (size_t)cnt, hipMemcpyDeviceToHost, st);
-    }
+    if (run.len) return copy_run_d2h(d_base, h_base, run.first, run.len, fs, f0, cnt, st);
     for (int i = 0; i < n_comp; i++) { // every plane by itself: rows of blocks_w * 8 bytes, `stride` apart, all frames' rows
         const hvc_component &k = comps[i];
         const size_t w = (size_t)k.blocks_w * 8, h = (size_t)k.blocks_h * 8;
@@ -764,12 +776,7 @@ hipError_t download_pixels(const hvc_component *comps, int n_comp, const RecordR
 hipError_t download_coefs(const hvc_component *comps, int n_comp, const RecordRun &run, int f0, int cnt, size_t fs,
                           const uint8_t *d_base, uint8_t *h_base, hipStream_t st) {
     if (cnt <= 0) return hipSuccess;
-    if (run.len) {
-        const size_t off = (size_t)f0 * fs + run.first;
-        if (cnt == 1 || fs == run.len)
-            return hipMemcpyAsync(h_base + off, d_base + off, (size_t)(cnt - 1) * fs + run.len, hipMemcpyDeviceToHost, st);
-        return hipMemcpy2DAsync(h_base + off, fs, d_base + off, fs, run.len, (size_t)cnt, hipMemcpyDeviceToHost, st);
-    }
+    if (run.len) return copy_run_d2h(d_base, h_base, run.first, run.len, fs, f0, cnt, st);
     for (int f = f0; f < f0 + cnt; f++)
         for (int i = 0; i < n_comp; i++) {
             const size_t off = (size_t)f * fs + comps[i].coef_offset * sizeof(int16_t);
@@ -791,11 +798,72 @@ static int frames_per_launch_capped(int n_frames, unsigned long long blocks_per_
     return per < 1 ? 1 : per;
 }
 
-// dc_plane (device memory calls only, default kernels only): see hvc::DecodeParams::dc_plane
-// wide (device memory calls only): blocks to recompute with their true DC once the launches are enqueued
+// ---------------------------------------------------------------------------
+// The steps every entry point of the block stage walks after its argument checks
+
+// the fix-up list holds at least `entries` block ids (one per block of a LAUNCH: launches follow one another on the stream,
+// each consumes its own)
+static int reserve_fix_list(hvc_ctx *c, size_t entries) {
+    if (entries <= c->fix_cap) return HVC_OK;
+    void *p = c->d_fix_list;
+    size_t cap = c->fix_cap * sizeof(unsigned);
+    const int r = grow(c, &p, &cap, entries * sizeof(unsigned));
+    c->d_fix_list = (unsigned *)p;
+    c->fix_cap = cap / sizeof(unsigned);
+    return r;
+}
+
+// frames [f0, f0 + cnt) of a batch in launches of `per` frames: launch(first frame, frames, k0, k1), with the event pair
+// around all of them -- k0 goes to the first launch, k1 to the last, the others get none
+template <class Launch>
+static hipError_t for_each_launch(int f0, int cnt, int per, hipEvent_t k0, hipEvent_t k1, Launch launch) {
+    for (int f = f0; f < f0 + cnt; f += per) {
+        const hipError_t e = launch(f, std::min(per, f0 + cnt - f), f == f0 ? k0 : nullptr, f + per >= f0 + cnt ? k1 : nullptr);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// Host memory: the caller's record layout mirrored in c->d_in (in_bytes) / c->d_out (out_bytes); up(f0, cnt) and
+// run(f0, cnt) enqueue on c->stream, down(f0, cnt, stream) on the stream it is given.  Large batches (by their coefficient
+// bytes) go in overlapped parts where the entry point allows it (may_overlap), the others in one piece.
+template <class Up, class Run, class Down>
+static int through_device(hvc_ctx *c, int n_frames, size_t in_bytes, size_t out_bytes, size_t coef_bytes, bool may_overlap, Up up, Run run,
+                          Down down) {
+    int r = grow(c, &c->d_in, &c->in_cap, in_bytes);
+    if (r) return r;
+    if ((r = grow(c, &c->d_out, &c->out_cap, out_bytes))) return r;
+    if (may_overlap && n_frames >= 8 && coef_bytes >= ((size_t)64 << 20)) // see overlapped_parts
+        return overlapped_parts(c, n_frames, up, [&](int, int f0, int cnt) { return run(f0, cnt); }, down);
+    HIPCHK(c, up(0, n_frames));
+    HIPCHK(c, run(0, n_frames));
+    HIPCHK(c, down(0, n_frames, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+}
+
+// comps with every plane tight, one after another: the pixel planes (stride = blocks_w * 8, plane_offset) or the
+// coefficient planes (coef_offset).  Returns the frame record's size -- bytes of pixels, elements of coefficients: 64 per
+// block either way -- and, where asked for, each plane's first block.
+static size_t tight_records(const hvc_component *comps, int n_comp, bool pixels, hvc_component *tight, int *blk0 = nullptr) {
+    size_t at = 0;
+    for (int i = 0; i < n_comp; i++) {
+        tight[i] = comps[i];
+        if (pixels) {
+            tight[i].stride = (size_t)comps[i].blocks_w * 8;
+            tight[i].plane_offset = at;
+        } else {
+            tight[i].coef_offset = at;
+        }
+        if (blk0) blk0[i] = (int)(at / 64);
+        at += (size_t)comps[i].blocks_w * comps[i].blocks_h * 64;
+    }
+    return at;
+}
+
 int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
                        const hvc_component *comps_in, int n_comp_in, int n_frames, uint8_t *pixels, size_t pixel_fs, int where,
-                       const int16_t *dc_plane, size_t dc_fs, const std::vector<WideFix> *wide) {
+                       const DecodeOpts &o) {
     if (!c || n_frames < 0) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     int r = check_qtabs(qtabs, n_qtabs, false);
@@ -816,32 +884,18 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
     const unsigned long long ids_per_frame = (unsigned long long)L.tiles_per_frame * HVC_TILE;
     const int per = frames_per_launch_capped(n_frames, L.blocks_per_frame, ids_per_frame);
     // (a side list of wide DCs names its blocks by ids of the WHOLE batch: the chunked pipelines that make one stay far below this)
-    if (wide && !wide->empty() && (unsigned long long)n_frames * ids_per_frame >= (1ull << 32)) return HVC_E_TOO_LARGE;
+    const bool has_wide = o.wide && !o.wide->empty();
+    if (has_wide && (unsigned long long)n_frames * ids_per_frame >= (1ull << 32)) return HVC_E_TOO_LARGE;
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
 
     // HVC_ARITH_HARDCAML: the RTL twin (hvc_hardcaml.hip) in place of the model's kernels -- exact in int32 for every
     // input, so no fix-up list and no wide kernel
-    const bool twin = c->arith == HVC_ARITH_HARDCAML;
-    // fix-up list: one entry per block of a LAUNCH at most (launches follow one another on the stream, each consumes its own)
-    size_t need = twin ? 0 : (size_t)((unsigned long long)per * ids_per_frame);
-    if (need > c->fix_cap) {
-        void *p = c->d_fix_list;
-        size_t cap = c->fix_cap * sizeof(unsigned);
-        r = grow(c, &p, &cap, need * sizeof(unsigned));
-        c->d_fix_list = (unsigned *)p;
-        c->fix_cap = cap / sizeof(unsigned);
-        if (r) return r;
-    }
+    const bool twin = o.arith == HVC_ARITH_HARDCAML;
+    if ((r = reserve_fix_list(c, twin ? 0 : (size_t)((unsigned long long)per * ids_per_frame)))) return r;
 
     hvc::DecodeParams P;
-    std::memset(&P, 0, sizeof P);
-    P.coef_fs = coef_fs;
-    P.pixel_fs = pixel_fs;
-    P.n_frames = n_frames;
-    P.n_comp = L.n_comp;
-    P.tiles_per_frame = L.tiles_per_frame;
-    for (int i = 0; i < L.n_comp; i++) P.comp[i] = L.comp[i];
+    fill_geometry(P, L, coef_fs, pixel_fs, n_frames);
     prepare_tables(qtabs, n_qtabs, P.qt, P.ethr, P.ethr_packed, P.qpair);
     wide_total_begin(c);
     fix_assign(c, P);
@@ -866,66 +920,53 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
     };
     // frames [f0, f0 + cnt) of the batch at d_coefs / d_pixels, in launches of `per` frames; the event pair brackets the
     // dominant kernel of all of them (and the few-microsecond fix-up kernels in between)
-    auto launch_range = [&](const int16_t *d_coefs, uint8_t *d_pixels, int f0, int cnt, hipEvent_t k0, hipEvent_t k1) -> hipError_t {
-        for (int f = f0; f < f0 + cnt; f += per) {
+    auto launch_range = [&](const int16_t *d_coefs, uint8_t *d_pixels, int f0, int cnt, hipEvent_t k0, hipEvent_t k1) {
+        return for_each_launch(f0, cnt, per, k0, k1, [&](int f, int n, hipEvent_t e0, hipEvent_t e1) {
             hvc::DecodeParams Pk = P;
-            Pk.n_frames = f0 + cnt - f < per ? f0 + cnt - f : per;
+            Pk.n_frames = n;
             Pk.coefs = d_coefs + (size_t)f * coef_fs;
             Pk.pixels = d_pixels + (size_t)f * pixel_fs;
-            if (dc_plane) Pk.dc_plane = dc_plane + (size_t)f * dc_fs;
-            const hipError_t e = launch(Pk, f == f0 ? k0 : nullptr, f + per >= f0 + cnt ? k1 : nullptr);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
+            if (o.dc_plane) Pk.dc_plane = o.dc_plane + (size_t)f * o.dc_fs;
+            return launch(Pk, e0, e1);
+        });
     };
 
     if (where == HVC_MEM_DEVICE) {
         if (((uintptr_t)coefs & 15) || ((uintptr_t)pixels & 7)) return HVC_E_ALIGNMENT;
-        if (dc_plane && P.kernel_sel != 0 && !twin) return HVC_E_INVALID_ARG;
+        if (o.dc_plane && P.kernel_sel != 0 && !twin) return HVC_E_INVALID_ARG;
         P.coefs = coefs;
         P.pixels = pixels;
-        P.dc_plane = dc_plane;
-        P.dc_fs = dc_fs;
-        const bool prof = c->profiling;
+        P.dc_plane = o.dc_plane;
+        P.dc_fs = o.dc_fs;
         const int slot = (int)(c->k_calls % HVC_PROF_RING);
-        HIPCHK(c, launch_range(coefs, pixels, 0, n_frames, prof ? c->k0[slot] : nullptr, prof ? c->k1[slot] : nullptr));
-        if (prof) c->k_calls++;
-        if (wide && !wide->empty()) return apply_wide_dc(c, P, *wide, qtabs, n_qtabs);
+        HIPCHK(c, launch_range(coefs, pixels, 0, n_frames, o.profile ? c->k0[slot] : nullptr, o.profile ? c->k1[slot] : nullptr));
+        if (o.profile) c->k_calls++;
+        if (has_wide) return apply_wide_dc(c, P, *o.wide, qtabs, n_qtabs, o.arith);
         return HVC_OK;
     }
-    if (dc_plane || (wide && !wide->empty())) return HVC_E_INVALID_ARG;
+    if (o.dc_plane || has_wide) return HVC_E_INVALID_ARG;
 
     // host memory: mirror the caller's record layout on the device
-    size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + L.coef_span) * sizeof(int16_t);
-    size_t pbytes = (size_t)(n_frames - 1) * pixel_fs + L.pixel_span;
-    r = grow(c, &c->d_in, &c->in_cap, cbytes);
-    if (r) return r;
-    r = grow(c, &c->d_out, &c->out_cap, pbytes);
-    if (r) return r;
+    const size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + L.coef_span) * sizeof(int16_t);
+    const size_t pbytes = (size_t)(n_frames - 1) * pixel_fs + L.pixel_span;
     // copy back only the pixels the kernels wrote (the caller's padding stays untouched)
     const RecordRun run = pixel_run(comps, n_comp);
-    if (run.len && n_frames >= 8 && cbytes >= ((size_t)64 << 20)) // large batches in the usual form: see overlapped_parts
-        return overlapped_parts(
-            c, n_frames,
-            [&](int f0, int cnt) {
-                return hipMemcpyAsync((int16_t *)c->d_in + (size_t)f0 * coef_fs, coefs + (size_t)f0 * coef_fs,
-                                      ((size_t)(cnt - 1) * coef_fs + L.coef_span) * sizeof(int16_t), hipMemcpyHostToDevice, c->stream);
-            },
-            [&](int, int f0, int cnt) { return launch_range((const int16_t *)c->d_in, (uint8_t *)c->d_out, f0, cnt, nullptr, nullptr); },
-            [&](int f0, int cnt, hipStream_t st) {
-                return download_pixels(comps, n_comp, run, f0, cnt, pixel_fs, (const uint8_t *)c->d_out, pixels, st);
-            });
-    HIPCHK(c, hipMemcpyAsync(c->d_in, coefs, cbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_range((const int16_t *)c->d_in, (uint8_t *)c->d_out, 0, n_frames, nullptr, nullptr));
-    HIPCHK(c, download_pixels(comps, n_comp, run, 0, n_frames, pixel_fs, (const uint8_t *)c->d_out, pixels, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return HVC_OK;
+    return through_device(
+        c, n_frames, cbytes, pbytes, cbytes, run.len != 0, // (overlapped: large batches in the usual form)
+        [&](int f0, int cnt) {
+            return hipMemcpyAsync((int16_t *)c->d_in + (size_t)f0 * coef_fs, coefs + (size_t)f0 * coef_fs,
+                                  ((size_t)(cnt - 1) * coef_fs + L.coef_span) * sizeof(int16_t), hipMemcpyHostToDevice, c->stream);
+        },
+        [&](int f0, int cnt) { return launch_range((const int16_t *)c->d_in, (uint8_t *)c->d_out, f0, cnt, nullptr, nullptr); },
+        [&](int f0, int cnt, hipStream_t st) {
+            return download_pixels(comps, n_comp, run, f0, cnt, pixel_fs, (const uint8_t *)c->d_out, pixels, st);
+        });
 }
 
 int hvc_decode_frames(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
                       const hvc_component *comps, int n_comp, int n_frames, uint8_t *pixels, size_t pixel_fs,
                       int where) try {
-    return decode_frames_impl(c, coefs, coef_fs, qtabs, n_qtabs, comps, n_comp, n_frames, pixels, pixel_fs, where, nullptr, 0);
+    return decode_frames_impl(c, coefs, coef_fs, qtabs, n_qtabs, comps, n_comp, n_frames, pixels, pixel_fs, where, DecodeOpts(c));
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------
@@ -944,17 +985,14 @@ int hvc_decode_frames_rgb(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, cons
     if (nothing) return HVC_OK;
     int cw, ch;
     rgb_chroma_window(sampling, width, height, cw, ch);
-    hvc_component tight[HVC_MAX_COMP];
-    size_t px_fs = 0, coef_span = 0;
+    size_t coef_span = 0;
     for (int k = 0; k < n_comp; k++) { // the window inside the decoded planes
         if (comps[k].blocks_w < 1 || comps[k].blocks_h < 1) return HVC_E_INVALID_ARG;
         if ((k ? cw : width) > 8 * comps[k].blocks_w || (k ? ch : height) > 8 * comps[k].blocks_h) return HVC_E_INVALID_ARG;
-        tight[k] = comps[k];
-        tight[k].stride = (size_t)comps[k].blocks_w * 8;
-        tight[k].plane_offset = px_fs;
-        px_fs += tight[k].stride * (size_t)comps[k].blocks_h * 8;
         coef_span = std::max(coef_span, comps[k].coef_offset + (size_t)comps[k].blocks_w * comps[k].blocks_h * 64);
     }
+    hvc_component tight[HVC_MAX_COMP];
+    const size_t px_fs = tight_records(comps, n_comp, true, tight);
     if (n_frames > 1 && coef_fs < coef_span) return HVC_E_INVALID_ARG;
     if (coef_fs & 7) return HVC_E_ALIGNMENT;
     if (where == HVC_MEM_DEVICE && ((uintptr_t)coefs & 15)) return HVC_E_ALIGNMENT;
@@ -975,7 +1013,7 @@ int hvc_decode_frames_rgb(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, cons
     for (int f0 = 0; f0 < n_frames; f0 += part) {
         const int cnt = std::min(part, n_frames - f0);
         if ((r = decode_frames_impl(c, d_coefs + (size_t)f0 * coef_fs, coef_fs, qtabs, n_qtabs, tight, n_comp, cnt, (uint8_t *)c->d_aux, px_fs,
-                                    HVC_MEM_DEVICE, nullptr, 0)))
+                                    HVC_MEM_DEVICE, DecodeOpts(c))))
             return r;
         HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, px_fs, tight, sampling, width, height, cw, ch, cnt,
                                     d_rgb + (size_t)f0 * im.frame_stride, im, c->stream));
@@ -988,9 +1026,39 @@ int hvc_decode_frames_rgb(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, cons
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------
-// max |model - hardcaml| per block: the model's block stage into device scratch (tight planes), then the twin's compare
-// form reads those pixels back beside its own and writes one byte per block.  Frames go in chunks of at most ~256 MB of
-// model pixels.
+// max |model - twin| per block, both directions: frames go in chunks of at most ~256 MB of the model's output (records of
+// model_fs bytes in c->d_div_px).  Per chunk: model(d_in, cnt) runs the model's block stage on the chunk's input records
+// (an hvc_status), compare(d_in, cnt, d_diff) launches the twin's compare form, which reads the model's output beside its
+// own and writes one byte per block.  Host memory: the input (records in_fs bytes apart, in_span bytes of the last one) is
+// staged in c->d_div_in, the divergence bytes in c->d_div_out.
+template <class Model, class Compare>
+static int divergence_chunks(hvc_ctx *c, const uint8_t *in, size_t in_fs, size_t in_span, size_t model_fs, int n_frames, uint8_t *max_diff,
+                             size_t diff_fs, size_t blocks, int where, Model model, Compare compare) {
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)256 << 20) / model_fs));
+    int r = grow(c, &c->d_div_px, &c->div_px_cap, (size_t)chunk * model_fs);
+    if (r) return r;
+    if (where == HVC_MEM_HOST) {
+        if ((r = grow(c, &c->d_div_in, &c->div_in_cap, (size_t)(chunk - 1) * in_fs + in_span))) return r;
+        if ((r = grow(c, &c->d_div_out, &c->div_out_cap, (size_t)(chunk - 1) * diff_fs + blocks))) return r;
+    }
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int cnt = std::min(chunk, n_frames - f0);
+        const uint8_t *d_in = in + (size_t)f0 * in_fs;
+        uint8_t *d_diff = max_diff + (size_t)f0 * diff_fs;
+        if (where == HVC_MEM_HOST) {
+            HIPCHK(c, hipMemcpyAsync(c->d_div_in, d_in, (size_t)(cnt - 1) * in_fs + in_span, hipMemcpyHostToDevice, c->stream));
+            d_in = (const uint8_t *)c->d_div_in;
+            d_diff = (uint8_t *)c->d_div_out;
+        }
+        if ((r = model(d_in, cnt))) return r;
+        HIPCHK(c, compare(d_in, cnt, d_diff));
+        if (where == HVC_MEM_HOST) HIPCHK(c, copy_run_d2h(d_diff, max_diff + (size_t)f0 * diff_fs, 0, blocks, diff_fs, 0, cnt, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+}
+
+// The decoder's: the model's block stage into tight pixel planes, then k_hardcaml's compare form.
 int hvc_decode_frames_divergence(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
                                  const hvc_component *comps_in, int n_comp_in, int n_frames, uint8_t *max_diff,
                                  size_t diff_fs, int where) try {
@@ -1005,16 +1073,8 @@ int hvc_decode_frames_divergence(hvc_ctx *c, const int16_t *coefs, size_t coef_f
     if (!coefs || !max_diff) return HVC_E_INVALID_ARG;
     // the model's pixels: every plane tight (stride = blocks_w * 8), one after the other
     hvc_component tight[HVC_MAX_COMP];
-    size_t px_fs = 0, blocks = 0;
     int blk0[HVC_MAX_COMP];
-    for (int i = 0; i < n_comp; i++) {
-        tight[i] = kept[i];
-        tight[i].stride = (size_t)kept[i].blocks_w * 8;
-        tight[i].plane_offset = px_fs;
-        px_fs += tight[i].stride * (size_t)kept[i].blocks_h * 8;
-        blk0[i] = (int)blocks;
-        blocks += (size_t)kept[i].blocks_w * kept[i].blocks_h;
-    }
+    const size_t px_fs = tight_records(kept, n_comp, true, tight, blk0), blocks = px_fs / 64;
     Layout L;
     if ((r = make_layout(tight, n_comp, n_qtabs, L))) return r;
     if (n_frames > 1 && (coef_fs < L.coef_span || diff_fs < blocks)) return HVC_E_INVALID_ARG;
@@ -1022,69 +1082,35 @@ int hvc_decode_frames_divergence(hvc_ctx *c, const int16_t *coefs, size_t coef_f
     if (where == HVC_MEM_DEVICE && ((uintptr_t)coefs & 15)) return HVC_E_ALIGNMENT;
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)256 << 20) / px_fs));
-    if ((r = grow(c, &c->d_div_px, &c->div_px_cap, (size_t)chunk * px_fs))) return r;
-    const size_t cspan = ((size_t)(chunk - 1) * coef_fs + L.coef_span) * sizeof(int16_t);
-    const size_t dspan = (size_t)(chunk - 1) * diff_fs + blocks;
-    if (where == HVC_MEM_HOST) {
-        if ((r = grow(c, &c->d_div_in, &c->div_in_cap, cspan))) return r;
-        if ((r = grow(c, &c->d_div_out, &c->div_out_cap, dspan))) return r;
-    }
-    const int arith_saved = c->arith;
-    const bool prof_saved = c->profiling;
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        const int cnt = std::min(chunk, n_frames - f0);
-        const int16_t *d_coefs = coefs + (size_t)f0 * coef_fs;
-        uint8_t *d_diff = max_diff + (size_t)f0 * diff_fs;
-        if (where == HVC_MEM_HOST) {
-            HIPCHK(c, hipMemcpyAsync(c->d_div_in, d_coefs, ((size_t)(cnt - 1) * coef_fs + L.coef_span) * sizeof(int16_t),
-                                     hipMemcpyHostToDevice, c->stream));
-            d_coefs = (const int16_t *)c->d_div_in;
-            d_diff = (uint8_t *)c->d_div_out;
-        }
-        c->arith = HVC_ARITH_MODEL;
-        c->profiling = false;
-        r = decode_frames_impl(c, d_coefs, coef_fs, qtabs, n_qtabs, tight, n_comp, cnt, (uint8_t *)c->d_div_px, px_fs,
-                               HVC_MEM_DEVICE, nullptr, 0, nullptr);
-        c->arith = arith_saved;
-        c->profiling = prof_saved;
-        if (r) return r;
-        hvc::DecodeParams P;
-        std::memset(&P, 0, sizeof P);
-        P.coefs = d_coefs;
-        P.pixels = (uint8_t *)c->d_div_px;
-        P.coef_fs = coef_fs;
-        P.pixel_fs = px_fs;
-        P.n_frames = cnt;
-        P.n_comp = L.n_comp;
-        P.tiles_per_frame = L.tiles_per_frame;
-        for (int i = 0; i < L.n_comp; i++) P.comp[i] = L.comp[i];
-        hvc::HardcamlParams H = hardcaml_params(P, qtabs, n_qtabs);
-        H.diff = d_diff;
-        H.diff_fs = diff_fs;
-        for (int i = 0; i < n_comp; i++) H.blk0[i] = blk0[i];
-        HIPCHK(c, hvc::launch_hardcaml(H, c->stream));
-        if (where == HVC_MEM_HOST) {
-            if (cnt == 1 || diff_fs == blocks)
-                HIPCHK(c, hipMemcpyAsync(max_diff + (size_t)f0 * diff_fs, d_diff, (size_t)(cnt - 1) * diff_fs + blocks,
-                                         hipMemcpyDeviceToHost, c->stream));
-            else
-                HIPCHK(c, hipMemcpy2DAsync(max_diff + (size_t)f0 * diff_fs, diff_fs, d_diff, diff_fs, blocks, (size_t)cnt,
-                                           hipMemcpyDeviceToHost, c->stream));
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return HVC_OK;
+    DecodeOpts model(c); // the model's arithmetic whatever the context's, and no entry of the profiling ring
+    model.arith = HVC_ARITH_MODEL;
+    model.profile = false;
+    return divergence_chunks(
+        c, (const uint8_t *)coefs, coef_fs * sizeof(int16_t), L.coef_span * sizeof(int16_t), px_fs, n_frames, max_diff, diff_fs, blocks, where,
+        [&](const uint8_t *d_in, int cnt) {
+            return decode_frames_impl(c, (const int16_t *)d_in, coef_fs, qtabs, n_qtabs, tight, n_comp, cnt, (uint8_t *)c->d_div_px, px_fs,
+                                      HVC_MEM_DEVICE, model);
+        },
+        [&](const uint8_t *d_in, int cnt, uint8_t *d_diff) {
+            hvc::DecodeParams P;
+            fill_geometry(P, L, coef_fs, px_fs, cnt);
+            P.coefs = (const int16_t *)d_in;
+            P.pixels = (uint8_t *)c->d_div_px;
+            hvc::HardcamlParams H = hardcaml_params(P, qtabs, n_qtabs);
+            H.diff = d_diff;
+            H.diff_fs = diff_fs;
+            for (int i = 0; i < n_comp; i++) H.blk0[i] = blk0[i];
+            return hvc::launch_hardcaml(H, c->stream);
+        });
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------
 // 4:2:0 coefficient records -> tight 4:4:4 frames (block stage + crop + chroma upsample fused)
 int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
                               const hvc_component *comps, int n_comp, int n_frames, int width, int height, uint8_t *frames,
-                              size_t frame_stride, int where, const int16_t *dc_plane, size_t dc_fs,
-                              const std::vector<WideFix> *wide) {
+                              size_t frame_stride, int where, const DecodeOpts &o) {
     if (!c || !coefs || !frames || !comps || n_frames < 0) return HVC_E_INVALID_ARG;
-    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path: hvc_set_arithmetic)
+    if (o.arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path: hvc_set_arithmetic)
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     int r = check_qtabs(qtabs, n_qtabs, false);
     if (r) return r;
@@ -1136,24 +1162,15 @@ int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
     // lists are per launch
     const unsigned long long ids_per_frame = (unsigned long long)P.tiles_per_frame * HVC_TILE * P.nw;
     const int per = frames_per_launch_capped(n_frames, L.blocks_per_frame, ids_per_frame);
-    if (wide && !wide->empty() && (unsigned long long)n_frames * ids_per_frame >= (1ull << 32)) return HVC_E_TOO_LARGE;
+    const bool has_wide = o.wide && !o.wide->empty();
+    if (has_wide && (unsigned long long)n_frames * ids_per_frame >= (1ull << 32)) return HVC_E_TOO_LARGE;
     const unsigned long long ids = (unsigned long long)per * ids_per_frame;
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    if ((size_t)ids > c->fix_cap) {
-        void *p = c->d_fix_list;
-        size_t cap = c->fix_cap * sizeof(unsigned);
-        r = grow(c, &p, &cap, (size_t)ids * sizeof(unsigned));
-        c->d_fix_list = (unsigned *)p;
-        c->fix_cap = cap / sizeof(unsigned);
-        if (r) return r;
-    }
     int ethr_unused[HVC_MAX_QTABS];
     prepare_tables(qtabs, n_qtabs, P.qt, ethr_unused, P.ethr_packed, P.qpair);
     bool wide_only = c->decode_kernel == 2;
     for (int i = 0; i < n_qtabs * 64; i++) wide_only |= qtabs[i] > 255;
-    P.fix_list = c->d_fix_list;
-    wide_total_begin(c);
     // How the block stage is launched (fused444_mode): one kernel for luma and chroma tiles, or -- where the luma crop is
     // whole blocks of the whole coefficient plane, which is every frame whose width and height are multiples of 16 and
     // 8 -- the luma planes through k_decode_packed ITSELF (one component, stride = width: the kernel, the schedule and
@@ -1161,15 +1178,9 @@ int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
     // by side on two streams.
     const int split = (aligned && !wide_only && c->decode_kernel == 0 && height % 8 == 0 && P.pl[0].cbw == P.pl[0].bw) ? fused444_mode() : 0;
     const size_t luma_ids = split ? (size_t)per * (size_t)((P.pl[0].cbw * P.pl[0].cbh + HVC_TILE - 1) / HVC_TILE) * HVC_TILE : 0;
-    if (luma_ids + (size_t)ids > c->fix_cap) { // (the luma list sits behind the 4:4:4 kernels' list)
-        void *p = c->d_fix_list;
-        size_t cap = c->fix_cap * sizeof(unsigned);
-        r = grow(c, &p, &cap, (luma_ids + (size_t)ids) * sizeof(unsigned));
-        c->d_fix_list = (unsigned *)p;
-        c->fix_cap = cap / sizeof(unsigned);
-        if (r) return r;
-        P.fix_list = c->d_fix_list;
-    }
+    if ((r = reserve_fix_list(c, luma_ids + (size_t)ids))) return r; // (the luma list sits behind the 4:4:4 kernels' list)
+    P.fix_list = c->d_fix_list;
+    wide_total_begin(c);
     if (split == 2 && !c->side_stream) {
         // (streams of one priority may share a hardware queue and then never overlap: HVC_444_SIDE_PRIO -1 / 0 / 1 =
         // highest / the default / lowest priority for the side stream, experiments)
@@ -1250,68 +1261,50 @@ int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
     };
 
     // frames [f0, f0 + cnt) of the batch at d_coefs / d_out, in launches of `per` frames
-    auto launch_range = [&](const int16_t *d_coefs, uint8_t *d_out, int f0, int cnt, hipEvent_t k0, hipEvent_t k1) -> hipError_t {
-        for (int f = f0; f < f0 + cnt; f += per) {
+    auto launch_range = [&](const int16_t *d_coefs, uint8_t *d_out, int f0, int cnt, hipEvent_t k0, hipEvent_t k1) {
+        return for_each_launch(f0, cnt, per, k0, k1, [&](int f, int n, hipEvent_t e0, hipEvent_t e1) {
             hvc::Decode444Params Pk = P;
-            Pk.n_frames = f0 + cnt - f < per ? f0 + cnt - f : per;
+            Pk.n_frames = n;
             Pk.coefs = d_coefs + (size_t)f * coef_fs;
             Pk.out = d_out + (size_t)f * frame_stride;
-            if (dc_plane) Pk.dc_plane = dc_plane + (size_t)f * dc_fs;
-            const hipError_t e = launch(Pk, f == f0 ? k0 : nullptr, f + per >= f0 + cnt ? k1 : nullptr);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
+            if (o.dc_plane) Pk.dc_plane = o.dc_plane + (size_t)f * o.dc_fs;
+            return launch(Pk, e0, e1);
+        });
     };
 
-    if (where == HVC_MEM_HOST && (dc_plane || (wide && !wide->empty()))) return HVC_E_INVALID_ARG;
+    if (where == HVC_MEM_HOST && (o.dc_plane || has_wide)) return HVC_E_INVALID_ARG;
     if (where == HVC_MEM_DEVICE) {
         if ((uintptr_t)coefs & 15) return HVC_E_ALIGNMENT;
         P.coefs = coefs;
         P.out = frames;
-        P.dc_plane = dc_plane;
-        P.dc_fs = dc_fs;
-        const bool prof = c->profiling && !wide_only;
+        P.dc_plane = o.dc_plane;
+        P.dc_fs = o.dc_fs;
+        const bool prof = o.profile && !wide_only;
         const int slot = (int)(c->k_calls % HVC_PROF_RING);
         HIPCHK(c, launch_range(coefs, frames, 0, n_frames, prof ? c->k0[slot] : nullptr, prof ? c->k1[slot] : nullptr));
         if (prof) c->k_calls++;
-        if (wide && !wide->empty()) return apply_wide_dc_444(c, P, *wide);
+        if (has_wide) return apply_wide_dc_444(c, P, *o.wide);
         return HVC_OK;
     }
     const size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + L.coef_span) * sizeof(int16_t);
     const size_t obytes = (size_t)(n_frames - 1) * frame_stride + out_span;
-    r = grow(c, &c->d_in, &c->in_cap, cbytes);
-    if (r) return r;
-    r = grow(c, &c->d_out, &c->out_cap, obytes);
-    if (r) return r;
-    if (n_frames >= 8 && cbytes >= ((size_t)64 << 20)) // large batches: see overlapped_parts
-        return overlapped_parts(
-            c, n_frames,
-            [&](int f0, int cnt) {
-                return hipMemcpyAsync((int16_t *)c->d_in + (size_t)f0 * coef_fs, coefs + (size_t)f0 * coef_fs,
-                                      ((size_t)(cnt - 1) * coef_fs + L.coef_span) * sizeof(int16_t), hipMemcpyHostToDevice, c->stream);
-            },
-            [&](int, int f0, int cnt) { return launch_range((const int16_t *)c->d_in, (uint8_t *)c->d_out, f0, cnt, nullptr, nullptr); },
-            [&](int f0, int cnt, hipStream_t st) {
-                const size_t off = (size_t)f0 * frame_stride;
-                return hipMemcpy2DAsync(frames + off, frame_stride, (uint8_t *)c->d_out + off, frame_stride, out_span, (size_t)cnt,
-                                        hipMemcpyDeviceToHost, st);
-            });
-    HIPCHK(c, hipMemcpyAsync(c->d_in, coefs, cbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_range((const int16_t *)c->d_in, (uint8_t *)c->d_out, 0, n_frames, nullptr, nullptr));
-    if (n_frames == 1) // frame_stride is irrelevant for a single frame (and may be smaller than the frame)
-        HIPCHK(c, hipMemcpyAsync(frames, c->d_out, out_span, hipMemcpyDeviceToHost, c->stream));
-    else
-        HIPCHK(c, hipMemcpy2DAsync(frames, frame_stride, c->d_out, frame_stride, out_span, (size_t)n_frames,
-                                   hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return HVC_OK;
+    return through_device(
+        c, n_frames, cbytes, obytes, cbytes, true,
+        [&](int f0, int cnt) {
+            return hipMemcpyAsync((int16_t *)c->d_in + (size_t)f0 * coef_fs, coefs + (size_t)f0 * coef_fs,
+                                  ((size_t)(cnt - 1) * coef_fs + L.coef_span) * sizeof(int16_t), hipMemcpyHostToDevice, c->stream);
+        },
+        [&](int f0, int cnt) { return launch_range((const int16_t *)c->d_in, (uint8_t *)c->d_out, f0, cnt, nullptr, nullptr); },
+        [&](int f0, int cnt, hipStream_t st) { // (frame_stride is irrelevant for a single frame, and may be smaller than the frame)
+            return copy_run_d2h((const uint8_t *)c->d_out, frames, 0, out_span, frame_stride, f0, cnt, st);
+        });
 }
 
 int hvc_decode_frames_yuv444(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
                              const hvc_component *comps, int n_comp, int n_frames, int width, int height,
                              uint8_t *frames, size_t frame_stride, int where) try {
     return decode_frames_yuv444_impl(c, coefs, coef_fs, qtabs, n_qtabs, comps, n_comp, n_frames, width, height, frames,
-                                     frame_stride, where, nullptr, 0);
+                                     frame_stride, where, DecodeOpts(c));
 } HVC_ABI_CATCH
 
 int hvc_dequant_idct_recon(hvc_ctx *c, const int16_t *coefs, size_t coef_plane_stride, const uint16_t *qtab,
@@ -1334,22 +1327,16 @@ int hvc_dequant_idct_recon(hvc_ctx *c, const int16_t *coefs, size_t coef_plane_s
 // The encoder twin's parameters for the geometry of an EncodeParams (hvc_hardcaml.h)
 static hvc::HardcamlEncodeParams hardcaml_encode_params(const hvc::EncodeParams &P, const uint16_t *qtabs, int n_qtabs) {
     hvc::HardcamlEncodeParams H;
-    std::memset(&H, 0, sizeof H);
+    fill_geometry(H, P, P.coef_fs, P.pixel_fs, P.n_frames);
     H.pixels = P.pixels;
     H.coefs = P.coefs;
-    H.coef_fs = P.coef_fs;
-    H.pixel_fs = P.pixel_fs;
-    H.n_frames = P.n_frames;
-    H.n_comp = P.n_comp;
-    H.tiles_per_frame = P.tiles_per_frame;
-    for (int i = 0; i < P.n_comp; i++) H.comp[i] = P.comp[i];
     hvc::prepare_hardcaml_encode_tables(qtabs, n_qtabs, H.qr);
     return H;
 }
 
-int hvc_encode_frames(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const uint16_t *qtabs, int n_qtabs,
-                      const hvc_component *comps, int n_comp, int n_frames, int16_t *coefs, size_t coef_fs,
-                      int where) try {
+int encode_frames_impl(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const uint16_t *qtabs, int n_qtabs,
+                       const hvc_component *comps, int n_comp, int n_frames, int16_t *coefs, size_t coef_fs, int where,
+                       const EncodeOpts &o) {
     if (!c || !coefs || !pixels || n_frames < 0) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     int r = check_qtabs(qtabs, n_qtabs, true);
@@ -1369,75 +1356,59 @@ int hvc_encode_frames(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const 
     const int per = frames_per_launch_capped(n_frames, L.blocks_per_frame, 0); // the 10 GB rule and the grid's 65535 frames
 
     hvc::EncodeParams P;
-    std::memset(&P, 0, sizeof P);
-    P.coef_fs = coef_fs;
-    P.pixel_fs = pixel_fs;
-    P.n_frames = n_frames;
-    P.n_comp = L.n_comp;
-    P.tiles_per_frame = L.tiles_per_frame;
-    for (int i = 0; i < L.n_comp; i++) P.comp[i] = L.comp[i];
+    fill_geometry(P, L, coef_fs, pixel_fs, n_frames);
     for (int i = 0; i < n_qtabs * 64; i++) // fl((1 + 2^-16) / (4t)): see quant1 in hvc_kernels.hip
         P.qrcp[i] = (float)((1.0 + 1.0 / 65536.0) / (4.0 * (double)qtabs[i]));
     // HVC_ARITH_HARDCAML (hvc_set_encode_arithmetic): the RTL encoder twin (hvc_hardcaml.hip) in place of k_encode
-    const bool twin = c->enc_arith == HVC_ARITH_HARDCAML;
+    const bool twin = o.arith == HVC_ARITH_HARDCAML;
     hvc::HardcamlEncodeParams H;
     if (twin) H = hardcaml_encode_params(P, qtabs, n_qtabs);
 
     // frames [f0, f0 + cnt) of the batch at d_pixels / d_coefs, in launches of `per` frames
-    auto launch_range = [&](const uint8_t *d_pixels, int16_t *d_coefs, int f0, int cnt, hipEvent_t k0, hipEvent_t k1) -> hipError_t {
-        for (int f = f0; f < f0 + cnt; f += per) {
-            hvc::EncodeParams Pk = P;
-            Pk.n_frames = f0 + cnt - f < per ? f0 + cnt - f : per;
-            Pk.coefs = d_coefs + (size_t)f * coef_fs;
-            Pk.pixels = d_pixels + (size_t)f * pixel_fs;
-            hipEvent_t e0 = f == f0 ? k0 : nullptr, e1 = f + per >= f0 + cnt ? k1 : nullptr;
-            hipError_t e;
+    auto launch_range = [&](const uint8_t *d_pixels, int16_t *d_coefs, int f0, int cnt, hipEvent_t k0, hipEvent_t k1) {
+        return for_each_launch(f0, cnt, per, k0, k1, [&](int f, int n, hipEvent_t e0, hipEvent_t e1) {
             if (twin) {
                 hvc::HardcamlEncodeParams Hk = H;
-                Hk.n_frames = Pk.n_frames;
-                Hk.coefs = Pk.coefs;
-                Hk.pixels = Pk.pixels;
-                e = hvc::launch_hardcaml_encode(Hk, c->stream, e0, e1);
-            } else {
-                e = hvc::launch_encode(Pk, c->stream, e0, e1);
+                Hk.n_frames = n;
+                Hk.coefs = d_coefs + (size_t)f * coef_fs;
+                Hk.pixels = d_pixels + (size_t)f * pixel_fs;
+                return hvc::launch_hardcaml_encode(Hk, c->stream, e0, e1);
             }
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
+            hvc::EncodeParams Pk = P;
+            Pk.n_frames = n;
+            Pk.coefs = d_coefs + (size_t)f * coef_fs;
+            Pk.pixels = d_pixels + (size_t)f * pixel_fs;
+            return hvc::launch_encode(Pk, c->stream, e0, e1);
+        });
     };
     if (where == HVC_MEM_DEVICE) {
         if (((uintptr_t)coefs & 15) || ((uintptr_t)pixels & 7)) return HVC_E_ALIGNMENT;
-        const bool prof = c->profiling;
         const int slot = (int)(c->k_calls % HVC_PROF_RING);
-        HIPCHK(c, launch_range(pixels, coefs, 0, n_frames, prof ? c->k0[slot] : nullptr, prof ? c->k1[slot] : nullptr));
-        if (prof) c->k_calls++;
+        HIPCHK(c, launch_range(pixels, coefs, 0, n_frames, o.profile ? c->k0[slot] : nullptr, o.profile ? c->k1[slot] : nullptr));
+        if (o.profile) c->k_calls++;
         return HVC_OK;
     }
 
-    size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + L.coef_span) * sizeof(int16_t);
-    size_t pbytes = (size_t)(n_frames - 1) * pixel_fs + L.pixel_span;
-    r = grow(c, &c->d_in, &c->in_cap, pbytes);
-    if (r) return r;
-    r = grow(c, &c->d_out, &c->out_cap, cbytes);
-    if (r) return r;
+    const size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + L.coef_span) * sizeof(int16_t);
+    const size_t pbytes = (size_t)(n_frames - 1) * pixel_fs + L.pixel_span;
     // copy back only the coefficient planes (gaps in the caller's records stay untouched)
     const RecordRun run = coef_run(comps, n_comp);
-    if (run.len && n_frames >= 8 && cbytes >= ((size_t)64 << 20)) // large batches in the usual form: see overlapped_parts
-        return overlapped_parts(
-            c, n_frames,
-            [&](int f0, int cnt) {
-                return hipMemcpyAsync((uint8_t *)c->d_in + (size_t)f0 * pixel_fs, pixels + (size_t)f0 * pixel_fs,
-                                      (size_t)(cnt - 1) * pixel_fs + L.pixel_span, hipMemcpyHostToDevice, c->stream);
-            },
-            [&](int, int f0, int cnt) { return launch_range((const uint8_t *)c->d_in, (int16_t *)c->d_out, f0, cnt, nullptr, nullptr); },
-            [&](int f0, int cnt, hipStream_t st) {
-                return download_coefs(comps, n_comp, run, f0, cnt, coef_fs * sizeof(int16_t), (const uint8_t *)c->d_out, (uint8_t *)coefs, st);
-            });
-    HIPCHK(c, hipMemcpyAsync(c->d_in, pixels, pbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_range((const uint8_t *)c->d_in, (int16_t *)c->d_out, 0, n_frames, nullptr, nullptr));
-    HIPCHK(c, download_coefs(comps, n_comp, run, 0, n_frames, coef_fs * sizeof(int16_t), (const uint8_t *)c->d_out, (uint8_t *)coefs, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return HVC_OK;
+    return through_device(
+        c, n_frames, pbytes, cbytes, cbytes, run.len != 0, // (overlapped: large batches in the usual form)
+        [&](int f0, int cnt) {
+            return hipMemcpyAsync((uint8_t *)c->d_in + (size_t)f0 * pixel_fs, pixels + (size_t)f0 * pixel_fs,
+                                  (size_t)(cnt - 1) * pixel_fs + L.pixel_span, hipMemcpyHostToDevice, c->stream);
+        },
+        [&](int f0, int cnt) { return launch_range((const uint8_t *)c->d_in, (int16_t *)c->d_out, f0, cnt, nullptr, nullptr); },
+        [&](int f0, int cnt, hipStream_t st) {
+            return download_coefs(comps, n_comp, run, f0, cnt, coef_fs * sizeof(int16_t), (const uint8_t *)c->d_out, (uint8_t *)coefs, st);
+        });
+}
+
+int hvc_encode_frames(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const uint16_t *qtabs, int n_qtabs,
+                      const hvc_component *comps, int n_comp, int n_frames, int16_t *coefs, size_t coef_fs,
+                      int where) try {
+    return encode_frames_impl(c, pixels, pixel_fs, qtabs, n_qtabs, comps, n_comp, n_frames, coefs, coef_fs, where, EncodeOpts(c));
 } HVC_ABI_CATCH
 
 // Encoder.encode_block with compute_reconstruction_error (encoder.ml:195-205): K3, then K1 on the coefficients it
@@ -1457,13 +1428,9 @@ int hvc_encode_frames_recon(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, 
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
     const size_t pbytes = (size_t)(n_frames - 1) * pixel_fs + L.pixel_span;
     const size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + L.coef_span) * sizeof(int16_t);
-    const bool prof_saved = c->profiling;
-    struct Restore {
-        hvc_ctx *c;
-        bool p;
-        ~Restore() { c->profiling = p; }
-    } restore{c, prof_saved};
-    c->profiling = false;
+    EncodeOpts enc(c); // the context's arithmetic on both sides, and no entry of the profiling ring for either
+    DecodeOpts dec(c);
+    enc.profile = dec.profile = false;
     // device pointers of the three pixel-layout records and of the coefficients
     const uint8_t *d_pix = pixels;
     int16_t *d_coefs = coefs;
@@ -1481,19 +1448,14 @@ int hvc_encode_frames_recon(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, 
         if ((r = grow(c, &c->d_aux, &c->aux_cap, pbytes))) return r;
         d_recon = (uint8_t *)c->d_aux;
     }
-    if ((r = hvc_encode_frames(c, d_pix, pixel_fs, qtabs, n_qtabs, comps, n_comp, n_frames, d_coefs, coef_fs, HVC_MEM_DEVICE)))
+    if ((r = encode_frames_impl(c, d_pix, pixel_fs, qtabs, n_qtabs, comps, n_comp, n_frames, d_coefs, coef_fs, HVC_MEM_DEVICE, enc)))
         return r;
-    if ((r = hvc_decode_frames(c, d_coefs, coef_fs, qtabs, n_qtabs, comps, n_comp, n_frames, d_recon, pixel_fs, HVC_MEM_DEVICE)))
+    if ((r = decode_frames_impl(c, d_coefs, coef_fs, qtabs, n_qtabs, comps, n_comp, n_frames, d_recon, pixel_fs, HVC_MEM_DEVICE, dec)))
         return r;
     if (error || where == HVC_MEM_HOST) {
         hvc::EncodeParams P;
-        std::memset(&P, 0, sizeof P);
+        fill_geometry(P, L, 0, pixel_fs, n_frames);
         P.pixels = d_pix;
-        P.pixel_fs = pixel_fs;
-        P.n_frames = n_frames;
-        P.n_comp = L.n_comp;
-        P.tiles_per_frame = L.tiles_per_frame;
-        for (int i = 0; i < L.n_comp; i++) P.comp[i] = L.comp[i];
         HIPCHK(c, hvc::launch_abs_error(P, d_recon, d_error, c->stream));
     }
     if (where == HVC_MEM_DEVICE) return HVC_OK;
@@ -1528,10 +1490,8 @@ int hvc_fdct_quant(hvc_ctx *c, const uint8_t *plane, size_t stride, size_t plane
     return hvc_encode_frames(c, plane, plane_stride, qtab, 1, &comp, 1, n_planes, coefs, coef_plane_stride, where);
 } HVC_ABI_CATCH
 
-// ---------------------------------------------------------------------------
-// max |model - hardcaml| per block of the encoder: the model's block stage (k_encode) into device scratch (tight
-// coefficient planes), then the encoder twin's compare form reads those records beside its own and writes one byte per
-// block.  Frames go in chunks of at most ~256 MB of model records.
+// The encoder's divergence (divergence_chunks): the model's block stage (k_encode) into tight coefficient planes, then
+// k_hardcaml_encode's compare form; a byte is min(255, max |q_model - q_hardcaml|).
 int hvc_encode_frames_divergence(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const uint16_t *qtabs, int n_qtabs,
                                  const hvc_component *comps, int n_comp, int n_frames, uint8_t *max_diff, size_t diff_fs,
                                  int where) try {
@@ -1546,15 +1506,8 @@ int hvc_encode_frames_divergence(hvc_ctx *c, const uint8_t *pixels, size_t pixel
     if (n_frames == 0) return HVC_OK;
     // the model's records: the caller's pixel geometry, every coefficient plane tight, one after the other
     hvc_component tight[HVC_MAX_COMP];
-    size_t cf = 0;
     int blk0[HVC_MAX_COMP];
-    for (int i = 0; i < n_comp; i++) {
-        tight[i] = comps[i];
-        tight[i].coef_offset = cf;
-        blk0[i] = (int)(cf / 64);
-        cf += (size_t)comps[i].blocks_w * comps[i].blocks_h * 64;
-    }
-    const size_t blocks = cf / 64;
+    const size_t cf = tight_records(comps, n_comp, false, tight, blk0), blocks = cf / 64;
     Layout T;
     if ((r = make_layout(tight, n_comp, n_qtabs, T))) return r;
     if (n_frames > 1 && (pixel_fs < L.pixel_span || diff_fs < blocks)) return HVC_E_INVALID_ARG;
@@ -1562,60 +1515,25 @@ int hvc_encode_frames_divergence(hvc_ctx *c, const uint8_t *pixels, size_t pixel
     if (where == HVC_MEM_DEVICE && ((uintptr_t)pixels & 7)) return HVC_E_ALIGNMENT;
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    const size_t rec_bytes = cf * sizeof(int16_t);
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)256 << 20) / rec_bytes));
-    if ((r = grow(c, &c->d_div_px, &c->div_px_cap, (size_t)chunk * rec_bytes))) return r;
-    const size_t pspan = (size_t)(chunk - 1) * pixel_fs + L.pixel_span;
-    const size_t dspan = (size_t)(chunk - 1) * diff_fs + blocks;
-    if (where == HVC_MEM_HOST) {
-        if ((r = grow(c, &c->d_div_in, &c->div_in_cap, pspan))) return r;
-        if ((r = grow(c, &c->d_div_out, &c->div_out_cap, dspan))) return r;
-    }
-    const int arith_saved = c->enc_arith;
-    const bool prof_saved = c->profiling;
-    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
-        const int cnt = std::min(chunk, n_frames - f0);
-        const uint8_t *d_pix = pixels + (size_t)f0 * pixel_fs;
-        uint8_t *d_diff = max_diff + (size_t)f0 * diff_fs;
-        if (where == HVC_MEM_HOST) {
-            HIPCHK(c, hipMemcpyAsync(c->d_div_in, d_pix, (size_t)(cnt - 1) * pixel_fs + L.pixel_span, hipMemcpyHostToDevice,
-                                     c->stream));
-            d_pix = (const uint8_t *)c->d_div_in;
-            d_diff = (uint8_t *)c->d_div_out;
-        }
-        c->enc_arith = HVC_ARITH_MODEL;
-        c->profiling = false;
-        r = hvc_encode_frames(c, d_pix, pixel_fs, qtabs, n_qtabs, tight, n_comp, cnt, (int16_t *)c->d_div_px, cf,
-                              HVC_MEM_DEVICE);
-        c->enc_arith = arith_saved;
-        c->profiling = prof_saved;
-        if (r) return r;
-        hvc::EncodeParams P;
-        std::memset(&P, 0, sizeof P);
-        P.pixels = d_pix;
-        P.coefs = (int16_t *)c->d_div_px;
-        P.coef_fs = cf;
-        P.pixel_fs = pixel_fs;
-        P.n_frames = cnt;
-        P.n_comp = T.n_comp;
-        P.tiles_per_frame = T.tiles_per_frame;
-        for (int i = 0; i < T.n_comp; i++) P.comp[i] = T.comp[i];
-        hvc::HardcamlEncodeParams H = hardcaml_encode_params(P, qtabs, n_qtabs);
-        H.diff = d_diff;
-        H.diff_fs = diff_fs;
-        for (int i = 0; i < n_comp; i++) H.blk0[i] = blk0[i];
-        HIPCHK(c, hvc::launch_hardcaml_encode(H, c->stream));
-        if (where == HVC_MEM_HOST) {
-            if (cnt == 1 || diff_fs == blocks)
-                HIPCHK(c, hipMemcpyAsync(max_diff + (size_t)f0 * diff_fs, d_diff, (size_t)(cnt - 1) * diff_fs + blocks,
-                                         hipMemcpyDeviceToHost, c->stream));
-            else
-                HIPCHK(c, hipMemcpy2DAsync(max_diff + (size_t)f0 * diff_fs, diff_fs, d_diff, diff_fs, blocks, (size_t)cnt,
-                                           hipMemcpyDeviceToHost, c->stream));
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return HVC_OK;
+    EncodeOpts model(c); // the model's arithmetic whatever the context's, and no entry of the profiling ring
+    model.arith = HVC_ARITH_MODEL;
+    model.profile = false;
+    return divergence_chunks(
+        c, pixels, pixel_fs, L.pixel_span, cf * sizeof(int16_t), n_frames, max_diff, diff_fs, blocks, where,
+        [&](const uint8_t *d_pix, int cnt) {
+            return encode_frames_impl(c, d_pix, pixel_fs, qtabs, n_qtabs, tight, n_comp, cnt, (int16_t *)c->d_div_px, cf, HVC_MEM_DEVICE, model);
+        },
+        [&](const uint8_t *d_pix, int cnt, uint8_t *d_diff) {
+            hvc::EncodeParams P;
+            fill_geometry(P, T, cf, pixel_fs, cnt);
+            P.pixels = d_pix;
+            P.coefs = (int16_t *)c->d_div_px;
+            hvc::HardcamlEncodeParams H = hardcaml_encode_params(P, qtabs, n_qtabs);
+            H.diff = d_diff;
+            H.diff_fs = diff_fs;
+            for (int i = 0; i < n_comp; i++) H.blk0[i] = blk0[i];
+            return hvc::launch_hardcaml_encode(H, c->stream);
+        });
 } HVC_ABI_CATCH
 
 int hvc_upsample420(hvc_ctx *c, const uint8_t *src, int cw, int ch, size_t src_stride, uint8_t *dst,

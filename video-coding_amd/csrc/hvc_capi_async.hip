@@ -148,11 +148,10 @@ int hvc_decode_frames_submit(hvc_ctx *c, int slot, const int16_t *coefs, size_t 
     if (e != hipSuccess) return abandon(c, fail_hip(c, e));
     // (the device-memory form of hvc_decode_frames: launches enqueued on c->stream, nothing waited for; its own event ring
     // is for hvc_set_profiling's callers, the slot has its pair)
-    const bool prof_saved = c->profiling;
-    c->profiling = false;
+    DecodeOpts o(c);
+    o.profile = false;
     r = decode_frames_impl(c, (const int16_t *)s.d_in, coef_fs, qtabs, n_qtabs, kept, n_comp, n_frames, d_pixels, pixel_fs,
-                           HVC_MEM_DEVICE, nullptr, 0);
-    c->profiling = prof_saved;
+                           HVC_MEM_DEVICE, o);
     if (r) return abandon(c, r);
     e = hipEventRecord(s.k1, c->stream);
     if (e == hipSuccess && down) {
@@ -208,10 +207,9 @@ int hvc_encode_frames_submit(hvc_ctx *c, int slot, const uint8_t *pixels, size_t
     if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, s.up1, 0);
     if (e == hipSuccess) e = hipEventRecord(s.k0, c->stream);
     if (e != hipSuccess) return abandon(c, fail_hip(c, e));
-    const bool prof_saved = c->profiling;
-    c->profiling = false;
-    r = hvc_encode_frames(c, (const uint8_t *)s.d_in, pixel_fs, qtabs, n_qtabs, comps, n_comp, n_frames, d_coefs, coef_fs, HVC_MEM_DEVICE);
-    c->profiling = prof_saved;
+    EncodeOpts o(c); // (its own event ring: as in hvc_decode_frames_submit)
+    o.profile = false;
+    r = encode_frames_impl(c, (const uint8_t *)s.d_in, pixel_fs, qtabs, n_qtabs, comps, n_comp, n_frames, d_coefs, coef_fs, HVC_MEM_DEVICE, o);
     if (r) return abandon(c, r);
     e = hipEventRecord(s.k1, c->stream);
     if (e == hipSuccess && down) {

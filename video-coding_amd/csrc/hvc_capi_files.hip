@@ -403,8 +403,8 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
     double h2d_ms = 0, k_ms = 0, d2h_ms = 0;
     unsigned long long seg_bytes = 0;
     hipStream_t compute = c->stream;
-    const bool prof_saved = c->profiling;
-    c->profiling = false;
+    EncodeOpts block_stage(c); // (the chunks' launches take no entry of the profiling ring)
+    block_stage.profile = false;
     try {
     for (int it = 0; it < n_chunks + 3 && rc == HVC_OK; it++) {
         // stage 1: pad chunk `it` (its pinned slot was uploaded and synchronised two iterations ago)
@@ -425,8 +425,8 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
             if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_up[slot], 0);
             if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][1], compute);
             if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-            rc = hvc_encode_frames(c, (const uint8_t *)c->ed_in[slot], pix_bytes, &info.qtabs[0][0], info.n_qtabs,
-                                   info.layout, 3, cnt, (int16_t *)c->ed_out[slot], info.coef_count, HVC_MEM_DEVICE);
+            rc = encode_frames_impl(c, (const uint8_t *)c->ed_in[slot], pix_bytes, &info.qtabs[0][0], info.n_qtabs,
+                                    info.layout, 3, cnt, (int16_t *)c->ed_out[slot], info.coef_count, HVC_MEM_DEVICE, block_stage);
             if (rc) break;
             if (!gpu_entropy) {
                 he = hipEventRecord(c->ev_et[slot][2], compute);
@@ -506,7 +506,6 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
     } catch (...) {
         rc = hvc::exception_code();
     }
-    c->profiling = prof_saved;
     {
         std::lock_guard<std::mutex> lk(mu);
         if (rc != HVC_OK) {

@@ -45,14 +45,14 @@ static int decode_one_with_wide_dc(hvc_ctx *c, const hvc_jpeg_info *info, const 
         return HVC_E_OUT_OF_MEMORY;
     }
     HIPCHK(c, hipMemcpyAsync(c->d_in, coefs, cb, hipMemcpyHostToDevice, c->stream));
-    const bool prof_saved = c->profiling;
-    c->profiling = false;
+    DecodeOpts o(c);
+    o.profile = false;
+    o.wide = &fix;
     r = yuv444 ? decode_frames_yuv444_impl(c, (const int16_t *)c->d_in, info->coef_count, &info->qtabs[0][0], info->n_qtabs,
                                            info->layout, info->n_comp, 1, info->width, info->height, (uint8_t *)c->d_out, ob,
-                                           HVC_MEM_DEVICE, nullptr, 0, &fix)
+                                           HVC_MEM_DEVICE, o)
                : decode_frames_impl(c, (const int16_t *)c->d_in, info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
-                                    info->n_comp, 1, (uint8_t *)c->d_out, info->pixel_bytes, HVC_MEM_DEVICE, nullptr, 0, &fix);
-    c->profiling = prof_saved;
+                                    info->n_comp, 1, (uint8_t *)c->d_out, info->pixel_bytes, HVC_MEM_DEVICE, o);
     if (r) return r;
     HIPCHK(c, hipMemcpyAsync(out, c->d_out, ob, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -82,9 +82,12 @@ int hvc_jpeg_decode_yuv444(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_i
         DeviceGuard g(c->device);
         int e = grow(c, &c->d_out, &c->out_cap, fb);
         if (e) return e;
+        DecodeOpts o(c); // (profiling as the context has it)
+        o.dc_plane = after.dc_plane;
+        o.dc_fs = after.dc_fs;
         e = decode_frames_yuv444_impl(c, (const int16_t *)c->gd_coefs, info->coef_count, &info->qtabs[0][0], info->n_qtabs,
                                       info->layout, info->n_comp, 1, info->width, info->height, (uint8_t *)c->d_out, fb,
-                                      HVC_MEM_DEVICE, after.dc_plane, after.dc_fs);
+                                      HVC_MEM_DEVICE, o);
         if (e) return e;
         HIPCHK(c, hipMemcpyAsync(frame, c->d_out, fb, hipMemcpyDeviceToHost, c->stream));
         return HVC_OK;
@@ -108,9 +111,9 @@ int hvc_jpeg_decode_yuv444(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_i
     r = hvc::entropy_decode_wide(jpeg, n, info, coefs.data(), wide);
     if (r) return r;
     if (!wide.empty()) return decode_one_with_wide_dc(c, info, coefs.data(), wide, true, frame);
-    return hvc_decode_frames_yuv444(c, coefs.data(), info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
-                                    info->n_comp, 1, info->width, info->height, frame,
-                                    (size_t)3 * info->width * info->height, HVC_MEM_HOST);
+    return decode_frames_yuv444_impl(c, coefs.data(), info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
+                                     info->n_comp, 1, info->width, info->height, frame,
+                                     (size_t)3 * info->width * info->height, HVC_MEM_HOST, DecodeOpts(c));
 } HVC_ABI_CATCH
 
 int hvc_jpeg_decode(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *info, uint8_t *pixels, size_t pixel_cap) try {
@@ -127,8 +130,11 @@ int hvc_jpeg_decode(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *in
         DeviceGuard g(c->device);
         int e = grow(c, &c->d_out, &c->out_cap, info->pixel_bytes);
         if (e) return e;
+        DecodeOpts o(c); // (profiling as the context has it)
+        o.dc_plane = after.dc_plane;
+        o.dc_fs = after.dc_fs;
         e = decode_frames_impl(c, (const int16_t *)c->gd_coefs, info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
-                               info->n_comp, 1, (uint8_t *)c->d_out, info->pixel_bytes, HVC_MEM_DEVICE, after.dc_plane, after.dc_fs);
+                               info->n_comp, 1, (uint8_t *)c->d_out, info->pixel_bytes, HVC_MEM_DEVICE, o);
         if (e) return e;
         HIPCHK(c, hipMemcpyAsync(pixels, c->d_out, info->pixel_bytes, hipMemcpyDeviceToHost, c->stream));
         return HVC_OK;
@@ -152,8 +158,8 @@ int hvc_jpeg_decode(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *in
     r = hvc::entropy_decode_wide(jpeg, n, info, coefs.data(), wide);
     if (r) return r;
     if (!wide.empty()) return decode_one_with_wide_dc(c, info, coefs.data(), wide, false, pixels);
-    return hvc_decode_frames(c, coefs.data(), info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
-                             info->n_comp, 1, pixels, info->pixel_bytes, HVC_MEM_HOST);
+    return decode_frames_impl(c, coefs.data(), info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
+                              info->n_comp, 1, pixels, info->pixel_bytes, HVC_MEM_HOST, DecodeOpts(c));
 } HVC_ABI_CATCH
 
 // hvc_jpeg_decode with the colour pass behind the block stage: the planes stay in device scratch (c->d_aux), the image is
@@ -188,8 +194,11 @@ int hvc_jpeg_decode_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info
     AfterReader after;
     auto block_stage = [&]() -> int { // coefficient record on the device, enqueued behind the reader at once
         DeviceGuard g(c->device);
+        DecodeOpts o(c); // (profiling as the context has it)
+        o.dc_plane = after.dc_plane;
+        o.dc_fs = after.dc_fs;
         const int e = decode_frames_impl(c, (const int16_t *)c->gd_coefs, info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
-                                         info->n_comp, 1, (uint8_t *)c->d_aux, info->pixel_bytes, HVC_MEM_DEVICE, after.dc_plane, after.dc_fs);
+                                         info->n_comp, 1, (uint8_t *)c->d_aux, info->pixel_bytes, HVC_MEM_DEVICE, o);
         return e ? e : colour();
     };
     after.enqueue = block_stage;
@@ -220,11 +229,11 @@ int hvc_jpeg_decode_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info
     const size_t cb = info->coef_count * sizeof(int16_t);
     if ((r = grow(c, &c->d_in, &c->in_cap, cb))) return r;
     HIPCHK(c, hipMemcpyAsync(c->d_in, coefs.data(), cb, hipMemcpyHostToDevice, c->stream));
-    const bool prof_saved = c->profiling;
-    c->profiling = false;
+    DecodeOpts o(c);
+    o.profile = false;
+    o.wide = &fix;
     r = decode_frames_impl(c, (const int16_t *)c->d_in, info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout, info->n_comp, 1,
-                           (uint8_t *)c->d_aux, info->pixel_bytes, HVC_MEM_DEVICE, nullptr, 0, &fix);
-    c->profiling = prof_saved;
+                           (uint8_t *)c->d_aux, info->pixel_bytes, HVC_MEM_DEVICE, o);
     if (r) return r;
     if ((r = colour())) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -284,11 +293,10 @@ static int encode_padded_on_device(hvc_ctx *c, const hvc_jpeg_info &info, size_t
     int r;
     std::vector<uint8_t> header;
     const int ri = c->restart_interval;
-    const bool prof_saved = c->profiling;
-    c->profiling = false;
-    r = hvc_encode_frames(c, (const uint8_t *)c->d_in, info.pixel_bytes, &info.qtabs[0][0], info.n_qtabs, info.layout, 3, 1,
-                          (int16_t *)c->d_out, info.coef_count, HVC_MEM_DEVICE);
-    c->profiling = prof_saved;
+    EncodeOpts o(c);
+    o.profile = false;
+    r = encode_frames_impl(c, (const uint8_t *)c->d_in, info.pixel_bytes, &info.qtabs[0][0], info.n_qtabs, info.layout, 3, 1,
+                           (int16_t *)c->d_out, info.coef_count, HVC_MEM_DEVICE, o);
     if (r) return r;
     hvc::HuffParams P;
     const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // the frame's own tables (hvc_set_huffman_tables)
@@ -529,16 +537,15 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
         if (he == hipSuccess) he = hipEventRecord(c->ev_h2d[slot], c->copy_stream);
         if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_h2d[slot], 0);
         if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-        const bool prof_saved = c->profiling;
-        c->profiling = false;
         he = hipEventRecord(c->ev_t[1], compute);
-        const std::vector<WideFix> *wf = &chunk_wide[(size_t)k]; // (complete: the chunk's workers are done)
+        DecodeOpts o(c);
+        o.profile = false;
+        o.wide = &chunk_wide[(size_t)k]; // (complete: the chunk's workers are done)
         rc = yuv444 ? decode_frames_yuv444_impl(c, (const int16_t *)c->d_ring[slot], info0.coef_count, &info0.qtabs[0][0],
                                                 info0.n_qtabs, info0.layout, info0.n_comp, cnt, info0.width, info0.height,
-                                                dst, dst_fs, HVC_MEM_DEVICE, nullptr, 0, wf)
+                                                dst, dst_fs, HVC_MEM_DEVICE, o)
                     : decode_frames_impl(c, (const int16_t *)c->d_ring[slot], info0.coef_count, &info0.qtabs[0][0],
-                                         info0.n_qtabs, info0.layout, info0.n_comp, cnt, dst, dst_fs, HVC_MEM_DEVICE, nullptr, 0, wf);
-        c->profiling = prof_saved;
+                                         info0.n_qtabs, info0.layout, info0.n_comp, cnt, dst, dst_fs, HVC_MEM_DEVICE, o);
         if (rc) break;
         if (he == hipSuccess) he = hipEventRecord(c->ev_t[2], compute);
         if (he == hipSuccess && where == HVC_MEM_HOST) {

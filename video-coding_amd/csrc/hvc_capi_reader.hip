@@ -806,8 +806,8 @@ static int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     double h2d_ms = 0, k_ms = 0;
     uint64_t ecs_total = 0;
     hipStream_t compute = c->stream;
-    const bool prof_saved = c->profiling;
-    c->profiling = false;
+    DecodeOpts block_stage(c); // (the chunks' launches take no entry of the profiling ring)
+    block_stage.profile = false;
     int pending_release = -1; // the chunk whose pinned segment slot is handed on once its upload has finished
     auto release_after_upload = [&](int k) -> hipError_t {
         const hipError_t he = wait_event(c->ev_h2d[k % NB]);
@@ -931,11 +931,12 @@ static int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_
         if (he != hipSuccess) { rc = fail_hip(c, he); break; }
         uint8_t *dst = where == HVC_MEM_DEVICE ? pixels + (size_t)first * pixel_fs : (uint8_t *)c->d_oring[slot];
         const size_t dst_fs = where == HVC_MEM_DEVICE ? pixel_fs : out_bytes;
+        block_stage.dc_plane = P.dc_plane;
+        block_stage.dc_fs = P.dc_fs;
         rc = yuv444 ? decode_frames_yuv444_impl(c, P.coefs, info0.coef_count, &info0.qtabs[0][0], info0.n_qtabs, info0.layout,
-                                                info0.n_comp, cnt, info0.width, info0.height, dst, dst_fs, HVC_MEM_DEVICE,
-                                                P.dc_plane, P.dc_fs)
+                                                info0.n_comp, cnt, info0.width, info0.height, dst, dst_fs, HVC_MEM_DEVICE, block_stage)
                     : decode_frames_impl(c, P.coefs, info0.coef_count, &info0.qtabs[0][0], info0.n_qtabs, info0.layout,
-                                         info0.n_comp, cnt, dst, dst_fs, HVC_MEM_DEVICE, P.dc_plane, P.dc_fs);
+                                         info0.n_comp, cnt, dst, dst_fs, HVC_MEM_DEVICE, block_stage);
         if (rc) break;
         he = hipEventRecord(c->ev_et[slot][2], compute);
         if (he == hipSuccess && where == HVC_MEM_HOST) { // the downloader takes over
@@ -959,7 +960,6 @@ static int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     } catch (...) {
         rc = hvc::exception_code();
     }
-    c->profiling = prof_saved;
     {
         std::lock_guard<std::mutex> lk(mu);
         if (rc != HVC_OK) error.store(rc);

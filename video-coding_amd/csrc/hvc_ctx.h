@@ -1,6 +1,7 @@
 // hvc_ctx.h -- what the translation units of the C ABI share (internal; nothing here is exported): the context, the
 // helpers every entry point uses, and the few functions one part of the ABI calls in another.
-//   hvc_capi.hip         context, streams, timers, memory; the block stage (hvc_decode_frames, hvc_encode_frames, ...)
+//   hvc_capi.hip         context, streams, timers, memory; the block stage (decode_frames_impl, decode_frames_yuv444_impl,
+//                        encode_frames_impl behind the entry points; the staging steps they share) and its divergence calls
 //   hvc_capi_jpeg.hip    files: one at a time (hvc_jpeg_decode, hvc_jpeg_encode) and the batch pipeline with the host reader
 //   hvc_capi_reader.hip  the GPU Huffman reader's entry point and the batch pipeline built on it
 //   hvc_capi_files.hip   the GPU Huffman coder's entry point and the batch pipelines that write files
@@ -320,16 +321,33 @@ struct WideFix {
     long long dc;
 };
 
-// hvc_capi.hip: the block stage behind hvc_decode_frames / hvc_decode_frames_yuv444.
-// dc_plane (device memory calls only, default kernels only): see hvc::DecodeParams::dc_plane
-// wide (device memory calls only): blocks to recompute with their true DC once the launches are enqueued
+// What one call of the block stage is to do beyond its records: stated by the caller with the call, never by changing the
+// context's settings around it.  The public entry points take the context's settings (the constructors); an internal
+// caller starts from those and overrides what it decides itself.
+struct DecodeOpts {
+    int arith = HVC_ARITH_MODEL;         // hvc_set_arithmetic
+    bool profile = false;                // a device-memory call takes an entry of the profiling ring (hvc_set_profiling)
+    const int16_t *dc_plane = nullptr;   // (device memory calls only, default kernels only): see hvc::DecodeParams::dc_plane
+    size_t dc_fs = 0;
+    const std::vector<WideFix> *wide = nullptr; // (device memory calls only): blocks to recompute with their true DC once the launches are enqueued
+    explicit DecodeOpts(const hvc_ctx *c) : arith(c ? c->arith : HVC_ARITH_MODEL), profile(c && c->profiling) {}
+};
+struct EncodeOpts {
+    int arith = HVC_ARITH_MODEL; // hvc_set_encode_arithmetic
+    bool profile = false;
+    explicit EncodeOpts(const hvc_ctx *c) : arith(c ? c->enc_arith : HVC_ARITH_MODEL), profile(c && c->profiling) {}
+};
+
+// hvc_capi.hip: the block stage behind hvc_decode_frames / hvc_decode_frames_yuv444 / hvc_encode_frames
 int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
                        const hvc_component *comps, int n_comp, int n_frames, uint8_t *pixels, size_t pixel_fs, int where,
-                       const int16_t *dc_plane, size_t dc_fs, const std::vector<WideFix> *wide = nullptr);
+                       const DecodeOpts &o);
 int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
                               const hvc_component *comps, int n_comp, int n_frames, int width, int height, uint8_t *frames,
-                              size_t frame_stride, int where, const int16_t *dc_plane, size_t dc_fs,
-                              const std::vector<WideFix> *wide = nullptr);
+                              size_t frame_stride, int where, const DecodeOpts &o);
+int encode_frames_impl(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const uint16_t *qtabs, int n_qtabs,
+                       const hvc_component *comps, int n_comp, int n_frames, int16_t *coefs, size_t coef_fs, int where,
+                       const EncodeOpts &o);
 
 // after_reader (optional): called once the reader's launches are enqueued and BEFORE its verdict is known -- the caller
 // enqueues what consumes the records (block stage, download) on the same stream, so that one call costs one host
