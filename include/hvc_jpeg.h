@@ -685,6 +685,63 @@ HVC_API int hvc_jpeg_decode_batch_rgb(hvc_ctx *ctx, const uint8_t *const *jpegs,
 HVC_API int hvc_jpeg_encode_rgb(hvc_ctx *ctx, const uint8_t *rgb, size_t rgb_row_stride, int layout, int width, int height,
                                 int chroma, int quality, uint8_t *out, size_t cap, size_t *out_len);
 
+/* ------------------------------------------------------------------------- */
+/* Decoding at reduced size: 1/2, 1/4, 1/8 (an EXTENSION; the model has no counterpart).  libjpeg's scale_denom: the inverse
+ * DCT produces N x N samples per block, N = 8 / scale_denom, straight from the coefficients -- the arithmetic of libjpeg's
+ * jidctred.c, bit for bit (tools/scaled_reference.py restates it in numpy and tests/test_scaled_reference.py holds that
+ * against libjpeg-turbo).  scale_denom s in {1, 2, 4, 8}; for a block d[k] = coefficient * table entry at natural position
+ * k = 8 * row + col; all arithmetic in unbounded integers; D(x, n) = (x + 2^(n-1)) >> n with an arithmetic shift; a sample
+ * is clamp(x + 128, 0, 255).
+ *   N = 1   x = D(d[0], 3).
+ *   N = 2   step on v[0..7]:  t10 = v0 << 15;  t0 = -5906 v7 + 6967 v5 - 10426 v3 + 29692 v1;  D(t10 + t0, sh), D(t10 - t0, sh).
+ *           Pass 1 down columns 0 1 3 5 7 with sh = 13 (columns 2 4 6 are not used), pass 2 along the two rows of the
+ *           workspace with sh = 20.
+ *   N = 4   t0 = v0 << 14;  t2 = 15137 v2 - 6270 v6;  t10 = t0 + t2;  t12 = t0 - t2;
+ *           o0 = -1730 v7 + 11893 v5 - 17799 v3 + 8697 v1;  o2 = -4176 v7 - 4926 v5 + 7373 v3 + 20995 v1;
+ *           D(t10 + o2, sh), D(t12 + o0, sh), D(t12 - o0, sh), D(t10 - o2, sh).  Pass 1 down columns 0 1 2 3 5 6 7 with sh = 12
+ *           (column 4 is not used), pass 2 along the four rows with sh = 19.
+ *   s = 1   the model's arithmetic, unchanged: the existing entry points.
+ * libjpeg's shortcut for a column without AC terms gives the same values and needs no case of its own; where libjpeg limits
+ * the range through a masked table (which wraps for absurd inputs) the definition here is the clamp.  EVERY component is
+ * scaled by the same s: a decoded plane of blocks_w * 8 x blocks_h * 8 samples becomes blocks_w * N x blocks_h * N.  This is
+ * NOT what libjpeg does with a subsampled file, where it decodes the chroma planes at a larger N in place of upsampling
+ * them: here a 4:2:0 file at s = 2 gives 4:2:0 planes of half the size, and the RGB form upsamples those.
+ * The GPU computes blocks within a proven bound in int32 and the others in int64 in the same kernel (hvc_last_wide_blocks
+ * counts the latter); both give the definition's value for every int16 coefficient and every 16-bit table entry.
+ * There is no Hardcaml RTL form: with HVC_ARITH_HARDCAML set, the entry points below return HVC_E_INVALID_ARG for s > 1 and
+ * leave their output untouched.  Any other scale_denom is HVC_E_INVALID_ARG.
+ *
+ * hvc_jpeg_scaled_info (host only): *out = *info at 1/s: width, height and every actual_* become ceil(x * N / 8), every
+ *   decoded_* becomes x * N / 8; the layout is tight (stride = blocks_w * N, planes back to back) and pixel_bytes its size;
+ *   tables, coef_count and the coefficient offsets are unchanged, layout[].blocks_* stay in blocks.
+ * hvc_decode_frames_scaled: hvc_decode_frames whose comps[].plane_offset / .stride describe the scaled planes.  These accept
+ *   any stride >= blocks_w * N, any plane_offset and any pixel_frame_stride >= the record's span (rows that all start on
+ *   4-byte boundaries are written as dwords, others byte by byte); the coefficients' alignment rules are hvc_decode_frames'.
+ *   s = 1 is hvc_decode_frames with all its rules.  A device-memory call honours hvc_set_profiling.
+ * hvc_jpeg_decode_scaled: one file, read on the host; *info receives the scaled info, pixels (pixel_cap >= its pixel_bytes)
+ *   the scaled padded planes.  Honours hvc_set_restart_markers.  At s > 1 a file with a block whose absolute DC does not
+ *   fit int16 is HVC_E_RANGE here and in the two below (as for the entry points that return records: the scaled block stage
+ *   keeps no side list of such blocks).  s = 1 is hvc_jpeg_decode / hvc_jpeg_decode_rgb / the full-size batch pipelines
+ *   themselves, which decode such a file as the model does.
+ * hvc_jpeg_decode_scaled_rgb: the same, then the JFIF colour conversion of hvc_jpeg_decode_rgb over the scaled info's width
+ *   x height; samplings and refusals as there.
+ * hvc_jpeg_decode_batch_scaled: hvc_jpeg_decode_batch (gpu_reader = 0) or hvc_jpeg_decode_batch_gpu (gpu_reader != 0) with
+ *   the scaled block stage per chunk; frames are scaled records pixel_frame_stride >= pixel_bytes apart.  Full-size planes
+ *   exist nowhere; behind the GPU reader the 1/8 decode reads nothing but the compact DC array.  With hvc_set_profiling on,
+ *   the scaled block stage of every chunk (s > 1) takes an entry of the ring: hvc_kernel_ms_history(n = chunks) after the
+ *   call holds k_decode_scaled's time per chunk (the full-size pipelines take none). */
+HVC_API int hvc_jpeg_scaled_info(const hvc_jpeg_info *info, int scale_denom, hvc_jpeg_info *out);
+HVC_API int hvc_decode_frames_scaled(hvc_ctx *ctx, const int16_t *coefs, size_t coef_frame_stride, const uint16_t *qtabs,
+                                     int n_qtabs, const hvc_component *comps, int n_comp, int n_frames, int scale_denom,
+                                     uint8_t *pixels, size_t pixel_frame_stride, int where);
+HVC_API int hvc_jpeg_decode_scaled(hvc_ctx *ctx, const uint8_t *jpeg, size_t n, int scale_denom, hvc_jpeg_info *info,
+                                   uint8_t *pixels, size_t pixel_cap);
+HVC_API int hvc_jpeg_decode_scaled_rgb(hvc_ctx *ctx, const uint8_t *jpeg, size_t n, int scale_denom, hvc_jpeg_info *info,
+                                       uint8_t *rgb, size_t rgb_cap, size_t rgb_row_stride, int layout);
+HVC_API int hvc_jpeg_decode_batch_scaled(hvc_ctx *ctx, const uint8_t *const *jpegs, const size_t *sizes, int n_frames,
+                                         int threads, int frames_per_chunk, int gpu_reader, int scale_denom, uint8_t *pixels,
+                                         size_t pixel_frame_stride, int where, hvc_batch_stats *stats);
+
 /* K5 (no counterpart in the reference): what a benchmark or a pipeline produced, said in
  * 64 bits per record without bringing the records back.  For r < n_records
  *     sums[r] = SUM_i (byte_i + 1) * ((2 i + 1) * 0x9E3779B97F4A7C15)   mod 2^64,  i = byte index in record r

@@ -196,14 +196,37 @@ class t {
     std::string bits_;
     std::vector<uint8_t> pixels_;
     bool decoded_ = false;
+    int side_ = 8; /* samples per block side of pixels_: 8, or 8 / scale_denom after decode_scaled */
+
+    hvc_jpeg_info file_info() const { /* the file's own geometry, whatever header_ holds by now */
+        hvc_jpeg_info own;
+        check(hvc_jpeg_read_header(reinterpret_cast<const uint8_t *>(bits_.data()), bits_.size(), &own), "Decoder.header");
+        return own;
+    }
 
   public:
     t(Ctx &ctx, Header header, std::string bits) : ctx_(&ctx), header_(std::move(header)), bits_(std::move(bits)) {}
     void decode() { /* Decoder.decode (decoder.ml:397): Huffman on the host, the block stage on the GPU */
-        pixels_.assign(header_.info.pixel_bytes ? header_.info.pixel_bytes : 1, 0);
+        const hvc_jpeg_info own = file_info(); /* (header_ may describe an earlier decode_scaled) */
+        pixels_.assign(own.pixel_bytes ? own.pixel_bytes : 1, 0);
         check(hvc_jpeg_decode(ctx_->get(), reinterpret_cast<const uint8_t *>(bits_.data()), bits_.size(), &header_.info,
                               pixels_.data(), pixels_.size()),
               "Decoder.decode");
+        side_ = 8;
+        decoded_ = true;
+    }
+    /* An extension (hvc_jpeg.h, "Decoding at reduced size"): decode at 1 / scale_denom (2, 4, 8; 1 = decode()).  header() then
+     * describes the scaled frame, and get_decoded_planes / get_yuv_frame return planes of that size; a later decode() or
+     * decode_scaled() starts from the file again. */
+    void decode_scaled(int scale_denom) {
+        const hvc_jpeg_info own = file_info();
+        hvc_jpeg_info scaled;
+        check(hvc_jpeg_scaled_info(&own, scale_denom, &scaled), "Decoder.decode_scaled");
+        pixels_.assign(scaled.pixel_bytes ? scaled.pixel_bytes : 1, 0);
+        check(hvc_jpeg_decode_scaled(ctx_->get(), reinterpret_cast<const uint8_t *>(bits_.data()), bits_.size(), scale_denom,
+                                     &header_.info, pixels_.data(), pixels_.size()),
+              "Decoder.decode_scaled");
+        side_ = 8 / scale_denom;
         decoded_ = true;
     }
     std::vector<Plane> get_decoded_planes() const { /* padded planes (decoder.ml:399-401) */
@@ -211,7 +234,7 @@ class t {
         std::vector<Plane> out;
         for (int i = 0; i < header_.info.n_comp; i++) {
             const hvc_component &L = header_.info.layout[i];
-            Plane p = Plane::create(L.blocks_w * 8, L.blocks_h * 8);
+            Plane p = Plane::create(L.blocks_w * side_, L.blocks_h * side_);
             for (int y = 0; y < p.height(); y++)
                 for (int x = 0; x < p.width(); x++) p.set(x, y, pixels_[L.plane_offset + (size_t)y * L.stride + x]);
             out.push_back(std::move(p));

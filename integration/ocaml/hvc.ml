@@ -763,6 +763,48 @@ let jpeg_decode_batch_rgb =
     @-> int @-> ptr Batch_stats.t @-> returning int)
 ;;
 
+(* Decoding at 1/2, 1/4, 1/8 size (include/hvc_jpeg.h, "Decoding at reduced size"): scale_denom = 1 | 2 | 4 | 8.
+   int hvc_jpeg_scaled_info(info, scale_denom, out)                                                          host only *)
+let jpeg_scaled_info =
+  foreign "hvc_jpeg_scaled_info" (ptr Jpeg_info.t @-> int @-> ptr Jpeg_info.t @-> returning int)
+;;
+
+(* int hvc_decode_frames_scaled(ctx, coefs, coef_frame_stride, qtabs, n_qtabs, comps, n_comp, n_frames, scale_denom, pixels,
+                                pixel_frame_stride, where) *)
+let decode_frames_scaled =
+  foreign
+    "hvc_decode_frames_scaled"
+    ~release_runtime_lock:true
+    (ctx @-> ptr int16_t @-> size_t @-> ptr uint16_t @-> int @-> ptr Component.t @-> int @-> int @-> int
+    @-> ptr char @-> size_t @-> int @-> returning int)
+;;
+
+(* int hvc_jpeg_decode_scaled(ctx, jpeg, n, scale_denom, info, pixels, pixel_cap) *)
+let jpeg_decode_scaled =
+  foreign
+    "hvc_jpeg_decode_scaled"
+    ~release_runtime_lock:true
+    (ctx @-> string @-> size_t @-> int @-> ptr Jpeg_info.t @-> ptr char @-> size_t @-> returning int)
+;;
+
+(* int hvc_jpeg_decode_scaled_rgb(ctx, jpeg, n, scale_denom, info, rgb, rgb_cap, rgb_row_stride, layout) *)
+let jpeg_decode_scaled_rgb =
+  foreign
+    "hvc_jpeg_decode_scaled_rgb"
+    ~release_runtime_lock:true
+    (ctx @-> string @-> size_t @-> int @-> ptr Jpeg_info.t @-> ptr char @-> size_t @-> size_t @-> int @-> returning int)
+;;
+
+(* int hvc_jpeg_decode_batch_scaled(ctx, jpegs, sizes, n_frames, threads, frames_per_chunk, gpu_reader, scale_denom, pixels,
+                                    pixel_frame_stride, where, stats) *)
+let jpeg_decode_batch_scaled =
+  foreign
+    "hvc_jpeg_decode_batch_scaled"
+    ~release_runtime_lock:true
+    (ctx @-> ptr string @-> ptr size_t @-> int @-> int @-> int @-> int @-> int @-> ptr char @-> size_t @-> int
+    @-> ptr Batch_stats.t @-> returning int)
+;;
+
 (* int hvc_jpeg_encode_rgb(ctx, rgb, rgb_row_stride, layout, width, height, chroma, quality, out, cap, out_len) *)
 let jpeg_encode_rgb =
   foreign

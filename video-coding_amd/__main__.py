@@ -5,6 +5,7 @@
     python -m video_coding_amd model encode frame IN.yuv WxH OUT.jpg [-quality 75] [-chroma 420] [-restart-interval N]
                                                                                   jpeg/bin/model.ml:86-109
     python -m video_coding_amd model decode frame IN.jpg OUT.ppm -rgb       the RGB image as a binary PPM (P6)
+    python -m video_coding_amd model decode frame IN.jpg OUT -scale 2|4|8   at reduced size: the cropped scaled planes (with -rgb: the PPM)
     python -m video_coding_amd model encode frame IN.ppm WxH OUT.jpg -rgb   from a binary PPM of that size
                                                       (an extension: JFIF colour conversion, hvc_jpeg_decode_rgb / _encode_rgb)
     python -m video_coding_amd oyuv compare {max-difference,mean-difference,mean-square-error,psnr}
@@ -92,17 +93,22 @@ def read_ppm(path, size):
 def model_decode_frame(a):
     if a.rgb and a.yuv444:
         raise SystemExit("-rgb and -yuv444 name two different outputs")
+    if a.scale != 1 and a.yuv444:
+        raise SystemExit("-scale and -yuv444 cannot be combined (the fused 4:4:4 path decodes at full size)")
     data = open(a.bits, "rb").read()
     ctx = hvc.Context(a.device)
     try:
         if a.restart_markers:
             ctx.set_restart_markers(True)
         if a.rgb:
-            info, image = ctx.jpeg_decode_rgb(data)
+            info, image = ctx.jpeg_decode_rgb(data) if a.scale == 1 else ctx.jpeg_decode_scaled_rgb(data, a.scale)
             out = np.concatenate([np.frombuffer(b"P6\n%d %d\n255\n" % (info.width, info.height), dtype=np.uint8), image.reshape(-1)])
         elif a.yuv444:
             _, frame = ctx.jpeg_decode_yuv444(data)
             out = frame.reshape(-1)
+        elif a.scale != 1:
+            info, pixels = ctx.jpeg_decode_scaled(data, a.scale)
+            out = hvc.jpeg_get_cropped_planes(info, pixels)  # every component's crop to its scaled actual size
         else:
             info, pixels = ctx.jpeg_decode(data)
             out = hvc.jpeg_get_yuv_frame(info, pixels)  # Decoder.get_yuv_frame: crop to the actual size
@@ -392,6 +398,8 @@ def parser():
     p.add_argument("-restart-markers", dest="restart_markers", action="store_true",
                    help="honour DRI + RSTn (hvc_set_restart_markers); off: the model's reading, the first interval only")
     p.add_argument("-rgb", action="store_true", help="write the RGB image as a binary PPM (hvc_jpeg_decode_rgb)")
+    p.add_argument("-scale", type=int, default=1, choices=[1, 2, 4, 8],
+                   help="decode at 1/2, 1/4 or 1/8 size (hvc_jpeg_decode_scaled / _scaled_rgb): the cropped scaled planes, or with -rgb the PPM")
     p.set_defaults(fn=model_decode_frame)
     enc = model.add_parser("encode").add_subparsers(dest="what", required=True)
     p = enc.add_parser("frame")

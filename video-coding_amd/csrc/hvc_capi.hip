@@ -97,15 +97,15 @@ int frames_per_launch(int n_frames, unsigned long long blocks_per_frame) {
     return (int)(((unsigned long long)n_frames + parts - 1) / parts);
 }
 
-int make_layout(const hvc_component *comps, int n_comp, int n_qtabs, Layout &L) {
+int make_layout(const hvc_component *comps, int n_comp, int n_qtabs, Layout &L, int n) {
     if (!comps || n_comp < 1 || n_comp > HVC_MAX_COMP) return HVC_E_INVALID_ARG;
     L.n_comp = n_comp;
     int tile = 0;
     for (int i = 0; i < n_comp; i++) {
         const hvc_component &c = comps[i];
         if (c.blocks_w < 1 || c.blocks_h < 1 || c.qtab < 0 || c.qtab >= n_qtabs) return HVC_E_INVALID_ARG;
-        if (c.stride < (size_t)c.blocks_w * 8) return HVC_E_INVALID_ARG;
-        if ((c.stride & 7) || (c.plane_offset & 7) || (c.coef_offset & 7)) return HVC_E_ALIGNMENT;
+        if (c.stride < (size_t)c.blocks_w * n) return HVC_E_INVALID_ARG;
+        if ((n == 8 && ((c.stride & 7) || (c.plane_offset & 7))) || (c.coef_offset & 7)) return HVC_E_ALIGNMENT;
         unsigned long long nblk = (unsigned long long)c.blocks_w * (unsigned long long)c.blocks_h;
         if (nblk * (unsigned long long)c.blocks_w >= (1ull << 32) || nblk >= (1ull << 31)) return HVC_E_TOO_LARGE;
         hvc::CompK &k = L.comp[i];
@@ -120,7 +120,7 @@ int make_layout(const hvc_component *comps, int n_comp, int n_qtabs, Layout &L) 
         k.stride = c.stride;
         tile += (int)((nblk + HVC_TILE - 1) / HVC_TILE);
         size_t ce = c.coef_offset + (size_t)nblk * 64;
-        size_t pe = c.plane_offset + ((size_t)c.blocks_h * 8 - 1) * c.stride + (size_t)c.blocks_w * 8;
+        size_t pe = c.plane_offset + ((size_t)c.blocks_h * n - 1) * c.stride + (size_t)c.blocks_w * n;
         if (ce > L.coef_span) L.coef_span = ce;
         if (pe > L.pixel_span) L.pixel_span = pe;
         L.blocks_per_frame += nblk;
@@ -967,6 +967,98 @@ int hvc_decode_frames(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const ui
                       const hvc_component *comps, int n_comp, int n_frames, uint8_t *pixels, size_t pixel_fs,
                       int where) try {
     return decode_frames_impl(c, coefs, coef_fs, qtabs, n_qtabs, comps, n_comp, n_frames, pixels, pixel_fs, where, DecodeOpts(c));
+} HVC_ABI_CATCH
+
+// ---------------------------------------------------------------------------
+// The block stage at 1/2, 1/4, 1/8 size (include/hvc_jpeg.h, "Decoding at reduced size"): k_decode_scaled writes planes of
+// blocks_w * N x blocks_h * N samples, N = 8 / scale_denom, wherever the caller put them -- any offset, any stride.  Rows
+// that all start on 4-byte boundaries take the kernel's dword stores, anything else its byte stores.
+int decode_frames_scaled_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
+                              const hvc_component *comps_in, int n_comp_in, int n_frames, int scale_denom, uint8_t *pixels,
+                              size_t pixel_fs, int where, const DecodeOpts &o) {
+    const int N = scaled_side(scale_denom);
+    if (!c || !N) return HVC_E_INVALID_ARG;
+    if (N == 8) return decode_frames_impl(c, coefs, coef_fs, qtabs, n_qtabs, comps_in, n_comp_in, n_frames, pixels, pixel_fs, where, o);
+    if (o.arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the scaled path: hvc_set_arithmetic)
+    if (n_frames < 0 || (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE)) return HVC_E_INVALID_ARG;
+    int r = check_qtabs(qtabs, n_qtabs, false);
+    if (r) return r;
+    hvc_component kept[HVC_MAX_COMP];
+    int n_comp = 0;
+    if ((r = drop_empty_components(comps_in, n_comp_in, kept, &n_comp))) return r;
+    if (n_comp == 0) return HVC_OK;
+    const hvc_component *const comps = kept;
+    if (!coefs || !pixels) return HVC_E_INVALID_ARG;
+    Layout L;
+    if ((r = make_layout(comps, n_comp, n_qtabs, L, N))) return r;
+    if (n_frames == 0) return HVC_OK;
+    if (n_frames > 1 && (coef_fs < L.coef_span || pixel_fs < L.pixel_span)) return HVC_E_INVALID_ARG;
+    if (coef_fs & 7) return HVC_E_ALIGNMENT;
+    const int per = frames_per_launch_capped(n_frames, L.blocks_per_frame, (unsigned long long)L.tiles_per_frame * HVC_TILE);
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+
+    hvc::DecodeParams P;
+    fill_geometry(P, L, coef_fs, pixel_fs, n_frames);
+    for (int i = 0; i < n_qtabs * 64; i++) P.qt[i] = (int)qtabs[i];
+    P.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count + 2);
+    wide_total_begin(c); // hvc_last_wide_blocks: the launches add the blocks of their int64 branch to a total cleared here
+    bool rows_on_dwords = ((n_frames > 1 ? pixel_fs : 0) & 3) == 0;
+    for (int i = 0; i < n_comp; i++) rows_on_dwords &= ((comps[i].plane_offset | comps[i].stride) & 3) == 0;
+
+    auto launch_range = [&](const int16_t *d_coefs, uint8_t *d_pixels, int f0, int cnt, hipEvent_t k0, hipEvent_t k1) {
+        const bool dwords = rows_on_dwords && ((uintptr_t)d_pixels & 3) == 0;
+        return for_each_launch(f0, cnt, per, k0, k1, [&](int f, int n, hipEvent_t e0, hipEvent_t e1) {
+            hvc::DecodeParams Pk = P;
+            Pk.n_frames = n;
+            Pk.coefs = d_coefs + (size_t)f * coef_fs;
+            Pk.pixels = d_pixels + (size_t)f * pixel_fs;
+            Pk.dc_plane = o.dc_plane ? o.dc_plane + (size_t)f * o.dc_fs : nullptr;
+            Pk.dc_fs = o.dc_fs;
+            return hvc::launch_decode_scaled(Pk, N, dwords, c->stream, e0, e1);
+        });
+    };
+
+    if (where == HVC_MEM_DEVICE) {
+        if ((uintptr_t)coefs & 15) return HVC_E_ALIGNMENT;
+        HIPCHK(c, hipMemsetAsync(P.wide_total, 0, sizeof *P.wide_total, c->stream));
+        const int slot = (int)(c->k_calls % HVC_PROF_RING);
+        HIPCHK(c, launch_range(coefs, pixels, 0, n_frames, o.profile ? c->k0[slot] : nullptr, o.profile ? c->k1[slot] : nullptr));
+        if (o.profile) c->k_calls++;
+        return HVC_OK;
+    }
+    if (o.dc_plane) return HVC_E_INVALID_ARG;
+
+    // host memory: the caller's record layout mirrored on the device; only the samples the kernel wrote come back
+    const size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + L.coef_span) * sizeof(int16_t);
+    const size_t pbytes = (size_t)(n_frames - 1) * pixel_fs + L.pixel_span;
+    return through_device(
+        c, n_frames, cbytes, pbytes, cbytes, false,
+        [&](int f0, int cnt) {
+            const hipError_t e = hipMemsetAsync(P.wide_total, 0, sizeof *P.wide_total, c->stream);
+            if (e != hipSuccess) return e;
+            return hipMemcpyAsync((int16_t *)c->d_in + (size_t)f0 * coef_fs, coefs + (size_t)f0 * coef_fs,
+                                  ((size_t)(cnt - 1) * coef_fs + L.coef_span) * sizeof(int16_t), hipMemcpyHostToDevice, c->stream);
+        },
+        [&](int f0, int cnt) { return launch_range((const int16_t *)c->d_in, (uint8_t *)c->d_out, f0, cnt, nullptr, nullptr); },
+        [&](int f0, int cnt, hipStream_t st) {
+            for (int f = f0; f < f0 + cnt; f++)
+                for (int i = 0; i < n_comp; i++) {
+                    const hvc_component &k = comps[i];
+                    const size_t off = (size_t)f * pixel_fs + k.plane_offset;
+                    const hipError_t e = hipMemcpy2DAsync(pixels + off, k.stride, (const uint8_t *)c->d_out + off, k.stride,
+                                                          (size_t)k.blocks_w * N, (size_t)k.blocks_h * N, hipMemcpyDeviceToHost, st);
+                    if (e != hipSuccess) return e;
+                }
+            return hipSuccess;
+        });
+}
+
+int hvc_decode_frames_scaled(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
+                             const hvc_component *comps, int n_comp, int n_frames, int scale_denom, uint8_t *pixels, size_t pixel_fs,
+                             int where) try {
+    return decode_frames_scaled_impl(c, coefs, coef_fs, qtabs, n_qtabs, comps, n_comp, n_frames, scale_denom, pixels, pixel_fs, where,
+                                     DecodeOpts(c));
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------

@@ -240,6 +240,123 @@ int hvc_jpeg_decode_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info
     return HVC_OK;
 } HVC_ABI_CATCH
 
+// ---------------------------------------------------------------------------
+// Decoding at reduced size (include/hvc_jpeg.h): the geometry, one file to planes, one file to RGB, a batch
+
+void scaled_info(const hvc_jpeg_info &in, int n, hvc_jpeg_info &out) {
+    const hvc_jpeg_info src = in; // (in and out may be one object)
+    auto up = [n](int x) { return (int)(((long long)x * n + 7) / 8); };
+    out = src;
+    out.width = up(src.width);
+    out.height = up(src.height);
+    size_t at = 0;
+    for (int i = 0; i < src.n_comp && i < 4; i++) {
+        hvc_jpeg_component &k = out.comp[i];
+        k.actual_width = up(src.comp[i].actual_width);
+        k.actual_height = up(src.comp[i].actual_height);
+        k.decoded_width = src.comp[i].decoded_width / 8 * n;
+        k.decoded_height = src.comp[i].decoded_height / 8 * n;
+        hvc_component &l = out.layout[i];
+        l.stride = l.blocks_w > 0 ? (size_t)l.blocks_w * n : 0;
+        l.plane_offset = at;
+        if (l.blocks_w > 0 && l.blocks_h > 0) at += (size_t)l.blocks_w * n * (size_t)l.blocks_h * n;
+    }
+    out.pixel_bytes = at;
+}
+
+int hvc_jpeg_scaled_info(const hvc_jpeg_info *info, int scale_denom, hvc_jpeg_info *out) try {
+    const int N = scaled_side(scale_denom);
+    if (!info || !out || !N || info->n_comp < 0 || info->n_comp > 4) return HVC_E_INVALID_ARG;
+    scaled_info(*info, N, *out);
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+// header + host reader of one file for the scaled entry points: *info = the SCALED info, `full` the file's own, `coefs` its record
+static int read_for_scaled(hvc_ctx *c, const uint8_t *jpeg, size_t n, int scale_denom, hvc_jpeg_info *info, hvc_jpeg_info &full,
+                           std::vector<int16_t> &coefs) {
+    if (!scaled_side(scale_denom)) return HVC_E_INVALID_ARG;
+    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the scaled path)
+    int r = hvc_jpeg_read_header(jpeg, n, &full);
+    if (r) return r;
+    scaled_info(full, scaled_side(scale_denom), *info);
+    try {
+        coefs.resize(full.coef_count);
+    } catch (const std::bad_alloc &) {
+        return HVC_E_OUT_OF_MEMORY;
+    }
+    return HVC_OK;
+}
+// (after the caller's checks of its output's size) the record: HVC_E_RANGE where a block's absolute DC leaves int16
+static int entropy_for_scaled(const uint8_t *jpeg, size_t n, const hvc_jpeg_info &full, std::vector<int16_t> &coefs) {
+    std::vector<hvc::WideDc> wide;
+    const int r = hvc::entropy_decode_wide(jpeg, n, &full, coefs.data(), wide);
+    return r ? r : wide.empty() ? HVC_OK : HVC_E_RANGE;
+}
+
+int hvc_jpeg_decode_scaled(hvc_ctx *c, const uint8_t *jpeg, size_t n, int scale_denom, hvc_jpeg_info *info, uint8_t *pixels,
+                           size_t pixel_cap) try {
+    if (!c || !jpeg || !info) return HVC_E_INVALID_ARG;
+    if (scale_denom == 1) return hvc_jpeg_decode(c, jpeg, n, info, pixels, pixel_cap); // full size: that call, with all its rules
+    hvc::RestartScope honour(c->honour_restart); // (hvc_set_restart_markers; off = the model's behaviour)
+    hvc_jpeg_info full;
+    std::vector<int16_t> coefs;
+    int r = read_for_scaled(c, jpeg, n, scale_denom, info, full, coefs);
+    if (r) return r;
+    if (pixel_cap < info->pixel_bytes || (!pixels && info->pixel_bytes)) return HVC_E_INVALID_ARG;
+    if ((r = entropy_for_scaled(jpeg, n, full, coefs))) return r;
+    return decode_frames_scaled_impl(c, coefs.data(), full.coef_count, &full.qtabs[0][0], full.n_qtabs, info->layout, full.n_comp, 1,
+                                     scale_denom, pixels, info->pixel_bytes, HVC_MEM_HOST, DecodeOpts(c));
+} HVC_ABI_CATCH
+
+int hvc_jpeg_decode_scaled_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, int scale_denom, hvc_jpeg_info *info, uint8_t *rgb,
+                               size_t rgb_cap, size_t rgb_row_stride, int layout) try {
+    if (!c || !jpeg || !info || !rgb) return HVC_E_INVALID_ARG;
+    if (scale_denom == 1) return hvc_jpeg_decode_rgb(c, jpeg, n, info, rgb, rgb_cap, rgb_row_stride, layout); // full size: that call
+    hvc::RestartScope honour(c->honour_restart);
+    hvc_jpeg_info full;
+    std::vector<int16_t> coefs;
+    int r = read_for_scaled(c, jpeg, n, scale_denom, info, full, coefs);
+    if (r) return r;
+    const int sampling = rgb_sampling_of(full);
+    RgbImage im;
+    if (!sampling || !rgb_image(layout, info->width, info->height, rgb_row_stride, 0, im)) return HVC_E_INVALID_ARG;
+    if (rgb_cap < rgb_bytes(im, 1)) return HVC_E_INVALID_ARG;
+    if ((r = entropy_for_scaled(jpeg, n, full, coefs))) return r;
+    if (info->width == 0 || info->height == 0 || info->pixel_bytes == 0) return HVC_OK; // a frame without a sample
+    int cw, ch;
+    rgb_chroma_window(sampling, info->width, info->height, cw, ch);
+    // the window lies inside the scaled decoded chroma planes: the MCU-rounded size divided by scale_denom is even
+    if (sampling != HVC_YUV_400 && (cw > info->comp[1].decoded_width || ch > info->comp[1].decoded_height ||
+                                    cw > info->comp[2].decoded_width || ch > info->comp[2].decoded_height))
+        return HVC_E_INTERNAL;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    const size_t cb = full.coef_count * sizeof(int16_t);
+    if ((r = grow(c, &c->d_aux, &c->aux_cap, info->pixel_bytes))) return r;
+    if ((r = grow(c, &c->d_aux2, &c->aux2_cap, rgb_bytes(im, 1)))) return r;
+    if ((r = grow(c, &c->d_in, &c->in_cap, cb))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_in, coefs.data(), cb, hipMemcpyHostToDevice, c->stream));
+    DecodeOpts o(c);
+    o.profile = false;
+    if ((r = decode_frames_scaled_impl(c, (const int16_t *)c->d_in, full.coef_count, &full.qtabs[0][0], full.n_qtabs, info->layout,
+                                       full.n_comp, 1, scale_denom, (uint8_t *)c->d_aux, info->pixel_bytes, HVC_MEM_DEVICE, o)))
+        return r;
+    HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, info->pixel_bytes, info->layout, sampling, info->width, info->height, cw, ch, 1,
+                                (uint8_t *)c->d_aux2, im, c->stream));
+    HIPCHK(c, rgb_download((const uint8_t *)c->d_aux2, rgb, im, 1, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_jpeg_decode_batch_scaled(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads,
+                                 int frames_per_chunk, int gpu_reader, int scale_denom, uint8_t *pixels, size_t pixel_fs, int where,
+                                 hvc_batch_stats *stats) try {
+    if (!c || !scaled_side(scale_denom)) return HVC_E_INVALID_ARG;
+    if (scale_denom != 1 && c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the scaled path)
+    return gpu_reader ? decode_batch_gpu(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, false, scale_denom)
+                      : decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, false, scale_denom);
+} HVC_ABI_CATCH
+
 // Encoder.encode_420/422/444 (encoder.ml:512-541)
 
 // The device half of hvc_jpeg_encode / hvc_jpeg_encode_rgb: scratch for one frame (padded planes c->d_in, records c->d_out,
@@ -352,11 +469,15 @@ int hvc_jpeg_encode_rgb(hvc_ctx *c, const uint8_t *rgb, size_t rgb_row_stride, i
 // BASELINE config 3: host Huffman || hipMemcpyAsync (copy stream) || block-stage kernel (compute stream)
 
 // yuv444 = false: padded component planes per frame (hvc_jpeg_decode_batch);
-// yuv444 = true: tight 4:4:4 frames through the fused kernel (hvc_jpeg_decode_batch_yuv444)
+// yuv444 = true: tight 4:4:4 frames through the fused kernel (hvc_jpeg_decode_batch_yuv444);
+// scale_denom = 2, 4, 8 (never with yuv444): the scaled planes of hvc_jpeg_scaled_info per frame, tight, through the scaled
+// block stage (hvc_jpeg_decode_batch_scaled) -- a file whose DC leaves int16 is HVC_E_RANGE there
 int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads,
                              int frames_per_chunk, uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats,
-                             bool yuv444) {
+                             bool yuv444, int scale_denom) {
     if (!c || !jpegs || !sizes || !pixels || n_frames < 0) return HVC_E_INVALID_ARG;
+    const bool scaled = scale_denom != 1;
+    if (scaled && (yuv444 || scaled_side(scale_denom) == 0)) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_frames == 0) return HVC_OK;
@@ -365,8 +486,10 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
     int r = hvc_jpeg_read_header(jpegs[0], sizes[0], &info0);
     if (r) return r;
     if (yuv444 && (!is_420_scan(info0) || (info0.width & 1) || (info0.height & 1))) return HVC_E_INVALID_ARG;
-    const size_t out_bytes = yuv444 ? (size_t)3 * info0.width * info0.height : info0.pixel_bytes; // per frame
-    if (pixel_fs < out_bytes || (!yuv444 && (pixel_fs & 7))) return HVC_E_INVALID_ARG;
+    hvc_jpeg_info sinfo0 = info0; // the output's geometry: info0's, or its scaled form
+    if (scaled) scaled_info(info0, scaled_side(scale_denom), sinfo0);
+    const size_t out_bytes = yuv444 ? (size_t)3 * info0.width * info0.height : sinfo0.pixel_bytes; // per frame
+    if (pixel_fs < out_bytes || (!yuv444 && !scaled && (pixel_fs & 7))) return HVC_E_INVALID_ARG;
     if (info0.coef_count == 0) { // frames without a block (a width or height of zero): nothing to upload, nothing to launch --
         for (int f = 0; f < n_frames; f++) { // every file is still read as the model reads it (headers, tables)
             hvc_jpeg_info fi;
@@ -539,9 +662,12 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
         if (he != hipSuccess) { rc = fail_hip(c, he); break; }
         he = hipEventRecord(c->ev_t[1], compute);
         DecodeOpts o(c);
-        o.profile = false;
+        o.profile = scaled && c->profiling; // (a scaled chunk's block stage takes a ring entry: hvc_jpeg_decode_batch_scaled)
         o.wide = &chunk_wide[(size_t)k]; // (complete: the chunk's workers are done)
-        rc = yuv444 ? decode_frames_yuv444_impl(c, (const int16_t *)c->d_ring[slot], info0.coef_count, &info0.qtabs[0][0],
+        if (scaled && !o.wide->empty()) { rc = HVC_E_RANGE; break; } // (no side list in the scaled block stage)
+        rc = scaled ? decode_frames_scaled_impl(c, (const int16_t *)c->d_ring[slot], info0.coef_count, &info0.qtabs[0][0], info0.n_qtabs,
+                                                sinfo0.layout, info0.n_comp, cnt, scale_denom, dst, dst_fs, HVC_MEM_DEVICE, o)
+           : yuv444 ? decode_frames_yuv444_impl(c, (const int16_t *)c->d_ring[slot], info0.coef_count, &info0.qtabs[0][0],
                                                 info0.n_qtabs, info0.layout, info0.n_comp, cnt, info0.width, info0.height,
                                                 dst, dst_fs, HVC_MEM_DEVICE, o)
                     : decode_frames_impl(c, (const int16_t *)c->d_ring[slot], info0.coef_count, &info0.qtabs[0][0],
@@ -611,7 +737,7 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
 
 int hvc_jpeg_decode_batch(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads,
                           int frames_per_chunk, uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats) try {
-    return decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, false);
+    return decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, false, 1);
 } HVC_ABI_CATCH
 
 int hvc_jpeg_decode_batch_yuv444(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames,
@@ -619,7 +745,7 @@ int hvc_jpeg_decode_batch_yuv444(hvc_ctx *c, const uint8_t *const *jpegs, const 
                                  hvc_batch_stats *stats) try {
     if (c && c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path: hvc_set_arithmetic)
     return decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, frames, frame_stride, where, stats,
-                             true);
+                             true, 1);
 } HVC_ABI_CATCH
 
 // hvc_jpeg_decode_batch_rgb: the batch pipelines as they are (host reader or GPU reader, whichever `gpu_reader` names), their

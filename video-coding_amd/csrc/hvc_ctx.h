@@ -34,6 +34,7 @@
 #include "hvc_huff.h"
 #include "hvc_kernels.h"
 #include "hvc_pool.h"
+#include "hvc_scaled_spec.h"
 
 #define HVC_PROF_RING 64
 #define HVC_FIX_WORDS 8 /* d_fix_count: [0] [1] counters, [2..3] the 64-bit total, [4] [5] the fused path's luma counters */
@@ -231,7 +232,9 @@ struct Layout {
     size_t pixel_span = 0; // bytes covered by one frame record
     unsigned long long blocks_per_frame = 0;
 };
-int make_layout(const hvc_component *comps, int n_comp, int n_qtabs, Layout &L);
+// n: samples per block side of the pixel planes -- 8, or 4 / 2 / 1 for the scaled block stage, whose planes (bw * n bytes
+// per row) may lie at any offset with any stride >= that
+int make_layout(const hvc_component *comps, int n_comp, int n_qtabs, Layout &L, int n = 8);
 int check_qtabs(const uint16_t *qtabs, int n_qtabs, bool divides); // divides: the encoder (an entry of zero is HVC_E_RANGE)
 
 // A component without a block (blocks_w or blocks_h of zero: the model's empty Plane.t) has no part in the block stage: the
@@ -345,6 +348,17 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
 int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
                               const hvc_component *comps, int n_comp, int n_frames, int width, int height, uint8_t *frames,
                               size_t frame_stride, int where, const DecodeOpts &o);
+// the block stage at 1 / scale_denom size (k_decode_scaled, hvc_scaled.hip) behind hvc_decode_frames_scaled and the file-level
+// scaled entry points; scale_denom = 1 is decode_frames_impl.  Of `o` it takes arith (HARDCAML: HVC_E_INVALID_ARG), profile,
+// dc_plane and dc_fs.
+int decode_frames_scaled_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
+                              const hvc_component *comps, int n_comp, int n_frames, int scale_denom, uint8_t *pixels, size_t pixel_fs,
+                              int where, const DecodeOpts &o);
+inline int scaled_side(int scale_denom) { // N = 8 / scale_denom, 0 for anything but 1, 2, 4, 8
+    return scale_denom == 1 || scale_denom == 2 || scale_denom == 4 || scale_denom == 8 ? 8 / scale_denom : 0;
+}
+// hvc_jpeg_scaled_info's arithmetic (hvc_capi_jpeg.hip); n = scaled_side(scale_denom) != 0
+void scaled_info(const hvc_jpeg_info &in, int n, hvc_jpeg_info &out);
 int encode_frames_impl(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const uint16_t *qtabs, int n_qtabs,
                        const hvc_component *comps, int n_comp, int n_frames, int16_t *coefs, size_t coef_fs, int where,
                        const EncodeOpts &o);
@@ -369,8 +383,13 @@ int gpu_entropy_decode(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *si
 
 // hvc_capi_jpeg.hip: the batch pipeline with the host reader (hvc_jpeg_decode_batch / _yuv444) -- also where the
 // pipeline with the GPU reader sends a batch it cannot take
+// scale_denom: 1 = full size (the block stage as it always was), 2 / 4 / 8 = the scaled block stage per chunk (not with yuv444)
 int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads,
-                      int frames_per_chunk, uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats, bool yuv444);
+                      int frames_per_chunk, uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats, bool yuv444,
+                      int scale_denom);
+// hvc_capi_reader.hip: the same with the GPU reader (behind hvc_jpeg_decode_batch_gpu)
+int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads, int frames_per_chunk,
+                     uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats, bool yuv444, int scale_denom);
 inline bool is_420_scan(const hvc_jpeg_info &info) { // Y 2x2, Cb / Cr 1x1 (frame.ml:42-61)
     return info.n_comp == 3 && info.comp[0].hscale == 2 && info.comp[0].vscale == 2 && info.comp[1].hscale == 1 &&
            info.comp[1].vscale == 1 && info.comp[2].hscale == 1 && info.comp[2].vscale == 1;

@@ -36,6 +36,8 @@ SYMBOLS = [
     "hvc_huffman_optimal_tables_restart", "hvc_huffman_encode_frames_restart",
     "hvc_yuv_to_rgb", "hvc_rgb_to_yuv", "hvc_decode_frames_rgb", "hvc_jpeg_decode_rgb", "hvc_jpeg_decode_batch_rgb",
     "hvc_jpeg_encode_rgb",
+    "hvc_jpeg_scaled_info", "hvc_decode_frames_scaled", "hvc_jpeg_decode_scaled", "hvc_jpeg_decode_scaled_rgb",
+    "hvc_jpeg_decode_batch_scaled",
 ]
 HVC_RGB = {"interleaved": 0, "planar": 1}  # enum hvc_rgb_layout: [H, W, 3] / [3, H, W]
 HVC_YUV_400 = 400   # luma only, beside 420 / 422 / 444
@@ -249,6 +251,12 @@ def lib():
         L.hvc_jpeg_decode_batch_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, i, i, vp, sz, sz, i, i,
                                                 C.POINTER(BatchStats)]
         L.hvc_jpeg_encode_rgb.argtypes = [vp, vp, sz, i, i, i, i, i, vp, sz, C.POINTER(sz)]
+        L.hvc_jpeg_scaled_info.argtypes = [ip, i, ip]
+        L.hvc_decode_frames_scaled.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, i, vp, sz, i]
+        L.hvc_jpeg_decode_scaled.argtypes = [vp, vp, sz, i, ip, vp, sz]
+        L.hvc_jpeg_decode_scaled_rgb.argtypes = [vp, vp, sz, i, ip, vp, sz, sz, i]
+        L.hvc_jpeg_decode_batch_scaled.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, i, i, i, vp, sz, i,
+                                                   C.POINTER(BatchStats)]
         L.hvc_checksum_records.argtypes = [vp, vp, sz, sz, i, vp, i]
         L.hvc_set_host_cpus.argtypes = [vp, C.c_char_p]
         L.hvc_get_host_cpus.argtypes = [vp, C.c_char_p, sz, C.POINTER(i)]
@@ -458,6 +466,13 @@ def jpeg_read_header(data: bytes):
     info = JpegInfo()
     _chk(lib().hvc_jpeg_read_header(data, len(data), C.byref(info)), "hvc_jpeg_read_header")
     return info
+
+
+def jpeg_scaled_info(info, scale_denom):
+    """the info of a file decoded at 1 / scale_denom (hvc_jpeg_scaled_info): sizes ceil(x * N / 8), tight scaled planes"""
+    out = JpegInfo()
+    _chk(lib().hvc_jpeg_scaled_info(C.byref(info), scale_denom, C.byref(out)), "hvc_jpeg_scaled_info")
+    return out
 
 
 def jpeg_entropy_decode(data: bytes, info=None, restart_markers=False):
@@ -1038,6 +1053,46 @@ class Context:
         _chk(lib().hvc_jpeg_decode_rgb(self._h, data, len(data), C.byref(info), out.ctypes.data, out.size, 0,
                                        _rgb_layout(layout)), "hvc_jpeg_decode_rgb")
         return info, out
+
+    # -- decoding at 1/2, 1/4, 1/8 size (include/hvc_jpeg.h, "Decoding at reduced size") ----------------------
+    def decode_frames_scaled(self, coefs, coef_frame_stride, qtabs, comps, n_frames, scale_denom, pixels, pixel_frame_stride):
+        """hvc_decode_frames at 1 / scale_denom: comps place planes of blocks_w * N x blocks_h * N samples, N = 8 / scale_denom"""
+        ca, w1 = _addr(coefs)
+        pa, w2 = _addr(pixels)
+        assert w1 == w2
+        q = np.ascontiguousarray(qtabs, dtype=np.uint16).reshape(-1, 64)
+        arr = comps if not isinstance(comps, list) else components(comps)
+        _chk(lib().hvc_decode_frames_scaled(self._h, ca, coef_frame_stride, q.ctypes.data, q.shape[0], arr, len(arr), n_frames,
+                                            scale_denom, pa, pixel_frame_stride, w1), "hvc_decode_frames_scaled")
+
+    def jpeg_decode_scaled(self, data: bytes, scale_denom):
+        """one file at 1 / scale_denom: (scaled info, its padded pixel record as numpy uint8)"""
+        info = jpeg_scaled_info(jpeg_read_header(data), scale_denom)
+        pixels = np.zeros(info.pixel_bytes, dtype=np.uint8)
+        _chk(lib().hvc_jpeg_decode_scaled(self._h, data, len(data), scale_denom, C.byref(info), pixels.ctypes.data, pixels.size),
+             "hvc_jpeg_decode_scaled")
+        return info, pixels
+
+    def jpeg_decode_scaled_rgb(self, data: bytes, scale_denom, layout="interleaved"):
+        """one file at 1 / scale_denom -> (scaled info, uint8 [h, w, 3] (interleaved) or [3, h, w] (planar))"""
+        info = jpeg_scaled_info(jpeg_read_header(data), scale_denom)
+        out = np.zeros(rgb_shape(layout, info.width, info.height), dtype=np.uint8)
+        _chk(lib().hvc_jpeg_decode_scaled_rgb(self._h, data, len(data), scale_denom, C.byref(info), out.ctypes.data, out.size, 0,
+                                              _rgb_layout(layout)), "hvc_jpeg_decode_scaled_rgb")
+        return info, out
+
+    def jpeg_decode_batch_scaled(self, jpegs, scale_denom, pixels, pixel_frame_stride, threads=8, frames_per_chunk=0,
+                                 gpu_entropy=False):
+        """a batch of files of one geometry -> scaled pixel records (numpy: host, torch CUDA tensor: device).  BatchStats."""
+        n = len(jpegs)
+        ptrs = (C.c_void_p * max(n, 1))(*[C.cast(C.c_char_p(j), C.c_void_p) for j in jpegs])
+        sizes = (C.c_size_t * max(n, 1))(*[len(j) for j in jpegs])
+        pa, where = _addr(pixels)
+        st = BatchStats()
+        _chk(lib().hvc_jpeg_decode_batch_scaled(self._h, ptrs, sizes, n, threads, frames_per_chunk, 1 if gpu_entropy else 0,
+                                                scale_denom, pa, pixel_frame_stride, where, C.byref(st)),
+             "hvc_jpeg_decode_batch_scaled")
+        return st
 
     def jpeg_decode_batch_rgb(self, jpegs, rgb, layout="interleaved", threads=8, frames_per_chunk=0, gpu_entropy=False,
                               rgb_row_stride=0, rgb_frame_stride=0):
