@@ -1,6 +1,8 @@
-// hvc_capi_jpeg.hip -- files through the C ABI: one at a time (hvc_jpeg_decode, hvc_jpeg_decode_yuv444, hvc_jpeg_decode_rgb,
-// hvc_jpeg_encode, hvc_jpeg_encode_rgb) and
-// BASELINE's configuration 3, the batch pipeline with the Huffman reader on the host (hvc_jpeg_decode_batch).
+// hvc_capi_jpeg.hip -- files through the C ABI.  One at a time: hvc_jpeg_decode, hvc_jpeg_decode_yuv444 and hvc_jpeg_decode_rgb
+// (one skeleton, decode_one_file, with a sink each), hvc_jpeg_decode_scaled and hvc_jpeg_decode_scaled_rgb (host reader only),
+// hvc_jpeg_encode, hvc_jpeg_encode_rgb.  Batches: BASELINE's configuration 3, the pipeline with the Huffman reader on the host
+// (decode_batch_impl behind hvc_jpeg_decode_batch, _batch_yuv444 and _batch_scaled), and hvc_jpeg_decode_batch_rgb over either
+// pipeline.
 #include "hvc_ctx.h"
 
 // ---------------------------------------------------------------------------
@@ -9,16 +11,16 @@
 // One file: Huffman reader on the GPU (hvc_hdec.hip) into device scratch; *used = 0 when the stream needs the
 // host decoder (nothing usable on the device then).
 static int single_frame_coefs_on_device(hvc_ctx *c, const uint8_t *jpeg, size_t n, const hvc_jpeg_info *info, int *used,
-                                        AfterReader *after = nullptr) {
+                                        AfterReader *after) {
     *used = 0;
     // Below ~128 kB the host reader is done before the GPU decoder's launches and synchronisations are
-    // (tools/bench_single.py on 1080p: 64 kB file 0.39 ms on the host vs 0.8 ms; 228 kB 1.7 vs 0.8 ms; 967 kB 3.9 vs 1.6 ms).
+    // (single calls on 1080p files: 64 kB file 0.39 ms on the host vs 0.8 ms; 228 kB 1.7 vs 0.8 ms; 967 kB 3.9 vs 1.6 ms).
     if (n < 128u * 1024u) return HVC_OK;
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
     int r = grow(c, &c->gd_coefs, &c->gd_coefs_cap, info->coef_count * sizeof(int16_t));
     if (r) return r;
-    if (after && c->decode_kernel != 1 && c->decode_kernel != 3) { // (the A/B alternates read the DC from the record)
+    if (c->decode_kernel != 1 && c->decode_kernel != 3) { // (the A/B alternates read the DC from the record)
         const size_t blocks = info->coef_count / 64;
         if ((r = grow(c, &c->gd_dcv, &c->gd_dcv_cap, ((blocks + 127) & ~(size_t)127) * sizeof(int16_t)))) return r;
         after->dc_plane = (int16_t *)c->gd_dcv;
@@ -27,198 +29,46 @@ static int single_frame_coefs_on_device(hvc_ctx *c, const uint8_t *jpeg, size_t 
     return gpu_entropy_decode(c, &jpeg, &n, 1, *info, (int16_t *)c->gd_coefs, info->coef_count, used, after);
 }
 
-// One frame whose record came from the host reader with blocks on the wide-DC list: upload, block stage, the int64
-// fix-up with the true DCs, download -- the model's output for a stream whose DC leaves int16 (decoder.ml:143).
-static int decode_one_with_wide_dc(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *coefs, const std::vector<hvc::WideDc> &wide,
-                                   bool yuv444, uint8_t *out) {
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    const size_t cb = info->coef_count * sizeof(int16_t);
-    const size_t ob = yuv444 ? (size_t)3 * info->width * info->height : info->pixel_bytes;
-    int r;
-    if ((r = grow(c, &c->d_in, &c->in_cap, cb))) return r;
-    if ((r = grow(c, &c->d_out, &c->out_cap, ob))) return r;
-    std::vector<WideFix> fix;
-    try {
-        for (const hvc::WideDc &w : wide) fix.push_back(WideFix{0, w.block, w.dc});
-    } catch (const std::bad_alloc &) {
-        return HVC_E_OUT_OF_MEMORY;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_in, coefs, cb, hipMemcpyHostToDevice, c->stream));
-    DecodeOpts o(c);
-    o.profile = false;
-    o.wide = &fix;
-    r = yuv444 ? decode_frames_yuv444_impl(c, (const int16_t *)c->d_in, info->coef_count, &info->qtabs[0][0], info->n_qtabs,
-                                           info->layout, info->n_comp, 1, info->width, info->height, (uint8_t *)c->d_out, ob,
-                                           HVC_MEM_DEVICE, o)
-               : decode_frames_impl(c, (const int16_t *)c->d_in, info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
-                                    info->n_comp, 1, (uint8_t *)c->d_out, info->pixel_bytes, HVC_MEM_DEVICE, o);
-    if (r) return r;
-    HIPCHK(c, hipMemcpyAsync(out, c->d_out, ob, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return HVC_OK;
-}
-
-// Decoder.decode_a_frame minus the crop (decoder.ml:422-427)
-int hvc_jpeg_decode_yuv444(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *info, uint8_t *frame,
-                           size_t frame_cap) try {
-    if (!c || !jpeg || !info || !frame) return HVC_E_INVALID_ARG;
-    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path: hvc_set_arithmetic)
-    hvc::RestartScope honour(c->honour_restart); // (hvc_set_restart_markers; off = the model's behaviour)
-    int r = hvc_jpeg_read_header(jpeg, n, info);
-    if (r) return r;
-    // a 4:2:0 scan: Y 2x2, Cb / Cr 1x1 (Frame.infer_chroma_subsampling, common/src/frame.ml:42-61)
-    if (info->n_comp != 3 || info->comp[0].hscale != 2 || info->comp[0].vscale != 2 || info->comp[1].hscale != 1 ||
-        info->comp[1].vscale != 1 || info->comp[2].hscale != 1 || info->comp[2].vscale != 1)
-        return HVC_E_INVALID_ARG;
-    if (frame_cap < (size_t)3 * info->width * info->height) return HVC_E_INVALID_ARG;
-    if (info->width == 0 || info->height == 0) // a frame without a sample: the model decodes no block (decoder.ml:377-395)
-        return hvc_jpeg_entropy_decode(jpeg, n, info, nullptr); // and of_420 of empty planes is an empty frame; the tables are still looked up
-    int on_gpu = 0;
-    const size_t fb = (size_t)3 * info->width * info->height;
-    AfterReader after;
-    // coefficient record on the device: fused block stage there, one download -- enqueued behind the reader at once
-    auto block_stage = [&]() -> int {
-        DeviceGuard g(c->device);
-        int e = grow(c, &c->d_out, &c->out_cap, fb);
-        if (e) return e;
-        DecodeOpts o(c); // (profiling as the context has it)
-        o.dc_plane = after.dc_plane;
-        o.dc_fs = after.dc_fs;
-        e = decode_frames_yuv444_impl(c, (const int16_t *)c->gd_coefs, info->coef_count, &info->qtabs[0][0], info->n_qtabs,
-                                      info->layout, info->n_comp, 1, info->width, info->height, (uint8_t *)c->d_out, fb,
-                                      HVC_MEM_DEVICE, o);
-        if (e) return e;
-        HIPCHK(c, hipMemcpyAsync(frame, c->d_out, fb, hipMemcpyDeviceToHost, c->stream));
-        return HVC_OK;
-    };
-    after.enqueue = block_stage;
-    if ((r = single_frame_coefs_on_device(c, jpeg, n, info, &on_gpu, &after))) return r;
-    if (on_gpu) {
-        if (after.speculated) return HVC_OK; // (the reader's one synchronisation covered the download)
-        DeviceGuard g(c->device);
-        if ((r = block_stage())) return r;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return HVC_OK;
-    }
-    std::vector<int16_t> coefs;
-    try {
-        coefs.resize(info->coef_count);
-    } catch (const std::bad_alloc &) {
-        return HVC_E_OUT_OF_MEMORY;
-    }
-    std::vector<hvc::WideDc> wide;
-    r = hvc::entropy_decode_wide(jpeg, n, info, coefs.data(), wide);
-    if (r) return r;
-    if (!wide.empty()) return decode_one_with_wide_dc(c, info, coefs.data(), wide, true, frame);
-    return decode_frames_yuv444_impl(c, coefs.data(), info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
-                                     info->n_comp, 1, info->width, info->height, frame,
-                                     (size_t)3 * info->width * info->height, HVC_MEM_HOST, DecodeOpts(c));
-} HVC_ABI_CATCH
-
-int hvc_jpeg_decode(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *info, uint8_t *pixels, size_t pixel_cap) try {
-    if (!c || !jpeg || !info) return HVC_E_INVALID_ARG;
-    hvc::RestartScope honour(c->honour_restart); // (hvc_set_restart_markers; off = the model's behaviour)
-    int r = hvc_jpeg_read_header(jpeg, n, info);
-    if (r) return r;
-    if (pixel_cap < info->pixel_bytes || (!pixels && info->pixel_bytes)) return HVC_E_INVALID_ARG; // (planes without a sample need no memory)
+// One file whose header is read and whose arguments are checked, to the caller's memory.  What the entry points differ in
+// is their sink:
+//   enqueue(d_coefs, o)  enqueues on c->stream the block stage of the device record d_coefs with the options o and
+//                        everything that brings its result to the caller's memory; it does not synchronise
+//   host(coefs)          decodes a host record straight to the caller's memory -- or nullptr: host records are uploaded
+// A file of 128 kB and more goes to the GPU reader with enqueue() behind it before the reader's verdict is known
+// (AfterReader); what the reader cannot take, the host reader reads, and blocks whose DC leaves int16 go through the int64
+// fix-up with their true DCs -- the model's output for such a stream (decoder.ml:143).
+template <class Enqueue, class Host>
+static int decode_one_file(hvc_ctx *c, const uint8_t *jpeg, size_t n, const hvc_jpeg_info *info, Enqueue enqueue, Host host) {
     int on_gpu = 0;
     AfterReader after;
-    // coefficient record on the device: ALL components' block stage there in one launch, one download -- enqueued
-    // behind the reader at once
-    auto block_stage = [&]() -> int {
-        DeviceGuard g(c->device);
-        int e = grow(c, &c->d_out, &c->out_cap, info->pixel_bytes);
-        if (e) return e;
-        DecodeOpts o(c); // (profiling as the context has it)
-        o.dc_plane = after.dc_plane;
-        o.dc_fs = after.dc_fs;
-        e = decode_frames_impl(c, (const int16_t *)c->gd_coefs, info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
-                               info->n_comp, 1, (uint8_t *)c->d_out, info->pixel_bytes, HVC_MEM_DEVICE, o);
-        if (e) return e;
-        HIPCHK(c, hipMemcpyAsync(pixels, c->d_out, info->pixel_bytes, hipMemcpyDeviceToHost, c->stream));
-        return HVC_OK;
-    };
-    after.enqueue = block_stage;
-    if ((r = single_frame_coefs_on_device(c, jpeg, n, info, &on_gpu, &after))) return r;
-    if (on_gpu) {
-        if (after.speculated) return HVC_OK; // (the reader's one synchronisation covered the download)
-        DeviceGuard g(c->device);
-        if ((r = block_stage())) return r;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return HVC_OK;
-    }
-    std::vector<int16_t> coefs;
-    try {
-        coefs.resize(info->coef_count);
-    } catch (const std::bad_alloc &) {
-        return HVC_E_OUT_OF_MEMORY;
-    }
-    std::vector<hvc::WideDc> wide;
-    r = hvc::entropy_decode_wide(jpeg, n, info, coefs.data(), wide);
-    if (r) return r;
-    if (!wide.empty()) return decode_one_with_wide_dc(c, info, coefs.data(), wide, false, pixels);
-    return decode_frames_impl(c, coefs.data(), info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
-                              info->n_comp, 1, pixels, info->pixel_bytes, HVC_MEM_HOST, DecodeOpts(c));
-} HVC_ABI_CATCH
-
-// hvc_jpeg_decode with the colour pass behind the block stage: the planes stay in device scratch (c->d_aux), the image is
-// made in c->d_aux2 and only its bytes come back.
-int hvc_jpeg_decode_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *info, uint8_t *rgb, size_t rgb_cap, size_t rgb_row_stride,
-                        int layout) try {
-    if (!c || !jpeg || !info || !rgb) return HVC_E_INVALID_ARG;
-    hvc::RestartScope honour(c->honour_restart); // (hvc_set_restart_markers; off = the model's behaviour)
-    int r = hvc_jpeg_read_header(jpeg, n, info);
-    if (r) return r;
-    const int sampling = rgb_sampling_of(*info);
-    RgbImage im;
-    if (!sampling || !rgb_image(layout, info->width, info->height, rgb_row_stride, 0, im)) return HVC_E_INVALID_ARG;
-    if (rgb_cap < rgb_bytes(im, 1)) return HVC_E_INVALID_ARG;
-    if (info->width == 0 || info->height == 0 || info->pixel_bytes == 0) // a frame without a sample: the file is still read as the model reads it
-        return hvc_jpeg_entropy_decode(jpeg, n, info, nullptr);
-    int cw, ch;
-    rgb_chroma_window(sampling, info->width, info->height, cw, ch);
-    {
-        DeviceGuard g(c->device);
-        if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-        if ((r = grow(c, &c->d_aux, &c->aux_cap, info->pixel_bytes))) return r;
-        if ((r = grow(c, &c->d_aux2, &c->aux2_cap, rgb_bytes(im, 1)))) return r;
-    }
-    auto colour = [&]() -> int { // planes at c->d_aux -> the caller's image
-        HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, info->pixel_bytes, info->layout, sampling, info->width, info->height, cw, ch, 1,
-                                    (uint8_t *)c->d_aux2, im, c->stream));
-        HIPCHK(c, rgb_download((const uint8_t *)c->d_aux2, rgb, im, 1, c->stream));
-        return HVC_OK;
-    };
-    int on_gpu = 0;
-    AfterReader after;
-    auto block_stage = [&]() -> int { // coefficient record on the device, enqueued behind the reader at once
+    auto from_reader = [&]() -> int { // the record the reader leaves at c->gd_coefs
         DeviceGuard g(c->device);
         DecodeOpts o(c); // (profiling as the context has it)
         o.dc_plane = after.dc_plane;
         o.dc_fs = after.dc_fs;
-        const int e = decode_frames_impl(c, (const int16_t *)c->gd_coefs, info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout,
-                                         info->n_comp, 1, (uint8_t *)c->d_aux, info->pixel_bytes, HVC_MEM_DEVICE, o);
-        return e ? e : colour();
+        return enqueue((const int16_t *)c->gd_coefs, o);
     };
-    after.enqueue = block_stage;
-    if ((r = single_frame_coefs_on_device(c, jpeg, n, info, &on_gpu, &after))) return r;
+    after.enqueue = from_reader;
+    int r = single_frame_coefs_on_device(c, jpeg, n, info, &on_gpu, &after);
+    if (r) return r;
     if (on_gpu) {
         if (after.speculated) return HVC_OK; // (the reader's one synchronisation covered the download)
         DeviceGuard g(c->device);
-        if ((r = block_stage())) return r;
+        if ((r = from_reader())) return r; // (what was enqueued ran on records the reader had not finished)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return HVC_OK;
     }
     std::vector<int16_t> coefs;
-    try {
-        coefs.resize(info->coef_count);
-    } catch (const std::bad_alloc &) {
-        return HVC_E_OUT_OF_MEMORY;
-    }
     std::vector<hvc::WideDc> wide;
     std::vector<WideFix> fix;
+    try {
+        coefs.resize(info->coef_count);
+    } catch (const std::bad_alloc &) {
+        return HVC_E_OUT_OF_MEMORY;
+    }
     if ((r = hvc::entropy_decode_wide(jpeg, n, info, coefs.data(), wide))) return r;
+    if constexpr (!std::is_null_pointer<Host>::value)
+        if (wide.empty()) return host(coefs.data());
     try {
         for (const hvc::WideDc &w : wide) fix.push_back(WideFix{0, w.block, w.dc});
     } catch (const std::bad_alloc &) {
@@ -232,12 +82,100 @@ int hvc_jpeg_decode_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info
     DecodeOpts o(c);
     o.profile = false;
     o.wide = &fix;
-    r = decode_frames_impl(c, (const int16_t *)c->d_in, info->coef_count, &info->qtabs[0][0], info->n_qtabs, info->layout, info->n_comp, 1,
-                           (uint8_t *)c->d_aux, info->pixel_bytes, HVC_MEM_DEVICE, o);
-    if (r) return r;
-    if ((r = colour())) return r;
+    if ((r = enqueue((const int16_t *)c->d_in, o))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HVC_OK;
+}
+
+// the sink of hvc_jpeg_decode and hvc_jpeg_decode_yuv444: the block stage's own output, from device records through c->d_out
+// (ALL components in one launch, one download), from host records as a host-memory call
+static int decode_file_to(hvc_ctx *c, const uint8_t *jpeg, size_t n, const OutputForm &form, uint8_t *dst) {
+    return decode_one_file(
+        c, jpeg, n, &form.info,
+        [&](const int16_t *d_coefs, const DecodeOpts &o) -> int {
+            int e = grow(c, &c->d_out, &c->out_cap, form.out_bytes);
+            if (e) return e;
+            if ((e = form.run(c, d_coefs, 1, (uint8_t *)c->d_out, form.out_bytes, HVC_MEM_DEVICE, o))) return e;
+            HIPCHK(c, hipMemcpyAsync(dst, c->d_out, form.out_bytes, hipMemcpyDeviceToHost, c->stream));
+            return HVC_OK;
+        },
+        [&](const int16_t *coefs) { return form.run(c, coefs, 1, dst, form.out_bytes, HVC_MEM_HOST, DecodeOpts(c)); });
+}
+
+// Decoder.decode_a_frame minus the crop (decoder.ml:422-427)
+int hvc_jpeg_decode_yuv444(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *info, uint8_t *frame,
+                           size_t frame_cap) try {
+    if (!c || !jpeg || !info || !frame) return HVC_E_INVALID_ARG;
+    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path: hvc_set_arithmetic)
+    hvc::RestartScope honour(c->honour_restart); // (hvc_set_restart_markers; off = the model's behaviour)
+    int r = hvc_jpeg_read_header(jpeg, n, info);
+    if (r) return r;
+    if (!is_420_scan(*info)) return HVC_E_INVALID_ARG; // (Frame.infer_chroma_subsampling, common/src/frame.ml:42-61)
+    OutputForm form(OutputForm::YUV444);
+    form.of(*info);
+    if (frame_cap < form.out_bytes) return HVC_E_INVALID_ARG;
+    if (info->width == 0 || info->height == 0) // a frame without a sample: the model decodes no block (decoder.ml:377-395)
+        return hvc_jpeg_entropy_decode(jpeg, n, info, nullptr); // and of_420 of empty planes is an empty frame; the tables are still looked up
+    return decode_file_to(c, jpeg, n, form, frame);
+} HVC_ABI_CATCH
+
+int hvc_jpeg_decode(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *info, uint8_t *pixels, size_t pixel_cap) try {
+    if (!c || !jpeg || !info) return HVC_E_INVALID_ARG;
+    hvc::RestartScope honour(c->honour_restart); // (hvc_set_restart_markers; off = the model's behaviour)
+    int r = hvc_jpeg_read_header(jpeg, n, info);
+    if (r) return r;
+    if (pixel_cap < info->pixel_bytes || (!pixels && info->pixel_bytes)) return HVC_E_INVALID_ARG; // (planes without a sample need no memory)
+    OutputForm form(OutputForm::PLANES);
+    form.of(*info);
+    return decode_file_to(c, jpeg, n, form, pixels);
+} HVC_ABI_CATCH
+
+// The tail of the single-file RGB calls: the planes `pi` describes (a file's info, or its scaled form) lie in c->d_aux, the
+// image is made of them in c->d_aux2 and only its bytes come back.
+struct RgbTail {
+    int sampling = 0;
+    RgbImage im;
+    int scratch(hvc_ctx *c, const hvc_jpeg_info &pi) const { // (before anything is written to c->d_aux)
+        const int r = grow(c, &c->d_aux, &c->aux_cap, pi.pixel_bytes);
+        return r ? r : grow(c, &c->d_aux2, &c->aux2_cap, rgb_bytes(im, 1));
+    }
+    int enqueue(hvc_ctx *c, const hvc_jpeg_info &pi, uint8_t *rgb) const { // colour pass and download on c->stream
+        int cw, ch;
+        rgb_chroma_window(sampling, pi.width, pi.height, cw, ch);
+        HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, pi.pixel_bytes, pi.layout, sampling, pi.width, pi.height, cw, ch, 1,
+                                    (uint8_t *)c->d_aux2, im, c->stream));
+        HIPCHK(c, rgb_download((const uint8_t *)c->d_aux2, rgb, im, 1, c->stream));
+        return HVC_OK;
+    }
+};
+
+// hvc_jpeg_decode with the colour pass behind the block stage: the planes stay in device scratch
+int hvc_jpeg_decode_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *info, uint8_t *rgb, size_t rgb_cap, size_t rgb_row_stride,
+                        int layout) try {
+    if (!c || !jpeg || !info || !rgb) return HVC_E_INVALID_ARG;
+    hvc::RestartScope honour(c->honour_restart); // (hvc_set_restart_markers; off = the model's behaviour)
+    int r = hvc_jpeg_read_header(jpeg, n, info);
+    if (r) return r;
+    RgbTail tail;
+    tail.sampling = rgb_sampling_of(*info);
+    if (!tail.sampling || !rgb_image(layout, info->width, info->height, rgb_row_stride, 0, tail.im)) return HVC_E_INVALID_ARG;
+    if (rgb_cap < rgb_bytes(tail.im, 1)) return HVC_E_INVALID_ARG;
+    if (info->width == 0 || info->height == 0 || info->pixel_bytes == 0) // a frame without a sample: the file is still read as the model reads it
+        return hvc_jpeg_entropy_decode(jpeg, n, info, nullptr);
+    {
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+        if ((r = tail.scratch(c, *info))) return r;
+    }
+    OutputForm form(OutputForm::PLANES);
+    form.of(*info);
+    return decode_one_file(
+        c, jpeg, n, info,
+        [&](const int16_t *d_coefs, const DecodeOpts &o) -> int {
+            const int e = form.run(c, d_coefs, 1, (uint8_t *)c->d_aux, form.out_bytes, HVC_MEM_DEVICE, o);
+            return e ? e : tail.enqueue(c, *info, rgb);
+        },
+        nullptr); // (the host reader's record is uploaded)
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------
@@ -271,14 +209,15 @@ int hvc_jpeg_scaled_info(const hvc_jpeg_info *info, int scale_denom, hvc_jpeg_in
     return HVC_OK;
 } HVC_ABI_CATCH
 
-// header + host reader of one file for the scaled entry points: *info = the SCALED info, `full` the file's own, `coefs` its record
-static int read_for_scaled(hvc_ctx *c, const uint8_t *jpeg, size_t n, int scale_denom, hvc_jpeg_info *info, hvc_jpeg_info &full,
-                           std::vector<int16_t> &coefs) {
-    if (!scaled_side(scale_denom)) return HVC_E_INVALID_ARG;
+// header of one file for the scaled entry points: `form` = its scaled form, *info = the SCALED info, `coefs` sized for its record
+static int read_for_scaled(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info *info, OutputForm &form, std::vector<int16_t> &coefs) {
+    if (!form.known()) return HVC_E_INVALID_ARG;
     if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the scaled path)
+    hvc_jpeg_info full;
     int r = hvc_jpeg_read_header(jpeg, n, &full);
     if (r) return r;
-    scaled_info(full, scaled_side(scale_denom), *info);
+    form.of(full);
+    *info = form.sinfo;
     try {
         coefs.resize(full.coef_count);
     } catch (const std::bad_alloc &) {
@@ -298,14 +237,13 @@ int hvc_jpeg_decode_scaled(hvc_ctx *c, const uint8_t *jpeg, size_t n, int scale_
     if (!c || !jpeg || !info) return HVC_E_INVALID_ARG;
     if (scale_denom == 1) return hvc_jpeg_decode(c, jpeg, n, info, pixels, pixel_cap); // full size: that call, with all its rules
     hvc::RestartScope honour(c->honour_restart); // (hvc_set_restart_markers; off = the model's behaviour)
-    hvc_jpeg_info full;
+    OutputForm form(OutputForm::SCALED, scale_denom);
     std::vector<int16_t> coefs;
-    int r = read_for_scaled(c, jpeg, n, scale_denom, info, full, coefs);
+    int r = read_for_scaled(c, jpeg, n, info, form, coefs);
     if (r) return r;
     if (pixel_cap < info->pixel_bytes || (!pixels && info->pixel_bytes)) return HVC_E_INVALID_ARG;
-    if ((r = entropy_for_scaled(jpeg, n, full, coefs))) return r;
-    return decode_frames_scaled_impl(c, coefs.data(), full.coef_count, &full.qtabs[0][0], full.n_qtabs, info->layout, full.n_comp, 1,
-                                     scale_denom, pixels, info->pixel_bytes, HVC_MEM_HOST, DecodeOpts(c));
+    if ((r = entropy_for_scaled(jpeg, n, form.info, coefs))) return r;
+    return form.run(c, coefs.data(), 1, pixels, form.out_bytes, HVC_MEM_HOST, DecodeOpts(c));
 } HVC_ABI_CATCH
 
 int hvc_jpeg_decode_scaled_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, int scale_denom, hvc_jpeg_info *info, uint8_t *rgb,
@@ -313,37 +251,32 @@ int hvc_jpeg_decode_scaled_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, int sc
     if (!c || !jpeg || !info || !rgb) return HVC_E_INVALID_ARG;
     if (scale_denom == 1) return hvc_jpeg_decode_rgb(c, jpeg, n, info, rgb, rgb_cap, rgb_row_stride, layout); // full size: that call
     hvc::RestartScope honour(c->honour_restart);
-    hvc_jpeg_info full;
+    OutputForm form(OutputForm::SCALED, scale_denom);
     std::vector<int16_t> coefs;
-    int r = read_for_scaled(c, jpeg, n, scale_denom, info, full, coefs);
+    int r = read_for_scaled(c, jpeg, n, info, form, coefs);
     if (r) return r;
-    const int sampling = rgb_sampling_of(full);
-    RgbImage im;
-    if (!sampling || !rgb_image(layout, info->width, info->height, rgb_row_stride, 0, im)) return HVC_E_INVALID_ARG;
-    if (rgb_cap < rgb_bytes(im, 1)) return HVC_E_INVALID_ARG;
-    if ((r = entropy_for_scaled(jpeg, n, full, coefs))) return r;
+    RgbTail tail;
+    tail.sampling = rgb_sampling_of(form.info);
+    if (!tail.sampling || !rgb_image(layout, info->width, info->height, rgb_row_stride, 0, tail.im)) return HVC_E_INVALID_ARG;
+    if (rgb_cap < rgb_bytes(tail.im, 1)) return HVC_E_INVALID_ARG;
+    if ((r = entropy_for_scaled(jpeg, n, form.info, coefs))) return r;
     if (info->width == 0 || info->height == 0 || info->pixel_bytes == 0) return HVC_OK; // a frame without a sample
     int cw, ch;
-    rgb_chroma_window(sampling, info->width, info->height, cw, ch);
+    rgb_chroma_window(tail.sampling, info->width, info->height, cw, ch);
     // the window lies inside the scaled decoded chroma planes: the MCU-rounded size divided by scale_denom is even
-    if (sampling != HVC_YUV_400 && (cw > info->comp[1].decoded_width || ch > info->comp[1].decoded_height ||
-                                    cw > info->comp[2].decoded_width || ch > info->comp[2].decoded_height))
+    if (tail.sampling != HVC_YUV_400 && (cw > info->comp[1].decoded_width || ch > info->comp[1].decoded_height ||
+                                         cw > info->comp[2].decoded_width || ch > info->comp[2].decoded_height))
         return HVC_E_INTERNAL;
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    const size_t cb = full.coef_count * sizeof(int16_t);
-    if ((r = grow(c, &c->d_aux, &c->aux_cap, info->pixel_bytes))) return r;
-    if ((r = grow(c, &c->d_aux2, &c->aux2_cap, rgb_bytes(im, 1)))) return r;
+    const size_t cb = form.info.coef_count * sizeof(int16_t);
+    if ((r = tail.scratch(c, *info))) return r;
     if ((r = grow(c, &c->d_in, &c->in_cap, cb))) return r;
     HIPCHK(c, hipMemcpyAsync(c->d_in, coefs.data(), cb, hipMemcpyHostToDevice, c->stream));
     DecodeOpts o(c);
     o.profile = false;
-    if ((r = decode_frames_scaled_impl(c, (const int16_t *)c->d_in, full.coef_count, &full.qtabs[0][0], full.n_qtabs, info->layout,
-                                       full.n_comp, 1, scale_denom, (uint8_t *)c->d_aux, info->pixel_bytes, HVC_MEM_DEVICE, o)))
-        return r;
-    HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, info->pixel_bytes, info->layout, sampling, info->width, info->height, cw, ch, 1,
-                                (uint8_t *)c->d_aux2, im, c->stream));
-    HIPCHK(c, rgb_download((const uint8_t *)c->d_aux2, rgb, im, 1, c->stream));
+    if ((r = form.run(c, (const int16_t *)c->d_in, 1, (uint8_t *)c->d_aux, form.out_bytes, HVC_MEM_DEVICE, o))) return r;
+    if ((r = tail.enqueue(c, *info, rgb))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HVC_OK;
 } HVC_ABI_CATCH
@@ -353,8 +286,9 @@ int hvc_jpeg_decode_batch_scaled(hvc_ctx *c, const uint8_t *const *jpegs, const 
                                  hvc_batch_stats *stats) try {
     if (!c || !scaled_side(scale_denom)) return HVC_E_INVALID_ARG;
     if (scale_denom != 1 && c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the scaled path)
-    return gpu_reader ? decode_batch_gpu(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, false, scale_denom)
-                      : decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, false, scale_denom);
+    const OutputForm form(OutputForm::SCALED, scale_denom);
+    return gpu_reader ? decode_batch_gpu(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, form)
+                      : decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, form);
 } HVC_ABI_CATCH
 
 // Encoder.encode_420/422/444 (encoder.ml:512-541)
@@ -468,16 +402,12 @@ int hvc_jpeg_encode_rgb(hvc_ctx *c, const uint8_t *rgb, size_t rgb_row_stride, i
 // ---------------------------------------------------------------------------
 // BASELINE config 3: host Huffman || hipMemcpyAsync (copy stream) || block-stage kernel (compute stream)
 
-// yuv444 = false: padded component planes per frame (hvc_jpeg_decode_batch);
-// yuv444 = true: tight 4:4:4 frames through the fused kernel (hvc_jpeg_decode_batch_yuv444);
-// scale_denom = 2, 4, 8 (never with yuv444): the scaled planes of hvc_jpeg_scaled_info per frame, tight, through the scaled
-// block stage (hvc_jpeg_decode_batch_scaled) -- a file whose DC leaves int16 is HVC_E_RANGE there
+// form: what every frame's records become (OutputForm, hvc_ctx.h) -- a file whose DC leaves int16 is HVC_E_RANGE in a scaled batch
 int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads,
                              int frames_per_chunk, uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats,
-                             bool yuv444, int scale_denom) {
+                             OutputForm form) {
     if (!c || !jpegs || !sizes || !pixels || n_frames < 0) return HVC_E_INVALID_ARG;
-    const bool scaled = scale_denom != 1;
-    if (scaled && (yuv444 || scaled_side(scale_denom) == 0)) return HVC_E_INVALID_ARG;
+    if (!form.known()) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_frames == 0) return HVC_OK;
@@ -485,11 +415,9 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
     hvc_jpeg_info info0;
     int r = hvc_jpeg_read_header(jpegs[0], sizes[0], &info0);
     if (r) return r;
-    if (yuv444 && (!is_420_scan(info0) || (info0.width & 1) || (info0.height & 1))) return HVC_E_INVALID_ARG;
-    hvc_jpeg_info sinfo0 = info0; // the output's geometry: info0's, or its scaled form
-    if (scaled) scaled_info(info0, scaled_side(scale_denom), sinfo0);
-    const size_t out_bytes = yuv444 ? (size_t)3 * info0.width * info0.height : sinfo0.pixel_bytes; // per frame
-    if (pixel_fs < out_bytes || (!yuv444 && !scaled && (pixel_fs & 7))) return HVC_E_INVALID_ARG;
+    form.of(info0);
+    if ((r = form.batch_check(pixel_fs))) return r;
+    const size_t out_bytes = form.out_bytes; // per frame
     if (info0.coef_count == 0) { // frames without a block (a width or height of zero): nothing to upload, nothing to launch --
         for (int f = 0; f < n_frames; f++) { // every file is still read as the model reads it (headers, tables)
             hvc_jpeg_info fi;
@@ -662,16 +590,9 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
         if (he != hipSuccess) { rc = fail_hip(c, he); break; }
         he = hipEventRecord(c->ev_t[1], compute);
         DecodeOpts o(c);
-        o.profile = scaled && c->profiling; // (a scaled chunk's block stage takes a ring entry: hvc_jpeg_decode_batch_scaled)
+        o.profile = form.chunk_profile(c);
         o.wide = &chunk_wide[(size_t)k]; // (complete: the chunk's workers are done)
-        if (scaled && !o.wide->empty()) { rc = HVC_E_RANGE; break; } // (no side list in the scaled block stage)
-        rc = scaled ? decode_frames_scaled_impl(c, (const int16_t *)c->d_ring[slot], info0.coef_count, &info0.qtabs[0][0], info0.n_qtabs,
-                                                sinfo0.layout, info0.n_comp, cnt, scale_denom, dst, dst_fs, HVC_MEM_DEVICE, o)
-           : yuv444 ? decode_frames_yuv444_impl(c, (const int16_t *)c->d_ring[slot], info0.coef_count, &info0.qtabs[0][0],
-                                                info0.n_qtabs, info0.layout, info0.n_comp, cnt, info0.width, info0.height,
-                                                dst, dst_fs, HVC_MEM_DEVICE, o)
-                    : decode_frames_impl(c, (const int16_t *)c->d_ring[slot], info0.coef_count, &info0.qtabs[0][0],
-                                         info0.n_qtabs, info0.layout, info0.n_comp, cnt, dst, dst_fs, HVC_MEM_DEVICE, o);
+        rc = form.run(c, (const int16_t *)c->d_ring[slot], cnt, dst, dst_fs, HVC_MEM_DEVICE, o);
         if (rc) break;
         if (he == hipSuccess) he = hipEventRecord(c->ev_t[2], compute);
         if (he == hipSuccess && where == HVC_MEM_HOST) {
@@ -737,7 +658,8 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
 
 int hvc_jpeg_decode_batch(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads,
                           int frames_per_chunk, uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats) try {
-    return decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, false, 1);
+    return decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats,
+                             OutputForm(OutputForm::PLANES));
 } HVC_ABI_CATCH
 
 int hvc_jpeg_decode_batch_yuv444(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames,
@@ -745,7 +667,7 @@ int hvc_jpeg_decode_batch_yuv444(hvc_ctx *c, const uint8_t *const *jpegs, const 
                                  hvc_batch_stats *stats) try {
     if (c && c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path: hvc_set_arithmetic)
     return decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, frames, frame_stride, where, stats,
-                             true, 1);
+                             OutputForm(OutputForm::YUV444));
 } HVC_ABI_CATCH
 
 // hvc_jpeg_decode_batch_rgb: the batch pipelines as they are (host reader or GPU reader, whichever `gpu_reader` names), their

@@ -474,27 +474,24 @@ int hvc_jpeg_entropy_decode_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const s
 // records that the block stage reads.  Anything the GPU decoder hands back (unusual tables, streams the
 // model treats specially, a chunk that does not settle in four launches) restarts the call on the
 // host-decoder pipeline, so results and error codes are always the host decoder's.
-// scale_denom = 2, 4, 8 (never with yuv444): the scaled block stage per chunk, with the chunk's compact DC array.
+// form: what every frame's records become (OutputForm, hvc_ctx.h); a scaled chunk's block stage reads the chunk's compact DC array.
 int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads, int frames_per_chunk,
-                     uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats, bool yuv444, int scale_denom) {
+                     uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats, OutputForm form) {
     if (!c || !jpegs || !sizes || !pixels || n_frames < 0) return HVC_E_INVALID_ARG;
-    const bool scaled = scale_denom != 1;
-    if (scaled && (yuv444 || scaled_side(scale_denom) == 0)) return HVC_E_INVALID_ARG;
+    if (!form.known()) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_frames == 0) return HVC_OK;
     hvc::RestartScope honour(c->honour_restart);
     auto host_pipeline = [&]() {
-        return decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, yuv444, scale_denom);
+        return decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, form);
     };
     hvc_jpeg_info info0;
     int r = hvc_jpeg_read_header(jpegs[0], sizes[0], &info0);
     if (r) return r;
-    if (yuv444 && (!is_420_scan(info0) || (info0.width & 1) || (info0.height & 1))) return HVC_E_INVALID_ARG;
-    hvc_jpeg_info sinfo0 = info0; // the output's geometry: info0's, or its scaled form
-    if (scaled) scaled_info(info0, scaled_side(scale_denom), sinfo0);
-    const size_t out_bytes = yuv444 ? (size_t)3 * info0.width * info0.height : sinfo0.pixel_bytes; // per frame
-    if (pixel_fs < out_bytes || (!yuv444 && !scaled && (pixel_fs & 7))) return HVC_E_INVALID_ARG;
+    form.of(info0);
+    if ((r = form.batch_check(pixel_fs))) return r;
+    const size_t out_bytes = form.out_bytes; // per frame
     hvc::HdParams G;
     hvc::HdTables tables0;
     const unsigned SB = HVC_HD_SUBSEQ_BITS / 8;
@@ -811,7 +808,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
     uint64_t ecs_total = 0;
     hipStream_t compute = c->stream;
     DecodeOpts block_stage(c); // (the chunks' launches take no entry of the profiling ring -- but a scaled chunk's: hvc_jpeg_decode_batch_scaled)
-    block_stage.profile = scaled && c->profiling;
+    block_stage.profile = form.chunk_profile(c);
     int pending_release = -1; // the chunk whose pinned segment slot is handed on once its upload has finished
     auto release_after_upload = [&](int k) -> hipError_t {
         const hipError_t he = wait_event(c->ev_h2d[k % NB]);
@@ -937,12 +934,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
         const size_t dst_fs = where == HVC_MEM_DEVICE ? pixel_fs : out_bytes;
         block_stage.dc_plane = P.dc_plane;
         block_stage.dc_fs = P.dc_fs;
-        rc = scaled ? decode_frames_scaled_impl(c, P.coefs, info0.coef_count, &info0.qtabs[0][0], info0.n_qtabs, sinfo0.layout,
-                                                info0.n_comp, cnt, scale_denom, dst, dst_fs, HVC_MEM_DEVICE, block_stage)
-           : yuv444 ? decode_frames_yuv444_impl(c, P.coefs, info0.coef_count, &info0.qtabs[0][0], info0.n_qtabs, info0.layout,
-                                                info0.n_comp, cnt, info0.width, info0.height, dst, dst_fs, HVC_MEM_DEVICE, block_stage)
-                    : decode_frames_impl(c, P.coefs, info0.coef_count, &info0.qtabs[0][0], info0.n_qtabs, info0.layout,
-                                         info0.n_comp, cnt, dst, dst_fs, HVC_MEM_DEVICE, block_stage);
+        rc = form.run(c, P.coefs, cnt, dst, dst_fs, HVC_MEM_DEVICE, block_stage);
         if (rc) break;
         he = hipEventRecord(c->ev_et[slot][2], compute);
         if (he == hipSuccess && where == HVC_MEM_HOST) { // the downloader takes over
@@ -986,7 +978,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
             const int first = k * C, cnt = (first + C <= n_frames) ? C : n_frames - first;
             hvc_batch_stats hs;
             rc = decode_batch_impl(c, jpegs + first, sizes + first, cnt, threads, 0, pixels + (size_t)first * pixel_fs, pixel_fs,
-                                   where, &hs, yuv444, scale_denom);
+                                   where, &hs, form);
             host_entropy_ms += hs.entropy_ms_sum;
         }
     if (stats) {
@@ -1007,5 +999,6 @@ int hvc_jpeg_decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const siz
                               int frames_per_chunk, uint8_t *pixels, size_t pixel_fs, int where, int yuv444,
                               hvc_batch_stats *stats) try {
     if (c && yuv444 && c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (no RTL form of the fused path)
-    return decode_batch_gpu(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats, yuv444 != 0, 1);
+    return decode_batch_gpu(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats,
+                            OutputForm(yuv444 ? OutputForm::YUV444 : OutputForm::PLANES));
 } HVC_ABI_CATCH

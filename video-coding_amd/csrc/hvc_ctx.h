@@ -2,7 +2,8 @@
 // helpers every entry point uses, and the few functions one part of the ABI calls in another.
 //   hvc_capi.hip         context, streams, timers, memory; the block stage (decode_frames_impl, decode_frames_yuv444_impl,
 //                        encode_frames_impl behind the entry points; the staging steps they share) and its divergence calls
-//   hvc_capi_jpeg.hip    files: one at a time (hvc_jpeg_decode, hvc_jpeg_encode) and the batch pipeline with the host reader
+//   hvc_capi_jpeg.hip    files: one at a time (hvc_jpeg_decode, _yuv444, _rgb on one skeleton; _scaled, _scaled_rgb; hvc_jpeg_encode,
+//                        _encode_rgb) and the batch pipeline with the host reader (hvc_jpeg_decode_batch, _yuv444, _scaled, _rgb)
 //   hvc_capi_reader.hip  the GPU Huffman reader's entry point and the batch pipeline built on it
 //   hvc_capi_files.hip   the GPU Huffman coder's entry point and the batch pipelines that write files
 //   hvc_rgb.hip          the RGB colour pass (kernels and launches; its entry points live with their families in the files above)
@@ -381,19 +382,62 @@ struct AfterReader {
 int gpu_entropy_decode(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, const hvc_jpeg_info &info0,
                        int16_t *d_coefs, size_t coef_fs, int *used_gpu, AfterReader *after = nullptr);
 
-// hvc_capi_jpeg.hip: the batch pipeline with the host reader (hvc_jpeg_decode_batch / _yuv444) -- also where the
-// pipeline with the GPU reader sends a batch it cannot take
-// scale_denom: 1 = full size (the block stage as it always was), 2 / 4 / 8 = the scaled block stage per chunk (not with yuv444)
-int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads,
-                      int frames_per_chunk, uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats, bool yuv444,
-                      int scale_denom);
-// hvc_capi_reader.hip: the same with the GPU reader (behind hvc_jpeg_decode_batch_gpu)
-int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads, int frames_per_chunk,
-                     uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats, bool yuv444, int scale_denom);
 inline bool is_420_scan(const hvc_jpeg_info &info) { // Y 2x2, Cb / Cr 1x1 (frame.ml:42-61)
     return info.n_comp == 3 && info.comp[0].hscale == 2 && info.comp[0].vscale == 2 && info.comp[1].hscale == 1 &&
            info.comp[1].vscale == 1 && info.comp[2].hscale == 1 && info.comp[2].vscale == 1;
 }
+
+// What the records of a file become, for the file-level decoders (hvc_capi_jpeg.hip, hvc_capi_reader.hip).  An entry point
+// states the kind (and scale_denom); of() adds the geometry once the first file's header is read.
+struct OutputForm {
+    enum Kind {
+        PLANES, // padded component planes (hvc_jpeg_decode, hvc_jpeg_decode_batch)
+        YUV444, // a 4:2:0 scan as a tight 4:4:4 frame through the fused kernel (hvc_jpeg_decode_yuv444, _batch_yuv444)
+        SCALED, // the planes of hvc_jpeg_scaled_info, tight, through the scaled block stage: scale_denom = 2, 4, 8
+    } kind;
+    int scale_denom;
+    hvc_jpeg_info info, sinfo; // the first file's, and the output's geometry: the same, or its scaled form
+    size_t out_bytes = 0;      // per frame
+    explicit OutputForm(Kind k, int denom = 1) : kind(denom == 1 && k == SCALED ? PLANES : k), scale_denom(denom) {}
+    bool known() const { return kind == SCALED ? scaled_side(scale_denom) != 0 : scale_denom == 1; }
+    void of(const hvc_jpeg_info &first) {
+        info = sinfo = first;
+        if (kind == SCALED) scaled_info(first, scaled_side(scale_denom), sinfo);
+        out_bytes = kind == YUV444 ? (size_t)3 * first.width * first.height : sinfo.pixel_bytes;
+    }
+    // a batch into frames `frame_stride` bytes apart: 4:4:4 frames need a 4:2:0 scan of even size, full-size planes a stride
+    // that keeps every frame's rows 8-byte aligned
+    int batch_check(size_t frame_stride) const {
+        if (kind == YUV444 && (!is_420_scan(info) || (info.width & 1) || (info.height & 1))) return HVC_E_INVALID_ARG;
+        return frame_stride < out_bytes || (kind == PLANES && (frame_stride & 7)) ? HVC_E_INVALID_ARG : HVC_OK;
+    }
+    // a batch pipeline's chunk takes a profiling-ring entry only through the scaled block stage (hvc_jpeg_decode_batch_scaled)
+    bool chunk_profile(const hvc_ctx *c) const { return kind == SCALED && c->profiling; }
+    // the block stage of n_frames records (info.coef_count apart) to dst; o.wide: HVC_E_RANGE where the form has no int64
+    // fix-up (the scaled block stage) and the list names a block
+    int run(hvc_ctx *c, const int16_t *coefs, int n_frames, uint8_t *dst, size_t dst_fs, int where, const DecodeOpts &o) const {
+        const uint16_t *q = &info.qtabs[0][0];
+        switch (kind) {
+        case SCALED:
+            if (o.wide && !o.wide->empty()) return HVC_E_RANGE;
+            return decode_frames_scaled_impl(c, coefs, info.coef_count, q, info.n_qtabs, sinfo.layout, info.n_comp, n_frames, scale_denom,
+                                             dst, dst_fs, where, o);
+        case YUV444:
+            return decode_frames_yuv444_impl(c, coefs, info.coef_count, q, info.n_qtabs, info.layout, info.n_comp, n_frames, info.width,
+                                             info.height, dst, dst_fs, where, o);
+        default:
+            return decode_frames_impl(c, coefs, info.coef_count, q, info.n_qtabs, info.layout, info.n_comp, n_frames, dst, dst_fs, where, o);
+        }
+    }
+};
+
+// hvc_capi_jpeg.hip: the batch pipeline with the host reader (hvc_jpeg_decode_batch / _yuv444 / _scaled) -- also where the
+// pipeline with the GPU reader sends a batch, or the chunks, it cannot take (with the form it was given)
+int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads,
+                      int frames_per_chunk, uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats, OutputForm form);
+// hvc_capi_reader.hip: the same with the GPU reader (behind hvc_jpeg_decode_batch_gpu)
+int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads, int frames_per_chunk,
+                     uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats, OutputForm form);
 
 // hvc_rgb.hip: the colour pass (k_ycc_to_rgb / k_rgb_to_ycc) on device memory, for the entry points that end or begin with it
 struct RgbImage { // an RGB image as the caller laid it out (hvc_rgb_layout; strides of 0 resolved to tight)
