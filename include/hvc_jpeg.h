@@ -742,6 +742,47 @@ HVC_API int hvc_jpeg_decode_batch_scaled(hvc_ctx *ctx, const uint8_t *const *jpe
                                          int threads, int frames_per_chunk, int gpu_reader, int scale_denom, uint8_t *pixels,
                                          size_t pixel_frame_stride, int where, hvc_batch_stats *stats);
 
+/* ------------------------------------------------------------------------- */
+/* Mixed batches: frames and files of DIFFERENT sizes, samplings and quantiser tables in one call.  Every other batch entry
+ * point takes one geometry and one set of tables and refuses a file that differs from the first (and still does); a directory
+ * of photographs has as many geometries as files.  Here the block stage takes its work decomposition from tables in device
+ * memory (k_decode_mixed): a launch serves any set of planes, a 64 x 64 thumbnail costs three wavefronts.  Full-size padded
+ * planes only: no RGB, 4:4:4 or reduced-size form, the host Huffman reader only, no side list of DCs beyond int16.  With
+ * HVC_ARITH_HARDCAML set the two ctx functions return HVC_E_INVALID_ARG; hvc_set_decode_kernel(ctx, 2) sends every block
+ * through the int64 arithmetic, other selections are ignored; hvc_last_wide_blocks counts the blocks that took it. */
+
+/* headers of n_files files -> infos[f], status[f] (what hvc_jpeg_read_header returns for file f),
+ * pixel_offsets[f] (bytes; each record = the file's padded planes exactly as hvc_jpeg_decode lays them out,
+ * info.pixel_bytes long, records in file order, each start rounded up to `align`), *total_bytes.
+ * A file whose status is not HVC_OK takes no room.  align: a power of two >= 8; 0 = 256. */
+HVC_API int hvc_jpeg_mixed_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, size_t align,
+                                  hvc_jpeg_info *infos, int *status, size_t *pixel_offsets, size_t *total_bytes);
+
+/* The block stage over frames of DIFFERENT geometry and tables in one launch: frame f is infos[f].layout / .qtabs,
+ * its coefficient record at coefs + coef_offsets[f] (int16 elements), its pixel record at pixels + pixel_offsets[f].
+ * infos/offsets: host memory always.  Same arithmetic and same bytes as hvc_decode_frames frame by frame.
+ * Every coefficient plane must start on 16 bytes, every pixel plane and stride on 8 (HVC_E_ALIGNMENT); a component
+ * without a block is skipped, a set without a block launches nothing.  HVC_MEM_DEVICE: enqueued on ctx's stream, honours
+ * hvc_set_profiling (the pair brackets k_decode_mixed); HVC_MEM_HOST: staged through context scratch, the call blocks. */
+HVC_API int hvc_decode_frames_mixed(hvc_ctx *ctx, const int16_t *coefs, const size_t *coef_offsets,
+                                    const hvc_jpeg_info *infos, int n_frames, uint8_t *pixels,
+                                    const size_t *pixel_offsets, int where);
+
+/* Files -> pixels.  infos / status / pixel_offsets as hvc_jpeg_mixed_layout made them (the caller sized `pixels` from
+ * *total_bytes).  Host threads read the files (the host Huffman reader, restart markers honoured when
+ * hvc_set_restart_markers says so) into a pinned ring, chunk by chunk; a chunk = consecutive files whose coefficient
+ * records fit chunk_bytes (0 = 64 MiB; a single file larger than that is a chunk of its own and the ring grows);
+ * upload || hvc_decode_frames_mixed of the previous chunk || reading of the next, as in hvc_jpeg_decode_batch.
+ * PER-FILE results: status[f] receives the file's own code; a file that fails (at its header or in its scan) leaves its
+ * pixel record untouched and does not stop the others.  The call itself fails only for its own reasons (arguments,
+ * HIP, memory, threads).  A file with a block whose absolute DC leaves int16 is HVC_E_RANGE here (no side list, as at
+ * the reduced scales).  Host output: the alignment padding between the records of two good files may be overwritten.
+ * stats->frames_per_chunk is the largest chunk's file count, stats->coef_bytes the sum uploaded. */
+HVC_API int hvc_jpeg_decode_batch_mixed(hvc_ctx *ctx, const uint8_t *const *jpegs, const size_t *sizes, int n_files,
+                                        int threads, size_t chunk_bytes, const hvc_jpeg_info *infos, int *status,
+                                        const size_t *pixel_offsets, uint8_t *pixels, size_t pixel_cap, int where,
+                                        hvc_batch_stats *stats);
+
 /* K5 (no counterpart in the reference): what a benchmark or a pipeline produced, said in
  * 64 bits per record without bringing the records back.  For r < n_records
  *     sums[r] = SUM_i (byte_i + 1) * ((2 i + 1) * 0x9E3779B97F4A7C15)   mod 2^64,  i = byte index in record r

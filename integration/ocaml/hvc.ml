@@ -805,6 +805,34 @@ let jpeg_decode_batch_scaled =
     @-> ptr Batch_stats.t @-> returning int)
 ;;
 
+(* Mixed batches (include/hvc_jpeg.h, "Mixed batches"): files and frames of different geometry and tables in one call.
+   int hvc_jpeg_mixed_layout(jpegs, sizes, n_files, align, infos, status, pixel_offsets, total_bytes)          host only *)
+let jpeg_mixed_layout =
+  foreign
+    "hvc_jpeg_mixed_layout"
+    (ptr string @-> ptr size_t @-> int @-> size_t @-> ptr Jpeg_info.t @-> ptr int @-> ptr size_t @-> ptr size_t
+    @-> returning int)
+;;
+
+(* int hvc_decode_frames_mixed(ctx, coefs, coef_offsets, infos, n_frames, pixels, pixel_offsets, where) *)
+let decode_frames_mixed =
+  foreign
+    "hvc_decode_frames_mixed"
+    ~release_runtime_lock:true
+    (ctx @-> ptr int16_t @-> ptr size_t @-> ptr Jpeg_info.t @-> int @-> ptr char @-> ptr size_t @-> int
+    @-> returning int)
+;;
+
+(* int hvc_jpeg_decode_batch_mixed(ctx, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, pixel_offsets, pixels,
+                                   pixel_cap, where, stats) *)
+let jpeg_decode_batch_mixed =
+  foreign
+    "hvc_jpeg_decode_batch_mixed"
+    ~release_runtime_lock:true
+    (ctx @-> ptr string @-> ptr size_t @-> int @-> int @-> size_t @-> ptr Jpeg_info.t @-> ptr int @-> ptr size_t
+    @-> ptr char @-> size_t @-> int @-> ptr Batch_stats.t @-> returning int)
+;;
+
 (* int hvc_jpeg_encode_rgb(ctx, rgb, rgb_row_stride, layout, width, height, chroma, quality, out, cap, out_len) *)
 let jpeg_encode_rgb =
   foreign

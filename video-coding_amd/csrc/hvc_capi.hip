@@ -284,6 +284,9 @@ void hvc_destroy(hvc_ctx *c) {
     if (c->gd_ftabs) (void)hipFree(c->gd_ftabs);
     if (c->gd_dcv) (void)hipFree(c->gd_dcv);
     if (c->d_dcfix) (void)hipFree(c->d_dcfix);
+    if (c->d_mixed) (void)hipFree(c->d_mixed);
+    if (c->h_mixed) (void)hipHostFree(c->h_mixed);
+    if (c->ev_mixed) (void)hipEventDestroy(c->ev_mixed);
     delete c->gd_tables_host;
     if (c->hd_tables) (void)hipFree(c->hd_tables);
     if (c->hd_opt) (void)hipFree(c->hd_opt);
@@ -967,6 +970,12 @@ int hvc_decode_frames(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const ui
                       const hvc_component *comps, int n_comp, int n_frames, uint8_t *pixels, size_t pixel_fs,
                       int where) try {
     return decode_frames_impl(c, coefs, coef_fs, qtabs, n_qtabs, comps, n_comp, n_frames, pixels, pixel_fs, where, DecodeOpts(c));
+} HVC_ABI_CATCH
+
+// frames of different geometry and tables in one launch: hvc_capi_mixed.hip
+int hvc_decode_frames_mixed(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
+                            uint8_t *pixels, const size_t *pixel_offsets, int where) try {
+    return decode_frames_mixed_impl(c, coefs, coef_offsets, infos, n_frames, pixels, pixel_offsets, where);
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------

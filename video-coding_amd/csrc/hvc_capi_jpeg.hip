@@ -4,6 +4,7 @@
 // (decode_batch_impl behind hvc_jpeg_decode_batch, _batch_yuv444 and _batch_scaled), and hvc_jpeg_decode_batch_rgb over either
 // pipeline.
 #include "hvc_ctx.h"
+#include "hvc_mixed_plan.h"
 
 // ---------------------------------------------------------------------------
 // single-frame conveniences (host memory)
@@ -660,6 +661,20 @@ int hvc_jpeg_decode_batch(hvc_ctx *c, const uint8_t *const *jpegs, const size_t 
                           int frames_per_chunk, uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats) try {
     return decode_batch_impl(c, jpegs, sizes, n_frames, threads, frames_per_chunk, pixels, pixel_fs, where, stats,
                              OutputForm(OutputForm::PLANES));
+} HVC_ABI_CATCH
+
+// where the pixel record of every file of a mixed batch goes (host only: hvc_mixed_plan.cpp)
+int hvc_jpeg_mixed_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, size_t align, hvc_jpeg_info *infos,
+                          int *status, size_t *pixel_offsets, size_t *total_bytes) try {
+    return hvc::mixed_layout(jpegs, sizes, n_files, align, infos, status, pixel_offsets, total_bytes);
+} HVC_ABI_CATCH
+
+// files of different sizes, samplings and tables in one call: hvc_capi_mixed.hip
+int hvc_jpeg_decode_batch_mixed(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads,
+                                size_t chunk_bytes, const hvc_jpeg_info *infos, int *status, const size_t *pixel_offsets,
+                                uint8_t *pixels, size_t pixel_cap, int where, hvc_batch_stats *stats) try {
+    return decode_batch_mixed_impl(c, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, pixel_offsets, pixels, pixel_cap,
+                                   where, stats);
 } HVC_ABI_CATCH
 
 int hvc_jpeg_decode_batch_yuv444(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames,

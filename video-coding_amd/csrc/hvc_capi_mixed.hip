@@ -1,0 +1,445 @@
+// hvc_capi_mixed.hip -- batches of frames (behind hvc_decode_frames_mixed) and of files (behind hvc_jpeg_decode_batch_mixed) that share
+// neither geometry nor quantiser tables: the host plan of hvc_mixed_plan.cpp, its tables in device memory, one launch of
+// k_decode_mixed (hvc_mixed.hip) per call or per chunk.  The pipeline reuses the context's pinned / device rings, events and
+// worker pool of hvc_jpeg_decode_batch; what it cuts the batch by is bytes, not frames.
+#include "hvc_ctx.h"
+#include "hvc_mixed.h"
+
+namespace {
+
+// the plan as one image: planes | tables | map, each part on 16 bytes
+struct ImageParts {
+    size_t planes = 0, tables = 0, map = 0, total = 0;
+};
+ImageParts image_parts(const hvc::MixedPlan &plan) {
+    ImageParts p;
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    p.planes = 0;
+    p.tables = up(plan.planes.size() * sizeof(hvc::MixedPlaneK));
+    p.map = p.tables + up(plan.tables.size() * sizeof(hvc::MixedTableK));
+    p.total = p.map + up(plan.map.size() * sizeof(unsigned));
+    return p;
+}
+
+// the plan's tables in c->d_mixed, in stream order: uploaded from the pinned image unless the device already holds these bytes
+int upload_plan(hvc_ctx *c, const hvc::MixedPlan &plan, hvc::MixedParams &P) {
+    const ImageParts ip = image_parts(plan);
+    std::vector<unsigned char> img(ip.total, 0);
+    std::memcpy(img.data() + ip.planes, plan.planes.data(), plan.planes.size() * sizeof(hvc::MixedPlaneK));
+    std::memcpy(img.data() + ip.tables, plan.tables.data(), plan.tables.size() * sizeof(hvc::MixedTableK));
+    std::memcpy(img.data() + ip.map, plan.map.data(), plan.map.size() * sizeof(unsigned));
+    if (!c->ev_mixed) HIPCHK(c, hipEventCreateWithFlags(&c->ev_mixed, hipEventDisableTiming));
+    const bool same = c->mixed_len == ip.total && c->h_mixed && !std::memcmp(c->h_mixed, img.data(), ip.total);
+    if (!same) {
+        c->mixed_len = 0;
+        int r = grow(c, &c->d_mixed, &c->mixed_cap, ip.total);
+        if (r) return r;
+        if (ip.total > c->h_mixed_cap) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (c->h_mixed) (void)hipHostFree(c->h_mixed);
+            c->h_mixed = nullptr;
+            c->h_mixed_cap = 0;
+            const size_t want = ip.total + ip.total / 4 + 4096;
+            if (hipHostMalloc(&c->h_mixed, want, hipHostMallocDefault) != hipSuccess) {
+                c->h_mixed = nullptr;
+                return HVC_E_OUT_OF_MEMORY;
+            }
+            c->h_mixed_cap = want;
+        } else {
+            HIPCHK(c, wait_event(c->ev_mixed)); // (the last upload has read the image)
+        }
+        std::memcpy(c->h_mixed, img.data(), ip.total);
+        HIPCHK(c, hipMemcpyAsync(c->d_mixed, c->h_mixed, ip.total, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_mixed, c->stream));
+        c->mixed_len = ip.total;
+    }
+    const unsigned char *d = (const unsigned char *)c->d_mixed;
+    P.planes = reinterpret_cast<const hvc::MixedPlaneK *>(d + ip.planes);
+    P.tables = reinterpret_cast<const hvc::MixedTableK *>(d + ip.tables);
+    P.map = reinterpret_cast<const unsigned *>(d + ip.map);
+    P.n_units = (unsigned)plan.map.size();
+    return HVC_OK;
+}
+
+// the fix-up list holds one id per block slot of the launch (every unit may send all 64 of its lanes)
+int reserve_mixed_fix_list(hvc_ctx *c, size_t entries) {
+    if (entries <= c->fix_cap) return HVC_OK;
+    void *p = c->d_fix_list;
+    size_t cap = c->fix_cap * sizeof(unsigned);
+    const int r = grow(c, &p, &cap, entries * sizeof(unsigned));
+    c->d_fix_list = (unsigned *)p;
+    c->fix_cap = cap / sizeof(unsigned);
+    return r;
+}
+
+// The block stage of a plan on DEVICE memory, enqueued on c->stream.  The caller has called wide_total_begin for the call
+// this launch belongs to.
+int mixed_launch_plan(hvc_ctx *c, const hvc::MixedPlan &plan, const int16_t *d_coefs, uint8_t *d_pixels, bool profile) {
+    int r;
+    if (plan.map.empty()) return HVC_OK; // no block at all: nothing to launch
+    if (((uintptr_t)d_coefs & 15) || ((uintptr_t)d_pixels & 7)) return HVC_E_ALIGNMENT;
+    if ((r = reserve_mixed_fix_list(c, plan.map.size() * HVC_MIXED_UNIT))) return r;
+    hvc::MixedParams P;
+    std::memset(&P, 0, sizeof P);
+    if ((r = upload_plan(c, plan, P))) return r;
+    P.coefs = d_coefs;
+    P.pixels = d_pixels;
+    P.all_wide = c->decode_kernel == 2;
+    fix_assign(c, P);
+    const int slot = (int)(c->k_calls % HVC_PROF_RING);
+    const hipError_t e = hvc::launch_decode_mixed(P, c->stream, profile ? c->k0[slot] : nullptr, profile ? c->k1[slot] : nullptr);
+    if (e != hipSuccess) {
+        fix_reset(c);
+        return fail_hip(c, e);
+    }
+    fix_commit(c);
+    if (profile) c->k_calls++;
+    return HVC_OK;
+}
+
+// ... of the listed frames: frames = indices into infos / the offset arrays (nullptr: 0 .. n_list - 1)
+int mixed_launch(hvc_ctx *c, const int16_t *d_coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, const int *frames,
+                 int n_list, uint8_t *d_pixels, const size_t *pixel_offsets, bool profile) {
+    hvc::MixedPlan plan;
+    const int r = hvc::mixed_plan_build(infos, coef_offsets, pixel_offsets, frames, n_list, plan);
+    return r ? r : mixed_launch_plan(c, plan, d_coefs, d_pixels, profile);
+}
+
+// what a frame's records cover: elements of coefficients, bytes of pixels (0: no block)
+void frame_spans(const hvc_jpeg_info &fi, size_t &coef_span, size_t &pixel_span) {
+    coef_span = pixel_span = 0;
+    for (int i = 0; i < fi.n_comp && i < 4; i++) {
+        const hvc_component &k = fi.layout[i];
+        if (k.blocks_w <= 0 || k.blocks_h <= 0) continue;
+        coef_span = std::max(coef_span, k.coef_offset + (size_t)k.blocks_w * k.blocks_h * 64);
+        pixel_span = std::max(pixel_span, k.plane_offset + ((size_t)k.blocks_h * 8 - 1) * k.stride + (size_t)k.blocks_w * 8);
+    }
+}
+
+} // namespace
+
+// behind hvc_decode_frames_mixed (hvc_capi.hip)
+int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
+                             uint8_t *pixels, const size_t *pixel_offsets, int where) {
+    if (!c || n_frames < 0 || (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE)) return HVC_E_INVALID_ARG;
+    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (the RTL arithmetic has no mixed form, as it has no scaled one)
+    if (n_frames == 0) return HVC_OK;
+    if (!infos || !coef_offsets || !pixel_offsets) return HVC_E_INVALID_ARG;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    int r;
+    {
+        hvc::MixedPlan plan; // the caller's own offsets: checked for either kind of memory, launched on for device memory
+        if ((r = hvc::mixed_plan_build(infos, coef_offsets, pixel_offsets, nullptr, n_frames, plan))) return r;
+        if (plan.map.empty()) return HVC_OK; // (a set without a block needs no memory)
+        if (!coefs || !pixels) return HVC_E_INVALID_ARG;
+        if (where == HVC_MEM_DEVICE) {
+            wide_total_begin(c);
+            return mixed_launch_plan(c, plan, coefs, pixels, c->profiling);
+        }
+    }
+    // host memory: the frames' records one after another in c->d_in / c->d_out (whole 128-byte blocks: every alignment rule
+    // holds), each plane's bytes copied back by themselves -- what the kernels wrote, never the caller's padding
+    std::vector<size_t> d_coef((size_t)n_frames), d_pix((size_t)n_frames), cspan((size_t)n_frames);
+    size_t ctot = 0, ptot = 0;
+    for (int f = 0; f < n_frames; f++) {
+        size_t ps;
+        frame_spans(infos[f], cspan[(size_t)f], ps);
+        d_coef[(size_t)f] = ctot;
+        d_pix[(size_t)f] = ptot;
+        ctot += (cspan[(size_t)f] + 63) & ~(size_t)63;
+        ptot += (ps + 63) & ~(size_t)63;
+    }
+    if ((r = grow(c, &c->d_in, &c->in_cap, ctot * sizeof(int16_t)))) return r;
+    if ((r = grow(c, &c->d_out, &c->out_cap, ptot))) return r;
+    for (int f = 0; f < n_frames; f++)
+        if (cspan[(size_t)f])
+            HIPCHK(c, hipMemcpyAsync((int16_t *)c->d_in + d_coef[(size_t)f], coefs + coef_offsets[f], cspan[(size_t)f] * sizeof(int16_t),
+                                     hipMemcpyHostToDevice, c->stream));
+    wide_total_begin(c);
+    if ((r = mixed_launch(c, (const int16_t *)c->d_in, d_coef.data(), infos, nullptr, n_frames, (uint8_t *)c->d_out, d_pix.data(), false))) {
+        (void)hipStreamSynchronize(c->stream);
+        return r;
+    }
+    for (int f = 0; f < n_frames; f++)
+        for (int i = 0; i < infos[f].n_comp; i++) {
+            const hvc_component &k = infos[f].layout[i];
+            if (k.blocks_w <= 0 || k.blocks_h <= 0) continue;
+            const size_t row = (size_t)k.blocks_w * 8, rows = (size_t)k.blocks_h * 8;
+            uint8_t *dst = pixels + pixel_offsets[f] + k.plane_offset;
+            const uint8_t *src = (const uint8_t *)c->d_out + d_pix[(size_t)f] + k.plane_offset;
+            if (k.stride == row)
+                HIPCHK(c, hipMemcpyAsync(dst, src, row * rows, hipMemcpyDeviceToHost, c->stream));
+            else
+                HIPCHK(c, hipMemcpy2DAsync(dst, k.stride, src, k.stride, row, rows, hipMemcpyDeviceToHost, c->stream));
+        }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Files -> pixels: host Huffman reader || upload (copy stream) || k_decode_mixed of the previous chunk (compute stream), as
+// decode_batch_impl (hvc_capi_jpeg.hip) -- with chunks cut by the bytes of their coefficient records, a plan per chunk, and a
+// status per file: a file that fails keeps its slot in the chunk's ring buffer and is left out of the chunk's plan.
+// (behind hvc_jpeg_decode_batch_mixed, hvc_capi_jpeg.hip)
+int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads,
+                            size_t chunk_bytes, const hvc_jpeg_info *infos, int *status, const size_t *pixel_offsets,
+                            uint8_t *pixels, size_t pixel_cap, int where, hvc_batch_stats *stats) {
+    if (!c || !jpegs || !sizes || !infos || !status || !pixel_offsets || n_files < 0) return HVC_E_INVALID_ARG;
+    if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
+    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_files == 0) return HVC_OK;
+    if (chunk_bytes == 0) chunk_bytes = (size_t)64 << 20;
+    if (threads < 1) threads = 1;
+    if (threads > 256) threads = 256;
+    const int NB = hvc_ctx::RING;
+
+    // the files that take part (their header was read), cut into chunks; everything else keeps the status it came with
+    struct Chunk {
+        int first = 0, count = 0;    // positions in `take`
+        size_t coef_bytes = 0;
+        size_t pix_lo = 0, pix_hi = 0; // the bytes of `pixels` its files cover
+    };
+    std::vector<int> take;
+    std::vector<Chunk> chunks;
+    std::vector<size_t> coef_rel((size_t)n_files, 0), pix_rel((size_t)n_files, 0);
+    std::vector<int> chunk_of((size_t)n_files, -1);
+    bool need_pixels = false;
+    for (int f = 0; f < n_files; f++) {
+        if (status[f] != HVC_OK) continue;
+        const hvc_jpeg_info &fi = infos[f];
+        if (!jpegs[f] || fi.n_comp < 0 || fi.n_comp > 4) return HVC_E_INVALID_ARG;
+        if (fi.pixel_bytes) {
+            if (pixel_offsets[f] & 7) return HVC_E_ALIGNMENT;
+            if (pixel_offsets[f] > pixel_cap || fi.pixel_bytes > pixel_cap - pixel_offsets[f]) return HVC_E_INVALID_ARG;
+            need_pixels = true;
+        }
+        const size_t cb = fi.coef_count * sizeof(int16_t);
+        if (chunks.empty() || (chunks.back().count > 0 && chunks.back().coef_bytes + cb > chunk_bytes)) {
+            chunks.emplace_back();
+            chunks.back().first = (int)take.size();
+        }
+        Chunk &k = chunks.back();
+        coef_rel[(size_t)f] = k.coef_bytes / sizeof(int16_t);
+        chunk_of[(size_t)f] = (int)chunks.size() - 1;
+        if (fi.pixel_bytes) {
+            if (k.pix_hi == 0) k.pix_lo = pixel_offsets[f];
+            k.pix_lo = std::min(k.pix_lo, pixel_offsets[f]);
+            k.pix_hi = std::max(k.pix_hi, pixel_offsets[f] + fi.pixel_bytes);
+        }
+        k.coef_bytes += cb;
+        k.count++;
+        take.push_back(f);
+    }
+    if (need_pixels && !pixels) return HVC_E_INVALID_ARG;
+    if (take.empty()) return HVC_OK;
+    const int n_chunks = (int)chunks.size(), n_take = (int)take.size();
+    size_t ring_bytes = 0, oring_bytes = 0;
+    int largest = 0;
+    uint64_t coef_total = 0;
+    for (const Chunk &k : chunks) {
+        ring_bytes = std::max(ring_bytes, k.coef_bytes);
+        if (where == HVC_MEM_HOST) oring_bytes = std::max(oring_bytes, k.pix_hi - k.pix_lo);
+        largest = std::max(largest, k.count);
+    }
+    if (where == HVC_MEM_HOST)
+        for (int f : take) pix_rel[(size_t)f] = infos[f].pixel_bytes ? pixel_offsets[f] - chunks[(size_t)chunk_of[(size_t)f]].pix_lo : 0;
+
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    for (int i = 0; i < NB; i++) {
+        if (!c->ev_h2d[i]) HIPCHK(c, hipEventCreate(&c->ev_h2d[i]));
+        if (!c->ev_kern[i]) HIPCHK(c, hipEventCreate(&c->ev_kern[i]));
+    }
+    for (int i = 0; i < 4; i++)
+        if (!c->ev_t[i]) HIPCHK(c, hipEventCreate(&c->ev_t[i]));
+    if (ring_bytes > c->ring_bytes) { // (a single file larger than chunk_bytes: the ring grows)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+        for (int i = 0; i < NB; i++) {
+            if (c->h_ring[i]) (void)hipHostFree(c->h_ring[i]);
+            if (c->d_ring[i]) (void)hipFree(c->d_ring[i]);
+            c->h_ring[i] = c->d_ring[i] = nullptr;
+        }
+        c->ring_bytes = 0;
+        for (int i = 0; i < NB; i++)
+            if (hipHostMalloc(&c->h_ring[i], ring_bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&c->d_ring[i], ring_bytes) != hipSuccess)
+                return HVC_E_OUT_OF_MEMORY;
+        c->ring_bytes = ring_bytes;
+    }
+    if (oring_bytes > c->oring_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int i = 0; i < NB; i++) {
+            if (c->d_oring[i]) (void)hipFree(c->d_oring[i]);
+            c->d_oring[i] = nullptr;
+        }
+        c->oring_bytes = 0;
+        for (int i = 0; i < NB; i++)
+            if (hipMalloc(&c->d_oring[i], oring_bytes) != hipSuccess) return HVC_E_OUT_OF_MEMORY;
+        c->oring_bytes = oring_bytes;
+    }
+
+    std::mutex mu;
+    std::condition_variable cv;
+    std::atomic<int> next{0}, error{0};
+    std::vector<int> done_in_chunk((size_t)n_chunks, 0);
+    int released_upto = NB - 1;
+    std::atomic<long long> entropy_ns{0};
+    auto worker_body = [&]() {
+        if (!pin_to_ctx_cpus(c)) error.store(HVC_E_INVALID_ARG);
+        hvc::RestartScope honour(c->honour_restart);
+        std::vector<hvc::WideDc> wide;
+        for (;;) {
+            const int t = next.fetch_add(1);
+            if (t >= n_take || error.load()) return;
+            const int f = take[(size_t)t], k = chunk_of[(size_t)f];
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return k <= released_upto || error.load(); });
+            }
+            if (error.load()) return;
+            const auto t0 = std::chrono::steady_clock::now();
+            int e;
+            if (infos[f].coef_count == 0) { // no block: the file is still read as the model reads it
+                e = hvc_jpeg_entropy_decode(jpegs[f], sizes[f], &infos[f], nullptr);
+            } else {
+                wide.clear();
+                e = hvc::entropy_decode_wide(jpegs[f], sizes[f], &infos[f], (int16_t *)c->h_ring[k % NB] + coef_rel[(size_t)f], wide);
+                if (!e && !wide.empty()) e = HVC_E_RANGE; // (a DC beyond int16: no side list here)
+            }
+            entropy_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+            std::lock_guard<std::mutex> lk(mu);
+            status[f] = e; // the file's own result: it stops nobody else
+            done_in_chunk[(size_t)k]++;
+            cv.notify_all();
+        }
+    };
+    auto worker = [&]() {
+        try {
+            worker_body();
+        } catch (...) {
+            const int e = hvc::exception_code();
+            std::lock_guard<std::mutex> lk(mu);
+            error.store(e);
+            cv.notify_all();
+        }
+    };
+    const auto wall0 = std::chrono::steady_clock::now();
+    int r = pool_ready(c, threads);
+    if (r) return r;
+    bool completed = false;
+    hvc::PoolScope scope(c->pool, [&] {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!completed && !error.load()) error.store(HVC_E_INTERNAL);
+        cv.notify_all();
+    });
+    if ((r = c->pool.submit(worker, threads))) {
+        std::lock_guard<std::mutex> lk(mu);
+        error.store(r);
+        return r;
+    }
+
+    int rc = HVC_OK;
+    double h2d_ms = 0, k_ms = 0, d2h_ms = 0;
+    hipStream_t compute = c->stream;
+    wide_total_begin(c);
+    try {
+        std::vector<int> ok;
+        for (int k = 0; k < n_chunks && rc == HVC_OK; k++) {
+            const Chunk &ch = chunks[(size_t)k];
+            const int slot = k % NB;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return done_in_chunk[(size_t)k] == ch.count || error.load(); });
+            }
+            if (error.load()) { rc = error.load(); break; }
+            ok.clear();
+            for (int t = ch.first; t < ch.first + ch.count; t++) // (status[] of this chunk is final: its workers are done)
+                if (status[take[(size_t)t]] == HVC_OK && infos[take[(size_t)t]].coef_count) ok.push_back(take[(size_t)t]);
+            hipError_t he = hipSuccess;
+            if (k >= NB) he = hipStreamWaitEvent(c->copy_stream, c->ev_kern[slot], 0);
+            if (he == hipSuccess) he = hipEventRecord(c->ev_t[0], c->copy_stream);
+            if (he == hipSuccess && ch.coef_bytes && !ok.empty()) {
+                he = hipMemcpyAsync(c->d_ring[slot], c->h_ring[slot], ch.coef_bytes, hipMemcpyHostToDevice, c->copy_stream);
+                coef_total += ch.coef_bytes;
+            }
+            if (he == hipSuccess) he = hipEventRecord(c->ev_h2d[slot], c->copy_stream);
+            if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_h2d[slot], 0);
+            if (he == hipSuccess) he = hipEventRecord(c->ev_t[1], compute);
+            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
+            uint8_t *dst = where == HVC_MEM_DEVICE ? pixels : (uint8_t *)c->d_oring[slot];
+            const size_t *dst_off = where == HVC_MEM_DEVICE ? pixel_offsets : pix_rel.data();
+            rc = mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), infos, ok.data(), (int)ok.size(), dst, dst_off, c->profiling);
+            if (rc) break;
+            he = hipEventRecord(c->ev_t[2], compute);
+            if (he == hipSuccess && where == HVC_MEM_HOST) {
+                // the records of consecutive good files go back in one copy where only alignment padding lies between them
+                // (the padding between records is nobody's; a failed file's record is never touched)
+                size_t run_lo = 0, run_hi = 0;
+                auto flush = [&]() {
+                    if (run_hi > run_lo && he == hipSuccess)
+                        he = hipMemcpyAsync(pixels + ch.pix_lo + run_lo, dst + run_lo, run_hi - run_lo, hipMemcpyDeviceToHost, compute);
+                    run_lo = run_hi = 0;
+                };
+                int prev_t = -2;
+                for (int t = ch.first; t < ch.first + ch.count; t++) {
+                    const int f = take[(size_t)t];
+                    if (status[f] != HVC_OK || !infos[f].pixel_bytes) continue;
+                    const size_t lo = pix_rel[(size_t)f], hi = lo + infos[f].pixel_bytes;
+                    const bool joins = run_hi > run_lo && t == prev_t + 1 && lo >= run_hi && lo - run_hi < 4096;
+                    if (!joins) flush();
+                    if (run_hi == run_lo) run_lo = lo;
+                    run_hi = hi;
+                    prev_t = t;
+                }
+                flush();
+            }
+            if (he == hipSuccess) he = hipEventRecord(c->ev_kern[slot], compute);
+            if (he == hipSuccess) he = hipEventRecord(c->ev_t[3], compute);
+            if (he == hipSuccess) he = wait_event(c->ev_h2d[slot]); // the pinned slot goes to chunk k + NB
+            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                released_upto = k + NB;
+                cv.notify_all();
+            }
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, c->ev_t[0], c->ev_h2d[slot]) == hipSuccess) h2d_ms += ms;
+            if (wait_event(c->ev_t[3]) == hipSuccess) { // (the events are shared by all chunks: read before the next records them)
+                if (hipEventElapsedTime(&ms, c->ev_t[1], c->ev_t[2]) == hipSuccess) k_ms += ms;
+                if (hipEventElapsedTime(&ms, c->ev_t[2], c->ev_t[3]) == hipSuccess) d2h_ms += ms;
+            }
+        }
+    } catch (...) {
+        rc = hvc::exception_code();
+    }
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (rc != HVC_OK) error.store(rc);
+        else completed = true;
+        cv.notify_all();
+    }
+    {
+        const int te = scope.finish();
+        if (rc == HVC_OK && te) rc = te;
+    }
+    if (rc == HVC_OK && error.load()) rc = error.load();
+    {
+        const hipError_t h1 = hipStreamSynchronize(compute), h2 = hipStreamSynchronize(c->copy_stream);
+        if (rc == HVC_OK && (h1 != hipSuccess || h2 != hipSuccess)) rc = fail_hip(c, h1 != hipSuccess ? h1 : h2);
+    }
+    if (stats) {
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+        stats->entropy_ms_sum = (double)entropy_ns.load() * 1e-6;
+        stats->h2d_ms_sum = h2d_ms;
+        stats->kernel_ms_sum = k_ms;
+        stats->d2h_ms_sum = d2h_ms;
+        stats->chunks = n_chunks;
+        stats->threads = threads;
+        stats->frames_per_chunk = largest;
+        stats->coef_bytes = coef_total;
+    }
+    return rc;
+}

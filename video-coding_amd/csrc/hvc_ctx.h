@@ -7,6 +7,7 @@
 //   hvc_capi_reader.hip  the GPU Huffman reader's entry point and the batch pipeline built on it
 //   hvc_capi_files.hip   the GPU Huffman coder's entry point and the batch pipelines that write files
 //   hvc_rgb.hip          the RGB colour pass (kernels and launches; its entry points live with their families in the files above)
+//   hvc_capi_mixed.hip   batches of frames / files of different geometry and tables (hvc_decode_frames_mixed, hvc_jpeg_decode_batch_mixed)
 //   hvc_capi_async.hip   pinned host memory and the slots of the asynchronous seam (hvc_decode_frames_submit / hvc_wait)
 #ifndef HVC_CTX_H
 #define HVC_CTX_H
@@ -110,6 +111,11 @@ struct hvc_ctx {
     size_t gd_dcv_cap = 0;
     void *d_dcfix = nullptr;  // blocks with a DC beyond int16 (hvc::WideDc): ids, true DCs, count
     size_t dcfix_cap = 0;
+    // hvc_decode_frames_mixed (hvc_capi_mixed.hip): the plan's tables on the device, the pinned image they were uploaded
+    // from (a call whose plan is the same bytes uploads nothing) and the event behind the last upload
+    void *d_mixed = nullptr, *h_mixed = nullptr;
+    size_t mixed_cap = 0, h_mixed_cap = 0, mixed_len = 0; // mixed_len: bytes of the image d_mixed holds, 0 = none
+    hipEvent_t ev_mixed = nullptr;
     // hvc_set_host_cpus: the CPUs the batch pipelines' host threads may run on (empty = no restriction)
     bool have_cpus = false;
     cpu_set_t cpus;
@@ -438,6 +444,14 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
 // hvc_capi_reader.hip: the same with the GPU reader (behind hvc_jpeg_decode_batch_gpu)
 int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads, int frames_per_chunk,
                      uint8_t *pixels, size_t pixel_fs, int where, hvc_batch_stats *stats, OutputForm form);
+
+// hvc_capi_mixed.hip: frames / files of different geometry and tables in one call (behind hvc_decode_frames_mixed in hvc_capi.hip
+// and hvc_jpeg_decode_batch_mixed in hvc_capi_jpeg.hip)
+int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
+                             uint8_t *pixels, const size_t *pixel_offsets, int where);
+int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads, size_t chunk_bytes,
+                            const hvc_jpeg_info *infos, int *status, const size_t *pixel_offsets, uint8_t *pixels, size_t pixel_cap,
+                            int where, hvc_batch_stats *stats);
 
 // hvc_rgb.hip: the colour pass (k_ycc_to_rgb / k_rgb_to_ycc) on device memory, for the entry points that end or begin with it
 struct RgbImage { // an RGB image as the caller laid it out (hvc_rgb_layout; strides of 0 resolved to tight)

@@ -38,6 +38,7 @@ SYMBOLS = [
     "hvc_jpeg_encode_rgb",
     "hvc_jpeg_scaled_info", "hvc_decode_frames_scaled", "hvc_jpeg_decode_scaled", "hvc_jpeg_decode_scaled_rgb",
     "hvc_jpeg_decode_batch_scaled",
+    "hvc_jpeg_mixed_layout", "hvc_decode_frames_mixed", "hvc_jpeg_decode_batch_mixed",
 ]
 HVC_RGB = {"interleaved": 0, "planar": 1}  # enum hvc_rgb_layout: [H, W, 3] / [3, H, W]
 HVC_YUV_400 = 400   # luma only, beside 420 / 422 / 444
@@ -257,6 +258,10 @@ def lib():
         L.hvc_jpeg_decode_scaled_rgb.argtypes = [vp, vp, sz, i, ip, vp, sz, sz, i]
         L.hvc_jpeg_decode_batch_scaled.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, i, i, i, vp, sz, i,
                                                    C.POINTER(BatchStats)]
+        L.hvc_jpeg_mixed_layout.argtypes = [C.POINTER(vp), C.POINTER(sz), i, sz, ip, C.POINTER(i), C.POINTER(sz), C.POINTER(sz)]
+        L.hvc_decode_frames_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), i]
+        L.hvc_jpeg_decode_batch_mixed.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, ip, C.POINTER(i), C.POINTER(sz), vp, sz, i,
+                                                  C.POINTER(BatchStats)]
         L.hvc_checksum_records.argtypes = [vp, vp, sz, sz, i, vp, i]
         L.hvc_set_host_cpus.argtypes = [vp, C.c_char_p]
         L.hvc_get_host_cpus.argtypes = [vp, C.c_char_p, sz, C.POINTER(i)]
@@ -466,6 +471,32 @@ def jpeg_read_header(data: bytes):
     info = JpegInfo()
     _chk(lib().hvc_jpeg_read_header(data, len(data), C.byref(info)), "hvc_jpeg_read_header")
     return info
+
+
+class MixedLayout:
+    """what hvc_jpeg_mixed_layout makes of a list of files: infos (ctypes array of JpegInfo), status and pixel_offsets (ctypes
+    arrays, one entry per file) and total_bytes -- the size of the buffer that holds every good file's pixel record"""
+
+    def __init__(self, jpegs, align=0):
+        n = len(jpegs)
+        self.jpegs = list(jpegs)
+        self.ptrs = (C.c_void_p * n)(*[C.cast(C.c_char_p(j), C.c_void_p) for j in self.jpegs])
+        self.sizes = (C.c_size_t * n)(*[len(j) for j in self.jpegs])
+        self.infos = (JpegInfo * n)()
+        self.status = (C.c_int * n)()
+        self.pixel_offsets = (C.c_size_t * n)()
+        total = C.c_size_t(0)
+        _chk(lib().hvc_jpeg_mixed_layout(self.ptrs, self.sizes, n, align, self.infos, self.status, self.pixel_offsets,
+                                         C.byref(total)), "hvc_jpeg_mixed_layout")
+        self.total_bytes = total.value
+
+    def __len__(self):
+        return len(self.jpegs)
+
+
+def jpeg_mixed_layout(jpegs, align=0):
+    """headers of a list of files (bytes) -> MixedLayout; align: a power of two >= 8, 0 = 256"""
+    return MixedLayout(jpegs, align)
 
 
 def jpeg_scaled_info(info, scale_denom):
@@ -951,6 +982,48 @@ class Context:
         arr = comps if not isinstance(comps, list) else components(comps)
         _chk(lib().hvc_decode_frames(self._h, ca, coef_frame_stride, q.ctypes.data, q.shape[0], arr, len(arr),
                                      n_frames, pa, pixel_frame_stride, w1))
+
+    def decode_frames_mixed(self, coefs, coef_offsets, infos, pixels, pixel_offsets):
+        """hvc_decode_frames_mixed: frame f = infos[f] (JpegInfo: layout and tables), its coefficient record at
+        coefs[coef_offsets[f]:] (int16 elements), its pixel record at pixels[pixel_offsets[f]:] (bytes).  coefs / pixels:
+        numpy (host) or torch cuda tensors, both in the same memory space."""
+        ca, w1 = _addr(coefs)
+        pa, w2 = _addr(pixels)
+        assert w1 == w2, "coefs and pixels must live in the same memory space"
+        n = len(infos)
+        arr = infos if isinstance(infos, C.Array) else (JpegInfo * n)(*infos)
+        co = coef_offsets if isinstance(coef_offsets, C.Array) else (C.c_size_t * n)(*[int(x) for x in coef_offsets])
+        po = pixel_offsets if isinstance(pixel_offsets, C.Array) else (C.c_size_t * n)(*[int(x) for x in pixel_offsets])
+        _chk(lib().hvc_decode_frames_mixed(self._h, ca, co, arr, n, pa, po, w1), "hvc_decode_frames_mixed")
+
+    def jpeg_decode_batch_mixed(self, jpegs, threads=8, chunk_bytes=0, device=False, layout=None, pixels=None):
+        """Files of any sizes, samplings and tables in one call.  Returns one (status, info, planes) per file: status = the file's
+        own hvc_status (0 = decoded), planes = info.planes(...) views of ONE buffer (numpy, or a torch cuda tensor with
+        device=True), None for a file whose header could not be read.  layout / pixels: a MixedLayout made before and a buffer of
+        layout.total_bytes to decode into (default: made here, zero-filled).  The call's hvc_batch_stats: self.last_batch_stats."""
+        lay = layout if layout is not None else MixedLayout(jpegs)
+        n = len(lay)
+        if pixels is None:
+            if device:
+                import torch
+                pixels = torch.zeros(max(lay.total_bytes, 8), dtype=torch.uint8, device="cuda")
+            else:
+                pixels = np.zeros(max(lay.total_bytes, 8), dtype=np.uint8)
+        pa, where = _addr(pixels)
+        cap = pixels.numel() if hasattr(pixels, "numel") else pixels.size
+        st = BatchStats()
+        status = (C.c_int * n)(*lay.status)
+        _chk(lib().hvc_jpeg_decode_batch_mixed(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, lay.infos, status,
+                                               lay.pixel_offsets, pa, cap, where, C.byref(st)), "hvc_jpeg_decode_batch_mixed")
+        self.last_batch_stats = st
+        out = []
+        for f in range(n):
+            if lay.status[f] != 0:
+                out.append((status[f], None, None))
+                continue
+            info, off = lay.infos[f], lay.pixel_offsets[f]
+            out.append((status[f], info, info.planes(pixels[off:off + info.pixel_bytes])))
+        return out
 
     def decode_frames_yuv444(self, coefs, coef_frame_stride, qtabs, comps, n_frames, width, height, frames,
                              frame_stride=None):
