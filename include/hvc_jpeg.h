@@ -746,9 +746,11 @@ HVC_API int hvc_jpeg_decode_batch_scaled(hvc_ctx *ctx, const uint8_t *const *jpe
 /* Mixed batches: frames and files of DIFFERENT sizes, samplings and quantiser tables in one call.  Every other batch entry
  * point takes one geometry and one set of tables and refuses a file that differs from the first (and still does); a directory
  * of photographs has as many geometries as files.  Here the block stage takes its work decomposition from tables in device
- * memory (k_decode_mixed): a launch serves any set of planes, a 64 x 64 thumbnail costs three wavefronts.  Full-size padded
- * planes only: no RGB, 4:4:4 or reduced-size form, the host Huffman reader only, no side list of DCs beyond int16.  With
- * HVC_ARITH_HARDCAML set the two ctx functions return HVC_E_INVALID_ARG; hvc_set_decode_kernel(ctx, 2) sends every block
+ * memory (k_decode_mixed): a launch serves any set of planes, a 64 x 64 thumbnail costs three wavefronts.  The output is
+ * full-size padded planes, or RGB images (below: hvc_jpeg_mixed_rgb_layout, hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb,
+ * hvc_jpeg_decode_batch_mixed_rgb, whose colour pass k_ycc_to_rgb_mixed takes its decomposition from device memory the same
+ * way); there is no 4:4:4-planar or reduced-size form, the host Huffman reader only, no side list of DCs beyond int16.  With
+ * HVC_ARITH_HARDCAML set the ctx functions return HVC_E_INVALID_ARG; hvc_set_decode_kernel(ctx, 2) sends every block
  * through the int64 arithmetic, other selections are ignored; hvc_last_wide_blocks counts the blocks that took it. */
 
 /* headers of n_files files -> infos[f], status[f] (what hvc_jpeg_read_header returns for file f),
@@ -782,6 +784,51 @@ HVC_API int hvc_jpeg_decode_batch_mixed(hvc_ctx *ctx, const uint8_t *const *jpeg
                                         int threads, size_t chunk_bytes, const hvc_jpeg_info *infos, int *status,
                                         const size_t *pixel_offsets, uint8_t *pixels, size_t pixel_cap, int where,
                                         hvc_batch_stats *stats);
+
+/* Mixed batches to RGB: the colour pass of the RGB section above (same definition, byte for byte what hvc_yuv_to_rgb /
+ * hvc_decode_frames_rgb / hvc_jpeg_decode_rgb give for each image alone) over images of ANY size and sampling in one launch.
+ * Image f is infos[f].width x .height; its sampling follows from infos[f].n_comp and .comp[].hscale / .vscale by the rule of
+ * hvc_jpeg_decode_rgb (4:2:0, 4:2:2, 4:4:4, grey; anything else has no RGB image); its chroma window is ceil(width / 2) x
+ * ceil(height / 2) (4:2:0) and so on, as in hvc_decode_frames_rgb.  It lies at rgb + rgb_offsets[f] -- any byte offset -- with
+ * rows rgb_row_strides[f] bytes apart (>= 3 * width interleaved, >= width planar; an entry of 0, or rgb_row_strides == NULL:
+ * tight rows) and planar planes rgb_row_strides[f] * height apart.  One call has one `layout`.  Images whose address and
+ * strides are multiples of 8 are written in 8-byte pieces, the others byte by byte: tight interleaved rows qualify only
+ * when width % 8 == 0, so row_align = 8 buys the fast path for every width.  A frame with width * height == 0 is skipped.
+ * Parameter lists are the issue's; none was adjusted.
+ *
+ * hvc_jpeg_mixed_rgb_layout (host only): headers as hvc_jpeg_mixed_layout reads them; a file whose header reads but whose
+ *   sampling has no RGB image gets status[f] = HVC_E_INVALID_ARG.  A file with a nonzero status takes no room.  A good
+ *   file's record is rgb_row_strides[f] * height bytes (planar: * 3), rgb_row_strides[f] = 3 * width (planar: width) rounded
+ *   up to row_align; records in file order, each start rounded up to align.  align, row_align: powers of two >= 1
+ *   (else HVC_E_INVALID_ARG); align 0 = 256, row_align 0 = 1 (tight rows: what a tensor view wants).
+ * hvc_yuv_to_rgb_mixed: the colour pass alone over planes that are already there: frame f's planes at yuv + yuv_offsets[f],
+ *   laid out by infos[f].layout (plane_offset, stride; a component that names its blocks must hold the window).
+ *   HVC_MEM_DEVICE: one launch, enqueued on ctx's stream, returns at once, honours hvc_set_profiling (the pair brackets
+ *   k_ycc_to_rgb_mixed); HVC_MEM_HOST: staged through context scratch, the call blocks.  Bytes between rows and between
+ *   records are never written.  HVC_E_INVALID_ARG: a frame whose sampling has no RGB image, a stride below its row, a window
+ *   outside its planes; HVC_E_TOO_LARGE: a side above 2^24 or more lanes than the launch can index.
+ * hvc_decode_frames_mixed_rgb: hvc_decode_frames_mixed into context scratch (tight records), then the mixed colour pass; the
+ *   planes never leave the GPU.  coefs / coef_offsets / alignment rules as there; hvc_last_wide_blocks counts as after
+ *   hvc_decode_frames_mixed; a device-memory call honours hvc_set_profiling as that one does (the pair brackets k_decode_mixed).
+ * hvc_jpeg_decode_batch_mixed_rgb: hvc_jpeg_decode_batch_mixed's pipeline with the colour pass behind every chunk's block
+ *   stage, on the same stream; infos / status / rgb_offsets / rgb_row_strides as hvc_jpeg_mixed_rgb_layout made them.  PER-FILE
+ *   results as there: a file that fails at its header, by its sampling (HVC_E_INVALID_ARG) or in its scan leaves its RGB record
+ *   untouched and stops nobody; a DC beyond int16 is HVC_E_RANGE.  rgb_cap: bytes of rgb; every good file's image must lie
+ *   inside (HVC_E_INVALID_ARG).  Host output: the alignment padding between the records of two good files may be overwritten
+ *   (bytes between the rows of an image are not).  stats as hvc_jpeg_decode_batch_mixed; kernel_ms_sum includes the colour pass. */
+HVC_API int hvc_jpeg_mixed_rgb_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int layout, size_t align,
+                                      size_t row_align, hvc_jpeg_info *infos, int *status, size_t *rgb_offsets,
+                                      size_t *rgb_row_strides, size_t *total_bytes);
+HVC_API int hvc_yuv_to_rgb_mixed(hvc_ctx *ctx, const uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos,
+                                 int n_frames, uint8_t *rgb, const size_t *rgb_offsets, const size_t *rgb_row_strides,
+                                 int layout, int where);
+HVC_API int hvc_decode_frames_mixed_rgb(hvc_ctx *ctx, const int16_t *coefs, const size_t *coef_offsets,
+                                        const hvc_jpeg_info *infos, int n_frames, uint8_t *rgb, const size_t *rgb_offsets,
+                                        const size_t *rgb_row_strides, int layout, int where);
+HVC_API int hvc_jpeg_decode_batch_mixed_rgb(hvc_ctx *ctx, const uint8_t *const *jpegs, const size_t *sizes, int n_files,
+                                            int threads, size_t chunk_bytes, const hvc_jpeg_info *infos, int *status,
+                                            const size_t *rgb_offsets, const size_t *rgb_row_strides, uint8_t *rgb,
+                                            size_t rgb_cap, int layout, int where, hvc_batch_stats *stats);
 
 /* K5 (no counterpart in the reference): what a benchmark or a pipeline produced, said in
  * 64 bits per record without bringing the records back.  For r < n_records

@@ -833,6 +833,45 @@ let jpeg_decode_batch_mixed =
     @-> ptr char @-> size_t @-> int @-> ptr Batch_stats.t @-> returning int)
 ;;
 
+(* mixed batches to RGB: one launch of the colour pass over images of any size and sampling.
+   int hvc_jpeg_mixed_rgb_layout(jpegs, sizes, n_files, layout, align, row_align, infos, status, rgb_offsets,
+                                 rgb_row_strides, total_bytes)                                                  host only *)
+let jpeg_mixed_rgb_layout =
+  foreign
+    "hvc_jpeg_mixed_rgb_layout"
+    (ptr string @-> ptr size_t @-> int @-> int @-> size_t @-> size_t @-> ptr Jpeg_info.t @-> ptr int @-> ptr size_t
+    @-> ptr size_t @-> ptr size_t @-> returning int)
+;;
+
+(* int hvc_yuv_to_rgb_mixed(ctx, yuv, yuv_offsets, infos, n_frames, rgb, rgb_offsets, rgb_row_strides, layout, where) *)
+let yuv_to_rgb_mixed =
+  foreign
+    "hvc_yuv_to_rgb_mixed"
+    ~release_runtime_lock:true
+    (ctx @-> ptr char @-> ptr size_t @-> ptr Jpeg_info.t @-> int @-> ptr char @-> ptr size_t @-> ptr size_t @-> int
+    @-> int @-> returning int)
+;;
+
+(* int hvc_decode_frames_mixed_rgb(ctx, coefs, coef_offsets, infos, n_frames, rgb, rgb_offsets, rgb_row_strides, layout,
+                                   where) *)
+let decode_frames_mixed_rgb =
+  foreign
+    "hvc_decode_frames_mixed_rgb"
+    ~release_runtime_lock:true
+    (ctx @-> ptr int16_t @-> ptr size_t @-> ptr Jpeg_info.t @-> int @-> ptr char @-> ptr size_t @-> ptr size_t @-> int
+    @-> int @-> returning int)
+;;
+
+(* int hvc_jpeg_decode_batch_mixed_rgb(ctx, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, rgb_offsets,
+                                       rgb_row_strides, rgb, rgb_cap, layout, where, stats) *)
+let jpeg_decode_batch_mixed_rgb =
+  foreign
+    "hvc_jpeg_decode_batch_mixed_rgb"
+    ~release_runtime_lock:true
+    (ctx @-> ptr string @-> ptr size_t @-> int @-> int @-> size_t @-> ptr Jpeg_info.t @-> ptr int @-> ptr size_t
+    @-> ptr size_t @-> ptr char @-> size_t @-> int @-> int @-> ptr Batch_stats.t @-> returning int)
+;;
+
 (* int hvc_jpeg_encode_rgb(ctx, rgb, rgb_row_stride, layout, width, height, chroma, quality, out, cap, out_len) *)
 let jpeg_encode_rgb =
   foreign

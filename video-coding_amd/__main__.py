@@ -7,9 +7,10 @@
     python -m video_coding_amd model decode frame IN.jpg OUT.ppm -rgb       the RGB image as a binary PPM (P6)
     python -m video_coding_amd model decode frame IN.jpg OUT -scale 2|4|8   at reduced size: the cropped scaled planes (with -rgb: the PPM)
     python -m video_coding_amd model encode frame IN.ppm WxH OUT.jpg -rgb   from a binary PPM of that size
-    python -m video_coding_amd model decode frames OUT_DIR IN1.jpg IN2.jpg ... [-restart-markers] [-threads 8]
+    python -m video_coding_amd model decode frames OUT_DIR IN1.jpg IN2.jpg ... [-restart-markers] [-threads 8] [-rgb]
                                                       files of any sizes, samplings and tables in ONE mixed batch call
-                                                      (hvc_jpeg_decode_batch_mixed): OUT_DIR/<name>.yuv as `decode frame` writes it
+                                                      (hvc_jpeg_decode_batch_mixed): OUT_DIR/<name>.yuv as `decode frame` writes it;
+                                                      -rgb (hvc_jpeg_decode_batch_mixed_rgb): OUT_DIR/<name>.ppm as `decode frame -rgb`
                                                       (an extension: JFIF colour conversion, hvc_jpeg_decode_rgb / _encode_rgb)
     python -m video_coding_amd oyuv compare {max-difference,mean-difference,mean-square-error,psnr}
                                             {y,u,v,yuv} FILE-1 FILE-2 WxH [-format 420]
@@ -124,11 +125,38 @@ def model_decode_frame(a):
         sys.stdout.buffer.write(out.tobytes())
 
 
+def model_decode_frames_rgb(a, datas):
+    """... through one hvc_jpeg_decode_batch_mixed_rgb call: OUT_DIR/<name>.ppm each"""
+    import os
+    ctx = hvc.Context(a.device)
+    try:
+        if a.restart_markers:
+            ctx.set_restart_markers(True)
+        results = ctx.jpeg_decode_batch_mixed_rgb(datas, threads=a.threads)
+    finally:
+        ctx.close()
+    os.makedirs(a.out_dir, exist_ok=True)
+    failed = 0
+    for path, (status, info, image) in zip(a.bits, results):
+        if status != 0:
+            failed += 1
+            print("%s: %s" % (path, hvc.HvcError(status)), file=sys.stderr)
+            continue
+        with open(os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + ".ppm"), "wb") as fh:
+            fh.write(b"P6\n%d %d\n255\n" % (info.width, info.height))
+            if image is not None:
+                fh.write(np.ascontiguousarray(image).tobytes())
+    if failed:
+        raise SystemExit(1)
+
+
 def model_decode_frames(a):
     """every file through one hvc_jpeg_decode_batch_mixed call; a file that fails gets a line on stderr and the others are
     still written; the exit status says whether any failed"""
     import os
     datas = [open(p, "rb").read() for p in a.bits]
+    if a.rgb:
+        return model_decode_frames_rgb(a, datas)
     lay = hvc.jpeg_mixed_layout(datas)
     pixels = np.zeros(max(lay.total_bytes, 8), dtype=np.uint8)
     ctx = hvc.Context(a.device)
@@ -443,6 +471,7 @@ def parser():
     p.add_argument("bits", nargs="+")
     p.add_argument("-restart-markers", dest="restart_markers", action="store_true")
     p.add_argument("-threads", type=int, default=8)
+    p.add_argument("-rgb", action="store_true", help="write every RGB image as a binary PPM (hvc_jpeg_decode_batch_mixed_rgb)")
     p.set_defaults(fn=model_decode_frames)
     enc = model.add_parser("encode").add_subparsers(dest="what", required=True)
     p = enc.add_parser("frame")

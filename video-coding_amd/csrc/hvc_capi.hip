@@ -243,6 +243,7 @@ void hvc_destroy(hvc_ctx *c) {
         if (c->h_ring[i]) (void)hipHostFree(c->h_ring[i]);
         if (c->d_ring[i]) (void)hipFree(c->d_ring[i]);
         if (c->d_oring[i]) (void)hipFree(c->d_oring[i]);
+        if (c->d_pring[i]) (void)hipFree(c->d_pring[i]);
         if (c->ev_h2d[i]) (void)hipEventDestroy(c->ev_h2d[i]);
         if (c->ev_kern[i]) (void)hipEventDestroy(c->ev_kern[i]);
         if (c->eh_in[i]) (void)hipHostFree(c->eh_in[i]);
@@ -287,6 +288,9 @@ void hvc_destroy(hvc_ctx *c) {
     if (c->d_mixed) (void)hipFree(c->d_mixed);
     if (c->h_mixed) (void)hipHostFree(c->h_mixed);
     if (c->ev_mixed) (void)hipEventDestroy(c->ev_mixed);
+    if (c->d_mixed_rgb) (void)hipFree(c->d_mixed_rgb);
+    if (c->h_mixed_rgb) (void)hipHostFree(c->h_mixed_rgb);
+    if (c->ev_mixed_rgb) (void)hipEventDestroy(c->ev_mixed_rgb);
     delete c->gd_tables_host;
     if (c->hd_tables) (void)hipFree(c->hd_tables);
     if (c->hd_opt) (void)hipFree(c->hd_opt);
@@ -976,6 +980,11 @@ int hvc_decode_frames(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const ui
 int hvc_decode_frames_mixed(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
                             uint8_t *pixels, const size_t *pixel_offsets, int where) try {
     return decode_frames_mixed_impl(c, coefs, coef_offsets, infos, n_frames, pixels, pixel_offsets, where);
+} HVC_ABI_CATCH
+// ... and on to RGB images through k_ycc_to_rgb_mixed: the planes stay in context scratch
+int hvc_decode_frames_mixed_rgb(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
+                                uint8_t *rgb, const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where) try {
+    return decode_frames_mixed_rgb_impl(c, coefs, coef_offsets, infos, n_frames, rgb, rgb_offsets, rgb_row_strides, layout, where);
 } HVC_ABI_CATCH
 
 // ---------------------------------------------------------------------------

@@ -5,6 +5,7 @@
 // pipeline.
 #include "hvc_ctx.h"
 #include "hvc_mixed_plan.h"
+#include "hvc_mixed_rgb_plan.h"
 
 // ---------------------------------------------------------------------------
 // single-frame conveniences (host memory)
@@ -675,6 +676,22 @@ int hvc_jpeg_decode_batch_mixed(hvc_ctx *c, const uint8_t *const *jpegs, const s
                                 uint8_t *pixels, size_t pixel_cap, int where, hvc_batch_stats *stats) try {
     return decode_batch_mixed_impl(c, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, pixel_offsets, pixels, pixel_cap,
                                    where, stats);
+} HVC_ABI_CATCH
+
+// ... to RGB images: where every file's image goes (host only: hvc_mixed_rgb_plan.cpp), and the pipeline with the colour pass
+// behind every chunk's block stage
+int hvc_jpeg_mixed_rgb_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int layout, size_t align, size_t row_align,
+                              hvc_jpeg_info *infos, int *status, size_t *rgb_offsets, size_t *rgb_row_strides, size_t *total_bytes) try {
+    return hvc::mixed_rgb_layout(jpegs, sizes, n_files, layout, align, row_align, infos, status, rgb_offsets, rgb_row_strides, total_bytes);
+} HVC_ABI_CATCH
+int hvc_jpeg_decode_batch_mixed_rgb(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads,
+                                    size_t chunk_bytes, const hvc_jpeg_info *infos, int *status, const size_t *rgb_offsets,
+                                    const size_t *rgb_row_strides, uint8_t *rgb, size_t rgb_cap, int layout, int where,
+                                    hvc_batch_stats *stats) try {
+    if (!rgb_offsets || (layout != HVC_RGB_INTERLEAVED && layout != HVC_RGB_PLANAR)) return HVC_E_INVALID_ARG;
+    MixedForm form;
+    form.rgb_offsets = rgb_offsets, form.rgb_row_strides = rgb_row_strides, form.layout = layout;
+    return decode_batch_mixed_impl(c, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, rgb_offsets, rgb, rgb_cap, where, stats, form);
 } HVC_ABI_CATCH
 
 int hvc_jpeg_decode_batch_yuv444(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames,

@@ -1,9 +1,12 @@
 // hvc_capi_mixed.hip -- batches of frames (behind hvc_decode_frames_mixed) and of files (behind hvc_jpeg_decode_batch_mixed) that share
 // neither geometry nor quantiser tables: the host plan of hvc_mixed_plan.cpp, its tables in device memory, one launch of
 // k_decode_mixed (hvc_mixed.hip) per call or per chunk.  The pipeline reuses the context's pinned / device rings, events and
-// worker pool of hvc_jpeg_decode_batch; what it cuts the batch by is bytes, not frames.
+// worker pool of hvc_jpeg_decode_batch; what it cuts the batch by is bytes, not frames.  The RGB forms (hvc_yuv_to_rgb_mixed,
+// hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed_rgb) put one launch of k_ycc_to_rgb_mixed (hvc_mixed_rgb.hip) behind
+// the planes, from the host plan of hvc_mixed_rgb_plan.cpp.
 #include "hvc_ctx.h"
 #include "hvc_mixed.h"
+#include "hvc_mixed_rgb.h"
 
 namespace {
 
@@ -21,43 +24,81 @@ ImageParts image_parts(const hvc::MixedPlan &plan) {
     return p;
 }
 
-// the plan's tables in c->d_mixed, in stream order: uploaded from the pinned image unless the device already holds these bytes
+// A plan's image in a device buffer of the context, in stream order: uploaded from the pinned copy unless the device
+// already holds these bytes.
+struct PlanBuf {
+    void *&d, *&h;
+    size_t &cap, &h_cap, &len; // len: bytes of the image d holds, 0 = none
+    hipEvent_t &ev;            // behind the last upload
+};
+int upload_image(hvc_ctx *c, const PlanBuf &b, const std::vector<unsigned char> &img) {
+    const size_t total = img.size();
+    if (!b.ev) HIPCHK(c, hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
+    const bool same = b.len == total && b.h && !std::memcmp(b.h, img.data(), total);
+    if (same) return HVC_OK;
+    b.len = 0;
+    int r = grow(c, &b.d, &b.cap, total);
+    if (r) return r;
+    if (total > b.h_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (b.h) (void)hipHostFree(b.h);
+        b.h = nullptr;
+        b.h_cap = 0;
+        const size_t want = total + total / 4 + 4096;
+        if (hipHostMalloc(&b.h, want, hipHostMallocDefault) != hipSuccess) {
+            b.h = nullptr;
+            return HVC_E_OUT_OF_MEMORY;
+        }
+        b.h_cap = want;
+    } else {
+        HIPCHK(c, wait_event(b.ev)); // (the last upload has read the image)
+    }
+    std::memcpy(b.h, img.data(), total);
+    HIPCHK(c, hipMemcpyAsync(b.d, b.h, total, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(b.ev, c->stream));
+    b.len = total;
+    return HVC_OK;
+}
+
+// the block stage's tables in c->d_mixed
 int upload_plan(hvc_ctx *c, const hvc::MixedPlan &plan, hvc::MixedParams &P) {
     const ImageParts ip = image_parts(plan);
     std::vector<unsigned char> img(ip.total, 0);
     std::memcpy(img.data() + ip.planes, plan.planes.data(), plan.planes.size() * sizeof(hvc::MixedPlaneK));
     std::memcpy(img.data() + ip.tables, plan.tables.data(), plan.tables.size() * sizeof(hvc::MixedTableK));
     std::memcpy(img.data() + ip.map, plan.map.data(), plan.map.size() * sizeof(unsigned));
-    if (!c->ev_mixed) HIPCHK(c, hipEventCreateWithFlags(&c->ev_mixed, hipEventDisableTiming));
-    const bool same = c->mixed_len == ip.total && c->h_mixed && !std::memcmp(c->h_mixed, img.data(), ip.total);
-    if (!same) {
-        c->mixed_len = 0;
-        int r = grow(c, &c->d_mixed, &c->mixed_cap, ip.total);
-        if (r) return r;
-        if (ip.total > c->h_mixed_cap) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->h_mixed) (void)hipHostFree(c->h_mixed);
-            c->h_mixed = nullptr;
-            c->h_mixed_cap = 0;
-            const size_t want = ip.total + ip.total / 4 + 4096;
-            if (hipHostMalloc(&c->h_mixed, want, hipHostMallocDefault) != hipSuccess) {
-                c->h_mixed = nullptr;
-                return HVC_E_OUT_OF_MEMORY;
-            }
-            c->h_mixed_cap = want;
-        } else {
-            HIPCHK(c, wait_event(c->ev_mixed)); // (the last upload has read the image)
-        }
-        std::memcpy(c->h_mixed, img.data(), ip.total);
-        HIPCHK(c, hipMemcpyAsync(c->d_mixed, c->h_mixed, ip.total, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_mixed, c->stream));
-        c->mixed_len = ip.total;
-    }
+    const int r = upload_image(c, PlanBuf{c->d_mixed, c->h_mixed, c->mixed_cap, c->h_mixed_cap, c->mixed_len, c->ev_mixed}, img);
+    if (r) return r;
     const unsigned char *d = (const unsigned char *)c->d_mixed;
     P.planes = reinterpret_cast<const hvc::MixedPlaneK *>(d + ip.planes);
     P.tables = reinterpret_cast<const hvc::MixedTableK *>(d + ip.tables);
     P.map = reinterpret_cast<const unsigned *>(d + ip.map);
     P.n_units = (unsigned)plan.map.size();
+    return HVC_OK;
+}
+
+// The colour pass of a plan on DEVICE memory, enqueued on c->stream: its tables (images | map, each part on 16 bytes) go to
+// c->d_mixed_rgb, a buffer of their own.
+int mixed_rgb_launch_plan(hvc_ctx *c, const hvc::MixedRgbPlan &plan, int layout, const uint8_t *d_yuv, uint8_t *d_rgb, bool profile) {
+    if (plan.map.empty()) return HVC_OK; // no pixel at all: nothing to launch
+    const size_t map_at = (plan.images.size() * sizeof(hvc::MixedRgbImageK) + 15) & ~(size_t)15;
+    std::vector<unsigned char> img(map_at + ((plan.map.size() * sizeof(unsigned) + 15) & ~(size_t)15), 0);
+    std::memcpy(img.data(), plan.images.data(), plan.images.size() * sizeof(hvc::MixedRgbImageK));
+    std::memcpy(img.data() + map_at, plan.map.data(), plan.map.size() * sizeof(unsigned));
+    const int r = upload_image(c, PlanBuf{c->d_mixed_rgb, c->h_mixed_rgb, c->mixed_rgb_cap, c->h_mixed_rgb_cap, c->mixed_rgb_len, c->ev_mixed_rgb}, img);
+    if (r) return r;
+    hvc::MixedRgbParams P;
+    std::memset(&P, 0, sizeof P);
+    P.yuv = d_yuv;
+    P.rgb = d_rgb;
+    P.images = reinterpret_cast<const hvc::MixedRgbImageK *>(c->d_mixed_rgb);
+    P.map = reinterpret_cast<const unsigned *>((const unsigned char *)c->d_mixed_rgb + map_at);
+    P.n_units = (unsigned)plan.map.size();
+    P.planar = layout == HVC_RGB_PLANAR;
+    const int slot = (int)(c->k_calls % HVC_PROF_RING);
+    const hipError_t e = hvc::launch_ycc_to_rgb_mixed(P, c->stream, profile ? c->k0[slot] : nullptr, profile ? c->k1[slot] : nullptr);
+    if (e != hipSuccess) return fail_hip(c, e);
+    if (profile) c->k_calls++;
     return HVC_OK;
 }
 
@@ -116,6 +157,60 @@ void frame_spans(const hvc_jpeg_info &fi, size_t &coef_span, size_t &pixel_span)
     }
 }
 
+// The tight placement of a set's records in device scratch, each on 64 bytes: d_coef (int16 elements) / d_pix (bytes) per
+// frame, ptot = the bytes of all pixel records; coefs != nullptr (host memory): uploaded to c->d_in in that placement.
+int stage_coefs(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
+                std::vector<size_t> &d_coef, std::vector<size_t> &d_pix, size_t &ptot) {
+    d_coef.assign((size_t)n_frames, 0);
+    d_pix.assign((size_t)n_frames, 0);
+    std::vector<size_t> cspan((size_t)n_frames);
+    size_t ctot = 0;
+    ptot = 0;
+    for (int f = 0; f < n_frames; f++) {
+        size_t ps;
+        frame_spans(infos[f], cspan[(size_t)f], ps);
+        d_coef[(size_t)f] = ctot;
+        d_pix[(size_t)f] = ptot;
+        ctot += (cspan[(size_t)f] + 63) & ~(size_t)63;
+        ptot += (ps + 63) & ~(size_t)63;
+    }
+    if (!coefs) return HVC_OK;
+    const int r = grow(c, &c->d_in, &c->in_cap, ctot * sizeof(int16_t));
+    if (r) return r;
+    for (int f = 0; f < n_frames; f++)
+        if (cspan[(size_t)f])
+            HIPCHK(c, hipMemcpyAsync((int16_t *)c->d_in + d_coef[(size_t)f], coefs + coef_offsets[f], cspan[(size_t)f] * sizeof(int16_t),
+                                     hipMemcpyHostToDevice, c->stream));
+    return HVC_OK;
+}
+
+// the rows of the plan's images, device -> host, laid out alike on both sides apart from the record offsets: only the bytes
+// written (rows that touch: one copy per image)
+hipError_t download_images(const hvc::MixedRgbPlan &plan, int layout, const uint8_t *d_rgb, uint8_t *h_rgb, const size_t *h_offsets, hipStream_t s) {
+    for (size_t i = 0; i < plan.images.size(); i++) {
+        const hvc::MixedRgbImageK &k = plan.images[i];
+        const size_t row = hvc::mixed_rgb_row_bytes(layout, k.w), rows = hvc::mixed_rgb_rows(layout, k.h);
+        uint8_t *dst = h_rgb + h_offsets[plan.frame[i]];
+        const uint8_t *src = d_rgb + k.rgb_base;
+        const hipError_t e = k.row_stride == row ? hipMemcpyAsync(dst, src, row * rows, hipMemcpyDeviceToHost, s)
+                                                 : hipMemcpy2DAsync(dst, k.row_stride, src, k.row_stride, row, rows, hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// where the images of a host-memory call go in device scratch: one after another, each keeping its offset modulo 64 (the
+// 8-byte paths then run for exactly the images a device-memory call with these offsets would take them for)
+size_t stage_offsets(const size_t *offsets, const std::vector<size_t> &spans, std::vector<size_t> &d_off) {
+    size_t tot = 0;
+    d_off.assign(spans.size(), 0);
+    for (size_t f = 0; f < spans.size(); f++) {
+        d_off[f] = tot + (offsets[f] & 63);
+        tot = (d_off[f] + spans[f] + 63) & ~(size_t)63;
+    }
+    return tot;
+}
+
 } // namespace
 
 // behind hvc_decode_frames_mixed (hvc_capi.hip)
@@ -140,22 +235,10 @@ int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coe
     }
     // host memory: the frames' records one after another in c->d_in / c->d_out (whole 128-byte blocks: every alignment rule
     // holds), each plane's bytes copied back by themselves -- what the kernels wrote, never the caller's padding
-    std::vector<size_t> d_coef((size_t)n_frames), d_pix((size_t)n_frames), cspan((size_t)n_frames);
-    size_t ctot = 0, ptot = 0;
-    for (int f = 0; f < n_frames; f++) {
-        size_t ps;
-        frame_spans(infos[f], cspan[(size_t)f], ps);
-        d_coef[(size_t)f] = ctot;
-        d_pix[(size_t)f] = ptot;
-        ctot += (cspan[(size_t)f] + 63) & ~(size_t)63;
-        ptot += (ps + 63) & ~(size_t)63;
-    }
-    if ((r = grow(c, &c->d_in, &c->in_cap, ctot * sizeof(int16_t)))) return r;
+    std::vector<size_t> d_coef, d_pix;
+    size_t ptot = 0;
+    if ((r = stage_coefs(c, coefs, coef_offsets, infos, n_frames, d_coef, d_pix, ptot))) return r;
     if ((r = grow(c, &c->d_out, &c->out_cap, ptot))) return r;
-    for (int f = 0; f < n_frames; f++)
-        if (cspan[(size_t)f])
-            HIPCHK(c, hipMemcpyAsync((int16_t *)c->d_in + d_coef[(size_t)f], coefs + coef_offsets[f], cspan[(size_t)f] * sizeof(int16_t),
-                                     hipMemcpyHostToDevice, c->stream));
     wide_total_begin(c);
     if ((r = mixed_launch(c, (const int16_t *)c->d_in, d_coef.data(), infos, nullptr, n_frames, (uint8_t *)c->d_out, d_pix.data(), false))) {
         (void)hipStreamSynchronize(c->stream);
@@ -177,14 +260,124 @@ int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coe
     return HVC_OK;
 }
 
+// what the three RGB entry points check alike; HVC_OK with nothing = true: an empty set
+static int mixed_rgb_args(const hvc_ctx *c, const void *infos, const void *in_offsets, const void *rgb_offsets, int n_frames, int layout,
+                          int where, bool &nothing) {
+    if (!c || n_frames < 0 || (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE)) return HVC_E_INVALID_ARG;
+    if (layout != HVC_RGB_INTERLEAVED && layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
+    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (as the mixed block stage: no RTL form)
+    nothing = n_frames == 0;
+    if (!nothing && (!infos || !in_offsets || !rgb_offsets)) return HVC_E_INVALID_ARG;
+    return HVC_OK;
+}
+
+// the images' spans (bytes from the record's start to the last byte written) by the caller's row strides
+static int rgb_spans(const hvc_jpeg_info *infos, const size_t *rgb_row_strides, int n_frames, int layout, std::vector<size_t> &spans) {
+    spans.assign((size_t)n_frames, 0);
+    for (int f = 0; f < n_frames; f++) {
+        if (infos[f].width < 0 || infos[f].height < 0) return HVC_E_INVALID_ARG;
+        const size_t tight = hvc::mixed_rgb_row_bytes(layout, infos[f].width);
+        const size_t rs = rgb_row_strides && rgb_row_strides[f] ? rgb_row_strides[f] : tight;
+        if (rs < tight) return HVC_E_INVALID_ARG;
+        spans[(size_t)f] = hvc::mixed_rgb_span(layout, infos[f].width, infos[f].height, rs);
+    }
+    return HVC_OK;
+}
+
+// behind hvc_yuv_to_rgb_mixed (hvc_yuv.hip)
+int yuv_to_rgb_mixed_impl(hvc_ctx *c, const uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos, int n_frames, uint8_t *rgb,
+                          const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where) {
+    bool nothing = false;
+    int r = mixed_rgb_args(c, infos, yuv_offsets, rgb_offsets, n_frames, layout, where, nothing);
+    if (r || nothing) return r;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    hvc::MixedRgbPlan plan; // the caller's own offsets: checked for either kind of memory, launched on for device memory
+    if ((r = hvc::mixed_rgb_plan_build(infos, yuv_offsets, rgb_offsets, rgb_row_strides, layout, nullptr, n_frames, (uintptr_t)yuv,
+                                       (uintptr_t)rgb, false, plan)))
+        return r;
+    if (plan.map.empty()) return HVC_OK; // (a set without a pixel needs no memory)
+    if (!yuv || !rgb) return HVC_E_INVALID_ARG;
+    if (where == HVC_MEM_DEVICE) return mixed_rgb_launch_plan(c, plan, layout, yuv, rgb, c->profiling);
+    // host memory: the listed images' plane records and RGB images one after another in c->d_in / c->d_out
+    std::vector<size_t> yspan((size_t)n_frames, 0), rspan, d_yuv, d_rgb;
+    if ((r = rgb_spans(infos, rgb_row_strides, n_frames, layout, rspan))) return r;
+    for (size_t i = 0; i < plan.images.size(); i++) {
+        const hvc::MixedRgbImageK &k = plan.images[i];
+        const int f = plan.frame[i];
+        yspan[(size_t)f] = rgb_yuv_span(infos[f].layout, k.sampling, k.w, k.h, k.cw, k.ch);
+    }
+    for (int f = 0; f < n_frames; f++)
+        if (!yspan[(size_t)f]) rspan[(size_t)f] = 0; // (no image: no room)
+    const size_t ytot = stage_offsets(yuv_offsets, yspan, d_yuv), rtot = stage_offsets(rgb_offsets, rspan, d_rgb);
+    if ((r = grow(c, &c->d_in, &c->in_cap, ytot))) return r;
+    if ((r = grow(c, &c->d_out, &c->out_cap, rtot))) return r;
+    if ((r = hvc::mixed_rgb_plan_build(infos, d_yuv.data(), d_rgb.data(), rgb_row_strides, layout, nullptr, n_frames, (uintptr_t)c->d_in,
+                                       (uintptr_t)c->d_out, false, plan)))
+        return r;
+    for (int f = 0; f < n_frames; f++)
+        if (yspan[(size_t)f])
+            HIPCHK(c, hipMemcpyAsync((uint8_t *)c->d_in + d_yuv[(size_t)f], yuv + yuv_offsets[f], yspan[(size_t)f], hipMemcpyHostToDevice, c->stream));
+    if ((r = mixed_rgb_launch_plan(c, plan, layout, (const uint8_t *)c->d_in, (uint8_t *)c->d_out, false))) {
+        (void)hipStreamSynchronize(c->stream);
+        return r;
+    }
+    HIPCHK(c, download_images(plan, layout, (const uint8_t *)c->d_out, rgb, rgb_offsets, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+}
+
+// behind hvc_decode_frames_mixed_rgb (hvc_capi.hip): hvc_decode_frames_mixed into c->d_aux (tight records on 64 bytes), the
+// colour pass from there; host memory: the images are staged in c->d_aux2
+int decode_frames_mixed_rgb_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
+                                 uint8_t *rgb, const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where) {
+    bool nothing = false;
+    int r = mixed_rgb_args(c, infos, coef_offsets, rgb_offsets, n_frames, layout, where, nothing);
+    if (r || nothing) return r;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    std::vector<size_t> d_coef, d_pix, rspan, d_rgb;
+    size_t ptot = 0;
+    if ((r = stage_coefs(c, nullptr, coef_offsets, infos, n_frames, d_coef, d_pix, ptot))) return r;
+    if ((r = rgb_spans(infos, rgb_row_strides, n_frames, layout, rspan))) return r;
+    const bool host = where == HVC_MEM_HOST;
+    const size_t rtot = host ? stage_offsets(rgb_offsets, rspan, d_rgb) : 0;
+    hvc::MixedPlan bplan; // both plans before anything is enqueued: a set that is refused leaves nothing behind
+    hvc::MixedRgbPlan cplan;
+    if ((r = hvc::mixed_plan_build(infos, host ? d_coef.data() : coef_offsets, d_pix.data(), nullptr, n_frames, bplan))) return r;
+    if ((r = grow(c, &c->d_aux, &c->aux_cap, ptot))) return r;
+    if (host && (r = grow(c, &c->d_aux2, &c->aux2_cap, rtot))) return r;
+    uint8_t *out = host ? (uint8_t *)c->d_aux2 : rgb;
+    if ((r = hvc::mixed_rgb_plan_build(infos, d_pix.data(), host ? d_rgb.data() : rgb_offsets, rgb_row_strides, layout, nullptr, n_frames,
+                                       (uintptr_t)c->d_aux, (uintptr_t)out, true, cplan)))
+        return r;
+    if (bplan.map.empty()) return HVC_OK; // (no block: no pixel)
+    if (!coefs || (!cplan.map.empty() && !rgb)) return HVC_E_INVALID_ARG;
+    if (host && (r = stage_coefs(c, coefs, coef_offsets, infos, n_frames, d_coef, d_pix, ptot))) return r;
+    wide_total_begin(c);
+    r = mixed_launch_plan(c, bplan, host ? (const int16_t *)c->d_in : coefs, (uint8_t *)c->d_aux, !host && c->profiling);
+    if (!r) r = mixed_rgb_launch_plan(c, cplan, layout, (const uint8_t *)c->d_aux, out, false);
+    if (r) {
+        (void)hipStreamSynchronize(c->stream);
+        return r;
+    }
+    if (host) {
+        HIPCHK(c, download_images(cplan, layout, out, rgb, rgb_offsets, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return HVC_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Files -> pixels: host Huffman reader || upload (copy stream) || k_decode_mixed of the previous chunk (compute stream), as
 // decode_batch_impl (hvc_capi_jpeg.hip) -- with chunks cut by the bytes of their coefficient records, a plan per chunk, and a
 // status per file: a file that fails keeps its slot in the chunk's ring buffer and is left out of the chunk's plan.
-// (behind hvc_jpeg_decode_batch_mixed, hvc_capi_jpeg.hip)
+// form.rgb(): a file's record in `pixels` is its RGB image; the chunk's planes go to a device slot of their own ring and
+// k_ycc_to_rgb_mixed follows k_decode_mixed on the compute stream.
+// (behind hvc_jpeg_decode_batch_mixed and hvc_jpeg_decode_batch_mixed_rgb, hvc_capi_jpeg.hip)
 int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads,
                             size_t chunk_bytes, const hvc_jpeg_info *infos, int *status, const size_t *pixel_offsets,
-                            uint8_t *pixels, size_t pixel_cap, int where, hvc_batch_stats *stats) {
+                            uint8_t *pixels, size_t pixel_cap, int where, hvc_batch_stats *stats, const MixedForm &form) {
     if (!c || !jpegs || !sizes || !infos || !status || !pixel_offsets || n_files < 0) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG;
@@ -200,19 +393,36 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
         int first = 0, count = 0;    // positions in `take`
         size_t coef_bytes = 0;
         size_t pix_lo = 0, pix_hi = 0; // the bytes of `pixels` its files cover
+        size_t plane_bytes = 0;        // (RGB form) its files' padded planes, each on 64 bytes
     };
     std::vector<int> take;
     std::vector<Chunk> chunks;
     std::vector<size_t> coef_rel((size_t)n_files, 0), pix_rel((size_t)n_files, 0);
+    std::vector<size_t> out_bytes((size_t)n_files, 0); // a file's record in `pixels`: its planes, or the span of its image
+    std::vector<size_t> plane_rel(form.rgb() ? (size_t)n_files : 0, 0);
     std::vector<int> chunk_of((size_t)n_files, -1);
     bool need_pixels = false;
     for (int f = 0; f < n_files; f++) {
         if (status[f] != HVC_OK) continue;
         const hvc_jpeg_info &fi = infos[f];
         if (!jpegs[f] || fi.n_comp < 0 || fi.n_comp > 4) return HVC_E_INVALID_ARG;
-        if (fi.pixel_bytes) {
-            if (pixel_offsets[f] & 7) return HVC_E_ALIGNMENT;
-            if (pixel_offsets[f] > pixel_cap || fi.pixel_bytes > pixel_cap - pixel_offsets[f]) return HVC_E_INVALID_ARG;
+        size_t &ob = out_bytes[(size_t)f];
+        if (form.rgb()) {
+            if (!rgb_sampling_of(fi)) { // as hvc_jpeg_decode_rgb answers it: the file's own result
+                status[f] = HVC_E_INVALID_ARG;
+                continue;
+            }
+            if (fi.width < 0 || fi.height < 0) return HVC_E_INVALID_ARG;
+            const size_t tight = hvc::mixed_rgb_row_bytes(form.layout, fi.width);
+            const size_t rs = form.rgb_row_strides && form.rgb_row_strides[f] ? form.rgb_row_strides[f] : tight;
+            if (rs < tight) return HVC_E_INVALID_ARG;
+            ob = hvc::mixed_rgb_span(form.layout, fi.width, fi.height, rs);
+        } else {
+            ob = fi.pixel_bytes;
+            if (ob && (pixel_offsets[f] & 7)) return HVC_E_ALIGNMENT;
+        }
+        if (ob) {
+            if (pixel_offsets[f] > pixel_cap || ob > pixel_cap - pixel_offsets[f]) return HVC_E_INVALID_ARG;
             need_pixels = true;
         }
         const size_t cb = fi.coef_count * sizeof(int16_t);
@@ -223,10 +433,14 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
         Chunk &k = chunks.back();
         coef_rel[(size_t)f] = k.coef_bytes / sizeof(int16_t);
         chunk_of[(size_t)f] = (int)chunks.size() - 1;
-        if (fi.pixel_bytes) {
-            if (k.pix_hi == 0) k.pix_lo = pixel_offsets[f];
-            k.pix_lo = std::min(k.pix_lo, pixel_offsets[f]);
-            k.pix_hi = std::max(k.pix_hi, pixel_offsets[f] + fi.pixel_bytes);
+        if (ob) {
+            if (k.pix_hi == 0) k.pix_lo = pixel_offsets[f] & ~(size_t)7; // (an image may start anywhere: the slot keeps its offset modulo 8)
+            k.pix_lo = std::min(k.pix_lo, pixel_offsets[f] & ~(size_t)7);
+            k.pix_hi = std::max(k.pix_hi, pixel_offsets[f] + ob);
+        }
+        if (form.rgb()) {
+            plane_rel[(size_t)f] = k.plane_bytes;
+            k.plane_bytes += (fi.pixel_bytes + 63) & ~(size_t)63;
         }
         k.coef_bytes += cb;
         k.count++;
@@ -235,16 +449,17 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     if (need_pixels && !pixels) return HVC_E_INVALID_ARG;
     if (take.empty()) return HVC_OK;
     const int n_chunks = (int)chunks.size(), n_take = (int)take.size();
-    size_t ring_bytes = 0, oring_bytes = 0;
+    size_t ring_bytes = 0, oring_bytes = 0, pring_bytes = 0;
     int largest = 0;
     uint64_t coef_total = 0;
     for (const Chunk &k : chunks) {
         ring_bytes = std::max(ring_bytes, k.coef_bytes);
         if (where == HVC_MEM_HOST) oring_bytes = std::max(oring_bytes, k.pix_hi - k.pix_lo);
+        pring_bytes = std::max(pring_bytes, k.plane_bytes);
         largest = std::max(largest, k.count);
     }
     if (where == HVC_MEM_HOST)
-        for (int f : take) pix_rel[(size_t)f] = infos[f].pixel_bytes ? pixel_offsets[f] - chunks[(size_t)chunk_of[(size_t)f]].pix_lo : 0;
+        for (int f : take) pix_rel[(size_t)f] = out_bytes[(size_t)f] ? pixel_offsets[f] - chunks[(size_t)chunk_of[(size_t)f]].pix_lo : 0;
 
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
@@ -279,6 +494,17 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
         for (int i = 0; i < NB; i++)
             if (hipMalloc(&c->d_oring[i], oring_bytes) != hipSuccess) return HVC_E_OUT_OF_MEMORY;
         c->oring_bytes = oring_bytes;
+    }
+    if (pring_bytes > c->pring_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int i = 0; i < NB; i++) {
+            if (c->d_pring[i]) (void)hipFree(c->d_pring[i]);
+            c->d_pring[i] = nullptr;
+        }
+        c->pring_bytes = 0;
+        for (int i = 0; i < NB; i++)
+            if (hipMalloc(&c->d_pring[i], pring_bytes) != hipSuccess) return HVC_E_OUT_OF_MEMORY;
+        c->pring_bytes = pring_bytes;
     }
 
     std::mutex mu;
@@ -371,7 +597,17 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
             if (he != hipSuccess) { rc = fail_hip(c, he); break; }
             uint8_t *dst = where == HVC_MEM_DEVICE ? pixels : (uint8_t *)c->d_oring[slot];
             const size_t *dst_off = where == HVC_MEM_DEVICE ? pixel_offsets : pix_rel.data();
-            rc = mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), infos, ok.data(), (int)ok.size(), dst, dst_off, c->profiling);
+            if (!form.rgb()) {
+                rc = mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), infos, ok.data(), (int)ok.size(), dst, dst_off, c->profiling);
+            } else { // the planes into the slot of their own ring, the colour pass from there to where the planes would have gone
+                uint8_t *planes = (uint8_t *)c->d_pring[slot];
+                hvc::MixedRgbPlan cplan;
+                rc = hvc::mixed_rgb_plan_build(infos, plane_rel.data(), dst_off, form.rgb_row_strides, form.layout, ok.data(), (int)ok.size(),
+                                               (uintptr_t)planes, (uintptr_t)dst, true, cplan);
+                if (!rc) rc = mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), infos, ok.data(), (int)ok.size(), planes,
+                                           plane_rel.data(), c->profiling);
+                if (!rc) rc = mixed_rgb_launch_plan(c, cplan, form.layout, planes, dst, false);
+            }
             if (rc) break;
             he = hipEventRecord(c->ev_t[2], compute);
             if (he == hipSuccess && where == HVC_MEM_HOST) {
@@ -386,8 +622,16 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
                 int prev_t = -2;
                 for (int t = ch.first; t < ch.first + ch.count; t++) {
                     const int f = take[(size_t)t];
-                    if (status[f] != HVC_OK || !infos[f].pixel_bytes) continue;
-                    const size_t lo = pix_rel[(size_t)f], hi = lo + infos[f].pixel_bytes;
+                    if (status[f] != HVC_OK || !out_bytes[(size_t)f]) continue;
+                    const size_t lo = pix_rel[(size_t)f], hi = lo + out_bytes[(size_t)f];
+                    if (form.rgb() && form.rgb_row_strides && form.rgb_row_strides[f] > hvc::mixed_rgb_row_bytes(form.layout, infos[f].width)) {
+                        flush(); // rows with room between them: the image row by row, the caller's bytes between rows stay
+                        if (he == hipSuccess)
+                            he = hipMemcpy2DAsync(pixels + ch.pix_lo + lo, form.rgb_row_strides[f], dst + lo, form.rgb_row_strides[f],
+                                                  hvc::mixed_rgb_row_bytes(form.layout, infos[f].width),
+                                                  hvc::mixed_rgb_rows(form.layout, infos[f].height), hipMemcpyDeviceToHost, compute);
+                        continue;
+                    }
                     const bool joins = run_hi > run_lo && t == prev_t + 1 && lo >= run_hi && lo - run_hi < 4096;
                     if (!joins) flush();
                     if (run_hi == run_lo) run_lo = lo;

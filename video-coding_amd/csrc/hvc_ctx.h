@@ -7,7 +7,8 @@
 //   hvc_capi_reader.hip  the GPU Huffman reader's entry point and the batch pipeline built on it
 //   hvc_capi_files.hip   the GPU Huffman coder's entry point and the batch pipelines that write files
 //   hvc_rgb.hip          the RGB colour pass (kernels and launches; its entry points live with their families in the files above)
-//   hvc_capi_mixed.hip   batches of frames / files of different geometry and tables (hvc_decode_frames_mixed, hvc_jpeg_decode_batch_mixed)
+//   hvc_capi_mixed.hip   batches of frames / files of different geometry and tables (hvc_decode_frames_mixed, hvc_jpeg_decode_batch_mixed,
+//                        and their RGB forms: hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed_rgb)
 //   hvc_capi_async.hip   pinned host memory and the slots of the asynchronous seam (hvc_decode_frames_submit / hvc_wait)
 #ifndef HVC_CTX_H
 #define HVC_CTX_H
@@ -116,6 +117,14 @@ struct hvc_ctx {
     void *d_mixed = nullptr, *h_mixed = nullptr;
     size_t mixed_cap = 0, h_mixed_cap = 0, mixed_len = 0; // mixed_len: bytes of the image d_mixed holds, 0 = none
     hipEvent_t ev_mixed = nullptr;
+    // ... and the same three for the colour pass over a mixed batch (k_ycc_to_rgb_mixed): a buffer of its own, so that the
+    // colour plan of a chunk never overwrites the block-stage plan of that chunk
+    void *d_mixed_rgb = nullptr, *h_mixed_rgb = nullptr;
+    size_t mixed_rgb_cap = 0, h_mixed_rgb_cap = 0, mixed_rgb_len = 0;
+    hipEvent_t ev_mixed_rgb = nullptr;
+    // hvc_jpeg_decode_batch_mixed_rgb: the ring of device slots the chunks' decoded planes live in (they never leave the GPU)
+    void *d_pring[RING] = {};
+    size_t pring_bytes = 0;
     // hvc_set_host_cpus: the CPUs the batch pipelines' host threads may run on (empty = no restriction)
     bool have_cpus = false;
     cpu_set_t cpus;
@@ -449,9 +458,22 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
 // and hvc_jpeg_decode_batch_mixed in hvc_capi_jpeg.hip)
 int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
                              uint8_t *pixels, const size_t *pixel_offsets, int where);
+// What the files of a mixed batch become.  Default: their padded planes, at pixel_offsets.  rgb_offsets set: RGB images
+// there (`pixels` / `pixel_cap` are the RGB buffer), rows rgb_row_strides[f] apart (nullptr: tight), through k_ycc_to_rgb_mixed
+// behind every chunk's block stage; the planes stay in a device ring.
+struct MixedForm {
+    const size_t *rgb_offsets = nullptr, *rgb_row_strides = nullptr;
+    int layout = 0;
+    bool rgb() const { return rgb_offsets != nullptr; }
+};
 int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads, size_t chunk_bytes,
                             const hvc_jpeg_info *infos, int *status, const size_t *pixel_offsets, uint8_t *pixels, size_t pixel_cap,
-                            int where, hvc_batch_stats *stats);
+                            int where, hvc_batch_stats *stats, const MixedForm &form = MixedForm());
+// the colour pass alone / behind the block stage (behind hvc_yuv_to_rgb_mixed in hvc_yuv.hip, hvc_decode_frames_mixed_rgb in hvc_capi.hip)
+int yuv_to_rgb_mixed_impl(hvc_ctx *c, const uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos, int n_frames, uint8_t *rgb,
+                          const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where);
+int decode_frames_mixed_rgb_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
+                                 uint8_t *rgb, const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where);
 
 // hvc_rgb.hip: the colour pass (k_ycc_to_rgb / k_rgb_to_ycc) on device memory, for the entry points that end or begin with it
 struct RgbImage { // an RGB image as the caller laid it out (hvc_rgb_layout; strides of 0 resolved to tight)

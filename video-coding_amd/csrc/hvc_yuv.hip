@@ -629,6 +629,12 @@ int hvc_yuv_to_rgb(hvc_ctx *c, const uint8_t *yuv, size_t yuv_fs, const hvc_comp
     return HVC_OK;
 } HVC_ABI_CATCH
 
+// the same over images of different size and sampling in one launch (k_ycc_to_rgb_mixed): hvc_capi_mixed.hip
+int hvc_yuv_to_rgb_mixed(hvc_ctx *c, const uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos, int n_frames, uint8_t *rgb,
+                         const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where) try {
+    return yuv_to_rgb_mixed_impl(c, yuv, yuv_offsets, infos, n_frames, rgb, rgb_offsets, rgb_row_strides, layout, where);
+} HVC_ABI_CATCH
+
 int hvc_rgb_to_yuv(hvc_ctx *c, const uint8_t *rgb, size_t rgb_row_stride, size_t rgb_frame_stride, int layout, int width, int height,
                    int sampling, int n_frames, uint8_t *yuv, size_t yuv_fs, const hvc_component *comps, int where) try {
     RgbImage im;

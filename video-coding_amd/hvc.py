@@ -39,6 +39,7 @@ SYMBOLS = [
     "hvc_jpeg_scaled_info", "hvc_decode_frames_scaled", "hvc_jpeg_decode_scaled", "hvc_jpeg_decode_scaled_rgb",
     "hvc_jpeg_decode_batch_scaled",
     "hvc_jpeg_mixed_layout", "hvc_decode_frames_mixed", "hvc_jpeg_decode_batch_mixed",
+    "hvc_jpeg_mixed_rgb_layout", "hvc_yuv_to_rgb_mixed", "hvc_decode_frames_mixed_rgb", "hvc_jpeg_decode_batch_mixed_rgb",
 ]
 HVC_RGB = {"interleaved": 0, "planar": 1}  # enum hvc_rgb_layout: [H, W, 3] / [3, H, W]
 HVC_YUV_400 = 400   # luma only, beside 420 / 422 / 444
@@ -262,6 +263,12 @@ def lib():
         L.hvc_decode_frames_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), i]
         L.hvc_jpeg_decode_batch_mixed.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, ip, C.POINTER(i), C.POINTER(sz), vp, sz, i,
                                                   C.POINTER(BatchStats)]
+        L.hvc_jpeg_mixed_rgb_layout.argtypes = [C.POINTER(vp), C.POINTER(sz), i, i, sz, sz, ip, C.POINTER(i), C.POINTER(sz), C.POINTER(sz),
+                                                C.POINTER(sz)]
+        L.hvc_yuv_to_rgb_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), C.POINTER(sz), i, i]
+        L.hvc_decode_frames_mixed_rgb.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), C.POINTER(sz), i, i]
+        L.hvc_jpeg_decode_batch_mixed_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, ip, C.POINTER(i), C.POINTER(sz),
+                                                      C.POINTER(sz), vp, sz, i, i, C.POINTER(BatchStats)]
         L.hvc_checksum_records.argtypes = [vp, vp, sz, sz, i, vp, i]
         L.hvc_set_host_cpus.argtypes = [vp, C.c_char_p]
         L.hvc_get_host_cpus.argtypes = [vp, C.c_char_p, sz, C.POINTER(i)]
@@ -497,6 +504,53 @@ class MixedLayout:
 def jpeg_mixed_layout(jpegs, align=0):
     """headers of a list of files (bytes) -> MixedLayout; align: a power of two >= 8, 0 = 256"""
     return MixedLayout(jpegs, align)
+
+
+class MixedRgbLayout:
+    """what hvc_jpeg_mixed_rgb_layout makes of a list of files: infos, status (nonzero also for a sampling without an RGB
+    image), rgb_offsets and rgb_row_strides (ctypes arrays, one entry per file) and total_bytes -- the size of the buffer
+    that holds every good file's RGB image"""
+
+    def __init__(self, jpegs, layout="interleaved", align=0, row_align=0):
+        n = len(jpegs)
+        self.jpegs = list(jpegs)
+        self.layout = _rgb_layout(layout)
+        self.ptrs = (C.c_void_p * n)(*[C.cast(C.c_char_p(j), C.c_void_p) for j in self.jpegs])
+        self.sizes = (C.c_size_t * n)(*[len(j) for j in self.jpegs])
+        self.infos = (JpegInfo * n)()
+        self.status = (C.c_int * n)()
+        self.rgb_offsets = (C.c_size_t * n)()
+        self.rgb_row_strides = (C.c_size_t * n)()
+        total = C.c_size_t(0)
+        _chk(lib().hvc_jpeg_mixed_rgb_layout(self.ptrs, self.sizes, n, self.layout, align, row_align, self.infos, self.status,
+                                             self.rgb_offsets, self.rgb_row_strides, C.byref(total)), "hvc_jpeg_mixed_rgb_layout")
+        self.total_bytes = total.value
+
+    def __len__(self):
+        return len(self.jpegs)
+
+
+def jpeg_mixed_rgb_layout(jpegs, layout="interleaved", align=0, row_align=0):
+    """headers of a list of files (bytes) -> MixedRgbLayout; align / row_align: powers of two, 0 = 256 / 1 (tight rows)"""
+    return MixedRgbLayout(jpegs, layout, align, row_align)
+
+
+def rgb_view(buf, offset, row_stride, width, height, layout):
+    """the [H, W, 3] / [3, H, W] view of one image of a mixed RGB buffer (numpy array or torch tensor of bytes)"""
+    row_stride = int(row_stride) or (width if _rgb_layout(layout) == 1 else 3 * width)
+    if _rgb_layout(layout) == 1:
+        shape, strides = (3, height, width), (row_stride * height, row_stride, 1)
+    else:
+        shape, strides = (height, width, 3), (row_stride, 3, 1)
+    if hasattr(buf, "as_strided"):   # torch
+        return buf.as_strided(shape, strides, int(offset))
+    return np.lib.stride_tricks.as_strided(buf[int(offset):], shape, strides)
+
+
+def _size_array(v, n):
+    if v is None or isinstance(v, C.Array):
+        return v
+    return (C.c_size_t * n)(*[int(x) for x in v])
 
 
 def jpeg_scaled_info(info, scale_denom):
@@ -1023,6 +1077,62 @@ class Context:
                 continue
             info, off = lay.infos[f], lay.pixel_offsets[f]
             out.append((status[f], info, info.planes(pixels[off:off + info.pixel_bytes])))
+        return out
+
+    def yuv_to_rgb_mixed(self, yuv, yuv_offsets, infos, rgb, rgb_offsets, rgb_row_strides=None, layout="interleaved"):
+        """hvc_yuv_to_rgb_mixed: the colour pass over images of any size and sampling in one launch.  Frame f = infos[f]
+        (JpegInfo: width, height, sampling factors, layout), its planes at yuv[yuv_offsets[f]:], its image at
+        rgb[rgb_offsets[f]:] with rows rgb_row_strides[f] apart (None: tight).  yuv / rgb: numpy (host) or torch cuda
+        tensors of bytes, both in the same memory space."""
+        ya, w1 = _addr(yuv)
+        ra, w2 = _addr(rgb)
+        assert w1 == w2, "yuv and rgb must live in the same memory space"
+        n = len(infos)
+        arr = infos if isinstance(infos, C.Array) else (JpegInfo * n)(*infos)
+        _chk(lib().hvc_yuv_to_rgb_mixed(self._h, ya, _size_array(yuv_offsets, n), arr, n, ra, _size_array(rgb_offsets, n),
+                                        _size_array(rgb_row_strides, n), _rgb_layout(layout), w1), "hvc_yuv_to_rgb_mixed")
+
+    def decode_frames_mixed_rgb(self, coefs, coef_offsets, infos, rgb, rgb_offsets, rgb_row_strides=None, layout="interleaved"):
+        """hvc_decode_frames_mixed_rgb: hvc_decode_frames_mixed into context scratch, then the mixed colour pass; arguments as
+        decode_frames_mixed and yuv_to_rgb_mixed."""
+        ca, w1 = _addr(coefs)
+        ra, w2 = _addr(rgb)
+        assert w1 == w2, "coefs and rgb must live in the same memory space"
+        n = len(infos)
+        arr = infos if isinstance(infos, C.Array) else (JpegInfo * n)(*infos)
+        _chk(lib().hvc_decode_frames_mixed_rgb(self._h, ca, _size_array(coef_offsets, n), arr, n, ra, _size_array(rgb_offsets, n),
+                                               _size_array(rgb_row_strides, n), _rgb_layout(layout), w1), "hvc_decode_frames_mixed_rgb")
+
+    def jpeg_decode_batch_mixed_rgb(self, jpegs, threads=8, chunk_bytes=0, device=False, layout="interleaved", row_align=0,
+                                    rgb_layout=None, rgb=None):
+        """Files of any sizes, samplings and tables to RGB images in one call.  Returns one (status, info, image) per file:
+        status = the file's own hvc_status (0 = decoded), image = a [H, W, 3] (interleaved) or [3, H, W] (planar) view into ONE
+        buffer (numpy, or a torch cuda tensor with device=True), None for a file that failed.  rgb_layout / rgb: a
+        MixedRgbLayout made before and a buffer of rgb_layout.total_bytes to decode into (default: made here, zero-filled).
+        The call's hvc_batch_stats: self.last_batch_stats."""
+        lay = rgb_layout if rgb_layout is not None else MixedRgbLayout(jpegs, layout, 0, row_align)
+        n = len(lay)
+        if rgb is None:
+            if device:
+                import torch
+                rgb = torch.zeros(max(lay.total_bytes, 8), dtype=torch.uint8, device="cuda")
+            else:
+                rgb = np.zeros(max(lay.total_bytes, 8), dtype=np.uint8)
+        ra, where = _addr(rgb)
+        cap = rgb.numel() if hasattr(rgb, "numel") else rgb.size
+        st = BatchStats()
+        status = (C.c_int * n)(*lay.status)
+        _chk(lib().hvc_jpeg_decode_batch_mixed_rgb(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, lay.infos, status,
+                                                   lay.rgb_offsets, lay.rgb_row_strides, ra, cap, lay.layout, where, C.byref(st)),
+             "hvc_jpeg_decode_batch_mixed_rgb")
+        self.last_batch_stats = st
+        out = []
+        for f in range(n):
+            info = lay.infos[f] if lay.status[f] == 0 else None
+            image = None
+            if status[f] == 0 and info is not None and info.width > 0 and info.height > 0:
+                image = rgb_view(rgb, lay.rgb_offsets[f], lay.rgb_row_strides[f], info.width, info.height, lay.layout)
+            out.append((status[f], info, image))
         return out
 
     def decode_frames_yuv444(self, coefs, coef_frame_stride, qtabs, comps, n_frames, width, height, frames,
