@@ -9,8 +9,10 @@ import time
 import numpy as np
 import pytest
 
+from conftest import golden_bytes
 from helpers import synth_pixels
 from oracle import orc
+from test_host_entropy import UNUSUAL_SAMPLINGS, unusual_sampling_file
 
 pytestmark = pytest.mark.gpu
 
@@ -253,3 +255,135 @@ def test_every_context_entry_point_refuses_null_buffers():
     for name in ("hvc_decode_frames", "hvc_encode_frames", "hvc_jpeg_decode", "hvc_jpeg_decode_batch", "hvc_jpeg_decode_batch_gpu",
                  "hvc_jpeg_encode_batch", "hvc_huffman_encode_frames", "hvc_checksum_records"):  # (a copy of zero bytes is one)
         assert int(seen[name]) < 0, (name, seen[name])
+
+
+# ---------------------------------------------------------------------------
+# the pipelines' shared parts (csrc/hvc_feed.h, hvc_batch.h, the ring helper of hvc_ctx.h) through every pipeline of one context
+
+def _uniform_files(n, seed):
+    """n files of one geometry (64 x 64, 4:2:0) and one set of tables, with their raw frames"""
+    frames = _frames(n, 64, 64, seed)
+    return [orc.encode_yuv(y, u, v, 64, 64, 420, 75) for y, u, v in frames], frames
+
+
+def _mixed_files():
+    """Mouse480 first (its record alone is a chunk), mini.jpg, unusual samplings at 40 x 24 and 97 x 51"""
+    files = [golden_bytes("Mouse480.jpg"), golden_bytes("mini.jpg")]
+    files += [unusual_sampling_file(UNUSUAL_SAMPLINGS[si], 40, 24, 100 * si + 40)[0] for si in (0, 3, 9)]
+    files += [unusual_sampling_file(UNUSUAL_SAMPLINGS[si], 97, 51, 100 * si + 97)[0] for si in (1, 8)]
+    return files
+
+
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else a
+
+
+def _decode_uniform(c, jpegs, fs, device, **kw):
+    if device:
+        import torch
+        out = torch.zeros(len(jpegs) * fs, dtype=torch.uint8, device="cuda")
+    else:
+        out = np.zeros(len(jpegs) * fs, np.uint8)
+    st = c.jpeg_decode_batch(jpegs, out, fs, **kw)
+    return _host(out).reshape(len(jpegs), fs), st
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_one_context_runs_every_pipeline_while_its_rings_regrow(device):
+    """uniform batch (4 chunks over 3 slots, the last ragged), the same in one chunk (the coefficient ring grows), a mixed
+    batch whose first file alone exceeds chunk_bytes (the ring grows inside the mixed path), its RGB form (the plane ring
+    appears), the GPU-reader batch, both encode pipelines, the first call again: byte for byte what the single-file entry
+    points give"""
+    import video_coding_amd as hvc
+    jpegs, frames = _uniform_files(7, 21000)
+    mixed = _mixed_files()
+    ref = hvc.Context(0)
+    try:
+        want = np.stack([ref.jpeg_decode(j)[1] for j in jpegs])
+        want_mixed = [ref.jpeg_decode(f) for f in mixed]
+        want_rgb = [ref.jpeg_decode_rgb(f)[1] for f in mixed[:2]]
+        want_files = [ref.jpeg_encode(y, u, v, 64, 64, 420, 75) for y, u, v in frames[:5]]
+    finally:
+        ref.close()
+    assert want_files == jpegs[:5]
+    raw = [np.concatenate([p.reshape(-1) for p in f]) for f in frames[:5]]
+    fs = want.shape[1]
+    mouse_record = 2 * hvc.hvc.jpeg_read_header(mixed[0]).coef_count
+    assert mouse_record > 7 * 2 * hvc.hvc.jpeg_read_header(jpegs[0]).coef_count   # larger than the ring the uniform calls leave
+    c = hvc.Context(0)
+    try:
+        got, st = _decode_uniform(c, jpegs, fs, device, threads=3, frames_per_chunk=2)
+        assert st.chunks == 4 and np.array_equal(got, want)
+        got, st = _decode_uniform(c, jpegs, fs, device, threads=3, frames_per_chunk=7)
+        assert st.chunks == 1 and np.array_equal(got, want)
+        results = c.jpeg_decode_batch_mixed(mixed, threads=3, chunk_bytes=mouse_record - 2, device=device)
+        assert c.last_batch_stats.chunks >= 2
+        for (status, info, planes), (winfo, wpx) in zip(results, want_mixed):
+            assert status == 0
+            for a, b in zip(planes, winfo.planes(wpx)):
+                assert np.array_equal(_host(a), b)
+        results = c.jpeg_decode_batch_mixed_rgb(mixed, threads=3, chunk_bytes=mouse_record - 2, device=device)
+        for f, wimg in enumerate(want_rgb):
+            assert results[f][0] == 0 and np.array_equal(_host(results[f][2]), wimg), f
+        got, st = _decode_uniform(c, jpegs, fs, device, threads=3, frames_per_chunk=2, gpu_entropy=True)
+        assert st.chunks == 4 and np.array_equal(got, want)
+        for gpu in (False, True):
+            files, st = c.jpeg_encode_batch(raw, 64, 64, 420, 75, threads=3, frames_per_chunk=2, gpu_entropy=gpu)
+            assert files == want_files and st.chunks == 3, gpu
+        got, st = _decode_uniform(c, jpegs, fs, device, threads=3, frames_per_chunk=2)
+        assert st.chunks == 4 and np.array_equal(got, want)
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("threads", [1, 4])
+@pytest.mark.parametrize("bad_at", [6, 1], ids=["chunk3", "chunk0"])
+def test_an_error_late_in_a_uniform_batch(threads, bad_at):
+    """8 files in chunks of 2, one cut inside its headers (chunk 3: a slot that has come round, or chunk 0): the call returns
+    that file's code, and the next call on the same context is byte-exact"""
+    import video_coding_amd as hvc
+    jpegs, _ = _uniform_files(8, 23000)
+    bad = list(jpegs)
+    bad[bad_at] = jpegs[bad_at][:100]
+    with pytest.raises(hvc.HvcError) as e:
+        hvc.hvc.jpeg_read_header(bad[bad_at])
+    code = e.value.code
+    assert code < 0
+    c = hvc.Context(0)
+    try:
+        want = np.stack([c.jpeg_decode(j)[1] for j in jpegs])
+        fs = want.shape[1]
+        with pytest.raises(hvc.HvcError) as e:
+            _decode_uniform(c, bad, fs, False, threads=threads, frames_per_chunk=2)
+        assert e.value.code == code
+        got, st = _decode_uniform(c, jpegs, fs, False, threads=threads, frames_per_chunk=2)
+        assert st.chunks == 4 and np.array_equal(got, want)
+    finally:
+        c.close()
+
+
+def test_batch_stats_are_still_filled():
+    import video_coding_amd as hvc
+    jpegs, _ = _uniform_files(7, 25000)
+    mini, mouse = golden_bytes("mini.jpg"), golden_bytes("Mouse480.jpg")
+    info = hvc.hvc.jpeg_read_header(mouse)
+    # cut in its scan and followed by one-bits, which no Huffman table has a code for: the host reader fails inside the scan
+    cut = mouse[:info.ecs_offset + 2000] + b"\xff\x00" * 64 + b"\xff\xd9"
+    small = unusual_sampling_file(UNUSUAL_SAMPLINGS[3], 40, 24, 340)[0]
+    files = [mini, cut, mini, small, small]
+    coef = [2 * hvc.hvc.jpeg_read_header(f).coef_count for f in files]
+    chunk = coef[0]                                       # chunks: [mini] [cut: alone, no good file] [mini] [small small]
+    assert coef[1] > chunk and coef[3] + coef[4] <= chunk < coef[2] + coef[3]
+    c = hvc.Context(0)
+    try:
+        fs = hvc.hvc.jpeg_read_header(jpegs[0]).pixel_bytes
+        _, st = _decode_uniform(c, jpegs, fs, False, threads=3, frames_per_chunk=2)
+        assert (st.chunks, st.threads, st.frames_per_chunk) == (4, 3, 2)
+        assert st.coef_bytes == 7 * 2 * hvc.hvc.jpeg_read_header(jpegs[0]).coef_count and st.wall_ms > 0
+        results = c.jpeg_decode_batch_mixed(files, threads=2, chunk_bytes=chunk)
+        assert [r[0] == 0 for r in results] == [True, False, True, True, True]
+        st = c.last_batch_stats
+        assert (st.chunks, st.threads, st.frames_per_chunk) == (4, 2, 2)
+        assert st.coef_bytes == sum(coef) - coef[1] and st.wall_ms > 0   # the chunk without a good file was not uploaded
+    finally:
+        c.close()

@@ -41,6 +41,38 @@ bool parse_cpulist(const char *s, cpu_set_t &set) {
     return n > 0;
 }
 
+void ring_free(const RingSet &s) {
+    for (int j = 0; j < s.n; j++) {
+        const RingMember &m = s.m[j];
+        for (void *&p : *m.ring) {
+            if (p) (void)(m.pinned ? hipHostFree(p) : hipFree(p));
+            p = nullptr;
+        }
+        *m.recorded = 0;
+    }
+}
+
+int ring_ensure(hvc_ctx *c, const RingSet &s, std::initializer_list<size_t> want) {
+    bool more = false;
+    int j = 0;
+    for (size_t w : want) more |= w > *s.m[j++].recorded;
+    if (!more) return HVC_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (s.drain_copy) HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+    ring_free(s); // (the recorded sizes stay zero until every member is there: a half-allocated set is freed by the next call)
+    for (int i = 0; i < hvc_ctx::RING; i++) {
+        j = 0;
+        for (size_t w : want) {
+            const RingMember &m = s.m[j++];
+            void **p = &(*m.ring)[i];
+            if ((m.pinned ? hipHostMalloc(p, w, m.flags) : hipMalloc(p, w + m.slack)) != hipSuccess) return HVC_E_OUT_OF_MEMORY;
+        }
+    }
+    j = 0;
+    for (size_t w : want) *s.m[j++].recorded = w;
+    return HVC_OK;
+}
+
 int grow(hvc_ctx *c, void **p, size_t *cap, size_t need) {
     if (need <= *cap) return HVC_OK;
     if (*p) {
@@ -239,32 +271,16 @@ void hvc_destroy(hvc_ctx *c) {
         if (c->k0[i]) (void)hipEventDestroy(c->k0[i]);
         if (c->k1[i]) (void)hipEventDestroy(c->k1[i]);
     }
+    for (const RingSet &s : {coef_rings(c), out_rings(c), plane_rings(c), reader_rings(c), enc_rings(c), enc_seg_rings(c), enc_spec_rings(c)})
+        ring_free(s);
     for (int i = 0; i < hvc_ctx::RING; i++) {
-        if (c->h_ring[i]) (void)hipHostFree(c->h_ring[i]);
-        if (c->d_ring[i]) (void)hipFree(c->d_ring[i]);
-        if (c->d_oring[i]) (void)hipFree(c->d_oring[i]);
-        if (c->d_pring[i]) (void)hipFree(c->d_pring[i]);
         if (c->ev_h2d[i]) (void)hipEventDestroy(c->ev_h2d[i]);
         if (c->ev_kern[i]) (void)hipEventDestroy(c->ev_kern[i]);
-        if (c->eh_in[i]) (void)hipHostFree(c->eh_in[i]);
-        if (c->eh_out[i]) (void)hipHostFree(c->eh_out[i]);
-        if (c->ed_in[i]) (void)hipFree(c->ed_in[i]);
-        if (c->ed_out[i]) (void)hipFree(c->ed_out[i]);
         if (c->ev_up[i]) (void)hipEventDestroy(c->ev_up[i]);
         if (c->ev_down[i]) (void)hipEventDestroy(c->ev_down[i]);
         for (int k = 0; k < 3; k++)
             if (c->ev_et[i][k]) (void)hipEventDestroy(c->ev_et[i][k]);
         if (c->ev_gpu[i]) (void)hipEventDestroy(c->ev_gpu[i]);
-        if (c->gp_h_ecs[i]) (void)hipHostFree(c->gp_h_ecs[i]);
-        if (c->gp_d_ecs[i]) (void)hipFree(c->gp_d_ecs[i]);
-        if (c->gp_h_meta[i]) (void)hipHostFree(c->gp_h_meta[i]);
-        if (c->gp_d_meta[i]) (void)hipFree(c->gp_d_meta[i]);
-        if (c->gp_h_ftabs[i]) (void)hipHostFree(c->gp_h_ftabs[i]);
-        if (c->gp_d_ftabs[i]) (void)hipFree(c->gp_d_ftabs[i]);
-        if (c->ed_seg[i]) (void)hipFree(c->ed_seg[i]);
-        if (c->ed_off[i]) (void)hipFree(c->ed_off[i]);
-        if (c->eh_off[i]) (void)hipHostFree(c->eh_off[i]);
-        if (c->eh_specs[i]) (void)hipHostFree(c->eh_specs[i]);
     }
     for (int i = 0; i < 4; i++)
         if (c->ev_t[i]) (void)hipEventDestroy(c->ev_t[i]);

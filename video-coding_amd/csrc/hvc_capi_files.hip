@@ -246,60 +246,16 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
     const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // each file its own tables (hvc_set_huffman_tables)
     const int ri = c->restart_interval;                    // DRI + RSTn every ri MCUs (hvc_set_restart_interval)
     if (gpu_entropy && opt) { // per slot: the chunk's specs, pinned
-        const size_t spec_bytes = (size_t)C * 4 * sizeof(hvc_huff_spec);
-        if (spec_bytes > c->e_specs_bytes) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (int i = 0; i < NB; i++) {
-                if (c->eh_specs[i]) (void)hipHostFree(c->eh_specs[i]);
-                c->eh_specs[i] = nullptr;
-            }
-            c->e_specs_bytes = 0;
-            for (int i = 0; i < NB; i++)
-                if (hipHostMalloc(&c->eh_specs[i], spec_bytes, hipHostMallocDefault) != hipSuccess) return HVC_E_OUT_OF_MEMORY;
-            c->e_specs_bytes = spec_bytes;
-        }
+        if ((r = ring_ensure(c, enc_spec_rings(c), {(size_t)C * 4 * sizeof(hvc_huff_spec)}))) return r;
     }
     if (gpu_entropy) {
         hvc::jpeg_header_bytes(&info, header_default, nullptr, ri);
         // per slot: packed segments on the device (capacity = the coefficient chunk: 2 bytes per sample, twice the raw
         // frames), and (C + 1) offsets + one status word, on the device and pinned
         const size_t off_bytes = ((size_t)C + 2) * sizeof(unsigned long long);
-        if (out_bytes > c->e_seg_bytes || off_bytes > c->e_off_bytes) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (int i = 0; i < NB; i++) {
-                if (c->ed_seg[i]) (void)hipFree(c->ed_seg[i]);
-                if (c->ed_off[i]) (void)hipFree(c->ed_off[i]);
-                if (c->eh_off[i]) (void)hipHostFree(c->eh_off[i]);
-                c->ed_seg[i] = c->ed_off[i] = c->eh_off[i] = nullptr;
-            }
-            c->e_seg_bytes = c->e_off_bytes = 0;
-            for (int i = 0; i < NB; i++)
-                if (hipMalloc(&c->ed_seg[i], out_bytes) != hipSuccess || hipMalloc(&c->ed_off[i], off_bytes) != hipSuccess ||
-                    hipHostMalloc(&c->eh_off[i], off_bytes, hipHostMallocDefault) != hipSuccess)
-                    return HVC_E_OUT_OF_MEMORY;
-            c->e_seg_bytes = out_bytes;
-            c->e_off_bytes = off_bytes;
-        }
+        if ((r = ring_ensure(c, enc_seg_rings(c), {out_bytes, off_bytes, off_bytes}))) return r;
     }
-    if (in_bytes > c->e_in_bytes || out_bytes > c->e_out_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-        for (int i = 0; i < NB; i++) {
-            if (c->eh_in[i]) (void)hipHostFree(c->eh_in[i]);
-            if (c->eh_out[i]) (void)hipHostFree(c->eh_out[i]);
-            if (c->ed_in[i]) (void)hipFree(c->ed_in[i]);
-            if (c->ed_out[i]) (void)hipFree(c->ed_out[i]);
-            c->eh_in[i] = c->eh_out[i] = c->ed_in[i] = c->ed_out[i] = nullptr;
-        }
-        c->e_in_bytes = c->e_out_bytes = 0;
-        for (int i = 0; i < NB; i++)
-            if (hipHostMalloc(&c->eh_in[i], in_bytes, HVC_UPLOAD_RING_FLAGS) != hipSuccess ||
-                hipHostMalloc(&c->eh_out[i], out_bytes, hipHostMallocDefault) != hipSuccess ||
-                hipMalloc(&c->ed_in[i], in_bytes) != hipSuccess || hipMalloc(&c->ed_out[i], out_bytes) != hipSuccess)
-                return HVC_E_OUT_OF_MEMORY;
-        c->e_in_bytes = in_bytes;
-        c->e_out_bytes = out_bytes;
-    }
+    if ((r = ring_ensure(c, enc_rings(c), {in_bytes, out_bytes, in_bytes, out_bytes}))) return r;
 
     const int cw = chroma == 444 ? width : width / 2, ch = chroma == 420 ? height / 2 : height;
     const int sw[3] = {width, cw, cw}, sh[3] = {height, ch, ch};

@@ -3,7 +3,7 @@
 // hvc_jpeg_encode, hvc_jpeg_encode_rgb.  Batches: BASELINE's configuration 3, the pipeline with the Huffman reader on the host
 // (decode_batch_impl behind hvc_jpeg_decode_batch, _batch_yuv444 and _batch_scaled), and hvc_jpeg_decode_batch_rgb over either
 // pipeline.
-#include "hvc_ctx.h"
+#include "hvc_batch.h"
 #include "hvc_mixed_plan.h"
 #include "hvc_mixed_rgb_plan.h"
 
@@ -441,68 +441,29 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
 
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < NB; i++) {
-        if (!c->ev_h2d[i]) HIPCHK(c, hipEventCreate(&c->ev_h2d[i]));
-        if (!c->ev_kern[i]) HIPCHK(c, hipEventCreate(&c->ev_kern[i]));
-    }
-    for (int i = 0; i < 4; i++)
-        if (!c->ev_t[i]) HIPCHK(c, hipEventCreate(&c->ev_t[i]));
-    if (ring_bytes > c->ring_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-        for (int i = 0; i < NB; i++) {
-            if (c->h_ring[i]) (void)hipHostFree(c->h_ring[i]);
-            if (c->d_ring[i]) (void)hipFree(c->d_ring[i]);
-            c->h_ring[i] = c->d_ring[i] = nullptr;
-        }
-        c->ring_bytes = 0;
-        for (int i = 0; i < NB; i++) {
-            if (hipHostMalloc(&c->h_ring[i], ring_bytes, hipHostMallocDefault) != hipSuccess ||
-                hipMalloc(&c->d_ring[i], ring_bytes) != hipSuccess)
-                return HVC_E_OUT_OF_MEMORY;
-        }
-        c->ring_bytes = ring_bytes;
-    }
-    if (oring_bytes > c->oring_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int i = 0; i < NB; i++) {
-            if (c->d_oring[i]) (void)hipFree(c->d_oring[i]);
-            c->d_oring[i] = nullptr;
-        }
-        c->oring_bytes = 0;
-        for (int i = 0; i < NB; i++)
-            if (hipMalloc(&c->d_oring[i], oring_bytes) != hipSuccess) return HVC_E_OUT_OF_MEMORY;
-        c->oring_bytes = oring_bytes;
-    }
+    if ((r = pipeline_events(c))) return r;
+    if ((r = ring_ensure(c, coef_rings(c), {ring_bytes, ring_bytes}))) return r;
+    if ((r = ring_ensure(c, out_rings(c), {oring_bytes}))) return r;
 
     // worker threads pull frames in order; a frame's chunk slot must have been released (its previous
     // occupant uploaded) before they write into it
-    std::mutex mu;
-    std::condition_variable cv;
-    std::atomic<int> next_frame{0};
-    std::atomic<int> error{0};
-    std::vector<int> done_in_chunk((size_t)n_chunks, 0);
     std::vector<std::vector<WideFix>> chunk_wide((size_t)n_chunks); // blocks whose DC left int16 (frame = index in the chunk)
-    int released_upto = NB - 1; // chunks 0..NB-1 may be written at once
     std::atomic<long long> entropy_ns{0};
-    auto worker_body = [&]() {
-        if (!pin_to_ctx_cpus(c)) error.store(HVC_E_INVALID_ARG); // hvc_set_host_cpus
+    const auto wall0 = std::chrono::steady_clock::now();
+    if ((r = pool_ready(c, threads))) return r;
+    hvc::ChunkFeed feed(c->pool, n_chunks, NB); // (after everything a pool task touches)
+    auto worker = [&]() {
+        if (!pin_to_ctx_cpus(c)) feed.raise(HVC_E_INVALID_ARG); // hvc_set_host_cpus
         hvc::RestartScope honour(c->honour_restart); // (a pool thread reads the files: the flag is its own)
         // Frames are taken TWO at a time and decoded symbol by symbol in turn (hvc::entropy_decode_wide2): one stream is
         // one dependency chain, two streams are two chains the core overlaps -- 1.4x the frames per second per thread.
         std::vector<hvc::WideDc> wide2[2];
         static const int take = [] { const char *v = std::getenv("HVC_HOST_PAIRS"); return v && v[0] == '0' ? 1 : 2; }(); // (A/B: 0 = one file at a time)
         for (;;) {
-            const int f0 = next_frame.fetch_add(take);
-            if (f0 >= n_frames || error.load()) return;
+            const int f0 = feed.claim(take);
+            if (f0 >= n_frames || feed.error()) return;
             const int cnt = (take == 2 && f0 + 1 < n_frames) ? 2 : 1;
-            const int k_last = (f0 + cnt - 1) / C;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return k_last <= released_upto || error.load(); });
-            }
-            if (error.load()) return;
+            if (!feed.wait_slot((f0 + cnt - 1) / C)) return;
             const auto t0 = std::chrono::steady_clock::now();
             hvc_jpeg_info fi[2];
             int e[2] = {HVC_OK, HVC_OK};
@@ -527,135 +488,48 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
                     if (!e[q]) e[q] = hvc::entropy_decode_wide(jpegs[f0 + q], sizes[f0 + q], &fi[q], dst[q], wide2[q]);
             }
             entropy_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-            std::lock_guard<std::mutex> lk(mu);
-            for (int q = 0; q < cnt; q++) {
+            for (int q = 0; q < cnt; q++) { // (the pair's first error: frame order)
                 const int f = f0 + q, k = f / C;
                 if (!e[q] && !wide2[q].empty()) {
+                    std::lock_guard<std::mutex> lk(feed.mutex());
                     try {
                         for (const hvc::WideDc &w : wide2[q]) chunk_wide[(size_t)k].push_back(WideFix{f - k * C, w.block, w.dc});
                     } catch (const std::bad_alloc &) {
                         e[q] = HVC_E_OUT_OF_MEMORY;
                     }
                 }
-                if (e[q] && !error.load()) error.store(e[q]); // (the pair's first error: frame order)
-                done_in_chunk[(size_t)k]++;
+                feed.report(k, 1, e[q]);
             }
-            cv.notify_all();
         }
     };
-    auto worker = [&]() { // (a pool thread: nothing may leave it but through the error flag the orchestrator watches)
-        try {
-            worker_body();
-        } catch (...) {
-            const int e = hvc::exception_code();
-            std::lock_guard<std::mutex> lk(mu);
-            error.store(e);
-            cv.notify_all();
-        }
-    };
-    const auto wall0 = std::chrono::steady_clock::now();
-    if ((r = pool_ready(c, threads))) return r;
-    bool completed = false; // (the workers have run out of frames by themselves)
-    hvc::PoolScope scope(c->pool, [&] {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!completed && !error.load()) error.store(HVC_E_INTERNAL);
-        cv.notify_all();
-    });
-    if ((r = c->pool.submit(worker, threads))) {
-        std::lock_guard<std::mutex> lk(mu);
-        error.store(r);
-        return r; // (the scope waits for the copies that were queued)
-    }
+    if ((r = feed.start(threads, worker))) return r;
 
-    int rc = HVC_OK;
-    double h2d_ms = 0, k_ms = 0, d2h_ms = 0;
-    hipStream_t compute = c->stream;
-    try {
-    for (int k = 0; k < n_chunks && rc == HVC_OK; k++) {
-        const int slot = k % NB, first = k * C, cnt = (first + C <= n_frames) ? C : n_frames - first;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return done_in_chunk[(size_t)k] == cnt || error.load(); });
-        }
-        if (error.load()) { rc = error.load(); break; }
-        hipError_t he = hipSuccess;
-        uint8_t *dst = where == HVC_MEM_DEVICE ? pixels + (size_t)first * pixel_fs : (uint8_t *)c->d_oring[slot];
-        const size_t dst_fs = where == HVC_MEM_DEVICE ? pixel_fs : out_bytes;
-        // the device chunk (and output ring slot) is reused every NB chunks: its previous kernel must be done
-        if (k >= NB) he = hipStreamWaitEvent(c->copy_stream, c->ev_kern[slot], 0);
-        if (he == hipSuccess) he = hipEventRecord(c->ev_t[0], c->copy_stream);
-        if (he == hipSuccess)
-            he = hipMemcpyAsync(c->d_ring[slot], c->h_ring[slot], frame_coef_bytes * (size_t)cnt, hipMemcpyHostToDevice,
-                                c->copy_stream);
-        if (he == hipSuccess) he = hipEventRecord(c->ev_h2d[slot], c->copy_stream);
-        if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_h2d[slot], 0);
-        if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-        he = hipEventRecord(c->ev_t[1], compute);
-        DecodeOpts o(c);
-        o.profile = form.chunk_profile(c);
-        o.wide = &chunk_wide[(size_t)k]; // (complete: the chunk's workers are done)
-        rc = form.run(c, (const int16_t *)c->d_ring[slot], cnt, dst, dst_fs, HVC_MEM_DEVICE, o);
-        if (rc) break;
-        if (he == hipSuccess) he = hipEventRecord(c->ev_t[2], compute);
-        if (he == hipSuccess && where == HVC_MEM_HOST) {
-            for (int f = 0; f < cnt && he == hipSuccess; f++)
-                he = hipMemcpyAsync(pixels + (size_t)(first + f) * pixel_fs, dst + (size_t)f * dst_fs, out_bytes,
-                                    hipMemcpyDeviceToHost, compute);
-        }
-        if (he == hipSuccess) he = hipEventRecord(c->ev_kern[slot], compute);
-        if (he == hipSuccess) he = hipEventRecord(c->ev_t[3], compute);
-        // wait for this chunk's upload, then hand the pinned slot to chunk k + NB
-        if (he == hipSuccess) he = wait_event(c->ev_h2d[slot]);
-        if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            released_upto = k + NB;
-            cv.notify_all();
-        }
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev_t[0], c->ev_h2d[slot]) == hipSuccess) h2d_ms += ms;
-        // kernel / d2h times of this chunk: the events are shared by all chunks, so they are read (and the
-        // chunk waited for) before the next one records them; the worker threads -- the bound of this
-        // pipeline -- keep decoding into the other ring slots meanwhile
-        if (wait_event(c->ev_t[3]) == hipSuccess) {
-            if (hipEventElapsedTime(&ms, c->ev_t[1], c->ev_t[2]) == hipSuccess) k_ms += ms;
-            if (hipEventElapsedTime(&ms, c->ev_t[2], c->ev_t[3]) == hipSuccess) d2h_ms += ms;
-        }
-    }
-    } catch (...) {
-        rc = hvc::exception_code();
-    }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (rc != HVC_OK) error.store(rc);
-        else completed = true;
-        cv.notify_all();
-    }
-    {
-        const int te = scope.finish();
-        if (rc == HVC_OK && te) rc = te;
-    }
-    if (rc == HVC_OK && error.load()) rc = error.load();
-    if (rc == HVC_OK) {
-        hipError_t he = hipStreamSynchronize(compute);
-        if (he == hipSuccess) he = hipStreamSynchronize(c->copy_stream);
-        if (he != hipSuccess) rc = fail_hip(c, he);
-    } else {
-        (void)hipStreamSynchronize(compute);
-        (void)hipStreamSynchronize(c->copy_stream);
-    }
+    auto first_of = [&](int k) { return k * C; };
+    auto count_of = [&](int k) { return first_of(k) + C <= n_frames ? C : n_frames - first_of(k); };
+    auto dst_of = [&](int k, int slot) { return where == HVC_MEM_DEVICE ? pixels + (size_t)first_of(k) * pixel_fs : (uint8_t *)c->d_oring[slot]; };
+    const size_t dst_fs = where == HVC_MEM_DEVICE ? pixel_fs : out_bytes;
+    r = host_reader_chunks(
+        c, feed, n_chunks, threads, wall0, count_of, [&](int k) { return frame_coef_bytes * (size_t)count_of(k); },
+        [&](int k, int slot) {
+            DecodeOpts o(c);
+            o.profile = form.chunk_profile(c);
+            o.wide = &chunk_wide[(size_t)k]; // (complete: the chunk's workers are done)
+            return form.run(c, (const int16_t *)c->d_ring[slot], count_of(k), dst_of(k, slot), dst_fs, HVC_MEM_DEVICE, o);
+        },
+        [&](int k, int slot) {
+            hipError_t he = hipSuccess;
+            for (int f = 0; f < count_of(k) && he == hipSuccess && where == HVC_MEM_HOST; f++)
+                he = hipMemcpyAsync(pixels + (size_t)(first_of(k) + f) * pixel_fs, dst_of(k, slot) + (size_t)f * dst_fs, out_bytes,
+                                    hipMemcpyDeviceToHost, c->stream);
+            return he;
+        },
+        stats);
     if (stats) {
-        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
         stats->entropy_ms_sum = (double)entropy_ns.load() * 1e-6;
-        stats->h2d_ms_sum = h2d_ms;
-        stats->kernel_ms_sum = k_ms;
-        stats->d2h_ms_sum = d2h_ms;
-        stats->chunks = n_chunks;
-        stats->threads = threads;
         stats->frames_per_chunk = C;
         stats->coef_bytes = (uint64_t)frame_coef_bytes * (uint64_t)n_frames;
     }
-    return rc;
+    return r;
 }
 
 int hvc_jpeg_decode_batch(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames, int threads,

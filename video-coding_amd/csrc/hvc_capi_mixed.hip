@@ -4,7 +4,7 @@
 // worker pool of hvc_jpeg_decode_batch; what it cuts the batch by is bytes, not frames.  The RGB forms (hvc_yuv_to_rgb_mixed,
 // hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed_rgb) put one launch of k_ycc_to_rgb_mixed (hvc_mixed_rgb.hip) behind
 // the planes, from the host plan of hvc_mixed_rgb_plan.cpp.
-#include "hvc_ctx.h"
+#include "hvc_batch.h"
 #include "hvc_mixed.h"
 #include "hvc_mixed_rgb.h"
 
@@ -463,69 +463,25 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
 
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < NB; i++) {
-        if (!c->ev_h2d[i]) HIPCHK(c, hipEventCreate(&c->ev_h2d[i]));
-        if (!c->ev_kern[i]) HIPCHK(c, hipEventCreate(&c->ev_kern[i]));
-    }
-    for (int i = 0; i < 4; i++)
-        if (!c->ev_t[i]) HIPCHK(c, hipEventCreate(&c->ev_t[i]));
-    if (ring_bytes > c->ring_bytes) { // (a single file larger than chunk_bytes: the ring grows)
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-        for (int i = 0; i < NB; i++) {
-            if (c->h_ring[i]) (void)hipHostFree(c->h_ring[i]);
-            if (c->d_ring[i]) (void)hipFree(c->d_ring[i]);
-            c->h_ring[i] = c->d_ring[i] = nullptr;
-        }
-        c->ring_bytes = 0;
-        for (int i = 0; i < NB; i++)
-            if (hipHostMalloc(&c->h_ring[i], ring_bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&c->d_ring[i], ring_bytes) != hipSuccess)
-                return HVC_E_OUT_OF_MEMORY;
-        c->ring_bytes = ring_bytes;
-    }
-    if (oring_bytes > c->oring_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int i = 0; i < NB; i++) {
-            if (c->d_oring[i]) (void)hipFree(c->d_oring[i]);
-            c->d_oring[i] = nullptr;
-        }
-        c->oring_bytes = 0;
-        for (int i = 0; i < NB; i++)
-            if (hipMalloc(&c->d_oring[i], oring_bytes) != hipSuccess) return HVC_E_OUT_OF_MEMORY;
-        c->oring_bytes = oring_bytes;
-    }
-    if (pring_bytes > c->pring_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int i = 0; i < NB; i++) {
-            if (c->d_pring[i]) (void)hipFree(c->d_pring[i]);
-            c->d_pring[i] = nullptr;
-        }
-        c->pring_bytes = 0;
-        for (int i = 0; i < NB; i++)
-            if (hipMalloc(&c->d_pring[i], pring_bytes) != hipSuccess) return HVC_E_OUT_OF_MEMORY;
-        c->pring_bytes = pring_bytes;
-    }
+    int r = pipeline_events(c);
+    if (r) return r;
+    if ((r = ring_ensure(c, coef_rings(c), {ring_bytes, ring_bytes}))) return r; // (a single file larger than chunk_bytes: the ring grows)
+    if ((r = ring_ensure(c, out_rings(c), {oring_bytes}))) return r;
+    if ((r = ring_ensure(c, plane_rings(c), {pring_bytes}))) return r;
 
-    std::mutex mu;
-    std::condition_variable cv;
-    std::atomic<int> next{0}, error{0};
-    std::vector<int> done_in_chunk((size_t)n_chunks, 0);
-    int released_upto = NB - 1;
     std::atomic<long long> entropy_ns{0};
-    auto worker_body = [&]() {
-        if (!pin_to_ctx_cpus(c)) error.store(HVC_E_INVALID_ARG);
+    const auto wall0 = std::chrono::steady_clock::now();
+    if ((r = pool_ready(c, threads))) return r;
+    hvc::ChunkFeed feed(c->pool, n_chunks, NB); // (after everything a pool task touches)
+    auto worker = [&]() {
+        if (!pin_to_ctx_cpus(c)) feed.raise(HVC_E_INVALID_ARG);
         hvc::RestartScope honour(c->honour_restart);
         std::vector<hvc::WideDc> wide;
         for (;;) {
-            const int t = next.fetch_add(1);
-            if (t >= n_take || error.load()) return;
+            const int t = feed.claim();
+            if (t >= n_take || feed.error()) return;
             const int f = take[(size_t)t], k = chunk_of[(size_t)f];
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return k <= released_upto || error.load(); });
-            }
-            if (error.load()) return;
+            if (!feed.wait_slot(k)) return;
             const auto t0 = std::chrono::steady_clock::now();
             int e;
             if (infos[f].coef_count == 0) { // no block: the file is still read as the model reads it
@@ -536,154 +492,81 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
                 if (!e && !wide.empty()) e = HVC_E_RANGE; // (a DC beyond int16: no side list here)
             }
             entropy_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-            std::lock_guard<std::mutex> lk(mu);
-            status[f] = e; // the file's own result: it stops nobody else
-            done_in_chunk[(size_t)k]++;
-            cv.notify_all();
+            status[f] = e; // the file's own result: it stops nobody else (read once the chunk is complete)
+            feed.report(k, 1, HVC_OK);
         }
     };
-    auto worker = [&]() {
-        try {
-            worker_body();
-        } catch (...) {
-            const int e = hvc::exception_code();
-            std::lock_guard<std::mutex> lk(mu);
-            error.store(e);
-            cv.notify_all();
-        }
-    };
-    const auto wall0 = std::chrono::steady_clock::now();
-    int r = pool_ready(c, threads);
-    if (r) return r;
-    bool completed = false;
-    hvc::PoolScope scope(c->pool, [&] {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!completed && !error.load()) error.store(HVC_E_INTERNAL);
-        cv.notify_all();
-    });
-    if ((r = c->pool.submit(worker, threads))) {
-        std::lock_guard<std::mutex> lk(mu);
-        error.store(r);
-        return r;
-    }
+    if ((r = feed.start(threads, worker))) return r;
 
-    int rc = HVC_OK;
-    double h2d_ms = 0, k_ms = 0, d2h_ms = 0;
-    hipStream_t compute = c->stream;
     wide_total_begin(c);
-    try {
-        std::vector<int> ok;
-        for (int k = 0; k < n_chunks && rc == HVC_OK; k++) {
+    std::vector<int> ok; // the chunk's good files with blocks
+    uint8_t *const out = where == HVC_MEM_DEVICE ? pixels : nullptr; // (host: the chunk's slot of d_oring)
+    const size_t *dst_off = where == HVC_MEM_DEVICE ? pixel_offsets : pix_rel.data();
+    r = host_reader_chunks(
+        c, feed, n_chunks, threads, wall0, [&](int k) { return chunks[(size_t)k].count; },
+        [&](int k) -> size_t {
             const Chunk &ch = chunks[(size_t)k];
-            const int slot = k % NB;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return done_in_chunk[(size_t)k] == ch.count || error.load(); });
-            }
-            if (error.load()) { rc = error.load(); break; }
             ok.clear();
             for (int t = ch.first; t < ch.first + ch.count; t++) // (status[] of this chunk is final: its workers are done)
                 if (status[take[(size_t)t]] == HVC_OK && infos[take[(size_t)t]].coef_count) ok.push_back(take[(size_t)t]);
-            hipError_t he = hipSuccess;
-            if (k >= NB) he = hipStreamWaitEvent(c->copy_stream, c->ev_kern[slot], 0);
-            if (he == hipSuccess) he = hipEventRecord(c->ev_t[0], c->copy_stream);
-            if (he == hipSuccess && ch.coef_bytes && !ok.empty()) {
-                he = hipMemcpyAsync(c->d_ring[slot], c->h_ring[slot], ch.coef_bytes, hipMemcpyHostToDevice, c->copy_stream);
-                coef_total += ch.coef_bytes;
-            }
-            if (he == hipSuccess) he = hipEventRecord(c->ev_h2d[slot], c->copy_stream);
-            if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_h2d[slot], 0);
-            if (he == hipSuccess) he = hipEventRecord(c->ev_t[1], compute);
-            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-            uint8_t *dst = where == HVC_MEM_DEVICE ? pixels : (uint8_t *)c->d_oring[slot];
-            const size_t *dst_off = where == HVC_MEM_DEVICE ? pixel_offsets : pix_rel.data();
-            if (!form.rgb()) {
-                rc = mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), infos, ok.data(), (int)ok.size(), dst, dst_off, c->profiling);
-            } else { // the planes into the slot of their own ring, the colour pass from there to where the planes would have gone
-                uint8_t *planes = (uint8_t *)c->d_pring[slot];
-                hvc::MixedRgbPlan cplan;
-                rc = hvc::mixed_rgb_plan_build(infos, plane_rel.data(), dst_off, form.rgb_row_strides, form.layout, ok.data(), (int)ok.size(),
+            if (ok.empty()) return 0;
+            coef_total += ch.coef_bytes;
+            return ch.coef_bytes;
+        },
+        [&](int, int slot) {
+            uint8_t *dst = out ? out : (uint8_t *)c->d_oring[slot];
+            if (!form.rgb())
+                return mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), infos, ok.data(), (int)ok.size(), dst, dst_off, c->profiling);
+            // the planes into the slot of their own ring, the colour pass from there to where the planes would have gone
+            uint8_t *planes = (uint8_t *)c->d_pring[slot];
+            hvc::MixedRgbPlan cplan;
+            int rc = hvc::mixed_rgb_plan_build(infos, plane_rel.data(), dst_off, form.rgb_row_strides, form.layout, ok.data(), (int)ok.size(),
                                                (uintptr_t)planes, (uintptr_t)dst, true, cplan);
-                if (!rc) rc = mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), infos, ok.data(), (int)ok.size(), planes,
-                                           plane_rel.data(), c->profiling);
-                if (!rc) rc = mixed_rgb_launch_plan(c, cplan, form.layout, planes, dst, false);
-            }
-            if (rc) break;
-            he = hipEventRecord(c->ev_t[2], compute);
-            if (he == hipSuccess && where == HVC_MEM_HOST) {
-                // the records of consecutive good files go back in one copy where only alignment padding lies between them
-                // (the padding between records is nobody's; a failed file's record is never touched)
-                size_t run_lo = 0, run_hi = 0;
-                auto flush = [&]() {
-                    if (run_hi > run_lo && he == hipSuccess)
-                        he = hipMemcpyAsync(pixels + ch.pix_lo + run_lo, dst + run_lo, run_hi - run_lo, hipMemcpyDeviceToHost, compute);
-                    run_lo = run_hi = 0;
-                };
-                int prev_t = -2;
-                for (int t = ch.first; t < ch.first + ch.count; t++) {
-                    const int f = take[(size_t)t];
-                    if (status[f] != HVC_OK || !out_bytes[(size_t)f]) continue;
-                    const size_t lo = pix_rel[(size_t)f], hi = lo + out_bytes[(size_t)f];
-                    if (form.rgb() && form.rgb_row_strides && form.rgb_row_strides[f] > hvc::mixed_rgb_row_bytes(form.layout, infos[f].width)) {
-                        flush(); // rows with room between them: the image row by row, the caller's bytes between rows stay
-                        if (he == hipSuccess)
-                            he = hipMemcpy2DAsync(pixels + ch.pix_lo + lo, form.rgb_row_strides[f], dst + lo, form.rgb_row_strides[f],
-                                                  hvc::mixed_rgb_row_bytes(form.layout, infos[f].width),
-                                                  hvc::mixed_rgb_rows(form.layout, infos[f].height), hipMemcpyDeviceToHost, compute);
-                        continue;
-                    }
-                    const bool joins = run_hi > run_lo && t == prev_t + 1 && lo >= run_hi && lo - run_hi < 4096;
-                    if (!joins) flush();
-                    if (run_hi == run_lo) run_lo = lo;
-                    run_hi = hi;
-                    prev_t = t;
+            if (!rc) rc = mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), infos, ok.data(), (int)ok.size(), planes,
+                                       plane_rel.data(), c->profiling);
+            if (!rc) rc = mixed_rgb_launch_plan(c, cplan, form.layout, planes, dst, false);
+            return rc;
+        },
+        [&](int k, int slot) {
+            hipError_t he = hipSuccess;
+            if (where != HVC_MEM_HOST) return he;
+            const Chunk &ch = chunks[(size_t)k];
+            const uint8_t *dst = (const uint8_t *)c->d_oring[slot];
+            // the records of consecutive good files go back in one copy where only alignment padding lies between them
+            // (the padding between records is nobody's; a failed file's record is never touched)
+            size_t run_lo = 0, run_hi = 0;
+            auto flush = [&]() {
+                if (run_hi > run_lo && he == hipSuccess)
+                    he = hipMemcpyAsync(pixels + ch.pix_lo + run_lo, dst + run_lo, run_hi - run_lo, hipMemcpyDeviceToHost, c->stream);
+                run_lo = run_hi = 0;
+            };
+            int prev_t = -2;
+            for (int t = ch.first; t < ch.first + ch.count; t++) {
+                const int f = take[(size_t)t];
+                if (status[f] != HVC_OK || !out_bytes[(size_t)f]) continue;
+                const size_t lo = pix_rel[(size_t)f], hi = lo + out_bytes[(size_t)f];
+                if (form.rgb() && form.rgb_row_strides && form.rgb_row_strides[f] > hvc::mixed_rgb_row_bytes(form.layout, infos[f].width)) {
+                    flush(); // rows with room between them: the image row by row, the caller's bytes between rows stay
+                    if (he == hipSuccess)
+                        he = hipMemcpy2DAsync(pixels + ch.pix_lo + lo, form.rgb_row_strides[f], dst + lo, form.rgb_row_strides[f],
+                                              hvc::mixed_rgb_row_bytes(form.layout, infos[f].width),
+                                              hvc::mixed_rgb_rows(form.layout, infos[f].height), hipMemcpyDeviceToHost, c->stream);
+                    continue;
                 }
-                flush();
+                const bool joins = run_hi > run_lo && t == prev_t + 1 && lo >= run_hi && lo - run_hi < 4096;
+                if (!joins) flush();
+                if (run_hi == run_lo) run_lo = lo;
+                run_hi = hi;
+                prev_t = t;
             }
-            if (he == hipSuccess) he = hipEventRecord(c->ev_kern[slot], compute);
-            if (he == hipSuccess) he = hipEventRecord(c->ev_t[3], compute);
-            if (he == hipSuccess) he = wait_event(c->ev_h2d[slot]); // the pinned slot goes to chunk k + NB
-            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                released_upto = k + NB;
-                cv.notify_all();
-            }
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, c->ev_t[0], c->ev_h2d[slot]) == hipSuccess) h2d_ms += ms;
-            if (wait_event(c->ev_t[3]) == hipSuccess) { // (the events are shared by all chunks: read before the next records them)
-                if (hipEventElapsedTime(&ms, c->ev_t[1], c->ev_t[2]) == hipSuccess) k_ms += ms;
-                if (hipEventElapsedTime(&ms, c->ev_t[2], c->ev_t[3]) == hipSuccess) d2h_ms += ms;
-            }
-        }
-    } catch (...) {
-        rc = hvc::exception_code();
-    }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (rc != HVC_OK) error.store(rc);
-        else completed = true;
-        cv.notify_all();
-    }
-    {
-        const int te = scope.finish();
-        if (rc == HVC_OK && te) rc = te;
-    }
-    if (rc == HVC_OK && error.load()) rc = error.load();
-    {
-        const hipError_t h1 = hipStreamSynchronize(compute), h2 = hipStreamSynchronize(c->copy_stream);
-        if (rc == HVC_OK && (h1 != hipSuccess || h2 != hipSuccess)) rc = fail_hip(c, h1 != hipSuccess ? h1 : h2);
-    }
+            flush();
+            return he;
+        },
+        stats);
     if (stats) {
-        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
         stats->entropy_ms_sum = (double)entropy_ns.load() * 1e-6;
-        stats->h2d_ms_sum = h2d_ms;
-        stats->kernel_ms_sum = k_ms;
-        stats->d2h_ms_sum = d2h_ms;
-        stats->chunks = n_chunks;
-        stats->threads = threads;
         stats->frames_per_chunk = largest;
         stats->coef_bytes = coef_total;
     }
-    return rc;
+    return r;
 }

@@ -1,7 +1,7 @@
 // hvc_capi_reader.hip -- the GPU Huffman reader (hvc_hdec.hip) behind the C ABI: hvc_jpeg_entropy_decode_gpu and the batch
 // pipeline built on it (hvc_jpeg_decode_batch_gpu: host threads unstuff, the copy engine uploads, the reader and the block
 // stage run per chunk).
-#include "hvc_ctx.h"
+#include "hvc_batch.h"
 
 // Two files of one batch: the same frame geometry (sizes, sampling, planes)?  The Huffman table selectors of the scan
 // may differ -- the GPU reader takes every file's tables from the file itself.
@@ -560,67 +560,13 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
 
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < NB; i++) {
-        if (!c->ev_h2d[i]) HIPCHK(c, hipEventCreate(&c->ev_h2d[i]));
-        if (!c->ev_kern[i]) HIPCHK(c, hipEventCreate(&c->ev_kern[i]));
-    }
-    for (int i = 0; i < 4; i++)
-        if (!c->ev_t[i]) HIPCHK(c, hipEventCreate(&c->ev_t[i]));
+    if ((r = pipeline_events(c))) return r;
     for (int i = 0; i < NB; i++)
         for (int k = 0; k < 3; k++)
             if (!c->ev_et[i][k]) HIPCHK(c, hipEventCreate(&c->ev_et[i][k])); // per-slot stage timers
-    if (ecs_bytes > c->gp_ecs_bytes || meta_bytes > c->gp_meta_bytes || ftabs_bytes > c->gp_ftabs_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-        for (int i = 0; i < NB; i++) {
-            if (c->gp_h_ecs[i]) (void)hipHostFree(c->gp_h_ecs[i]);
-            if (c->gp_d_ecs[i]) (void)hipFree(c->gp_d_ecs[i]);
-            if (c->gp_h_meta[i]) (void)hipHostFree(c->gp_h_meta[i]);
-            if (c->gp_d_meta[i]) (void)hipFree(c->gp_d_meta[i]);
-            if (c->gp_h_ftabs[i]) (void)hipHostFree(c->gp_h_ftabs[i]);
-            if (c->gp_d_ftabs[i]) (void)hipFree(c->gp_d_ftabs[i]);
-            c->gp_h_ecs[i] = c->gp_d_ecs[i] = c->gp_h_meta[i] = c->gp_d_meta[i] = c->gp_h_ftabs[i] = c->gp_d_ftabs[i] = nullptr;
-        }
-        c->gp_ecs_bytes = c->gp_meta_bytes = c->gp_ftabs_bytes = 0;
-        for (int i = 0; i < NB; i++)
-            if (hipHostMalloc(&c->gp_h_ecs[i], ecs_bytes, HVC_UPLOAD_RING_FLAGS) != hipSuccess ||
-                hipMalloc(&c->gp_d_ecs[i], ecs_bytes + HVC_HD_ECS_SLACK) != hipSuccess ||
-                hipHostMalloc(&c->gp_h_meta[i], meta_bytes, hipHostMallocDefault) != hipSuccess ||
-                hipMalloc(&c->gp_d_meta[i], meta_bytes) != hipSuccess ||
-                hipHostMalloc(&c->gp_h_ftabs[i], ftabs_bytes, HVC_UPLOAD_RING_FLAGS) != hipSuccess ||
-                hipMalloc(&c->gp_d_ftabs[i], ftabs_bytes) != hipSuccess)
-                return HVC_E_OUT_OF_MEMORY;
-        c->gp_ecs_bytes = ecs_bytes;
-        c->gp_meta_bytes = meta_bytes;
-        c->gp_ftabs_bytes = ftabs_bytes;
-    }
-    if (coef_chunk > c->ring_bytes) { // the device coefficient ring of the host-decoder pipeline is reused
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-        for (int i = 0; i < NB; i++) {
-            if (c->h_ring[i]) (void)hipHostFree(c->h_ring[i]);
-            if (c->d_ring[i]) (void)hipFree(c->d_ring[i]);
-            c->h_ring[i] = c->d_ring[i] = nullptr;
-        }
-        c->ring_bytes = 0;
-        for (int i = 0; i < NB; i++)
-            if (hipHostMalloc(&c->h_ring[i], coef_chunk, hipHostMallocDefault) != hipSuccess ||
-                hipMalloc(&c->d_ring[i], coef_chunk) != hipSuccess)
-                return HVC_E_OUT_OF_MEMORY;
-        c->ring_bytes = coef_chunk;
-    }
-    if (oring_bytes > c->oring_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int i = 0; i < NB; i++) {
-            if (c->d_oring[i]) (void)hipFree(c->d_oring[i]);
-            c->d_oring[i] = nullptr;
-        }
-        c->oring_bytes = 0;
-        for (int i = 0; i < NB; i++)
-            if (hipMalloc(&c->d_oring[i], oring_bytes) != hipSuccess) return HVC_E_OUT_OF_MEMORY;
-        c->oring_bytes = oring_bytes;
-    }
+    if ((r = ring_ensure(c, reader_rings(c), {ecs_bytes, ecs_bytes, meta_bytes, meta_bytes, ftabs_bytes, ftabs_bytes}))) return r;
+    if ((r = ring_ensure(c, coef_rings(c), {coef_chunk, coef_chunk}))) return r; // the coefficient ring of the host-decoder pipeline is reused
+    if ((r = ring_ensure(c, out_rings(c), {oring_bytes}))) return r;
     // The reader of chunk k runs on rd_stream[k & 1] with its own per-subsequence state, the block stage of all
     // chunks on c->stream: the last synchronisation rounds of a chunk (a handful of wavefronts chasing the few
     // stretches that are slow to synchronise, each round a full kernel's latency) overlap with the next chunk's
@@ -668,15 +614,10 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
     std::vector<char> frame_pf((size_t)n_frames, 0); // the frame has tables of its own
 
     // workers: header parse, table check, unstuffing into the pinned segment ring
-    std::mutex mu;
-    std::condition_variable cv;
-    std::atomic<int> next_frame{0};
-    std::atomic<int> error{0};
     // chunks the GPU reader cannot or must not do (a file with other Huffman tables, tables that are no prefix code, a
     // stream the model raises on or that ends early, rounds that do not settle): skipped here or found out at the
     // verdict, and redone by the host-reader pipeline once this one has drained -- chunk by chunk, not the whole call
     std::vector<char> chunk_host((size_t)n_chunks, 0), skipped((size_t)n_chunks, 0);
-    std::vector<int> done_in_chunk((size_t)n_chunks, 0);
     std::vector<unsigned> ecs_size((size_t)n_frames, 0);
     std::vector<unsigned> unit_off, unit_len; // restart intervals: [file][interval] place inside the file's ring region, bytes
     if (ipf > 1) {
@@ -687,21 +628,24 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
             return HVC_E_OUT_OF_MEMORY;
         }
     }
-    int released_upto = NB - 1;
     std::atomic<long long> prep_ns{0};
-    auto worker_body = [&]() {
+    std::atomic<int> stage_done{0}, dl_abort{0}, dl_err{0}; // chunks whose block stage is enqueued
+    std::vector<char> downloaded((size_t)n_chunks, 0);      // (everything a pool task touches is declared BEFORE the feed,
+                                                            // whose scope waits for the tasks: destroyed after it has waited)
+    const auto wall0 = std::chrono::steady_clock::now();
+    if ((r = pool_ready(c, threads, where == HVC_MEM_HOST ? 1 : 0))) return r;
+    hvc::ChunkFeed feed(c->pool, n_chunks, NB, [&] { dl_abort.store(1); });
+    std::mutex &mu = feed.mutex(); // ... which also guards chunk_host, skipped, stage_done and downloaded
+    std::condition_variable &cv = feed.cv();
+    auto worker = [&]() {
         hvc::HdTables t;
-        if (!pin_to_ctx_cpus(c)) error.store(HVC_E_INVALID_ARG); // hvc_set_host_cpus
+        if (!pin_to_ctx_cpus(c)) feed.raise(HVC_E_INVALID_ARG); // hvc_set_host_cpus
         hvc::RestartScope honour(c->honour_restart);
         for (;;) {
-            const int f = next_frame.fetch_add(1);
-            if (f >= n_frames || error.load()) return;
+            const int f = feed.claim();
+            if (f >= n_frames || feed.error()) return;
             const int k = f / C, slot = k % NB;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return k <= released_upto || error.load(); });
-            }
-            if (error.load()) return;
+            if (!feed.wait_slot(k)) return;
             const auto t0 = std::chrono::steady_clock::now();
             hvc_jpeg_info fi;
             int e = hvc_jpeg_read_header(jpegs[f], sizes[f], &fi);
@@ -730,44 +674,17 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
                 ecs_size[(size_t)f] = (unsigned)got;
             }
             prep_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-            std::lock_guard<std::mutex> lk(mu);
-            if (e) error.store(e);
-            if (unfit) chunk_host[(size_t)k] = 1;
-            done_in_chunk[(size_t)k]++;
-            cv.notify_all();
+            if (unfit) {
+                std::lock_guard<std::mutex> lk(mu);
+                chunk_host[(size_t)k] = 1;
+            }
+            feed.report(k, 1, e);
         }
     };
-    auto worker = [&]() { // (a pool thread: nothing may leave it but through the error flag the orchestrator watches)
-        try {
-            worker_body();
-        } catch (...) {
-            const int e = hvc::exception_code();
-            std::lock_guard<std::mutex> lk(mu);
-            error.store(e);
-            cv.notify_all();
-        }
-    };
-    const auto wall0 = std::chrono::steady_clock::now();
-    if ((r = pool_ready(c, threads, where == HVC_MEM_HOST ? 1 : 0))) return r;
-    std::atomic<int> stage_done{0}, dl_abort{0}, dl_err{0}; // chunks whose block stage is enqueued
-    std::vector<char> downloaded((size_t)n_chunks, 0);      // (everything a pool task touches is declared BEFORE the scope
-                                                            // that waits for the tasks: destroyed after it has waited)
-    bool completed = false; // (the workers have run out of frames, the downloader out of chunks)
-    hvc::PoolScope scope(c->pool, [&] {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!completed && !error.load()) error.store(HVC_E_INTERNAL);
-        dl_abort.store(1);
-        cv.notify_all();
-    });
 
     // Host output: a thread of its own downloads chunk after chunk on c->down_stream (copies to pageable memory hold
     // their caller -- issued from the loop below they kept the next chunk's launches waiting, and on the block
     // stage's stream its kernels too: 18 Gpixel/s, 33 with this).
-    auto submit_failed = [&](int e) {
-        std::lock_guard<std::mutex> lk(mu);
-        error.store(e);
-        return e; // (the scope wakes and waits for whatever was queued)
-    };
     if (where == HVC_MEM_HOST) { // (first: it must run beside the workers, never queue behind them)
         r = c->pool.submit([&] {
             (void)pin_to_ctx_cpus(c);
@@ -799,9 +716,9 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
                 if (e != hipSuccess) return;
             }
         }, 1);
-        if (r) return submit_failed(r);
+        if (r) return feed.finish(r); // (wakes and waits for whatever was queued)
     }
-    if ((r = c->pool.submit(worker, threads))) return submit_failed(r);
+    if ((r = feed.start(threads, worker))) return r;
 
     int rc = HVC_OK;
     double h2d_ms = 0, k_ms = 0;
@@ -813,9 +730,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
     auto release_after_upload = [&](int k) -> hipError_t {
         const hipError_t he = wait_event(c->ev_h2d[k % NB]);
         if (he != hipSuccess) return he;
-        std::lock_guard<std::mutex> lk(mu);
-        released_upto = k + NB;
-        cv.notify_all();
+        feed.release(k);
         return hipSuccess;
     };
     try {
@@ -841,11 +756,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
         }
         if (it >= n_chunks) continue;
         const int k = it, slot = k % NB, first = k * C, cnt = (first + C <= n_frames) ? C : n_frames - first;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return done_in_chunk[(size_t)k] == cnt || error.load(); });
-        }
-        if (error.load()) { rc = error.load(); break; }
+        if ((rc = feed.wait_chunk(k, cnt))) break;
         bool skip;
         {
             std::lock_guard<std::mutex> lk(mu);
@@ -859,7 +770,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
             }
             std::lock_guard<std::mutex> lk(mu);
             skipped[(size_t)k] = 1;
-            released_upto = k + NB;
+            feed.release_locked(k);
             stage_done.store(k + 1);
             cv.notify_all();
             continue;
@@ -958,20 +869,10 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
     } catch (...) {
         rc = hvc::exception_code();
     }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (rc != HVC_OK) error.store(rc);
-        else completed = true;
-        cv.notify_all();
-    }
-    { // (after a complete run the downloader has finished: the last verdicts waited for its last chunks)
-        const int te = scope.finish();
-        if (rc == HVC_OK && te) rc = te;
-    }
+    rc = feed.finish(rc); // (after a complete run the downloader has finished: the last verdicts waited for its last chunks)
     for (int i = 0; i < 3; i++) (void)hipStreamSynchronize(c->rd_stream[i]);
     (void)hipStreamSynchronize(compute);
     (void)hipStreamSynchronize(c->copy_stream);
-    if (rc == HVC_OK && error.load()) rc = error.load();
     double host_entropy_ms = 0;
     for (int k = 0; k < n_chunks && rc == HVC_OK; k++) // everything has drained: the chunks left to the host reader
         if (chunk_host[(size_t)k]) {

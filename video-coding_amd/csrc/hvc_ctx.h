@@ -29,6 +29,7 @@
 #include <thread>
 #include <deque>
 #include <functional>
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/hvc_jpeg.h"
@@ -160,6 +161,51 @@ struct hvc_ctx {
 #ifndef HVC_UPLOAD_RING_FLAGS
 #define HVC_UPLOAD_RING_FLAGS hipHostMallocDefault
 #endif
+
+// The pipelines' rings: RING pinned / device buffers per member, members that are (re)allocated together as a set.
+struct RingMember {
+    void *(*ring)[hvc_ctx::RING];
+    size_t *recorded; // the bytes it was last allocated for (members of the same size share one)
+    bool pinned;      // hipHostMalloc with `flags`, else hipMalloc of the bytes + `slack`
+    unsigned flags;
+    size_t slack;
+};
+struct RingSet {
+    RingMember m[6];
+    int n;
+    bool drain_copy; // copy_stream is drained as well as `stream` before the old buffers go
+};
+inline RingSet coef_rings(hvc_ctx *c) { // coefficient chunks of the decode pipelines
+    return {{{&c->h_ring, &c->ring_bytes, true, hipHostMallocDefault, 0}, {&c->d_ring, &c->ring_bytes, false, 0, 0}}, 2, true};
+}
+inline RingSet out_rings(hvc_ctx *c) { return {{{&c->d_oring, &c->oring_bytes, false, 0, 0}}, 1, false}; } // decoded chunks on their way to the host
+inline RingSet plane_rings(hvc_ctx *c) { return {{{&c->d_pring, &c->pring_bytes, false, 0, 0}}, 1, false}; }
+inline RingSet reader_rings(hvc_ctx *c) { // hvc_jpeg_decode_batch_gpu: segments, index arrays, per-frame tables
+    return {{{&c->gp_h_ecs, &c->gp_ecs_bytes, true, HVC_UPLOAD_RING_FLAGS, 0},
+             {&c->gp_d_ecs, &c->gp_ecs_bytes, false, 0, HVC_HD_ECS_SLACK},
+             {&c->gp_h_meta, &c->gp_meta_bytes, true, hipHostMallocDefault, 0},
+             {&c->gp_d_meta, &c->gp_meta_bytes, false, 0, 0},
+             {&c->gp_h_ftabs, &c->gp_ftabs_bytes, true, HVC_UPLOAD_RING_FLAGS, 0},
+             {&c->gp_d_ftabs, &c->gp_ftabs_bytes, false, 0, 0}},
+            6, true};
+}
+inline RingSet enc_rings(hvc_ctx *c) { // hvc_jpeg_encode_batch: padded pixel chunks in, coefficient chunks out
+    return {{{&c->eh_in, &c->e_in_bytes, true, HVC_UPLOAD_RING_FLAGS, 0},
+             {&c->eh_out, &c->e_out_bytes, true, hipHostMallocDefault, 0},
+             {&c->ed_in, &c->e_in_bytes, false, 0, 0},
+             {&c->ed_out, &c->e_out_bytes, false, 0, 0}},
+            4, true};
+}
+inline RingSet enc_seg_rings(hvc_ctx *c) { // hvc_jpeg_encode_batch_gpu: packed segments + offsets
+    return {{{&c->ed_seg, &c->e_seg_bytes, false, 0, 0}, {&c->ed_off, &c->e_off_bytes, false, 0, 0},
+             {&c->eh_off, &c->e_off_bytes, true, hipHostMallocDefault, 0}},
+            3, false};
+}
+inline RingSet enc_spec_rings(hvc_ctx *c) { return {{{&c->eh_specs, &c->e_specs_bytes, true, hipHostMallocDefault, 0}}, 1, false}; }
+// A set grows when any member wants more than it has (`want`: bytes per member, in the set's order), and is then allocated
+// at the sizes wanted now.  HVC_OK, HVC_E_HIP (a stream did not drain) or HVC_E_OUT_OF_MEMORY.
+int ring_ensure(hvc_ctx *c, const RingSet &s, std::initializer_list<size_t> want);
+void ring_free(const RingSet &s);
 
 struct DeviceGuard {
     int prev = -1;
