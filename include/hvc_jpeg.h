@@ -749,7 +749,8 @@ HVC_API int hvc_jpeg_decode_batch_scaled(hvc_ctx *ctx, const uint8_t *const *jpe
  * memory (k_decode_mixed): a launch serves any set of planes, a 64 x 64 thumbnail costs three wavefronts.  The output is
  * full-size padded planes, or RGB images (below: hvc_jpeg_mixed_rgb_layout, hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb,
  * hvc_jpeg_decode_batch_mixed_rgb, whose colour pass k_ycc_to_rgb_mixed takes its decomposition from device memory the same
- * way); there is no 4:4:4-planar or reduced-size form, the host Huffman reader only, no side list of DCs beyond int16.  With
+ * way), or either at 1/2, 1/4, 1/8 size (further below: the *_mixed_scaled* entry points, block stage k_decode_mixed_scaled);
+ * there is no 4:4:4-planar form, the host Huffman reader only, no side list of DCs beyond int16.  With
  * HVC_ARITH_HARDCAML set the ctx functions return HVC_E_INVALID_ARG; hvc_set_decode_kernel(ctx, 2) sends every block
  * through the int64 arithmetic, other selections are ignored; hvc_last_wide_blocks counts the blocks that took it. */
 
@@ -829,6 +830,52 @@ HVC_API int hvc_jpeg_decode_batch_mixed_rgb(hvc_ctx *ctx, const uint8_t *const *
                                             int threads, size_t chunk_bytes, const hvc_jpeg_info *infos, int *status,
                                             const size_t *rgb_offsets, const size_t *rgb_row_strides, uint8_t *rgb,
                                             size_t rgb_cap, int layout, int where, hvc_batch_stats *stats);
+
+/* Mixed batches at reduced size: thumbnails or previews of a set of files in one call.  scale_denom is 1, 2, 4 or 8 (anything
+ * else: HVC_E_INVALID_ARG); 1 IS the full-size entry point of the same name without "_scaled", with all its rules (its 8-byte
+ * alignment; scaled[f] == infos[f]).  At 2, 4, 8 the block stage is k_decode_mixed_scaled: the reduced-size inverse DCT of
+ * "Decoding at reduced size" above (N = 8 / scale_denom samples per block side, its int32 guard and int64 branch in the same
+ * lane) under k_decode_mixed's work decomposition; every byte is what hvc_decode_frames_scaled / hvc_jpeg_decode_scaled[_rgb]
+ * give for that frame or file alone.  Full-size planes exist nowhere.  HVC_ARITH_HARDCAML: HVC_E_INVALID_ARG, output untouched.
+ * hvc_last_wide_blocks counts the blocks of the int64 branch, as after hvc_decode_frames_scaled; hvc_set_decode_kernel is
+ * ignored.  In the file pipelines the host Huffman reader is the bound at every scale: what the scaled form saves is the
+ * output's memory and download, not time in the block stage.
+ *
+ * hvc_jpeg_mixed_scaled_layout (host only): headers -> infos[f] (FULL-size, what hvc_jpeg_read_header gives: the batch call's
+ *   input), scaled[f] (hvc_jpeg_scaled_info of it: what describes file f's output record), status[f], pixel_offsets[f],
+ *   *total_bytes; records = scaled[f].pixel_bytes, in file order, each start rounded up to align (a power of two >= 8; 0 =
+ *   256); a file with a nonzero status takes no room (and its scaled[f] is not written).
+ * hvc_decode_frames_mixed_scaled: frame f: infos[f].layout's blocks_w / blocks_h / qtab / coef_offset as ever, .plane_offset /
+ *   .stride describe its SCALED planes by hvc_decode_frames_scaled's rule: any offset, any stride >= blocks_w * N (below:
+ *   HVC_E_INVALID_ARG); coefficient planes on 16 bytes as ever.  A plane whose first byte and stride are multiples of 4 is
+ *   written in dwords, any other in 2-byte / 1-byte pieces (tight strides: blocks_w odd at N = 2, blocks_w % 4 != 0 at N = 1).
+ *   Bytes between rows and between records are never written.  HVC_MEM_DEVICE: one launch on ctx's stream, honours
+ *   hvc_set_profiling (the pair brackets k_decode_mixed_scaled); HVC_MEM_HOST: staged through context scratch, the call blocks.
+ * hvc_jpeg_decode_batch_mixed_scaled: hvc_jpeg_decode_batch_mixed's pipeline, statuses, chunks and stats; infos = the FULL-size
+ *   infos of the layout call, records as hvc_jpeg_mixed_scaled_layout placed them (any offset is accepted).  pixel_cap: every
+ *   good file's record must lie inside (HVC_E_INVALID_ARG).  Host output: no byte outside the good files' records is written.
+ * hvc_jpeg_mixed_scaled_rgb_layout / hvc_jpeg_decode_batch_mixed_scaled_rgb: as hvc_jpeg_mixed_rgb_layout /
+ *   hvc_jpeg_decode_batch_mixed_rgb with image f = scaled[f].width x scaled[f].height, byte for byte what
+ *   hvc_jpeg_decode_scaled_rgb gives for file f alone; the chunk's scaled planes go to the device plane ring (sized from the
+ *   scaled pixel_bytes) and k_ycc_to_rgb_mixed runs from there. */
+HVC_API int hvc_jpeg_mixed_scaled_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int scale_denom,
+                                         size_t align, hvc_jpeg_info *infos, hvc_jpeg_info *scaled, int *status,
+                                         size_t *pixel_offsets, size_t *total_bytes);
+HVC_API int hvc_decode_frames_mixed_scaled(hvc_ctx *ctx, const int16_t *coefs, const size_t *coef_offsets,
+                                           const hvc_jpeg_info *infos, int n_frames, int scale_denom, uint8_t *pixels,
+                                           const size_t *pixel_offsets, int where);
+HVC_API int hvc_jpeg_decode_batch_mixed_scaled(hvc_ctx *ctx, const uint8_t *const *jpegs, const size_t *sizes, int n_files,
+                                               int threads, size_t chunk_bytes, int scale_denom, const hvc_jpeg_info *infos,
+                                               int *status, const size_t *pixel_offsets, uint8_t *pixels, size_t pixel_cap,
+                                               int where, hvc_batch_stats *stats);
+HVC_API int hvc_jpeg_mixed_scaled_rgb_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int scale_denom,
+                                             int layout, size_t align, size_t row_align, hvc_jpeg_info *infos,
+                                             hvc_jpeg_info *scaled, int *status, size_t *rgb_offsets,
+                                             size_t *rgb_row_strides, size_t *total_bytes);
+HVC_API int hvc_jpeg_decode_batch_mixed_scaled_rgb(hvc_ctx *ctx, const uint8_t *const *jpegs, const size_t *sizes, int n_files,
+                                                   int threads, size_t chunk_bytes, int scale_denom, const hvc_jpeg_info *infos,
+                                                   int *status, const size_t *rgb_offsets, const size_t *rgb_row_strides,
+                                                   uint8_t *rgb, size_t rgb_cap, int layout, int where, hvc_batch_stats *stats);
 
 /* K5 (no counterpart in the reference): what a benchmark or a pipeline produced, said in
  * 64 bits per record without bringing the records back.  For r < n_records

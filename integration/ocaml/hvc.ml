@@ -872,6 +872,54 @@ let jpeg_decode_batch_mixed_rgb =
     @-> ptr size_t @-> ptr char @-> size_t @-> int @-> int @-> ptr Batch_stats.t @-> returning int)
 ;;
 
+(* mixed batches at 1/2, 1/4, 1/8 size (scale_denom 1 = the full-size call of the same name without "_scaled").
+   int hvc_jpeg_mixed_scaled_layout(jpegs, sizes, n_files, scale_denom, align, infos, scaled, status, pixel_offsets,
+                                    total_bytes)                                                                host only *)
+let jpeg_mixed_scaled_layout =
+  foreign
+    "hvc_jpeg_mixed_scaled_layout"
+    (ptr string @-> ptr size_t @-> int @-> int @-> size_t @-> ptr Jpeg_info.t @-> ptr Jpeg_info.t @-> ptr int
+    @-> ptr size_t @-> ptr size_t @-> returning int)
+;;
+
+(* int hvc_decode_frames_mixed_scaled(ctx, coefs, coef_offsets, infos, n_frames, scale_denom, pixels, pixel_offsets, where) *)
+let decode_frames_mixed_scaled =
+  foreign
+    "hvc_decode_frames_mixed_scaled"
+    ~release_runtime_lock:true
+    (ctx @-> ptr int16_t @-> ptr size_t @-> ptr Jpeg_info.t @-> int @-> int @-> ptr char @-> ptr size_t @-> int
+    @-> returning int)
+;;
+
+(* int hvc_jpeg_decode_batch_mixed_scaled(ctx, jpegs, sizes, n_files, threads, chunk_bytes, scale_denom, infos, status,
+                                          pixel_offsets, pixels, pixel_cap, where, stats) *)
+let jpeg_decode_batch_mixed_scaled =
+  foreign
+    "hvc_jpeg_decode_batch_mixed_scaled"
+    ~release_runtime_lock:true
+    (ctx @-> ptr string @-> ptr size_t @-> int @-> int @-> size_t @-> int @-> ptr Jpeg_info.t @-> ptr int @-> ptr size_t
+    @-> ptr char @-> size_t @-> int @-> ptr Batch_stats.t @-> returning int)
+;;
+
+(* int hvc_jpeg_mixed_scaled_rgb_layout(jpegs, sizes, n_files, scale_denom, layout, align, row_align, infos, scaled, status,
+                                        rgb_offsets, rgb_row_strides, total_bytes)                              host only *)
+let jpeg_mixed_scaled_rgb_layout =
+  foreign
+    "hvc_jpeg_mixed_scaled_rgb_layout"
+    (ptr string @-> ptr size_t @-> int @-> int @-> int @-> size_t @-> size_t @-> ptr Jpeg_info.t @-> ptr Jpeg_info.t
+    @-> ptr int @-> ptr size_t @-> ptr size_t @-> ptr size_t @-> returning int)
+;;
+
+(* int hvc_jpeg_decode_batch_mixed_scaled_rgb(ctx, jpegs, sizes, n_files, threads, chunk_bytes, scale_denom, infos, status,
+                                              rgb_offsets, rgb_row_strides, rgb, rgb_cap, layout, where, stats) *)
+let jpeg_decode_batch_mixed_scaled_rgb =
+  foreign
+    "hvc_jpeg_decode_batch_mixed_scaled_rgb"
+    ~release_runtime_lock:true
+    (ctx @-> ptr string @-> ptr size_t @-> int @-> int @-> size_t @-> int @-> ptr Jpeg_info.t @-> ptr int @-> ptr size_t
+    @-> ptr size_t @-> ptr char @-> size_t @-> int @-> int @-> ptr Batch_stats.t @-> returning int)
+;;
+
 (* int hvc_jpeg_encode_rgb(ctx, rgb, rgb_row_stride, layout, width, height, chroma, quality, out, cap, out_len) *)
 let jpeg_encode_rgb =
   foreign

@@ -7,10 +7,12 @@
     python -m video_coding_amd model decode frame IN.jpg OUT.ppm -rgb       the RGB image as a binary PPM (P6)
     python -m video_coding_amd model decode frame IN.jpg OUT -scale 2|4|8   at reduced size: the cropped scaled planes (with -rgb: the PPM)
     python -m video_coding_amd model encode frame IN.ppm WxH OUT.jpg -rgb   from a binary PPM of that size
-    python -m video_coding_amd model decode frames OUT_DIR IN1.jpg IN2.jpg ... [-restart-markers] [-threads 8] [-rgb]
+    python -m video_coding_amd model decode frames OUT_DIR IN1.jpg IN2.jpg ... [-restart-markers] [-threads 8] [-rgb] [-scale 2|4|8]
                                                       files of any sizes, samplings and tables in ONE mixed batch call
                                                       (hvc_jpeg_decode_batch_mixed): OUT_DIR/<name>.yuv as `decode frame` writes it;
                                                       -rgb (hvc_jpeg_decode_batch_mixed_rgb): OUT_DIR/<name>.ppm as `decode frame -rgb`
+                                                      -scale (hvc_jpeg_decode_batch_mixed_scaled / _scaled_rgb): either as
+                                                      `decode frame -scale` writes it
                                                       (an extension: JFIF colour conversion, hvc_jpeg_decode_rgb / _encode_rgb)
     python -m video_coding_amd oyuv compare {max-difference,mean-difference,mean-square-error,psnr}
                                             {y,u,v,yuv} FILE-1 FILE-2 WxH [-format 420]
@@ -126,13 +128,16 @@ def model_decode_frame(a):
 
 
 def model_decode_frames_rgb(a, datas):
-    """... through one hvc_jpeg_decode_batch_mixed_rgb call: OUT_DIR/<name>.ppm each"""
+    """... through one hvc_jpeg_decode_batch_mixed_rgb (-scale: _mixed_scaled_rgb) call: OUT_DIR/<name>.ppm each"""
     import os
     ctx = hvc.Context(a.device)
     try:
         if a.restart_markers:
             ctx.set_restart_markers(True)
-        results = ctx.jpeg_decode_batch_mixed_rgb(datas, threads=a.threads)
+        if a.scale == 1:
+            results = ctx.jpeg_decode_batch_mixed_rgb(datas, threads=a.threads)
+        else:
+            results = ctx.jpeg_decode_batch_mixed_scaled_rgb(datas, a.scale, threads=a.threads)
     finally:
         ctx.close()
     os.makedirs(a.out_dir, exist_ok=True)
@@ -157,13 +162,16 @@ def model_decode_frames(a):
     datas = [open(p, "rb").read() for p in a.bits]
     if a.rgb:
         return model_decode_frames_rgb(a, datas)
-    lay = hvc.jpeg_mixed_layout(datas)
+    lay = hvc.jpeg_mixed_layout(datas) if a.scale == 1 else hvc.jpeg_mixed_scaled_layout(datas, a.scale)
     pixels = np.zeros(max(lay.total_bytes, 8), dtype=np.uint8)
     ctx = hvc.Context(a.device)
     try:
         if a.restart_markers:
             ctx.set_restart_markers(True)
-        results = ctx.jpeg_decode_batch_mixed(datas, threads=a.threads, layout=lay, pixels=pixels)
+        if a.scale == 1:
+            results = ctx.jpeg_decode_batch_mixed(datas, threads=a.threads, layout=lay, pixels=pixels)
+        else:
+            results = ctx.jpeg_decode_batch_mixed_scaled(datas, a.scale, threads=a.threads, layout=lay, pixels=pixels)
     finally:
         ctx.close()
     os.makedirs(a.out_dir, exist_ok=True)
@@ -173,7 +181,9 @@ def model_decode_frames(a):
         if status == 0:
             off = lay.pixel_offsets[f]
             try:
-                out = hvc.jpeg_get_yuv_frame(info, pixels[off:off + info.pixel_bytes])
+                rec = pixels[off:off + info.pixel_bytes]
+                # (-scale: every component's crop to its scaled actual size, as `decode frame -scale` writes it)
+                out = hvc.jpeg_get_yuv_frame(info, rec) if a.scale == 1 else hvc.jpeg_get_cropped_planes(info, rec)
             except hvc.HvcError as e:   # (planes Frame.of_planes has no name for)
                 status = e.code
         if out is None:
@@ -472,6 +482,8 @@ def parser():
     p.add_argument("-restart-markers", dest="restart_markers", action="store_true")
     p.add_argument("-threads", type=int, default=8)
     p.add_argument("-rgb", action="store_true", help="write every RGB image as a binary PPM (hvc_jpeg_decode_batch_mixed_rgb)")
+    p.add_argument("-scale", type=int, default=1, choices=[1, 2, 4, 8],
+                   help="decode the set at 1/2, 1/4 or 1/8 size (hvc_jpeg_decode_batch_mixed_scaled / _scaled_rgb)")
     p.set_defaults(fn=model_decode_frames)
     enc = model.add_parser("encode").add_subparsers(dest="what", required=True)
     p = enc.add_parser("frame")

@@ -997,6 +997,11 @@ int hvc_decode_frames_mixed(hvc_ctx *c, const int16_t *coefs, const size_t *coef
                             uint8_t *pixels, const size_t *pixel_offsets, int where) try {
     return decode_frames_mixed_impl(c, coefs, coef_offsets, infos, n_frames, pixels, pixel_offsets, where);
 } HVC_ABI_CATCH
+// ... at 1/2, 1/4, 1/8 size through k_decode_mixed_scaled (scale_denom = 1: hvc_decode_frames_mixed itself)
+int hvc_decode_frames_mixed_scaled(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
+                                   int scale_denom, uint8_t *pixels, const size_t *pixel_offsets, int where) try {
+    return decode_frames_mixed_impl(c, coefs, coef_offsets, infos, n_frames, pixels, pixel_offsets, where, scale_denom);
+} HVC_ABI_CATCH
 // ... and on to RGB images through k_ycc_to_rgb_mixed: the planes stay in context scratch
 int hvc_decode_frames_mixed_rgb(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
                                 uint8_t *rgb, const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where) try {

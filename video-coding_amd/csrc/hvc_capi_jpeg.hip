@@ -183,27 +183,6 @@ int hvc_jpeg_decode_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info
 // ---------------------------------------------------------------------------
 // Decoding at reduced size (include/hvc_jpeg.h): the geometry, one file to planes, one file to RGB, a batch
 
-void scaled_info(const hvc_jpeg_info &in, int n, hvc_jpeg_info &out) {
-    const hvc_jpeg_info src = in; // (in and out may be one object)
-    auto up = [n](int x) { return (int)(((long long)x * n + 7) / 8); };
-    out = src;
-    out.width = up(src.width);
-    out.height = up(src.height);
-    size_t at = 0;
-    for (int i = 0; i < src.n_comp && i < 4; i++) {
-        hvc_jpeg_component &k = out.comp[i];
-        k.actual_width = up(src.comp[i].actual_width);
-        k.actual_height = up(src.comp[i].actual_height);
-        k.decoded_width = src.comp[i].decoded_width / 8 * n;
-        k.decoded_height = src.comp[i].decoded_height / 8 * n;
-        hvc_component &l = out.layout[i];
-        l.stride = l.blocks_w > 0 ? (size_t)l.blocks_w * n : 0;
-        l.plane_offset = at;
-        if (l.blocks_w > 0 && l.blocks_h > 0) at += (size_t)l.blocks_w * n * (size_t)l.blocks_h * n;
-    }
-    out.pixel_bytes = at;
-}
-
 int hvc_jpeg_scaled_info(const hvc_jpeg_info *info, int scale_denom, hvc_jpeg_info *out) try {
     const int N = scaled_side(scale_denom);
     if (!info || !out || !N || info->n_comp < 0 || info->n_comp > 4) return HVC_E_INVALID_ARG;
@@ -550,6 +529,44 @@ int hvc_jpeg_decode_batch_mixed(hvc_ctx *c, const uint8_t *const *jpegs, const s
                                 uint8_t *pixels, size_t pixel_cap, int where, hvc_batch_stats *stats) try {
     return decode_batch_mixed_impl(c, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, pixel_offsets, pixels, pixel_cap,
                                    where, stats);
+} HVC_ABI_CATCH
+
+// ... at 1/2, 1/4, 1/8 size: the layout of the scaled records and the same pipeline with k_decode_mixed_scaled as its block
+// stage; scale_denom = 1 is the full-size entry point itself
+int hvc_jpeg_mixed_scaled_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int scale_denom, size_t align,
+                                 hvc_jpeg_info *infos, hvc_jpeg_info *scaled, int *status, size_t *pixel_offsets, size_t *total_bytes) try {
+    return hvc::mixed_scaled_layout(jpegs, sizes, n_files, scale_denom, align, infos, scaled, status, pixel_offsets, total_bytes);
+} HVC_ABI_CATCH
+
+int hvc_jpeg_decode_batch_mixed_scaled(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads,
+                                       size_t chunk_bytes, int scale_denom, const hvc_jpeg_info *infos, int *status,
+                                       const size_t *pixel_offsets, uint8_t *pixels, size_t pixel_cap, int where, hvc_batch_stats *stats) try {
+    if (!scaled_side(scale_denom)) return HVC_E_INVALID_ARG;
+    MixedForm form;
+    form.scale_denom = scale_denom;
+    return decode_batch_mixed_impl(c, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, pixel_offsets, pixels, pixel_cap,
+                                   where, stats, form);
+} HVC_ABI_CATCH
+
+int hvc_jpeg_mixed_scaled_rgb_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int scale_denom, int layout,
+                                     size_t align, size_t row_align, hvc_jpeg_info *infos, hvc_jpeg_info *scaled, int *status,
+                                     size_t *rgb_offsets, size_t *rgb_row_strides, size_t *total_bytes) try {
+    return hvc::mixed_scaled_rgb_layout(jpegs, sizes, n_files, scale_denom, layout, align, row_align, infos, scaled, status, rgb_offsets,
+                                        rgb_row_strides, total_bytes);
+} HVC_ABI_CATCH
+
+int hvc_jpeg_decode_batch_mixed_scaled_rgb(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads,
+                                           size_t chunk_bytes, int scale_denom, const hvc_jpeg_info *infos, int *status,
+                                           const size_t *rgb_offsets, const size_t *rgb_row_strides, uint8_t *rgb, size_t rgb_cap,
+                                           int layout, int where, hvc_batch_stats *stats) try {
+    if (!scaled_side(scale_denom) || !rgb_offsets) return HVC_E_INVALID_ARG;
+    if (layout != HVC_RGB_INTERLEAVED && layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
+    MixedForm form;
+    form.rgb_offsets = rgb_offsets;
+    form.rgb_row_strides = rgb_row_strides;
+    form.layout = layout;
+    form.scale_denom = scale_denom;
+    return decode_batch_mixed_impl(c, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, rgb_offsets, rgb, rgb_cap, where, stats, form);
 } HVC_ABI_CATCH
 
 // ... to RGB images: where every file's image goes (host only: hvc_mixed_rgb_plan.cpp), and the pipeline with the colour pass

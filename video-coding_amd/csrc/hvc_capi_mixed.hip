@@ -4,6 +4,8 @@
 // worker pool of hvc_jpeg_decode_batch; what it cuts the batch by is bytes, not frames.  The RGB forms (hvc_yuv_to_rgb_mixed,
 // hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed_rgb) put one launch of k_ycc_to_rgb_mixed (hvc_mixed_rgb.hip) behind
 // the planes, from the host plan of hvc_mixed_rgb_plan.cpp.
+// The reduced-size forms (hvc_decode_frames_mixed_scaled, hvc_jpeg_decode_batch_mixed_scaled, _scaled_rgb) are the same code with the
+// plan built for N = 8 / scale_denom samples per block side and k_decode_mixed_scaled (hvc_mixed_scaled.hip) as the block stage.
 #include "hvc_batch.h"
 #include "hvc_mixed.h"
 #include "hvc_mixed_rgb.h"
@@ -114,17 +116,28 @@ int reserve_mixed_fix_list(hvc_ctx *c, size_t entries) {
 }
 
 // The block stage of a plan on DEVICE memory, enqueued on c->stream.  The caller has called wide_total_begin for the call
-// this launch belongs to.
-int mixed_launch_plan(hvc_ctx *c, const hvc::MixedPlan &plan, const int16_t *d_coefs, uint8_t *d_pixels, bool profile) {
+// this launch belongs to.  n = 4, 2, 1: a plan built for the scaled block stage with d_pixels as its pix_addr
+// (k_decode_mixed_scaled: no fix-up list, the call's first launch clears the total its int64 branch adds to).
+int mixed_launch_plan(hvc_ctx *c, const hvc::MixedPlan &plan, const int16_t *d_coefs, uint8_t *d_pixels, bool profile, int n = 8) {
     int r;
     if (plan.map.empty()) return HVC_OK; // no block at all: nothing to launch
-    if (((uintptr_t)d_coefs & 15) || ((uintptr_t)d_pixels & 7)) return HVC_E_ALIGNMENT;
-    if ((r = reserve_mixed_fix_list(c, plan.map.size() * HVC_MIXED_UNIT))) return r;
+    if (((uintptr_t)d_coefs & 15) || (n == 8 && ((uintptr_t)d_pixels & 7))) return HVC_E_ALIGNMENT;
+    if (n == 8 && (r = reserve_mixed_fix_list(c, plan.map.size() * HVC_MIXED_UNIT))) return r;
     hvc::MixedParams P;
     std::memset(&P, 0, sizeof P);
     if ((r = upload_plan(c, plan, P))) return r;
     P.coefs = d_coefs;
     P.pixels = d_pixels;
+    if (n != 8) {
+        P.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count + 2);
+        if (!c->wide_total_started) HIPCHK(c, hipMemsetAsync(P.wide_total, 0, sizeof *P.wide_total, c->stream));
+        c->wide_total_started = true;
+        const int slot = (int)(c->k_calls % HVC_PROF_RING);
+        const hipError_t e = hvc::launch_decode_mixed_scaled(P, n, c->stream, profile ? c->k0[slot] : nullptr, profile ? c->k1[slot] : nullptr);
+        if (e != hipSuccess) return fail_hip(c, e);
+        if (profile) c->k_calls++;
+        return HVC_OK;
+    }
     P.all_wide = c->decode_kernel == 2;
     fix_assign(c, P);
     const int slot = (int)(c->k_calls % HVC_PROF_RING);
@@ -140,27 +153,29 @@ int mixed_launch_plan(hvc_ctx *c, const hvc::MixedPlan &plan, const int16_t *d_c
 
 // ... of the listed frames: frames = indices into infos / the offset arrays (nullptr: 0 .. n_list - 1)
 int mixed_launch(hvc_ctx *c, const int16_t *d_coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, const int *frames,
-                 int n_list, uint8_t *d_pixels, const size_t *pixel_offsets, bool profile) {
+                 int n_list, uint8_t *d_pixels, const size_t *pixel_offsets, bool profile, int n = 8) {
     hvc::MixedPlan plan;
-    const int r = hvc::mixed_plan_build(infos, coef_offsets, pixel_offsets, frames, n_list, plan);
-    return r ? r : mixed_launch_plan(c, plan, d_coefs, d_pixels, profile);
+    const int r = hvc::mixed_plan_build(infos, coef_offsets, pixel_offsets, frames, n_list, plan, n, (uintptr_t)d_pixels);
+    return r ? r : mixed_launch_plan(c, plan, d_coefs, d_pixels, profile, n);
 }
 
-// what a frame's records cover: elements of coefficients, bytes of pixels (0: no block)
-void frame_spans(const hvc_jpeg_info &fi, size_t &coef_span, size_t &pixel_span) {
+// what a frame's records cover: elements of coefficients, bytes of pixels (0: no block); n samples per block side
+void frame_spans(const hvc_jpeg_info &fi, size_t &coef_span, size_t &pixel_span, int n = 8) {
     coef_span = pixel_span = 0;
     for (int i = 0; i < fi.n_comp && i < 4; i++) {
         const hvc_component &k = fi.layout[i];
         if (k.blocks_w <= 0 || k.blocks_h <= 0) continue;
         coef_span = std::max(coef_span, k.coef_offset + (size_t)k.blocks_w * k.blocks_h * 64);
-        pixel_span = std::max(pixel_span, k.plane_offset + ((size_t)k.blocks_h * 8 - 1) * k.stride + (size_t)k.blocks_w * 8);
+        pixel_span = std::max(pixel_span, k.plane_offset + ((size_t)k.blocks_h * n - 1) * k.stride + (size_t)k.blocks_w * n);
     }
 }
 
 // The tight placement of a set's records in device scratch, each on 64 bytes: d_coef (int16 elements) / d_pix (bytes) per
 // frame, ptot = the bytes of all pixel records; coefs != nullptr (host memory): uploaded to c->d_in in that placement.
+// pix_addr (the scaled block stage, n < 8; may be nullptr): where the caller's pixel record f starts -- its d_pix keeps that
+// address modulo 64, so that the planes take the dword or byte stores they would take in the caller's own placement.
 int stage_coefs(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
-                std::vector<size_t> &d_coef, std::vector<size_t> &d_pix, size_t &ptot) {
+                std::vector<size_t> &d_coef, std::vector<size_t> &d_pix, size_t &ptot, int n = 8, const uintptr_t *pix_addr = nullptr) {
     d_coef.assign((size_t)n_frames, 0);
     d_pix.assign((size_t)n_frames, 0);
     std::vector<size_t> cspan((size_t)n_frames);
@@ -168,11 +183,12 @@ int stage_coefs(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, co
     ptot = 0;
     for (int f = 0; f < n_frames; f++) {
         size_t ps;
-        frame_spans(infos[f], cspan[(size_t)f], ps);
+        frame_spans(infos[f], cspan[(size_t)f], ps, n);
+        const size_t shift = pix_addr ? (size_t)(pix_addr[f] & 63) : 0;
         d_coef[(size_t)f] = ctot;
-        d_pix[(size_t)f] = ptot;
+        d_pix[(size_t)f] = ptot + shift;
         ctot += (cspan[(size_t)f] + 63) & ~(size_t)63;
-        ptot += (ps + 63) & ~(size_t)63;
+        ptot += (shift + ps + 63) & ~(size_t)63;
     }
     if (!coefs) return HVC_OK;
     const int r = grow(c, &c->d_in, &c->in_cap, ctot * sizeof(int16_t));
@@ -215,8 +231,9 @@ size_t stage_offsets(const size_t *offsets, const std::vector<size_t> &spans, st
 
 // behind hvc_decode_frames_mixed (hvc_capi.hip)
 int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
-                             uint8_t *pixels, const size_t *pixel_offsets, int where) {
-    if (!c || n_frames < 0 || (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE)) return HVC_E_INVALID_ARG;
+                             uint8_t *pixels, const size_t *pixel_offsets, int where, int scale_denom) {
+    const int N = scaled_side(scale_denom);
+    if (!c || !N || n_frames < 0 || (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE)) return HVC_E_INVALID_ARG;
     if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (the RTL arithmetic has no mixed form, as it has no scaled one)
     if (n_frames == 0) return HVC_OK;
     if (!infos || !coef_offsets || !pixel_offsets) return HVC_E_INVALID_ARG;
@@ -225,22 +242,25 @@ int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coe
     int r;
     {
         hvc::MixedPlan plan; // the caller's own offsets: checked for either kind of memory, launched on for device memory
-        if ((r = hvc::mixed_plan_build(infos, coef_offsets, pixel_offsets, nullptr, n_frames, plan))) return r;
+        if ((r = hvc::mixed_plan_build(infos, coef_offsets, pixel_offsets, nullptr, n_frames, plan, N, (uintptr_t)pixels))) return r;
         if (plan.map.empty()) return HVC_OK; // (a set without a block needs no memory)
         if (!coefs || !pixels) return HVC_E_INVALID_ARG;
         if (where == HVC_MEM_DEVICE) {
             wide_total_begin(c);
-            return mixed_launch_plan(c, plan, coefs, pixels, c->profiling);
+            return mixed_launch_plan(c, plan, coefs, pixels, c->profiling, N);
         }
     }
     // host memory: the frames' records one after another in c->d_in / c->d_out (whole 128-byte blocks: every alignment rule
     // holds), each plane's bytes copied back by themselves -- what the kernels wrote, never the caller's padding
     std::vector<size_t> d_coef, d_pix;
+    std::vector<uintptr_t> h_pix; // (scaled: where the caller's records start)
+    if (N != 8)
+        for (int f = 0; f < n_frames; f++) h_pix.push_back((uintptr_t)pixels + pixel_offsets[f]);
     size_t ptot = 0;
-    if ((r = stage_coefs(c, coefs, coef_offsets, infos, n_frames, d_coef, d_pix, ptot))) return r;
+    if ((r = stage_coefs(c, coefs, coef_offsets, infos, n_frames, d_coef, d_pix, ptot, N, N != 8 ? h_pix.data() : nullptr))) return r;
     if ((r = grow(c, &c->d_out, &c->out_cap, ptot))) return r;
     wide_total_begin(c);
-    if ((r = mixed_launch(c, (const int16_t *)c->d_in, d_coef.data(), infos, nullptr, n_frames, (uint8_t *)c->d_out, d_pix.data(), false))) {
+    if ((r = mixed_launch(c, (const int16_t *)c->d_in, d_coef.data(), infos, nullptr, n_frames, (uint8_t *)c->d_out, d_pix.data(), false, N))) {
         (void)hipStreamSynchronize(c->stream);
         return r;
     }
@@ -248,7 +268,7 @@ int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coe
         for (int i = 0; i < infos[f].n_comp; i++) {
             const hvc_component &k = infos[f].layout[i];
             if (k.blocks_w <= 0 || k.blocks_h <= 0) continue;
-            const size_t row = (size_t)k.blocks_w * 8, rows = (size_t)k.blocks_h * 8;
+            const size_t row = (size_t)k.blocks_w * N, rows = (size_t)k.blocks_h * N;
             uint8_t *dst = pixels + pixel_offsets[f] + k.plane_offset;
             const uint8_t *src = (const uint8_t *)c->d_out + d_pix[(size_t)f] + k.plane_offset;
             if (k.stride == row)
@@ -373,7 +393,8 @@ int decode_frames_mixed_rgb_impl(hvc_ctx *c, const int16_t *coefs, const size_t 
 // decode_batch_impl (hvc_capi_jpeg.hip) -- with chunks cut by the bytes of their coefficient records, a plan per chunk, and a
 // status per file: a file that fails keeps its slot in the chunk's ring buffer and is left out of the chunk's plan.
 // form.rgb(): a file's record in `pixels` is its RGB image; the chunk's planes go to a device slot of their own ring and
-// k_ycc_to_rgb_mixed follows k_decode_mixed on the compute stream.
+// k_ycc_to_rgb_mixed follows k_decode_mixed on the compute stream.  form.scale_denom = 2, 4, 8: the same pipeline with the
+// scaled infos describing every output and k_decode_mixed_scaled as the block stage; full-size planes exist nowhere.
 // (behind hvc_jpeg_decode_batch_mixed and hvc_jpeg_decode_batch_mixed_rgb, hvc_capi_jpeg.hip)
 int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads,
                             size_t chunk_bytes, const hvc_jpeg_info *infos, int *status, const size_t *pixel_offsets,
@@ -381,8 +402,19 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     if (!c || !jpegs || !sizes || !infos || !status || !pixel_offsets || n_files < 0) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG;
+    const int N = scaled_side(form.scale_denom);
+    if (!N) return HVC_E_INVALID_ARG;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_files == 0) return HVC_OK;
+    // what describes a file's OUTPUT (its planes, its image's size): its info, or the scaled form of it -- blocks, tables and
+    // coefficient offsets are the same in both
+    std::vector<hvc_jpeg_info> scaled;
+    if (N != 8) {
+        scaled.resize((size_t)n_files);
+        for (int f = 0; f < n_files; f++)
+            if (status[f] == HVC_OK && infos[f].n_comp >= 0 && infos[f].n_comp <= 4) scaled_info(infos[f], N, scaled[(size_t)f]);
+    }
+    const hvc_jpeg_info *const oinfos = N != 8 ? scaled.data() : infos;
     if (chunk_bytes == 0) chunk_bytes = (size_t)64 << 20;
     if (threads < 1) threads = 1;
     if (threads > 256) threads = 256;
@@ -404,7 +436,7 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     bool need_pixels = false;
     for (int f = 0; f < n_files; f++) {
         if (status[f] != HVC_OK) continue;
-        const hvc_jpeg_info &fi = infos[f];
+        const hvc_jpeg_info &fi = infos[f], &oi = oinfos[f];
         if (!jpegs[f] || fi.n_comp < 0 || fi.n_comp > 4) return HVC_E_INVALID_ARG;
         size_t &ob = out_bytes[(size_t)f];
         if (form.rgb()) {
@@ -412,14 +444,14 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
                 status[f] = HVC_E_INVALID_ARG;
                 continue;
             }
-            if (fi.width < 0 || fi.height < 0) return HVC_E_INVALID_ARG;
-            const size_t tight = hvc::mixed_rgb_row_bytes(form.layout, fi.width);
+            if (oi.width < 0 || oi.height < 0) return HVC_E_INVALID_ARG;
+            const size_t tight = hvc::mixed_rgb_row_bytes(form.layout, oi.width);
             const size_t rs = form.rgb_row_strides && form.rgb_row_strides[f] ? form.rgb_row_strides[f] : tight;
             if (rs < tight) return HVC_E_INVALID_ARG;
-            ob = hvc::mixed_rgb_span(form.layout, fi.width, fi.height, rs);
+            ob = hvc::mixed_rgb_span(form.layout, oi.width, oi.height, rs);
         } else {
-            ob = fi.pixel_bytes;
-            if (ob && (pixel_offsets[f] & 7)) return HVC_E_ALIGNMENT;
+            ob = oi.pixel_bytes;
+            if (N == 8 && ob && (pixel_offsets[f] & 7)) return HVC_E_ALIGNMENT; // (scaled planes: any offset)
         }
         if (ob) {
             if (pixel_offsets[f] > pixel_cap || ob > pixel_cap - pixel_offsets[f]) return HVC_E_INVALID_ARG;
@@ -440,7 +472,7 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
         }
         if (form.rgb()) {
             plane_rel[(size_t)f] = k.plane_bytes;
-            k.plane_bytes += (fi.pixel_bytes + 63) & ~(size_t)63;
+            k.plane_bytes += (oinfos[f].pixel_bytes + 63) & ~(size_t)63;
         }
         k.coef_bytes += cb;
         k.count++;
@@ -516,14 +548,14 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
         [&](int, int slot) {
             uint8_t *dst = out ? out : (uint8_t *)c->d_oring[slot];
             if (!form.rgb())
-                return mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), infos, ok.data(), (int)ok.size(), dst, dst_off, c->profiling);
+                return mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), oinfos, ok.data(), (int)ok.size(), dst, dst_off, c->profiling, N);
             // the planes into the slot of their own ring, the colour pass from there to where the planes would have gone
             uint8_t *planes = (uint8_t *)c->d_pring[slot];
             hvc::MixedRgbPlan cplan;
-            int rc = hvc::mixed_rgb_plan_build(infos, plane_rel.data(), dst_off, form.rgb_row_strides, form.layout, ok.data(), (int)ok.size(),
-                                               (uintptr_t)planes, (uintptr_t)dst, true, cplan);
-            if (!rc) rc = mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), infos, ok.data(), (int)ok.size(), planes,
-                                       plane_rel.data(), c->profiling);
+            int rc = hvc::mixed_rgb_plan_build(oinfos, plane_rel.data(), dst_off, form.rgb_row_strides, form.layout, ok.data(), (int)ok.size(),
+                                               (uintptr_t)planes, (uintptr_t)dst, true, cplan, N);
+            if (!rc) rc = mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), oinfos, ok.data(), (int)ok.size(), planes,
+                                       plane_rel.data(), c->profiling, N);
             if (!rc) rc = mixed_rgb_launch_plan(c, cplan, form.layout, planes, dst, false);
             return rc;
         },
@@ -545,15 +577,16 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
                 const int f = take[(size_t)t];
                 if (status[f] != HVC_OK || !out_bytes[(size_t)f]) continue;
                 const size_t lo = pix_rel[(size_t)f], hi = lo + out_bytes[(size_t)f];
-                if (form.rgb() && form.rgb_row_strides && form.rgb_row_strides[f] > hvc::mixed_rgb_row_bytes(form.layout, infos[f].width)) {
+                if (form.rgb() && form.rgb_row_strides && form.rgb_row_strides[f] > hvc::mixed_rgb_row_bytes(form.layout, oinfos[f].width)) {
                     flush(); // rows with room between them: the image row by row, the caller's bytes between rows stay
                     if (he == hipSuccess)
                         he = hipMemcpy2DAsync(pixels + ch.pix_lo + lo, form.rgb_row_strides[f], dst + lo, form.rgb_row_strides[f],
-                                              hvc::mixed_rgb_row_bytes(form.layout, infos[f].width),
-                                              hvc::mixed_rgb_rows(form.layout, infos[f].height), hipMemcpyDeviceToHost, c->stream);
+                                              hvc::mixed_rgb_row_bytes(form.layout, oinfos[f].width),
+                                              hvc::mixed_rgb_rows(form.layout, oinfos[f].height), hipMemcpyDeviceToHost, c->stream);
                     continue;
                 }
-                const bool joins = run_hi > run_lo && t == prev_t + 1 && lo >= run_hi && lo - run_hi < 4096;
+                // (scaled records lie at any offset: there the runs join only where they touch, and no byte between records is written)
+                const bool joins = run_hi > run_lo && t == prev_t + 1 && lo >= run_hi && lo - run_hi < (N == 8 ? (size_t)4096 : (size_t)1);
                 if (!joins) flush();
                 if (run_hi == run_lo) run_lo = lo;
                 run_hi = hi;

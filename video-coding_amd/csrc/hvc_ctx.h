@@ -8,7 +8,8 @@
 //   hvc_capi_files.hip   the GPU Huffman coder's entry point and the batch pipelines that write files
 //   hvc_rgb.hip          the RGB colour pass (kernels and launches; its entry points live with their families in the files above)
 //   hvc_capi_mixed.hip   batches of frames / files of different geometry and tables (hvc_decode_frames_mixed, hvc_jpeg_decode_batch_mixed,
-//                        and their RGB forms: hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed_rgb)
+//                        their RGB forms: hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed_rgb, and the
+//                        reduced-size forms hvc_decode_frames_mixed_scaled, hvc_jpeg_decode_batch_mixed_scaled, _scaled_rgb)
 //   hvc_capi_async.hip   pinned host memory and the slots of the asynchronous seam (hvc_decode_frames_submit / hvc_wait)
 #ifndef HVC_CTX_H
 #define HVC_CTX_H
@@ -37,6 +38,7 @@
 #include "hvc_hardcaml.h"
 #include "hvc_huff.h"
 #include "hvc_kernels.h"
+#include "hvc_mixed_plan.h"
 #include "hvc_pool.h"
 #include "hvc_scaled_spec.h"
 
@@ -416,11 +418,7 @@ int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
 int decode_frames_scaled_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
                               const hvc_component *comps, int n_comp, int n_frames, int scale_denom, uint8_t *pixels, size_t pixel_fs,
                               int where, const DecodeOpts &o);
-inline int scaled_side(int scale_denom) { // N = 8 / scale_denom, 0 for anything but 1, 2, 4, 8
-    return scale_denom == 1 || scale_denom == 2 || scale_denom == 4 || scale_denom == 8 ? 8 / scale_denom : 0;
-}
-// hvc_jpeg_scaled_info's arithmetic (hvc_capi_jpeg.hip); n = scaled_side(scale_denom) != 0
-void scaled_info(const hvc_jpeg_info &in, int n, hvc_jpeg_info &out);
+// scaled_side(scale_denom) and scaled_info (hvc_jpeg_scaled_info's arithmetic): hvc_mixed_plan.h, plain C++ for the host plans too
 int encode_frames_impl(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const uint16_t *qtabs, int n_qtabs,
                        const hvc_component *comps, int n_comp, int n_frames, int16_t *coefs, size_t coef_fs, int where,
                        const EncodeOpts &o);
@@ -503,13 +501,16 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
 // hvc_capi_mixed.hip: frames / files of different geometry and tables in one call (behind hvc_decode_frames_mixed in hvc_capi.hip
 // and hvc_jpeg_decode_batch_mixed in hvc_capi_jpeg.hip)
 int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
-                             uint8_t *pixels, const size_t *pixel_offsets, int where);
+                             uint8_t *pixels, const size_t *pixel_offsets, int where, int scale_denom = 1);
 // What the files of a mixed batch become.  Default: their padded planes, at pixel_offsets.  rgb_offsets set: RGB images
 // there (`pixels` / `pixel_cap` are the RGB buffer), rows rgb_row_strides[f] apart (nullptr: tight), through k_ycc_to_rgb_mixed
 // behind every chunk's block stage; the planes stay in a device ring.
+// scale_denom 2, 4, 8: the planes (or the planes the images are made of) are those of hvc_jpeg_scaled_info, through
+// k_decode_mixed_scaled; `infos` stay the FULL-size infos, the pipeline derives the scaled ones.
 struct MixedForm {
     const size_t *rgb_offsets = nullptr, *rgb_row_strides = nullptr;
     int layout = 0;
+    int scale_denom = 1;
     bool rgb() const { return rgb_offsets != nullptr; }
 };
 int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads, size_t chunk_bytes,

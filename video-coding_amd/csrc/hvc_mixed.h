@@ -1,5 +1,5 @@
-// hvc_mixed.h -- parameter block and launcher of the mixed block stage (internal): k_decode_mixed / k_decode_mixed_wide,
-// hvc_mixed.hip.  The tables come from hvc_mixed_plan.h, in device memory.
+// hvc_mixed.h -- parameter block and launchers of the mixed block stage (internal): k_decode_mixed / k_decode_mixed_wide,
+// hvc_mixed.hip, and k_decode_mixed_scaled, hvc_mixed_scaled.hip.  The tables come from hvc_mixed_plan.h, in device memory.
 #ifndef HVC_MIXED_H
 #define HVC_MIXED_H
 
@@ -27,6 +27,10 @@ struct MixedParams {
 
 // k_decode_mixed over all units, then k_decode_mixed_wide over the list; k0 / k1 (optional) bracket the first
 hipError_t launch_decode_mixed(const MixedParams &P, hipStream_t s, hipEvent_t k0 = nullptr, hipEvent_t k1 = nullptr);
+
+// k_decode_mixed_scaled<n> (hvc_mixed_scaled.hip), n = 4, 2, 1, over all units of a plan built for n: of the fix-up fields
+// it takes wide_total alone (cleared by the caller; the blocks of the int64 branch are added to it)
+hipError_t launch_decode_mixed_scaled(const MixedParams &P, int n, hipStream_t s, hipEvent_t k0 = nullptr, hipEvent_t k1 = nullptr);
 
 } // namespace hvc
 #endif

@@ -1,4 +1,5 @@
-// hvc_mixed_plan.cpp -- host plan of a mixed batch: mixed_layout behind hvc_jpeg_mixed_layout (where every file's pixel record goes) and the
+// hvc_mixed_plan.cpp -- host plan of a mixed batch: mixed_layout / mixed_scaled_layout behind hvc_jpeg_mixed_layout / hvc_jpeg_mixed_scaled_layout
+// (where every file's pixel record goes) and the
 // descriptor builder behind hvc_decode_frames_mixed / hvc_jpeg_decode_batch_mixed (hvc_mixed_plan.h).  Plain C++ (no HIP),
 // usable without a GPU.
 #include <cstring>
@@ -38,11 +39,12 @@ void table_entry(const uint16_t *q, MixedTableK &t) {
 } // namespace
 
 int mixed_plan_build(const hvc_jpeg_info *infos, const size_t *coef_offsets, const size_t *pixel_offsets, const int *frames,
-                     int n_list, MixedPlan &plan) {
+                     int n_list, MixedPlan &plan, int n, uintptr_t pix_addr) {
     plan.planes.clear();
     plan.tables.clear();
     plan.map.clear();
     plan.blocks = 0;
+    if (n != 8 && n != 4 && n != 2 && n != 1) return HVC_E_INVALID_ARG;
     if (n_list < 0 || (n_list > 0 && (!infos || !coef_offsets || !pixel_offsets))) return HVC_E_INVALID_ARG;
     std::vector<const uint16_t *> table_src; // the content behind plan.tables[k]
     unsigned long long units = 0;
@@ -55,9 +57,9 @@ int mixed_plan_build(const hvc_jpeg_info *infos, const size_t *coef_offsets, con
             const hvc_component &c = fi.layout[i];
             if (c.blocks_w < 0 || c.blocks_h < 0) return HVC_E_INVALID_ARG;
             if (c.blocks_w == 0 || c.blocks_h == 0) continue; // the model's empty plane: no descriptor, no unit
-            if (c.qtab < 0 || c.qtab >= fi.n_qtabs || c.stride < (size_t)c.blocks_w * 8) return HVC_E_INVALID_ARG;
+            if (c.qtab < 0 || c.qtab >= fi.n_qtabs || c.stride < (size_t)c.blocks_w * (size_t)n) return HVC_E_INVALID_ARG;
             const size_t coef_base = coef_offsets[f] + c.coef_offset, pix_base = pixel_offsets[f] + c.plane_offset;
-            if ((coef_base & 7) || (pix_base & 7) || (c.stride & 7)) return HVC_E_ALIGNMENT;
+            if ((coef_base & 7) || (n == 8 && ((pix_base & 7) || (c.stride & 7)))) return HVC_E_ALIGNMENT;
             const unsigned long long nblk = (unsigned long long)c.blocks_w * (unsigned long long)c.blocks_h;
             if (nblk * (unsigned long long)c.blocks_w >= (1ull << 32) || nblk >= (1ull << 31)) return HVC_E_TOO_LARGE;
             const unsigned long long nu = (nblk + HVC_MIXED_UNIT - 1) / HVC_MIXED_UNIT;
@@ -81,6 +83,7 @@ int mixed_plan_build(const hvc_jpeg_info *infos, const size_t *coef_offsets, con
             p.magic = c.blocks_w == 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)c.blocks_w - 1) / (unsigned)c.blocks_w);
             p.table = t;
             p.unit0 = (unsigned)units;
+            p.dwords = n != 8 && (((unsigned long long)pix_addr + pix_base) | c.stride) % 4 == 0;
             plan.map.insert(plan.map.end(), (size_t)nu, (unsigned)plan.planes.size());
             plan.planes.push_back(p);
             units += nu;
@@ -103,6 +106,34 @@ int mixed_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, 
         pixel_offsets[f] = start;
         if (status[f] != HVC_OK || infos[f].pixel_bytes == 0) continue; // takes no room
         end = start + infos[f].pixel_bytes;
+    }
+    *total_bytes = end;
+    return HVC_OK;
+}
+
+// hvc_jpeg_mixed_scaled_layout (include/hvc_jpeg.h): scale_denom = 1 is mixed_layout itself, with scaled[f] == infos[f]
+int mixed_scaled_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int scale_denom, size_t align, hvc_jpeg_info *infos,
+                        hvc_jpeg_info *scaled, int *status, size_t *pixel_offsets, size_t *total_bytes) {
+    const int n = scaled_side(scale_denom);
+    if (!n || !scaled) return HVC_E_INVALID_ARG;
+    if (n == 8) {
+        const int r = mixed_layout(jpegs, sizes, n_files, align, infos, status, pixel_offsets, total_bytes);
+        for (int f = 0; !r && f < n_files; f++)
+            if (status[f] == HVC_OK) scaled[f] = infos[f];
+        return r;
+    }
+    if (!jpegs || !sizes || !infos || !status || !pixel_offsets || !total_bytes || n_files < 0) return HVC_E_INVALID_ARG;
+    if (align == 0) align = 256;
+    if (align < 8 || (align & (align - 1))) return HVC_E_INVALID_ARG;
+    size_t end = 0; // the end of the last record placed
+    for (int f = 0; f < n_files; f++) {
+        status[f] = jpegs[f] ? hvc_jpeg_read_header(jpegs[f], sizes[f], &infos[f]) : HVC_E_INVALID_ARG;
+        const size_t start = (end + align - 1) & ~(align - 1);
+        pixel_offsets[f] = start;
+        if (status[f] != HVC_OK) continue; // takes no room
+        scaled_info(infos[f], n, scaled[f]);
+        if (scaled[f].pixel_bytes == 0) continue;
+        end = start + scaled[f].pixel_bytes;
     }
     *total_bytes = end;
     return HVC_OK;

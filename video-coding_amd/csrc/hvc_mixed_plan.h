@@ -21,6 +21,32 @@
 #define HVC_MIXED_GROUP 4      /* units per workgroup */
 #define HVC_MIXED_MAX_UNITS (1u << 26) /* a fix-list id is unit * 64 + lane in 32 bits */
 
+// N = 8 / scale_denom, 0 for anything but 1, 2, 4, 8
+inline int scaled_side(int scale_denom) {
+    return scale_denom == 1 || scale_denom == 2 || scale_denom == 4 || scale_denom == 8 ? 8 / scale_denom : 0;
+}
+// hvc_jpeg_scaled_info's arithmetic; n = scaled_side(scale_denom) != 0
+inline void scaled_info(const hvc_jpeg_info &in, int n, hvc_jpeg_info &out) {
+    const hvc_jpeg_info src = in; // (in and out may be one object)
+    auto up = [n](int x) { return (int)(((long long)x * n + 7) / 8); };
+    out = src;
+    out.width = up(src.width);
+    out.height = up(src.height);
+    size_t at = 0;
+    for (int i = 0; i < src.n_comp && i < 4; i++) {
+        hvc_jpeg_component &k = out.comp[i];
+        k.actual_width = up(src.comp[i].actual_width);
+        k.actual_height = up(src.comp[i].actual_height);
+        k.decoded_width = src.comp[i].decoded_width / 8 * n;
+        k.decoded_height = src.comp[i].decoded_height / 8 * n;
+        hvc_component &l = out.layout[i];
+        l.stride = l.blocks_w > 0 ? (size_t)l.blocks_w * n : 0;
+        l.plane_offset = at;
+        if (l.blocks_w > 0 && l.blocks_h > 0) at += (size_t)l.blocks_w * n * (size_t)l.blocks_h * n;
+    }
+    out.pixel_bytes = at;
+}
+
 namespace hvc {
 
 struct MixedPlaneK {            // 48 bytes
@@ -31,7 +57,7 @@ struct MixedPlaneK {            // 48 bytes
     unsigned magic;               // ceil(2^32 / bw), 0 for bw == 1 (CompK::magic)
     int table;                    // index of its table entry
     unsigned unit0;               // its first work unit
-    unsigned pad;
+    unsigned dwords;              // (the scaled block stage) its first byte and its stride are multiples of 4: dword stores
 };
 
 struct MixedTableK {            // 400 bytes
@@ -56,12 +82,19 @@ struct MixedPlan {
 // HVC_E_ALIGNMENT: a coefficient plane not on 16 bytes, a pixel plane or stride not on 8; HVC_E_INVALID_ARG: a negative
 // size, a table index outside the frame's tables, a stride below the row; HVC_E_TOO_LARGE: a plane beyond CompK's index
 // range or more than HVC_MIXED_MAX_UNITS units.
+// n = 4, 2, 1: the plan of the SCALED block stage (k_decode_mixed_scaled, hvc_mixed_scaled.hip) -- units, map and tables as
+// for n = 8; .plane_offset / .stride describe planes of blocks_w * n x blocks_h * n samples, which may lie at any offset
+// with any stride >= blocks_w * n (the 16-byte rule of the coefficient planes stays); a descriptor's `dwords` is set when
+// pix_addr (the address pixel offsets count from: only its low bits matter) + pix_base and the stride are multiples of 4.
 int mixed_plan_build(const hvc_jpeg_info *infos, const size_t *coef_offsets, const size_t *pixel_offsets, const int *frames,
-                     int n_list, MixedPlan &plan);
+                     int n_list, MixedPlan &plan, int n = 8, uintptr_t pix_addr = 0);
 
 // hvc_jpeg_mixed_layout of include/hvc_jpeg.h
 int mixed_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, size_t align, hvc_jpeg_info *infos, int *status,
                  size_t *pixel_offsets, size_t *total_bytes);
+// hvc_jpeg_mixed_scaled_layout of include/hvc_jpeg.h
+int mixed_scaled_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int scale_denom, size_t align, hvc_jpeg_info *infos,
+                        hvc_jpeg_info *scaled, int *status, size_t *pixel_offsets, size_t *total_bytes);
 
 } // namespace hvc
 #endif

@@ -27,12 +27,13 @@ namespace hvc {
 
 int mixed_rgb_plan_build(const hvc_jpeg_info *infos, const size_t *yuv_offsets, const size_t *rgb_offsets, const size_t *rgb_row_strides,
                          int layout, const int *frames, int n_list, uintptr_t yuv_addr, uintptr_t rgb_addr, bool decoded,
-                         MixedRgbPlan &plan) {
+                         MixedRgbPlan &plan, int n) {
     plan.images.clear();
     plan.map.clear();
     plan.frame.clear();
     plan.lanes = 0;
     if (layout != HVC_RGB_INTERLEAVED && layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
+    if (n != 8 && n != 4 && n != 2 && n != 1) return HVC_E_INVALID_ARG;
     if (n_list < 0 || (n_list > 0 && (!infos || !yuv_offsets || !rgb_offsets))) return HVC_E_INVALID_ARG;
     unsigned long long units = 0;
     for (int l = 0; l < n_list; l++) {
@@ -54,7 +55,7 @@ int mixed_rgb_plan_build(const hvc_jpeg_info *infos, const size_t *yuv_offsets, 
             const int pw = i ? k.cw : k.w, ph = i ? k.ch : k.h;
             if (c.stride < (size_t)pw) return HVC_E_INVALID_ARG;
             if (c.blocks_w < 0 || c.blocks_h < 0 || (decoded && (c.blocks_w == 0 || c.blocks_h == 0))) return HVC_E_INVALID_ARG;
-            if (c.blocks_w > 0 && c.blocks_h > 0 && (pw > 8 * (long long)c.blocks_w || ph > 8 * (long long)c.blocks_h)) return HVC_E_INVALID_ARG;
+            if (c.blocks_w > 0 && c.blocks_h > 0 && (pw > n * (long long)c.blocks_w || ph > n * (long long)c.blocks_h)) return HVC_E_INVALID_ARG;
             const unsigned long long base = (unsigned long long)yuv_offsets[f] + c.plane_offset;
             (i == 0 ? k.y_base : i == 1 ? k.cb_base : k.cr_base) = base;
             (i == 0 ? k.y_stride : i == 1 ? k.cb_stride : k.cr_stride) = c.stride;
@@ -109,6 +110,42 @@ int mixed_rgb_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_fil
         const size_t row = (mixed_rgb_row_bytes(layout, infos[f].width) + row_align - 1) & ~(row_align - 1);
         rgb_row_strides[f] = row;
         const size_t bytes = row * mixed_rgb_rows(layout, infos[f].height);
+        if (bytes == 0) continue;
+        end = start + bytes;
+    }
+    *total_bytes = end;
+    return HVC_OK;
+}
+
+// hvc_jpeg_mixed_scaled_rgb_layout (include/hvc_jpeg.h): scale_denom = 1 is mixed_rgb_layout itself, with scaled[f] == infos[f]
+int mixed_scaled_rgb_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int scale_denom, int layout, size_t align,
+                            size_t row_align, hvc_jpeg_info *infos, hvc_jpeg_info *scaled, int *status, size_t *rgb_offsets,
+                            size_t *rgb_row_strides, size_t *total_bytes) {
+    const int n = scaled_side(scale_denom);
+    if (!n || !scaled) return HVC_E_INVALID_ARG;
+    if (n == 8) {
+        const int r = mixed_rgb_layout(jpegs, sizes, n_files, layout, align, row_align, infos, status, rgb_offsets, rgb_row_strides, total_bytes);
+        for (int f = 0; !r && f < n_files; f++)
+            if (status[f] == HVC_OK) scaled[f] = infos[f];
+        return r;
+    }
+    if (!jpegs || !sizes || !infos || !status || !rgb_offsets || !rgb_row_strides || !total_bytes || n_files < 0) return HVC_E_INVALID_ARG;
+    if (layout != HVC_RGB_INTERLEAVED && layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
+    if (align == 0) align = 256;
+    if (row_align == 0) row_align = 1;
+    if ((align & (align - 1)) || (row_align & (row_align - 1))) return HVC_E_INVALID_ARG;
+    size_t end = 0; // the end of the last record placed
+    for (int f = 0; f < n_files; f++) {
+        status[f] = jpegs[f] ? hvc_jpeg_read_header(jpegs[f], sizes[f], &infos[f]) : HVC_E_INVALID_ARG;
+        if (status[f] == HVC_OK && !rgb_sampling_of(infos[f])) status[f] = HVC_E_INVALID_ARG; // as hvc_jpeg_decode_scaled_rgb answers it
+        const size_t start = (end + align - 1) & ~(align - 1);
+        rgb_offsets[f] = start;
+        rgb_row_strides[f] = 0;
+        if (status[f] != HVC_OK) continue; // takes no room
+        scaled_info(infos[f], n, scaled[f]);
+        const size_t row = (mixed_rgb_row_bytes(layout, scaled[f].width) + row_align - 1) & ~(row_align - 1);
+        rgb_row_strides[f] = row;
+        const size_t bytes = row * mixed_rgb_rows(layout, scaled[f].height);
         if (bytes == 0) continue;
         end = start + bytes;
     }

@@ -65,11 +65,17 @@ inline size_t mixed_rgb_span(int layout, int width, int height, size_t row_strid
 // (a side above 2^24, lanes * groups >= 2^32) or more than HVC_MIXED_MAX_UNITS units.
 int mixed_rgb_plan_build(const hvc_jpeg_info *infos, const size_t *yuv_offsets, const size_t *rgb_offsets, const size_t *rgb_row_strides,
                          int layout, const int *frames, int n_list, uintptr_t yuv_addr, uintptr_t rgb_addr, bool decoded,
-                         MixedRgbPlan &plan);
+                         MixedRgbPlan &plan, int n = 8);
+// (n = 4, 2, 1: infos[] are SCALED infos, their planes what the scaled block stage writes: a window must lie inside
+// n * blocks_w x n * blocks_h)
 
 // hvc_jpeg_mixed_rgb_layout of include/hvc_jpeg.h
 int mixed_rgb_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int layout, size_t align, size_t row_align,
                      hvc_jpeg_info *infos, int *status, size_t *rgb_offsets, size_t *rgb_row_strides, size_t *total_bytes);
+// hvc_jpeg_mixed_scaled_rgb_layout of include/hvc_jpeg.h
+int mixed_scaled_rgb_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int scale_denom, int layout, size_t align,
+                            size_t row_align, hvc_jpeg_info *infos, hvc_jpeg_info *scaled, int *status, size_t *rgb_offsets,
+                            size_t *rgb_row_strides, size_t *total_bytes);
 
 } // namespace hvc
 #endif

@@ -40,6 +40,8 @@ SYMBOLS = [
     "hvc_jpeg_decode_batch_scaled",
     "hvc_jpeg_mixed_layout", "hvc_decode_frames_mixed", "hvc_jpeg_decode_batch_mixed",
     "hvc_jpeg_mixed_rgb_layout", "hvc_yuv_to_rgb_mixed", "hvc_decode_frames_mixed_rgb", "hvc_jpeg_decode_batch_mixed_rgb",
+    "hvc_jpeg_mixed_scaled_layout", "hvc_decode_frames_mixed_scaled", "hvc_jpeg_decode_batch_mixed_scaled",
+    "hvc_jpeg_mixed_scaled_rgb_layout", "hvc_jpeg_decode_batch_mixed_scaled_rgb",
 ]
 HVC_RGB = {"interleaved": 0, "planar": 1}  # enum hvc_rgb_layout: [H, W, 3] / [3, H, W]
 HVC_YUV_400 = 400   # luma only, beside 420 / 422 / 444
@@ -265,6 +267,15 @@ def lib():
                                                   C.POINTER(BatchStats)]
         L.hvc_jpeg_mixed_rgb_layout.argtypes = [C.POINTER(vp), C.POINTER(sz), i, i, sz, sz, ip, C.POINTER(i), C.POINTER(sz), C.POINTER(sz),
                                                 C.POINTER(sz)]
+        L.hvc_jpeg_mixed_scaled_layout.argtypes = [C.POINTER(vp), C.POINTER(sz), i, i, sz, ip, ip, C.POINTER(i), C.POINTER(sz),
+                                                   C.POINTER(sz)]
+        L.hvc_decode_frames_mixed_scaled.argtypes = [vp, vp, C.POINTER(sz), ip, i, i, vp, C.POINTER(sz), i]
+        L.hvc_jpeg_decode_batch_mixed_scaled.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, i, ip, C.POINTER(i), C.POINTER(sz),
+                                                         vp, sz, i, C.POINTER(BatchStats)]
+        L.hvc_jpeg_mixed_scaled_rgb_layout.argtypes = [C.POINTER(vp), C.POINTER(sz), i, i, i, sz, sz, ip, ip, C.POINTER(i),
+                                                       C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+        L.hvc_jpeg_decode_batch_mixed_scaled_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, i, ip, C.POINTER(i),
+                                                             C.POINTER(sz), C.POINTER(sz), vp, sz, i, i, C.POINTER(BatchStats)]
         L.hvc_yuv_to_rgb_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), C.POINTER(sz), i, i]
         L.hvc_decode_frames_mixed_rgb.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), C.POINTER(sz), i, i]
         L.hvc_jpeg_decode_batch_mixed_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, ip, C.POINTER(i), C.POINTER(sz),
@@ -533,6 +544,66 @@ class MixedRgbLayout:
 def jpeg_mixed_rgb_layout(jpegs, layout="interleaved", align=0, row_align=0):
     """headers of a list of files (bytes) -> MixedRgbLayout; align / row_align: powers of two, 0 = 256 / 1 (tight rows)"""
     return MixedRgbLayout(jpegs, layout, align, row_align)
+
+
+class MixedScaledLayout:
+    """what hvc_jpeg_mixed_scaled_layout makes of a list of files: infos (FULL-size: the batch call's input), scaled (the infos
+    of the output records), status, pixel_offsets and total_bytes -- the size of the buffer that holds every good file's
+    scaled pixel record"""
+
+    def __init__(self, jpegs, scale_denom, align=0):
+        n = len(jpegs)
+        self.jpegs = list(jpegs)
+        self.scale_denom = int(scale_denom)
+        self.ptrs = (C.c_void_p * n)(*[C.cast(C.c_char_p(j), C.c_void_p) for j in self.jpegs])
+        self.sizes = (C.c_size_t * n)(*[len(j) for j in self.jpegs])
+        self.infos = (JpegInfo * n)()
+        self.scaled = (JpegInfo * n)()
+        self.status = (C.c_int * n)()
+        self.pixel_offsets = (C.c_size_t * n)()
+        total = C.c_size_t(0)
+        _chk(lib().hvc_jpeg_mixed_scaled_layout(self.ptrs, self.sizes, n, self.scale_denom, align, self.infos, self.scaled, self.status,
+                                                self.pixel_offsets, C.byref(total)), "hvc_jpeg_mixed_scaled_layout")
+        self.total_bytes = total.value
+
+    def __len__(self):
+        return len(self.jpegs)
+
+
+def jpeg_mixed_scaled_layout(jpegs, scale_denom, align=0):
+    """headers of a list of files (bytes) -> MixedScaledLayout; scale_denom 1, 2, 4, 8; align: a power of two >= 8, 0 = 256"""
+    return MixedScaledLayout(jpegs, scale_denom, align)
+
+
+class MixedScaledRgbLayout:
+    """what hvc_jpeg_mixed_scaled_rgb_layout makes of a list of files: infos (FULL-size), scaled (image f is scaled[f].width x
+    .height), status, rgb_offsets, rgb_row_strides and total_bytes"""
+
+    def __init__(self, jpegs, scale_denom, layout="interleaved", align=0, row_align=0):
+        n = len(jpegs)
+        self.jpegs = list(jpegs)
+        self.scale_denom = int(scale_denom)
+        self.layout = _rgb_layout(layout)
+        self.ptrs = (C.c_void_p * n)(*[C.cast(C.c_char_p(j), C.c_void_p) for j in self.jpegs])
+        self.sizes = (C.c_size_t * n)(*[len(j) for j in self.jpegs])
+        self.infos = (JpegInfo * n)()
+        self.scaled = (JpegInfo * n)()
+        self.status = (C.c_int * n)()
+        self.rgb_offsets = (C.c_size_t * n)()
+        self.rgb_row_strides = (C.c_size_t * n)()
+        total = C.c_size_t(0)
+        _chk(lib().hvc_jpeg_mixed_scaled_rgb_layout(self.ptrs, self.sizes, n, self.scale_denom, self.layout, align, row_align, self.infos,
+                                                    self.scaled, self.status, self.rgb_offsets, self.rgb_row_strides, C.byref(total)),
+             "hvc_jpeg_mixed_scaled_rgb_layout")
+        self.total_bytes = total.value
+
+    def __len__(self):
+        return len(self.jpegs)
+
+
+def jpeg_mixed_scaled_rgb_layout(jpegs, scale_denom, layout="interleaved", align=0, row_align=0):
+    """headers of a list of files (bytes) -> MixedScaledRgbLayout; align / row_align: powers of two, 0 = 256 / 1 (tight rows)"""
+    return MixedScaledRgbLayout(jpegs, scale_denom, layout, align, row_align)
 
 
 def rgb_view(buf, offset, row_stride, width, height, layout):
@@ -1129,6 +1200,76 @@ class Context:
         out = []
         for f in range(n):
             info = lay.infos[f] if lay.status[f] == 0 else None
+            image = None
+            if status[f] == 0 and info is not None and info.width > 0 and info.height > 0:
+                image = rgb_view(rgb, lay.rgb_offsets[f], lay.rgb_row_strides[f], info.width, info.height, lay.layout)
+            out.append((status[f], info, image))
+        return out
+
+    def decode_frames_mixed_scaled(self, coefs, coef_offsets, infos, scale_denom, pixels, pixel_offsets):
+        """hvc_decode_frames_mixed_scaled: decode_frames_mixed at 1 / scale_denom; infos[f].layout's plane_offset / stride place
+        planes of blocks_w * N x blocks_h * N samples, N = 8 / scale_denom (any offset, any stride >= blocks_w * N)."""
+        ca, w1 = _addr(coefs)
+        pa, w2 = _addr(pixels)
+        assert w1 == w2, "coefs and pixels must live in the same memory space"
+        n = len(infos)
+        arr = infos if isinstance(infos, C.Array) else (JpegInfo * n)(*infos)
+        _chk(lib().hvc_decode_frames_mixed_scaled(self._h, ca, _size_array(coef_offsets, n), arr, n, scale_denom, pa,
+                                                  _size_array(pixel_offsets, n), w1), "hvc_decode_frames_mixed_scaled")
+
+    def jpeg_decode_batch_mixed_scaled(self, jpegs, scale_denom, threads=8, chunk_bytes=0, device=False, layout=None, pixels=None):
+        """Files of any sizes, samplings and tables at 1 / scale_denom in one call.  Returns one (status, scaled info, planes) per
+        file, as jpeg_decode_batch_mixed does at full size; planes = views of the scaled padded planes inside ONE buffer.
+        layout / pixels: a MixedScaledLayout made before and a buffer of layout.total_bytes (default: made here, zero-filled)."""
+        lay = layout if layout is not None else MixedScaledLayout(jpegs, scale_denom)
+        n = len(lay)
+        if pixels is None:
+            if device:
+                import torch
+                pixels = torch.zeros(max(lay.total_bytes, 8), dtype=torch.uint8, device="cuda")
+            else:
+                pixels = np.zeros(max(lay.total_bytes, 8), dtype=np.uint8)
+        pa, where = _addr(pixels)
+        cap = pixels.numel() if hasattr(pixels, "numel") else pixels.size
+        st = BatchStats()
+        status = (C.c_int * n)(*lay.status)
+        _chk(lib().hvc_jpeg_decode_batch_mixed_scaled(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, scale_denom, lay.infos,
+                                                      status, lay.pixel_offsets, pa, cap, where, C.byref(st)),
+             "hvc_jpeg_decode_batch_mixed_scaled")
+        self.last_batch_stats = st
+        out = []
+        for f in range(n):
+            if lay.status[f] != 0:
+                out.append((status[f], None, None))
+                continue
+            info, off = lay.scaled[f], lay.pixel_offsets[f]
+            out.append((status[f], info, info.planes(pixels[off:off + info.pixel_bytes])))
+        return out
+
+    def jpeg_decode_batch_mixed_scaled_rgb(self, jpegs, scale_denom, threads=8, chunk_bytes=0, device=False, layout="interleaved",
+                                           row_align=0, rgb_layout=None, rgb=None):
+        """Files of any sizes, samplings and tables to RGB images at 1 / scale_denom in one call.  Returns one (status, scaled
+        info, image) per file, as jpeg_decode_batch_mixed_rgb does at full size.  rgb_layout / rgb: a MixedScaledRgbLayout made
+        before and a buffer of rgb_layout.total_bytes (default: made here, zero-filled)."""
+        lay = rgb_layout if rgb_layout is not None else MixedScaledRgbLayout(jpegs, scale_denom, layout, 0, row_align)
+        n = len(lay)
+        if rgb is None:
+            if device:
+                import torch
+                rgb = torch.zeros(max(lay.total_bytes, 8), dtype=torch.uint8, device="cuda")
+            else:
+                rgb = np.zeros(max(lay.total_bytes, 8), dtype=np.uint8)
+        ra, where = _addr(rgb)
+        cap = rgb.numel() if hasattr(rgb, "numel") else rgb.size
+        st = BatchStats()
+        status = (C.c_int * n)(*lay.status)
+        _chk(lib().hvc_jpeg_decode_batch_mixed_scaled_rgb(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, scale_denom, lay.infos,
+                                                          status, lay.rgb_offsets, lay.rgb_row_strides, ra, cap, lay.layout, where,
+                                                          C.byref(st)), "hvc_jpeg_decode_batch_mixed_scaled_rgb")
+        self.last_batch_stats = st
+        out = []
+        for f in range(n):
+            info = lay.scaled[f] if lay.status[f] == 0 else None
             image = None
             if status[f] == 0 and info is not None and info.width > 0 and info.height > 0:
                 image = rgb_view(rgb, lay.rgb_offsets[f], lay.rgb_row_strides[f], info.width, info.height, lay.layout)
