@@ -750,7 +750,8 @@ HVC_API int hvc_jpeg_decode_batch_scaled(hvc_ctx *ctx, const uint8_t *const *jpe
  * full-size padded planes, or RGB images (below: hvc_jpeg_mixed_rgb_layout, hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb,
  * hvc_jpeg_decode_batch_mixed_rgb, whose colour pass k_ycc_to_rgb_mixed takes its decomposition from device memory the same
  * way), or either at 1/2, 1/4, 1/8 size (further below: the *_mixed_scaled* entry points, block stage k_decode_mixed_scaled);
- * there is no 4:4:4-planar form, the host Huffman reader only, no side list of DCs beyond int16.  With
+ * there is no 4:4:4-planar form and no side list of DCs beyond int16; the files are read by the host Huffman reader or, with
+ * hvc_set_mixed_reader(ctx, HVC_READER_GPU), by the mixed GPU Huffman reader (further below).  With
  * HVC_ARITH_HARDCAML set the ctx functions return HVC_E_INVALID_ARG; hvc_set_decode_kernel(ctx, 2) sends every block
  * through the int64 arithmetic, other selections are ignored; hvc_last_wide_blocks counts the blocks that took it. */
 
@@ -785,6 +786,35 @@ HVC_API int hvc_jpeg_decode_batch_mixed(hvc_ctx *ctx, const uint8_t *const *jpeg
                                         int threads, size_t chunk_bytes, const hvc_jpeg_info *infos, int *status,
                                         const size_t *pixel_offsets, uint8_t *pixels, size_t pixel_cap, int where,
                                         hvc_batch_stats *stats);
+
+/* Which Huffman reader the mixed batch calls use (hvc_jpeg_decode_batch_mixed, _mixed_rgb, _mixed_scaled, _mixed_scaled_rgb).
+ * HVC_READER_HOST (the default): host threads read the files, every launch and byte as described above.
+ * HVC_READER_GPU: the mixed GPU Huffman reader (csrc/hvc_hdec_mixed.hip) -- hvc_jpeg_entropy_decode_gpu's self-synchronising
+ *   reader with everything a lane needs about its file (geometry, place of its segment and of its record, table set) in a
+ *   per-file descriptor in device memory, so that one chain of launches serves files of any size, sampling and tables, and
+ *   with one verdict per FILE.  Host threads only unstuff the segments into a pinned ring; the reader writes the
+ *   coefficient records into the device slot the block stage reads; chunks are cut as above.  A file is handed back to the
+ *   host reader when its verdict is not clean (whatever the model raises on, a DC beyond int16, a stream that ends early or
+ *   does not fall into step within the reader's fixed number of rounds), when the reader cannot take it (no 1..3 components,
+ *   more than 16 blocks per MCU, an MCU grid that leaves a plane, sizes beyond 32-bit indices, tables that are no prefix
+ *   code, a table set or segment that does not fit its chunk's slot), or when it carries restart intervals while
+ *   hvc_set_restart_markers is on.  The handed-back files go through the host-reader pipeline in one pass behind the GPU
+ *   chunks: results and error codes are the host reader's, byte for byte -- which reader ran never changes a result.
+ * hvc_last_mixed_reader_files: of the files that reached a reader in the last mixed batch call, how many records the GPU
+ *   reader produced and how many the host reader read (either pointer may be NULL). */
+#define HVC_READER_HOST 0
+#define HVC_READER_GPU 1
+HVC_API int hvc_set_mixed_reader(hvc_ctx *ctx, int which);
+HVC_API int hvc_get_mixed_reader(const hvc_ctx *ctx, int *which);
+HVC_API int hvc_last_mixed_reader_files(const hvc_ctx *ctx, uint64_t *gpu_files, uint64_t *host_files);
+/* The mixed counterpart of hvc_jpeg_entropy_decode_gpu: the files' coefficient records exactly as hvc_jpeg_entropy_decode
+ * writes them, file f's at coefs + coef_offsets[f] (int16 elements, a multiple of 8: 16 bytes; `where` says where coefs
+ * lives; coef_cap elements in all).  infos / status as hvc_jpeg_mixed_layout made them: a file whose status is not HVC_OK
+ * is skipped; status[f] receives the file's own code.  used_gpu[f] (optional) = 1 where the GPU reader produced the record;
+ * a handed-back file (see hvc_set_mixed_reader) is read by the host reader on the calling thread.  Blocking. */
+HVC_API int hvc_jpeg_entropy_decode_gpu_mixed(hvc_ctx *ctx, const uint8_t *const *jpegs, const size_t *sizes, int n_files,
+                                              const hvc_jpeg_info *infos, int *status, int16_t *coefs,
+                                              const size_t *coef_offsets, size_t coef_cap, int where, int *used_gpu);
 
 /* Mixed batches to RGB: the colour pass of the RGB section above (same definition, byte for byte what hvc_yuv_to_rgb /
  * hvc_decode_frames_rgb / hvc_jpeg_decode_rgb give for each image alone) over images of ANY size and sampling in one launch.

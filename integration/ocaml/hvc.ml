@@ -833,6 +833,26 @@ let jpeg_decode_batch_mixed =
     @-> ptr char @-> size_t @-> int @-> ptr Batch_stats.t @-> returning int)
 ;;
 
+(* who reads the files of the mixed batch calls: 0 = HVC_READER_HOST (default), 1 = HVC_READER_GPU (the mixed GPU Huffman reader).
+   int hvc_set_mixed_reader(ctx, which);  int hvc_get_mixed_reader(ctx, which);
+   int hvc_last_mixed_reader_files(ctx, gpu_files, host_files) *)
+let set_mixed_reader = foreign "hvc_set_mixed_reader" (ctx @-> int @-> returning int)
+let get_mixed_reader = foreign "hvc_get_mixed_reader" (ctx @-> ptr int @-> returning int)
+
+let last_mixed_reader_files =
+  foreign "hvc_last_mixed_reader_files" (ctx @-> ptr uint64_t @-> ptr uint64_t @-> returning int)
+;;
+
+(* int hvc_jpeg_entropy_decode_gpu_mixed(ctx, jpegs, sizes, n_files, infos, status, coefs, coef_offsets, coef_cap, where,
+                                         used_gpu) *)
+let jpeg_entropy_decode_gpu_mixed =
+  foreign
+    "hvc_jpeg_entropy_decode_gpu_mixed"
+    ~release_runtime_lock:true
+    (ctx @-> ptr string @-> ptr size_t @-> int @-> ptr Jpeg_info.t @-> ptr int @-> ptr int16_t @-> ptr size_t @-> size_t
+    @-> int @-> ptr int @-> returning int)
+;;
+
 (* mixed batches to RGB: one launch of the colour pass over images of any size and sampling.
    int hvc_jpeg_mixed_rgb_layout(jpegs, sizes, n_files, layout, align, row_align, infos, status, rgb_offsets,
                                  rgb_row_strides, total_bytes)                                                  host only *)

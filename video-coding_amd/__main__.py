@@ -7,7 +7,7 @@
     python -m video_coding_amd model decode frame IN.jpg OUT.ppm -rgb       the RGB image as a binary PPM (P6)
     python -m video_coding_amd model decode frame IN.jpg OUT -scale 2|4|8   at reduced size: the cropped scaled planes (with -rgb: the PPM)
     python -m video_coding_amd model encode frame IN.ppm WxH OUT.jpg -rgb   from a binary PPM of that size
-    python -m video_coding_amd model decode frames OUT_DIR IN1.jpg IN2.jpg ... [-restart-markers] [-threads 8] [-rgb] [-scale 2|4|8]
+    python -m video_coding_amd model decode frames OUT_DIR IN1.jpg IN2.jpg ... [-restart-markers] [-threads 8] [-rgb] [-scale 2|4|8] [-reader gpu|host]
                                                       files of any sizes, samplings and tables in ONE mixed batch call
                                                       (hvc_jpeg_decode_batch_mixed): OUT_DIR/<name>.yuv as `decode frame` writes it;
                                                       -rgb (hvc_jpeg_decode_batch_mixed_rgb): OUT_DIR/<name>.ppm as `decode frame -rgb`
@@ -134,6 +134,7 @@ def model_decode_frames_rgb(a, datas):
     try:
         if a.restart_markers:
             ctx.set_restart_markers(True)
+        ctx.set_mixed_reader(a.reader)
         if a.scale == 1:
             results = ctx.jpeg_decode_batch_mixed_rgb(datas, threads=a.threads)
         else:
@@ -168,6 +169,7 @@ def model_decode_frames(a):
     try:
         if a.restart_markers:
             ctx.set_restart_markers(True)
+        ctx.set_mixed_reader(a.reader)
         if a.scale == 1:
             results = ctx.jpeg_decode_batch_mixed(datas, threads=a.threads, layout=lay, pixels=pixels)
         else:
@@ -482,6 +484,8 @@ def parser():
     p.add_argument("-restart-markers", dest="restart_markers", action="store_true")
     p.add_argument("-threads", type=int, default=8)
     p.add_argument("-rgb", action="store_true", help="write every RGB image as a binary PPM (hvc_jpeg_decode_batch_mixed_rgb)")
+    p.add_argument("-reader", choices=["host", "gpu"], default="host",
+                   help="who reads the files' Huffman data (hvc_set_mixed_reader): host threads, or the mixed GPU reader; same files either way")
     p.add_argument("-scale", type=int, default=1, choices=[1, 2, 4, 8],
                    help="decode the set at 1/2, 1/4 or 1/8 size (hvc_jpeg_decode_batch_mixed_scaled / _scaled_rgb)")
     p.set_defaults(fn=model_decode_frames)

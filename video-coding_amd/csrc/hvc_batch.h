@@ -25,6 +25,8 @@ inline int pipeline_events(hvc_ctx *c) {
 // entropy_ms_sum, frames_per_chunk and coef_bytes).
 //   count_of(k)       items of chunk k
 //   upload_bytes(k)   bytes of h_ring[slot] to upload once chunk k is complete; 0: no copy
+//                     (called with the copy stream waiting for the slot's last kernel: a pipeline whose chunk is not
+//                     coefficients -- the mixed GPU reader's segments and descriptors -- enqueues its own copies there and returns 0)
 //   stage(k, slot)    enqueues the block stage on c->stream: an hvc_status
 //   download(k, slot) enqueues what brings the chunk home on c->stream: a hipError_t
 template <class Count, class Bytes, class Stage, class Download>

@@ -531,6 +531,32 @@ int hvc_jpeg_decode_batch_mixed(hvc_ctx *c, const uint8_t *const *jpegs, const s
                                    where, stats);
 } HVC_ABI_CATCH
 
+// who reads the files of the mixed batch calls (hvc_capi_mixed.hip, hvc_capi_mixed_reader.hip), and the last call's split
+int hvc_set_mixed_reader(hvc_ctx *c, int which) try {
+    if (!c || (which != HVC_READER_HOST && which != HVC_READER_GPU)) return HVC_E_INVALID_ARG;
+    c->mixed_reader = which;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_get_mixed_reader(const hvc_ctx *c, int *which) try {
+    if (!c || !which) return HVC_E_INVALID_ARG;
+    *which = c->mixed_reader;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_last_mixed_reader_files(const hvc_ctx *c, uint64_t *gpu_files, uint64_t *host_files) try {
+    if (!c) return HVC_E_INVALID_ARG;
+    if (gpu_files) *gpu_files = c->mixed_gpu_files;
+    if (host_files) *host_files = c->mixed_host_files;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+// the mixed counterpart of hvc_jpeg_entropy_decode_gpu: hvc_capi_mixed_reader.hip
+int hvc_jpeg_entropy_decode_gpu_mixed(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, const hvc_jpeg_info *infos,
+                                      int *status, int16_t *coefs, const size_t *coef_offsets, size_t coef_cap, int where, int *used_gpu) try {
+    return entropy_decode_gpu_mixed_impl(c, jpegs, sizes, n_files, infos, status, coefs, coef_offsets, coef_cap, where, used_gpu);
+} HVC_ABI_CATCH
+
 // ... at 1/2, 1/4, 1/8 size: the layout of the scaled records and the same pipeline with k_decode_mixed_scaled as its block
 // stage; scale_denom = 1 is the full-size entry point itself
 int hvc_jpeg_mixed_scaled_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int scale_denom, size_t align,

@@ -9,6 +9,7 @@
 #include "hvc_batch.h"
 #include "hvc_mixed.h"
 #include "hvc_mixed_rgb.h"
+#include "hvc_mixed_reader.h"
 
 namespace {
 
@@ -395,10 +396,17 @@ int decode_frames_mixed_rgb_impl(hvc_ctx *c, const int16_t *coefs, const size_t 
 // form.rgb(): a file's record in `pixels` is its RGB image; the chunk's planes go to a device slot of their own ring and
 // k_ycc_to_rgb_mixed follows k_decode_mixed on the compute stream.  form.scale_denom = 2, 4, 8: the same pipeline with the
 // scaled infos describing every output and k_decode_mixed_scaled as the block stage; full-size planes exist nowhere.
+// hvc_set_mixed_reader(HVC_READER_GPU) (and not host_reader_only): the workers only unstuff the files' segments into the pinned
+// reader ring (MixedGpuReader::prepare), the copy stream uploads them with the chunk's descriptors and table records, and the
+// mixed GPU Huffman reader writes the coefficient records into d_ring[slot] in front of the block stage, which runs over the
+// files whose verdict is clean; chunks, coef_rel and everything from the coefficient slot on are the same.  The files the
+// reader hands back are decoded by this function itself, host_reader_only, in one call once the chunks are through.
 // (behind hvc_jpeg_decode_batch_mixed and hvc_jpeg_decode_batch_mixed_rgb, hvc_capi_jpeg.hip)
 int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads,
                             size_t chunk_bytes, const hvc_jpeg_info *infos, int *status, const size_t *pixel_offsets,
-                            uint8_t *pixels, size_t pixel_cap, int where, hvc_batch_stats *stats, const MixedForm &form) {
+                            uint8_t *pixels, size_t pixel_cap, int where, hvc_batch_stats *stats, const MixedForm &form,
+                            bool host_reader_only) {
+    if (c && !host_reader_only) c->mixed_gpu_files = c->mixed_host_files = 0;
     if (!c || !jpegs || !sizes || !infos || !status || !pixel_offsets || n_files < 0) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG;
@@ -500,6 +508,21 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     if ((r = ring_ensure(c, coef_rings(c), {ring_bytes, ring_bytes}))) return r; // (a single file larger than chunk_bytes: the ring grows)
     if ((r = ring_ensure(c, out_rings(c), {oring_bytes}))) return r;
     if ((r = ring_ensure(c, plane_rings(c), {pring_bytes}))) return r;
+    // the GPU reader: which files of a chunk it hands back (known once the chunk's verdict is read), how many it read
+    const bool gpu = c->mixed_reader == HVC_READER_GPU && !host_reader_only;
+    MixedGpuReader rd; // (before the feed: pool tasks use it)
+    std::vector<char> back(gpu ? (size_t)n_files : 0, 0);
+    std::vector<int> chunk_first, chunk_count;
+    unsigned long long gpu_files = 0;
+    hipError_t gpu_upload_err = hipSuccess;
+    if (gpu) {
+        for (const Chunk &k : chunks) {
+            chunk_first.push_back(k.first);
+            chunk_count.push_back(k.count);
+        }
+        if ((r = rd.begin(c, jpegs, sizes, infos, coef_rel.data(), take, chunk_first, chunk_count))) return r;
+    }
+    auto gone = [&](int f) { return gpu && back[(size_t)f]; }; // the host reader has it: its record is not this pass's
 
     std::atomic<long long> entropy_ns{0};
     const auto wall0 = std::chrono::steady_clock::now();
@@ -515,6 +538,12 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
             const int f = take[(size_t)t], k = chunk_of[(size_t)f];
             if (!feed.wait_slot(k)) return;
             const auto t0 = std::chrono::steady_clock::now();
+            if (gpu) { // the segment into the pinned reader ring; the file's result comes with its chunk's verdict
+                rd.prepare(k, t);
+                entropy_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+                feed.report(k, 1, HVC_OK);
+                continue;
+            }
             int e;
             if (infos[f].coef_count == 0) { // no block: the file is still read as the model reads it
                 e = hvc_jpeg_entropy_decode(jpegs[f], sizes[f], &infos[f], nullptr);
@@ -539,13 +568,29 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
         [&](int k) -> size_t {
             const Chunk &ch = chunks[(size_t)k];
             ok.clear();
+            if (gpu) { // segments, descriptors, map and table records instead of coefficients (on the copy stream, as the copy would be)
+                gpu_upload_err = rd.upload(k, c->copy_stream);
+                coef_total += ch.coef_bytes;
+                return 0;
+            }
             for (int t = ch.first; t < ch.first + ch.count; t++) // (status[] of this chunk is final: its workers are done)
                 if (status[take[(size_t)t]] == HVC_OK && infos[take[(size_t)t]].coef_count) ok.push_back(take[(size_t)t]);
             if (ok.empty()) return 0;
             coef_total += ch.coef_bytes;
             return ch.coef_bytes;
         },
-        [&](int, int slot) {
+        [&](int k, int slot) {
+            if (gpu) { // the reader in front of the block stage; the chunk's good files are known from its verdict
+                if (gpu_upload_err != hipSuccess) return fail_hip(c, gpu_upload_err);
+                const Chunk &ch = chunks[(size_t)k];
+                int n_gpu = 0;
+                const int rc = rd.read(k, (int16_t *)c->d_ring[slot], c->stream, back, &n_gpu);
+                if (rc) return rc;
+                gpu_files += (unsigned long long)n_gpu;
+                for (int t = ch.first; t < ch.first + ch.count; t++)
+                    if (!back[(size_t)take[(size_t)t]] && infos[take[(size_t)t]].coef_count) ok.push_back(take[(size_t)t]);
+                if (ok.empty()) return (int)HVC_OK;
+            }
             uint8_t *dst = out ? out : (uint8_t *)c->d_oring[slot];
             if (!form.rgb())
                 return mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), oinfos, ok.data(), (int)ok.size(), dst, dst_off, c->profiling, N);
@@ -575,7 +620,7 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
             int prev_t = -2;
             for (int t = ch.first; t < ch.first + ch.count; t++) {
                 const int f = take[(size_t)t];
-                if (status[f] != HVC_OK || !out_bytes[(size_t)f]) continue;
+                if (status[f] != HVC_OK || !out_bytes[(size_t)f] || gone(f)) continue;
                 const size_t lo = pix_rel[(size_t)f], hi = lo + out_bytes[(size_t)f];
                 if (form.rgb() && form.rgb_row_strides && form.rgb_row_strides[f] > hvc::mixed_rgb_row_bytes(form.layout, oinfos[f].width)) {
                     flush(); // rows with room between them: the image row by row, the caller's bytes between rows stay
@@ -586,7 +631,9 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
                     continue;
                 }
                 // (scaled records lie at any offset: there the runs join only where they touch, and no byte between records is written)
-                const bool joins = run_hi > run_lo && t == prev_t + 1 && lo >= run_hi && lo - run_hi < (N == 8 ? (size_t)4096 : (size_t)1);
+                // (host_reader_only: the files masked out of this pass keep their room, so what lies between two of its files
+                // may be another file's record -- its runs join only where they touch)
+                const bool joins = run_hi > run_lo && t == prev_t + 1 && lo >= run_hi && lo - run_hi < (N == 8 && !host_reader_only ? (size_t)4096 : (size_t)1);
                 if (!joins) flush();
                 if (run_hi == run_lo) run_lo = lo;
                 run_hi = hi;
@@ -600,6 +647,29 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
         stats->entropy_ms_sum = (double)entropy_ns.load() * 1e-6;
         stats->frames_per_chunk = largest;
         stats->coef_bytes = coef_total;
+    }
+    if (host_reader_only) return r;
+    c->mixed_gpu_files = gpu_files;
+    c->mixed_host_files = (unsigned long long)n_take - gpu_files;
+    if (!gpu || r != HVC_OK || gpu_files == (unsigned long long)n_take) return r;
+    // The handed-back files, through this pipeline with the host reader: every other file masked out by its status.
+    std::vector<int> kept((size_t)n_files);
+    for (int f = 0; f < n_files; f++) {
+        kept[(size_t)f] = status[f];
+        if (status[f] == HVC_OK && !(chunk_of[(size_t)f] >= 0 && back[(size_t)f])) status[f] = HVC_E_INTERNAL;
+    }
+    hvc_batch_stats tail;
+    r = decode_batch_mixed_impl(c, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, pixel_offsets, pixels, pixel_cap, where, &tail,
+                                form, true);
+    for (int f = 0; f < n_files; f++)
+        if (!(kept[(size_t)f] == HVC_OK && chunk_of[(size_t)f] >= 0 && back[(size_t)f])) status[f] = kept[(size_t)f];
+    if (stats) {
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+        stats->entropy_ms_sum += tail.entropy_ms_sum;
+        stats->h2d_ms_sum += tail.h2d_ms_sum;
+        stats->kernel_ms_sum += tail.kernel_ms_sum;
+        stats->d2h_ms_sum += tail.d2h_ms_sum;
+        stats->chunks += tail.chunks;
     }
     return r;
 }

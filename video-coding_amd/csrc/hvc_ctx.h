@@ -10,6 +10,7 @@
 //   hvc_capi_mixed.hip   batches of frames / files of different geometry and tables (hvc_decode_frames_mixed, hvc_jpeg_decode_batch_mixed,
 //                        their RGB forms: hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed_rgb, and the
 //                        reduced-size forms hvc_decode_frames_mixed_scaled, hvc_jpeg_decode_batch_mixed_scaled, _scaled_rgb)
+//   hvc_capi_mixed_reader.hip  the mixed GPU Huffman reader's driver (hvc_mixed_reader.h) and hvc_jpeg_entropy_decode_gpu_mixed
 //   hvc_capi_async.hip   pinned host memory and the slots of the asynchronous seam (hvc_decode_frames_submit / hvc_wait)
 #ifndef HVC_CTX_H
 #define HVC_CTX_H
@@ -54,6 +55,8 @@ struct hvc_ctx {
     hipEvent_t k0[HVC_PROF_RING] = {}, k1[HVC_PROF_RING] = {};
     unsigned long long k_calls = 0;
     bool profiling = false;
+    int mixed_reader = HVC_READER_HOST; // hvc_set_mixed_reader: who reads the files of the mixed batch calls
+    unsigned long long mixed_gpu_files = 0, mixed_host_files = 0; // hvc_last_mixed_reader_files: the last mixed batch call's split
     bool honour_restart = false; // hvc_set_restart_markers: restart intervals honoured by the file-level entry points (an extension)
     int decode_kernel = 0; // hvc_set_decode_kernel: 0 packed (default), 1 unpacked int32, 2 int64 for every block, 3 q16
     int arith = HVC_ARITH_MODEL; // hvc_set_arithmetic: the block stage's arithmetic (HARDCAML: k_hardcaml, hvc_hardcaml.hip)
@@ -515,7 +518,11 @@ struct MixedForm {
 };
 int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads, size_t chunk_bytes,
                             const hvc_jpeg_info *infos, int *status, const size_t *pixel_offsets, uint8_t *pixels, size_t pixel_cap,
-                            int where, hvc_batch_stats *stats, const MixedForm &form = MixedForm());
+                            int where, hvc_batch_stats *stats, const MixedForm &form = MixedForm(), bool host_reader_only = false);
+// hvc_capi_mixed_reader.hip: the mixed GPU Huffman reader over one chunk on the calling thread (behind hvc_jpeg_entropy_decode_gpu_mixed
+// in hvc_capi_jpeg.hip)
+int entropy_decode_gpu_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, const hvc_jpeg_info *infos,
+                                  int *status, int16_t *coefs, const size_t *coef_offsets, size_t coef_cap, int where, int *used_gpu);
 // the colour pass alone / behind the block stage (behind hvc_yuv_to_rgb_mixed in hvc_yuv.hip, hvc_decode_frames_mixed_rgb in hvc_capi.hip)
 int yuv_to_rgb_mixed_impl(hvc_ctx *c, const uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos, int n_frames, uint8_t *rgb,
                           const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where);

@@ -39,6 +39,7 @@ SYMBOLS = [
     "hvc_jpeg_scaled_info", "hvc_decode_frames_scaled", "hvc_jpeg_decode_scaled", "hvc_jpeg_decode_scaled_rgb",
     "hvc_jpeg_decode_batch_scaled",
     "hvc_jpeg_mixed_layout", "hvc_decode_frames_mixed", "hvc_jpeg_decode_batch_mixed",
+    "hvc_set_mixed_reader", "hvc_get_mixed_reader", "hvc_last_mixed_reader_files", "hvc_jpeg_entropy_decode_gpu_mixed",
     "hvc_jpeg_mixed_rgb_layout", "hvc_yuv_to_rgb_mixed", "hvc_decode_frames_mixed_rgb", "hvc_jpeg_decode_batch_mixed_rgb",
     "hvc_jpeg_mixed_scaled_layout", "hvc_decode_frames_mixed_scaled", "hvc_jpeg_decode_batch_mixed_scaled",
     "hvc_jpeg_mixed_scaled_rgb_layout", "hvc_jpeg_decode_batch_mixed_scaled_rgb",
@@ -201,6 +202,10 @@ def lib():
         L.hvc_jpeg_entropy_decode.argtypes = [vp, sz, ip, vp]
         L.hvc_jpeg_entropy_decode_restart.argtypes = [vp, sz, ip, vp]
         L.hvc_set_restart_markers.argtypes = [vp, i]
+        L.hvc_set_mixed_reader.argtypes = [vp, i]
+        L.hvc_get_mixed_reader.argtypes = [vp, C.POINTER(i)]
+        L.hvc_last_mixed_reader_files.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.hvc_jpeg_entropy_decode_gpu_mixed.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, vp, C.POINTER(i), vp, C.POINTER(sz), sz, i, C.POINTER(i)]
         L.hvc_set_arithmetic.argtypes = [vp, i]
         L.hvc_get_arithmetic.argtypes = [vp, C.POINTER(i)]
         L.hvc_decode_frames_divergence.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
@@ -510,6 +515,18 @@ class MixedLayout:
 
     def __len__(self):
         return len(self.jpegs)
+
+
+def mixed_coef_offsets(layout):
+    """where jpeg_entropy_decode_gpu_mixed puts the coefficient record of every file of a MixedLayout: (offsets, a ctypes array
+    of int16 elements, each on a whole block; the elements of all records)"""
+    n = len(layout)
+    offs, total = (C.c_size_t * n)(), 0
+    for f in range(n):
+        offs[f] = total
+        if layout.status[f] == 0:
+            total += (layout.infos[f].coef_count + 63) // 64 * 64
+    return offs, total
 
 
 def jpeg_mixed_layout(jpegs, align=0):
@@ -1469,6 +1486,53 @@ class Context:
         _chk(lib().hvc_jpeg_entropy_decode_gpu(self._h, ptrs, sizes, n, out.ctypes.data, info.coef_count, 0, C.byref(info),
                                                C.byref(used)), "hvc_jpeg_entropy_decode_gpu")
         return info, out, used.value
+
+    MIXED_READERS = {"host": 0, "gpu": 1}
+
+    def set_mixed_reader(self, which="gpu"):
+        """hvc_set_mixed_reader: who reads the files of the mixed batch calls, "host" (the default) or "gpu" -- the mixed GPU
+        Huffman reader; which one ran never changes a result"""
+        _chk(lib().hvc_set_mixed_reader(self._h, self.MIXED_READERS[which] if isinstance(which, str) else int(which)),
+             "hvc_set_mixed_reader")
+
+    def get_mixed_reader(self):
+        v = C.c_int(-1)
+        _chk(lib().hvc_get_mixed_reader(self._h, C.byref(v)), "hvc_get_mixed_reader")
+        return {0: "host", 1: "gpu"}[v.value]
+
+    def last_mixed_reader_files(self):
+        """(gpu_files, host_files) of the last mixed batch call: the files that reached a reader, by the reader that read them"""
+        g, h = C.c_uint64(0), C.c_uint64(0)
+        _chk(lib().hvc_last_mixed_reader_files(self._h, C.byref(g), C.byref(h)), "hvc_last_mixed_reader_files")
+        return g.value, h.value
+
+    def jpeg_entropy_decode_gpu_mixed(self, files, device=False, layout=None, coefs=None):
+        """Huffman decoding of files of any geometry on the GPU (hvc_jpeg_entropy_decode_gpu_mixed).  Returns one
+        (status, info, record, used_gpu) per file: status = the file's own hvc_status, record = its coefficient record
+        (numpy int16 [coef_count]; None unless status is 0), used_gpu = 1 where the GPU reader produced it.
+        layout / coefs: a MixedLayout made before and an int16 buffer (numpy, or a torch cuda tensor: then `device` is what
+        the buffer says) of at least mixed_coef_offsets(layout)[1] elements to decode into (default: made here)."""
+        lay = layout if layout is not None else MixedLayout(files, 8)
+        n = len(lay)
+        offs, total = mixed_coef_offsets(lay)
+        status = (C.c_int * n)(*lay.status)
+        used = (C.c_int * n)()
+        if coefs is None:
+            if device:
+                import torch
+                coefs = torch.zeros(max(total, 8), dtype=torch.int16, device="cuda")
+            else:
+                coefs = np.zeros(max(total, 8), dtype=np.int16)
+        addr, where = _addr(coefs)
+        _chk(lib().hvc_jpeg_entropy_decode_gpu_mixed(self._h, lay.ptrs, lay.sizes, n, lay.infos, status, addr, offs, total, where,
+                                                     used), "hvc_jpeg_entropy_decode_gpu_mixed")
+        host = coefs.cpu().numpy() if hasattr(coefs, "cpu") else coefs
+        out = []
+        for f in range(n):
+            info = lay.infos[f] if lay.status[f] == 0 else None
+            rec = host[offs[f]:offs[f] + info.coef_count].copy() if info is not None and status[f] == 0 else None
+            out.append((status[f], info, rec, used[f]))
+        return out
 
     def _restart_slack(self, width, height):
         """what the context's restart interval adds to a file of this size at most (see restart_slack)"""
