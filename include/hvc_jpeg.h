@@ -226,8 +226,11 @@ HVC_API int hvc_set_decode_kernel(hvc_ctx *ctx, int which);
  * 4:4:4 entry points (hvc_decode_frames_yuv444, hvc_jpeg_decode_yuv444, hvc_jpeg_decode_batch_yuv444) have no RTL form:
  * under HARDCAML they return HVC_E_INVALID_ARG and leave their output untouched.  The encoder ignores the setting: it has
  * its own, hvc_set_encode_arithmetic below.
- * hvc_set_arithmetic: HVC_E_INVALID_ARG for any other value. */
-typedef enum { HVC_ARITH_MODEL = 0, HVC_ARITH_HARDCAML = 1 } hvc_arith;
+ * HVC_ARITH_LIBJPEG is libjpeg's decoder at its defaults (jidctint.c and fancy upsampling), bit for bit: the section
+ * "Bit-exact to libjpeg" below states it and says where it applies.
+ * hvc_set_arithmetic: HVC_E_INVALID_ARG for any other value.  The value 2 is NOT an arithmetic and stays refused: LIBJPEG is
+ * 3 (hvc_set_decode_kernel has a 2, and a test pins hvc_set_arithmetic(ctx, 2) as an error). */
+typedef enum { HVC_ARITH_MODEL = 0, HVC_ARITH_HARDCAML = 1, HVC_ARITH_LIBJPEG = 3 } hvc_arith;
 HVC_API int hvc_set_arithmetic(hvc_ctx *ctx, int arith);
 HVC_API int hvc_get_arithmetic(const hvc_ctx *ctx, int *arith);
 
@@ -613,7 +616,8 @@ HVC_API int hvc_jpeg_encode_batch_gpu(hvc_ctx *ctx, const uint8_t *const *frames
  *      nothing (4:4:4) -- the arithmetic of hvc_upsample420 / hvc_upsample422 -- of the top-left chroma_w x chroma_h window
  *      of the chroma planes, chroma_w = ceil(width / 2) (4:2:0, 4:2:2), chroma_h = ceil(height / 2) (4:2:0); the last column
  *      and row of THAT WINDOW are the ones repeated, and the top-left width x height of the result is used.  For even sizes
- *      this is hvc_decode_frames_yuv444's frame; odd sizes use the one extra chroma column / row the decoded plane holds;
+ *      this is hvc_decode_frames_yuv444's frame; odd sizes use the one extra chroma column / row the decoded plane holds
+ *      (under HVC_ARITH_LIBJPEG the filter over that window is libjpeg's: "Bit-exact to libjpeg" below);
  *   3. libjpeg's 16-bit fixed-point form of the JFIF matrix (ITU-T T.871), >> arithmetic, cb = Cb - 128, cr = Cr - 128:
  *          R = clamp(Y + ((  91881 * cr              + 32768) >> 16))
  *          G = clamp(Y + (( -22554 * cb - 46802 * cr + 32768) >> 16))
@@ -684,6 +688,54 @@ HVC_API int hvc_jpeg_decode_batch_rgb(hvc_ctx *ctx, const uint8_t *const *jpegs,
                                       hvc_batch_stats *stats);
 HVC_API int hvc_jpeg_encode_rgb(hvc_ctx *ctx, const uint8_t *rgb, size_t rgb_row_stride, int layout, int width, int height,
                                 int chroma, int quality, uint8_t *out, size_t cap, size_t *out_len);
+
+/* ------------------------------------------------------------------------- */
+/* Bit-exact to libjpeg (an EXTENSION; csrc/hvc_libjpeg.hip): hvc_set_arithmetic(ctx, HVC_ARITH_LIBJPEG) makes the decode
+ * entry points compute what libjpeg / libjpeg-turbo compute at their defaults -- the pixels of Pillow, OpenCV, torchvision
+ * and djpeg -- instead of the model's.  Two things change: the block stage's inverse DCT, and, in the RGB image of a file,
+ * how chroma is brought to full size.  tools/libjpeg_reference.py restates both in numpy; tests/test_libjpeg_reference.py
+ * holds that against libjpeg-turbo with 0 mismatches.
+ *
+ * Block stage: jidctint.c ("islow").  d[k] = coefficient * table entry at natural position k = 8 * row + col; all arithmetic
+ * in unbounded integers; D(x, n) = (x + 2^(n-1)) >> n with an arithmetic shift.  One step on v[0..7] with shift sh:
+ *     z1 = (v2 + v6) * 4433;  tmp2 = z1 - v6 * 15137;  tmp3 = z1 + v2 * 6270
+ *     tmp0 = (v0 + v4) << 13;  tmp1 = (v0 - v4) << 13
+ *     t10 = tmp0 + tmp3;  t13 = tmp0 - tmp3;  t11 = tmp1 + tmp2;  t12 = tmp1 - tmp2
+ *     a0 = v7; a1 = v5; a2 = v3; a3 = v1
+ *     z1 = a0 + a3;  z2 = a1 + a2;  z3 = a0 + a2;  z4 = a1 + a3;  z5 = (z3 + z4) * 9633
+ *     a0 *= 2446;  a1 *= 16819;  a2 *= 25172;  a3 *= 12299
+ *     z1 *= -7373;  z2 *= -20995;  z3 = z3 * (-16069) + z5;  z4 = z4 * (-3196) + z5
+ *     a0 += z1 + z3;  a1 += z2 + z4;  a2 += z2 + z3;  a3 += z1 + z4
+ *     D(t10 + a3, sh), D(t11 + a2, sh), D(t12 + a1, sh), D(t13 + a0, sh), D(t13 - a0, sh), D(t12 - a1, sh), D(t11 - a2, sh), D(t10 - a3, sh)
+ * Pass 1 runs down the eight columns with sh = 11, pass 2 along the eight rows of the workspace with sh = 18; the sample is
+ * clamp(x + 128, 0, 255).  libjpeg's shortcut for a column without AC terms gives the same values and needs no case of its
+ * own.  libjpeg-turbo's SIMD code keeps 16-bit intermediates that WRAP for blocks whose pass-1 workspace goes far beyond
+ * any real image's (observed around 20 000: every coefficient +-8 with table entries up to 255); as with the range-limit
+ * table of jidctred.c in the next section, the definition is the formula, not the wrap.
+ * The GPU computes blocks with SUM |d[k]| <= 14000 in int32 and the others in int64 in the same kernel (hvc_last_wide_blocks
+ * counts the latter; csrc/hvc_islow_spec.h holds the operation list and the guard, tests/test_islow_guard.py its proof); both
+ * give the definition's value for every int16 coefficient and every 16-bit table entry.  hvc_set_decode_kernel has no
+ * effect under LIBJPEG, except that 2 sends every block down the int64 path (hvc_last_wide_blocks then reports all of them).
+ *
+ * Chroma to full size (step 2 of the RGB section above, under LIBJPEG only; steps 1 and 3 and everything else of step 2 --
+ * the top-left chroma_w x chroma_h window, ITS edges being the ones repeated, the top-left width x height of the result
+ * being used -- are unchanged): libjpeg's "fancy" triangle filter.  With s the window, cw = chroma_w, ch = chroma_h:
+ *   4:2:2, cw > 2   out[2i] = (3 s[i] + s[i-1] + 1) >> 2,  out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2,
+ *                   except out[0] = s[0] and out[2 cw - 1] = s[cw - 1]
+ *   4:2:0, cw > 2   vertically first, unrounded: t[2r] = 3 s[r] + s[max(r-1, 0)],  t[2r+1] = 3 s[r] + s[min(r+1, ch-1)];
+ *                   then along each row: out[2i] = (3 t[i] + t[i-1] + 8) >> 4,  out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4,
+ *                   except out[0] = (4 t[0] + 8) >> 4 and out[2 cw - 1] = (4 t[cw-1] + 7) >> 4
+ *   cw <= 2         (images at most 4 pixels wide) every chroma sample replicated, 2 x or 2 x 2: libjpeg chooses its plain
+ *                   routine there
+ *   4:4:4, grey     unchanged.
+ *
+ * Where it applies: hvc_dequant_idct_recon, hvc_decode_frames (host and device memory), hvc_decode_frames_submit,
+ * hvc_jpeg_decode, hvc_jpeg_decode_batch, hvc_jpeg_decode_batch_gpu, hvc_yuv_to_rgb, hvc_decode_frames_rgb,
+ * hvc_jpeg_decode_rgb and hvc_jpeg_decode_batch_rgb; hvc_set_restart_markers is honoured as before.  A file with a block
+ * whose absolute DC does not fit int16 is HVC_E_RANGE (as at the reduced scales: no side list of such blocks).  The fused
+ * 4:4:4, scaled (scale_denom > 1) and mixed entry points refuse any arithmetic but MODEL with HVC_E_INVALID_ARG, output
+ * untouched, as they do for HARDCAML: their libjpeg forms are not built yet.  hvc_decode_frames_divergence is unaffected,
+ * and there is no encoder side: hvc_set_encode_arithmetic refuses the value. */
 
 /* ------------------------------------------------------------------------- */
 /* Decoding at reduced size: 1/2, 1/4, 1/8 (an EXTENSION; the model has no counterpart).  libjpeg's scale_denom: the inverse

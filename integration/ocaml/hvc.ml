@@ -354,7 +354,7 @@ let jpeg_entropy_decode_restart =
 
 let set_restart_markers = foreign "hvc_set_restart_markers" (ctx @-> int @-> returning int)
 
-(* the block stage's arithmetic: 0 = the model (default), 1 = the Hardcaml RTL datapath
+(* the block stage's arithmetic: 0 = the model (default), 1 = the Hardcaml RTL datapath, 3 = libjpeg's (islow + fancy upsampling)
    int hvc_set_arithmetic(ctx, arith);  int hvc_get_arithmetic(ctx, arith) *)
 let set_arithmetic = foreign "hvc_set_arithmetic" (ctx @-> int @-> returning int)
 let get_arithmetic = foreign "hvc_get_arithmetic" (ctx @-> ptr int @-> returning int)

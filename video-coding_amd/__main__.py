@@ -1,6 +1,6 @@
 """Command line of the path, shaped after the two executables the reference's cram tests drive:
 
-    python -m video_coding_amd model decode frame IN.jpg [OUT.yuv] [-yuv444] [-restart-markers]
+    python -m video_coding_amd model decode frame IN.jpg [OUT.yuv] [-yuv444] [-restart-markers] [-rgb] [-arithmetic model|libjpeg]
                                                                                   jpeg/bin/model.ml:29-45
     python -m video_coding_amd model encode frame IN.yuv WxH OUT.jpg [-quality 75] [-chroma 420] [-restart-interval N]
                                                                                   jpeg/bin/model.ml:86-109
@@ -101,11 +101,14 @@ def model_decode_frame(a):
         raise SystemExit("-rgb and -yuv444 name two different outputs")
     if a.scale != 1 and a.yuv444:
         raise SystemExit("-scale and -yuv444 cannot be combined (the fused 4:4:4 path decodes at full size)")
+    if a.arithmetic != "model" and (a.yuv444 or a.scale != 1):
+        raise SystemExit("-arithmetic %s decodes at full size into planes or -rgb (no -yuv444, no -scale)" % a.arithmetic)
     data = open(a.bits, "rb").read()
     ctx = hvc.Context(a.device)
     try:
         if a.restart_markers:
             ctx.set_restart_markers(True)
+        ctx.set_arithmetic(a.arithmetic)
         if a.rgb:
             info, image = ctx.jpeg_decode_rgb(data) if a.scale == 1 else ctx.jpeg_decode_scaled_rgb(data, a.scale)
             out = np.concatenate([np.frombuffer(b"P6\n%d %d\n255\n" % (info.width, info.height), dtype=np.uint8), image.reshape(-1)])
@@ -477,6 +480,9 @@ def parser():
     p.add_argument("-rgb", action="store_true", help="write the RGB image as a binary PPM (hvc_jpeg_decode_rgb)")
     p.add_argument("-scale", type=int, default=1, choices=[1, 2, 4, 8],
                    help="decode at 1/2, 1/4 or 1/8 size (hvc_jpeg_decode_scaled / _scaled_rgb): the cropped scaled planes, or with -rgb the PPM")
+    p.add_argument("-arithmetic", default="model", choices=["model", "libjpeg"],
+                   help="libjpeg: libjpeg's islow inverse DCT and, with -rgb, its fancy upsampling -- the pixels of Pillow, OpenCV "
+                        "and djpeg (hvc_set_arithmetic HVC_ARITH_LIBJPEG)")
     p.set_defaults(fn=model_decode_frame)
     p = dec.add_parser("frames", help="files of any sizes, samplings and tables in one mixed batch: OUT_DIR/<name>.yuv each")
     p.add_argument("out_dir")

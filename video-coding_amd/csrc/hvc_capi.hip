@@ -452,7 +452,7 @@ int hvc_set_restart_markers(hvc_ctx *c, int honour) try {
 } HVC_ABI_CATCH
 
 int hvc_set_arithmetic(hvc_ctx *c, int arith) try {
-    if (!c || (arith != HVC_ARITH_MODEL && arith != HVC_ARITH_HARDCAML)) return HVC_E_INVALID_ARG;
+    if (!c || (arith != HVC_ARITH_MODEL && arith != HVC_ARITH_HARDCAML && arith != HVC_ARITH_LIBJPEG)) return HVC_E_INVALID_ARG;
     c->arith = arith;
     return HVC_OK;
 } HVC_ABI_CATCH
@@ -658,6 +658,20 @@ static hvc::HardcamlParams hardcaml_params(const hvc::DecodeParams &P, const uin
     H.dc_plane = P.dc_plane;
     H.dc_fs = P.dc_fs;
     return H;
+}
+
+// k_islow's parameters for the geometry and records of a DecodeParams (hvc_libjpeg.h)
+static hvc::IslowParams islow_params(const hvc::DecodeParams &P, const uint16_t *qtabs, int n_qtabs, bool all_wide) {
+    hvc::IslowParams I;
+    fill_geometry(I, P, P.coef_fs, P.pixel_fs, P.n_frames);
+    I.coefs = P.coefs;
+    I.pixels = P.pixels;
+    hvc::prepare_islow_tables(qtabs, n_qtabs, I.qq);
+    I.dc_plane = P.dc_plane;
+    I.dc_fs = P.dc_fs;
+    I.wide_total = P.wide_total;
+    I.all_wide = all_wide;
+    return I;
 }
 
 // qtabs: the call's tables (the twin's form is made from them)
@@ -915,7 +929,11 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
     // HVC_ARITH_HARDCAML: the RTL twin (hvc_hardcaml.hip) in place of the model's kernels -- exact in int32 for every
     // input, so no fix-up list and no wide kernel
     const bool twin = o.arith == HVC_ARITH_HARDCAML;
-    if ((r = reserve_fix_list(c, twin ? 0 : (size_t)((unsigned long long)per * ids_per_frame)))) return r;
+    // HVC_ARITH_LIBJPEG: k_islow (hvc_libjpeg.hip) -- its int64 path runs in the same lane, so no fix-up list either; it keeps
+    // no side list of DCs beyond int16 (as the scaled block stage)
+    const bool islow = o.arith == HVC_ARITH_LIBJPEG;
+    if (islow && has_wide) return HVC_E_RANGE;
+    if ((r = reserve_fix_list(c, twin || islow ? 0 : (size_t)((unsigned long long)per * ids_per_frame)))) return r;
 
     hvc::DecodeParams P;
     fill_geometry(P, L, coef_fs, pixel_fs, n_frames);
@@ -932,8 +950,13 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
     if (wide_only) c->wide_host = (long long)((unsigned long long)n_frames * L.blocks_per_frame);
     // one launch: consumes counter fix_phase, its wide kernel clears the other one (fix_assign / fix_commit above)
     if (twin) c->wide_host = 0;
+    // k_islow counts its int64 blocks into the total itself (cleared below, ahead of the launches); hvc_set_decode_kernel(ctx, 2)
+    // sends every block there
+    const bool islow_all_wide = c->decode_kernel == 2;
+    if (islow) c->wide_host = islow_all_wide ? (long long)((unsigned long long)n_frames * L.blocks_per_frame) : -1;
     auto launch = [&](hvc::DecodeParams &Q, hipEvent_t k0, hipEvent_t k1) -> hipError_t {
         if (twin) return hvc::launch_hardcaml(hardcaml_params(Q, qtabs, n_qtabs), c->stream, k0, k1);
+        if (islow) return hvc::launch_islow(islow_params(Q, qtabs, n_qtabs, islow_all_wide), c->stream, k0, k1);
         if (wide_only) return hvc::launch_decode_wide_only(Q, c->stream, k0, k1);
         fix_assign(c, Q);
         const hipError_t e = hvc::launch_decode(Q, c->stream, k0, k1);
@@ -956,7 +979,8 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
 
     if (where == HVC_MEM_DEVICE) {
         if (((uintptr_t)coefs & 15) || ((uintptr_t)pixels & 7)) return HVC_E_ALIGNMENT;
-        if (o.dc_plane && P.kernel_sel != 0 && !twin) return HVC_E_INVALID_ARG;
+        if (o.dc_plane && P.kernel_sel != 0 && !twin && !islow) return HVC_E_INVALID_ARG;
+        if (islow) HIPCHK(c, hipMemsetAsync(P.wide_total, 0, sizeof *P.wide_total, c->stream));
         P.coefs = coefs;
         P.pixels = pixels;
         P.dc_plane = o.dc_plane;
@@ -974,6 +998,7 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
     const size_t pbytes = (size_t)(n_frames - 1) * pixel_fs + L.pixel_span;
     // copy back only the pixels the kernels wrote (the caller's padding stays untouched)
     const RecordRun run = pixel_run(comps, n_comp);
+    if (islow) HIPCHK(c, hipMemsetAsync(P.wide_total, 0, sizeof *P.wide_total, c->stream)); // (stream order: ahead of every launch)
     return through_device(
         c, n_frames, cbytes, pbytes, cbytes, run.len != 0, // (overlapped: large batches in the usual form)
         [&](int f0, int cnt) {
@@ -1147,7 +1172,7 @@ int hvc_decode_frames_rgb(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, cons
                                     HVC_MEM_DEVICE, DecodeOpts(c))))
             return r;
         HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, px_fs, tight, sampling, width, height, cw, ch, cnt,
-                                    d_rgb + (size_t)f0 * im.frame_stride, im, c->stream));
+                                    d_rgb + (size_t)f0 * im.frame_stride, im, c->stream, c->arith));
     }
     if (where == HVC_MEM_HOST) {
         HIPCHK(c, rgb_download(d_rgb, rgb, im, n_frames, c->stream));

@@ -145,7 +145,7 @@ struct RgbTail {
         int cw, ch;
         rgb_chroma_window(sampling, pi.width, pi.height, cw, ch);
         HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, pi.pixel_bytes, pi.layout, sampling, pi.width, pi.height, cw, ch, 1,
-                                    (uint8_t *)c->d_aux2, im, c->stream));
+                                    (uint8_t *)c->d_aux2, im, c->stream, c->arith));
         HIPCHK(c, rgb_download((const uint8_t *)c->d_aux2, rgb, im, 1, c->stream));
         return HVC_OK;
     }
@@ -667,7 +667,7 @@ int hvc_jpeg_decode_batch_rgb(hvc_ctx *c, const uint8_t *const *jpegs, const siz
         if (empty) continue;
         uint8_t *out = where == HVC_MEM_HOST ? d_rgb : d_rgb + (size_t)f0 * im.frame_stride;
         HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, px_fs, info0.layout, sampling, info0.width, info0.height, cw, ch, cnt, out, im,
-                                    c->stream));
+                                    c->stream, c->arith));
         if (where == HVC_MEM_HOST) {
             HIPCHK(c, rgb_download(out, rgb + (size_t)f0 * im.frame_stride, im, cnt, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -37,6 +37,7 @@
 #include "../../include/hvc_jpeg.h"
 #include "hvc_hdec.h"
 #include "hvc_hardcaml.h"
+#include "hvc_libjpeg.h"
 #include "hvc_huff.h"
 #include "hvc_kernels.h"
 #include "hvc_mixed_plan.h"
@@ -59,7 +60,8 @@ struct hvc_ctx {
     unsigned long long mixed_gpu_files = 0, mixed_host_files = 0; // hvc_last_mixed_reader_files: the last mixed batch call's split
     bool honour_restart = false; // hvc_set_restart_markers: restart intervals honoured by the file-level entry points (an extension)
     int decode_kernel = 0; // hvc_set_decode_kernel: 0 packed (default), 1 unpacked int32, 2 int64 for every block, 3 q16
-    int arith = HVC_ARITH_MODEL; // hvc_set_arithmetic: the block stage's arithmetic (HARDCAML: k_hardcaml, hvc_hardcaml.hip)
+    int arith = HVC_ARITH_MODEL; // hvc_set_arithmetic: the block stage's arithmetic (HARDCAML: k_hardcaml, hvc_hardcaml.hip;
+                                 // LIBJPEG: k_islow and, in the colour pass, k_ycc_to_rgb_fancy, hvc_libjpeg.hip)
     int enc_arith = HVC_ARITH_MODEL; // hvc_set_encode_arithmetic: the encoder's (HARDCAML: k_hardcaml_encode, hvc_hardcaml.hip)
     int huff_tables = HVC_HUFF_DEFAULT; // hvc_set_huffman_tables: the files' Huffman tables (OPTIMISED: k_huff_hist / k_huff_build)
     int restart_interval = 0; // hvc_set_restart_interval: MCUs per restart interval of the files written, 0 = no DRI / RSTn
@@ -416,7 +418,7 @@ int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
                               const hvc_component *comps, int n_comp, int n_frames, int width, int height, uint8_t *frames,
                               size_t frame_stride, int where, const DecodeOpts &o);
 // the block stage at 1 / scale_denom size (k_decode_scaled, hvc_scaled.hip) behind hvc_decode_frames_scaled and the file-level
-// scaled entry points; scale_denom = 1 is decode_frames_impl.  Of `o` it takes arith (HARDCAML: HVC_E_INVALID_ARG), profile,
+// scaled entry points; scale_denom = 1 is decode_frames_impl.  Of `o` it takes arith (anything but MODEL: HVC_E_INVALID_ARG), profile,
 // dc_plane and dc_fs.
 int decode_frames_scaled_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
                               const hvc_component *comps, int n_comp, int n_frames, int scale_denom, uint8_t *pixels, size_t pixel_fs,
@@ -539,8 +541,11 @@ bool rgb_image(int layout, int width, int height, size_t row_stride, size_t fram
 size_t rgb_bytes(const RgbImage &im, int n_frames); // from the first byte of frame 0 to the last byte written
 int rgb_sampling_of(const hvc_jpeg_info &info);     // HVC_YUV_420 / 422 / 444 / 400 by the scan's sampling factors, 0 = none of them
 void rgb_chroma_window(int sampling, int width, int height, int &cw, int &ch); // ceil(width / 2) x ceil(height / 2) for 4:2:0, ...
+// arith: the context's hvc_set_arithmetic -- HVC_ARITH_LIBJPEG takes k_ycc_to_rgb_fancy (hvc_libjpeg.hip), anything else k_ycc_to_rgb
 hipError_t ycc_to_rgb_device(const uint8_t *d_yuv, size_t yuv_fs, const hvc_component *comps, int sampling, int width, int height, int cw,
-                             int ch, int n_frames, uint8_t *d_rgb, const RgbImage &im, hipStream_t s);
+                             int ch, int n_frames, uint8_t *d_rgb, const RgbImage &im, hipStream_t s, int arith);
+hipError_t ycc_to_rgb_fancy_device(const uint8_t *d_yuv, size_t yuv_fs, const hvc_component *comps, int sampling, int width, int height,
+                                   int cw, int ch, int n_frames, uint8_t *d_rgb, const RgbImage &im, hipStream_t s);
 hipError_t rgb_to_ycc_device(const uint8_t *d_rgb, const RgbImage &im, int width, int height, int sampling, int n_frames, uint8_t *d_yuv,
                              size_t yuv_fs, const hvc_component *comps, hipStream_t s);
 size_t rgb_yuv_span(const hvc_component *comps, int sampling, int w, int h, int cw, int ch); // bytes of a frame record the pass touches

@@ -185,7 +185,8 @@ bool rgb_image(int layout, int width, int height, size_t row_stride, size_t fram
 // (rgb_sampling_of and rgb_chroma_window are host rules without HIP: hvc_mixed_rgb_plan.cpp)
 
 hipError_t ycc_to_rgb_device(const uint8_t *d_yuv, size_t yuv_fs, const hvc_component *comps, int sampling, int width, int height, int cw,
-                             int ch, int n_frames, uint8_t *d_rgb, const RgbImage &im, hipStream_t s) {
+                             int ch, int n_frames, uint8_t *d_rgb, const RgbImage &im, hipStream_t s, int arith) {
+    if (arith == HVC_ARITH_LIBJPEG) return ycc_to_rgb_fancy_device(d_yuv, yuv_fs, comps, sampling, width, height, cw, ch, n_frames, d_rgb, im, s);
     return launch_colour(true, d_yuv, yuv_fs, comps, sampling, width, height, cw, ch, n_frames, d_rgb, im, s);
 }
 hipError_t rgb_to_ycc_device(const uint8_t *d_rgb, const RgbImage &im, int width, int height, int sampling, int n_frames, uint8_t *d_yuv,

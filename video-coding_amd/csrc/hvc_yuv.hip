@@ -615,7 +615,7 @@ int hvc_yuv_to_rgb(hvc_ctx *c, const uint8_t *yuv, size_t yuv_fs, const hvc_comp
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
     if (where == HVC_MEM_DEVICE) {
-        HIPCHK(c, ycc_to_rgb_device(yuv, yuv_fs, comps, sampling, width, height, chroma_w, chroma_h, n_frames, rgb, im, c->stream));
+        HIPCHK(c, ycc_to_rgb_device(yuv, yuv_fs, comps, sampling, width, height, chroma_w, chroma_h, n_frames, rgb, im, c->stream, c->arith));
         return HVC_OK;
     }
     const size_t in_bytes = (size_t)(n_frames - 1) * yuv_fs + span;
@@ -623,7 +623,7 @@ int hvc_yuv_to_rgb(hvc_ctx *c, const uint8_t *yuv, size_t yuv_fs, const hvc_comp
     if ((r = grow(c, &c->d_out, &c->out_cap, rgb_bytes(im, n_frames)))) return r;
     HIPCHK(c, hipMemcpyAsync(c->d_in, yuv, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_in, yuv_fs, comps, sampling, width, height, chroma_w, chroma_h, n_frames,
-                                (uint8_t *)c->d_out, im, c->stream));
+                                (uint8_t *)c->d_out, im, c->stream, c->arith));
     HIPCHK(c, rgb_download((const uint8_t *)c->d_out, rgb, im, n_frames, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HVC_OK;

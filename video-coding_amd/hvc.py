@@ -47,7 +47,7 @@ SYMBOLS = [
 HVC_RGB = {"interleaved": 0, "planar": 1}  # enum hvc_rgb_layout: [H, W, 3] / [3, H, W]
 HVC_YUV_400 = 400   # luma only, beside 420 / 422 / 444
 HVC_HUFF = {"default": 0, "optimised": 1}  # enum hvc_huff_tables
-HVC_ARITH = {"model": 0, "hardcaml": 1}  # enum hvc_arith
+HVC_ARITH = {"model": 0, "hardcaml": 1, "libjpeg": 3}  # enum hvc_arith (2 is not an arithmetic)
 HVC_SLOTS = 4       # enum { HVC_SLOTS }
 HVC_E_BUSY = -12
 
@@ -889,8 +889,9 @@ class Context:
         _chk(lib().hvc_set_restart_markers(self._h, 1 if honour else 0), "hvc_set_restart_markers")
 
     def set_arithmetic(self, arith):
-        """"model" (default: the OCaml model's decoder) | "hardcaml" (the reference's RTL decoder datapath, bit for bit):
-        the block stage of every decode entry point except the fused 4:4:4 ones, which refuse "hardcaml"."""
+        """"model" (default: the OCaml model's decoder) | "hardcaml" (the reference's RTL decoder datapath, bit for bit) |
+        "libjpeg" (libjpeg's islow inverse DCT and, in the RGB forms, its fancy upsampling, bit for bit): the block stage
+        of every decode entry point except the fused 4:4:4, scaled and mixed ones, which refuse anything but "model"."""
         _chk(lib().hvc_set_arithmetic(self._h, HVC_ARITH[arith] if isinstance(arith, str) else int(arith)),
              "hvc_set_arithmetic")
 
