@@ -549,7 +549,8 @@ HVC_API int hvc_jpeg_entropy_encode_tables(const hvc_jpeg_info *info, const hvc_
                                            uint8_t *out, size_t cap, size_t *out_len);
 /* hvc_huffman_encode_frames with each frame's own optimal tables, counted and built on the GPU (k_huff_hist,
  * k_huff_build, csrc/hvc_huff.hip).  specs is host memory of n_frames x 4 entries and receives each frame's tables; the
- * segments equal hvc_jpeg_entropy_encode_tables' with them. */
+ * segments equal hvc_jpeg_entropy_encode_tables' with them.  An info whose components all select one table set leaves the
+ * other without a symbol to fit a table to: HVC_E_INVALID_ARG, as from hvc_huffman_optimal_tables. */
 HVC_API int hvc_huffman_encode_frames_optimised(hvc_ctx *ctx, const hvc_jpeg_info *info, const int16_t *coefs,
                                                 size_t coef_frame_stride, int n_frames, uint8_t *out, size_t out_cap,
                                                 uint64_t *offsets, hvc_huff_spec *specs, int where);

@@ -5,9 +5,9 @@ small frames and a handful of 1080p ones (about 3 s each)."""
 import numpy as np
 
 
-def _optimal_lengths(freq):
-    """Code lengths (<= 16) for the symbols with freq > 0: ITU-T T.81 Annex K.2 (figures K.1-K.3), with the
-    reserved 257th symbol so that no code is all ones.  Returns (bits[1..16] as a list of 17, huffval)."""
+def _code_sizes(freq):
+    """Code sizes BEFORE figure K.3 (they may exceed 16) for the symbols with freq > 0, index 256 the reserved symbol:
+    ITU-T T.81 Annex K.2 figure K.1, the largest index among the smallest counts first."""
     f = list(freq) + [1]
     codesize = [0] * 257
     others = [-1] * 257
@@ -33,6 +33,13 @@ def _optimal_lengths(freq):
         while others[c2] >= 0:
             c2 = others[c2]
             codesize[c2] += 1
+    return codesize
+
+
+def _optimal_lengths(freq):
+    """Code lengths (<= 16) for the symbols with freq > 0: ITU-T T.81 Annex K.2 (figures K.1-K.3), with the
+    reserved 257th symbol so that no code is all ones.  Returns (bits[1..16] as a list of 17, huffval)."""
+    codesize = _code_sizes(freq)
     bits = [0] * 33
     for i in range(257):
         if codesize[i]:

@@ -66,6 +66,9 @@ int huffman_prepare(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *d_coef
     }
     P.tiles_per_frame = tile;
     P.blocks_per_mcu = base;
+    // a table set that no component selects has no symbol to fit a table to: refused as hvc_huffman_optimal_tables refuses
+    // it (k_huff_build would look for the reserved symbol's code length in a table without one)
+    if (optimised && P.comp[0].table == P.comp[1].table && P.comp[1].table == P.comp[2].table) return HVC_E_INVALID_ARG;
     const unsigned long long bpf = (unsigned long long)P.mbs_wide * P.mbs_high * base;
     // restart intervals: a scan of a single interval (Ri >= MCUs) holds no marker and is the plain segment
     const unsigned long long mcus = (unsigned long long)P.mbs_wide * P.mbs_high;

@@ -404,8 +404,8 @@ __global__ __launch_bounds__(64) void k_huff_build(HuffParams P) {
                 bits[j]--;
             }
         int i = 16;
-        while (bits[i] == 0) i--;
-        bits[i]--;
+        while (i > 0 && bits[i] == 0) i--; // (i = 0: no symbol counted at all, which huffman_prepare does not let through)
+        if (i) bits[i]--;
         // canonical codes (tables.ml:27-45)
         int n = 0;
         unsigned code = 0;
