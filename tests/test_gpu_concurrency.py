@@ -9,22 +9,12 @@ import time
 import numpy as np
 import pytest
 
+from batch_files import frames as _frames, mixed_files as _mixed_files, uniform_files as _uniform_files
 from conftest import golden_bytes
-from helpers import synth_pixels
 from oracle import orc
 from test_host_entropy import UNUSUAL_SAMPLINGS, unusual_sampling_file
 
 pytestmark = pytest.mark.gpu
-
-
-def _frames(n, w, h, seed):
-    out = []
-    for f in range(n):
-        y = synth_pixels(seed + f, h, w)
-        u = synth_pixels(seed + 100 + f, h // 2, w // 2)
-        v = synth_pixels(seed + 200 + f, h // 2, w // 2)
-        out.append((y, u, v))
-    return out
 
 
 def test_two_contexts_run_their_batch_pipelines_concurrently():
@@ -259,20 +249,6 @@ def test_every_context_entry_point_refuses_null_buffers():
 
 # ---------------------------------------------------------------------------
 # the pipelines' shared parts (csrc/hvc_feed.h, hvc_batch.h, the ring helper of hvc_ctx.h) through every pipeline of one context
-
-def _uniform_files(n, seed):
-    """n files of one geometry (64 x 64, 4:2:0) and one set of tables, with their raw frames"""
-    frames = _frames(n, 64, 64, seed)
-    return [orc.encode_yuv(y, u, v, 64, 64, 420, 75) for y, u, v in frames], frames
-
-
-def _mixed_files():
-    """Mouse480 first (its record alone is a chunk), mini.jpg, unusual samplings at 40 x 24 and 97 x 51"""
-    files = [golden_bytes("Mouse480.jpg"), golden_bytes("mini.jpg")]
-    files += [unusual_sampling_file(UNUSUAL_SAMPLINGS[si], 40, 24, 100 * si + 40)[0] for si in (0, 3, 9)]
-    files += [unusual_sampling_file(UNUSUAL_SAMPLINGS[si], 97, 51, 100 * si + 97)[0] for si in (1, 8)]
-    return files
-
 
 def _host(a):
     return a.cpu().numpy() if hasattr(a, "cpu") else a

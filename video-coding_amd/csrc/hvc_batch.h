@@ -9,13 +9,13 @@
 
 // the copy stream and the events of the decode pipelines, created by the first call that needs them
 inline int pipeline_events(hvc_ctx *c) {
-    if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    HIPCHK(c, c->copy_stream.ensure());
     for (int i = 0; i < hvc_ctx::RING; i++) {
-        if (!c->ev_h2d[i]) HIPCHK(c, hipEventCreate(&c->ev_h2d[i]));
-        if (!c->ev_kern[i]) HIPCHK(c, hipEventCreate(&c->ev_kern[i]));
+        HIPCHK(c, c->ev_h2d[i].ensure());
+        HIPCHK(c, c->ev_kern[i].ensure());
     }
     for (int i = 0; i < 4; i++)
-        if (!c->ev_t[i]) HIPCHK(c, hipEventCreate(&c->ev_t[i]));
+        HIPCHK(c, c->ev_t[i].ensure());
     return HVC_OK;
 }
 
@@ -46,7 +46,7 @@ inline int host_reader_chunks(hvc_ctx *c, hvc::ChunkFeed &feed, int n_chunks, in
             if (he == hipSuccess) he = hipEventRecord(c->ev_t[0], c->copy_stream);
             if (he == hipSuccess)
                 if (const size_t bytes = upload_bytes(k))
-                    he = hipMemcpyAsync(c->d_ring[slot], c->h_ring[slot], bytes, hipMemcpyHostToDevice, c->copy_stream);
+                    he = hipMemcpyAsync(c->d_ring[slot].p, c->h_ring[slot].p, bytes, hipMemcpyHostToDevice, c->copy_stream);
             if (he == hipSuccess) he = hipEventRecord(c->ev_h2d[slot], c->copy_stream);
             if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_h2d[slot], 0);
             if (he == hipSuccess) he = hipEventRecord(c->ev_t[1], compute);

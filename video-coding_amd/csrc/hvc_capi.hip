@@ -41,14 +41,10 @@ bool parse_cpulist(const char *s, cpu_set_t &set) {
     return n > 0;
 }
 
-void ring_free(const RingSet &s) {
+static void ring_free(const RingSet &s) {
     for (int j = 0; j < s.n; j++) {
-        const RingMember &m = s.m[j];
-        for (void *&p : *m.ring) {
-            if (p) (void)(m.pinned ? hipHostFree(p) : hipFree(p));
-            p = nullptr;
-        }
-        *m.recorded = 0;
+        for (Buf &b : *s.m[j].ring) (void)b.release();
+        *s.m[j].recorded = 0;
     }
 }
 
@@ -64,8 +60,12 @@ int ring_ensure(hvc_ctx *c, const RingSet &s, std::initializer_list<size_t> want
         j = 0;
         for (size_t w : want) {
             const RingMember &m = s.m[j++];
-            void **p = &(*m.ring)[i];
-            if ((m.pinned ? hipHostMalloc(p, w, m.flags) : hipMalloc(p, w + m.slack)) != hipSuccess) return HVC_E_OUT_OF_MEMORY;
+            Buf &b = (*m.ring)[i];
+            if ((b.pinned ? hipHostMalloc(&b.p, w, b.flags) : hipMalloc(&b.p, w + m.slack)) != hipSuccess) {
+                b.p = nullptr;
+                return HVC_E_OUT_OF_MEMORY;
+            }
+            b.cap = b.pinned ? w : w + m.slack;
         }
     }
     j = 0;
@@ -73,22 +73,20 @@ int ring_ensure(hvc_ctx *c, const RingSet &s, std::initializer_list<size_t> want
     return HVC_OK;
 }
 
-int grow(hvc_ctx *c, void **p, size_t *cap, size_t need) {
-    if (need <= *cap) return HVC_OK;
-    if (*p) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(*p));
-        *p = nullptr;
-        *cap = 0;
-    }
-    size_t want = need + need / 4 + 4096;
-    hipError_t e = hipMalloc(p, want);
+int grow(hvc_ctx *c, Buf &b, size_t need, const GrowRule &rule) {
+    if (need <= b.cap) return HVC_OK;
+    if (rule.drain == GrowRule::DRAIN_ALWAYS || (rule.drain == GrowRule::DRAIN_HELD && b)) HIPCHK(c, hipStreamSynchronize(c->stream));
+    const hipError_t freed = b.release();
+    if (!b.pinned) HIPCHK(c, freed);
+    const size_t want = need + (rule.spare_div ? need / rule.spare_div : 0) + rule.spare_add;
+    const hipError_t e = b.pinned ? hipHostMalloc(&b.p, want, b.flags) : hipMalloc(&b.p, want);
     if (e != hipSuccess) {
-        *p = nullptr;
-        c->last_hip = (int)e;
+        if (rule.clear_error) (void)hipGetLastError();
+        b.p = nullptr;
+        if (!b.pinned) c->last_hip = (int)e;
         return HVC_E_OUT_OF_MEMORY;
     }
-    *cap = want;
+    b.cap = want;
     return HVC_OK;
 }
 
@@ -219,15 +217,14 @@ int hvc_create(hvc_ctx **out, int device) try {
     if (!c) return HVC_E_OUT_OF_MEMORY;
     c->device = device;
     DeviceGuard g(device);
-    bool ok = g.ok && hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
+    bool ok = g.ok && c->own_stream.ensure() == hipSuccess && c->ev0.ensure() == hipSuccess && c->ev1.ensure() == hipSuccess &&
               [&] {
                   for (int i = 0; i < HVC_PROF_RING; i++)
-                      if (hipEventCreate(&c->k0[i]) != hipSuccess || hipEventCreate(&c->k1[i]) != hipSuccess) return false;
+                      if (c->k0[i].ensure() != hipSuccess || c->k1[i].ensure() != hipSuccess) return false;
                   return true;
               }() &&
-              hipMalloc((void **)&c->d_fix_count, HVC_FIX_WORDS * sizeof(unsigned)) == hipSuccess &&
-              hipMemset(c->d_fix_count, 0, HVC_FIX_WORDS * sizeof(unsigned)) == hipSuccess;
+              grow(c, c->d_fix_count, HVC_FIX_WORDS * sizeof(unsigned), GROW_EXACT) == HVC_OK &&
+              hipMemset(c->d_fix_count.p, 0, HVC_FIX_WORDS * sizeof(unsigned)) == hipSuccess;
     if (!ok) {
         hvc_destroy(c);
         return HVC_E_NO_DEVICE;
@@ -244,7 +241,8 @@ void hvc_destroy(hvc_ctx *c) {
     c->pool.shutdown(); // (idle: every call waits for its own tasks)
     DeviceGuard g(c->device);
     // everything this context may still have in flight: the caller's stream (NULL is HIP's default stream -- a
-    // stream like any other), its own, and the pipelines' side streams
+    // stream like any other), its own, and the pipelines' side streams.  What the context owns then goes with it: the
+    // members of hvc_ctx release themselves, the streams last, with the device guard still in place.
     (void)hipStreamSynchronize(c->stream);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
@@ -252,80 +250,6 @@ void hvc_destroy(hvc_ctx *c) {
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     for (int i = 0; i < 3; i++)
         if (c->rd_stream[i]) (void)hipStreamSynchronize(c->rd_stream[i]);
-    if (c->d_fix_count) (void)hipFree(c->d_fix_count);
-    if (c->d_fix_list) (void)hipFree(c->d_fix_list);
-    if (c->d_in) (void)hipFree(c->d_in);
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_div_px) (void)hipFree(c->d_div_px);
-    if (c->d_div_in) (void)hipFree(c->d_div_in);
-    if (c->d_div_out) (void)hipFree(c->d_div_out);
-    if (c->d_dct_tab) (void)hipFree(c->d_dct_tab);
-    if (c->d_dct_a) (void)hipFree(c->d_dct_a);
-    if (c->d_dct_b) (void)hipFree(c->d_dct_b);
-    if (c->d_sums) (void)hipFree(c->d_sums);
-    if (c->d_aux) (void)hipFree(c->d_aux);
-    if (c->d_aux2) (void)hipFree(c->d_aux2);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    for (int i = 0; i < HVC_PROF_RING; i++) {
-        if (c->k0[i]) (void)hipEventDestroy(c->k0[i]);
-        if (c->k1[i]) (void)hipEventDestroy(c->k1[i]);
-    }
-    for (const RingSet &s : {coef_rings(c), out_rings(c), plane_rings(c), reader_rings(c), enc_rings(c), enc_seg_rings(c), enc_spec_rings(c)})
-        ring_free(s);
-    for (int i = 0; i < hvc_ctx::RING; i++) {
-        if (c->ev_h2d[i]) (void)hipEventDestroy(c->ev_h2d[i]);
-        if (c->ev_kern[i]) (void)hipEventDestroy(c->ev_kern[i]);
-        if (c->ev_up[i]) (void)hipEventDestroy(c->ev_up[i]);
-        if (c->ev_down[i]) (void)hipEventDestroy(c->ev_down[i]);
-        for (int k = 0; k < 3; k++)
-            if (c->ev_et[i][k]) (void)hipEventDestroy(c->ev_et[i][k]);
-        if (c->ev_gpu[i]) (void)hipEventDestroy(c->ev_gpu[i]);
-    }
-    for (int i = 0; i < 4; i++)
-        if (c->ev_t[i]) (void)hipEventDestroy(c->ev_t[i]);
-    for (hvc_ctx::Slot &s : c->slots) { // (a submission nobody waited for: the streams were drained above)
-        if (s.d_in) (void)hipFree(s.d_in);
-        if (s.d_out) (void)hipFree(s.d_out);
-        for (hipEvent_t e : {s.up0, s.up1, s.k0, s.k1, s.dn0, s.dn1})
-            if (e) (void)hipEventDestroy(e);
-    }
-    if (c->gd_ecs) (void)hipFree(c->gd_ecs);
-    if (c->gd_h_ecs) (void)hipHostFree(c->gd_h_ecs);
-    if (c->gd_fcnt) (void)hipFree(c->gd_fcnt);
-    if (c->gd_meta) (void)hipFree(c->gd_meta);
-    if (c->gd_state) (void)hipFree(c->gd_state);
-    if (c->gd_tables) (void)hipFree(c->gd_tables);
-    if (c->gd_coefs) (void)hipFree(c->gd_coefs);
-    if (c->gd_dcd) (void)hipFree(c->gd_dcd);
-    if (c->gd_ftabs) (void)hipFree(c->gd_ftabs);
-    if (c->gd_dcv) (void)hipFree(c->gd_dcv);
-    if (c->d_dcfix) (void)hipFree(c->d_dcfix);
-    if (c->d_mixed) (void)hipFree(c->d_mixed);
-    if (c->h_mixed) (void)hipHostFree(c->h_mixed);
-    if (c->ev_mixed) (void)hipEventDestroy(c->ev_mixed);
-    if (c->d_mixed_rgb) (void)hipFree(c->d_mixed_rgb);
-    if (c->h_mixed_rgb) (void)hipHostFree(c->h_mixed_rgb);
-    if (c->ev_mixed_rgb) (void)hipEventDestroy(c->ev_mixed_rgb);
-    delete c->gd_tables_host;
-    if (c->hd_tables) (void)hipFree(c->hd_tables);
-    if (c->hd_opt) (void)hipFree(c->hd_opt);
-    if (c->hd_lens) (void)hipFree(c->hd_lens);
-    if (c->hd_meta) (void)hipFree(c->hd_meta);
-    if (c->hd_bitbuf) (void)hipFree(c->hd_bitbuf);
-    if (c->hd_ff) (void)hipFree(c->hd_ff);
-    if (c->hd_ivl) (void)hipFree(c->hd_ivl);
-    if (c->hd_out) (void)hipFree(c->hd_out);
-    for (int i = 0; i < 3; i++)
-        if (c->rd_stream[i]) (void)hipStreamDestroy(c->rd_stream[i]);
-    for (int i = 0; i < 3; i++)
-        if (c->ev_rd[i]) (void)hipEventDestroy(c->ev_rd[i]);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->down_stream) (void)hipStreamDestroy(c->down_stream);
-    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
 
@@ -567,15 +491,15 @@ int hvc_checksum_records(hvc_ctx *c, const void *data, size_t record_bytes, size
     int r;
     if (where == HVC_MEM_HOST) {
         const size_t bytes = (size_t)(n_records - 1) * record_stride + record_bytes;
-        if ((r = grow(c, &c->d_in, &c->in_cap, bytes ? bytes : 1))) return r;
-        if (bytes) HIPCHK(c, hipMemcpyAsync(c->d_in, data, bytes, hipMemcpyHostToDevice, c->stream));
-        d = (const uint8_t *)c->d_in;
+        if ((r = grow(c, c->d_in, bytes ? bytes : 1))) return r;
+        if (bytes) HIPCHK(c, hipMemcpyAsync(c->d_in.p, data, bytes, hipMemcpyHostToDevice, c->stream));
+        d = c->d_in.as<const uint8_t>();
     }
-    if ((r = grow(c, &c->d_sums, &c->sums_cap, sum_bytes))) return r;
+    if ((r = grow(c, c->d_sums, sum_bytes))) return r;
     for (int r0 = 0; r0 < n_records; r0 += 65535) // (the grid's y dimension holds 65535 records)
         HIPCHK(c, hvc::launch_checksum(d + (size_t)r0 * record_stride, record_bytes, record_stride,
-                                       n_records - r0 < 65535 ? n_records - r0 : 65535, (unsigned long long *)c->d_sums + r0, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sums, c->d_sums, sum_bytes, hipMemcpyDeviceToHost, c->stream));
+                                       n_records - r0 < 65535 ? n_records - r0 : 65535, c->d_sums.as<unsigned long long>() + r0, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sums, c->d_sums.p, sum_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HVC_OK;
 } HVC_ABI_CATCH
@@ -584,7 +508,7 @@ int hvc_last_wide_blocks(hvc_ctx *c, uint64_t *count) try {
     if (!c || !count) return HVC_E_INVALID_ARG;
     DeviceGuard g(c->device);
     unsigned long long v = 0; // the total over ALL launches of the last call (a large batch is cut into several)
-    HIPCHK(c, hipMemcpyAsync(&v, c->d_fix_count + 2, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&v, c->d_fix_count.as<unsigned>() + 2, sizeof v, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *count = c->wide_host >= 0 ? (uint64_t)c->wide_host : (uint64_t)v;
     return HVC_OK;
@@ -621,10 +545,10 @@ static int upload_dcfix(hvc_ctx *c, const std::vector<unsigned> &ids, const std:
                         const unsigned **d_ids, const long long **d_dcs) {
     const size_t n = ids.size();
     const size_t off_ids = 16, off_dcs = (off_ids + n * sizeof(unsigned) + 15) & ~(size_t)15;
-    int r = grow(c, &c->d_dcfix, &c->dcfix_cap, off_dcs + n * sizeof(long long));
+    int r = grow(c, c->d_dcfix, off_dcs + n * sizeof(long long));
     if (r) return r;
     const unsigned cnt = (unsigned)n;
-    char *base = (char *)c->d_dcfix;
+    char *base = c->d_dcfix.as<char>();
     HIPCHK(c, hipMemcpyAsync(base, &cnt, sizeof cnt, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(base + off_ids, ids.data(), n * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(base + off_dcs, dcs.data(), n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
@@ -840,15 +764,7 @@ static int frames_per_launch_capped(int n_frames, unsigned long long blocks_per_
 
 // the fix-up list holds at least `entries` block ids (one per block of a LAUNCH: launches follow one another on the stream,
 // each consumes its own)
-static int reserve_fix_list(hvc_ctx *c, size_t entries) {
-    if (entries <= c->fix_cap) return HVC_OK;
-    void *p = c->d_fix_list;
-    size_t cap = c->fix_cap * sizeof(unsigned);
-    const int r = grow(c, &p, &cap, entries * sizeof(unsigned));
-    c->d_fix_list = (unsigned *)p;
-    c->fix_cap = cap / sizeof(unsigned);
-    return r;
-}
+static int reserve_fix_list(hvc_ctx *c, size_t entries) { return grow(c, c->d_fix_list, entries * sizeof(unsigned)); }
 
 // frames [f0, f0 + cnt) of a batch in launches of `per` frames: launch(first frame, frames, k0, k1), with the event pair
 // around all of them -- k0 goes to the first launch, k1 to the last, the others get none
@@ -867,9 +783,9 @@ static hipError_t for_each_launch(int f0, int cnt, int per, hipEvent_t k0, hipEv
 template <class Up, class Run, class Down>
 static int through_device(hvc_ctx *c, int n_frames, size_t in_bytes, size_t out_bytes, size_t coef_bytes, bool may_overlap, Up up, Run run,
                           Down down) {
-    int r = grow(c, &c->d_in, &c->in_cap, in_bytes);
+    int r = grow(c, c->d_in, in_bytes);
     if (r) return r;
-    if ((r = grow(c, &c->d_out, &c->out_cap, out_bytes))) return r;
+    if ((r = grow(c, c->d_out, out_bytes))) return r;
     if (may_overlap && n_frames >= 8 && coef_bytes >= ((size_t)64 << 20)) // see overlapped_parts
         return overlapped_parts(c, n_frames, up, [&](int, int f0, int cnt) { return run(f0, cnt); }, down);
     HIPCHK(c, up(0, n_frames));
@@ -1002,12 +918,12 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
     return through_device(
         c, n_frames, cbytes, pbytes, cbytes, run.len != 0, // (overlapped: large batches in the usual form)
         [&](int f0, int cnt) {
-            return hipMemcpyAsync((int16_t *)c->d_in + (size_t)f0 * coef_fs, coefs + (size_t)f0 * coef_fs,
+            return hipMemcpyAsync(c->d_in.as<int16_t>() + (size_t)f0 * coef_fs, coefs + (size_t)f0 * coef_fs,
                                   ((size_t)(cnt - 1) * coef_fs + L.coef_span) * sizeof(int16_t), hipMemcpyHostToDevice, c->stream);
         },
-        [&](int f0, int cnt) { return launch_range((const int16_t *)c->d_in, (uint8_t *)c->d_out, f0, cnt, nullptr, nullptr); },
+        [&](int f0, int cnt) { return launch_range(c->d_in.as<const int16_t>(), c->d_out.as<uint8_t>(), f0, cnt, nullptr, nullptr); },
         [&](int f0, int cnt, hipStream_t st) {
-            return download_pixels(comps, n_comp, run, f0, cnt, pixel_fs, (const uint8_t *)c->d_out, pixels, st);
+            return download_pixels(comps, n_comp, run, f0, cnt, pixel_fs, c->d_out.as<const uint8_t>(), pixels, st);
         });
 }
 
@@ -1065,7 +981,7 @@ int decode_frames_scaled_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
     hvc::DecodeParams P;
     fill_geometry(P, L, coef_fs, pixel_fs, n_frames);
     for (int i = 0; i < n_qtabs * 64; i++) P.qt[i] = (int)qtabs[i];
-    P.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count + 2);
+    P.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count.as<unsigned>() + 2);
     wide_total_begin(c); // hvc_last_wide_blocks: the launches add the blocks of their int64 branch to a total cleared here
     bool rows_on_dwords = ((n_frames > 1 ? pixel_fs : 0) & 3) == 0;
     for (int i = 0; i < n_comp; i++) rows_on_dwords &= ((comps[i].plane_offset | comps[i].stride) & 3) == 0;
@@ -1101,16 +1017,16 @@ int decode_frames_scaled_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
         [&](int f0, int cnt) {
             const hipError_t e = hipMemsetAsync(P.wide_total, 0, sizeof *P.wide_total, c->stream);
             if (e != hipSuccess) return e;
-            return hipMemcpyAsync((int16_t *)c->d_in + (size_t)f0 * coef_fs, coefs + (size_t)f0 * coef_fs,
+            return hipMemcpyAsync(c->d_in.as<int16_t>() + (size_t)f0 * coef_fs, coefs + (size_t)f0 * coef_fs,
                                   ((size_t)(cnt - 1) * coef_fs + L.coef_span) * sizeof(int16_t), hipMemcpyHostToDevice, c->stream);
         },
-        [&](int f0, int cnt) { return launch_range((const int16_t *)c->d_in, (uint8_t *)c->d_out, f0, cnt, nullptr, nullptr); },
+        [&](int f0, int cnt) { return launch_range(c->d_in.as<const int16_t>(), c->d_out.as<uint8_t>(), f0, cnt, nullptr, nullptr); },
         [&](int f0, int cnt, hipStream_t st) {
             for (int f = f0; f < f0 + cnt; f++)
                 for (int i = 0; i < n_comp; i++) {
                     const hvc_component &k = comps[i];
                     const size_t off = (size_t)f * pixel_fs + k.plane_offset;
-                    const hipError_t e = hipMemcpy2DAsync(pixels + off, k.stride, (const uint8_t *)c->d_out + off, k.stride,
+                    const hipError_t e = hipMemcpy2DAsync(pixels + off, k.stride, c->d_out.as<const uint8_t>() + off, k.stride,
                                                           (size_t)k.blocks_w * N, (size_t)k.blocks_h * N, hipMemcpyDeviceToHost, st);
                     if (e != hipSuccess) return e;
                 }
@@ -1155,23 +1071,23 @@ int hvc_decode_frames_rgb(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, cons
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
     const int part = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)4 << 30) / px_fs));
-    if ((r = grow(c, &c->d_aux, &c->aux_cap, (size_t)part * px_fs))) return r;
+    if ((r = grow(c, c->d_aux, (size_t)part * px_fs))) return r;
     const int16_t *d_coefs = coefs;
     uint8_t *d_rgb = rgb;
     if (where == HVC_MEM_HOST) {
         const size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + coef_span) * sizeof(int16_t);
-        if ((r = grow(c, &c->d_in, &c->in_cap, cbytes))) return r;
-        if ((r = grow(c, &c->d_aux2, &c->aux2_cap, rgb_bytes(im, n_frames)))) return r;
-        HIPCHK(c, hipMemcpyAsync(c->d_in, coefs, cbytes, hipMemcpyHostToDevice, c->stream));
-        d_coefs = (const int16_t *)c->d_in;
-        d_rgb = (uint8_t *)c->d_aux2;
+        if ((r = grow(c, c->d_in, cbytes))) return r;
+        if ((r = grow(c, c->d_aux2, rgb_bytes(im, n_frames)))) return r;
+        HIPCHK(c, hipMemcpyAsync(c->d_in.p, coefs, cbytes, hipMemcpyHostToDevice, c->stream));
+        d_coefs = c->d_in.as<const int16_t>();
+        d_rgb = c->d_aux2.as<uint8_t>();
     }
     for (int f0 = 0; f0 < n_frames; f0 += part) {
         const int cnt = std::min(part, n_frames - f0);
-        if ((r = decode_frames_impl(c, d_coefs + (size_t)f0 * coef_fs, coef_fs, qtabs, n_qtabs, tight, n_comp, cnt, (uint8_t *)c->d_aux, px_fs,
+        if ((r = decode_frames_impl(c, d_coefs + (size_t)f0 * coef_fs, coef_fs, qtabs, n_qtabs, tight, n_comp, cnt, c->d_aux.as<uint8_t>(), px_fs,
                                     HVC_MEM_DEVICE, DecodeOpts(c))))
             return r;
-        HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, px_fs, tight, sampling, width, height, cw, ch, cnt,
+        HIPCHK(c, ycc_to_rgb_device(c->d_aux.as<const uint8_t>(), px_fs, tight, sampling, width, height, cw, ch, cnt,
                                     d_rgb + (size_t)f0 * im.frame_stride, im, c->stream, c->arith));
     }
     if (where == HVC_MEM_HOST) {
@@ -1191,20 +1107,20 @@ template <class Model, class Compare>
 static int divergence_chunks(hvc_ctx *c, const uint8_t *in, size_t in_fs, size_t in_span, size_t model_fs, int n_frames, uint8_t *max_diff,
                              size_t diff_fs, size_t blocks, int where, Model model, Compare compare) {
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)256 << 20) / model_fs));
-    int r = grow(c, &c->d_div_px, &c->div_px_cap, (size_t)chunk * model_fs);
+    int r = grow(c, c->d_div_px, (size_t)chunk * model_fs);
     if (r) return r;
     if (where == HVC_MEM_HOST) {
-        if ((r = grow(c, &c->d_div_in, &c->div_in_cap, (size_t)(chunk - 1) * in_fs + in_span))) return r;
-        if ((r = grow(c, &c->d_div_out, &c->div_out_cap, (size_t)(chunk - 1) * diff_fs + blocks))) return r;
+        if ((r = grow(c, c->d_div_in, (size_t)(chunk - 1) * in_fs + in_span))) return r;
+        if ((r = grow(c, c->d_div_out, (size_t)(chunk - 1) * diff_fs + blocks))) return r;
     }
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         const int cnt = std::min(chunk, n_frames - f0);
         const uint8_t *d_in = in + (size_t)f0 * in_fs;
         uint8_t *d_diff = max_diff + (size_t)f0 * diff_fs;
         if (where == HVC_MEM_HOST) {
-            HIPCHK(c, hipMemcpyAsync(c->d_div_in, d_in, (size_t)(cnt - 1) * in_fs + in_span, hipMemcpyHostToDevice, c->stream));
-            d_in = (const uint8_t *)c->d_div_in;
-            d_diff = (uint8_t *)c->d_div_out;
+            HIPCHK(c, hipMemcpyAsync(c->d_div_in.p, d_in, (size_t)(cnt - 1) * in_fs + in_span, hipMemcpyHostToDevice, c->stream));
+            d_in = c->d_div_in.as<const uint8_t>();
+            d_diff = c->d_div_out.as<uint8_t>();
         }
         if ((r = model(d_in, cnt))) return r;
         HIPCHK(c, compare(d_in, cnt, d_diff));
@@ -1244,14 +1160,14 @@ int hvc_decode_frames_divergence(hvc_ctx *c, const int16_t *coefs, size_t coef_f
     return divergence_chunks(
         c, (const uint8_t *)coefs, coef_fs * sizeof(int16_t), L.coef_span * sizeof(int16_t), px_fs, n_frames, max_diff, diff_fs, blocks, where,
         [&](const uint8_t *d_in, int cnt) {
-            return decode_frames_impl(c, (const int16_t *)d_in, coef_fs, qtabs, n_qtabs, tight, n_comp, cnt, (uint8_t *)c->d_div_px, px_fs,
+            return decode_frames_impl(c, (const int16_t *)d_in, coef_fs, qtabs, n_qtabs, tight, n_comp, cnt, c->d_div_px.as<uint8_t>(), px_fs,
                                       HVC_MEM_DEVICE, model);
         },
         [&](const uint8_t *d_in, int cnt, uint8_t *d_diff) {
             hvc::DecodeParams P;
             fill_geometry(P, L, coef_fs, px_fs, cnt);
             P.coefs = (const int16_t *)d_in;
-            P.pixels = (uint8_t *)c->d_div_px;
+            P.pixels = c->d_div_px.as<uint8_t>();
             hvc::HardcamlParams H = hardcaml_params(P, qtabs, n_qtabs);
             H.diff = d_diff;
             H.diff_fs = diff_fs;
@@ -1335,7 +1251,7 @@ int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
     const int split = (aligned && !wide_only && c->decode_kernel == 0 && height % 8 == 0 && P.pl[0].cbw == P.pl[0].bw) ? fused444_mode() : 0;
     const size_t luma_ids = split ? (size_t)per * (size_t)((P.pl[0].cbw * P.pl[0].cbh + HVC_TILE - 1) / HVC_TILE) * HVC_TILE : 0;
     if ((r = reserve_fix_list(c, luma_ids + (size_t)ids))) return r; // (the luma list sits behind the 4:4:4 kernels' list)
-    P.fix_list = c->d_fix_list;
+    P.fix_list = c->d_fix_list.as<unsigned>();
     wide_total_begin(c);
     if (split == 2 && !c->side_stream) {
         // (streams of one priority may share a hardware queue and then never overlap: HVC_444_SIDE_PRIO -1 / 0 / 1 =
@@ -1343,9 +1259,9 @@ int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
         static const int prio_sel = [] { const char *v = std::getenv("HVC_444_SIDE_PRIO"); return v ? std::atoi(v) : 0; }();
         int least = 0, greatest = 0;
         HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(c, hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, prio_sel < 0 ? greatest : prio_sel > 0 ? least : 0));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+        HIPCHK(c, c->side_stream.ensure(prio_sel < 0 ? greatest : prio_sel > 0 ? least : 0));
+        HIPCHK(c, c->ev_fork.ensure(hipEventDisableTiming));
+        HIPCHK(c, c->ev_join.ensure(hipEventDisableTiming));
     }
     auto launch_split = [&](hvc::Decode444Params &Q, hipEvent_t k0, hipEvent_t k1) -> hipError_t {
         const hvc::Plane444K &K = Q.pl[0];
@@ -1369,10 +1285,10 @@ int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
         prepare_tables(qtabs, n_qtabs, Y.qt, Y.ethr, Y.ethr_packed, Y.qpair);
         Y.dc_plane = Q.dc_plane;
         Y.dc_fs = Q.dc_fs;
-        Y.fix_count = c->d_fix_count + 4 + c->fix_phase_l;
-        Y.fix_count_next = c->d_fix_count + 4 + (c->fix_phase_l ^ 1);
-        Y.fix_list = c->d_fix_list + (size_t)ids;
-        Y.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count + 2);
+        Y.fix_count = c->d_fix_count.as<unsigned>() + 4 + c->fix_phase_l;
+        Y.fix_count_next = c->d_fix_count.as<unsigned>() + 4 + (c->fix_phase_l ^ 1);
+        Y.fix_list = c->d_fix_list.as<unsigned>() + (size_t)ids;
+        Y.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count.as<unsigned>() + 2);
         fix_assign(c, Q);
         Q.tile0 = Q.y_tiles; // the chroma tiles alone
         hipStream_t ys = c->stream;
@@ -1447,12 +1363,12 @@ int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
     return through_device(
         c, n_frames, cbytes, obytes, cbytes, true,
         [&](int f0, int cnt) {
-            return hipMemcpyAsync((int16_t *)c->d_in + (size_t)f0 * coef_fs, coefs + (size_t)f0 * coef_fs,
+            return hipMemcpyAsync(c->d_in.as<int16_t>() + (size_t)f0 * coef_fs, coefs + (size_t)f0 * coef_fs,
                                   ((size_t)(cnt - 1) * coef_fs + L.coef_span) * sizeof(int16_t), hipMemcpyHostToDevice, c->stream);
         },
-        [&](int f0, int cnt) { return launch_range((const int16_t *)c->d_in, (uint8_t *)c->d_out, f0, cnt, nullptr, nullptr); },
+        [&](int f0, int cnt) { return launch_range(c->d_in.as<const int16_t>(), c->d_out.as<uint8_t>(), f0, cnt, nullptr, nullptr); },
         [&](int f0, int cnt, hipStream_t st) { // (frame_stride is irrelevant for a single frame, and may be smaller than the frame)
-            return copy_run_d2h((const uint8_t *)c->d_out, frames, 0, out_span, frame_stride, f0, cnt, st);
+            return copy_run_d2h(c->d_out.as<const uint8_t>(), frames, 0, out_span, frame_stride, f0, cnt, st);
         });
 }
 
@@ -1552,12 +1468,12 @@ int encode_frames_impl(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const
     return through_device(
         c, n_frames, pbytes, cbytes, cbytes, run.len != 0, // (overlapped: large batches in the usual form)
         [&](int f0, int cnt) {
-            return hipMemcpyAsync((uint8_t *)c->d_in + (size_t)f0 * pixel_fs, pixels + (size_t)f0 * pixel_fs,
+            return hipMemcpyAsync(c->d_in.as<uint8_t>() + (size_t)f0 * pixel_fs, pixels + (size_t)f0 * pixel_fs,
                                   (size_t)(cnt - 1) * pixel_fs + L.pixel_span, hipMemcpyHostToDevice, c->stream);
         },
-        [&](int f0, int cnt) { return launch_range((const uint8_t *)c->d_in, (int16_t *)c->d_out, f0, cnt, nullptr, nullptr); },
+        [&](int f0, int cnt) { return launch_range(c->d_in.as<const uint8_t>(), c->d_out.as<int16_t>(), f0, cnt, nullptr, nullptr); },
         [&](int f0, int cnt, hipStream_t st) {
-            return download_coefs(comps, n_comp, run, f0, cnt, coef_fs * sizeof(int16_t), (const uint8_t *)c->d_out, (uint8_t *)coefs, st);
+            return download_coefs(comps, n_comp, run, f0, cnt, coef_fs * sizeof(int16_t), c->d_out.as<const uint8_t>(), (uint8_t *)coefs, st);
         });
 }
 
@@ -1593,16 +1509,16 @@ int hvc_encode_frames_recon(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, 
     uint8_t *d_recon = recon, *d_error = error;
     if (where == HVC_MEM_HOST) { // [pixels | recon | error] in one scratch allocation, coefficients in another
         const size_t slot = (pbytes + 255) & ~(size_t)255;
-        if ((r = grow(c, &c->d_aux, &c->aux_cap, 3 * slot))) return r;
-        if ((r = grow(c, &c->d_aux2, &c->aux2_cap, cbytes))) return r;
-        d_pix = (const uint8_t *)c->d_aux;
-        d_recon = (uint8_t *)c->d_aux + slot;
-        d_error = (uint8_t *)c->d_aux + 2 * slot;
-        d_coefs = (int16_t *)c->d_aux2;
-        HIPCHK(c, hipMemcpyAsync(c->d_aux, pixels, pbytes, hipMemcpyHostToDevice, c->stream));
+        if ((r = grow(c, c->d_aux, 3 * slot))) return r;
+        if ((r = grow(c, c->d_aux2, cbytes))) return r;
+        d_pix = c->d_aux.as<const uint8_t>();
+        d_recon = c->d_aux.as<uint8_t>() + slot;
+        d_error = c->d_aux.as<uint8_t>() + 2 * slot;
+        d_coefs = c->d_aux2.as<int16_t>();
+        HIPCHK(c, hipMemcpyAsync(c->d_aux.p, pixels, pbytes, hipMemcpyHostToDevice, c->stream));
     } else if (!recon) { // the error plane needs the reconstruction somewhere
-        if ((r = grow(c, &c->d_aux, &c->aux_cap, pbytes))) return r;
-        d_recon = (uint8_t *)c->d_aux;
+        if ((r = grow(c, c->d_aux, pbytes))) return r;
+        d_recon = c->d_aux.as<uint8_t>();
     }
     if ((r = encode_frames_impl(c, d_pix, pixel_fs, qtabs, n_qtabs, comps, n_comp, n_frames, d_coefs, coef_fs, HVC_MEM_DEVICE, enc)))
         return r;
@@ -1677,13 +1593,13 @@ int hvc_encode_frames_divergence(hvc_ctx *c, const uint8_t *pixels, size_t pixel
     return divergence_chunks(
         c, pixels, pixel_fs, L.pixel_span, cf * sizeof(int16_t), n_frames, max_diff, diff_fs, blocks, where,
         [&](const uint8_t *d_pix, int cnt) {
-            return encode_frames_impl(c, d_pix, pixel_fs, qtabs, n_qtabs, tight, n_comp, cnt, (int16_t *)c->d_div_px, cf, HVC_MEM_DEVICE, model);
+            return encode_frames_impl(c, d_pix, pixel_fs, qtabs, n_qtabs, tight, n_comp, cnt, c->d_div_px.as<int16_t>(), cf, HVC_MEM_DEVICE, model);
         },
         [&](const uint8_t *d_pix, int cnt, uint8_t *d_diff) {
             hvc::EncodeParams P;
             fill_geometry(P, T, cf, pixel_fs, cnt);
             P.pixels = d_pix;
-            P.coefs = (int16_t *)c->d_div_px;
+            P.coefs = c->d_div_px.as<int16_t>();
             hvc::HardcamlEncodeParams H = hardcaml_encode_params(P, qtabs, n_qtabs);
             H.diff = d_diff;
             H.diff_fs = diff_fs;
@@ -1728,14 +1644,14 @@ int hvc_upsample420(hvc_ctx *c, const uint8_t *src, int cw, int ch, size_t src_s
     }
     size_t sbytes = (size_t)(n_planes - 1) * src_ps + (size_t)(ch - 1) * src_stride + (size_t)cw;
     size_t dbytes = (size_t)(n_planes - 1) * dst_ps + (size_t)(2 * ch - 1) * dst_stride + (size_t)cw * 2;
-    int r = grow(c, &c->d_in, &c->in_cap, sbytes);
+    int r = grow(c, c->d_in, sbytes);
     if (r) return r;
-    r = grow(c, &c->d_out, &c->out_cap, dbytes);
+    r = grow(c, c->d_out, dbytes);
     if (r) return r;
-    HIPCHK(c, hipMemcpyAsync(c->d_in, src, sbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_all((const uint8_t *)c->d_in, (uint8_t *)c->d_out));
+    HIPCHK(c, hipMemcpyAsync(c->d_in.p, src, sbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_all(c->d_in.as<const uint8_t>(), c->d_out.as<uint8_t>()));
     for (int p = 0; p < n_planes; p++)
-        HIPCHK(c, hipMemcpy2DAsync(dst + (size_t)p * dst_ps, dst_stride, (uint8_t *)c->d_out + (size_t)p * dst_ps,
+        HIPCHK(c, hipMemcpy2DAsync(dst + (size_t)p * dst_ps, dst_stride, c->d_out.as<uint8_t>() + (size_t)p * dst_ps,
                                    dst_stride, (size_t)cw * 2, (size_t)ch * 2, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HVC_OK;
@@ -1777,21 +1693,14 @@ bool prec_ok(int rom, int tp) { return rom >= 0 && rom <= HVC_DCT_ROM_PREC_MAX &
 // the context's copy of the tables (uploaded at its first DCT call) and the word k_dct_fixed flags range errors in
 int dct_tables(hvc_ctx *c, const DctTables **d_tab, unsigned **d_bad) {
     if (!c->d_dct_tab) {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, sizeof(DctTables) + 256);
-        if (e != hipSuccess) {
-            c->last_hip = (int)e;
-            return HVC_E_OUT_OF_MEMORY;
-        }
-        e = hipMemcpy(p, &dct_host_tables(), sizeof(DctTables), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            return fail_hip(c, e);
-        }
-        c->d_dct_tab = p;
+        Buf t; // (the context holds the tables only once the copy has succeeded)
+        const int r = grow(c, t, sizeof(DctTables) + 256, GROW_EXACT);
+        if (r) return r;
+        HIPCHK(c, hipMemcpy(t.p, &dct_host_tables(), sizeof(DctTables), hipMemcpyHostToDevice));
+        c->d_dct_tab.adopt(t);
     }
-    *d_tab = (const DctTables *)c->d_dct_tab;
-    if (d_bad) *d_bad = (unsigned *)((char *)c->d_dct_tab + sizeof(DctTables));
+    *d_tab = c->d_dct_tab.as<const DctTables>();
+    if (d_bad) *d_bad = (unsigned *)(c->d_dct_tab.as<char>() + sizeof(DctTables));
     return HVC_OK;
 }
 
@@ -1844,11 +1753,11 @@ int hvc_dct_fixed(hvc_ctx *c, int direction, int rom_prec, int transpose_prec, c
     const int32_t *d_in = in;
     int32_t *d_out = out;
     if (where == HVC_MEM_HOST) {
-        if ((r = grow(c, &c->d_dct_a, &c->dct_a_cap, bytes))) return r;
-        if ((r = grow(c, &c->d_dct_b, &c->dct_b_cap, bytes))) return r;
-        HIPCHK(c, hipMemcpyAsync(c->d_dct_a, in, bytes, hipMemcpyHostToDevice, c->stream));
-        d_in = (const int32_t *)c->d_dct_a;
-        d_out = (int32_t *)c->d_dct_b;
+        if ((r = grow(c, c->d_dct_a, bytes))) return r;
+        if ((r = grow(c, c->d_dct_b, bytes))) return r;
+        HIPCHK(c, hipMemcpyAsync(c->d_dct_a.p, in, bytes, hipMemcpyHostToDevice, c->stream));
+        d_in = c->d_dct_a.as<const int32_t>();
+        d_out = c->d_dct_b.as<int32_t>();
     }
     HIPCHK(c, hipMemsetAsync(bad, 0, sizeof(unsigned), c->stream));
     HIPCHK(c, hvc::launch_dct_fixed(tab, direction == HVC_DCT_INVERSE, rom_prec, transpose_prec, d_in, d_out, n_blocks, bad,
@@ -1871,11 +1780,11 @@ int hvc_dct_reference(hvc_ctx *c, int direction, const int32_t *in, double *out,
     const int32_t *d_in = in;
     double *d_out = out;
     if (where == HVC_MEM_HOST) {
-        if ((r = grow(c, &c->d_dct_a, &c->dct_a_cap, ibytes))) return r;
-        if ((r = grow(c, &c->d_dct_b, &c->dct_b_cap, obytes))) return r;
-        HIPCHK(c, hipMemcpyAsync(c->d_dct_a, in, ibytes, hipMemcpyHostToDevice, c->stream));
-        d_in = (const int32_t *)c->d_dct_a;
-        d_out = (double *)c->d_dct_b;
+        if ((r = grow(c, c->d_dct_a, ibytes))) return r;
+        if ((r = grow(c, c->d_dct_b, obytes))) return r;
+        HIPCHK(c, hipMemcpyAsync(c->d_dct_a.p, in, ibytes, hipMemcpyHostToDevice, c->stream));
+        d_in = c->d_dct_a.as<const int32_t>();
+        d_out = c->d_dct_b.as<double>();
     }
     HIPCHK(c, hvc::launch_dct_reference(tab, direction == HVC_DCT_INVERSE, d_in, d_out, n_blocks, c->stream));
     if (where == HVC_MEM_HOST) {
@@ -1924,9 +1833,9 @@ int hvc_dct_error_search(hvc_ctx *c, const hvc_dct_config *cfg, size_t n_cfg, ui
     }
     const size_t cfg_bytes = (n_cfg * sizeof(DctCfg) + 255) & ~(size_t)255;
     const size_t worst_bytes = n_cfg * sizeof(DctWorst);
-    if ((r = grow(c, &c->d_dct_a, &c->dct_a_cap, cfg_bytes + worst_bytes + slab * sizeof(DctWorst)))) return r;
-    DctCfg *d_cfg = (DctCfg *)c->d_dct_a;
-    DctWorst *d_worst = (DctWorst *)((char *)c->d_dct_a + cfg_bytes);
+    if ((r = grow(c, c->d_dct_a, cfg_bytes + worst_bytes + slab * sizeof(DctWorst)))) return r;
+    DctCfg *d_cfg = c->d_dct_a.as<DctCfg>();
+    DctWorst *d_worst = (DctWorst *)(c->d_dct_a.as<char>() + cfg_bytes);
     DctWorst *d_slab = d_worst + n_cfg;
     HIPCHK(c, hipMemcpyAsync(d_cfg, sorted.data(), n_cfg * sizeof(DctCfg), hipMemcpyHostToDevice, c->stream));
     for (int m = 0; m < 3; m++) {

@@ -25,30 +25,9 @@ int slot_of(hvc_ctx *c, int slot, hvc_ctx::Slot **out) {
 
 // streams and the slot's events, created by the first submission that needs them
 int slot_prepare(hvc_ctx *c, hvc_ctx::Slot &s) {
-    if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    if (!c->down_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->down_stream, hipStreamNonBlocking));
-    hipEvent_t *const ev[6] = {&s.up0, &s.up1, &s.k0, &s.k1, &s.dn0, &s.dn1};
-    for (hipEvent_t *e : ev)
-        if (!*e) HIPCHK(c, hipEventCreate(e));
-    return HVC_OK;
-}
-
-// the slot is free: nothing of it is in flight, its buffers may be replaced
-int slot_grow(hvc_ctx *c, void **p, size_t *cap, size_t need) {
-    if (need <= *cap) return HVC_OK;
-    if (*p) {
-        HIPCHK(c, hipFree(*p));
-        *p = nullptr;
-        *cap = 0;
-    }
-    const size_t want = need + need / 8 + 4096;
-    const hipError_t e = hipMalloc(p, want);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        c->last_hip = (int)e;
-        return HVC_E_OUT_OF_MEMORY;
-    }
-    *cap = want;
+    HIPCHK(c, c->copy_stream.ensure());
+    HIPCHK(c, c->down_stream.ensure());
+    for (Event *e : {&s.up0, &s.up1, &s.k0, &s.k1, &s.dn0, &s.dn1}) HIPCHK(c, e->ensure());
     return HVC_OK;
 }
 
@@ -135,13 +114,13 @@ int hvc_decode_frames_submit(hvc_ctx *c, int slot, const int16_t *coefs, size_t 
     const size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + L.coef_span) * sizeof(int16_t);
     const size_t pbytes = (size_t)(n_frames - 1) * pixel_fs + L.pixel_span;
     const bool down = pixels_where == HVC_MEM_HOST;
-    if ((r = slot_grow(c, &s.d_in, &s.in_cap, cbytes))) return r;
-    if (down && (r = slot_grow(c, &s.d_out, &s.out_cap, pbytes))) return r;
-    uint8_t *const d_pixels = down ? (uint8_t *)s.d_out : pixels;
+    if ((r = grow(c, s.d_in, cbytes, GROW_SLOT))) return r;
+    if (down && (r = grow(c, s.d_out, pbytes, GROW_SLOT))) return r;
+    uint8_t *const d_pixels = down ? s.d_out.as<uint8_t>() : pixels;
 
     // upload on the copy stream; the block stage waits for it on the context's stream
     HIPCHK(c, hipEventRecord(s.up0, c->copy_stream));
-    hipError_t e = hipMemcpyAsync(s.d_in, coefs, cbytes, hipMemcpyHostToDevice, c->copy_stream);
+    hipError_t e = hipMemcpyAsync(s.d_in.p, coefs, cbytes, hipMemcpyHostToDevice, c->copy_stream);
     if (e == hipSuccess) e = hipEventRecord(s.up1, c->copy_stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, s.up1, 0);
     if (e == hipSuccess) e = hipEventRecord(s.k0, c->stream);
@@ -150,7 +129,7 @@ int hvc_decode_frames_submit(hvc_ctx *c, int slot, const int16_t *coefs, size_t 
     // is for hvc_set_profiling's callers, the slot has its pair)
     DecodeOpts o(c);
     o.profile = false;
-    r = decode_frames_impl(c, (const int16_t *)s.d_in, coef_fs, qtabs, n_qtabs, kept, n_comp, n_frames, d_pixels, pixel_fs,
+    r = decode_frames_impl(c, s.d_in.as<const int16_t>(), coef_fs, qtabs, n_qtabs, kept, n_comp, n_frames, d_pixels, pixel_fs,
                            HVC_MEM_DEVICE, o);
     if (r) return abandon(c, r);
     e = hipEventRecord(s.k1, c->stream);
@@ -158,7 +137,7 @@ int hvc_decode_frames_submit(hvc_ctx *c, int slot, const int16_t *coefs, size_t 
         e = hipStreamWaitEvent(c->down_stream, s.k1, 0);
         if (e == hipSuccess) e = hipEventRecord(s.dn0, c->down_stream);
         if (e == hipSuccess)
-            e = download_pixels(kept, n_comp, pixel_run(kept, n_comp), 0, n_frames, pixel_fs, (const uint8_t *)s.d_out, pixels,
+            e = download_pixels(kept, n_comp, pixel_run(kept, n_comp), 0, n_frames, pixel_fs, s.d_out.as<const uint8_t>(), pixels,
                                 c->down_stream);
         if (e == hipSuccess) e = hipEventRecord(s.dn1, c->down_stream);
     }
@@ -197,26 +176,26 @@ int hvc_encode_frames_submit(hvc_ctx *c, int slot, const uint8_t *pixels, size_t
     const size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + L.coef_span) * sizeof(int16_t);
     const size_t pbytes = (size_t)(n_frames - 1) * pixel_fs + L.pixel_span;
     const bool down = coefs_where == HVC_MEM_HOST;
-    if ((r = slot_grow(c, &s.d_in, &s.in_cap, pbytes))) return r;
-    if (down && (r = slot_grow(c, &s.d_out, &s.out_cap, cbytes))) return r;
-    int16_t *const d_coefs = down ? (int16_t *)s.d_out : coefs;
+    if ((r = grow(c, s.d_in, pbytes, GROW_SLOT))) return r;
+    if (down && (r = grow(c, s.d_out, cbytes, GROW_SLOT))) return r;
+    int16_t *const d_coefs = down ? s.d_out.as<int16_t>() : coefs;
 
     HIPCHK(c, hipEventRecord(s.up0, c->copy_stream));
-    hipError_t e = hipMemcpyAsync(s.d_in, pixels, pbytes, hipMemcpyHostToDevice, c->copy_stream);
+    hipError_t e = hipMemcpyAsync(s.d_in.p, pixels, pbytes, hipMemcpyHostToDevice, c->copy_stream);
     if (e == hipSuccess) e = hipEventRecord(s.up1, c->copy_stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, s.up1, 0);
     if (e == hipSuccess) e = hipEventRecord(s.k0, c->stream);
     if (e != hipSuccess) return abandon(c, fail_hip(c, e));
     EncodeOpts o(c); // (its own event ring: as in hvc_decode_frames_submit)
     o.profile = false;
-    r = encode_frames_impl(c, (const uint8_t *)s.d_in, pixel_fs, qtabs, n_qtabs, comps, n_comp, n_frames, d_coefs, coef_fs, HVC_MEM_DEVICE, o);
+    r = encode_frames_impl(c, s.d_in.as<const uint8_t>(), pixel_fs, qtabs, n_qtabs, comps, n_comp, n_frames, d_coefs, coef_fs, HVC_MEM_DEVICE, o);
     if (r) return abandon(c, r);
     e = hipEventRecord(s.k1, c->stream);
     if (e == hipSuccess && down) {
         e = hipStreamWaitEvent(c->down_stream, s.k1, 0);
         if (e == hipSuccess) e = hipEventRecord(s.dn0, c->down_stream);
         if (e == hipSuccess)
-            e = download_coefs(comps, n_comp, coef_run(comps, n_comp), 0, n_frames, coef_fs * sizeof(int16_t), (const uint8_t *)s.d_out,
+            e = download_coefs(comps, n_comp, coef_run(comps, n_comp), 0, n_frames, coef_fs * sizeof(int16_t), s.d_out.as<const uint8_t>(),
                                (uint8_t *)coefs, c->down_stream);
         if (e == hipSuccess) e = hipEventRecord(s.dn1, c->down_stream);
     }

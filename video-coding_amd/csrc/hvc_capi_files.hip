@@ -11,14 +11,10 @@ static int upload_enc_tables(hvc_ctx *c) {
     if (c->hd_tables) return HVC_OK;
     uint32_t t[2][16 + 256];
     hvc::default_enc_tables(t);
-    unsigned *d = nullptr;
-    HIPCHK(c, hipMalloc((void **)&d, sizeof t));
-    const hipError_t e = hipMemcpy(d, t, sizeof t, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail_hip(c, e);
-    }
-    c->hd_tables = d;
+    Buf d;
+    if (grow(c, d, sizeof t, GROW_EXACT)) return HVC_E_HIP; // (last_hip says why)
+    HIPCHK(c, hipMemcpy(d.p, t, sizeof t, hipMemcpyHostToDevice));
+    c->hd_tables.adopt(d);
     return HVC_OK;
 }
 
@@ -35,7 +31,7 @@ int hvc_huffman_code_tables(hvc_ctx *c, int table_set, int where, uint32_t *code
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
     int r = upload_enc_tables(c);
     if (r) return r;
-    HIPCHK(c, hipMemcpy(codes, c->hd_tables + (size_t)table_set * (16 + 256), (16 + 256) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(codes, c->hd_tables.as<unsigned>() + (size_t)table_set * (16 + 256), (16 + 256) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return HVC_OK;
 } HVC_ABI_CATCH
 
@@ -89,33 +85,33 @@ int huffman_prepare(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *d_coef
     const size_t nf = (size_t)n_frames;
     if (optimised) { // per frame: counts, code tables (both HUFF_TABLE_WORDS words), four specs
         const size_t words = nf * hvc::HUFF_TABLE_WORDS;
-        if ((r = grow(c, &c->hd_opt, &c->hd_opt_cap, 2 * words * sizeof(unsigned) + nf * 4 * sizeof(hvc_huff_spec)))) return r;
-        P.hist = (unsigned *)c->hd_opt;
+        if ((r = grow(c, c->hd_opt, 2 * words * sizeof(unsigned) + nf * 4 * sizeof(hvc_huff_spec)))) return r;
+        P.hist = c->hd_opt.as<unsigned>();
         P.opt_tables = P.hist + words;
         P.specs = (hvc_huff_spec *)(P.opt_tables + words);
         P.tables = P.opt_tables;
         P.table_stride = hvc::HUFF_TABLE_WORDS;
     } else {
         if ((r = upload_enc_tables(c))) return r;
-        P.tables = c->hd_tables;
+        P.tables = c->hd_tables.as<unsigned>();
     }
-    if ((r = grow(c, &c->hd_lens, &c->hd_lens_cap, nf * bpf * sizeof(unsigned)))) return r;
-    if ((r = grow(c, &c->hd_meta, &c->hd_meta_cap, (4 * nf + 2 * (nf + 1) + 4) * sizeof(unsigned) + 64))) return r;
-    if ((r = grow(c, &c->hd_bitbuf, &c->hd_bitbuf_cap, nf * P.bitbuf_words * sizeof(unsigned)))) return r;
-    if ((r = grow(c, &c->hd_ff, &c->hd_ff_cap, nf * P.ff_stride * sizeof(unsigned)))) return r;
-    P.lens = (unsigned *)c->hd_lens;
-    unsigned *m = (unsigned *)c->hd_meta;
+    if ((r = grow(c, c->hd_lens, nf * bpf * sizeof(unsigned)))) return r;
+    if ((r = grow(c, c->hd_meta, (4 * nf + 2 * (nf + 1) + 4) * sizeof(unsigned) + 64))) return r;
+    if ((r = grow(c, c->hd_bitbuf, nf * P.bitbuf_words * sizeof(unsigned)))) return r;
+    if ((r = grow(c, c->hd_ff, nf * P.ff_stride * sizeof(unsigned)))) return r;
+    P.lens = c->hd_lens.as<unsigned>();
+    unsigned *m = c->hd_meta.as<unsigned>();
     P.status = m;
     P.frame_bits = m + 4;
     P.frame_bytes = P.frame_bits + nf;
     P.frame_pieces = P.frame_bytes + nf;
     P.frame_ff = P.frame_pieces + nf;
     unsigned long long *scratch_off = (unsigned long long *)(((uintptr_t)(P.frame_ff + nf) + 7) & ~(uintptr_t)7);
-    P.bitbuf = (unsigned *)c->hd_bitbuf;
-    P.ff = (unsigned *)c->hd_ff;
+    P.bitbuf = c->hd_bitbuf.as<unsigned>();
+    P.ff = c->hd_ff.as<unsigned>();
     if (n_ivl) {
-        if ((r = grow(c, &c->hd_ivl, &c->hd_ivl_cap, nf * (size_t)n_ivl * sizeof(unsigned)))) return r;
-        P.ivl = (unsigned *)c->hd_ivl;
+        if ((r = grow(c, c->hd_ivl, nf * (size_t)n_ivl * sizeof(unsigned)))) return r;
+        P.ivl = c->hd_ivl.as<unsigned>();
     }
     P.out_offsets = d_offsets ? d_offsets : scratch_off;
     P.out = d_out;
@@ -161,12 +157,12 @@ static int huffman_encode_frames_impl(hvc_ctx *c, const hvc_jpeg_info *info, con
         HIPCHK(c, hipStreamSynchronize(c->stream));
     } else {
         const size_t cbytes = ((size_t)(n_frames - 1) * coef_fs + info->coef_count) * sizeof(int16_t);
-        if ((r = grow(c, &c->d_in, &c->in_cap, cbytes))) return r;
-        if ((r = grow(c, &c->hd_out, &c->hd_out_cap, out_cap))) return r;
-        if ((r = huffman_prepare(c, info, (const int16_t *)c->d_in, coef_fs, n_frames, (uint8_t *)c->hd_out, out_cap, nullptr, P,
+        if ((r = grow(c, c->d_in, cbytes))) return r;
+        if ((r = grow(c, c->hd_out, out_cap))) return r;
+        if ((r = huffman_prepare(c, info, c->d_in.as<const int16_t>(), coef_fs, n_frames, c->hd_out.as<uint8_t>(), out_cap, nullptr, P,
                                    specs != nullptr, restart)))
             return r;
-        HIPCHK(c, hipMemcpyAsync(c->d_in, coefs, cbytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_in.p, coefs, cbytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hvc::launch_huffman_encode(P, c->stream));
         HIPCHK(c, hipMemcpyAsync(&status, P.status, sizeof status, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(offsets, P.out_offsets, (size_t)(n_frames + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
@@ -175,7 +171,7 @@ static int huffman_encode_frames_impl(hvc_ctx *c, const hvc_jpeg_info *info, con
             HIPCHK(c, hipMemcpyAsync(specs, P.specs, (size_t)n_frames * 4 * sizeof(hvc_huff_spec), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (!(status & 7u) && offsets[n_frames] <= out_cap)
-            HIPCHK(c, hipMemcpy(out, c->hd_out, (size_t)offsets[n_frames], hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(out, c->hd_out.p, (size_t)offsets[n_frames], hipMemcpyDeviceToHost));
     }
     if (status & 1u) return HVC_E_RANGE;       // a value the tables have no code for (DC category > 11, AC size > 10)
     if (status & 6u) return HVC_E_INVALID_ARG; // out_cap too small
@@ -236,14 +232,14 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
 
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    if (!c->down_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->down_stream, hipStreamNonBlocking));
+    HIPCHK(c, c->copy_stream.ensure());
+    HIPCHK(c, c->down_stream.ensure());
     for (int i = 0; i < NB; i++) {
-        if (!c->ev_up[i]) HIPCHK(c, hipEventCreate(&c->ev_up[i]));
-        if (!c->ev_down[i]) HIPCHK(c, hipEventCreate(&c->ev_down[i]));
+        HIPCHK(c, c->ev_up[i].ensure());
+        HIPCHK(c, c->ev_down[i].ensure());
         for (int k = 0; k < 3; k++)
-            if (!c->ev_et[i][k]) HIPCHK(c, hipEventCreate(&c->ev_et[i][k]));
-        if (!c->ev_gpu[i]) HIPCHK(c, hipEventCreate(&c->ev_gpu[i]));
+            HIPCHK(c, c->ev_et[i][k].ensure());
+        HIPCHK(c, c->ev_gpu[i].ensure());
     }
     std::vector<uint8_t> header_default;
     const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // each file its own tables (hvc_set_huffman_tables)
@@ -288,7 +284,7 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
             int e = HVC_OK;
             if (error.load() == 0) try {
                 if (t.kind == 0) {
-                    uint8_t *rec = (uint8_t *)c->eh_in[slot] + (size_t)(f - k * C) * pix_bytes;
+                    uint8_t *rec = c->eh_in[slot].as<uint8_t>() + (size_t)(f - k * C) * pix_bytes;
                     const uint8_t *src = frames[f];
                     for (int i = 0; i < 3; i++) {
                         const hvc_component &L = info.layout[i];
@@ -307,22 +303,22 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
                         src += (size_t)sw[i] * sh[i];
                     }
                 } else if (!gpu_entropy) {
-                    const int16_t *cf = (const int16_t *)c->eh_out[slot] + (size_t)(f - k * C) * info.coef_count;
+                    const int16_t *cf = c->eh_out[slot].as<const int16_t>() + (size_t)(f - k * C) * info.coef_count;
                     e = opt ? hvc::entropy_encode_optimised(&info, cf, jpegs[f], caps[f], &sizes[f], ri)
                             : hvc::entropy_encode_file(&info, nullptr, cf, jpegs[f], caps[f], &sizes[f], ri);
                 } else { // header + the frame's segment + EOI (complete_and_write_eoi, encoder.ml:507-510)
-                    const unsigned long long *off = (const unsigned long long *)c->eh_off[slot];
+                    const unsigned long long *off = c->eh_off[slot].as<const unsigned long long>();
                     const int fi = f - k * C;
                     const size_t seg = (size_t)(off[fi + 1] - off[fi]);
                     std::vector<uint8_t> own; // optimised: the frame's own DHT bodies
-                    if (opt) hvc::jpeg_header_bytes(&info, own, (const hvc_huff_spec *)c->eh_specs[slot] + 4 * fi, ri);
+                    if (opt) hvc::jpeg_header_bytes(&info, own, c->eh_specs[slot].as<const hvc_huff_spec>() + 4 * fi, ri);
                     const std::vector<uint8_t> &header = opt ? own : header_default;
                     sizes[f] = header.size() + seg + 2;
                     if (sizes[f] > caps[f]) {
                         e = HVC_E_INVALID_ARG;
                     } else {
                         std::memcpy(jpegs[f], header.data(), header.size());
-                        std::memcpy(jpegs[f] + header.size(), (const uint8_t *)c->eh_out[slot] + off[fi], seg);
+                        std::memcpy(jpegs[f] + header.size(), c->eh_out[slot].as<const uint8_t>() + off[fi], seg);
                         jpegs[f][header.size() + seg] = 0xff;
                         jpegs[f][header.size() + seg + 1] = 0xd9;
                     }
@@ -378,37 +374,37 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
             if (j >= NB) wait_for(ent_done, j - NB);
             hipError_t he = hipEventRecord(c->ev_et[slot][0], c->copy_stream);
             if (he == hipSuccess)
-                he = hipMemcpyAsync(c->ed_in[slot], c->eh_in[slot], pix_bytes * (size_t)cnt, hipMemcpyHostToDevice,
+                he = hipMemcpyAsync(c->ed_in[slot].p, c->eh_in[slot].p, pix_bytes * (size_t)cnt, hipMemcpyHostToDevice,
                                     c->copy_stream);
             if (he == hipSuccess) he = hipEventRecord(c->ev_up[slot], c->copy_stream);
             if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_up[slot], 0);
             if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][1], compute);
             if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-            rc = encode_frames_impl(c, (const uint8_t *)c->ed_in[slot], pix_bytes, &info.qtabs[0][0], info.n_qtabs,
-                                    info.layout, 3, cnt, (int16_t *)c->ed_out[slot], info.coef_count, HVC_MEM_DEVICE, block_stage);
+            rc = encode_frames_impl(c, c->ed_in[slot].as<const uint8_t>(), pix_bytes, &info.qtabs[0][0], info.n_qtabs,
+                                    info.layout, 3, cnt, c->ed_out[slot].as<int16_t>(), info.coef_count, HVC_MEM_DEVICE, block_stage);
             if (rc) break;
             if (!gpu_entropy) {
                 he = hipEventRecord(c->ev_et[slot][2], compute);
                 if (he == hipSuccess)
-                    he = hipMemcpyAsync(c->eh_out[slot], c->ed_out[slot], coef_bytes * (size_t)cnt, hipMemcpyDeviceToHost,
+                    he = hipMemcpyAsync(c->eh_out[slot].p, c->ed_out[slot].p, coef_bytes * (size_t)cnt, hipMemcpyDeviceToHost,
                                         compute);
                 if (he == hipSuccess) he = hipEventRecord(c->ev_down[slot], compute);
             } else {
                 hvc::HuffParams HP;
-                rc = huffman_prepare(c, &info, (const int16_t *)c->ed_out[slot], info.coef_count, cnt,
-                                     (uint8_t *)c->ed_seg[slot], out_bytes, (unsigned long long *)c->ed_off[slot], HP, opt, ri);
+                rc = huffman_prepare(c, &info, c->ed_out[slot].as<const int16_t>(), info.coef_count, cnt,
+                                     c->ed_seg[slot].as<uint8_t>(), out_bytes, c->ed_off[slot].as<unsigned long long>(), HP, opt, ri);
                 if (rc) break;
                 he = hvc::launch_huffman_encode(HP, compute);
                 if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][2], compute);
                 // offsets, then the status word behind them (slot C + 1 of the pinned array)
                 if (he == hipSuccess)
-                    he = hipMemcpyAsync(c->eh_off[slot], c->ed_off[slot], ((size_t)cnt + 1) * sizeof(unsigned long long),
+                    he = hipMemcpyAsync(c->eh_off[slot].p, c->ed_off[slot].p, ((size_t)cnt + 1) * sizeof(unsigned long long),
                                         hipMemcpyDeviceToHost, compute);
                 if (he == hipSuccess)
-                    he = hipMemcpyAsync((unsigned long long *)c->eh_off[slot] + C + 1, HP.status, sizeof(unsigned),
+                    he = hipMemcpyAsync(c->eh_off[slot].as<unsigned long long>() + C + 1, HP.status, sizeof(unsigned),
                                         hipMemcpyDeviceToHost, compute);
                 if (he == hipSuccess && opt) // (the context's scratch: copied before the next chunk's coder reuses it)
-                    he = hipMemcpyAsync(c->eh_specs[slot], HP.specs, (size_t)cnt * 4 * sizeof(hvc_huff_spec),
+                    he = hipMemcpyAsync(c->eh_specs[slot].p, HP.specs, (size_t)cnt * 4 * sizeof(hvc_huff_spec),
                                         hipMemcpyDeviceToHost, compute);
                 if (he == hipSuccess) he = hipEventRecord(c->ev_gpu[slot], compute);
             }
@@ -432,7 +428,7 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
                 hipError_t he = wait_event(c->ev_gpu[slot]);
                 if (he != hipSuccess) { rc = fail_hip(c, he); break; }
                 if (hipEventElapsedTime(&ms, c->ev_et[slot][0], c->ev_up[slot]) == hipSuccess) h2d_ms += ms;
-                const unsigned long long *off = (const unsigned long long *)c->eh_off[slot];
+                const unsigned long long *off = c->eh_off[slot].as<const unsigned long long>();
                 const int cnt = chunk_count(e);
                 const unsigned status = (unsigned)off[C + 1];
                 if (status & 1u) { rc = HVC_E_RANGE; break; }              // a value without a code
@@ -440,7 +436,7 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
                 if (e >= NB) wait_for(ent_done, e - NB); // the pinned segment slot has been assembled
                 he = hipEventRecord(c->ev_et[slot][0], c->down_stream);
                 if (he == hipSuccess && off[cnt])
-                    he = hipMemcpyAsync(c->eh_out[slot], c->ed_seg[slot], (size_t)off[cnt], hipMemcpyDeviceToHost,
+                    he = hipMemcpyAsync(c->eh_out[slot].p, c->ed_seg[slot].p, (size_t)off[cnt], hipMemcpyDeviceToHost,
                                         c->down_stream);
                 if (he == hipSuccess) he = hipEventRecord(c->ev_down[slot], c->down_stream);
                 if (he != hipSuccess) { rc = fail_hip(c, he); break; }

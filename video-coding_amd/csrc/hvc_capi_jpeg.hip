@@ -20,15 +20,15 @@ static int single_frame_coefs_on_device(hvc_ctx *c, const uint8_t *jpeg, size_t 
     if (n < 128u * 1024u) return HVC_OK;
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    int r = grow(c, &c->gd_coefs, &c->gd_coefs_cap, info->coef_count * sizeof(int16_t));
+    int r = grow(c, c->gd_coefs, info->coef_count * sizeof(int16_t));
     if (r) return r;
     if (c->decode_kernel != 1 && c->decode_kernel != 3) { // (the A/B alternates read the DC from the record)
         const size_t blocks = info->coef_count / 64;
-        if ((r = grow(c, &c->gd_dcv, &c->gd_dcv_cap, ((blocks + 127) & ~(size_t)127) * sizeof(int16_t)))) return r;
-        after->dc_plane = (int16_t *)c->gd_dcv;
+        if ((r = grow(c, c->gd_dcv, ((blocks + 127) & ~(size_t)127) * sizeof(int16_t)))) return r;
+        after->dc_plane = c->gd_dcv.as<int16_t>();
         after->dc_fs = blocks;
     }
-    return gpu_entropy_decode(c, &jpeg, &n, 1, *info, (int16_t *)c->gd_coefs, info->coef_count, used, after);
+    return gpu_entropy_decode(c, &jpeg, &n, 1, *info, c->gd_coefs.as<int16_t>(), info->coef_count, used, after);
 }
 
 // One file whose header is read and whose arguments are checked, to the caller's memory.  What the entry points differ in
@@ -48,7 +48,7 @@ static int decode_one_file(hvc_ctx *c, const uint8_t *jpeg, size_t n, const hvc_
         DecodeOpts o(c); // (profiling as the context has it)
         o.dc_plane = after.dc_plane;
         o.dc_fs = after.dc_fs;
-        return enqueue((const int16_t *)c->gd_coefs, o);
+        return enqueue(c->gd_coefs.as<const int16_t>(), o);
     };
     after.enqueue = from_reader;
     int r = single_frame_coefs_on_device(c, jpeg, n, info, &on_gpu, &after);
@@ -79,12 +79,12 @@ static int decode_one_file(hvc_ctx *c, const uint8_t *jpeg, size_t n, const hvc_
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
     const size_t cb = info->coef_count * sizeof(int16_t);
-    if ((r = grow(c, &c->d_in, &c->in_cap, cb))) return r;
-    HIPCHK(c, hipMemcpyAsync(c->d_in, coefs.data(), cb, hipMemcpyHostToDevice, c->stream));
+    if ((r = grow(c, c->d_in, cb))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_in.p, coefs.data(), cb, hipMemcpyHostToDevice, c->stream));
     DecodeOpts o(c);
     o.profile = false;
     o.wide = &fix;
-    if ((r = enqueue((const int16_t *)c->d_in, o))) return r;
+    if ((r = enqueue(c->d_in.as<const int16_t>(), o))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HVC_OK;
 }
@@ -95,10 +95,10 @@ static int decode_file_to(hvc_ctx *c, const uint8_t *jpeg, size_t n, const Outpu
     return decode_one_file(
         c, jpeg, n, &form.info,
         [&](const int16_t *d_coefs, const DecodeOpts &o) -> int {
-            int e = grow(c, &c->d_out, &c->out_cap, form.out_bytes);
+            int e = grow(c, c->d_out, form.out_bytes);
             if (e) return e;
-            if ((e = form.run(c, d_coefs, 1, (uint8_t *)c->d_out, form.out_bytes, HVC_MEM_DEVICE, o))) return e;
-            HIPCHK(c, hipMemcpyAsync(dst, c->d_out, form.out_bytes, hipMemcpyDeviceToHost, c->stream));
+            if ((e = form.run(c, d_coefs, 1, c->d_out.as<uint8_t>(), form.out_bytes, HVC_MEM_DEVICE, o))) return e;
+            HIPCHK(c, hipMemcpyAsync(dst, c->d_out.p, form.out_bytes, hipMemcpyDeviceToHost, c->stream));
             return HVC_OK;
         },
         [&](const int16_t *coefs) { return form.run(c, coefs, 1, dst, form.out_bytes, HVC_MEM_HOST, DecodeOpts(c)); });
@@ -138,15 +138,15 @@ struct RgbTail {
     int sampling = 0;
     RgbImage im;
     int scratch(hvc_ctx *c, const hvc_jpeg_info &pi) const { // (before anything is written to c->d_aux)
-        const int r = grow(c, &c->d_aux, &c->aux_cap, pi.pixel_bytes);
-        return r ? r : grow(c, &c->d_aux2, &c->aux2_cap, rgb_bytes(im, 1));
+        const int r = grow(c, c->d_aux, pi.pixel_bytes);
+        return r ? r : grow(c, c->d_aux2, rgb_bytes(im, 1));
     }
     int enqueue(hvc_ctx *c, const hvc_jpeg_info &pi, uint8_t *rgb) const { // colour pass and download on c->stream
         int cw, ch;
         rgb_chroma_window(sampling, pi.width, pi.height, cw, ch);
-        HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, pi.pixel_bytes, pi.layout, sampling, pi.width, pi.height, cw, ch, 1,
-                                    (uint8_t *)c->d_aux2, im, c->stream, c->arith));
-        HIPCHK(c, rgb_download((const uint8_t *)c->d_aux2, rgb, im, 1, c->stream));
+        HIPCHK(c, ycc_to_rgb_device(c->d_aux.as<const uint8_t>(), pi.pixel_bytes, pi.layout, sampling, pi.width, pi.height, cw, ch, 1,
+                                    c->d_aux2.as<uint8_t>(), im, c->stream, c->arith));
+        HIPCHK(c, rgb_download(c->d_aux2.as<const uint8_t>(), rgb, im, 1, c->stream));
         return HVC_OK;
     }
 };
@@ -174,7 +174,7 @@ int hvc_jpeg_decode_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, hvc_jpeg_info
     return decode_one_file(
         c, jpeg, n, info,
         [&](const int16_t *d_coefs, const DecodeOpts &o) -> int {
-            const int e = form.run(c, d_coefs, 1, (uint8_t *)c->d_aux, form.out_bytes, HVC_MEM_DEVICE, o);
+            const int e = form.run(c, d_coefs, 1, c->d_aux.as<uint8_t>(), form.out_bytes, HVC_MEM_DEVICE, o);
             return e ? e : tail.enqueue(c, *info, rgb);
         },
         nullptr); // (the host reader's record is uploaded)
@@ -252,11 +252,11 @@ int hvc_jpeg_decode_scaled_rgb(hvc_ctx *c, const uint8_t *jpeg, size_t n, int sc
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
     const size_t cb = form.info.coef_count * sizeof(int16_t);
     if ((r = tail.scratch(c, *info))) return r;
-    if ((r = grow(c, &c->d_in, &c->in_cap, cb))) return r;
-    HIPCHK(c, hipMemcpyAsync(c->d_in, coefs.data(), cb, hipMemcpyHostToDevice, c->stream));
+    if ((r = grow(c, c->d_in, cb))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_in.p, coefs.data(), cb, hipMemcpyHostToDevice, c->stream));
     DecodeOpts o(c);
     o.profile = false;
-    if ((r = form.run(c, (const int16_t *)c->d_in, 1, (uint8_t *)c->d_aux, form.out_bytes, HVC_MEM_DEVICE, o))) return r;
+    if ((r = form.run(c, c->d_in.as<const int16_t>(), 1, c->d_aux.as<uint8_t>(), form.out_bytes, HVC_MEM_DEVICE, o))) return r;
     if ((r = tail.enqueue(c, *info, rgb))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HVC_OK;
@@ -282,9 +282,9 @@ static int encode_scratch(hvc_ctx *c, const hvc_jpeg_info &info, size_t *seg_cap
     const size_t n_ivl = ri ? (info.coef_count / 64 + (size_t)ri - 1) / (size_t)ri : 0; // (at most: an MCU holds >= 3 blocks)
     *seg_cap = (info.coef_count / 64) * 243 + 64 + 4 * n_ivl; // worst case incl. stuffing; a (stuffed) pad byte + marker per interval
     int r;
-    if ((r = grow(c, &c->d_in, &c->in_cap, info.pixel_bytes))) return r;
-    if ((r = grow(c, &c->d_out, &c->out_cap, coef_bytes))) return r;
-    return grow(c, &c->hd_out, &c->hd_out_cap, *seg_cap);
+    if ((r = grow(c, c->d_in, info.pixel_bytes))) return r;
+    if ((r = grow(c, c->d_out, coef_bytes))) return r;
+    return grow(c, c->hd_out, *seg_cap);
 }
 static int encode_padded_on_device(hvc_ctx *c, const hvc_jpeg_info &info, size_t seg_cap, uint8_t *out, size_t cap, size_t *out_len);
 
@@ -317,7 +317,7 @@ int hvc_jpeg_encode(hvc_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
     size_t seg_cap = 0;
     if ((r = encode_scratch(c, info, &seg_cap))) return r;
-    HIPCHK(c, hipMemcpyAsync(c->d_in, planes.data(), info.pixel_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_in.p, planes.data(), info.pixel_bytes, hipMemcpyHostToDevice, c->stream));
     return encode_padded_on_device(c, info, seg_cap, out, cap, out_len);
 } HVC_ABI_CATCH
 
@@ -327,12 +327,12 @@ static int encode_padded_on_device(hvc_ctx *c, const hvc_jpeg_info &info, size_t
     const int ri = c->restart_interval;
     EncodeOpts o(c);
     o.profile = false;
-    r = encode_frames_impl(c, (const uint8_t *)c->d_in, info.pixel_bytes, &info.qtabs[0][0], info.n_qtabs, info.layout, 3, 1,
-                           (int16_t *)c->d_out, info.coef_count, HVC_MEM_DEVICE, o);
+    r = encode_frames_impl(c, c->d_in.as<const uint8_t>(), info.pixel_bytes, &info.qtabs[0][0], info.n_qtabs, info.layout, 3, 1,
+                           c->d_out.as<int16_t>(), info.coef_count, HVC_MEM_DEVICE, o);
     if (r) return r;
     hvc::HuffParams P;
     const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // the frame's own tables (hvc_set_huffman_tables)
-    if ((r = huffman_prepare(c, &info, (const int16_t *)c->d_out, info.coef_count, 1, (uint8_t *)c->hd_out, seg_cap, nullptr, P,
+    if ((r = huffman_prepare(c, &info, c->d_out.as<const int16_t>(), info.coef_count, 1, c->hd_out.as<uint8_t>(), seg_cap, nullptr, P,
                              opt, ri)))
         return r;
     HIPCHK(c, hvc::launch_huffman_encode(P, c->stream));
@@ -349,7 +349,7 @@ static int encode_padded_on_device(hvc_ctx *c, const hvc_jpeg_info &info, size_t
     *out_len = header.size() + (size_t)off[1] + 2;
     if (!out || *out_len > cap) return HVC_E_INVALID_ARG;
     std::memcpy(out, header.data(), header.size());
-    HIPCHK(c, hipMemcpy(out + header.size(), c->hd_out, (size_t)off[1], hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out + header.size(), c->hd_out.p, (size_t)off[1], hipMemcpyDeviceToHost));
     out[header.size() + off[1]] = 0xff; // complete_and_write_eoi (encoder.ml:507-510)
     out[header.size() + off[1] + 1] = 0xd9;
     return HVC_OK;
@@ -372,10 +372,10 @@ int hvc_jpeg_encode_rgb(hvc_ctx *c, const uint8_t *rgb, size_t rgb_row_stride, i
     size_t seg_cap = 0;
     if ((r = encode_scratch(c, info, &seg_cap))) return r;
     const size_t in_bytes = rgb_bytes(im, 1);
-    if ((r = grow(c, &c->d_aux2, &c->aux2_cap, in_bytes))) return r;
-    HIPCHK(c, hipMemcpyAsync(c->d_aux2, rgb, in_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_in, 0, info.pixel_bytes, c->stream));
-    HIPCHK(c, rgb_to_ycc_device((const uint8_t *)c->d_aux2, im, width, height, chroma, 1, (uint8_t *)c->d_in, info.pixel_bytes, info.layout,
+    if ((r = grow(c, c->d_aux2, in_bytes))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_aux2.p, rgb, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_in.p, 0, info.pixel_bytes, c->stream));
+    HIPCHK(c, rgb_to_ycc_device(c->d_aux2.as<const uint8_t>(), im, width, height, chroma, 1, c->d_in.as<uint8_t>(), info.pixel_bytes, info.layout,
                                 c->stream));
     return encode_padded_on_device(c, info, seg_cap, out, cap, out_len);
 } HVC_ABI_CATCH
@@ -454,7 +454,7 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
                               std::memcmp(fi[q].layout, info0.layout, sizeof fi[q].layout) ||
                               std::memcmp(fi[q].qtabs, info0.qtabs, sizeof fi[q].qtabs)))
                     e[q] = HVC_E_INVALID_ARG; // a batch shares one geometry and one set of tables
-                dst[q] = (int16_t *)c->h_ring[k % NB] + (size_t)(f - k * C) * info0.coef_count;
+                dst[q] = c->h_ring[k % NB].as<int16_t>() + (size_t)(f - k * C) * info0.coef_count;
             }
             if (cnt == 2 && !e[0] && !e[1]) {
                 const uint8_t *const data[2] = {jpegs[f0], jpegs[f0 + 1]};
@@ -485,7 +485,7 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
 
     auto first_of = [&](int k) { return k * C; };
     auto count_of = [&](int k) { return first_of(k) + C <= n_frames ? C : n_frames - first_of(k); };
-    auto dst_of = [&](int k, int slot) { return where == HVC_MEM_DEVICE ? pixels + (size_t)first_of(k) * pixel_fs : (uint8_t *)c->d_oring[slot]; };
+    auto dst_of = [&](int k, int slot) { return where == HVC_MEM_DEVICE ? pixels + (size_t)first_of(k) * pixel_fs : c->d_oring[slot].as<uint8_t>(); };
     const size_t dst_fs = where == HVC_MEM_DEVICE ? pixel_fs : out_bytes;
     r = host_reader_chunks(
         c, feed, n_chunks, threads, wall0, count_of, [&](int k) { return frame_coef_bytes * (size_t)count_of(k); },
@@ -493,7 +493,7 @@ int decode_batch_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *siz
             DecodeOpts o(c);
             o.profile = form.chunk_profile(c);
             o.wide = &chunk_wide[(size_t)k]; // (complete: the chunk's workers are done)
-            return form.run(c, (const int16_t *)c->d_ring[slot], count_of(k), dst_of(k, slot), dst_fs, HVC_MEM_DEVICE, o);
+            return form.run(c, c->d_ring[slot].as<const int16_t>(), count_of(k), dst_of(k, slot), dst_fs, HVC_MEM_DEVICE, o);
         },
         [&](int k, int slot) {
             hipError_t he = hipSuccess;
@@ -643,19 +643,19 @@ int hvc_jpeg_decode_batch_rgb(hvc_ctx *c, const uint8_t *const *jpegs, const siz
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
     const size_t px_fs = info0.pixel_bytes;
     const int part = empty ? n_frames : (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)4 << 30) / px_fs));
-    if ((r = grow(c, &c->d_aux, &c->aux_cap, empty ? 8 : (size_t)part * px_fs))) return r;
+    if ((r = grow(c, c->d_aux, empty ? 8 : (size_t)part * px_fs))) return r;
     uint8_t *d_rgb = rgb;
     if (where == HVC_MEM_HOST && !empty) {
-        if ((r = grow(c, &c->d_aux2, &c->aux2_cap, rgb_bytes(im, part)))) return r;
-        d_rgb = (uint8_t *)c->d_aux2;
+        if ((r = grow(c, c->d_aux2, rgb_bytes(im, part)))) return r;
+        d_rgb = c->d_aux2.as<uint8_t>();
     }
     const auto wall0 = std::chrono::steady_clock::now();
     for (int f0 = 0; f0 < n_frames; f0 += part) {
         const int cnt = std::min(part, n_frames - f0);
         hvc_batch_stats ps;
-        r = gpu_reader ? hvc_jpeg_decode_batch_gpu(c, jpegs + f0, sizes + f0, cnt, threads, frames_per_chunk, (uint8_t *)c->d_aux, px_fs,
+        r = gpu_reader ? hvc_jpeg_decode_batch_gpu(c, jpegs + f0, sizes + f0, cnt, threads, frames_per_chunk, c->d_aux.as<uint8_t>(), px_fs,
                                                    HVC_MEM_DEVICE, 0, &ps)
-                       : hvc_jpeg_decode_batch(c, jpegs + f0, sizes + f0, cnt, threads, frames_per_chunk, (uint8_t *)c->d_aux, px_fs,
+                       : hvc_jpeg_decode_batch(c, jpegs + f0, sizes + f0, cnt, threads, frames_per_chunk, c->d_aux.as<uint8_t>(), px_fs,
                                                HVC_MEM_DEVICE, &ps);
         if (r) return r;
         if (stats) {
@@ -666,7 +666,7 @@ int hvc_jpeg_decode_batch_rgb(hvc_ctx *c, const uint8_t *const *jpegs, const siz
         }
         if (empty) continue;
         uint8_t *out = where == HVC_MEM_HOST ? d_rgb : d_rgb + (size_t)f0 * im.frame_stride;
-        HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_aux, px_fs, info0.layout, sampling, info0.width, info0.height, cw, ch, cnt, out, im,
+        HIPCHK(c, ycc_to_rgb_device(c->d_aux.as<const uint8_t>(), px_fs, info0.layout, sampling, info0.width, info0.height, cw, ch, cnt, out, im,
                                     c->stream, c->arith));
         if (where == HVC_MEM_HOST) {
             HIPCHK(c, rgb_download(out, rgb + (size_t)f0 * im.frame_stride, im, cnt, c->stream));

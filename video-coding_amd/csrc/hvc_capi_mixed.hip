@@ -29,50 +29,36 @@ ImageParts image_parts(const hvc::MixedPlan &plan) {
 
 // A plan's image in a device buffer of the context, in stream order: uploaded from the pinned copy unless the device
 // already holds these bytes.
-struct PlanBuf {
-    void *&d, *&h;
-    size_t &cap, &h_cap, &len; // len: bytes of the image d holds, 0 = none
-    hipEvent_t &ev;            // behind the last upload
-};
-int upload_image(hvc_ctx *c, const PlanBuf &b, const std::vector<unsigned char> &img) {
+int upload_image(hvc_ctx *c, PlanBuf &b, const std::vector<unsigned char> &img) {
     const size_t total = img.size();
-    if (!b.ev) HIPCHK(c, hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
-    const bool same = b.len == total && b.h && !std::memcmp(b.h, img.data(), total);
+    HIPCHK(c, b.ev.ensure(hipEventDisableTiming));
+    const bool same = b.len == total && b.h && !std::memcmp(b.h.p, img.data(), total);
     if (same) return HVC_OK;
     b.len = 0;
-    int r = grow(c, &b.d, &b.cap, total);
+    int r = grow(c, b.d, total);
     if (r) return r;
-    if (total > b.h_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (b.h) (void)hipHostFree(b.h);
-        b.h = nullptr;
-        b.h_cap = 0;
-        const size_t want = total + total / 4 + 4096;
-        if (hipHostMalloc(&b.h, want, hipHostMallocDefault) != hipSuccess) {
-            b.h = nullptr;
-            return HVC_E_OUT_OF_MEMORY;
-        }
-        b.h_cap = want;
+    if (total > b.h.cap) {
+        if ((r = grow(c, b.h, total, GROW_PLAN_IMAGE))) return r;
     } else {
         HIPCHK(c, wait_event(b.ev)); // (the last upload has read the image)
     }
-    std::memcpy(b.h, img.data(), total);
-    HIPCHK(c, hipMemcpyAsync(b.d, b.h, total, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(b.h.p, img.data(), total);
+    HIPCHK(c, hipMemcpyAsync(b.d.p, b.h.p, total, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(b.ev, c->stream));
     b.len = total;
     return HVC_OK;
 }
 
-// the block stage's tables in c->d_mixed
+// the block stage's tables in c->mixed_plan
 int upload_plan(hvc_ctx *c, const hvc::MixedPlan &plan, hvc::MixedParams &P) {
     const ImageParts ip = image_parts(plan);
     std::vector<unsigned char> img(ip.total, 0);
     std::memcpy(img.data() + ip.planes, plan.planes.data(), plan.planes.size() * sizeof(hvc::MixedPlaneK));
     std::memcpy(img.data() + ip.tables, plan.tables.data(), plan.tables.size() * sizeof(hvc::MixedTableK));
     std::memcpy(img.data() + ip.map, plan.map.data(), plan.map.size() * sizeof(unsigned));
-    const int r = upload_image(c, PlanBuf{c->d_mixed, c->h_mixed, c->mixed_cap, c->h_mixed_cap, c->mixed_len, c->ev_mixed}, img);
+    const int r = upload_image(c, c->mixed_plan, img);
     if (r) return r;
-    const unsigned char *d = (const unsigned char *)c->d_mixed;
+    const unsigned char *d = c->mixed_plan.d.as<const unsigned char>();
     P.planes = reinterpret_cast<const hvc::MixedPlaneK *>(d + ip.planes);
     P.tables = reinterpret_cast<const hvc::MixedTableK *>(d + ip.tables);
     P.map = reinterpret_cast<const unsigned *>(d + ip.map);
@@ -81,21 +67,21 @@ int upload_plan(hvc_ctx *c, const hvc::MixedPlan &plan, hvc::MixedParams &P) {
 }
 
 // The colour pass of a plan on DEVICE memory, enqueued on c->stream: its tables (images | map, each part on 16 bytes) go to
-// c->d_mixed_rgb, a buffer of their own.
+// c->mixed_rgb_plan, a buffer of their own.
 int mixed_rgb_launch_plan(hvc_ctx *c, const hvc::MixedRgbPlan &plan, int layout, const uint8_t *d_yuv, uint8_t *d_rgb, bool profile) {
     if (plan.map.empty()) return HVC_OK; // no pixel at all: nothing to launch
     const size_t map_at = (plan.images.size() * sizeof(hvc::MixedRgbImageK) + 15) & ~(size_t)15;
     std::vector<unsigned char> img(map_at + ((plan.map.size() * sizeof(unsigned) + 15) & ~(size_t)15), 0);
     std::memcpy(img.data(), plan.images.data(), plan.images.size() * sizeof(hvc::MixedRgbImageK));
     std::memcpy(img.data() + map_at, plan.map.data(), plan.map.size() * sizeof(unsigned));
-    const int r = upload_image(c, PlanBuf{c->d_mixed_rgb, c->h_mixed_rgb, c->mixed_rgb_cap, c->h_mixed_rgb_cap, c->mixed_rgb_len, c->ev_mixed_rgb}, img);
+    const int r = upload_image(c, c->mixed_rgb_plan, img);
     if (r) return r;
     hvc::MixedRgbParams P;
     std::memset(&P, 0, sizeof P);
     P.yuv = d_yuv;
     P.rgb = d_rgb;
-    P.images = reinterpret_cast<const hvc::MixedRgbImageK *>(c->d_mixed_rgb);
-    P.map = reinterpret_cast<const unsigned *>((const unsigned char *)c->d_mixed_rgb + map_at);
+    P.images = c->mixed_rgb_plan.d.as<const hvc::MixedRgbImageK>();
+    P.map = reinterpret_cast<const unsigned *>(c->mixed_rgb_plan.d.as<const unsigned char>() + map_at);
     P.n_units = (unsigned)plan.map.size();
     P.planar = layout == HVC_RGB_PLANAR;
     const int slot = (int)(c->k_calls % HVC_PROF_RING);
@@ -106,15 +92,7 @@ int mixed_rgb_launch_plan(hvc_ctx *c, const hvc::MixedRgbPlan &plan, int layout,
 }
 
 // the fix-up list holds one id per block slot of the launch (every unit may send all 64 of its lanes)
-int reserve_mixed_fix_list(hvc_ctx *c, size_t entries) {
-    if (entries <= c->fix_cap) return HVC_OK;
-    void *p = c->d_fix_list;
-    size_t cap = c->fix_cap * sizeof(unsigned);
-    const int r = grow(c, &p, &cap, entries * sizeof(unsigned));
-    c->d_fix_list = (unsigned *)p;
-    c->fix_cap = cap / sizeof(unsigned);
-    return r;
-}
+int reserve_mixed_fix_list(hvc_ctx *c, size_t entries) { return grow(c, c->d_fix_list, entries * sizeof(unsigned)); }
 
 // The block stage of a plan on DEVICE memory, enqueued on c->stream.  The caller has called wide_total_begin for the call
 // this launch belongs to.  n = 4, 2, 1: a plan built for the scaled block stage with d_pixels as its pix_addr
@@ -130,7 +108,7 @@ int mixed_launch_plan(hvc_ctx *c, const hvc::MixedPlan &plan, const int16_t *d_c
     P.coefs = d_coefs;
     P.pixels = d_pixels;
     if (n != 8) {
-        P.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count + 2);
+        P.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count.as<unsigned>() + 2);
         if (!c->wide_total_started) HIPCHK(c, hipMemsetAsync(P.wide_total, 0, sizeof *P.wide_total, c->stream));
         c->wide_total_started = true;
         const int slot = (int)(c->k_calls % HVC_PROF_RING);
@@ -192,11 +170,11 @@ int stage_coefs(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, co
         ptot += (shift + ps + 63) & ~(size_t)63;
     }
     if (!coefs) return HVC_OK;
-    const int r = grow(c, &c->d_in, &c->in_cap, ctot * sizeof(int16_t));
+    const int r = grow(c, c->d_in, ctot * sizeof(int16_t));
     if (r) return r;
     for (int f = 0; f < n_frames; f++)
         if (cspan[(size_t)f])
-            HIPCHK(c, hipMemcpyAsync((int16_t *)c->d_in + d_coef[(size_t)f], coefs + coef_offsets[f], cspan[(size_t)f] * sizeof(int16_t),
+            HIPCHK(c, hipMemcpyAsync(c->d_in.as<int16_t>() + d_coef[(size_t)f], coefs + coef_offsets[f], cspan[(size_t)f] * sizeof(int16_t),
                                      hipMemcpyHostToDevice, c->stream));
     return HVC_OK;
 }
@@ -259,9 +237,9 @@ int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coe
         for (int f = 0; f < n_frames; f++) h_pix.push_back((uintptr_t)pixels + pixel_offsets[f]);
     size_t ptot = 0;
     if ((r = stage_coefs(c, coefs, coef_offsets, infos, n_frames, d_coef, d_pix, ptot, N, N != 8 ? h_pix.data() : nullptr))) return r;
-    if ((r = grow(c, &c->d_out, &c->out_cap, ptot))) return r;
+    if ((r = grow(c, c->d_out, ptot))) return r;
     wide_total_begin(c);
-    if ((r = mixed_launch(c, (const int16_t *)c->d_in, d_coef.data(), infos, nullptr, n_frames, (uint8_t *)c->d_out, d_pix.data(), false, N))) {
+    if ((r = mixed_launch(c, c->d_in.as<const int16_t>(), d_coef.data(), infos, nullptr, n_frames, c->d_out.as<uint8_t>(), d_pix.data(), false, N))) {
         (void)hipStreamSynchronize(c->stream);
         return r;
     }
@@ -271,7 +249,7 @@ int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coe
             if (k.blocks_w <= 0 || k.blocks_h <= 0) continue;
             const size_t row = (size_t)k.blocks_w * N, rows = (size_t)k.blocks_h * N;
             uint8_t *dst = pixels + pixel_offsets[f] + k.plane_offset;
-            const uint8_t *src = (const uint8_t *)c->d_out + d_pix[(size_t)f] + k.plane_offset;
+            const uint8_t *src = c->d_out.as<const uint8_t>() + d_pix[(size_t)f] + k.plane_offset;
             if (k.stride == row)
                 HIPCHK(c, hipMemcpyAsync(dst, src, row * rows, hipMemcpyDeviceToHost, c->stream));
             else
@@ -331,19 +309,19 @@ int yuv_to_rgb_mixed_impl(hvc_ctx *c, const uint8_t *yuv, const size_t *yuv_offs
     for (int f = 0; f < n_frames; f++)
         if (!yspan[(size_t)f]) rspan[(size_t)f] = 0; // (no image: no room)
     const size_t ytot = stage_offsets(yuv_offsets, yspan, d_yuv), rtot = stage_offsets(rgb_offsets, rspan, d_rgb);
-    if ((r = grow(c, &c->d_in, &c->in_cap, ytot))) return r;
-    if ((r = grow(c, &c->d_out, &c->out_cap, rtot))) return r;
-    if ((r = hvc::mixed_rgb_plan_build(infos, d_yuv.data(), d_rgb.data(), rgb_row_strides, layout, nullptr, n_frames, (uintptr_t)c->d_in,
-                                       (uintptr_t)c->d_out, false, plan)))
+    if ((r = grow(c, c->d_in, ytot))) return r;
+    if ((r = grow(c, c->d_out, rtot))) return r;
+    if ((r = hvc::mixed_rgb_plan_build(infos, d_yuv.data(), d_rgb.data(), rgb_row_strides, layout, nullptr, n_frames, (uintptr_t)c->d_in.p,
+                                       (uintptr_t)c->d_out.p, false, plan)))
         return r;
     for (int f = 0; f < n_frames; f++)
         if (yspan[(size_t)f])
-            HIPCHK(c, hipMemcpyAsync((uint8_t *)c->d_in + d_yuv[(size_t)f], yuv + yuv_offsets[f], yspan[(size_t)f], hipMemcpyHostToDevice, c->stream));
-    if ((r = mixed_rgb_launch_plan(c, plan, layout, (const uint8_t *)c->d_in, (uint8_t *)c->d_out, false))) {
+            HIPCHK(c, hipMemcpyAsync(c->d_in.as<uint8_t>() + d_yuv[(size_t)f], yuv + yuv_offsets[f], yspan[(size_t)f], hipMemcpyHostToDevice, c->stream));
+    if ((r = mixed_rgb_launch_plan(c, plan, layout, c->d_in.as<const uint8_t>(), c->d_out.as<uint8_t>(), false))) {
         (void)hipStreamSynchronize(c->stream);
         return r;
     }
-    HIPCHK(c, download_images(plan, layout, (const uint8_t *)c->d_out, rgb, rgb_offsets, c->stream));
+    HIPCHK(c, download_images(plan, layout, c->d_out.as<const uint8_t>(), rgb, rgb_offsets, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HVC_OK;
 }
@@ -366,18 +344,18 @@ int decode_frames_mixed_rgb_impl(hvc_ctx *c, const int16_t *coefs, const size_t 
     hvc::MixedPlan bplan; // both plans before anything is enqueued: a set that is refused leaves nothing behind
     hvc::MixedRgbPlan cplan;
     if ((r = hvc::mixed_plan_build(infos, host ? d_coef.data() : coef_offsets, d_pix.data(), nullptr, n_frames, bplan))) return r;
-    if ((r = grow(c, &c->d_aux, &c->aux_cap, ptot))) return r;
-    if (host && (r = grow(c, &c->d_aux2, &c->aux2_cap, rtot))) return r;
-    uint8_t *out = host ? (uint8_t *)c->d_aux2 : rgb;
+    if ((r = grow(c, c->d_aux, ptot))) return r;
+    if (host && (r = grow(c, c->d_aux2, rtot))) return r;
+    uint8_t *out = host ? c->d_aux2.as<uint8_t>() : rgb;
     if ((r = hvc::mixed_rgb_plan_build(infos, d_pix.data(), host ? d_rgb.data() : rgb_offsets, rgb_row_strides, layout, nullptr, n_frames,
-                                       (uintptr_t)c->d_aux, (uintptr_t)out, true, cplan)))
+                                       (uintptr_t)c->d_aux.p, (uintptr_t)out, true, cplan)))
         return r;
     if (bplan.map.empty()) return HVC_OK; // (no block: no pixel)
     if (!coefs || (!cplan.map.empty() && !rgb)) return HVC_E_INVALID_ARG;
     if (host && (r = stage_coefs(c, coefs, coef_offsets, infos, n_frames, d_coef, d_pix, ptot))) return r;
     wide_total_begin(c);
-    r = mixed_launch_plan(c, bplan, host ? (const int16_t *)c->d_in : coefs, (uint8_t *)c->d_aux, !host && c->profiling);
-    if (!r) r = mixed_rgb_launch_plan(c, cplan, layout, (const uint8_t *)c->d_aux, out, false);
+    r = mixed_launch_plan(c, bplan, host ? c->d_in.as<const int16_t>() : coefs, c->d_aux.as<uint8_t>(), !host && c->profiling);
+    if (!r) r = mixed_rgb_launch_plan(c, cplan, layout, c->d_aux.as<const uint8_t>(), out, false);
     if (r) {
         (void)hipStreamSynchronize(c->stream);
         return r;
@@ -549,7 +527,7 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
                 e = hvc_jpeg_entropy_decode(jpegs[f], sizes[f], &infos[f], nullptr);
             } else {
                 wide.clear();
-                e = hvc::entropy_decode_wide(jpegs[f], sizes[f], &infos[f], (int16_t *)c->h_ring[k % NB] + coef_rel[(size_t)f], wide);
+                e = hvc::entropy_decode_wide(jpegs[f], sizes[f], &infos[f], c->h_ring[k % NB].as<int16_t>() + coef_rel[(size_t)f], wide);
                 if (!e && !wide.empty()) e = HVC_E_RANGE; // (a DC beyond int16: no side list here)
             }
             entropy_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
@@ -584,22 +562,22 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
                 if (gpu_upload_err != hipSuccess) return fail_hip(c, gpu_upload_err);
                 const Chunk &ch = chunks[(size_t)k];
                 int n_gpu = 0;
-                const int rc = rd.read(k, (int16_t *)c->d_ring[slot], c->stream, back, &n_gpu);
+                const int rc = rd.read(k, c->d_ring[slot].as<int16_t>(), c->stream, back, &n_gpu);
                 if (rc) return rc;
                 gpu_files += (unsigned long long)n_gpu;
                 for (int t = ch.first; t < ch.first + ch.count; t++)
                     if (!back[(size_t)take[(size_t)t]] && infos[take[(size_t)t]].coef_count) ok.push_back(take[(size_t)t]);
                 if (ok.empty()) return (int)HVC_OK;
             }
-            uint8_t *dst = out ? out : (uint8_t *)c->d_oring[slot];
+            uint8_t *dst = out ? out : c->d_oring[slot].as<uint8_t>();
             if (!form.rgb())
-                return mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), oinfos, ok.data(), (int)ok.size(), dst, dst_off, c->profiling, N);
+                return mixed_launch(c, c->d_ring[slot].as<const int16_t>(), coef_rel.data(), oinfos, ok.data(), (int)ok.size(), dst, dst_off, c->profiling, N);
             // the planes into the slot of their own ring, the colour pass from there to where the planes would have gone
-            uint8_t *planes = (uint8_t *)c->d_pring[slot];
+            uint8_t *planes = c->d_pring[slot].as<uint8_t>();
             hvc::MixedRgbPlan cplan;
             int rc = hvc::mixed_rgb_plan_build(oinfos, plane_rel.data(), dst_off, form.rgb_row_strides, form.layout, ok.data(), (int)ok.size(),
                                                (uintptr_t)planes, (uintptr_t)dst, true, cplan, N);
-            if (!rc) rc = mixed_launch(c, (const int16_t *)c->d_ring[slot], coef_rel.data(), oinfos, ok.data(), (int)ok.size(), planes,
+            if (!rc) rc = mixed_launch(c, c->d_ring[slot].as<const int16_t>(), coef_rel.data(), oinfos, ok.data(), (int)ok.size(), planes,
                                        plane_rel.data(), c->profiling, N);
             if (!rc) rc = mixed_rgb_launch_plan(c, cplan, form.layout, planes, dst, false);
             return rc;
@@ -608,7 +586,7 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
             hipError_t he = hipSuccess;
             if (where != HVC_MEM_HOST) return he;
             const Chunk &ch = chunks[(size_t)k];
-            const uint8_t *dst = (const uint8_t *)c->d_oring[slot];
+            const uint8_t *dst = c->d_oring[slot].as<const uint8_t>();
             // the records of consecutive good files go back in one copy where only alignment padding lies between them
             // (the padding between records is nobody's; a failed file's record is never touched)
             size_t run_lo = 0, run_hi = 0;

@@ -58,8 +58,8 @@ int MixedGpuReader::begin(hvc_ctx *c, const uint8_t *const *jpegs, const size_t 
     if ((r = ring_ensure(c, reader_rings(c), {ecs_cap_ + 16, ecs_cap_ + 16, meta_bytes + 16, meta_bytes + 16, sets_most * sizeof(hvc::HdFrameTabs) + 16,
                                               sets_most * sizeof(hvc::HdFrameTabs) + 16})))
         return r;
-    if ((r = grow(c, &c->gd_state, &c->gd_state_cap, HVC_HDM_STATE_BYTES(subs_most)))) return r;
-    if ((r = grow(c, &c->gd_dcd, &c->gd_dcd_cap, dcd_most * sizeof(int16_t) + 16))) return r;
+    if ((r = grow(c, c->gd_state, HVC_HDM_STATE_BYTES(subs_most)))) return r;
+    if ((r = grow(c, c->gd_dcd, dcd_most * sizeof(int16_t) + 16))) return r;
     slots_.reset(new Slot[hvc_ctx::RING]);
     return HVC_OK;
 }
@@ -82,7 +82,7 @@ void MixedGpuReader::prepare(int k, int t) {
     if (geo_[(size_t)t] == hvc::HDM_TAKEN && !dri && off + room_most(size) <= ecs_cap_) {
         std::unique_ptr<hvc::HdTables> tabs(new hvc::HdTables);
         std::memset(tabs.get(), 0, sizeof(hvc::HdTables)); // (compared byte by byte below)
-        uint8_t *dst = (uint8_t *)c_->gp_h_ecs[slot] + off;
+        uint8_t *dst = c_->gp_h_ecs[slot].as<uint8_t>() + off;
         size_t got = 0;
         bool ok = false;
         const int r = hvc::prepare_gpu_decode_to(jpegs_[f], size, &infos_[f], *tabs, dst, (size + SB - 1) / SB * SB, &got, ok);
@@ -102,7 +102,7 @@ void MixedGpuReader::prepare(int k, int t) {
                     fresh = true;
                 }
             }
-            if (fresh) hvc::make_frame_tabs(*tabs, infos_[f].n_comp, ((hvc::HdFrameTabs *)c_->gp_h_ftabs[slot])[set]);
+            if (fresh) hvc::make_frame_tabs(*tabs, infos_[f].n_comp, (c_->gp_h_ftabs[slot].as<hvc::HdFrameTabs>())[set]);
             if (set >= 0) {
                 sf.ok = true;
                 sf.set = set;
@@ -130,13 +130,13 @@ hipError_t MixedGpuReader::upload(int k, hipStream_t s) {
     // descriptors | map | verdicts (device only), each part on 16 bytes
     const size_t map_at = up16(plan.files.size() * sizeof(hvc::HdmFileK));
     S.status_at = map_at + up16(plan.map.size() * sizeof(unsigned));
-    uint8_t *hm = (uint8_t *)c_->gp_h_meta[slot];
+    uint8_t *hm = c_->gp_h_meta[slot].as<uint8_t>();
     std::memcpy(hm, plan.files.data(), plan.files.size() * sizeof(hvc::HdmFileK)); // (tabrec: the slot's set index, as the records lie)
     std::memcpy(hm + map_at, plan.map.data(), plan.map.size() * sizeof(unsigned));
-    hipError_t e = hipMemcpyAsync(c_->gp_d_ecs[slot], c_->gp_h_ecs[slot], plan.seg_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(c_->gp_d_meta[slot], hm, S.status_at, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(c_->gp_d_ecs[slot].p, c_->gp_h_ecs[slot].p, plan.seg_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(c_->gp_d_meta[slot].p, hm, S.status_at, hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(c_->gp_d_ftabs[slot], c_->gp_h_ftabs[slot], S.sets.size() * sizeof(hvc::HdFrameTabs), hipMemcpyHostToDevice, s);
+        e = hipMemcpyAsync(c_->gp_d_ftabs[slot].p, c_->gp_h_ftabs[slot].p, S.sets.size() * sizeof(hvc::HdFrameTabs), hipMemcpyHostToDevice, s);
     return e;
 }
 
@@ -150,17 +150,17 @@ int MixedGpuReader::read(int k, int16_t *d_coefs, hipStream_t s, std::vector<cha
     if ((uintptr_t)d_coefs & 15) return HVC_E_ALIGNMENT;
     hvc::HdmParams P;
     std::memset(&P, 0, sizeof P);
-    const uint8_t *dm = (const uint8_t *)c_->gp_d_meta[slot];
-    P.ecs = (const uint8_t *)c_->gp_d_ecs[slot];
+    const uint8_t *dm = c_->gp_d_meta[slot].as<const uint8_t>();
+    P.ecs = c_->gp_d_ecs[slot].as<const uint8_t>();
     P.files = (const hvc::HdmFileK *)dm;
     P.map = (const unsigned *)(dm + up16(plan.files.size() * sizeof(hvc::HdmFileK)));
     P.status = (unsigned *)(dm + S.status_at);
-    P.ftabs = (const hvc::HdFrameTabs *)c_->gp_d_ftabs[slot];
+    P.ftabs = c_->gp_d_ftabs[slot].as<const hvc::HdFrameTabs>();
     P.n_files = (unsigned)plan.files.size();
     P.n_units = (unsigned)plan.map.size();
     P.coefs = d_coefs;
-    P.dcd = (int16_t *)c_->gd_dcd;
-    hvc::hdm_carve_state(P, c_->gd_state, plan.total_sub);
+    P.dcd = c_->gd_dcd.as<int16_t>();
+    hvc::hdm_carve_state(P, c_->gd_state.p, plan.total_sub);
     HIPCHK(c_, hvc::launch_hd_mixed(P, s));
     verdict_.assign(plan.files.size(), 0xffu);
     HIPCHK(c_, hipMemcpyAsync(verdict_.data(), P.status, plan.files.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
@@ -200,8 +200,8 @@ int entropy_decode_gpu_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const
     int r;
     int16_t *d = coefs;
     if (where == HVC_MEM_HOST) {
-        if ((r = grow(c, &c->gd_coefs, &c->gd_coefs_cap, span * sizeof(int16_t) + 16))) return r;
-        d = (int16_t *)c->gd_coefs;
+        if ((r = grow(c, c->gd_coefs, span * sizeof(int16_t) + 16))) return r;
+        d = c->gd_coefs.as<int16_t>();
     }
     const std::vector<int> first{0}, count{(int)take.size()};
     std::vector<char> back((size_t)n_files, 0);

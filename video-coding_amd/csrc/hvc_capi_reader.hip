@@ -67,30 +67,30 @@ static void gd_carve_state(hvc::HdParams &P, void *mem, size_t n) {
 // sets, the synchronisation tables (HdSpec) behind them.  Fills P.tables / P.spec / P.slotmask.
 static int gd_upload_tables(hvc_ctx *c, const hvc::HdTables &t, hvc::HdParams &P, hipStream_t st) {
     int r;
-    if ((r = grow(c, &c->gd_tables, &c->gd_tables_cap, sizeof(hvc::HdTables) + sizeof(hvc::HdSpec) + sizeof(hvc::HdSpecOvf)))) return r;
+    if ((r = grow(c, c->gd_tables, sizeof(hvc::HdTables) + sizeof(hvc::HdSpec) + sizeof(hvc::HdSpecOvf)))) return r;
     hvc::HdSpec spec;
     hvc::HdSpecOvf spec_ovf; // (the overflow records of tables with more than HVC_HD_SUBTABLES long prefixes: hvc_hdec.h)
     unsigned char slot[4];
     static const bool classic = std::getenv("HVC_HD_CLASSIC") != nullptr; // tests: force k_hd_round / k_hd_write
     const bool have_spec = hvc::make_spec(t, P.n_comp, spec, slot, P.slot_rep, &spec_ovf) && !classic;
     // file after file with the same tables (the usual case: an encoder's fixed set) finds them on the device already
-    if (!c->gd_tables_host) c->gd_tables_host = new (std::nothrow) hvc::HdTables;
+    if (!c->gd_tables_host) c->gd_tables_host.reset(new (std::nothrow) hvc::HdTables);
     if (!c->gd_tables_host) return HVC_E_OUT_OF_MEMORY;
-    if (!(c->gd_tables_valid && c->gd_tables_ncomp == P.n_comp && !std::memcmp(c->gd_tables_host, &t, sizeof t))) {
+    if (!(c->gd_tables_valid && c->gd_tables_ncomp == P.n_comp && !std::memcmp(c->gd_tables_host.get(), &t, sizeof t))) {
         c->gd_tables_valid = false;
-        HIPCHK(c, hipMemcpyAsync(c->gd_tables, &t, sizeof t, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->gd_tables.p, &t, sizeof t, hipMemcpyHostToDevice, st));
         if (have_spec) {
-            HIPCHK(c, hipMemcpyAsync((char *)c->gd_tables + sizeof t, &spec, sizeof spec, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync((char *)c->gd_tables + sizeof t + sizeof spec, &spec_ovf, sizeof spec_ovf, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(c->gd_tables.as<char>() + sizeof t, &spec, sizeof spec, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(c->gd_tables.as<char>() + sizeof t + sizeof spec, &spec_ovf, sizeof spec_ovf, hipMemcpyHostToDevice, st));
         }
         HIPCHK(c, hipStreamSynchronize(st)); // the sources live on a stack frame
-        std::memcpy(c->gd_tables_host, &t, sizeof t);
+        std::memcpy(c->gd_tables_host.get(), &t, sizeof t);
         c->gd_tables_ncomp = P.n_comp;
         c->gd_tables_valid = true;
     }
-    P.tables = (const hvc::HdTables *)c->gd_tables;
-    P.spec = have_spec ? (const hvc::HdSpec *)((char *)c->gd_tables + sizeof t) : nullptr;
-    P.spec_ovf = have_spec ? (const hvc::HdSpecOvf *)((char *)c->gd_tables + sizeof t + sizeof(hvc::HdSpec)) : nullptr;
+    P.tables = c->gd_tables.as<const hvc::HdTables>();
+    P.spec = have_spec ? (const hvc::HdSpec *)(c->gd_tables.as<char>() + sizeof t) : nullptr;
+    P.spec_ovf = have_spec ? (const hvc::HdSpecOvf *)(c->gd_tables.as<char>() + sizeof t + sizeof(hvc::HdSpec)) : nullptr;
     P.ftabs = nullptr;
     P.tabset_of = nullptr;
     P.slotmask = P.selmask = 0;
@@ -206,19 +206,8 @@ int gpu_entropy_decode(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *si
     } catch (const std::bad_alloc &) {
         return HVC_E_OUT_OF_MEMORY;
     }
-    if (bytes > c->gd_h_ecs_cap) {
-        if (c->gd_h_ecs) (void)hipHostFree(c->gd_h_ecs);
-        c->gd_h_ecs = nullptr;
-        c->gd_h_ecs_cap = 0;
-        const size_t want = bytes + bytes / 2;
-        if (hipHostMalloc(&c->gd_h_ecs, want, HVC_UPLOAD_RING_FLAGS) != hipSuccess) {
-            (void)hipGetLastError();
-            c->gd_h_ecs = nullptr;
-            return HVC_E_OUT_OF_MEMORY;
-        }
-        c->gd_h_ecs_cap = want;
-    }
-    uint8_t *const h_ecs = (uint8_t *)c->gd_h_ecs;
+    if (int r = grow(c, c->gd_h_ecs, bytes, GROW_READER_STAGE)) return r;
+    uint8_t *const h_ecs = c->gd_h_ecs.as<uint8_t>();
     try {
         hvc::HdTables t;
         for (int f = 0; f < n_frames; f++) {
@@ -284,12 +273,12 @@ int gpu_entropy_decode(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *si
     }
     h_meta[2 * nU] = sub_off[nU];
     int r;
-    if ((r = grow(c, &c->gd_ecs, &c->gd_ecs_cap, bytes + HVC_HD_ECS_SLACK))) return r;
-    if ((r = grow(c, &c->gd_meta, &c->gd_meta_cap, meta_words * sizeof(unsigned) + 64))) return r;
-    if ((r = grow(c, &c->gd_state, &c->gd_state_cap, HVC_HD_STATE_BYTES(subs)))) return r;
-    if ((r = grow(c, &c->gd_dcd, &c->gd_dcd_cap, nU * P.blocks_per_frame * sizeof(int16_t)))) return r;
-    P.dcd = (int16_t *)c->gd_dcd;
-    unsigned *m = (unsigned *)c->gd_meta;
+    if ((r = grow(c, c->gd_ecs, bytes + HVC_HD_ECS_SLACK))) return r;
+    if ((r = grow(c, c->gd_meta, meta_words * sizeof(unsigned) + 64))) return r;
+    if ((r = grow(c, c->gd_state, HVC_HD_STATE_BYTES(subs)))) return r;
+    if ((r = grow(c, c->gd_dcd, nU * P.blocks_per_frame * sizeof(int16_t)))) return r;
+    P.dcd = c->gd_dcd.as<int16_t>();
+    unsigned *m = c->gd_meta.as<unsigned>();
     unsigned *d_ecs_off = m, *d_sub_off = m + nU, *d_frame_of = d_sub_off + nU + 1;
     unsigned *d_frame_blocks = d_frame_of + subs, *d_flags = d_frame_blocks + nU;
     hipStream_t st = c->stream;
@@ -300,7 +289,7 @@ int gpu_entropy_decode(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *si
         hipStream_t s;
         ~SyncOnExit() { (void)hipStreamSynchronize(s); }
     } sync_on_exit{st};
-    HIPCHK(c, hipMemcpyAsync(c->gd_ecs, h_ecs, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->gd_ecs.p, h_ecs, bytes, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(m, h_meta.data(), h_meta.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
     bool pf = sets.size() > 1;
     bool any_ovf = false; // a table with prefixes beyond its sub-tables: only the fast kernels know the overflow search
@@ -322,27 +311,27 @@ int gpu_entropy_decode(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *si
         }
         for (size_t k = 0; k < sets.size(); k++) hvc::make_frame_tabs(sets[k], P.n_comp, ftabs[k]);
         const size_t tb = sets.size() * sizeof(hvc::HdFrameTabs);
-        if ((r = grow(c, &c->gd_ftabs, &c->gd_ftabs_cap, tb + nU * sizeof(unsigned)))) return r;
-        HIPCHK(c, hipMemcpyAsync(c->gd_ftabs, ftabs.data(), tb, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync((char *)c->gd_ftabs + tb, tabset_of.data(), nU * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        if ((r = grow(c, c->gd_ftabs, tb + nU * sizeof(unsigned)))) return r;
+        HIPCHK(c, hipMemcpyAsync(c->gd_ftabs.p, ftabs.data(), tb, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->gd_ftabs.as<char>() + tb, tabset_of.data(), nU * sizeof(unsigned), hipMemcpyHostToDevice, st));
         P.tables = nullptr;
         P.spec = nullptr;
-        P.ftabs = (const hvc::HdFrameTabs *)c->gd_ftabs;
-        P.tabset_of = (const unsigned *)((char *)c->gd_ftabs + tb);
+        P.ftabs = c->gd_ftabs.as<const hvc::HdFrameTabs>();
+        P.tabset_of = (const unsigned *)(c->gd_ftabs.as<char>() + tb);
         P.selmask = gd_component_selmask(P);
         if (gd_lists_per_frame(P.total_sub, n_frames)) {
-            if ((r = grow(c, &c->gd_fcnt, &c->gd_fcnt_cap, (size_t)HVC_HD_LIST_N * nU * sizeof(unsigned)))) return r;
-            P.list_fn = (unsigned *)c->gd_fcnt; // work lists per file (k_hd_sync_pf)
+            if ((r = grow(c, c->gd_fcnt, (size_t)HVC_HD_LIST_N * nU * sizeof(unsigned)))) return r;
+            P.list_fn = c->gd_fcnt.as<unsigned>(); // work lists per file (k_hd_sync_pf)
             for (size_t f = 0; f < (size_t)n_frames; f++) P.max_frame_sub = std::max(P.max_frame_sub, sub_off[(f + 1) * ipf] - sub_off[f * ipf]);
         }
     }
-    P.ecs = (const uint8_t *)c->gd_ecs;
+    P.ecs = c->gd_ecs.as<const uint8_t>();
     P.ecs_off = d_ecs_off;
     P.sub_off = d_sub_off;
     P.frame_of = d_frame_of;
     P.coefs = d_coefs;
     P.coef_fs = coef_fs;
-    gd_carve_state(P, c->gd_state, subs);
+    gd_carve_state(P, c->gd_state.p, subs);
     P.frame_blocks = d_frame_blocks;
     P.changed = d_flags;
     P.status = d_flags + 1;
@@ -430,8 +419,8 @@ int hvc_jpeg_entropy_decode_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const s
     int16_t *d = coefs;
     const size_t total = ((size_t)(n_frames - 1) * coef_fs + info->coef_count) * sizeof(int16_t);
     if (where == HVC_MEM_HOST) {
-        if ((r = grow(c, &c->gd_coefs, &c->gd_coefs_cap, total))) return r;
-        d = (int16_t *)c->gd_coefs;
+        if ((r = grow(c, c->gd_coefs, total))) return r;
+        d = c->gd_coefs.as<int16_t>();
     } else if ((uintptr_t)coefs & 15) {
         return HVC_E_ALIGNMENT;
     }
@@ -563,7 +552,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
     if ((r = pipeline_events(c))) return r;
     for (int i = 0; i < NB; i++)
         for (int k = 0; k < 3; k++)
-            if (!c->ev_et[i][k]) HIPCHK(c, hipEventCreate(&c->ev_et[i][k])); // per-slot stage timers
+            HIPCHK(c, c->ev_et[i][k].ensure()); // per-slot stage timers
     if ((r = ring_ensure(c, reader_rings(c), {ecs_bytes, ecs_bytes, meta_bytes, meta_bytes, ftabs_bytes, ftabs_bytes}))) return r;
     if ((r = ring_ensure(c, coef_rings(c), {coef_chunk, coef_chunk}))) return r; // the coefficient ring of the host-decoder pipeline is reused
     if ((r = ring_ensure(c, out_rings(c), {oring_bytes}))) return r;
@@ -572,34 +561,34 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
     // stretches that are slow to synchronise, each round a full kernel's latency) overlap with the next chunk's
     // first ones, which fill the GPU.
     static_assert(hvc_ctx::RING <= 3, "ev_rd");
-    if (where == HVC_MEM_HOST && !c->down_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->down_stream, hipStreamNonBlocking));
+    if (where == HVC_MEM_HOST) HIPCHK(c, c->down_stream.ensure());
     if (!c->rd_stream[0]) {
         // two streams of the same priority can end up on one hardware queue (they did: no overlap at all);
         // streams of different priorities never share one
         int least = 0, greatest = 0;
         HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(c, hipStreamCreateWithPriority(&c->rd_stream[0], hipStreamNonBlocking, least));
-        HIPCHK(c, hipStreamCreateWithPriority(&c->rd_stream[1], hipStreamNonBlocking, greatest));
-        HIPCHK(c, hipStreamCreateWithPriority(&c->rd_stream[2], hipStreamNonBlocking, (least + greatest) / 2));
+        HIPCHK(c, c->rd_stream[0].ensure(least));
+        HIPCHK(c, c->rd_stream[1].ensure(greatest));
+        HIPCHK(c, c->rd_stream[2].ensure((least + greatest) / 2));
     }
     for (int i = 0; i < NB; i++)
-        if (!c->ev_rd[i]) HIPCHK(c, hipEventCreate(&c->ev_rd[i]));
+        HIPCHK(c, c->ev_rd[i].ensure());
 #ifndef HVC_NRD
 #define HVC_NRD 2
 #endif
     constexpr int NRD = HVC_NRD; // reader streams in use (round 1: 1: 71 Gpixel/s on config 3, 2: 77, 3: 79 with half as much scratch again)
     const size_t state_bytes = (HVC_HD_STATE_BYTES((size_t)C * nsub_max) + 255) & ~(size_t)255;
-    if ((r = grow(c, &c->gd_state, &c->gd_state_cap, NRD * state_bytes))) return r;
-    if ((r = grow(c, &c->gd_fcnt, &c->gd_fcnt_cap, (size_t)NRD * HVC_HD_LIST_N * CU * sizeof(unsigned)))) return r;
+    if ((r = grow(c, c->gd_state, NRD * state_bytes))) return r;
+    if ((r = grow(c, c->gd_fcnt, (size_t)NRD * HVC_HD_LIST_N * CU * sizeof(unsigned)))) return r;
     const size_t dcd_elems = (CU * G.blocks_per_frame + 127) & ~(size_t)127;
-    if ((r = grow(c, &c->gd_dcd, &c->gd_dcd_cap, NRD * dcd_elems * sizeof(int16_t)))) return r;
+    if ((r = grow(c, c->gd_dcd, NRD * dcd_elems * sizeof(int16_t)))) return r;
     // The DC values go from the reader's DC pass to the block stage through a compact array, one per ring slot (a
     // chunk's block stage may still read it while the next chunk's DC pass runs), instead of 2 bytes into each
     // 128-byte record -- unless a diagnostic kernel selection asks for the A/B alternates, which read the records.
     const bool dc_compact = c->decode_kernel == 0 || c->decode_kernel == 2;
     const size_t dcv_fs = info0.coef_count / 64; // (a tight record: whole blocks)
     const size_t dcv_elems = ((size_t)C * dcv_fs + 127) & ~(size_t)127;
-    if (dc_compact && (r = grow(c, &c->gd_dcv, &c->gd_dcv_cap, (size_t)NB * dcv_elems * sizeof(int16_t)))) return r;
+    if (dc_compact && (r = grow(c, c->gd_dcv, (size_t)NB * dcv_elems * sizeof(int16_t)))) return r;
     if ((r = gd_upload_tables(c, tables0, G, c->stream))) return r;
     // A chunk whose files all carry the first file's tables (and those fit two slots) runs on the LDS-table kernels;
     // any other chunk in PF mode (hvc_hdec.h): per-frame tables in device memory, record 0 of every ring slot = the
@@ -609,7 +598,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
     if (!uniform_ok && !pf_fits) return host_pipeline();
     // tables with overflow prefixes (hvc_hdec.h HVC_HD_OVF) need the fast write pass, which a chunk this size may not fit
     if (!pf_fits && hvc::tables_use_overflow(tables0, G.n_comp)) return host_pipeline();
-    for (int i = 0; i < NB; i++) hvc::make_frame_tabs(tables0, G.n_comp, *(hvc::HdFrameTabs *)c->gp_h_ftabs[i]);
+    for (int i = 0; i < NB; i++) hvc::make_frame_tabs(tables0, G.n_comp, *c->gp_h_ftabs[i].as<hvc::HdFrameTabs>());
     const unsigned comp_selmask = gd_component_selmask(G);
     std::vector<char> frame_pf((size_t)n_frames, 0); // the frame has tables of its own
 
@@ -652,7 +641,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
             if (!e && (!same_geometry(fi, info0) || fi.n_qtabs != info0.n_qtabs || std::memcmp(fi.qtabs, info0.qtabs, sizeof fi.qtabs)))
                 e = HVC_E_INVALID_ARG; // a batch shares one geometry and one set of quantiser tables
             bool ok = false;
-            uint8_t *dst = (uint8_t *)c->gp_h_ecs[slot] + (size_t)(f - k * C) * R; // unstuffed straight into the pinned slot
+            uint8_t *dst = c->gp_h_ecs[slot].as<uint8_t>() + (size_t)(f - k * C) * R; // unstuffed straight into the pinned slot
             size_t got = 0;
             if (!e && ipf > 1) { // (every interval's slot is zero-filled behind its bytes as it is written)
                 hvc::RstUnits ru{rst, ipf, unit_off.data() + (size_t)f * ipf, unit_len.data() + (size_t)f * ipf};
@@ -663,7 +652,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
             const bool own_tables = !e && ok && std::memcmp(&t, &tables0, sizeof t) != 0;
             const bool unfit = !e && (!ok || (own_tables && !pf_fits) || (!pf_fits && ok && hvc::tables_use_overflow(t, info0.n_comp)));
             if (own_tables && !unfit) { // its own Huffman tables: a record of its own
-                hvc::make_frame_tabs(t, info0.n_comp, ((hvc::HdFrameTabs *)c->gp_h_ftabs[slot])[1 + (f - k * C)]);
+                hvc::make_frame_tabs(t, info0.n_comp, (c->gp_h_ftabs[slot].as<hvc::HdFrameTabs>())[1 + (f - k * C)]);
                 frame_pf[(size_t)f] = 1;
             }
             if (!e && !unfit) {
@@ -706,7 +695,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
                 const int slot = k % NB, first = k * C, cnt = (first + C <= n_frames) ? C : n_frames - first;
                 hipError_t e = hipStreamWaitEvent(c->down_stream, c->ev_et[slot][2], 0);
                 if (e == hipSuccess)
-                    e = hipMemcpy2DAsync(pixels + (size_t)first * pixel_fs, pixel_fs, c->d_oring[slot], out_bytes, out_bytes,
+                    e = hipMemcpy2DAsync(pixels + (size_t)first * pixel_fs, pixel_fs, c->d_oring[slot].p, out_bytes, out_bytes,
                                          (size_t)cnt, hipMemcpyDeviceToHost, c->down_stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(c->down_stream);
                 if (e != hipSuccess) dl_err.store((int)e);
@@ -748,7 +737,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
                 he = wait_event(c->ev_kern[slot]);
             }
             if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-            const unsigned *flags = (const unsigned *)c->gp_h_meta[slot] + (meta_words - 2);
+            const unsigned *flags = c->gp_h_meta[slot].as<const unsigned>() + (meta_words - 2);
             if (gd_unsettled(flags[0], 4) || flags[1]) chunk_host[(size_t)v] = 1; // not settled / the model raises / truncated: what was decoded is redone
             float ms = 0; // stage times of the chunk that just finished (read late so that nothing waits for them)
             if (hipEventElapsedTime(&ms, c->ev_et[slot][0], c->ev_h2d[slot]) == hipSuccess) h2d_ms += ms;
@@ -776,7 +765,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
             continue;
         }
         // the chunk's index arrays
-        unsigned *hm = (unsigned *)c->gp_h_meta[slot];
+        unsigned *hm = c->gp_h_meta[slot].as<unsigned>();
         unsigned *h_ecs_off = hm, *h_sub_off = hm + CU, *h_tabset_of = h_sub_off + CU + 1; // (frame_of: filled on the GPU)
         unsigned subs = 0;
         bool pf = !uniform_ok;
@@ -794,42 +783,42 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
         }
         const size_t nu = (size_t)cnt * ipf;
         h_sub_off[nu] = subs;
-        unsigned *dm = (unsigned *)c->gp_d_meta[slot];
+        unsigned *dm = c->gp_d_meta[slot].as<unsigned>();
         hvc::HdParams P = G;
         P.n_frames = (int)nu;
         P.total_sub = subs;
-        P.ecs = (const uint8_t *)c->gp_d_ecs[slot];
+        P.ecs = c->gp_d_ecs[slot].as<const uint8_t>();
         P.ecs_off = dm;
         P.sub_off = dm + CU;
         P.frame_of = dm + CU + CU + 1 + CU;
         if (pf) {
             P.tables = nullptr;
             P.spec = nullptr;
-            P.ftabs = (const hvc::HdFrameTabs *)c->gp_d_ftabs[slot];
+            P.ftabs = c->gp_d_ftabs[slot].as<const hvc::HdFrameTabs>();
             P.tabset_of = dm + CU + CU + 1;
             P.selmask = comp_selmask;
             if (gd_lists_per_frame(subs, cnt)) {
-                P.list_fn = (unsigned *)c->gd_fcnt + (size_t)(k % NRD) * HVC_HD_LIST_N * CU; // work lists per frame (k_hd_sync_pf)
+                P.list_fn = c->gd_fcnt.as<unsigned>() + (size_t)(k % NRD) * HVC_HD_LIST_N * CU; // work lists per frame (k_hd_sync_pf)
                 P.max_frame_sub = (unsigned)nsub_max;
             }
         }
         P.frame_blocks = dm + (meta_words - 2 - CU);
         P.changed = dm + (meta_words - 2);
         P.status = dm + (meta_words - 1);
-        P.coefs = (int16_t *)c->d_ring[slot];
+        P.coefs = c->d_ring[slot].as<int16_t>();
         P.coef_fs = info0.coef_count;
-        gd_carve_state(P, (char *)c->gd_state + (size_t)(k % NRD) * state_bytes, (size_t)C * nsub_max);
-        P.dcd = (int16_t *)c->gd_dcd + (size_t)(k % NRD) * dcd_elems;
-        P.dc_plane = dc_compact ? (int16_t *)c->gd_dcv + (size_t)slot * dcv_elems : nullptr;
+        gd_carve_state(P, c->gd_state.as<char>() + (size_t)(k % NRD) * state_bytes, (size_t)C * nsub_max);
+        P.dcd = c->gd_dcd.as<int16_t>() + (size_t)(k % NRD) * dcd_elems;
+        P.dc_plane = dc_compact ? c->gd_dcv.as<int16_t>() + (size_t)slot * dcv_elems : nullptr;
         P.dc_fs = dcv_fs;
         hipStream_t rs = c->rd_stream[k % NRD];
         hipError_t he = hipEventRecord(c->ev_et[slot][0], c->copy_stream);
         if (he == hipSuccess)
-            he = hipMemcpyAsync(c->gp_d_ecs[slot], c->gp_h_ecs[slot], (size_t)cnt * R, hipMemcpyHostToDevice, c->copy_stream);
+            he = hipMemcpyAsync(c->gp_d_ecs[slot].p, c->gp_h_ecs[slot].p, (size_t)cnt * R, hipMemcpyHostToDevice, c->copy_stream);
         if (he == hipSuccess)
             he = hipMemcpyAsync(dm, hm, (3 * CU + 1) * sizeof(unsigned), hipMemcpyHostToDevice, c->copy_stream);
         if (he == hipSuccess && pf) // the tables of the chunk's frames (36 KB a frame against ~1 MB of segment)
-            he = hipMemcpyAsync(c->gp_d_ftabs[slot], c->gp_h_ftabs[slot], ((size_t)cnt + 1) * sizeof(hvc::HdFrameTabs),
+            he = hipMemcpyAsync(c->gp_d_ftabs[slot].p, c->gp_h_ftabs[slot].p, ((size_t)cnt + 1) * sizeof(hvc::HdFrameTabs),
                                 hipMemcpyHostToDevice, c->copy_stream);
         if (he == hipSuccess) he = hipEventRecord(c->ev_h2d[slot], c->copy_stream);
         // (the slot's records and index arrays are free: the verdict above waited for chunk k - NB's block stage)
@@ -841,7 +830,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
         if (he == hipSuccess) he = hipEventRecord(c->ev_rd[slot], rs);
         if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_rd[slot], 0);
         if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-        uint8_t *dst = where == HVC_MEM_DEVICE ? pixels + (size_t)first * pixel_fs : (uint8_t *)c->d_oring[slot];
+        uint8_t *dst = where == HVC_MEM_DEVICE ? pixels + (size_t)first * pixel_fs : c->d_oring[slot].as<uint8_t>();
         const size_t dst_fs = where == HVC_MEM_DEVICE ? pixel_fs : out_bytes;
         block_stage.dc_plane = P.dc_plane;
         block_stage.dc_fs = P.dc_fs;

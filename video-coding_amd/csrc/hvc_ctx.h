@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -47,13 +48,94 @@
 #define HVC_PROF_RING 64
 #define HVC_FIX_WORDS 8 /* d_fix_count: [0] [1] counters, [2..3] the 64-bit total, [4] [5] the fused path's luma counters */
 
+// ---------------------------------------------------------------------------
+// What a context owns.  Three types, each a member that can be neither copied nor moved and whose destructor releases
+// what it holds; hvc_destroy drains the streams and deletes the context, nothing else.
+
+struct Pinned { // pinned host memory with these hipHostMalloc flags (a Buf declared without one is device memory)
+    unsigned flags;
+};
+// A buffer: pointer and capacity in bytes.  Filled by grow (below), or by ring_ensure for the slots of a ring.
+struct Buf {
+    void *p = nullptr;
+    size_t cap = 0;
+    const bool pinned = false;
+    const unsigned flags = 0;
+    Buf() = default;
+    Buf(Pinned k) : pinned(true), flags(k.flags) {}
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() { (void)release(); }
+    template <class T = void>
+    T *as() const { return static_cast<T *>(p); }
+    explicit operator bool() const { return p != nullptr; }
+    hipError_t release() {
+        const hipError_t e = !p ? hipSuccess : pinned ? hipHostFree(p) : hipFree(p);
+        p = nullptr;
+        cap = 0;
+        return e;
+    }
+    void adopt(Buf &from) { // (of the same kind) a local that is complete becomes the context's
+        (void)release();
+        p = from.p, cap = from.cap;
+        from.p = nullptr, from.cap = 0;
+    }
+};
+// An event, created by the first ensure() with the flags given there.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    operator hipEvent_t() const { return e; }
+    hipError_t ensure(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+};
+// A stream of the context's own, created by the first ensure(): non-blocking, with a priority where one is given.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+    operator hipStream_t() const { return s; }
+    hipError_t ensure() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    hipError_t ensure(int priority) { return s ? hipSuccess : hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority); }
+};
+
+// A plan's image in a device buffer, the pinned image it was uploaded from (a call whose plan is the same bytes uploads
+// nothing) and the event behind the last upload (upload_image, hvc_capi_mixed.hip)
+struct PlanBuf {
+    Buf d, h{Pinned{hipHostMallocDefault}};
+    size_t len = 0; // bytes of the image d holds, 0 = none
+    Event ev;
+};
+
+// pinned rings the host only ever writes (unstuffed segments, padded raw frames) and the copy engine reads
+#ifndef HVC_UPLOAD_RING_FLAGS
+#define HVC_UPLOAD_RING_FLAGS hipHostMallocDefault
+#endif
+#define HVC_RING3(kind) {kind, kind, kind} /* the RING slots of a ring, all of one kind */
+#define HVC_PINNED_RING HVC_RING3(Pinned{hipHostMallocDefault})
+#define HVC_UPLOAD_RING HVC_RING3(Pinned{HVC_UPLOAD_RING_FLAGS})
+
+// Members are destroyed in reverse order of declaration: the streams come FIRST, so that every buffer and event below
+// them is released before the streams are destroyed (hvc_destroy has drained them by then).  Adding a buffer is one line:
+// declare it here, as a Buf (device), a Buf{Pinned{flags}} or a ring of them, and grow it where it is used.
 struct hvc_ctx {
     int device = -1;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Stream own_stream;
+    hipStream_t stream = nullptr; // own_stream, or the caller's (hvc_set_stream): never destroyed here
+    Stream side_stream;           // the fused 4:4:4 path's side-by-side form: the stream the luma kernel runs on
+    Stream down_stream, copy_stream; // hvc_jpeg_decode_batch: copy stream + ring of pinned host / device coefficient chunks
+    Stream rd_stream[3];          // hvc_jpeg_decode_batch_gpu: the Huffman reader of even / odd chunks
+    Event ev0, ev1;
     // ring of event pairs around the dominant kernel of the last HVC_PROF_RING profiled calls
-    hipEvent_t k0[HVC_PROF_RING] = {}, k1[HVC_PROF_RING] = {};
+    Event k0[HVC_PROF_RING], k1[HVC_PROF_RING];
     unsigned long long k_calls = 0;
     bool profiling = false;
     int mixed_reader = HVC_READER_HOST; // hvc_set_mixed_reader: who reads the files of the mixed batch calls
@@ -65,73 +147,55 @@ struct hvc_ctx {
     int enc_arith = HVC_ARITH_MODEL; // hvc_set_encode_arithmetic: the encoder's (HARDCAML: k_hardcaml_encode, hvc_hardcaml.hip)
     int huff_tables = HVC_HUFF_DEFAULT; // hvc_set_huffman_tables: the files' Huffman tables (OPTIMISED: k_huff_hist / k_huff_build)
     int restart_interval = 0; // hvc_set_restart_interval: MCUs per restart interval of the files written, 0 = no DRI / RSTn
-    unsigned *d_fix_count = nullptr; // two counters, used alternately (see k_decode_wide); behind them (+ 8 bytes) the 64-bit
-                                     // total of the last call's fix-up blocks over all its launches (hvc_last_wide_blocks)
+    Buf d_fix_count; // two counters, used alternately (see k_decode_wide); behind them (+ 8 bytes) the 64-bit
+                     // total of the last call's fix-up blocks over all its launches (hvc_last_wide_blocks)
     // [4], [5]: a second pair of counters, for the luma planes of the fused 4:4:4 path when they run through
     // k_decode_packed beside (or before) the chroma tiles' kernel, which uses the first pair
     int fix_phase_l = 0;
-    hipStream_t side_stream = nullptr; // ... and the stream that kernel runs on in the side-by-side form, with its fork / join events
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    Event ev_fork, ev_join; // ... and the side stream's fork / join events
     bool wide_total_started = false; // the current call has enqueued a launch that stores (rather than adds to) that total
     long long wide_host = -1;        // >= 0: the last call sent every block through the int64 kernel (no list): this many
     int fix_phase = 0;               // index of the counter the NEXT decode call appends to
     int fix_last = 0;                // index of the counter the last decode call used
-    unsigned *d_fix_list = nullptr;
-    size_t fix_cap = 0; // entries
-    void *d_in = nullptr, *d_out = nullptr, *d_sums = nullptr, *d_aux = nullptr, *d_aux2 = nullptr;
-    size_t in_cap = 0, out_cap = 0, sums_cap = 0, aux_cap = 0, aux2_cap = 0;
+    Buf d_fix_list; // unsigned entries
+    Buf d_in, d_out, d_sums, d_aux, d_aux2;
     // hvc_decode_frames_divergence / hvc_encode_frames_divergence: the model's output (pixels / records), and (host memory
     // calls) the input and the divergence bytes
-    void *d_div_px = nullptr, *d_div_in = nullptr, *d_div_out = nullptr;
-    size_t div_px_cap = 0, div_in_cap = 0, div_out_cap = 0;
+    Buf d_div_px, d_div_in, d_div_out;
     // hvc_dct_*: the tables (uploaded at the first call) with k_dct_fixed's range flag, and two scratch buffers
-    void *d_dct_tab = nullptr, *d_dct_a = nullptr, *d_dct_b = nullptr;
-    size_t dct_a_cap = 0, dct_b_cap = 0;
+    Buf d_dct_tab, d_dct_a, d_dct_b;
     int last_hip = 0;
-    // hvc_jpeg_decode_batch: copy stream + ring of pinned host / device coefficient chunks
     static constexpr int RING = 3;
-    hipStream_t copy_stream = nullptr, down_stream = nullptr;
-    hipStream_t rd_stream[3] = {}; // hvc_jpeg_decode_batch_gpu: the Huffman reader of even / odd chunks
-    hipEvent_t ev_rd[3] = {};      // ... its "records complete" per ring slot (RING entries)
-    void *h_ring[RING] = {}, *d_ring[RING] = {}, *d_oring[RING] = {};
+    static_assert(RING == 3, "HVC_RING3 names the slots of a ring one by one");
+    Event ev_rd[3]; // the Huffman reader's "records complete" per ring slot (RING entries)
+    Buf h_ring[RING] = HVC_PINNED_RING, d_ring[RING], d_oring[RING];
     size_t ring_bytes = 0, oring_bytes = 0;
-    hipEvent_t ev_h2d[RING] = {}, ev_kern[RING] = {}, ev_t[4] = {};
+    Event ev_h2d[RING], ev_kern[RING], ev_t[4];
     // hvc_jpeg_encode_batch: pinned / device rings of padded pixel chunks (in) and coefficient chunks (out)
-    void *eh_in[RING] = {}, *ed_in[RING] = {}, *eh_out[RING] = {}, *ed_out[RING] = {};
+    Buf eh_in[RING] = HVC_UPLOAD_RING, ed_in[RING], eh_out[RING] = HVC_PINNED_RING, ed_out[RING];
     size_t e_in_bytes = 0, e_out_bytes = 0;
-    hipEvent_t ev_up[RING] = {}, ev_down[RING] = {}, ev_et[RING][3] = {}, ev_gpu[RING] = {};
-    void *ed_seg[RING] = {}, *ed_off[RING] = {}, *eh_off[RING] = {}; // hvc_jpeg_encode_batch_gpu: packed segments + offsets
+    Event ev_up[RING], ev_down[RING], ev_et[RING][3], ev_gpu[RING];
+    Buf ed_seg[RING], ed_off[RING], eh_off[RING] = HVC_PINNED_RING; // hvc_jpeg_encode_batch_gpu: packed segments + offsets
     size_t e_seg_bytes = 0, e_off_bytes = 0;
-    void *eh_specs[RING] = {}; // ... and, with optimised tables, each frame's four specs (pinned)
+    Buf eh_specs[RING] = HVC_PINNED_RING; // ... and, with optimised tables, each frame's four specs
     size_t e_specs_bytes = 0;
     // hvc_jpeg_decode_batch_gpu: pinned / device rings of unstuffed segments and their index arrays
-    void *gp_h_ecs[RING] = {}, *gp_d_ecs[RING] = {}, *gp_h_meta[RING] = {}, *gp_d_meta[RING] = {};
-    void *gp_h_ftabs[RING] = {}, *gp_d_ftabs[RING] = {}; // ... and of per-frame Huffman tables (hvc::HdFrameTabs, PF mode)
+    Buf gp_h_ecs[RING] = HVC_UPLOAD_RING, gp_d_ecs[RING], gp_h_meta[RING] = HVC_PINNED_RING, gp_d_meta[RING];
+    Buf gp_h_ftabs[RING] = HVC_UPLOAD_RING, gp_d_ftabs[RING]; // ... and of per-frame Huffman tables (hvc::HdFrameTabs, PF mode)
     size_t gp_ecs_bytes = 0, gp_meta_bytes = 0, gp_ftabs_bytes = 0;
     // GPU Huffman decoder (hvc_jpeg_entropy_decode_gpu): device scratch, grown on demand
-    void *gd_ecs = nullptr, *gd_meta = nullptr, *gd_state = nullptr, *gd_tables = nullptr, *gd_coefs = nullptr, *gd_dcd = nullptr;
-    void *gd_h_ecs = nullptr; // pinned: the batch's unstuffed segments on their way to gd_ecs
-    size_t gd_h_ecs_cap = 0;
-    void *gd_fcnt = nullptr;  // PF mode: per-frame list lengths per round (hvc::HdParams::list_fn)
-    size_t gd_fcnt_cap = 0;
-    void *gd_ftabs = nullptr; // per-frame tables of hvc_jpeg_entropy_decode_gpu (PF mode)
-    size_t gd_ftabs_cap = 0;
-    void *gd_dcv = nullptr;   // batch pipeline: the blocks' DC values as a compact array (hvc::DecodeParams::dc_plane)
-    size_t gd_dcv_cap = 0;
-    void *d_dcfix = nullptr;  // blocks with a DC beyond int16 (hvc::WideDc): ids, true DCs, count
-    size_t dcfix_cap = 0;
-    // hvc_decode_frames_mixed (hvc_capi_mixed.hip): the plan's tables on the device, the pinned image they were uploaded
-    // from (a call whose plan is the same bytes uploads nothing) and the event behind the last upload
-    void *d_mixed = nullptr, *h_mixed = nullptr;
-    size_t mixed_cap = 0, h_mixed_cap = 0, mixed_len = 0; // mixed_len: bytes of the image d_mixed holds, 0 = none
-    hipEvent_t ev_mixed = nullptr;
-    // ... and the same three for the colour pass over a mixed batch (k_ycc_to_rgb_mixed): a buffer of its own, so that the
-    // colour plan of a chunk never overwrites the block-stage plan of that chunk
-    void *d_mixed_rgb = nullptr, *h_mixed_rgb = nullptr;
-    size_t mixed_rgb_cap = 0, h_mixed_rgb_cap = 0, mixed_rgb_len = 0;
-    hipEvent_t ev_mixed_rgb = nullptr;
+    Buf gd_ecs, gd_meta, gd_state, gd_tables, gd_coefs, gd_dcd;
+    Buf gd_h_ecs{Pinned{HVC_UPLOAD_RING_FLAGS}}; // the batch's unstuffed segments on their way to gd_ecs
+    Buf gd_fcnt;  // PF mode: per-frame list lengths per round (hvc::HdParams::list_fn)
+    Buf gd_ftabs; // per-frame tables of hvc_jpeg_entropy_decode_gpu (PF mode)
+    Buf gd_dcv;   // batch pipeline: the blocks' DC values as a compact array (hvc::DecodeParams::dc_plane)
+    Buf d_dcfix;  // blocks with a DC beyond int16 (hvc::WideDc): ids, true DCs, count
+    // hvc_decode_frames_mixed (hvc_capi_mixed.hip): the block stage's plan, and the plan of the colour pass over a mixed batch
+    // (k_ycc_to_rgb_mixed): a buffer of its own, so that the colour plan of a chunk never overwrites the block-stage plan of
+    // that chunk
+    PlanBuf mixed_plan, mixed_rgb_plan;
     // hvc_jpeg_decode_batch_mixed_rgb: the ring of device slots the chunks' decoded planes live in (they never leave the GPU)
-    void *d_pring[RING] = {};
+    Buf d_pring[RING];
     size_t pring_bytes = 0;
     // hvc_set_host_cpus: the CPUs the batch pipelines' host threads may run on (empty = no restriction)
     bool have_cpus = false;
@@ -140,79 +204,55 @@ struct hvc_ctx {
     bool have_default_cpus = false; // the process's own mask when the context was created: what the pool's threads go
     cpu_set_t default_cpus;         // back to when a restriction is lifted (they outlive the call that pinned them)
     hvc::WorkerPool pool;           // the batch pipelines' host threads (hvc_pool.h): persistent, joined in hvc_destroy
-    hvc::HdTables *gd_tables_host = nullptr; // what gd_tables holds (value tables; the HdSpec behind them follows from these)
+    std::unique_ptr<hvc::HdTables> gd_tables_host; // what gd_tables holds (value tables; the HdSpec behind them follows from these)
     bool gd_tables_valid = false;
     int gd_tables_ncomp = 0;
-    size_t gd_ecs_cap = 0, gd_meta_cap = 0, gd_state_cap = 0, gd_tables_cap = 0, gd_coefs_cap = 0, gd_dcd_cap = 0;
     // GPU Huffman coder (hvc_huffman_encode_frames): tables + scratch, grown on demand
-    unsigned *hd_tables = nullptr;
-    void *hd_opt = nullptr; // optimised tables: per-frame counts, code tables and specs (HuffParams hist / opt_tables / specs)
-    size_t hd_opt_cap = 0;
-    void *hd_lens = nullptr, *hd_meta = nullptr, *hd_bitbuf = nullptr, *hd_ff = nullptr, *hd_out = nullptr;
-    size_t hd_lens_cap = 0, hd_meta_cap = 0, hd_bitbuf_cap = 0, hd_ff_cap = 0, hd_out_cap = 0;
-    void *hd_ivl = nullptr; // restart intervals: bytes / byte bases per interval (HuffParams ivl)
-    size_t hd_ivl_cap = 0;
+    Buf hd_tables; // (unsigned words)
+    Buf hd_opt;    // optimised tables: per-frame counts, code tables and specs (HuffParams hist / opt_tables / specs)
+    Buf hd_lens, hd_meta, hd_bitbuf, hd_ff, hd_out;
+    Buf hd_ivl; // restart intervals: bytes / byte bases per interval (HuffParams ivl)
     // The asynchronous seam (hvc_capi_async.hip): one batch in flight per slot.  Uploads run on copy_stream, the block stage
     // on `stream`, downloads on down_stream; a slot's device buffers are its own (grown while the slot is free).
     struct Slot {
-        void *d_in = nullptr, *d_out = nullptr;
-        size_t in_cap = 0, out_cap = 0;
+        Buf d_in, d_out;
         // up0 / up1 around the upload, k0 / k1 around the block stage, dn0 / dn1 around the download; `done` = the last of them
-        hipEvent_t up0 = nullptr, up1 = nullptr, k0 = nullptr, k1 = nullptr, dn0 = nullptr, dn1 = nullptr;
+        Event up0, up1, k0, k1, dn0, dn1;
         bool busy = false, has_down = false, timed = false;
         unsigned long long h2d_bytes = 0, d2h_bytes = 0;
     } slots[HVC_SLOTS];
 };
 
-// pinned rings the host only ever writes (unstuffed segments, padded raw frames) and the copy engine reads
-#ifndef HVC_UPLOAD_RING_FLAGS
-#define HVC_UPLOAD_RING_FLAGS hipHostMallocDefault
-#endif
-
 // The pipelines' rings: RING pinned / device buffers per member, members that are (re)allocated together as a set.
 struct RingMember {
-    void *(*ring)[hvc_ctx::RING];
+    Buf (*ring)[hvc_ctx::RING];
     size_t *recorded; // the bytes it was last allocated for (members of the same size share one)
-    bool pinned;      // hipHostMalloc with `flags`, else hipMalloc of the bytes + `slack`
-    unsigned flags;
-    size_t slack;
+    size_t slack;     // a device member is allocated with this many bytes more
 };
 struct RingSet {
     RingMember m[6];
     int n;
     bool drain_copy; // copy_stream is drained as well as `stream` before the old buffers go
 };
-inline RingSet coef_rings(hvc_ctx *c) { // coefficient chunks of the decode pipelines
-    return {{{&c->h_ring, &c->ring_bytes, true, hipHostMallocDefault, 0}, {&c->d_ring, &c->ring_bytes, false, 0, 0}}, 2, true};
-}
-inline RingSet out_rings(hvc_ctx *c) { return {{{&c->d_oring, &c->oring_bytes, false, 0, 0}}, 1, false}; } // decoded chunks on their way to the host
-inline RingSet plane_rings(hvc_ctx *c) { return {{{&c->d_pring, &c->pring_bytes, false, 0, 0}}, 1, false}; }
+inline RingSet coef_rings(hvc_ctx *c) { return {{{&c->h_ring, &c->ring_bytes, 0}, {&c->d_ring, &c->ring_bytes, 0}}, 2, true}; } // coefficient chunks of the decode pipelines
+inline RingSet out_rings(hvc_ctx *c) { return {{{&c->d_oring, &c->oring_bytes, 0}}, 1, false}; } // decoded chunks on their way to the host
+inline RingSet plane_rings(hvc_ctx *c) { return {{{&c->d_pring, &c->pring_bytes, 0}}, 1, false}; }
 inline RingSet reader_rings(hvc_ctx *c) { // hvc_jpeg_decode_batch_gpu: segments, index arrays, per-frame tables
-    return {{{&c->gp_h_ecs, &c->gp_ecs_bytes, true, HVC_UPLOAD_RING_FLAGS, 0},
-             {&c->gp_d_ecs, &c->gp_ecs_bytes, false, 0, HVC_HD_ECS_SLACK},
-             {&c->gp_h_meta, &c->gp_meta_bytes, true, hipHostMallocDefault, 0},
-             {&c->gp_d_meta, &c->gp_meta_bytes, false, 0, 0},
-             {&c->gp_h_ftabs, &c->gp_ftabs_bytes, true, HVC_UPLOAD_RING_FLAGS, 0},
-             {&c->gp_d_ftabs, &c->gp_ftabs_bytes, false, 0, 0}},
+    return {{{&c->gp_h_ecs, &c->gp_ecs_bytes, 0}, {&c->gp_d_ecs, &c->gp_ecs_bytes, HVC_HD_ECS_SLACK}, {&c->gp_h_meta, &c->gp_meta_bytes, 0},
+             {&c->gp_d_meta, &c->gp_meta_bytes, 0}, {&c->gp_h_ftabs, &c->gp_ftabs_bytes, 0}, {&c->gp_d_ftabs, &c->gp_ftabs_bytes, 0}},
             6, true};
 }
 inline RingSet enc_rings(hvc_ctx *c) { // hvc_jpeg_encode_batch: padded pixel chunks in, coefficient chunks out
-    return {{{&c->eh_in, &c->e_in_bytes, true, HVC_UPLOAD_RING_FLAGS, 0},
-             {&c->eh_out, &c->e_out_bytes, true, hipHostMallocDefault, 0},
-             {&c->ed_in, &c->e_in_bytes, false, 0, 0},
-             {&c->ed_out, &c->e_out_bytes, false, 0, 0}},
+    return {{{&c->eh_in, &c->e_in_bytes, 0}, {&c->eh_out, &c->e_out_bytes, 0}, {&c->ed_in, &c->e_in_bytes, 0}, {&c->ed_out, &c->e_out_bytes, 0}},
             4, true};
 }
 inline RingSet enc_seg_rings(hvc_ctx *c) { // hvc_jpeg_encode_batch_gpu: packed segments + offsets
-    return {{{&c->ed_seg, &c->e_seg_bytes, false, 0, 0}, {&c->ed_off, &c->e_off_bytes, false, 0, 0},
-             {&c->eh_off, &c->e_off_bytes, true, hipHostMallocDefault, 0}},
-            3, false};
+    return {{{&c->ed_seg, &c->e_seg_bytes, 0}, {&c->ed_off, &c->e_off_bytes, 0}, {&c->eh_off, &c->e_off_bytes, 0}}, 3, false};
 }
-inline RingSet enc_spec_rings(hvc_ctx *c) { return {{{&c->eh_specs, &c->e_specs_bytes, true, hipHostMallocDefault, 0}}, 1, false}; }
+inline RingSet enc_spec_rings(hvc_ctx *c) { return {{{&c->eh_specs, &c->e_specs_bytes, 0}}, 1, false}; }
 // A set grows when any member wants more than it has (`want`: bytes per member, in the set's order), and is then allocated
 // at the sizes wanted now.  HVC_OK, HVC_E_HIP (a stream did not drain) or HVC_E_OUT_OF_MEMORY.
 int ring_ensure(hvc_ctx *c, const RingSet &s, std::initializer_list<size_t> want);
-void ring_free(const RingSet &s);
 
 struct DeviceGuard {
     int prev = -1;
@@ -247,8 +287,23 @@ inline int pool_ready(hvc_ctx *c, int n, int extra = 0) { return c->pool.ensure(
 // Linux cpulist format ("0-15,32-47") -> cpu_set_t; false on a syntax error, an empty set or a CPU beyond CPU_SETSIZE
 bool parse_cpulist(const char *s, cpu_set_t &set);
 
-// device scratch *p of at least `need` bytes (grown with a quarter to spare; the stream is drained before the old one goes)
-int grow(hvc_ctx *c, void **p, size_t *cap, size_t need);
+// How a buffer grows: to need + need / spare_div + spare_add bytes (spare_div 0: no fraction), and whether c->stream is
+// drained before the old allocation goes.  Growth sizes are behaviour: they decide the resident footprint and when a
+// reallocation, with its drain, happens.
+struct GrowRule {
+    unsigned spare_div;
+    size_t spare_add;
+    enum { NO_DRAIN, DRAIN_HELD, DRAIN_ALWAYS } drain; // never / when there is an old allocation / whenever it grows
+    bool clear_error; // a refused allocation's error is taken off the runtime (hipGetLastError)
+};
+constexpr GrowRule GROW_SCRATCH{4, 4096, GrowRule::DRAIN_HELD, false};      // the context's device scratch: the default
+constexpr GrowRule GROW_SLOT{8, 4096, GrowRule::NO_DRAIN, false};           // a slot of the asynchronous seam, grown while it is free
+constexpr GrowRule GROW_PLAN_IMAGE{4, 4096, GrowRule::DRAIN_ALWAYS, false}; // PlanBuf::h
+constexpr GrowRule GROW_READER_STAGE{2, 0, GrowRule::NO_DRAIN, true};       // gd_h_ecs
+constexpr GrowRule GROW_EXACT{0, 0, GrowRule::NO_DRAIN, false};             // tables of a fixed size, allocated once
+// `b` of at least `need` bytes: HVC_OK, HVC_E_HIP (the stream did not drain, the old device allocation could not be freed) or
+// HVC_E_OUT_OF_MEMORY (device memory: with last_hip set)
+int grow(hvc_ctx *c, Buf &b, size_t need, const GrowRule &rule = GROW_SCRATCH);
 
 // The two fix-up counters alternate between launches: a launch appends to counter fix_phase and its wide kernel
 // clears the other one for the launch after it (no memset node).  The roles change hands only once a launch has
@@ -257,10 +312,10 @@ int grow(hvc_ctx *c, void **p, size_t *cap, size_t need);
 // would re-process old list entries under the new geometry).
 template <class Params>
 inline void fix_assign(const hvc_ctx *c, Params &P) {
-    P.fix_count = c->d_fix_count + c->fix_phase;
-    P.fix_count_next = c->d_fix_count + (c->fix_phase ^ 1);
-    P.fix_list = c->d_fix_list;
-    P.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count + 2);
+    P.fix_count = c->d_fix_count.as<unsigned>() + c->fix_phase;
+    P.fix_count_next = c->d_fix_count.as<unsigned>() + (c->fix_phase ^ 1);
+    P.fix_list = c->d_fix_list.as<unsigned>();
+    P.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count.as<unsigned>() + 2);
     P.wide_first = c->wide_total_started ? 0 : 1;
 }
 inline void fix_commit(hvc_ctx *c) {
@@ -274,7 +329,7 @@ inline void wide_total_begin(hvc_ctx *c) {
     c->wide_host = -1;
 }
 inline void fix_reset(hvc_ctx *c) { // after a failed launch: all counters to zero, in stream order
-    (void)hipMemsetAsync(c->d_fix_count, 0, HVC_FIX_WORDS * sizeof(unsigned), c->stream); // (and the total behind the first pair)
+    (void)hipMemsetAsync(c->d_fix_count.p, 0, HVC_FIX_WORDS * sizeof(unsigned), c->stream); // (and the total behind the first pair)
 }
 
 // Launches longer than about 3 ms lose 2-3 % against back-to-back shorter ones (measured on MI355X: 1080p batches of
@@ -339,9 +394,8 @@ hipError_t wait_event(hipEvent_t e);
 template <class Up, class Run, class Down>
 inline int overlapped_parts(hvc_ctx *c, int n_frames, Up up, Run run, Down down) {
     constexpr int K = 4;
-    if (!c->down_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->down_stream, hipStreamNonBlocking));
-    for (int i = 0; i < K; i++)
-        if (!c->ev_t[i]) HIPCHK(c, hipEventCreate(&c->ev_t[i]));
+    HIPCHK(c, c->down_stream.ensure());
+    for (int i = 0; i < K; i++) HIPCHK(c, c->ev_t[i].ensure());
     std::atomic<int> launched{0}, herr{0};
     auto part = [&](int k, int &f0, int &cnt) {
         f0 = (int)((long long)n_frames * k / K);

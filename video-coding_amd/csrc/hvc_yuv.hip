@@ -366,15 +366,15 @@ int plane_op(hvc_ctx *c, OpKind kind, const uint8_t *src, int sw, int sh, size_t
     }
     const size_t sbytes = (size_t)(n_planes - 1) * src_ps + (size_t)(sh - 1) * src_stride + (size_t)sw;
     const size_t dbytes = (size_t)(n_planes - 1) * dst_ps + (size_t)(dh - 1) * dst_stride + (size_t)dw;
-    int r = grow(c, &c->d_in, &c->in_cap, sbytes);
+    int r = grow(c, c->d_in, sbytes);
     if (r) return r;
-    if ((r = grow(c, &c->d_out, &c->out_cap, dbytes))) return r;
-    HIPCHK(c, hipMemcpyAsync(c->d_in, src, sbytes, hipMemcpyHostToDevice, c->stream));
-    P.src = (const uint8_t *)c->d_in;
-    P.dst = (uint8_t *)c->d_out;
+    if ((r = grow(c, c->d_out, dbytes))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_in.p, src, sbytes, hipMemcpyHostToDevice, c->stream));
+    P.src = c->d_in.as<const uint8_t>();
+    P.dst = c->d_out.as<uint8_t>();
     HIPCHK(c, launch_plane_op(kind, P, n_planes, c->stream));
     for (int p = 0; p < n_planes; p++) // (only what was written: the caller's padding stays)
-        HIPCHK(c, hipMemcpy2DAsync(dst + (size_t)p * dst_ps, dst_stride, (uint8_t *)c->d_out + (size_t)p * dst_ps, dst_stride,
+        HIPCHK(c, hipMemcpy2DAsync(dst + (size_t)p * dst_ps, dst_stride, c->d_out.as<uint8_t>() + (size_t)p * dst_ps, dst_stride,
                                    (size_t)dw, (size_t)dh, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HVC_OK;
@@ -460,18 +460,18 @@ int hvc_yuv_convert(hvc_ctx *c, const uint8_t *src, int src_format, int src_w, i
     uint8_t *d_dst = dst;
     int r;
     if (where == HVC_MEM_HOST) {
-        if ((r = grow(c, &c->d_in, &c->in_cap, in_fs * (size_t)n_frames))) return r;
-        if ((r = grow(c, &c->d_out, &c->out_cap, out_fs * (size_t)n_frames))) return r;
-        HIPCHK(c, hipMemcpyAsync(c->d_in, src, in_fs * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
-        d_src = (const uint8_t *)c->d_in;
-        d_dst = (uint8_t *)c->d_out;
+        if ((r = grow(c, c->d_in, in_fs * (size_t)n_frames))) return r;
+        if ((r = grow(c, c->d_out, out_fs * (size_t)n_frames))) return r;
+        HIPCHK(c, hipMemcpyAsync(c->d_in.p, src, in_fs * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
+        d_src = c->d_in.as<const uint8_t>();
+        d_dst = c->d_out.as<uint8_t>();
     }
     // scratch: [planar 4:2:2 of a packed input: 2 sp][full-size chroma of the input: 2 sp] and
     //          [cropped 4:4:4 chroma, or all three planes for a packed output: 3 dp][planar 4:2:2 of a packed output: 2 dp]
     const size_t a_fs = 4 * sp, b_fs = 5 * dp;
-    if ((r = grow(c, &c->d_aux, &c->aux_cap, a_fs * (size_t)n_frames))) return r;
-    if ((r = grow(c, &c->d_aux2, &c->aux2_cap, b_fs * (size_t)n_frames))) return r;
-    uint8_t *const A = (uint8_t *)c->d_aux, *const B = (uint8_t *)c->d_aux2;
+    if ((r = grow(c, c->d_aux, a_fs * (size_t)n_frames))) return r;
+    if ((r = grow(c, c->d_aux2, b_fs * (size_t)n_frames))) return r;
+    uint8_t *const A = c->d_aux.as<uint8_t>(), *const B = c->d_aux2.as<uint8_t>();
     hipStream_t st = c->stream;
     auto op = [&](OpKind kind, const uint8_t *s, int sw, int sh, size_t s_fs, uint8_t *d, int dw, int dh, size_t d_fs,
                   size_t s_stride = 0) -> hipError_t { // (s_stride: the source is a window of wider rows)
@@ -619,12 +619,12 @@ int hvc_yuv_to_rgb(hvc_ctx *c, const uint8_t *yuv, size_t yuv_fs, const hvc_comp
         return HVC_OK;
     }
     const size_t in_bytes = (size_t)(n_frames - 1) * yuv_fs + span;
-    if ((r = grow(c, &c->d_in, &c->in_cap, in_bytes))) return r;
-    if ((r = grow(c, &c->d_out, &c->out_cap, rgb_bytes(im, n_frames)))) return r;
-    HIPCHK(c, hipMemcpyAsync(c->d_in, yuv, in_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, ycc_to_rgb_device((const uint8_t *)c->d_in, yuv_fs, comps, sampling, width, height, chroma_w, chroma_h, n_frames,
-                                (uint8_t *)c->d_out, im, c->stream, c->arith));
-    HIPCHK(c, rgb_download((const uint8_t *)c->d_out, rgb, im, n_frames, c->stream));
+    if ((r = grow(c, c->d_in, in_bytes))) return r;
+    if ((r = grow(c, c->d_out, rgb_bytes(im, n_frames)))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_in.p, yuv, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, ycc_to_rgb_device(c->d_in.as<const uint8_t>(), yuv_fs, comps, sampling, width, height, chroma_w, chroma_h, n_frames,
+                                c->d_out.as<uint8_t>(), im, c->stream, c->arith));
+    HIPCHK(c, rgb_download(c->d_out.as<const uint8_t>(), rgb, im, n_frames, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HVC_OK;
 } HVC_ABI_CATCH
@@ -659,14 +659,14 @@ int hvc_rgb_to_yuv(hvc_ctx *c, const uint8_t *rgb, size_t rgb_row_stride, size_t
         return HVC_OK;
     }
     const size_t in_bytes = rgb_bytes(im, n_frames), out_bytes = (size_t)(n_frames - 1) * yuv_fs + span;
-    if ((r = grow(c, &c->d_in, &c->in_cap, in_bytes))) return r;
-    if ((r = grow(c, &c->d_out, &c->out_cap, out_bytes))) return r;
-    HIPCHK(c, hipMemcpyAsync(c->d_in, rgb, in_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, rgb_to_ycc_device((const uint8_t *)c->d_in, im, width, height, sampling, n_frames, (uint8_t *)c->d_out, yuv_fs, comps, c->stream));
+    if ((r = grow(c, c->d_in, in_bytes))) return r;
+    if ((r = grow(c, c->d_out, out_bytes))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_in.p, rgb, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, rgb_to_ycc_device(c->d_in.as<const uint8_t>(), im, width, height, sampling, n_frames, c->d_out.as<uint8_t>(), yuv_fs, comps, c->stream));
     for (int f = 0; f < n_frames; f++) // (only the frame's own samples: padding stays the caller's)
         for (int k = 0; k < (grey ? 1 : 3); k++) {
             const size_t at = (size_t)f * yuv_fs + comps[k].plane_offset;
-            HIPCHK(c, hipMemcpy2DAsync(yuv + at, comps[k].stride, (const uint8_t *)c->d_out + at, comps[k].stride, (size_t)(k ? cw : width),
+            HIPCHK(c, hipMemcpy2DAsync(yuv + at, comps[k].stride, c->d_out.as<const uint8_t>() + at, comps[k].stride, (size_t)(k ? cw : width),
                                        (size_t)(k ? ch : height), hipMemcpyDeviceToHost, c->stream));
         }
     HIPCHK(c, hipStreamSynchronize(c->stream));
