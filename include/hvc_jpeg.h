@@ -960,6 +960,50 @@ HVC_API int hvc_jpeg_decode_batch_mixed_scaled_rgb(hvc_ctx *ctx, const uint8_t *
                                                    int *status, const size_t *rgb_offsets, const size_t *rgb_row_strides,
                                                    uint8_t *rgb, size_t rgb_cap, int layout, int where, hvc_batch_stats *stats);
 
+/* ------------------------------------------------------------------------- */
+/* Mixed batches, ENCODING: frames of DIFFERENT sizes, samplings and qualities in one call -- what hvc_jpeg_decode_batch_mixed
+ * [_scaled] hands back (thumbnails, a photo set to recompress, a dataset rewritten at another quality) made into files again.
+ * The forward block stage takes its work decomposition from tables in device memory as the mixed decode does
+ * (k_encode_mixed, csrc/hvc_mixed_encode.hip: one wavefront per 64 blocks of one plane, k_encode's arithmetic per block), so
+ * every coefficient is what hvc_encode_frames gives for that frame alone and every file what hvc_jpeg_encode gives for it.
+ * With HVC_ARITH_HARDCAML as the ENCODE arithmetic (hvc_set_encode_arithmetic) the ctx functions return HVC_E_INVALID_ARG,
+ * outputs untouched.  Not here: the Huffman coder on the GPU (the files are coded by host threads), RGB input, monochrome.
+ *
+ * hvc_jpeg_encoder_mixed_layout (host only, no ctx): per frame hvc_jpeg_encoder_layout(widths[f], heights[f], chromas[f],
+ *   qualities[f]) + hvc_jpeg_encoder_check -> infos[f], status[f] (that frame's own code: a refused frame takes no room and
+ *   stops nobody).  A good frame's padded pixel record (info.pixel_bytes) lies at pixel_offsets[f], bytes, each start
+ *   rounded up to align (0, or a power of two >= 8; 0 = 64); its coefficient record (info.coef_count) at coef_offsets[f],
+ *   int16 elements, each start on 16 bytes.  *pixel_total bytes and *coef_total elements hold all of them.
+ * hvc_encode_frames_mixed: frame f is infos[f].layout / .qtabs; its padded planes are read from pixels + pixel_offsets[f],
+ *   its coefficient record is written at coefs + coef_offsets[f].  infos / offsets: host memory always.  Every coefficient
+ *   plane must start on 16 bytes, every pixel plane and stride on 8 (HVC_E_ALIGNMENT).  HVC_E_INVALID_ARG: a component with
+ *   blocks_w or blocks_h of 0 (hvc_component: the encoding entry points refuse it); HVC_E_RANGE: a table entry of 0 or above
+ *   255 (the model's encoder tables are 8-bit); nothing is written then.  HVC_MEM_DEVICE: one launch, enqueued on ctx's
+ *   stream, returns at once, honours hvc_set_profiling (the pair brackets k_encode_mixed); HVC_MEM_HOST: staged through
+ *   context scratch, the call blocks, and only the coefficient planes are copied back (gaps in `coefs` stay untouched).
+ *   A set without a frame is HVC_OK and needs no memory.
+ * hvc_jpeg_encode_batch_mixed: frames[f] = one raw planar frame as `model encode frame` reads it (tight Y, U, V of
+ *   infos[f].width x .height at its sampling); infos / status as the layout call made them: only frames with status[f] ==
+ *   HVC_OK take part.  hvc_jpeg_encode_batch's pipeline with chunks cut by the bytes of the frames' padded pixel records
+ *   (chunk_bytes 0 = 64 MiB; a frame larger than that is a chunk of its own and the ring grows): host threads pad each frame
+ *   into a pinned ring, upload on the copy stream || k_encode_mixed with one plan per chunk || download of the chunk's
+ *   records, `threads` host threads code each file with its own info (a quarter as many more do the padding).  Honours
+ *   hvc_set_huffman_tables (default, or per-file optimised), hvc_set_restart_interval and hvc_set_host_cpus.  PER-FILE
+ *   results: sizes[f] bytes at jpegs[f] for a good file; caps[f] too small: status[f] = HVC_E_INVALID_ARG and sizes[f] = the
+ *   size it needs; a value without a Huffman code: HVC_E_RANGE for that file alone; a frame that was refused before the
+ *   call keeps its status, jpegs[f] and sizes[f] untouched.  The call's own return value is for what concerns the whole
+ *   call (arguments, memory, HIP, threads).  stats as hvc_jpeg_encode_batch; frames_per_chunk = the largest chunk's count. */
+HVC_API int hvc_jpeg_encoder_mixed_layout(const int *widths, const int *heights, const int *chromas, const int *qualities,
+                                          int n_frames, size_t align, hvc_jpeg_info *infos, int *status,
+                                          size_t *pixel_offsets, size_t *coef_offsets, size_t *pixel_total,
+                                          size_t *coef_total);
+HVC_API int hvc_encode_frames_mixed(hvc_ctx *ctx, const uint8_t *pixels, const size_t *pixel_offsets,
+                                    const hvc_jpeg_info *infos, int n_frames, int16_t *coefs, const size_t *coef_offsets,
+                                    int where);
+HVC_API int hvc_jpeg_encode_batch_mixed(hvc_ctx *ctx, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status,
+                                        int n_frames, int threads, size_t chunk_bytes, uint8_t *const *jpegs,
+                                        const size_t *caps, size_t *sizes, hvc_batch_stats *stats);
+
 /* K5 (no counterpart in the reference): what a benchmark or a pipeline produced, said in
  * 64 bits per record without bringing the records back.  For r < n_records
  *     sums[r] = SUM_i (byte_i + 1) * ((2 i + 1) * 0x9E3779B97F4A7C15)   mod 2^64,  i = byte index in record r

@@ -940,6 +940,34 @@ let jpeg_decode_batch_mixed_scaled_rgb =
     @-> ptr size_t @-> ptr char @-> size_t @-> int @-> int @-> ptr Batch_stats.t @-> returning int)
 ;;
 
+(* mixed batches, encoding: frames of different sizes, samplings and qualities in one call.
+   int hvc_jpeg_encoder_mixed_layout(widths, heights, chromas, qualities, n_frames, align, infos, status, pixel_offsets,
+                                     coef_offsets, pixel_total, coef_total)                                     host only *)
+let jpeg_encoder_mixed_layout =
+  foreign
+    "hvc_jpeg_encoder_mixed_layout"
+    (ptr int @-> ptr int @-> ptr int @-> ptr int @-> int @-> size_t @-> ptr Jpeg_info.t @-> ptr int @-> ptr size_t
+    @-> ptr size_t @-> ptr size_t @-> ptr size_t @-> returning int)
+;;
+
+(* int hvc_encode_frames_mixed(ctx, pixels, pixel_offsets, infos, n_frames, coefs, coef_offsets, where) *)
+let encode_frames_mixed =
+  foreign
+    "hvc_encode_frames_mixed"
+    ~release_runtime_lock:true
+    (ctx @-> ptr char @-> ptr size_t @-> ptr Jpeg_info.t @-> int @-> ptr int16_t @-> ptr size_t @-> int
+    @-> returning int)
+;;
+
+(* int hvc_jpeg_encode_batch_mixed(ctx, frames, infos, status, n_frames, threads, chunk_bytes, jpegs, caps, sizes, stats) *)
+let jpeg_encode_batch_mixed =
+  foreign
+    "hvc_jpeg_encode_batch_mixed"
+    ~release_runtime_lock:true
+    (ctx @-> ptr (ptr char) @-> ptr Jpeg_info.t @-> ptr int @-> int @-> int @-> size_t @-> ptr (ptr char) @-> ptr size_t
+    @-> ptr size_t @-> ptr Batch_stats.t @-> returning int)
+;;
+
 (* int hvc_jpeg_encode_rgb(ctx, rgb, rgb_row_stride, layout, width, height, chroma, quality, out, cap, out_len) *)
 let jpeg_encode_rgb =
   foreign

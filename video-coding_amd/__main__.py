@@ -7,6 +7,10 @@
     python -m video_coding_amd model decode frame IN.jpg OUT.ppm -rgb       the RGB image as a binary PPM (P6)
     python -m video_coding_amd model decode frame IN.jpg OUT -scale 2|4|8   at reduced size: the cropped scaled planes (with -rgb: the PPM)
     python -m video_coding_amd model encode frame IN.ppm WxH OUT.jpg -rgb   from a binary PPM of that size
+    python -m video_coding_amd model encode frames OUT_DIR IN1.yuv WxH IN2.yuv WxH ... [-quality Q] [-chroma C] [-huffman optimised] [-restart-interval N]
+                                                      raw frames of any sizes in ONE mixed batch call (hvc_jpeg_encode_batch_mixed):
+                                                      OUT_DIR/<name>.jpg as `encode frame` writes it; a refused frame is
+                                                      printed with its code and the others are still written
     python -m video_coding_amd model decode frames OUT_DIR IN1.jpg IN2.jpg ... [-restart-markers] [-threads 8] [-rgb] [-scale 2|4|8] [-reader gpu|host]
                                                       files of any sizes, samplings and tables in ONE mixed batch call
                                                       (hvc_jpeg_decode_batch_mixed): OUT_DIR/<name>.yuv as `decode frame` writes it;
@@ -220,6 +224,44 @@ def model_encode_frame(a):
         ctx.close()
     with open(a.bits, "wb") as f:
         f.write(jpg)
+
+
+def model_encode_frames(a):
+    """every frame through one hvc_jpeg_encode_batch_mixed call: OUT_DIR/<name>.jpg as `encode frame` writes it; a frame that
+    is refused gets a line with its code on stderr and the others are still written; the exit status says whether any was"""
+    import os
+    if len(a.inputs) % 2:
+        raise SystemExit("model encode frames: IN.yuv WxH pairs expected")
+    paths = a.inputs[0::2]
+    try:
+        sizes = [size_arg(s) for s in a.inputs[1::2]]
+    except ValueError:
+        raise SystemExit("model encode frames: IN.yuv WxH pairs expected")
+    lay = hvc.jpeg_encoder_mixed_layout([(w, h, a.chroma, a.quality) for w, h in sizes])
+    frames = []
+    for f, (path, (w, h)) in enumerate(zip(paths, sizes)):
+        if lay.status[f]:
+            frames.append(np.zeros(8, dtype=np.uint8))   # (takes no part)
+        else:
+            frames.append(np.concatenate([np.asarray(p, dtype=np.uint8).reshape(-1) for p in yuv.read_frame(path, w, h, a.chroma)]))
+    ctx = hvc.Context(a.device)
+    try:
+        ctx.set_huffman_tables(a.huffman)
+        ctx.set_restart_interval(a.restart_interval)
+        results = ctx.jpeg_encode_batch_mixed(frames, threads=a.threads, layout=lay)
+    finally:
+        ctx.close()
+    os.makedirs(a.out_dir, exist_ok=True)
+    failed = 0
+    for path, (status, jpg, _) in zip(paths, results):
+        if status:
+            failed += 1
+            print("%s: %s" % (path, hvc.HvcError(status)), file=sys.stderr)
+            continue
+        with open(os.path.join(a.out_dir, os.path.splitext(os.path.basename(path))[0] + ".jpg"), "wb") as fh:
+            fh.write(jpg)
+    if failed:
+        raise SystemExit(1)
 
 
 METRICS = {"max-difference": (yuv.max_difference, str), "mean-difference": (yuv.mean_difference, yuv.float_to_string),
@@ -510,8 +552,17 @@ def parser():
                    help="N > 0: a DRI segment and an RSTn marker every N MCUs (hvc_set_restart_interval)")
     p.add_argument("-rgb", action="store_true", help="the input is a binary PPM (P6) of that size (hvc_jpeg_encode_rgb)")
     p.set_defaults(fn=model_encode_frame)
+    p = enc.add_parser("frames", help="raw frames of any sizes in one mixed batch: OUT_DIR/<name>.jpg each")
+    p.add_argument("out_dir")
+    p.add_argument("inputs", nargs="+", metavar="IN.yuv WxH")
+    p.add_argument("-quality", type=int, default=75)
+    p.add_argument("-chroma", type=int, default=420, choices=[420, 422, 444])
+    p.add_argument("-huffman", default="default", choices=["default", "optimised"])
+    p.add_argument("-restart-interval", dest="restart_interval", type=int, default=0)
+    p.add_argument("-threads", type=int, default=8)
+    p.set_defaults(fn=model_encode_frames)
 
-    oyuv = top.add_parser("oyuv").add_subparsers(dest="cmd", required=True)
+    oyuv =top.add_parser("oyuv").add_subparsers(dest="cmd", required=True)
     p = oyuv.add_parser("compare")
     p.add_argument("metric", choices=sorted(METRICS))
     p.add_argument("plane", choices=["y", "u", "v", "yuv"])

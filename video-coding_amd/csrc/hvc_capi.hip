@@ -1430,7 +1430,7 @@ int encode_frames_impl(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const
     hvc::EncodeParams P;
     fill_geometry(P, L, coef_fs, pixel_fs, n_frames);
     for (int i = 0; i < n_qtabs * 64; i++) // fl((1 + 2^-16) / (4t)): see quant1 in hvc_kernels.hip
-        P.qrcp[i] = (float)((1.0 + 1.0 / 65536.0) / (4.0 * (double)qtabs[i]));
+        P.qrcp[i] = hvc::encode_quant_reciprocal(qtabs[i]); // (hvc_mixed_encode_plan.h: k_encode_mixed's tables come from it too)
     // HVC_ARITH_HARDCAML (hvc_set_encode_arithmetic): the RTL encoder twin (hvc_hardcaml.hip) in place of k_encode
     const bool twin = o.arith == HVC_ARITH_HARDCAML;
     hvc::HardcamlEncodeParams H;

@@ -506,3 +506,24 @@ int hvc_jpeg_encode_batch_gpu(hvc_ctx *c, const uint8_t *const *frames, int n_fr
     return encode_batch_impl(c, frames, n_frames, width, height, chroma, quality, threads, frames_per_chunk, jpegs, caps,
                              sizes, stats, true);
 } HVC_ABI_CATCH
+
+// ---------------------------------------------------------------------------
+// Mixed batches, encoding (hvc_capi_mixed_encode.hip, hvc_mixed_encode_plan.cpp)
+
+int hvc_jpeg_encoder_mixed_layout(const int *widths, const int *heights, const int *chromas, const int *qualities, int n_frames,
+                                  size_t align, hvc_jpeg_info *infos, int *status, size_t *pixel_offsets, size_t *coef_offsets,
+                                  size_t *pixel_total, size_t *coef_total) try {
+    return hvc::encoder_mixed_layout(widths, heights, chromas, qualities, n_frames, align, infos, status, pixel_offsets, coef_offsets,
+                                     pixel_total, coef_total);
+} HVC_ABI_CATCH
+
+int hvc_encode_frames_mixed(hvc_ctx *c, const uint8_t *pixels, const size_t *pixel_offsets, const hvc_jpeg_info *infos, int n_frames,
+                            int16_t *coefs, const size_t *coef_offsets, int where) try {
+    return encode_frames_mixed_impl(c, pixels, pixel_offsets, infos, n_frames, coefs, coef_offsets, where);
+} HVC_ABI_CATCH
+
+int hvc_jpeg_encode_batch_mixed(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames,
+                                int threads, size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes,
+                                hvc_batch_stats *stats) try {
+    return encode_batch_mixed_impl(c, frames, infos, status, n_frames, threads, chunk_bytes, jpegs, caps, sizes, stats);
+} HVC_ABI_CATCH

@@ -27,8 +27,10 @@ ImageParts image_parts(const hvc::MixedPlan &plan) {
     return p;
 }
 
+} // namespace
+
 // A plan's image in a device buffer of the context, in stream order: uploaded from the pinned copy unless the device
-// already holds these bytes.
+// already holds these bytes.  (hvc_ctx.h: the mixed encode plans use it too)
 int upload_image(hvc_ctx *c, PlanBuf &b, const std::vector<unsigned char> &img) {
     const size_t total = img.size();
     HIPCHK(c, b.ev.ensure(hipEventDisableTiming));
@@ -48,6 +50,8 @@ int upload_image(hvc_ctx *c, PlanBuf &b, const std::vector<unsigned char> &img) 
     b.len = total;
     return HVC_OK;
 }
+
+namespace {
 
 // the block stage's tables in c->mixed_plan
 int upload_plan(hvc_ctx *c, const hvc::MixedPlan &plan, hvc::MixedParams &P) {

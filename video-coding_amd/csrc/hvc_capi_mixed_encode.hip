@@ -1,0 +1,333 @@
+// hvc_capi_mixed_encode.hip -- ENCODING batches of frames that share neither geometry, sampling nor quality: what stands
+// behind hvc_encode_frames_mixed (the forward block stage over a set of frames, one launch of k_encode_mixed,
+// hvc_mixed_encode.hip) and hvc_jpeg_encode_batch_mixed (raw frames in, JPEG files out); the entry points themselves stand
+// in hvc_capi_files.hip, with hvc_jpeg_encoder_mixed_layout (host only).  The host plan is hvc_mixed_encode_plan.cpp's, its
+// tables go to device memory as the mixed decode plans do (upload_image).
+// The file pipeline is hvc_jpeg_encode_batch's with chunks cut by bytes and a status per file:
+//   host threads: Plane.blit_available into zero-padded planes (pinned ring)       encoder.ml:514-516
+//   copy stream:  hipMemcpyAsync H2D           compute stream: k_encode_mixed (a plan per chunk), D2H of the chunk's records
+//   host threads: write_headers + rle + write_bits + EOI per file, with its own info      encoder.ml:127-193, 371-418
+// Two chunk feeds (hvc_feed.h) hand the chunks over: the padding workers fill pinned pixel slots for the orchestrating
+// thread, the orchestrating thread hands pinned coefficient slots to the coder workers.
+#include "hvc_batch.h"
+#include "hvc_mixed_encode.h"
+
+namespace {
+
+// the plan as one image: planes | tables | map, each part on 16 bytes, in c->mixed_enc_plan
+int upload_encode_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, hvc::MixedEncodeParams &P) {
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t tables_at = up(plan.planes.size() * sizeof(hvc::MixedPlaneK));
+    const size_t map_at = tables_at + up(plan.tables.size() * sizeof(hvc::MixedEncTableK));
+    std::vector<unsigned char> img(map_at + up(plan.map.size() * sizeof(unsigned)), 0);
+    std::memcpy(img.data(), plan.planes.data(), plan.planes.size() * sizeof(hvc::MixedPlaneK));
+    std::memcpy(img.data() + tables_at, plan.tables.data(), plan.tables.size() * sizeof(hvc::MixedEncTableK));
+    std::memcpy(img.data() + map_at, plan.map.data(), plan.map.size() * sizeof(unsigned));
+    const int r = upload_image(c, c->mixed_enc_plan, img);
+    if (r) return r;
+    const unsigned char *d = c->mixed_enc_plan.d.as<const unsigned char>();
+    P.planes = reinterpret_cast<const hvc::MixedPlaneK *>(d);
+    P.tables = reinterpret_cast<const hvc::MixedEncTableK *>(d + tables_at);
+    P.map = reinterpret_cast<const unsigned *>(d + map_at);
+    P.n_units = (unsigned)plan.map.size();
+    return HVC_OK;
+}
+
+// The block stage of a plan on DEVICE memory, enqueued on c->stream
+int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const uint8_t *d_pixels, int16_t *d_coefs, bool profile) {
+    if (plan.map.empty()) return HVC_OK; // no block at all: nothing to launch
+    if (((uintptr_t)d_coefs & 15) || ((uintptr_t)d_pixels & 7)) return HVC_E_ALIGNMENT;
+    hvc::MixedEncodeParams P;
+    std::memset(&P, 0, sizeof P);
+    const int r = upload_encode_plan(c, plan, P);
+    if (r) return r;
+    P.pixels = d_pixels;
+    P.coefs = d_coefs;
+    const int slot = (int)(c->k_calls % HVC_PROF_RING);
+    const hipError_t e = hvc::launch_encode_mixed(P, c->stream, profile ? c->k0[slot] : nullptr, profile ? c->k1[slot] : nullptr);
+    if (e != hipSuccess) return fail_hip(c, e);
+    if (profile) c->k_calls++;
+    return HVC_OK;
+}
+
+// what a frame's records cover: bytes of pixels, elements of coefficients
+void encode_frame_spans(const hvc_jpeg_info &fi, size_t &pixel_span, size_t &coef_span) {
+    pixel_span = coef_span = 0;
+    for (int i = 0; i < fi.n_comp && i < 4; i++) {
+        const hvc_component &k = fi.layout[i];
+        if (k.blocks_w <= 0 || k.blocks_h <= 0) continue;
+        coef_span = std::max(coef_span, k.coef_offset + (size_t)k.blocks_w * k.blocks_h * 64);
+        pixel_span = std::max(pixel_span, k.plane_offset + ((size_t)k.blocks_h * 8 - 1) * k.stride + (size_t)k.blocks_w * 8);
+    }
+}
+
+// Plane.blit_available of a raw planar frame (tight Y, U, V of the info's actual sizes) into the zero-padded planes of `rec`
+void pad_frame(const hvc_jpeg_info &info, const uint8_t *src, uint8_t *rec) {
+    for (int i = 0; i < 3; i++) {
+        const hvc_component &L = info.layout[i];
+        const int sw = info.comp[i].actual_width, sh = info.comp[i].actual_height;
+        const int pw = info.comp[i].decoded_width, ph = info.comp[i].decoded_height;
+        const int bw = sw < pw ? sw : pw, bh = sh < ph ? sh : ph;
+        uint8_t *dst = rec + L.plane_offset;
+        for (int row = 0; row < ph; row++) {
+            uint8_t *d = dst + (size_t)row * L.stride;
+            if (row < bh) {
+                std::memcpy(d, src + (size_t)row * sw, (size_t)bw);
+                std::memset(d + bw, 0, (size_t)(pw - bw)); // Plane.create is zero-filled
+            } else {
+                std::memset(d, 0, (size_t)pw);
+            }
+        }
+        src += (size_t)sw * sh;
+    }
+}
+
+} // namespace
+
+// behind hvc_encode_frames_mixed (hvc_capi_files.hip)
+int encode_frames_mixed_impl(hvc_ctx *c, const uint8_t *pixels, const size_t *pixel_offsets, const hvc_jpeg_info *infos, int n_frames,
+                             int16_t *coefs, const size_t *coef_offsets, int where) {
+    if (!c || n_frames < 0 || (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE)) return HVC_E_INVALID_ARG;
+    if (c->enc_arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (the RTL encoder's arithmetic has no mixed form)
+    if (n_frames == 0) return HVC_OK;
+    if (!infos || !coef_offsets || !pixel_offsets) return HVC_E_INVALID_ARG;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    int r;
+    hvc::MixedEncodePlan plan; // the caller's own offsets: checked for either kind of memory, launched on for device memory
+    if ((r = hvc::mixed_encode_plan_build(infos, coef_offsets, pixel_offsets, nullptr, n_frames, plan))) return r;
+    if (plan.map.empty()) return HVC_OK; // (a set without a block needs no memory)
+    if (!coefs || !pixels) return HVC_E_INVALID_ARG;
+    if (where == HVC_MEM_DEVICE) return encode_mixed_launch_plan(c, plan, pixels, coefs, c->profiling);
+    // host memory: the frames' records one after another in c->d_in / c->d_out, each on 64 bytes; only the coefficient
+    // planes come back (gaps in the caller's buffer stay untouched)
+    std::vector<size_t> d_pix((size_t)n_frames, 0), d_coef((size_t)n_frames, 0), pspan((size_t)n_frames, 0);
+    size_t ptot = 0, ctot = 0;
+    for (int f = 0; f < n_frames; f++) {
+        size_t cs;
+        encode_frame_spans(infos[f], pspan[(size_t)f], cs);
+        d_pix[(size_t)f] = ptot;
+        d_coef[(size_t)f] = ctot;
+        ptot += (pspan[(size_t)f] + 63) & ~(size_t)63;
+        ctot += (cs + 31) & ~(size_t)31;
+    }
+    if ((r = grow(c, c->d_in, ptot))) return r;
+    if ((r = grow(c, c->d_out, ctot * sizeof(int16_t)))) return r;
+    if ((r = hvc::mixed_encode_plan_build(infos, d_coef.data(), d_pix.data(), nullptr, n_frames, plan))) return r;
+    for (int f = 0; f < n_frames; f++)
+        if (pspan[(size_t)f])
+            HIPCHK(c, hipMemcpyAsync(c->d_in.as<uint8_t>() + d_pix[(size_t)f], pixels + pixel_offsets[f], pspan[(size_t)f],
+                                     hipMemcpyHostToDevice, c->stream));
+    if ((r = encode_mixed_launch_plan(c, plan, c->d_in.as<const uint8_t>(), c->d_out.as<int16_t>(), false))) {
+        (void)hipStreamSynchronize(c->stream);
+        return r;
+    }
+    for (int f = 0; f < n_frames; f++)
+        for (int i = 0; i < infos[f].n_comp; i++) {
+            const hvc_component &k = infos[f].layout[i];
+            const size_t n = (size_t)k.blocks_w * k.blocks_h * 64;
+            HIPCHK(c, hipMemcpyAsync(coefs + coef_offsets[f] + k.coef_offset, c->d_out.as<const int16_t>() + d_coef[(size_t)f] + k.coef_offset,
+                                     n * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+        }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+}
+
+// behind hvc_jpeg_encode_batch_mixed (hvc_capi_files.hip)
+int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
+                            size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats) {
+    if (!c || !frames || !infos || !status || !jpegs || !caps || !sizes || n_frames < 0) return HVC_E_INVALID_ARG;
+    if (c->enc_arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_frames == 0) return HVC_OK;
+    if (chunk_bytes == 0) chunk_bytes = (size_t)64 << 20;
+    if (threads < 1) threads = 1;
+    if (threads > 256) threads = 256;
+    constexpr int NB = hvc_ctx::RING;
+
+    // the frames that take part, cut into chunks by the bytes of their padded pixel records; a frame the block stage or the
+    // coder would refuse gets its own status here and is left out
+    struct Chunk {
+        int first = 0, count = 0; // positions in `take`
+        size_t pix_bytes = 0, coef_elems = 0;
+    };
+    std::vector<int> take, chunk_of((size_t)n_frames, -1);
+    std::vector<Chunk> chunks;
+    std::vector<size_t> pix_rel((size_t)n_frames, 0), coef_rel((size_t)n_frames, 0);
+    for (int f = 0; f < n_frames; f++) {
+        if (status[f] != HVC_OK) continue;
+        if (!frames[f] || !jpegs[f]) return HVC_E_INVALID_ARG;
+        const size_t zero = 0;
+        hvc::MixedEncodePlan own;
+        int e = hvc_jpeg_encoder_check(&infos[f]);
+        if (!e) e = hvc::mixed_encode_plan_build(&infos[f], &zero, &zero, nullptr, 1, own);
+        if (!e && (infos[f].pixel_bytes == 0 || infos[f].coef_count == 0)) e = HVC_E_INVALID_ARG;
+        for (int i = 0; i < 3 && !e; i++) { // what the padding workers go by
+            const hvc_jpeg_component &k = infos[f].comp[i];
+            if (k.decoded_width != 8 * infos[f].layout[i].blocks_w || k.decoded_height != 8 * infos[f].layout[i].blocks_h ||
+                k.actual_width < 0 || k.actual_height < 0)
+                e = HVC_E_INVALID_ARG;
+        }
+        if (e) {
+            status[f] = e;
+            continue;
+        }
+        size_t ps, cs;
+        encode_frame_spans(infos[f], ps, cs);
+        if (ps > infos[f].pixel_bytes || cs > infos[f].coef_count) return HVC_E_INVALID_ARG; // (not a record of the layout call)
+        const size_t pb = (infos[f].pixel_bytes + 63) & ~(size_t)63;
+        if (chunks.empty() || (chunks.back().count > 0 && chunks.back().pix_bytes + pb > chunk_bytes)) {
+            chunks.emplace_back();
+            chunks.back().first = (int)take.size();
+        }
+        Chunk &k = chunks.back();
+        pix_rel[(size_t)f] = k.pix_bytes;
+        coef_rel[(size_t)f] = k.coef_elems;
+        chunk_of[(size_t)f] = (int)chunks.size() - 1;
+        k.pix_bytes += pb;
+        k.coef_elems += (infos[f].coef_count + 31) & ~(size_t)31;
+        k.count++;
+        take.push_back(f);
+    }
+    if (take.empty()) return HVC_OK;
+    const int n_chunks = (int)chunks.size(), n_take = (int)take.size();
+    size_t in_bytes = 0, out_bytes = 0;
+    int largest = 0;
+    uint64_t coef_total = 0;
+    for (const Chunk &k : chunks) {
+        in_bytes = std::max(in_bytes, k.pix_bytes);
+        out_bytes = std::max(out_bytes, k.coef_elems * sizeof(int16_t));
+        largest = std::max(largest, k.count);
+        coef_total += k.coef_elems * sizeof(int16_t);
+    }
+
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    HIPCHK(c, c->copy_stream.ensure());
+    for (int i = 0; i < NB; i++) {
+        HIPCHK(c, c->ev_up[i].ensure());
+        HIPCHK(c, c->ev_down[i].ensure());
+        for (int k = 0; k < 3; k++) HIPCHK(c, c->ev_et[i][k].ensure());
+    }
+    int r = ring_ensure(c, enc_rings(c), {in_bytes, out_bytes, in_bytes, out_bytes}); // (a frame larger than chunk_bytes: the ring grows)
+    if (r) return r;
+    const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // each file its own tables (hvc_set_huffman_tables)
+    const int ri = c->restart_interval;                    // DRI + RSTn every ri MCUs (hvc_set_restart_interval)
+
+    std::atomic<long long> pad_ns{0}, ent_ns{0};
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int pad_threads = (threads + 3) / 4; // (padding is a copy: a quarter of the coder's threads keeps ahead of them)
+    if ((r = pool_ready(c, threads, pad_threads))) return r;
+    bool left = false; // the coder feed goes first when the call is left: it ends the padding workers with it
+    hvc::ChunkFeed padf(c->pool, n_chunks, NB);
+    // ring 0: chunk k may be read by the coder workers once release(k) says its records have landed
+    hvc::ChunkFeed codf(c->pool, n_chunks, 0, [&] { if (!left) padf.raise(HVC_E_INTERNAL); });
+    auto ns_since = [](std::chrono::steady_clock::time_point t0) {
+        return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    };
+    auto pad_worker = [&]() {
+        if (!pin_to_ctx_cpus(c)) padf.raise(HVC_E_INVALID_ARG); // hvc_set_host_cpus
+        for (;;) {
+            const int t = padf.claim();
+            if (t >= n_take || padf.error()) return;
+            const int f = take[(size_t)t], k = chunk_of[(size_t)f];
+            if (!padf.wait_slot(k)) return;
+            const auto t0 = std::chrono::steady_clock::now();
+            pad_frame(infos[f], frames[f], c->eh_in[k % NB].as<uint8_t>() + pix_rel[(size_t)f]);
+            pad_ns += ns_since(t0);
+            padf.report(k, 1, HVC_OK);
+        }
+    };
+    auto code_worker = [&]() {
+        if (!pin_to_ctx_cpus(c)) codf.raise(HVC_E_INVALID_ARG);
+        for (;;) {
+            const int t = codf.claim();
+            if (t >= n_take || codf.error()) return;
+            const int f = take[(size_t)t], k = chunk_of[(size_t)f];
+            if (!codf.wait_slot(k)) return;
+            const auto t0 = std::chrono::steady_clock::now();
+            const int16_t *cf = c->eh_out[k % NB].as<const int16_t>() + coef_rel[(size_t)f];
+            const int e = opt ? hvc::entropy_encode_optimised(&infos[f], cf, jpegs[f], caps[f], &sizes[f], ri)
+                              : hvc::entropy_encode_file(&infos[f], nullptr, cf, jpegs[f], caps[f], &sizes[f], ri);
+            ent_ns += ns_since(t0);
+            status[f] = e; // the file's own result: it stops nobody else
+            codf.report(k, 1, HVC_OK);
+        }
+    };
+    r = padf.start(pad_threads, pad_worker);
+    if (!r) r = codf.start(threads, code_worker);
+
+    int rc = r;
+    double h2d_ms = 0, k_ms = 0, d2h_ms = 0;
+    hipStream_t compute = c->stream;
+    std::vector<int> list;
+    // chunk j's records have landed: its times are read, its pinned slot goes to the coder workers
+    auto landed = [&](int j) {
+        const int slot = j % NB;
+        const hipError_t he = wait_event(c->ev_down[slot]);
+        if (he != hipSuccess) return fail_hip(c, he);
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c->ev_et[slot][0], c->ev_up[slot]) == hipSuccess) h2d_ms += ms;
+        if (hipEventElapsedTime(&ms, c->ev_et[slot][1], c->ev_et[slot][2]) == hipSuccess) k_ms += ms;
+        if (hipEventElapsedTime(&ms, c->ev_et[slot][2], c->ev_down[slot]) == hipSuccess) d2h_ms += ms;
+        codf.release(j);
+        return (int)HVC_OK;
+    };
+    try {
+        for (int k = 0; k < n_chunks && rc == HVC_OK; k++) {
+            const Chunk &ch = chunks[(size_t)k];
+            const int slot = k % NB;
+            if ((rc = padf.wait_chunk(k, ch.count))) break;
+            // the pinned coefficient slot is free again once chunk k - NB has been coded (its download and the kernel that
+            // read the device slots are behind it: ev_down[slot] was waited for before that chunk went to the coders)
+            if (k >= NB && (rc = codf.wait_chunk(k - NB, chunks[(size_t)(k - NB)].count))) break;
+            hipError_t he = hipEventRecord(c->ev_et[slot][0], c->copy_stream);
+            if (he == hipSuccess) he = hipMemcpyAsync(c->ed_in[slot].p, c->eh_in[slot].p, ch.pix_bytes, hipMemcpyHostToDevice, c->copy_stream);
+            if (he == hipSuccess) he = hipEventRecord(c->ev_up[slot], c->copy_stream);
+            if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_up[slot], 0);
+            if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][1], compute);
+            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
+            list.assign(take.begin() + ch.first, take.begin() + ch.first + ch.count);
+            hvc::MixedEncodePlan plan;
+            if ((rc = hvc::mixed_encode_plan_build(infos, coef_rel.data(), pix_rel.data(), list.data(), ch.count, plan))) break;
+            if ((rc = encode_mixed_launch_plan(c, plan, c->ed_in[slot].as<const uint8_t>(), c->ed_out[slot].as<int16_t>(), false))) break;
+            he = hipEventRecord(c->ev_et[slot][2], compute);
+            if (he == hipSuccess)
+                he = hipMemcpyAsync(c->eh_out[slot].p, c->ed_out[slot].p, ch.coef_elems * sizeof(int16_t), hipMemcpyDeviceToHost, compute);
+            if (he == hipSuccess) he = hipEventRecord(c->ev_down[slot], compute);
+            // wait for this chunk's upload, then hand the pinned pixel slot to chunk k + NB
+            if (he == hipSuccess) he = wait_event(c->ev_up[slot]);
+            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
+            padf.release(k);
+            if (k > 0 && (rc = landed(k - 1))) break; // (while this chunk's kernel runs)
+        }
+        if (rc == HVC_OK) rc = landed(n_chunks - 1);
+        for (int k = std::max(0, n_chunks - NB); k < n_chunks && rc == HVC_OK; k++) rc = codf.wait_chunk(k, chunks[(size_t)k].count);
+    } catch (...) {
+        rc = hvc::exception_code();
+    }
+    if (rc != HVC_OK) { // both feeds end before either waits for the pool
+        padf.raise(rc);
+        codf.raise(rc);
+    }
+    left = true;
+    rc = padf.finish(rc);
+    rc = codf.finish(rc);
+    {
+        const hipError_t h1 = hipStreamSynchronize(compute), h2 = hipStreamSynchronize(c->copy_stream);
+        if (rc == HVC_OK && (h1 != hipSuccess || h2 != hipSuccess)) rc = fail_hip(c, h1 != hipSuccess ? h1 : h2);
+    }
+    if (stats) {
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+        stats->entropy_ms_sum = (double)ent_ns.load() * 1e-6;
+        stats->host_prep_ms_sum = (double)pad_ns.load() * 1e-6;
+        stats->h2d_ms_sum = h2d_ms;
+        stats->kernel_ms_sum = k_ms;
+        stats->d2h_ms_sum = d2h_ms;
+        stats->chunks = n_chunks;
+        stats->threads = threads;
+        stats->frames_per_chunk = largest;
+        stats->coef_bytes = coef_total; // bytes downloaded
+    }
+    return rc;
+}

@@ -10,6 +10,8 @@
 //   hvc_capi_mixed.hip   batches of frames / files of different geometry and tables (hvc_decode_frames_mixed, hvc_jpeg_decode_batch_mixed,
 //                        their RGB forms: hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed_rgb, and the
 //                        reduced-size forms hvc_decode_frames_mixed_scaled, hvc_jpeg_decode_batch_mixed_scaled, _scaled_rgb)
+//   hvc_capi_mixed_encode.hip  the same in the other direction: raw frames of different geometry, sampling and quality to records
+//                        and files (behind hvc_encode_frames_mixed, hvc_jpeg_encode_batch_mixed)
 //   hvc_capi_mixed_reader.hip  the mixed GPU Huffman reader's driver (hvc_mixed_reader.h) and hvc_jpeg_entropy_decode_gpu_mixed
 //   hvc_capi_async.hip   pinned host memory and the slots of the asynchronous seam (hvc_decode_frames_submit / hvc_wait)
 #ifndef HVC_CTX_H
@@ -42,6 +44,7 @@
 #include "hvc_huff.h"
 #include "hvc_kernels.h"
 #include "hvc_mixed_plan.h"
+#include "hvc_mixed_encode_plan.h"
 #include "hvc_pool.h"
 #include "hvc_scaled_spec.h"
 
@@ -194,6 +197,7 @@ struct hvc_ctx {
     // (k_ycc_to_rgb_mixed): a buffer of its own, so that the colour plan of a chunk never overwrites the block-stage plan of
     // that chunk
     PlanBuf mixed_plan, mixed_rgb_plan;
+    PlanBuf mixed_enc_plan; // hvc_encode_frames_mixed / hvc_jpeg_encode_batch_mixed (hvc_capi_mixed_encode.hip): k_encode_mixed's plan
     // hvc_jpeg_decode_batch_mixed_rgb: the ring of device slots the chunks' decoded planes live in (they never leave the GPU)
     Buf d_pring[RING];
     size_t pring_bytes = 0;
@@ -575,6 +579,15 @@ struct MixedForm {
 int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads, size_t chunk_bytes,
                             const hvc_jpeg_info *infos, int *status, const size_t *pixel_offsets, uint8_t *pixels, size_t pixel_cap,
                             int where, hvc_batch_stats *stats, const MixedForm &form = MixedForm(), bool host_reader_only = false);
+// A plan's image in a device buffer of the context, in stream order on c->stream: uploaded from the pinned copy unless the
+// device already holds these bytes (hvc_capi_mixed.hip; the mixed encode plans of hvc_capi_mixed_encode.hip go the same way)
+int upload_image(hvc_ctx *c, PlanBuf &b, const std::vector<unsigned char> &img);
+// hvc_capi_mixed_encode.hip: frames of different geometry, sampling and quality ENCODED in one call (behind
+// hvc_encode_frames_mixed and hvc_jpeg_encode_batch_mixed in hvc_capi_files.hip)
+int encode_frames_mixed_impl(hvc_ctx *c, const uint8_t *pixels, const size_t *pixel_offsets, const hvc_jpeg_info *infos, int n_frames,
+                             int16_t *coefs, const size_t *coef_offsets, int where);
+int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
+                            size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats);
 // hvc_capi_mixed_reader.hip: the mixed GPU Huffman reader over one chunk on the calling thread (behind hvc_jpeg_entropy_decode_gpu_mixed
 // in hvc_capi_jpeg.hip)
 int entropy_decode_gpu_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, const hvc_jpeg_info *infos,

@@ -43,6 +43,7 @@ SYMBOLS = [
     "hvc_jpeg_mixed_rgb_layout", "hvc_yuv_to_rgb_mixed", "hvc_decode_frames_mixed_rgb", "hvc_jpeg_decode_batch_mixed_rgb",
     "hvc_jpeg_mixed_scaled_layout", "hvc_decode_frames_mixed_scaled", "hvc_jpeg_decode_batch_mixed_scaled",
     "hvc_jpeg_mixed_scaled_rgb_layout", "hvc_jpeg_decode_batch_mixed_scaled_rgb",
+    "hvc_jpeg_encoder_mixed_layout", "hvc_encode_frames_mixed", "hvc_jpeg_encode_batch_mixed",
 ]
 HVC_RGB = {"interleaved": 0, "planar": 1}  # enum hvc_rgb_layout: [H, W, 3] / [3, H, W]
 HVC_YUV_400 = 400   # luma only, beside 420 / 422 / 444
@@ -285,6 +286,11 @@ def lib():
         L.hvc_decode_frames_mixed_rgb.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), C.POINTER(sz), i, i]
         L.hvc_jpeg_decode_batch_mixed_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, ip, C.POINTER(i), C.POINTER(sz),
                                                       C.POINTER(sz), vp, sz, i, i, C.POINTER(BatchStats)]
+        L.hvc_jpeg_encoder_mixed_layout.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, sz, ip, C.POINTER(i),
+                                                    C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+        L.hvc_encode_frames_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), i]
+        L.hvc_jpeg_encode_batch_mixed.argtypes = [vp, C.POINTER(vp), ip, C.POINTER(i), i, i, sz, C.POINTER(vp), C.POINTER(sz),
+                                                  C.POINTER(sz), C.POINTER(BatchStats)]
         L.hvc_checksum_records.argtypes = [vp, vp, sz, sz, i, vp, i]
         L.hvc_set_host_cpus.argtypes = [vp, C.c_char_p]
         L.hvc_get_host_cpus.argtypes = [vp, C.c_char_p, sz, C.POINTER(i)]
@@ -778,6 +784,34 @@ def jpeg_encoder_layout(width, height, chroma, quality):
     info = JpegInfo()
     _chk(lib().hvc_jpeg_encoder_layout(width, height, chroma, quality, C.byref(info)), "hvc_jpeg_encoder_layout")
     return info
+
+
+class EncoderMixedLayout:
+    """what hvc_jpeg_encoder_mixed_layout makes of a list of (width, height, chroma, quality): infos (ctypes array of JpegInfo),
+    status (per frame: what jpeg_encoder_layout + hvc_jpeg_encoder_check answer), pixel_offsets (bytes) and coef_offsets (int16
+    elements) of the good frames' records, pixel_total and coef_total"""
+
+    def __init__(self, frames, align=0):
+        n = len(frames)
+        m = max(n, 1)
+        col = lambda k: (C.c_int * m)(*[int(f[k]) for f in frames])
+        self.n = n
+        self.infos = (JpegInfo * m)()
+        self.status = (C.c_int * m)()
+        self.pixel_offsets = (C.c_size_t * m)()
+        self.coef_offsets = (C.c_size_t * m)()
+        pt, ct = C.c_size_t(), C.c_size_t()
+        _chk(lib().hvc_jpeg_encoder_mixed_layout(col(0), col(1), col(2), col(3), n, align, self.infos, self.status, self.pixel_offsets,
+                                                 self.coef_offsets, C.byref(pt), C.byref(ct)), "hvc_jpeg_encoder_mixed_layout")
+        self.pixel_total, self.coef_total = pt.value, ct.value
+
+    def __len__(self):
+        return self.n
+
+
+def jpeg_encoder_mixed_layout(frames, align=0):
+    """frames: (width, height, chroma, quality) each -> EncoderMixedLayout"""
+    return EncoderMixedLayout(frames, align)
 
 
 def encoder_pixel_record(info, y, u, v, width, height, chroma):
@@ -1645,7 +1679,56 @@ class Context:
              "hvc_jpeg_encode_batch_gpu" if gpu_entropy else "hvc_jpeg_encode_batch")
         return [outs[f][:sizes[f]].tobytes() for f in range(n)], st
 
+    def jpeg_encode_batch_mixed(self, frames, specs=None, threads=8, chunk_bytes=0, layout=None, caps=None, outs=None):
+        """hvc_jpeg_encode_batch_mixed: raw planar frames (bytes / uint8 arrays, tight Y, U, V) of any sizes, samplings and
+        qualities -> files, in one call.  specs: (width, height, chroma, quality) per frame, or layout: an EncoderMixedLayout
+        made before.  Returns one (status, jpeg bytes or None, size) per frame: status = the frame's own hvc_status (0 = a file),
+        size = sizes[f] as the call left it (the size needed where caps[f] was too small).  caps / outs (optional): the
+        capacity and the uint8 output array of every frame (default: made here, large enough).  The call's hvc_batch_stats:
+        self.last_batch_stats."""
+        lay = layout if layout is not None else EncoderMixedLayout(specs)
+        n = len(lay)
+        m = max(n, 1)
+        arrs = [np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray)) else
+                np.ascontiguousarray(f, dtype=np.uint8).reshape(-1) for f in frames]
+        assert len(arrs) == n
+        for f, a in enumerate(arrs):
+            if lay.status[f] == 0:
+                k = lay.infos[f].comp
+                need = sum(k[i].actual_width * k[i].actual_height for i in range(3))
+                if a.size < need:
+                    raise ValueError("frame %d shorter than %d bytes" % (f, need))
+        if outs is None:
+            ri = self.restart_interval
+            outs = [np.empty(8, dtype=np.uint8) if lay.status[f] else
+                    np.empty(4 * lay.infos[f].width * lay.infos[f].height + 65536 + restart_slack(lay.infos[f], ri), dtype=np.uint8)
+                    for f in range(n)]
+        if caps is None:
+            caps = [o.size for o in outs]
+        fp = (C.c_void_p * m)(*[a.ctypes.data for a in arrs])
+        op = (C.c_void_p * m)(*[o.ctypes.data for o in outs])
+        cp = (C.c_size_t * m)(*[int(x) for x in caps])
+        sizes = (C.c_size_t * m)()
+        status = (C.c_int * m)(*lay.status)
+        st = BatchStats()
+        _chk(lib().hvc_jpeg_encode_batch_mixed(self._h, fp, lay.infos, status, n, threads, chunk_bytes, op, cp, sizes, C.byref(st)),
+             "hvc_jpeg_encode_batch_mixed")
+        self.last_batch_stats = st
+        return [(status[f], outs[f][:sizes[f]].tobytes() if status[f] == 0 else None, sizes[f]) for f in range(n)]
+
     # -- encode -------------------------------------------------------------
+    def encode_frames_mixed(self, pixels, pixel_offsets, infos, coefs, coef_offsets):
+        """hvc_encode_frames_mixed: frame f = infos[f] (JpegInfo: layout and tables), its padded pixel record at
+        pixels[pixel_offsets[f]:] (bytes), its coefficient record written at coefs[coef_offsets[f]:] (int16 elements).
+        pixels / coefs: numpy (host) or torch cuda tensors, both in the same memory space."""
+        pa, w1 = _addr(pixels)
+        ca, w2 = _addr(coefs)
+        assert w1 == w2, "pixels and coefs must live in the same memory space"
+        n = len(infos)
+        arr = infos if isinstance(infos, C.Array) else (JpegInfo * max(n, 1))(*infos)
+        _chk(lib().hvc_encode_frames_mixed(self._h, pa, _size_array(pixel_offsets, n), arr, n, ca, _size_array(coef_offsets, n), w1),
+             "hvc_encode_frames_mixed")
+
     def fdct_quant(self, plane, qtab, blocks_w, blocks_h, n_planes, coefs, stride=None, plane_stride=0,
                    coef_plane_stride=0):
         pa, w1 = _addr(plane)
