@@ -4,7 +4,8 @@
 //                        encode_frames_impl behind the entry points; the staging steps they share) and its divergence calls
 //   hvc_capi_jpeg.hip    files: one at a time (hvc_jpeg_decode, _yuv444, _rgb on one skeleton; _scaled, _scaled_rgb; hvc_jpeg_encode,
 //                        _encode_rgb) and the batch pipeline with the host reader (hvc_jpeg_decode_batch, _yuv444, _scaled, _rgb)
-//   hvc_capi_reader.hip  the GPU Huffman reader's entry point and the batch pipeline built on it
+//   hvc_capi_reader.hip  the GPU Huffman reader's entry point and the batch pipeline built on it (its per-chunk driver:
+//                        hvc_uniform_reader.h; what both lay out on the host: hvc_hdec_plan.h)
 //   hvc_capi_files.hip   the GPU Huffman coder's entry point and the batch pipelines that write files
 //   hvc_rgb.hip          the RGB colour pass (kernels and launches; its entry points live with their families in the files above)
 //   hvc_capi_mixed.hip   batches of frames / files of different geometry and tables (hvc_decode_frames_mixed, hvc_jpeg_decode_batch_mixed,
