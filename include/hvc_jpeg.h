@@ -967,7 +967,8 @@ HVC_API int hvc_jpeg_decode_batch_mixed_scaled_rgb(hvc_ctx *ctx, const uint8_t *
  * (k_encode_mixed, csrc/hvc_mixed_encode.hip: one wavefront per 64 blocks of one plane, k_encode's arithmetic per block), so
  * every coefficient is what hvc_encode_frames gives for that frame alone and every file what hvc_jpeg_encode gives for it.
  * With HVC_ARITH_HARDCAML as the ENCODE arithmetic (hvc_set_encode_arithmetic) the ctx functions return HVC_E_INVALID_ARG,
- * outputs untouched.  Not here: the Huffman coder on the GPU (the files are coded by host threads), RGB input, monochrome.
+ * outputs untouched.  Here the files are coded by host threads (the Huffman coder on the GPU: the next section).  Not here:
+ * RGB input, monochrome.
  *
  * hvc_jpeg_encoder_mixed_layout (host only, no ctx): per frame hvc_jpeg_encoder_layout(widths[f], heights[f], chromas[f],
  *   qualities[f]) + hvc_jpeg_encoder_check -> infos[f], status[f] (that frame's own code: a refused frame takes no room and
@@ -1003,6 +1004,46 @@ HVC_API int hvc_encode_frames_mixed(hvc_ctx *ctx, const uint8_t *pixels, const s
 HVC_API int hvc_jpeg_encode_batch_mixed(hvc_ctx *ctx, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status,
                                         int n_frames, int threads, size_t chunk_bytes, uint8_t *const *jpegs,
                                         const size_t *caps, size_t *sizes, hvc_batch_stats *stats);
+
+/* ------------------------------------------------------------------------- */
+/* Mixed batches, ENCODING, with the Huffman coder on the GPU: the passes of hvc_huffman_encode_frames with the geometry of
+ * every work unit taken from device memory (csrc/hvc_huff_mixed.hip: one wavefront per 64 blocks of one plane of one file, a
+ * status word per file), so frames of different sizes and samplings are coded in one chain of launches.  Not in this coder:
+ * restart intervals (the batch call hands such calls to the host coder), RGB input, monochrome, the Hardcaml arithmetic.
+ *
+ * hvc_huffman_encode_frames_mixed: the coder alone.  Frame f is infos[f]; its coefficient record (as hvc_encode_frames_mixed
+ *   writes it) is read from coefs + coef_offsets[f], which must lie on 16 bytes (HVC_E_ALIGNMENT for the call: an offset that
+ *   is no multiple of 8 elements; HVC_MEM_DEVICE: coefs off 16 bytes, offsets off 8).  tables = HVC_HUFF_DEFAULT or
+ *   HVC_HUFF_OPTIMISED (anything else: HVC_E_INVALID_ARG).  Frame f's entropy-coded segment -- the bytes between the header
+ *   and EOI of hvc_jpeg_entropy_encode / hvc_jpeg_entropy_encode_tables for that frame -- is out[offsets[f] .. offsets[f + 1]);
+ *   offsets has n_frames + 1 entries, the segments lie back to back.  status[f] is the frame's OWN code, and a frame that is
+ *   refused or flagged has an empty segment and stops nobody: hvc_jpeg_encoder_check's refusal (n_comp != 3 among them), a
+ *   component without a block or a grid without an MCU (HVC_E_INVALID_ARG), more than 2^32 bits (HVC_E_TOO_LARGE), under
+ *   HVC_HUFF_OPTIMISED all components on one table set (HVC_E_INVALID_ARG, as hvc_huffman_optimal_tables), a value without a
+ *   code -- a DC difference beyond 11 bits, an AC value beyond 10 -- HVC_E_RANGE.  With HVC_HUFF_OPTIMISED specs (n_frames x 4:
+ *   DC0, DC1, AC0, AC1) receives each good frame's tables, equal to hvc_huffman_optimal_tables'; otherwise specs may be NULL.
+ *   out_cap smaller than the segments: HVC_E_INVALID_ARG for the call, `out` untouched.  coefs, out and offsets live where
+ *   `where` says; infos, coef_offsets, status and specs are host memory always.  The call blocks.  More than 65535 good frames:
+ *   HVC_E_TOO_LARGE.  A set without a frame is HVC_OK and needs no memory.
+ * hvc_jpeg_encode_batch_mixed_gpu: hvc_jpeg_encode_batch_mixed, argument for argument, with that coder behind k_encode_mixed:
+ *   the same files byte for byte, the same status[f] and sizes[f] (caps[f] too small: HVC_E_INVALID_ARG, sizes[f] = the size
+ *   needed, jpegs[f] untouched).  Chunks are cut as there, and hold at most 65535 files; a chunk's records stay on the device,
+ *   the coder writes its packed segments into a device slot of the size of its records, and only the offsets, the status
+ *   words, the specs (optimised tables) and exactly the segments come down (stats->coef_bytes counts the segment bytes);
+ *   `threads` host threads put header + segment + EOI together.  Honours hvc_set_huffman_tables and hvc_set_host_cpus.  Files
+ *   the GPU path does not finish -- flagged by the length pass, past the segment slot, refused by the coder's plan, and EVERY
+ *   file when hvc_set_restart_interval is non-zero -- are coded by the host coder in one pass behind the GPU chunks; which
+ *   coder ran never changes a byte, a status or a size.  Measured against the host coder on a seeded set of 4096 frames: 102 ms
+ *   against 202 ms (default tables), 100 ms against 247 ms (optimised tables): profiles/mixed_coder_rocprofv3.txt:54-58.
+ * hvc_last_mixed_coder_files: how many files of the last hvc_jpeg_encode_batch_mixed_gpu call the GPU coder finished and how
+ *   many went to the host coder (either pointer may be NULL). */
+HVC_API int hvc_huffman_encode_frames_mixed(hvc_ctx *ctx, const hvc_jpeg_info *infos, const int16_t *coefs,
+                                            const size_t *coef_offsets, int n_frames, int tables, uint8_t *out, size_t out_cap,
+                                            uint64_t *offsets, int *status, hvc_huff_spec *specs, int where);
+HVC_API int hvc_jpeg_encode_batch_mixed_gpu(hvc_ctx *ctx, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status,
+                                            int n_frames, int threads, size_t chunk_bytes, uint8_t *const *jpegs,
+                                            const size_t *caps, size_t *sizes, hvc_batch_stats *stats);
+HVC_API int hvc_last_mixed_coder_files(const hvc_ctx *ctx, uint64_t *gpu_files, uint64_t *host_files);
 
 /* K5 (no counterpart in the reference): what a benchmark or a pipeline produced, said in
  * 64 bits per record without bringing the records back.  For r < n_records

@@ -968,6 +968,31 @@ let jpeg_encode_batch_mixed =
     @-> ptr size_t @-> ptr Batch_stats.t @-> returning int)
 ;;
 
+(* mixed batches, encoding, with the Huffman coder on the GPU.
+   int hvc_huffman_encode_frames_mixed(ctx, infos, coefs, coef_offsets, n_frames, tables, out, out_cap, offsets, status,
+                                       specs, where): the coder alone, a status and a segment per frame *)
+let huffman_encode_frames_mixed =
+  foreign
+    "hvc_huffman_encode_frames_mixed"
+    ~release_runtime_lock:true
+    (ctx @-> ptr Jpeg_info.t @-> ptr int16_t @-> ptr size_t @-> int @-> int @-> ptr char @-> size_t @-> ptr uint64_t
+    @-> ptr int @-> ptr Huff_spec.t @-> int @-> returning int)
+;;
+
+(* int hvc_jpeg_encode_batch_mixed_gpu(ctx, frames, infos, status, n_frames, threads, chunk_bytes, jpegs, caps, sizes, stats) *)
+let jpeg_encode_batch_mixed_gpu =
+  foreign
+    "hvc_jpeg_encode_batch_mixed_gpu"
+    ~release_runtime_lock:true
+    (ctx @-> ptr (ptr char) @-> ptr Jpeg_info.t @-> ptr int @-> int @-> int @-> size_t @-> ptr (ptr char) @-> ptr size_t
+    @-> ptr size_t @-> ptr Batch_stats.t @-> returning int)
+;;
+
+(* int hvc_last_mixed_coder_files(ctx, gpu_files, host_files) *)
+let last_mixed_coder_files =
+  foreign "hvc_last_mixed_coder_files" (ctx @-> ptr uint64_t @-> ptr uint64_t @-> returning int)
+;;
+
 (* int hvc_jpeg_encode_rgb(ctx, rgb, rgb_row_stride, layout, width, height, chroma, quality, out, cap, out_len) *)
 let jpeg_encode_rgb =
   foreign

@@ -7,8 +7,8 @@
     python -m video_coding_amd model decode frame IN.jpg OUT.ppm -rgb       the RGB image as a binary PPM (P6)
     python -m video_coding_amd model decode frame IN.jpg OUT -scale 2|4|8   at reduced size: the cropped scaled planes (with -rgb: the PPM)
     python -m video_coding_amd model encode frame IN.ppm WxH OUT.jpg -rgb   from a binary PPM of that size
-    python -m video_coding_amd model encode frames OUT_DIR IN1.yuv WxH IN2.yuv WxH ... [-quality Q] [-chroma C] [-huffman optimised] [-restart-interval N]
-                                                      raw frames of any sizes in ONE mixed batch call (hvc_jpeg_encode_batch_mixed):
+    python -m video_coding_amd model encode frames OUT_DIR IN1.yuv WxH IN2.yuv WxH ... [-quality Q] [-chroma C] [-huffman optimised] [-restart-interval N] [-coder gpu|host]
+                                                      raw frames of any sizes in ONE mixed batch call (hvc_jpeg_encode_batch_mixed[_gpu]):
                                                       OUT_DIR/<name>.jpg as `encode frame` writes it; a refused frame is
                                                       printed with its code and the others are still written
     python -m video_coding_amd model decode frames OUT_DIR IN1.jpg IN2.jpg ... [-restart-markers] [-threads 8] [-rgb] [-scale 2|4|8] [-reader gpu|host]
@@ -248,7 +248,7 @@ def model_encode_frames(a):
     try:
         ctx.set_huffman_tables(a.huffman)
         ctx.set_restart_interval(a.restart_interval)
-        results = ctx.jpeg_encode_batch_mixed(frames, threads=a.threads, layout=lay)
+        results = ctx.jpeg_encode_batch_mixed(frames, threads=a.threads, layout=lay, coder=a.coder)
     finally:
         ctx.close()
     os.makedirs(a.out_dir, exist_ok=True)
@@ -560,6 +560,8 @@ def parser():
     p.add_argument("-huffman", default="default", choices=["default", "optimised"])
     p.add_argument("-restart-interval", dest="restart_interval", type=int, default=0)
     p.add_argument("-threads", type=int, default=8)
+    p.add_argument("-coder", default="host", choices=["gpu", "host"],
+                   help="who Huffman-codes the files: host threads, or the mixed GPU coder (hvc_jpeg_encode_batch_mixed_gpu); same bytes")
     p.set_defaults(fn=model_encode_frames)
 
     oyuv =top.add_parser("oyuv").add_subparsers(dest="cmd", required=True)

@@ -7,7 +7,7 @@
 
 // the default code tables on the device, once per context (hvc_huff.hip reads them through HuffParams::tables).  The
 // context holds them only once the copy has succeeded: a failed upload is tried again by the next call.
-static int upload_enc_tables(hvc_ctx *c) {
+int upload_enc_tables(hvc_ctx *c) {
     if (c->hd_tables) return HVC_OK;
     uint32_t t[2][16 + 256];
     hvc::default_enc_tables(t);
@@ -526,4 +526,24 @@ int hvc_jpeg_encode_batch_mixed(hvc_ctx *c, const uint8_t *const *frames, const 
                                 int threads, size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes,
                                 hvc_batch_stats *stats) try {
     return encode_batch_mixed_impl(c, frames, infos, status, n_frames, threads, chunk_bytes, jpegs, caps, sizes, stats);
+} HVC_ABI_CATCH
+
+// the same with the mixed GPU Huffman coder (hvc_capi_mixed_coder.hip, hvc_huff_mixed.hip)
+int hvc_huffman_encode_frames_mixed(hvc_ctx *c, const hvc_jpeg_info *infos, const int16_t *coefs, const size_t *coef_offsets, int n_frames,
+                                    int tables, uint8_t *out, size_t out_cap, uint64_t *offsets, int *status, hvc_huff_spec *specs,
+                                    int where) try {
+    return huffman_encode_frames_mixed_impl(c, infos, coefs, coef_offsets, n_frames, tables, out, out_cap, offsets, status, specs, where);
+} HVC_ABI_CATCH
+
+int hvc_jpeg_encode_batch_mixed_gpu(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames,
+                                    int threads, size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes,
+                                    hvc_batch_stats *stats) try {
+    return encode_batch_mixed_gpu_impl(c, frames, infos, status, n_frames, threads, chunk_bytes, jpegs, caps, sizes, stats);
+} HVC_ABI_CATCH
+
+int hvc_last_mixed_coder_files(const hvc_ctx *c, uint64_t *gpu_files, uint64_t *host_files) try {
+    if (!c) return HVC_E_INVALID_ARG;
+    if (gpu_files) *gpu_files = c->mixed_coder_gpu_files;
+    if (host_files) *host_files = c->mixed_coder_host_files;
+    return HVC_OK;
 } HVC_ABI_CATCH

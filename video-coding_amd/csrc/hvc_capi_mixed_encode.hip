@@ -33,7 +33,10 @@ int upload_encode_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, hvc::MixedE
     return HVC_OK;
 }
 
-// The block stage of a plan on DEVICE memory, enqueued on c->stream
+} // namespace
+
+// The block stage of a plan on DEVICE memory, enqueued on c->stream (also the first stage of the pipeline with the GPU coder,
+// hvc_capi_mixed_coder.hip, as pad_frame and encode_frame_spans below)
 int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const uint8_t *d_pixels, int16_t *d_coefs, bool profile) {
     if (plan.map.empty()) return HVC_OK; // no block at all: nothing to launch
     if (((uintptr_t)d_coefs & 15) || ((uintptr_t)d_pixels & 7)) return HVC_E_ALIGNMENT;
@@ -81,8 +84,6 @@ void pad_frame(const hvc_jpeg_info &info, const uint8_t *src, uint8_t *rec) {
         src += (size_t)sw * sh;
     }
 }
-
-} // namespace
 
 // behind hvc_encode_frames_mixed (hvc_capi_files.hip)
 int encode_frames_mixed_impl(hvc_ctx *c, const uint8_t *pixels, const size_t *pixel_offsets, const hvc_jpeg_info *infos, int n_frames,

@@ -13,6 +13,8 @@
 //                        reduced-size forms hvc_decode_frames_mixed_scaled, hvc_jpeg_decode_batch_mixed_scaled, _scaled_rgb)
 //   hvc_capi_mixed_encode.hip  the same in the other direction: raw frames of different geometry, sampling and quality to records
 //                        and files (behind hvc_encode_frames_mixed, hvc_jpeg_encode_batch_mixed)
+//   hvc_capi_mixed_coder.hip   the mixed GPU Huffman coder alone and the file pipeline built on it (behind
+//                        hvc_huffman_encode_frames_mixed, hvc_jpeg_encode_batch_mixed_gpu)
 //   hvc_capi_mixed_reader.hip  the mixed GPU Huffman reader's driver (hvc_mixed_reader.h) and hvc_jpeg_entropy_decode_gpu_mixed
 //   hvc_capi_async.hip   pinned host memory and the slots of the asynchronous seam (hvc_decode_frames_submit / hvc_wait)
 #ifndef HVC_CTX_H
@@ -199,6 +201,8 @@ struct hvc_ctx {
     // that chunk
     PlanBuf mixed_plan, mixed_rgb_plan;
     PlanBuf mixed_enc_plan; // hvc_encode_frames_mixed / hvc_jpeg_encode_batch_mixed (hvc_capi_mixed_encode.hip): k_encode_mixed's plan
+    PlanBuf mixed_huff_plan; // hvc_huffman_encode_frames_mixed / hvc_jpeg_encode_batch_mixed_gpu (hvc_capi_mixed_coder.hip): the mixed coder's plan
+    unsigned long long mixed_coder_gpu_files = 0, mixed_coder_host_files = 0; // hvc_last_mixed_coder_files
     // hvc_jpeg_decode_batch_mixed_rgb: the ring of device slots the chunks' decoded planes live in (they never leave the GPU)
     Buf d_pring[RING];
     size_t pring_bytes = 0;
@@ -589,6 +593,17 @@ int encode_frames_mixed_impl(hvc_ctx *c, const uint8_t *pixels, const size_t *pi
                              int16_t *coefs, const size_t *coef_offsets, int where);
 int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
                             size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats);
+// hvc_capi_mixed_encode.hip, for the pipeline with the GPU coder: k_encode_mixed over a plan on device memory, enqueued on
+// c->stream; Plane.blit_available of a raw planar frame into its padded record; what a frame's records cover
+int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const uint8_t *d_pixels, int16_t *d_coefs, bool profile);
+void pad_frame(const hvc_jpeg_info &info, const uint8_t *src, uint8_t *rec);
+void encode_frame_spans(const hvc_jpeg_info &fi, size_t &pixel_span, size_t &coef_span);
+// hvc_capi_mixed_coder.hip: the mixed GPU Huffman coder alone and behind the block stage (behind
+// hvc_huffman_encode_frames_mixed and hvc_jpeg_encode_batch_mixed_gpu in hvc_capi_files.hip)
+int huffman_encode_frames_mixed_impl(hvc_ctx *c, const hvc_jpeg_info *infos, const int16_t *coefs, const size_t *coef_offsets, int n_frames,
+                                     int tables, uint8_t *out, size_t out_cap, uint64_t *offsets, int *status, hvc_huff_spec *specs, int where);
+int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
+                                size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats);
 // hvc_capi_mixed_reader.hip: the mixed GPU Huffman reader over one chunk on the calling thread (behind hvc_jpeg_entropy_decode_gpu_mixed
 // in hvc_capi_jpeg.hip)
 int entropy_decode_gpu_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, const hvc_jpeg_info *infos,
@@ -622,6 +637,8 @@ int rgb_check_args(const hvc_ctx *c, int sampling, int width, int height, int n_
                    size_t rgb_frame_stride, RgbImage &im, bool &nothing);
 hipError_t rgb_download(const uint8_t *d_rgb, uint8_t *h_rgb, const RgbImage &im, int n_frames, hipStream_t s); // only the bytes written
 
+// hvc_capi_files.hip: the default code tables in c->hd_tables (uploaded by the first call)
+int upload_enc_tables(hvc_ctx *c);
 // hvc_capi_files.hip: geometry + scratch + tables of one GPU Huffman coder call (hvc_huff.hip)
 int huffman_prepare(hvc_ctx *c, const hvc_jpeg_info *info, const int16_t *d_coefs, size_t coef_fs, int n_frames, uint8_t *d_out,
                     size_t out_cap, unsigned long long *d_offsets, hvc::HuffParams &P, bool optimised = false, int restart = 0);

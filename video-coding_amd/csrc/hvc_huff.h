@@ -55,6 +55,8 @@ constexpr size_t HUFF_TABLE_WORDS = 2 * (16 + 256); // one frame's two table set
 // P.hist != nullptr: the frames' own tables first (k_huff_hist, k_huff_build), then the coder's passes with them.
 // P.restart > 0: the *_rst instantiations of the passes, plus k_ivl_bytes and one more scan (hvc_huff.hip)
 hipError_t launch_huffman_encode(const HuffParams &P, hipStream_t s);
+// k_huff_build over P.n_frames (frame, table) rows of P.hist -> P.opt_tables, P.specs; nothing else of P is read
+hipError_t launch_huffman_build(const HuffParams &P, hipStream_t s);
 
 // hvc_entropy.cpp
 void default_enc_tables(uint32_t (*out)[16 + 256]);

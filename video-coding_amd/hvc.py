@@ -44,6 +44,7 @@ SYMBOLS = [
     "hvc_jpeg_mixed_scaled_layout", "hvc_decode_frames_mixed_scaled", "hvc_jpeg_decode_batch_mixed_scaled",
     "hvc_jpeg_mixed_scaled_rgb_layout", "hvc_jpeg_decode_batch_mixed_scaled_rgb",
     "hvc_jpeg_encoder_mixed_layout", "hvc_encode_frames_mixed", "hvc_jpeg_encode_batch_mixed",
+    "hvc_huffman_encode_frames_mixed", "hvc_jpeg_encode_batch_mixed_gpu", "hvc_last_mixed_coder_files",
 ]
 HVC_RGB = {"interleaved": 0, "planar": 1}  # enum hvc_rgb_layout: [H, W, 3] / [3, H, W]
 HVC_YUV_400 = 400   # luma only, beside 420 / 422 / 444
@@ -291,6 +292,9 @@ def lib():
         L.hvc_encode_frames_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), i]
         L.hvc_jpeg_encode_batch_mixed.argtypes = [vp, C.POINTER(vp), ip, C.POINTER(i), i, i, sz, C.POINTER(vp), C.POINTER(sz),
                                                   C.POINTER(sz), C.POINTER(BatchStats)]
+        L.hvc_huffman_encode_frames_mixed.argtypes = [vp, ip, vp, C.POINTER(sz), i, i, vp, sz, vp, C.POINTER(i), hs, i]
+        L.hvc_jpeg_encode_batch_mixed_gpu.argtypes = L.hvc_jpeg_encode_batch_mixed.argtypes
+        L.hvc_last_mixed_coder_files.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.hvc_checksum_records.argtypes = [vp, vp, sz, sz, i, vp, i]
         L.hvc_set_host_cpus.argtypes = [vp, C.c_char_p]
         L.hvc_get_host_cpus.argtypes = [vp, C.c_char_p, sz, C.POINTER(i)]
@@ -1679,8 +1683,57 @@ class Context:
              "hvc_jpeg_encode_batch_gpu" if gpu_entropy else "hvc_jpeg_encode_batch")
         return [outs[f][:sizes[f]].tobytes() for f in range(n)], st
 
-    def jpeg_encode_batch_mixed(self, frames, specs=None, threads=8, chunk_bytes=0, layout=None, caps=None, outs=None):
-        """hvc_jpeg_encode_batch_mixed: raw planar frames (bytes / uint8 arrays, tight Y, U, V) of any sizes, samplings and
+    def jpeg_encode_batch_mixed_gpu(self, frames, specs=None, threads=8, chunk_bytes=0, layout=None, caps=None, outs=None):
+        """hvc_jpeg_encode_batch_mixed_gpu: jpeg_encode_batch_mixed with the Huffman coder on the GPU too (the mixed coder,
+        csrc/hvc_huff_mixed.hip): the same arguments, the same result tuples.  last_mixed_coder_files() says who coded what."""
+        return self.jpeg_encode_batch_mixed(frames, specs, threads, chunk_bytes, layout, caps, outs, coder="gpu")
+
+    def last_mixed_coder_files(self):
+        """(gpu_files, host_files) of the last jpeg_encode_batch_mixed_gpu call: the files each coder wrote"""
+        g, h = C.c_uint64(0), C.c_uint64(0)
+        _chk(lib().hvc_last_mixed_coder_files(self._h, C.byref(g), C.byref(h)), "hvc_last_mixed_coder_files")
+        return g.value, h.value
+
+    def huffman_encode_frames_mixed(self, infos, coefs, coef_offsets, optimised=False, out_cap=None, out=None):
+        """hvc_huffman_encode_frames_mixed: the mixed GPU Huffman coder alone.  Frame f = infos[f] (JpegInfo), its coefficient
+        record at coefs[coef_offsets[f]:] (int16 elements; numpy = host, torch cuda tensor = device).  Returns (segments, status,
+        specs): per frame its entropy-coded segment as bytes (empty for a refused or flagged frame), its own hvc_status, and --
+        optimised -- its [(bits, vals)] x 4 (None where the frame is not good); specs is None with the default tables.
+        out_cap: the capacity to offer (default: enough); out: the uint8 output array / tensor to write into (default: made
+        here)."""
+        n = len(infos)
+        m = max(n, 1)
+        arr = infos if isinstance(infos, C.Array) else (JpegInfo * m)(*infos)
+        ca, where = _addr(coefs) if coefs is not None else (None, HVC_MEM_HOST)
+        cap = out_cap if out_cap is not None else sum((arr[f].coef_count // 64) * 243 for f in range(n)) + 4096
+        status = (C.c_int * m)(*([77] * m))
+        specs = (HuffSpec * (4 * m))() if optimised else None
+        tables = HVC_HUFF["optimised" if optimised else "default"]
+        co = _size_array(coef_offsets, n)
+        if where == 1:
+            import torch
+            if out is None:
+                out = torch.empty(max(cap, 1), dtype=torch.uint8, device="cuda")
+            offs = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            _chk(lib().hvc_huffman_encode_frames_mixed(self._h, arr, ca, co, n, tables, out.data_ptr(), cap, offs.data_ptr(), status,
+                                                       specs, 1), "hvc_huffman_encode_frames_mixed")
+            o = offs.cpu().numpy()
+            data = out[:int(o[-1])].cpu().numpy()
+        else:
+            if out is None:
+                out = np.empty(max(cap, 1), dtype=np.uint8)
+            offs = np.zeros(n + 1, dtype=np.uint64)
+            _chk(lib().hvc_huffman_encode_frames_mixed(self._h, arr, ca, co, n, tables, out.ctypes.data, cap, offs.ctypes.data, status,
+                                                       specs, 0), "hvc_huffman_encode_frames_mixed")
+            o, data = offs, out
+        segs = [data[int(o[f]):int(o[f + 1])].tobytes() for f in range(n)]
+        st = [status[f] for f in range(n)]
+        sp = [[specs[4 * f + t].to_pair() for t in range(4)] if st[f] == 0 else None for f in range(n)] if optimised else None
+        return segs, st, sp
+
+    def jpeg_encode_batch_mixed(self, frames, specs=None, threads=8, chunk_bytes=0, layout=None, caps=None, outs=None, coder="host"):
+        """hvc_jpeg_encode_batch_mixed (coder="gpu": hvc_jpeg_encode_batch_mixed_gpu, the Huffman coder on the GPU too): raw planar frames (bytes / uint8 arrays, tight Y, U, V) of any sizes, samplings and
         qualities -> files, in one call.  specs: (width, height, chroma, quality) per frame, or layout: an EncoderMixedLayout
         made before.  Returns one (status, jpeg bytes or None, size) per frame: status = the frame's own hvc_status (0 = a file),
         size = sizes[f] as the call left it (the size needed where caps[f] was too small).  caps / outs (optional): the
@@ -1711,8 +1764,8 @@ class Context:
         sizes = (C.c_size_t * m)()
         status = (C.c_int * m)(*lay.status)
         st = BatchStats()
-        _chk(lib().hvc_jpeg_encode_batch_mixed(self._h, fp, lay.infos, status, n, threads, chunk_bytes, op, cp, sizes, C.byref(st)),
-             "hvc_jpeg_encode_batch_mixed")
+        name = {"host": "hvc_jpeg_encode_batch_mixed", "gpu": "hvc_jpeg_encode_batch_mixed_gpu"}[coder]
+        _chk(getattr(lib(), name)(self._h, fp, lay.infos, status, n, threads, chunk_bytes, op, cp, sizes, C.byref(st)), name)
         self.last_batch_stats = st
         return [(status[f], outs[f][:sizes[f]].tobytes() if status[f] == 0 else None, sizes[f]) for f in range(n)]
 
