@@ -967,8 +967,8 @@ HVC_API int hvc_jpeg_decode_batch_mixed_scaled_rgb(hvc_ctx *ctx, const uint8_t *
  * (k_encode_mixed, csrc/hvc_mixed_encode.hip: one wavefront per 64 blocks of one plane, k_encode's arithmetic per block), so
  * every coefficient is what hvc_encode_frames gives for that frame alone and every file what hvc_jpeg_encode gives for it.
  * With HVC_ARITH_HARDCAML as the ENCODE arithmetic (hvc_set_encode_arithmetic) the ctx functions return HVC_E_INVALID_ARG,
- * outputs untouched.  Here the files are coded by host threads (the Huffman coder on the GPU: the next section).  Not here:
- * RGB input, monochrome.
+ * outputs untouched.  Here the files are coded by host threads (the Huffman coder on the GPU: the next section).  RGB input:
+ * the section after that.  Not here: monochrome.
  *
  * hvc_jpeg_encoder_mixed_layout (host only, no ctx): per frame hvc_jpeg_encoder_layout(widths[f], heights[f], chromas[f],
  *   qualities[f]) + hvc_jpeg_encoder_check -> infos[f], status[f] (that frame's own code: a refused frame takes no room and
@@ -1009,7 +1009,7 @@ HVC_API int hvc_jpeg_encode_batch_mixed(hvc_ctx *ctx, const uint8_t *const *fram
 /* Mixed batches, ENCODING, with the Huffman coder on the GPU: the passes of hvc_huffman_encode_frames with the geometry of
  * every work unit taken from device memory (csrc/hvc_huff_mixed.hip: one wavefront per 64 blocks of one plane of one file, a
  * status word per file), so frames of different sizes and samplings are coded in one chain of launches.  Not in this coder:
- * restart intervals (the batch call hands such calls to the host coder), RGB input, monochrome, the Hardcaml arithmetic.
+ * restart intervals (the batch call hands such calls to the host coder), monochrome, the Hardcaml arithmetic.
  *
  * hvc_huffman_encode_frames_mixed: the coder alone.  Frame f is infos[f]; its coefficient record (as hvc_encode_frames_mixed
  *   writes it) is read from coefs + coef_offsets[f], which must lie on 16 bytes (HVC_E_ALIGNMENT for the call: an offset that
@@ -1044,6 +1044,69 @@ HVC_API int hvc_jpeg_encode_batch_mixed_gpu(hvc_ctx *ctx, const uint8_t *const *
                                             int n_frames, int threads, size_t chunk_bytes, uint8_t *const *jpegs,
                                             const size_t *caps, size_t *sizes, hvc_batch_stats *stats);
 HVC_API int hvc_last_mixed_coder_files(const hvc_ctx *ctx, uint64_t *gpu_files, uint64_t *host_files);
+
+/* ------------------------------------------------------------------------- */
+/* Mixed batches, ENCODING, from RGB images: what hvc_jpeg_decode_batch_mixed_rgb / _scaled_rgb hand back -- a directory of
+ * photographs, or their thumbnails, as RGB images of any size -- made into files again in one call.  One colour pass over
+ * images of ANY size and sampling (k_rgb_to_ycc_mixed, csrc/hvc_mixed_rgb.hip: k_ycc_to_rgb_mixed's work decomposition, one
+ * wavefront per 64 lanes of one image, and k_rgb_to_ycc's arithmetic per lane) stands in front of the mixed block stage, so
+ * every plane byte is what hvc_rgb_to_yuv gives for that image alone and every file byte for byte what hvc_jpeg_encode_rgb
+ * gives for it.  Image f is infos[f].width x .height at the sampling infos[f].comp[] names (4:2:0, 4:2:2, 4:4:4; the encoder's
+ * rule holds per frame: an even width under 4:2:0 / 4:2:2, an even height under 4:2:0); it is read from rgb + rgb_offsets[f]
+ * (or frames[f]) with rows rgb_row_strides[f] bytes apart (>= 3 * width interleaved, >= width planar; an entry of 0, or
+ * rgb_row_strides == NULL: tight rows) and planar planes rgb_row_strides[f] * height apart.  One call has one `layout`.
+ * Images and planes whose address and strides are multiples of 8 (chroma of 4:2:0 / 4:2:2: of 4) move in 8-byte (4-byte)
+ * pieces, the others byte by byte.  With HVC_ARITH_HARDCAML as the ENCODE arithmetic the encoding calls return
+ * HVC_E_INVALID_ARG, outputs untouched.  Not here: monochrome.  hvc_jpeg_encode_rgb itself is unchanged.
+ *
+ * hvc_jpeg_encoder_mixed_rgb_layout (host only, no ctx): per frame what hvc_jpeg_encode_rgb would answer for that geometry --
+ *   hvc_jpeg_encoder_layout's code, then hvc_jpeg_encoder_check's, then the even-size rule (HVC_E_INVALID_ARG) -> infos[f],
+ *   status[f]; a refused frame takes no room and stops nobody.  A good frame's image lies at rgb_offsets[f], rows
+ *   rgb_row_strides[f] = 3 * width (planar: width) rounded up to row_align, records in frame order, each start rounded up to
+ *   align (powers of two >= 1, else HVC_E_INVALID_ARG; align 0 = 256, row_align 0 = 1: tight rows); *rgb_total bytes hold all of
+ *   them.  pixel_offsets / coef_offsets / *pixel_total / *coef_total are what hvc_jpeg_encoder_mixed_layout gives (align 0: pixel
+ *   records on 64 bytes) for the good frames.
+ * hvc_rgb_to_yuv_mixed: the way back of hvc_yuv_to_rgb_mixed, argument for argument: frame f's planes are WRITTEN at yuv +
+ *   yuv_offsets[f], laid out by infos[f].layout (plane_offset, stride; a component that names its blocks must hold the
+ *   samples), from the image at rgb + rgb_offsets[f].  Only each frame's own samples are written: the padding of its planes
+ *   stays the caller's.  HVC_MEM_DEVICE: one launch, enqueued on ctx's stream, returns at once, honours hvc_set_profiling (the
+ *   pair brackets k_rgb_to_ycc_mixed); HVC_MEM_HOST: staged through context scratch, the call blocks.  For the whole call,
+ *   nothing written: HVC_E_INVALID_ARG for an odd size under its sampling, a sampling that is none of the three, a stride below
+ *   its row, a negative size; HVC_E_TOO_LARGE: a side above 2^24 or more lanes than the launch can index.  A frame with
+ *   width * height == 0 is skipped.
+ * hvc_encode_frames_mixed_rgb: RGB images to coefficient records, as hvc_encode_frames_mixed of the planes hvc_rgb_to_yuv makes
+ *   of each image in a zeroed padded record.  The padded planes live in context scratch (tight records on 64 bytes, zero-filled
+ *   as Plane.create) and never leave the GPU; coefs / coef_offsets / alignment rules and HVC_E_RANGE as hvc_encode_frames_mixed.
+ *   A set that is refused leaves nothing behind: both plans are built before anything is enqueued.  HVC_MEM_DEVICE: enqueued on
+ *   ctx's stream, honours hvc_set_profiling (the pair brackets k_encode_mixed); HVC_MEM_HOST: the call blocks, and only the
+ *   coefficient planes are copied back.
+ * hvc_jpeg_encode_batch_mixed_rgb / hvc_jpeg_encode_batch_mixed_rgb_gpu: hvc_jpeg_encode_batch_mixed / _gpu with RGB images as
+ *   frames[f]: the same pipelines, chunks (cut by the bytes of the padded pixel records, so the same infos give the same
+ *   chunks), statuses, caps / sizes rules, HVC_E_RANGE, stats and hvc_last_mixed_coder_files.  The padding workers copy each
+ *   image's rows tight into the pinned ring, the copy stream uploads them into a device RGB slot, and on the compute stream a
+ *   memset of the chunk's plane slot and k_rgb_to_ycc_mixed run in front of k_encode_mixed (kernel_ms_sum includes both).  An
+ *   image with an odd size under its sampling, or a row stride below its row, gets HVC_E_INVALID_ARG as its own status; a frame
+ *   refused before the call keeps its status, jpegs[f] and sizes[f].  Both honour hvc_set_huffman_tables,
+ *   hvc_set_restart_interval and hvc_set_host_cpus; under a restart interval the GPU variant hands every file to the host coder. */
+HVC_API int hvc_jpeg_encoder_mixed_rgb_layout(const int *widths, const int *heights, const int *chromas, const int *qualities,
+                                              int n_frames, int layout, size_t align, size_t row_align, hvc_jpeg_info *infos,
+                                              int *status, size_t *rgb_offsets, size_t *rgb_row_strides, size_t *rgb_total,
+                                              size_t *pixel_offsets, size_t *coef_offsets, size_t *pixel_total,
+                                              size_t *coef_total);
+HVC_API int hvc_rgb_to_yuv_mixed(hvc_ctx *ctx, uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos, int n_frames,
+                                 const uint8_t *rgb, const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout,
+                                 int where);
+HVC_API int hvc_encode_frames_mixed_rgb(hvc_ctx *ctx, const uint8_t *rgb, const size_t *rgb_offsets,
+                                        const size_t *rgb_row_strides, int layout, const hvc_jpeg_info *infos, int n_frames,
+                                        int16_t *coefs, const size_t *coef_offsets, int where);
+HVC_API int hvc_jpeg_encode_batch_mixed_rgb(hvc_ctx *ctx, const uint8_t *const *frames, const size_t *rgb_row_strides, int layout,
+                                            const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
+                                            size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes,
+                                            hvc_batch_stats *stats);
+HVC_API int hvc_jpeg_encode_batch_mixed_rgb_gpu(hvc_ctx *ctx, const uint8_t *const *frames, const size_t *rgb_row_strides,
+                                                int layout, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
+                                                size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes,
+                                                hvc_batch_stats *stats);
 
 /* K5 (no counterpart in the reference): what a benchmark or a pipeline produced, said in
  * 64 bits per record without bringing the records back.  For r < n_records

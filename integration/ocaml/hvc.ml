@@ -993,6 +993,57 @@ let last_mixed_coder_files =
   foreign "hvc_last_mixed_coder_files" (ctx @-> ptr uint64_t @-> ptr uint64_t @-> returning int)
 ;;
 
+(* mixed batches, encoding, from RGB images.
+   int hvc_jpeg_encoder_mixed_rgb_layout(widths, heights, chromas, qualities, n_frames, layout, align, row_align, infos, status,
+                                         rgb_offsets, rgb_row_strides, rgb_total, pixel_offsets, coef_offsets, pixel_total,
+                                         coef_total)                                                            host only *)
+let jpeg_encoder_mixed_rgb_layout =
+  foreign
+    "hvc_jpeg_encoder_mixed_rgb_layout"
+    (ptr int @-> ptr int @-> ptr int @-> ptr int @-> int @-> int @-> size_t @-> size_t @-> ptr Jpeg_info.t @-> ptr int
+    @-> ptr size_t @-> ptr size_t @-> ptr size_t @-> ptr size_t @-> ptr size_t @-> ptr size_t @-> ptr size_t
+    @-> returning int)
+;;
+
+(* int hvc_rgb_to_yuv_mixed(ctx, yuv, yuv_offsets, infos, n_frames, rgb, rgb_offsets, rgb_row_strides, layout, where) *)
+let rgb_to_yuv_mixed =
+  foreign
+    "hvc_rgb_to_yuv_mixed"
+    ~release_runtime_lock:true
+    (ctx @-> ptr char @-> ptr size_t @-> ptr Jpeg_info.t @-> int @-> ptr char @-> ptr size_t @-> ptr size_t @-> int
+    @-> int @-> returning int)
+;;
+
+(* int hvc_encode_frames_mixed_rgb(ctx, rgb, rgb_offsets, rgb_row_strides, layout, infos, n_frames, coefs, coef_offsets,
+                                   where) *)
+let encode_frames_mixed_rgb =
+  foreign
+    "hvc_encode_frames_mixed_rgb"
+    ~release_runtime_lock:true
+    (ctx @-> ptr char @-> ptr size_t @-> ptr size_t @-> int @-> ptr Jpeg_info.t @-> int @-> ptr int16_t @-> ptr size_t
+    @-> int @-> returning int)
+;;
+
+(* int hvc_jpeg_encode_batch_mixed_rgb(ctx, frames, rgb_row_strides, layout, infos, status, n_frames, threads, chunk_bytes,
+                                       jpegs, caps, sizes, stats) *)
+let jpeg_encode_batch_mixed_rgb =
+  foreign
+    "hvc_jpeg_encode_batch_mixed_rgb"
+    ~release_runtime_lock:true
+    (ctx @-> ptr (ptr char) @-> ptr size_t @-> int @-> ptr Jpeg_info.t @-> ptr int @-> int @-> int @-> size_t
+    @-> ptr (ptr char) @-> ptr size_t @-> ptr size_t @-> ptr Batch_stats.t @-> returning int)
+;;
+
+(* int hvc_jpeg_encode_batch_mixed_rgb_gpu(ctx, frames, rgb_row_strides, layout, infos, status, n_frames, threads, chunk_bytes,
+                                           jpegs, caps, sizes, stats) *)
+let jpeg_encode_batch_mixed_rgb_gpu =
+  foreign
+    "hvc_jpeg_encode_batch_mixed_rgb_gpu"
+    ~release_runtime_lock:true
+    (ctx @-> ptr (ptr char) @-> ptr size_t @-> int @-> ptr Jpeg_info.t @-> ptr int @-> int @-> int @-> size_t
+    @-> ptr (ptr char) @-> ptr size_t @-> ptr size_t @-> ptr Batch_stats.t @-> returning int)
+;;
+
 (* int hvc_jpeg_encode_rgb(ctx, rgb, rgb_row_stride, layout, width, height, chroma, quality, out, cap, out_len) *)
 let jpeg_encode_rgb =
   foreign

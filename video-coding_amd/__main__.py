@@ -11,6 +11,9 @@
                                                       raw frames of any sizes in ONE mixed batch call (hvc_jpeg_encode_batch_mixed[_gpu]):
                                                       OUT_DIR/<name>.jpg as `encode frame` writes it; a refused frame is
                                                       printed with its code and the others are still written
+    python -m video_coding_amd model encode frames OUT_DIR IN1.ppm WxH IN2.ppm WxH ... -rgb [the other flags as above]
+                                                      binary PPMs (P6) of those sizes in ONE call (hvc_jpeg_encode_batch_mixed_rgb[_gpu]):
+                                                      OUT_DIR/<name>.jpg as `encode frame -rgb` writes it
     python -m video_coding_amd model decode frames OUT_DIR IN1.jpg IN2.jpg ... [-restart-markers] [-threads 8] [-rgb] [-scale 2|4|8] [-reader gpu|host]
                                                       files of any sizes, samplings and tables in ONE mixed batch call
                                                       (hvc_jpeg_decode_batch_mixed): OUT_DIR/<name>.yuv as `decode frame` writes it;
@@ -227,7 +230,7 @@ def model_encode_frame(a):
 
 
 def model_encode_frames(a):
-    """every frame through one hvc_jpeg_encode_batch_mixed call: OUT_DIR/<name>.jpg as `encode frame` writes it; a frame that
+    """every frame through one hvc_jpeg_encode_batch_mixed call (-rgb: hvc_jpeg_encode_batch_mixed_rgb, from PPMs): OUT_DIR/<name>.jpg as `encode frame` writes it; a frame that
     is refused gets a line with its code on stderr and the others are still written; the exit status says whether any was"""
     import os
     if len(a.inputs) % 2:
@@ -237,18 +240,27 @@ def model_encode_frames(a):
         sizes = [size_arg(s) for s in a.inputs[1::2]]
     except ValueError:
         raise SystemExit("model encode frames: IN.yuv WxH pairs expected")
-    lay = hvc.jpeg_encoder_mixed_layout([(w, h, a.chroma, a.quality) for w, h in sizes])
+    specs = [(w, h, a.chroma, a.quality) for w, h in sizes]
+    lay = hvc.jpeg_encoder_mixed_rgb_layout(specs) if a.rgb else hvc.jpeg_encoder_mixed_layout(specs)
     frames = []
     for f, (path, (w, h)) in enumerate(zip(paths, sizes)):
         if lay.status[f]:
             frames.append(np.zeros(8, dtype=np.uint8))   # (takes no part)
+        elif a.rgb:
+            try:
+                frames.append(read_ppm(path, (w, h)))    # (refused here, before any GPU call, when it is not a WxH PPM)
+            except ValueError as e:
+                raise SystemExit(str(e))
         else:
             frames.append(np.concatenate([np.asarray(p, dtype=np.uint8).reshape(-1) for p in yuv.read_frame(path, w, h, a.chroma)]))
     ctx = hvc.Context(a.device)
     try:
         ctx.set_huffman_tables(a.huffman)
         ctx.set_restart_interval(a.restart_interval)
-        results = ctx.jpeg_encode_batch_mixed(frames, threads=a.threads, layout=lay, coder=a.coder)
+        if a.rgb:
+            results = ctx.jpeg_encode_batch_mixed_rgb(frames, threads=a.threads, enc_layout=lay, coder=a.coder)
+        else:
+            results = ctx.jpeg_encode_batch_mixed(frames, threads=a.threads, layout=lay, coder=a.coder)
     finally:
         ctx.close()
     os.makedirs(a.out_dir, exist_ok=True)
@@ -562,6 +574,8 @@ def parser():
     p.add_argument("-threads", type=int, default=8)
     p.add_argument("-coder", default="host", choices=["gpu", "host"],
                    help="who Huffman-codes the files: host threads, or the mixed GPU coder (hvc_jpeg_encode_batch_mixed_gpu); same bytes")
+    p.add_argument("-rgb", action="store_true",
+                   help="the inputs are binary PPMs (P6) of those sizes (hvc_jpeg_encode_batch_mixed_rgb[_gpu]): the files of `encode frame -rgb`")
     p.set_defaults(fn=model_encode_frames)
 
     oyuv =top.add_parser("oyuv").add_subparsers(dest="cmd", required=True)

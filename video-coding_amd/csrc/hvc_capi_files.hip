@@ -1,6 +1,7 @@
 // hvc_capi_files.hip -- the encoder's back end behind the C ABI: the GPU Huffman coder (hvc_huffman_encode_frames) and
 // BASELINE's configuration 5 end to end, raw frames in, JPEG files out (hvc_jpeg_encode_batch, hvc_jpeg_encode_batch_gpu).
 #include "hvc_ctx.h"
+#include "hvc_mixed_rgb_plan.h"
 
 // ---------------------------------------------------------------------------
 // Encoder back end on the GPU: RLE + Huffman + byte stuffing of coefficient records (hvc_huff.hip)
@@ -539,6 +540,36 @@ int hvc_jpeg_encode_batch_mixed_gpu(hvc_ctx *c, const uint8_t *const *frames, co
                                     int threads, size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes,
                                     hvc_batch_stats *stats) try {
     return encode_batch_mixed_gpu_impl(c, frames, infos, status, n_frames, threads, chunk_bytes, jpegs, caps, sizes, stats);
+} HVC_ABI_CATCH
+
+// ... from RGB images (k_rgb_to_ycc_mixed in front of the block stage: hvc_mixed_rgb.hip, hvc_mixed_rgb_plan.cpp)
+int hvc_jpeg_encoder_mixed_rgb_layout(const int *widths, const int *heights, const int *chromas, const int *qualities, int n_frames,
+                                      int layout, size_t align, size_t row_align, hvc_jpeg_info *infos, int *status, size_t *rgb_offsets,
+                                      size_t *rgb_row_strides, size_t *rgb_total, size_t *pixel_offsets, size_t *coef_offsets,
+                                      size_t *pixel_total, size_t *coef_total) try {
+    return hvc::encoder_mixed_rgb_layout(widths, heights, chromas, qualities, n_frames, layout, align, row_align, infos, status, rgb_offsets,
+                                         rgb_row_strides, rgb_total, pixel_offsets, coef_offsets, pixel_total, coef_total);
+} HVC_ABI_CATCH
+
+int hvc_encode_frames_mixed_rgb(hvc_ctx *c, const uint8_t *rgb, const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout,
+                                const hvc_jpeg_info *infos, int n_frames, int16_t *coefs, const size_t *coef_offsets, int where) try {
+    return encode_frames_mixed_rgb_impl(c, rgb, rgb_offsets, rgb_row_strides, layout, infos, n_frames, coefs, coef_offsets, where);
+} HVC_ABI_CATCH
+
+int hvc_jpeg_encode_batch_mixed_rgb(hvc_ctx *c, const uint8_t *const *frames, const size_t *rgb_row_strides, int layout,
+                                    const hvc_jpeg_info *infos, int *status, int n_frames, int threads, size_t chunk_bytes,
+                                    uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats) try {
+    MixedEncodeInput in;
+    in.rgb = true, in.layout = layout, in.rgb_row_strides = rgb_row_strides;
+    return encode_batch_mixed_impl(c, frames, infos, status, n_frames, threads, chunk_bytes, jpegs, caps, sizes, stats, in);
+} HVC_ABI_CATCH
+
+int hvc_jpeg_encode_batch_mixed_rgb_gpu(hvc_ctx *c, const uint8_t *const *frames, const size_t *rgb_row_strides, int layout,
+                                        const hvc_jpeg_info *infos, int *status, int n_frames, int threads, size_t chunk_bytes,
+                                        uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats) try {
+    MixedEncodeInput in;
+    in.rgb = true, in.layout = layout, in.rgb_row_strides = rgb_row_strides;
+    return encode_batch_mixed_gpu_impl(c, frames, infos, status, n_frames, threads, chunk_bytes, jpegs, caps, sizes, stats, in);
 } HVC_ABI_CATCH
 
 int hvc_last_mixed_coder_files(const hvc_ctx *c, uint64_t *gpu_files, uint64_t *host_files) try {

@@ -70,9 +70,13 @@ int upload_plan(hvc_ctx *c, const hvc::MixedPlan &plan, hvc::MixedParams &P) {
     return HVC_OK;
 }
 
+} // namespace
+
 // The colour pass of a plan on DEVICE memory, enqueued on c->stream: its tables (images | map, each part on 16 bytes) go to
-// c->mixed_rgb_plan, a buffer of their own.
-int mixed_rgb_launch_plan(hvc_ctx *c, const hvc::MixedRgbPlan &plan, int layout, const uint8_t *d_yuv, uint8_t *d_rgb, bool profile) {
+// c->mixed_rgb_plan, a buffer of their own.  to_ycc: the way back, k_rgb_to_ycc_mixed over a plan of
+// mixed_rgb_encode_plan_build -- d_rgb is read, the planes at d_yuv are written (hvc_capi_mixed_encode.hip).
+int mixed_rgb_launch_plan(hvc_ctx *c, const hvc::MixedRgbPlan &plan, int layout, const uint8_t *d_yuv, uint8_t *d_rgb, bool profile,
+                          bool to_ycc) {
     if (plan.map.empty()) return HVC_OK; // no pixel at all: nothing to launch
     const size_t map_at = (plan.images.size() * sizeof(hvc::MixedRgbImageK) + 15) & ~(size_t)15;
     std::vector<unsigned char> img(map_at + ((plan.map.size() * sizeof(unsigned) + 15) & ~(size_t)15), 0);
@@ -89,11 +93,14 @@ int mixed_rgb_launch_plan(hvc_ctx *c, const hvc::MixedRgbPlan &plan, int layout,
     P.n_units = (unsigned)plan.map.size();
     P.planar = layout == HVC_RGB_PLANAR;
     const int slot = (int)(c->k_calls % HVC_PROF_RING);
-    const hipError_t e = hvc::launch_ycc_to_rgb_mixed(P, c->stream, profile ? c->k0[slot] : nullptr, profile ? c->k1[slot] : nullptr);
+    const hipEvent_t k0 = profile ? (hipEvent_t)c->k0[slot] : nullptr, k1 = profile ? (hipEvent_t)c->k1[slot] : nullptr;
+    const hipError_t e = to_ycc ? hvc::launch_rgb_to_ycc_mixed(P, c->stream, k0, k1) : hvc::launch_ycc_to_rgb_mixed(P, c->stream, k0, k1);
     if (e != hipSuccess) return fail_hip(c, e);
     if (profile) c->k_calls++;
     return HVC_OK;
 }
+
+namespace {
 
 // the fix-up list holds one id per block slot of the launch (every unit may send all 64 of its lanes)
 int reserve_mixed_fix_list(hvc_ctx *c, size_t entries) { return grow(c, c->d_fix_list, entries * sizeof(unsigned)); }
@@ -198,6 +205,8 @@ hipError_t download_images(const hvc::MixedRgbPlan &plan, int layout, const uint
     return hipSuccess;
 }
 
+} // namespace
+
 // where the images of a host-memory call go in device scratch: one after another, each keeping its offset modulo 64 (the
 // 8-byte paths then run for exactly the images a device-memory call with these offsets would take them for)
 size_t stage_offsets(const size_t *offsets, const std::vector<size_t> &spans, std::vector<size_t> &d_off) {
@@ -209,8 +218,6 @@ size_t stage_offsets(const size_t *offsets, const std::vector<size_t> &spans, st
     }
     return tot;
 }
-
-} // namespace
 
 // behind hvc_decode_frames_mixed (hvc_capi.hip)
 int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,

@@ -2,8 +2,9 @@
 // the coder alone over a set of coefficient records (behind hvc_huffman_encode_frames_mixed) and the file pipeline built on it
 // (behind hvc_jpeg_encode_batch_mixed_gpu); the entry points themselves stand in hvc_capi_files.hip.
 // The pipeline is encode_batch_mixed_impl's (hvc_capi_mixed_encode.hip) with the coder stage of hvc_jpeg_encode_batch_gpu:
-//   host threads: Plane.blit_available into zero-padded planes (pinned ring)
-//   copy stream:  hipMemcpyAsync H2D           compute stream: k_encode_mixed into the device slot, the mixed coder over it,
+//   host threads: Plane.blit_available into zero-padded planes (pinned ring)  [RGB input, MixedEncodeInput: the image's rows, tight]
+//   copy stream:  hipMemcpyAsync H2D           compute stream: [RGB input: the plane slot cleared, k_rgb_to_ycc_mixed into it,]
+//                                               k_encode_mixed into the device slot, the mixed coder over it,
 //                                               D2H of the chunk's offsets, status words and (optimised) specs
 //   down stream:  exactly the packed segments of the files the GPU finished, into the pinned slot
 //   host threads: header (jpeg_header_bytes with the file's info and its own specs) + segment + EOI per file
@@ -169,9 +170,11 @@ int huffman_encode_frames_mixed_impl(hvc_ctx *c, const hvc_jpeg_info *infos, con
 
 // behind hvc_jpeg_encode_batch_mixed_gpu (hvc_capi_files.hip)
 int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
-                                size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats) {
+                                size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats,
+                                const MixedEncodeInput &in) {
     if (!c || !frames || !infos || !status || !jpegs || !caps || !sizes || n_frames < 0) return HVC_E_INVALID_ARG;
     if (c->enc_arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG;
+    if (in.rgb && in.layout != HVC_RGB_INTERLEAVED && in.layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
     if (stats) std::memset(stats, 0, sizeof *stats);
     c->mixed_coder_gpu_files = c->mixed_coder_host_files = 0;
     if (n_frames == 0) return HVC_OK;
@@ -181,7 +184,7 @@ int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const 
         unsigned long long n = 0;
         for (int f = 0; f < n_frames; f++)
             if (mine[(size_t)f]) st2[(size_t)f] = HVC_OK, n++;
-        const int r = encode_batch_mixed_impl(c, frames, infos, st2.data(), n_frames, threads, chunk_bytes, jpegs, caps, sizes, st);
+        const int r = encode_batch_mixed_impl(c, frames, infos, st2.data(), n_frames, threads, chunk_bytes, jpegs, caps, sizes, st, in);
         for (int f = 0; f < n_frames; f++)
             if (mine[(size_t)f]) status[f] = st2[(size_t)f];
         c->mixed_coder_host_files += n;
@@ -200,11 +203,11 @@ int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const 
     // the frames that take part, cut into chunks as encode_batch_mixed_impl cuts them (+ the coder's cap on a chunk's files)
     struct Chunk {
         int first = 0, count = 0; // positions in `take`
-        size_t pix_bytes = 0, coef_elems = 0;
+        size_t pix_bytes = 0, coef_elems = 0, rgb_bytes = 0;
     };
     std::vector<int> take, chunk_of((size_t)n_frames, -1);
     std::vector<Chunk> chunks;
-    std::vector<size_t> pix_rel((size_t)n_frames, 0), coef_rel((size_t)n_frames, 0);
+    std::vector<size_t> pix_rel((size_t)n_frames, 0), coef_rel((size_t)n_frames, 0), rgb_rel(in.rgb ? (size_t)n_frames : 0, 0);
     for (int f = 0; f < n_frames; f++) {
         if (status[f] != HVC_OK) continue;
         if (!frames[f] || !jpegs[f]) return HVC_E_INVALID_ARG;
@@ -219,6 +222,7 @@ int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const 
                 k.actual_width < 0 || k.actual_height < 0)
                 e = HVC_E_INVALID_ARG;
         }
+        if (!e && in.rgb) e = encode_rgb_frame_status(infos[f], in, f);
         if (e) {
             status[f] = e;
             continue;
@@ -238,15 +242,20 @@ int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const 
         chunk_of[(size_t)f] = (int)chunks.size() - 1;
         k.pix_bytes += pb;
         k.coef_elems += (infos[f].coef_count + 31) & ~(size_t)31;
+        if (in.rgb) { // the tight image in the chunk's RGB slot, on 64 bytes
+            rgb_rel[(size_t)f] = k.rgb_bytes;
+            k.rgb_bytes += (encode_rgb_frame_bytes(infos[f], in) + 63) & ~(size_t)63;
+        }
         k.count++;
         take.push_back(f);
     }
     if (take.empty()) return HVC_OK;
     const int n_chunks = (int)chunks.size(), n_take = (int)take.size();
-    size_t in_bytes = 0, out_bytes = 0;
+    size_t in_bytes = 0, out_bytes = 0, rgb_bytes = 0;
     int largest = 0;
     for (const Chunk &k : chunks) {
-        in_bytes = std::max(in_bytes, k.pix_bytes);
+        in_bytes = std::max(in_bytes, std::max(k.pix_bytes, k.rgb_bytes)); // (eh_in: the pinned images; ed_in: the planes)
+        rgb_bytes = std::max(rgb_bytes, k.rgb_bytes);
         out_bytes = std::max(out_bytes, k.coef_elems * sizeof(int16_t));
         largest = std::max(largest, k.count);
     }
@@ -270,6 +279,7 @@ int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const 
     const size_t off_bytes = words_at + (size_t)largest * sizeof(unsigned);
     if ((r = ring_ensure(c, enc_seg_rings(c), {out_bytes, off_bytes, off_bytes}))) return r;
     if ((r = ring_ensure(c, enc_rings(c), {in_bytes, out_bytes, in_bytes, out_bytes}))) return r;
+    if (in.rgb && (r = ring_ensure(c, enc_rgb_rings(c), {rgb_bytes}))) return r;
 
     // what the orchestrating thread leaves for the assembling workers, per position in `take` (written before the chunk's
     // release, which the feed's mutex orders)
@@ -298,7 +308,10 @@ int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const 
             const int f = take[(size_t)t], k = chunk_of[(size_t)f];
             if (!padf.wait_slot(k)) return;
             const auto t0 = std::chrono::steady_clock::now();
-            pad_frame(infos[f], frames[f], c->eh_in[k % NB].as<uint8_t>() + pix_rel[(size_t)f]);
+            if (in.rgb)
+                encode_rgb_frame_copy(infos[f], in, f, frames[f], c->eh_in[k % NB].as<uint8_t>() + rgb_rel[(size_t)f]);
+            else
+                pad_frame(infos[f], frames[f], c->eh_in[k % NB].as<uint8_t>() + pix_rel[(size_t)f]);
             pad_ns += ns_since(t0);
             padf.report(k, 1, HVC_OK);
         }
@@ -388,12 +401,17 @@ int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const 
             // been assembled (its downloads are behind it: ev_down[slot] was waited for before that chunk went to the workers)
             if (k >= NB && (rc = codf.wait_chunk(k - NB, chunks[(size_t)(k - NB)].count))) break;
             hipError_t he = hipEventRecord(c->ev_et[slot][0], c->copy_stream);
-            if (he == hipSuccess) he = hipMemcpyAsync(c->ed_in[slot].p, c->eh_in[slot].p, ch.pix_bytes, hipMemcpyHostToDevice, c->copy_stream);
+            if (he == hipSuccess)
+                he = in.rgb ? hipMemcpyAsync(c->ed_rgb[slot].p, c->eh_in[slot].p, ch.rgb_bytes, hipMemcpyHostToDevice, c->copy_stream)
+                            : hipMemcpyAsync(c->ed_in[slot].p, c->eh_in[slot].p, ch.pix_bytes, hipMemcpyHostToDevice, c->copy_stream);
             if (he == hipSuccess) he = hipEventRecord(c->ev_up[slot], c->copy_stream);
             if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_up[slot], 0);
             if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][1], compute);
             if (he != hipSuccess) { rc = fail_hip(c, he); break; }
             list.assign(take.begin() + ch.first, take.begin() + ch.first + ch.count);
+            if (in.rgb && (rc = encode_rgb_stage(c, in, infos, list.data(), ch.count, pix_rel.data(), rgb_rel.data(),
+                                                 c->ed_rgb[slot].as<const uint8_t>(), c->ed_in[slot].as<uint8_t>(), ch.pix_bytes)))
+                break;
             hvc::MixedEncodePlan plan;
             if ((rc = hvc::mixed_encode_plan_build(infos, coef_rel.data(), pix_rel.data(), list.data(), ch.count, plan))) break;
             if ((rc = encode_mixed_launch_plan(c, plan, c->ed_in[slot].as<const uint8_t>(), c->ed_out[slot].as<int16_t>(), false))) break;

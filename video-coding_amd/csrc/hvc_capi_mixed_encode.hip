@@ -7,10 +7,15 @@
 //   host threads: Plane.blit_available into zero-padded planes (pinned ring)       encoder.ml:514-516
 //   copy stream:  hipMemcpyAsync H2D           compute stream: k_encode_mixed (a plan per chunk), D2H of the chunk's records
 //   host threads: write_headers + rle + write_bits + EOI per file, with its own info      encoder.ml:127-193, 371-418
+// With RGB images as input (MixedEncodeInput, hvc_ctx.h; behind hvc_jpeg_encode_batch_mixed_rgb) the host threads copy each
+// image's rows tight into the pinned ring, the copy stream uploads them into a device RGB slot, and on the compute stream a
+// hipMemsetAsync of the chunk's plane slot and k_rgb_to_ycc_mixed (hvc_mixed_rgb.hip) stand in front of k_encode_mixed.  The
+// colour pass alone is behind hvc_rgb_to_yuv_mixed, in front of one block stage behind hvc_encode_frames_mixed_rgb (below).
 // Two chunk feeds (hvc_feed.h) hand the chunks over: the padding workers fill pinned pixel slots for the orchestrating
 // thread, the orchestrating thread hands pinned coefficient slots to the coder workers.
 #include "hvc_batch.h"
 #include "hvc_mixed_encode.h"
+#include "hvc_mixed_rgb.h"
 
 namespace {
 
@@ -136,9 +141,11 @@ int encode_frames_mixed_impl(hvc_ctx *c, const uint8_t *pixels, const size_t *pi
 
 // behind hvc_jpeg_encode_batch_mixed (hvc_capi_files.hip)
 int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
-                            size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats) {
+                            size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats,
+                            const MixedEncodeInput &in) {
     if (!c || !frames || !infos || !status || !jpegs || !caps || !sizes || n_frames < 0) return HVC_E_INVALID_ARG;
     if (c->enc_arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG;
+    if (in.rgb && in.layout != HVC_RGB_INTERLEAVED && in.layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_frames == 0) return HVC_OK;
     if (chunk_bytes == 0) chunk_bytes = (size_t)64 << 20;
@@ -150,11 +157,11 @@ int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_
     // coder would refuse gets its own status here and is left out
     struct Chunk {
         int first = 0, count = 0; // positions in `take`
-        size_t pix_bytes = 0, coef_elems = 0;
+        size_t pix_bytes = 0, coef_elems = 0, rgb_bytes = 0;
     };
     std::vector<int> take, chunk_of((size_t)n_frames, -1);
     std::vector<Chunk> chunks;
-    std::vector<size_t> pix_rel((size_t)n_frames, 0), coef_rel((size_t)n_frames, 0);
+    std::vector<size_t> pix_rel((size_t)n_frames, 0), coef_rel((size_t)n_frames, 0), rgb_rel(in.rgb ? (size_t)n_frames : 0, 0);
     for (int f = 0; f < n_frames; f++) {
         if (status[f] != HVC_OK) continue;
         if (!frames[f] || !jpegs[f]) return HVC_E_INVALID_ARG;
@@ -169,6 +176,7 @@ int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_
                 k.actual_width < 0 || k.actual_height < 0)
                 e = HVC_E_INVALID_ARG;
         }
+        if (!e && in.rgb) e = encode_rgb_frame_status(infos[f], in, f);
         if (e) {
             status[f] = e;
             continue;
@@ -187,16 +195,21 @@ int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_
         chunk_of[(size_t)f] = (int)chunks.size() - 1;
         k.pix_bytes += pb;
         k.coef_elems += (infos[f].coef_count + 31) & ~(size_t)31;
+        if (in.rgb) { // the tight image in the chunk's RGB slot, on 64 bytes
+            rgb_rel[(size_t)f] = k.rgb_bytes;
+            k.rgb_bytes += (encode_rgb_frame_bytes(infos[f], in) + 63) & ~(size_t)63;
+        }
         k.count++;
         take.push_back(f);
     }
     if (take.empty()) return HVC_OK;
     const int n_chunks = (int)chunks.size(), n_take = (int)take.size();
-    size_t in_bytes = 0, out_bytes = 0;
+    size_t in_bytes = 0, out_bytes = 0, rgb_bytes = 0;
     int largest = 0;
     uint64_t coef_total = 0;
     for (const Chunk &k : chunks) {
-        in_bytes = std::max(in_bytes, k.pix_bytes);
+        in_bytes = std::max(in_bytes, std::max(k.pix_bytes, k.rgb_bytes)); // (eh_in: the pinned images; ed_in: the planes)
+        rgb_bytes = std::max(rgb_bytes, k.rgb_bytes);
         out_bytes = std::max(out_bytes, k.coef_elems * sizeof(int16_t));
         largest = std::max(largest, k.count);
         coef_total += k.coef_elems * sizeof(int16_t);
@@ -212,6 +225,7 @@ int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_
     }
     int r = ring_ensure(c, enc_rings(c), {in_bytes, out_bytes, in_bytes, out_bytes}); // (a frame larger than chunk_bytes: the ring grows)
     if (r) return r;
+    if (in.rgb && (r = ring_ensure(c, enc_rgb_rings(c), {rgb_bytes}))) return r;
     const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // each file its own tables (hvc_set_huffman_tables)
     const int ri = c->restart_interval;                    // DRI + RSTn every ri MCUs (hvc_set_restart_interval)
 
@@ -234,7 +248,10 @@ int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_
             const int f = take[(size_t)t], k = chunk_of[(size_t)f];
             if (!padf.wait_slot(k)) return;
             const auto t0 = std::chrono::steady_clock::now();
-            pad_frame(infos[f], frames[f], c->eh_in[k % NB].as<uint8_t>() + pix_rel[(size_t)f]);
+            if (in.rgb)
+                encode_rgb_frame_copy(infos[f], in, f, frames[f], c->eh_in[k % NB].as<uint8_t>() + rgb_rel[(size_t)f]);
+            else
+                pad_frame(infos[f], frames[f], c->eh_in[k % NB].as<uint8_t>() + pix_rel[(size_t)f]);
             pad_ns += ns_since(t0);
             padf.report(k, 1, HVC_OK);
         }
@@ -283,12 +300,17 @@ int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_
             // read the device slots are behind it: ev_down[slot] was waited for before that chunk went to the coders)
             if (k >= NB && (rc = codf.wait_chunk(k - NB, chunks[(size_t)(k - NB)].count))) break;
             hipError_t he = hipEventRecord(c->ev_et[slot][0], c->copy_stream);
-            if (he == hipSuccess) he = hipMemcpyAsync(c->ed_in[slot].p, c->eh_in[slot].p, ch.pix_bytes, hipMemcpyHostToDevice, c->copy_stream);
+            if (he == hipSuccess)
+                he = in.rgb ? hipMemcpyAsync(c->ed_rgb[slot].p, c->eh_in[slot].p, ch.rgb_bytes, hipMemcpyHostToDevice, c->copy_stream)
+                            : hipMemcpyAsync(c->ed_in[slot].p, c->eh_in[slot].p, ch.pix_bytes, hipMemcpyHostToDevice, c->copy_stream);
             if (he == hipSuccess) he = hipEventRecord(c->ev_up[slot], c->copy_stream);
             if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_up[slot], 0);
             if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][1], compute);
             if (he != hipSuccess) { rc = fail_hip(c, he); break; }
             list.assign(take.begin() + ch.first, take.begin() + ch.first + ch.count);
+            if (in.rgb && (rc = encode_rgb_stage(c, in, infos, list.data(), ch.count, pix_rel.data(), rgb_rel.data(),
+                                                 c->ed_rgb[slot].as<const uint8_t>(), c->ed_in[slot].as<uint8_t>(), ch.pix_bytes)))
+                break;
             hvc::MixedEncodePlan plan;
             if ((rc = hvc::mixed_encode_plan_build(infos, coef_rel.data(), pix_rel.data(), list.data(), ch.count, plan))) break;
             if ((rc = encode_mixed_launch_plan(c, plan, c->ed_in[slot].as<const uint8_t>(), c->ed_out[slot].as<int16_t>(), false))) break;
@@ -331,4 +353,167 @@ int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_
         stats->coef_bytes = coef_total; // bytes downloaded
     }
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// RGB input: k_rgb_to_ycc_mixed (hvc_mixed_rgb.hip) from the host plan mixed_rgb_encode_plan_build (hvc_mixed_rgb_plan.cpp)
+
+namespace {
+
+// bytes from the start of frame f's image to its last byte, by the caller's row stride (0: no image, or a stride below the row)
+size_t rgb_image_span(const hvc_jpeg_info &fi, const size_t *rgb_row_strides, int f, int layout) {
+    if (fi.width < 1 || fi.height < 1) return 0;
+    const size_t tight = hvc::mixed_rgb_row_bytes(layout, fi.width);
+    const size_t rs = rgb_row_strides && rgb_row_strides[f] ? rgb_row_strides[f] : tight;
+    return rs < tight ? 0 : hvc::mixed_rgb_span(layout, fi.width, fi.height, rs);
+}
+
+} // namespace
+
+int encode_rgb_frame_status(const hvc_jpeg_info &info, const MixedEncodeInput &in, int f) {
+    const int s = rgb_sampling_of(info);
+    if (s != HVC_YUV_420 && s != HVC_YUV_422 && s != HVC_YUV_444) return HVC_E_INVALID_ARG;
+    if ((s != HVC_YUV_444 && (info.width & 1)) || (s == HVC_YUV_420 && (info.height & 1))) return HVC_E_INVALID_ARG; // Yuv.assert_is_420 / _422
+    if (in.rgb_row_strides && in.rgb_row_strides[f] && in.rgb_row_strides[f] < hvc::mixed_rgb_row_bytes(in.layout, info.width)) return HVC_E_INVALID_ARG;
+    return HVC_OK;
+}
+
+size_t encode_rgb_frame_bytes(const hvc_jpeg_info &info, const MixedEncodeInput &in) {
+    return hvc::mixed_rgb_row_bytes(in.layout, info.width) * hvc::mixed_rgb_rows(in.layout, info.height);
+}
+
+void encode_rgb_frame_copy(const hvc_jpeg_info &info, const MixedEncodeInput &in, int f, const uint8_t *src, uint8_t *dst) {
+    const size_t row = hvc::mixed_rgb_row_bytes(in.layout, info.width), rows = hvc::mixed_rgb_rows(in.layout, info.height);
+    const size_t rs = in.rgb_row_strides && in.rgb_row_strides[f] ? in.rgb_row_strides[f] : row;
+    if (rs == row) {
+        std::memcpy(dst, src, row * rows);
+        return;
+    }
+    for (size_t y = 0; y < rows; y++) std::memcpy(dst + y * row, src + y * rs, row); // (planar: the planes are rs * height apart)
+}
+
+int encode_rgb_stage(hvc_ctx *c, const MixedEncodeInput &in, const hvc_jpeg_info *infos, const int *list, int count, const size_t *pix_rel,
+                     const size_t *rgb_rel, const uint8_t *d_rgb, uint8_t *d_planes, size_t plane_bytes) {
+    hvc::MixedRgbPlan plan;
+    const int r = hvc::mixed_rgb_encode_plan_build(infos, pix_rel, rgb_rel, nullptr, in.layout, list, count, (uintptr_t)d_planes, (uintptr_t)d_rgb, plan);
+    if (r) return r;
+    HIPCHK(c, hipMemsetAsync(d_planes, 0, plane_bytes, c->stream)); // Plane.create is zero-filled: the kernel writes the frames' own samples only
+    return mixed_rgb_launch_plan(c, plan, in.layout, d_planes, const_cast<uint8_t *>(d_rgb), false, true); // (d_rgb is read only)
+}
+
+// behind hvc_rgb_to_yuv_mixed (hvc_yuv.hip)
+int rgb_to_yuv_mixed_impl(hvc_ctx *c, uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos, int n_frames, const uint8_t *rgb,
+                          const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where) {
+    if (!c || n_frames < 0 || (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE)) return HVC_E_INVALID_ARG;
+    if (layout != HVC_RGB_INTERLEAVED && layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
+    if (n_frames == 0) return HVC_OK;
+    if (!infos || !yuv_offsets || !rgb_offsets) return HVC_E_INVALID_ARG;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    int r;
+    hvc::MixedRgbPlan plan; // the caller's own offsets: checked for either kind of memory, launched on for device memory
+    if ((r = hvc::mixed_rgb_encode_plan_build(infos, yuv_offsets, rgb_offsets, rgb_row_strides, layout, nullptr, n_frames, (uintptr_t)yuv,
+                                              (uintptr_t)rgb, plan)))
+        return r;
+    if (plan.map.empty()) return HVC_OK; // (a set without a pixel needs no memory)
+    if (!yuv || !rgb) return HVC_E_INVALID_ARG;
+    if (where == HVC_MEM_DEVICE) return mixed_rgb_launch_plan(c, plan, layout, yuv, const_cast<uint8_t *>(rgb), c->profiling, true);
+    // host memory: the images and the plane records one after another in c->d_in / c->d_out; only each frame's own samples
+    // come back (the padding of its planes stays the caller's)
+    std::vector<size_t> yspan((size_t)n_frames, 0), rspan((size_t)n_frames, 0), d_yuv, d_rgb;
+    for (size_t i = 0; i < plan.images.size(); i++) {
+        const hvc::MixedRgbImageK &k = plan.images[i];
+        const int f = plan.frame[i];
+        yspan[(size_t)f] = rgb_yuv_span(infos[f].layout, k.sampling, k.w, k.h, k.cw, k.ch);
+        rspan[(size_t)f] = rgb_image_span(infos[f], rgb_row_strides, f, layout);
+    }
+    const size_t ytot = stage_offsets(yuv_offsets, yspan, d_yuv), rtot = stage_offsets(rgb_offsets, rspan, d_rgb);
+    if ((r = grow(c, c->d_in, rtot))) return r;
+    if ((r = grow(c, c->d_out, ytot))) return r;
+    if ((r = hvc::mixed_rgb_encode_plan_build(infos, d_yuv.data(), d_rgb.data(), rgb_row_strides, layout, nullptr, n_frames, (uintptr_t)c->d_out.p,
+                                              (uintptr_t)c->d_in.p, plan)))
+        return r;
+    for (int f = 0; f < n_frames; f++)
+        if (rspan[(size_t)f])
+            HIPCHK(c, hipMemcpyAsync(c->d_in.as<uint8_t>() + d_rgb[(size_t)f], rgb + rgb_offsets[f], rspan[(size_t)f], hipMemcpyHostToDevice, c->stream));
+    if ((r = mixed_rgb_launch_plan(c, plan, layout, c->d_out.as<const uint8_t>(), c->d_in.as<uint8_t>(), false, true))) {
+        (void)hipStreamSynchronize(c->stream);
+        return r;
+    }
+    for (size_t i = 0; i < plan.images.size(); i++) {
+        const hvc::MixedRgbImageK &k = plan.images[i];
+        const int f = plan.frame[i];
+        for (int p = 0; p < 3; p++) {
+            const hvc_component &L = infos[f].layout[p];
+            const size_t at = L.plane_offset;
+            HIPCHK(c, hipMemcpy2DAsync(yuv + yuv_offsets[f] + at, L.stride, c->d_out.as<const uint8_t>() + d_yuv[(size_t)f] + at, L.stride,
+                                       (size_t)(p ? k.cw : k.w), (size_t)(p ? k.ch : k.h), hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
+}
+
+// behind hvc_encode_frames_mixed_rgb (hvc_capi_files.hip): zeroed padded planes in c->d_aux (tight records on 64 bytes), the
+// colour pass into them, k_encode_mixed from there; host memory: the images are staged in c->d_in, the records in c->d_out
+int encode_frames_mixed_rgb_impl(hvc_ctx *c, const uint8_t *rgb, const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout,
+                                 const hvc_jpeg_info *infos, int n_frames, int16_t *coefs, const size_t *coef_offsets, int where) {
+    if (!c || n_frames < 0 || (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE)) return HVC_E_INVALID_ARG;
+    if (layout != HVC_RGB_INTERLEAVED && layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
+    if (c->enc_arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (the RTL encoder's arithmetic has no mixed form)
+    if (n_frames == 0) return HVC_OK;
+    if (!infos || !coef_offsets || !rgb_offsets) return HVC_E_INVALID_ARG;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    const bool host = where == HVC_MEM_HOST;
+    std::vector<size_t> d_pix((size_t)n_frames, 0), d_coef((size_t)n_frames, 0), rspan((size_t)n_frames, 0), d_rgb;
+    size_t ptot = 0, ctot = 0;
+    for (int f = 0; f < n_frames; f++) {
+        size_t ps, cs;
+        encode_frame_spans(infos[f], ps, cs);
+        d_pix[(size_t)f] = ptot;
+        d_coef[(size_t)f] = ctot;
+        ptot += (ps + 63) & ~(size_t)63;
+        ctot += (cs + 31) & ~(size_t)31;
+        rspan[(size_t)f] = rgb_image_span(infos[f], rgb_row_strides, f, layout);
+    }
+    const size_t rtot = host ? stage_offsets(rgb_offsets, rspan, d_rgb) : 0;
+    int r;
+    hvc::MixedEncodePlan bplan; // both plans before anything is enqueued: a set that is refused leaves nothing behind
+    hvc::MixedRgbPlan cplan;
+    if ((r = hvc::mixed_encode_plan_build(infos, host ? d_coef.data() : coef_offsets, d_pix.data(), nullptr, n_frames, bplan))) return r;
+    if ((r = hvc::mixed_rgb_encode_plan_build(infos, d_pix.data(), host ? d_rgb.data() : rgb_offsets, rgb_row_strides, layout, nullptr, n_frames, 0,
+                                              host ? 0 : (uintptr_t)rgb, cplan)))
+        return r;
+    if (bplan.map.empty()) return HVC_OK; // (a set without a block needs no memory)
+    if (!coefs || (!cplan.map.empty() && !rgb)) return HVC_E_INVALID_ARG;
+    if (!host && ((uintptr_t)coefs & 15)) return HVC_E_ALIGNMENT;
+    if ((r = grow(c, c->d_aux, ptot))) return r;
+    if (host && (r = grow(c, c->d_in, rtot))) return r;
+    if (host && (r = grow(c, c->d_out, ctot * sizeof(int16_t)))) return r;
+    const uint8_t *src = host ? c->d_in.as<const uint8_t>() : rgb;
+    // (the flags follow the actual addresses: the plan again, now that the scratch is there)
+    if ((r = hvc::mixed_rgb_encode_plan_build(infos, d_pix.data(), host ? d_rgb.data() : rgb_offsets, rgb_row_strides, layout, nullptr, n_frames,
+                                              (uintptr_t)c->d_aux.p, (uintptr_t)src, cplan)))
+        return r;
+    for (int f = 0; host && f < n_frames; f++)
+        if (rspan[(size_t)f])
+            HIPCHK(c, hipMemcpyAsync(c->d_in.as<uint8_t>() + d_rgb[(size_t)f], rgb + rgb_offsets[f], rspan[(size_t)f], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_aux.p, 0, ptot, c->stream)); // Plane.create is zero-filled
+    r = mixed_rgb_launch_plan(c, cplan, layout, c->d_aux.as<const uint8_t>(), const_cast<uint8_t *>(src), false, true);
+    if (!r) r = encode_mixed_launch_plan(c, bplan, c->d_aux.as<const uint8_t>(), host ? c->d_out.as<int16_t>() : coefs, !host && c->profiling);
+    if (r) {
+        (void)hipStreamSynchronize(c->stream);
+        return r;
+    }
+    if (!host) return HVC_OK;
+    for (int f = 0; f < n_frames; f++)
+        for (int i = 0; i < infos[f].n_comp; i++) {
+            const hvc_component &k = infos[f].layout[i];
+            const size_t n = (size_t)k.blocks_w * k.blocks_h * 64;
+            HIPCHK(c, hipMemcpyAsync(coefs + coef_offsets[f] + k.coef_offset, c->d_out.as<const int16_t>() + d_coef[(size_t)f] + k.coef_offset,
+                                     n * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+        }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HVC_OK;
 }

@@ -12,7 +12,8 @@
 //                        their RGB forms: hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed_rgb, and the
 //                        reduced-size forms hvc_decode_frames_mixed_scaled, hvc_jpeg_decode_batch_mixed_scaled, _scaled_rgb)
 //   hvc_capi_mixed_encode.hip  the same in the other direction: raw frames of different geometry, sampling and quality to records
-//                        and files (behind hvc_encode_frames_mixed, hvc_jpeg_encode_batch_mixed)
+//                        and files (behind hvc_encode_frames_mixed, hvc_jpeg_encode_batch_mixed), and the same from RGB images
+//                        (behind hvc_rgb_to_yuv_mixed, hvc_encode_frames_mixed_rgb, hvc_jpeg_encode_batch_mixed_rgb[_gpu])
 //   hvc_capi_mixed_coder.hip   the mixed GPU Huffman coder alone and the file pipeline built on it (behind
 //                        hvc_huffman_encode_frames_mixed, hvc_jpeg_encode_batch_mixed_gpu)
 //   hvc_capi_mixed_reader.hip  the mixed GPU Huffman reader's driver (hvc_mixed_reader.h) and hvc_jpeg_entropy_decode_gpu_mixed
@@ -185,6 +186,10 @@ struct hvc_ctx {
     size_t e_seg_bytes = 0, e_off_bytes = 0;
     Buf eh_specs[RING] = HVC_PINNED_RING; // ... and, with optimised tables, each frame's four specs
     size_t e_specs_bytes = 0;
+    // hvc_jpeg_encode_batch_mixed_rgb[_gpu]: the device slots the chunks' RGB images are uploaded into (eh_in holds them pinned,
+    // ed_in the planes k_rgb_to_ycc_mixed makes of them)
+    Buf ed_rgb[RING];
+    size_t e_rgb_bytes = 0;
     // hvc_jpeg_decode_batch_gpu: pinned / device rings of unstuffed segments and their index arrays
     Buf gp_h_ecs[RING] = HVC_UPLOAD_RING, gp_d_ecs[RING], gp_h_meta[RING] = HVC_PINNED_RING, gp_d_meta[RING];
     Buf gp_h_ftabs[RING] = HVC_UPLOAD_RING, gp_d_ftabs[RING]; // ... and of per-frame Huffman tables (hvc::HdFrameTabs, PF mode)
@@ -259,6 +264,7 @@ inline RingSet enc_seg_rings(hvc_ctx *c) { // hvc_jpeg_encode_batch_gpu: packed 
     return {{{&c->ed_seg, &c->e_seg_bytes, 0}, {&c->ed_off, &c->e_off_bytes, 0}, {&c->eh_off, &c->e_off_bytes, 0}}, 3, false};
 }
 inline RingSet enc_spec_rings(hvc_ctx *c) { return {{{&c->eh_specs, &c->e_specs_bytes, 0}}, 1, false}; }
+inline RingSet enc_rgb_rings(hvc_ctx *c) { return {{{&c->ed_rgb, &c->e_rgb_bytes, 0}}, 1, true}; } // RGB chunks of the mixed encode pipelines
 // A set grows when any member wants more than it has (`want`: bytes per member, in the set's order), and is then allocated
 // at the sizes wanted now.  HVC_OK, HVC_E_HIP (a stream did not drain) or HVC_E_OUT_OF_MEMORY.
 int ring_ensure(hvc_ctx *c, const RingSet &s, std::initializer_list<size_t> want);
@@ -591,8 +597,40 @@ int upload_image(hvc_ctx *c, PlanBuf &b, const std::vector<unsigned char> &img);
 // hvc_encode_frames_mixed and hvc_jpeg_encode_batch_mixed in hvc_capi_files.hip)
 int encode_frames_mixed_impl(hvc_ctx *c, const uint8_t *pixels, const size_t *pixel_offsets, const hvc_jpeg_info *infos, int n_frames,
                              int16_t *coefs, const size_t *coef_offsets, int where);
+// What frames[f] of a mixed encode batch is.  Default: a raw planar frame (tight Y, U, V).  rgb: an RGB image of `layout`
+// with rows rgb_row_strides[f] apart (nullptr, or an entry of 0: tight); the padding workers copy its rows tight into the
+// pinned ring, the chunk goes up into a device RGB slot and k_rgb_to_ycc_mixed writes the chunk's zeroed plane slot from it in
+// front of k_encode_mixed.  Chunks, records and everything behind the block stage are the same.
+struct MixedEncodeInput {
+    bool rgb = false;
+    int layout = 0;
+    const size_t *rgb_row_strides = nullptr;
+};
 int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
-                            size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats);
+                            size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats,
+                            const MixedEncodeInput &in = MixedEncodeInput());
+// the RGB input form's parts, shared by the two pipelines: the frame's own status (HVC_E_INVALID_ARG: an odd size under its
+// sampling, a row stride below the row), the bytes of its tight image, its rows into the pinned slot, and the chunk's colour
+// stage on c->stream -- the plane slot cleared (Plane.create is zero-filled), then k_rgb_to_ycc_mixed over the listed frames
+int encode_rgb_frame_status(const hvc_jpeg_info &info, const MixedEncodeInput &in, int f);
+size_t encode_rgb_frame_bytes(const hvc_jpeg_info &info, const MixedEncodeInput &in);
+void encode_rgb_frame_copy(const hvc_jpeg_info &info, const MixedEncodeInput &in, int f, const uint8_t *src, uint8_t *dst);
+int encode_rgb_stage(hvc_ctx *c, const MixedEncodeInput &in, const hvc_jpeg_info *infos, const int *list, int count, const size_t *pix_rel,
+                     const size_t *rgb_rel, const uint8_t *d_rgb, uint8_t *d_planes, size_t plane_bytes);
+// hvc_capi_mixed.hip, for both directions: the mixed colour pass of a plan on device memory, enqueued on c->stream (to_ycc:
+// k_rgb_to_ycc_mixed, d_rgb read and the planes at d_yuv written); where the records of a host-memory call go in device scratch
+namespace hvc {
+struct MixedRgbPlan;
+}
+int mixed_rgb_launch_plan(hvc_ctx *c, const hvc::MixedRgbPlan &plan, int layout, const uint8_t *d_yuv, uint8_t *d_rgb, bool profile,
+                          bool to_ycc = false);
+size_t stage_offsets(const size_t *offsets, const std::vector<size_t> &spans, std::vector<size_t> &d_off);
+// the colour pass alone / in front of the block stage (behind hvc_rgb_to_yuv_mixed in hvc_yuv.hip, hvc_encode_frames_mixed_rgb in
+// hvc_capi_files.hip)
+int rgb_to_yuv_mixed_impl(hvc_ctx *c, uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos, int n_frames, const uint8_t *rgb,
+                          const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where);
+int encode_frames_mixed_rgb_impl(hvc_ctx *c, const uint8_t *rgb, const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout,
+                                 const hvc_jpeg_info *infos, int n_frames, int16_t *coefs, const size_t *coef_offsets, int where);
 // hvc_capi_mixed_encode.hip, for the pipeline with the GPU coder: k_encode_mixed over a plan on device memory, enqueued on
 // c->stream; Plane.blit_available of a raw planar frame into its padded record; what a frame's records cover
 int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const uint8_t *d_pixels, int16_t *d_coefs, bool profile);
@@ -603,7 +641,8 @@ void encode_frame_spans(const hvc_jpeg_info &fi, size_t &pixel_span, size_t &coe
 int huffman_encode_frames_mixed_impl(hvc_ctx *c, const hvc_jpeg_info *infos, const int16_t *coefs, const size_t *coef_offsets, int n_frames,
                                      int tables, uint8_t *out, size_t out_cap, uint64_t *offsets, int *status, hvc_huff_spec *specs, int where);
 int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
-                                size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats);
+                                size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats,
+                                const MixedEncodeInput &in = MixedEncodeInput());
 // hvc_capi_mixed_reader.hip: the mixed GPU Huffman reader over one chunk on the calling thread (behind hvc_jpeg_entropy_decode_gpu_mixed
 // in hvc_capi_jpeg.hip)
 int entropy_decode_gpu_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, const hvc_jpeg_info *infos,

@@ -18,9 +18,9 @@
 // beyond nblk are not stored; an inactive lane computes the plane's last block and stores nothing.
 // LDS per workgroup: 32 KiB, as k_encode with HVC_TILE 256.  No scratch (profiles/mixed_encode_rocprofv3.txt).
 //
-// (The Huffman coder on the GPU for mixed sets is hvc_huff_mixed.hip, behind hvc_jpeg_encode_batch_mixed_gpu.)
+// (The Huffman coder on the GPU for mixed sets is hvc_huff_mixed.hip, behind hvc_jpeg_encode_batch_mixed_gpu; RGB input for
+// mixed sets is k_rgb_to_ycc_mixed, hvc_mixed_rgb.hip, in front of this block stage, behind hvc_jpeg_encode_batch_mixed_rgb.)
 // Out of scope, each a step of its own:
-//   - RGB input for mixed sets: a k_rgb_to_ycc_mixed in front of this block stage
 //   - the Hardcaml encode arithmetic (hvc_set_encode_arithmetic): the entry points return HVC_E_INVALID_ARG under it
 //   - monochrome files
 #include <hip/hip_runtime.h>

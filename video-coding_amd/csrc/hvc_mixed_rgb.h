@@ -1,5 +1,5 @@
-// hvc_mixed_rgb.h -- parameter block and launcher of the colour pass over a mixed batch (internal): k_ycc_to_rgb_mixed,
-// hvc_mixed_rgb.hip.  The tables come from hvc_mixed_rgb_plan.h, in device memory.
+// hvc_mixed_rgb.h -- parameter block and launcher of the colour pass over a mixed batch (internal): k_ycc_to_rgb_mixed and
+// k_rgb_to_ycc_mixed, hvc_mixed_rgb.hip.  The tables come from hvc_mixed_rgb_plan.h, in device memory.
 #ifndef HVC_MIXED_RGB_H
 #define HVC_MIXED_RGB_H
 
@@ -20,6 +20,8 @@ struct MixedRgbParams {
 
 // one launch over all units; k0 / k1 (optional) bracket it
 hipError_t launch_ycc_to_rgb_mixed(const MixedRgbParams &P, hipStream_t s, hipEvent_t k0 = nullptr, hipEvent_t k1 = nullptr);
+// the way back (k_rgb_to_ycc_mixed, tables from mixed_rgb_encode_plan_build): P.rgb is read, the planes at P.yuv are written
+hipError_t launch_rgb_to_ycc_mixed(const MixedRgbParams &P, hipStream_t s, hipEvent_t k0 = nullptr, hipEvent_t k1 = nullptr);
 
 } // namespace hvc
 #endif

@@ -1,7 +1,8 @@
 // hvc_mixed_rgb_plan.h -- the host plan of the colour pass over a MIXED batch (internal): images of different size and
 // sampling in one launch of k_ycc_to_rgb_mixed (hvc_mixed_rgb.hip).  Plain C++, no HIP: hvc_mixed_rgb_plan.cpp builds the two
 // tables the kernel reads from device memory, and the stand-alone program tests/host_harness/mixed_rgb_plan_harness.cpp runs
-// it under sanitizers.
+// it under sanitizers.  The way back, k_rgb_to_ycc_mixed, reads the same two tables: mixed_rgb_encode_plan_build below
+// (tests/host_harness/mixed_rgb_encode_plan_harness.cpp).
 //
 //   image descriptors  one per listed frame with width * height > 0, in list order
 //   work map           one image index per work unit; a unit = 64 consecutive LANES of ONE image = one wavefront, so that
@@ -68,6 +69,23 @@ int mixed_rgb_plan_build(const hvc_jpeg_info *infos, const size_t *yuv_offsets, 
                          MixedRgbPlan &plan, int n = 8);
 // (n = 4, 2, 1: infos[] are SCALED infos, their planes what the scaled block stage writes: a window must lie inside
 // n * blocks_w x n * blocks_h)
+
+// The same tables for the ENCODE direction, k_rgb_to_ycc_mixed: frame f's RGB image at rgb_offsets[f] is read, its planes at
+// yuv_offsets[f] + infos[f].layout[k].plane_offset are written.  A lane is what a lane of k_rgb_to_ycc is: ceil(w / 8) lanes
+// per lane row, h lane rows (4:2:0: h / 2 -- sizes are even here, not rounded up), chroma rows of w / 2 samples (4:4:4: w);
+// cw / ch of the descriptor hold that chroma size.  Arguments as mixed_rgb_plan_build.  HVC_E_INVALID_ARG for the whole
+// plan: an odd width under 4:2:0 / 4:2:2, an odd height under 4:2:0 (Yuv.assert_is_420 / _422), a sampling that is not one of
+// those three (grey among them), a stride below its row, samples outside a component that names its blocks, a negative size,
+// a bad layout; HVC_E_TOO_LARGE as there.  A frame without a pixel gets no descriptor.
+int mixed_rgb_encode_plan_build(const hvc_jpeg_info *infos, const size_t *yuv_offsets, const size_t *rgb_offsets,
+                                const size_t *rgb_row_strides, int layout, const int *frames, int n_list, uintptr_t yuv_addr,
+                                uintptr_t rgb_addr, MixedRgbPlan &plan);
+
+// hvc_jpeg_encoder_mixed_rgb_layout of include/hvc_jpeg.h
+int encoder_mixed_rgb_layout(const int *widths, const int *heights, const int *chromas, const int *qualities, int n_frames, int layout,
+                             size_t align, size_t row_align, hvc_jpeg_info *infos, int *status, size_t *rgb_offsets,
+                             size_t *rgb_row_strides, size_t *rgb_total, size_t *pixel_offsets, size_t *coef_offsets, size_t *pixel_total,
+                             size_t *coef_total);
 
 // hvc_jpeg_mixed_rgb_layout of include/hvc_jpeg.h
 int mixed_rgb_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, int layout, size_t align, size_t row_align,

@@ -1,5 +1,5 @@
 // hvc_rgb_dev.h -- device side of the RGB colour pass (internal): what k_ycc_to_rgb / k_rgb_to_ycc (hvc_rgb.hip, one geometry
-// per launch) and k_ycc_to_rgb_mixed (hvc_mixed_rgb.hip, geometry per wavefront from device memory) share.  The definition of
+// per launch) and k_ycc_to_rgb_mixed / k_rgb_to_ycc_mixed (hvc_mixed_rgb.hip, geometry per wavefront from device memory) share.  The definition of
 // every byte is the one at the top of hvc_rgb.hip.  Everything here has internal linkage: include it in a .hip file only.
 #ifndef HVC_RGB_DEV_H
 #define HVC_RGB_DEV_H
@@ -213,6 +213,54 @@ __device__ __forceinline__ void load_rgb(const RgbOp &P, const uint8_t *frame, i
             } \
             store_rgb<PLANAR>((P), frame, row, x0, (P).vec_rgb && full, r, gg, b); \
         } \
+    } while (0)
+
+// One lane of RGB -> planes, the way back, spelled inline in its kernel for the same reason: columns 8 g .. 8 g + 7 of lane row
+// lr of frame f of P.  w is even for 4:2:2 and 4:2:0, h even for 4:2:0 (the launch / the plan checks), so a lane row of 4:2:0
+// is two whole image rows and a lane's 8 columns give 4 chroma samples of a row of w / 2.
+#define HVC_RGB_LANE_TO_YCC(P, f, lr, g) \
+    do { \
+        constexpr int ROWS = S == 420 ? 2 : 1; \
+        const int x0 = (int)(8 * (g)); \
+        const bool full = x0 + 8 <= (P).w; \
+        const uint8_t *frame = (P).rgb + (f) * (P).frame_stride; \
+        unsigned cb[ROWS][2], cr[ROWS][2]; \
+        _Pragma("unroll") for (int rr = 0; rr < ROWS; rr++) { \
+            const int row = (int)(lr) * ROWS + rr; \
+            unsigned r[2], gg[2], b[2], y[2]; \
+            load_rgb<PLANAR>((P), frame, row, x0, (P).vec_rgb && full, r, gg, b); \
+            rgb4_to_ycc(r[0], gg[0], b[0], y[0], cb[rr][0], cr[rr][0]); \
+            rgb4_to_ycc(r[1], gg[1], b[1], y[1], cb[rr][1], cr[rr][1]); \
+            store8((P).y + (f) * (P).yuv_fs + (size_t)row * (P).y_stride, x0, (P).w, (P).vec_y && full, y[0], y[1]); \
+        } \
+        if (S == 400) break; \
+        uint8_t *pcb = (P).cb + (f) * (P).yuv_fs + (size_t)(lr) * (P).cb_stride, *pcr = (P).cr + (f) * (P).yuv_fs + (size_t)(lr) * (P).cr_stride; \
+        if (S == 444) { \
+            store8(pcb, x0, (P).w, (P).vec_c && full, cb[0][0], cb[0][1]); \
+            store8(pcr, x0, (P).w, (P).vec_c && full, cr[0][0], cr[0][1]); \
+            break; \
+        } \
+        unsigned ob, orr; \
+        if (S == 422) { /* subsample_h2: avg2 of the pair */ \
+            ob = pack_even(((pairsum(cb[0][0]) + 0x00010001u) >> 1) & 0x00ff00ffu, ((pairsum(cb[0][1]) + 0x00010001u) >> 1) & 0x00ff00ffu); \
+            orr = pack_even(((pairsum(cr[0][0]) + 0x00010001u) >> 1) & 0x00ff00ffu, ((pairsum(cr[0][1]) + 0x00010001u) >> 1) & 0x00ff00ffu); \
+        } else { /* subsample_hv2: avg4 of the 2 x 2 */ \
+            ob = pack_even(((pairsum(cb[0][0]) + pairsum(cb[ROWS - 1][0]) + 0x00020002u) >> 2) & 0x00ff00ffu, \
+                           ((pairsum(cb[0][1]) + pairsum(cb[ROWS - 1][1]) + 0x00020002u) >> 2) & 0x00ff00ffu); \
+            orr = pack_even(((pairsum(cr[0][0]) + pairsum(cr[ROWS - 1][0]) + 0x00020002u) >> 2) & 0x00ff00ffu, \
+                            ((pairsum(cr[0][1]) + pairsum(cr[ROWS - 1][1]) + 0x00020002u) >> 2) & 0x00ff00ffu); \
+        } \
+        const int c0 = (int)(4 * (g)), cw = (P).w >> 1; \
+        if ((P).vec_c && full) { \
+            __builtin_nontemporal_store(ob, reinterpret_cast<unsigned *>(pcb + c0)); \
+            __builtin_nontemporal_store(orr, reinterpret_cast<unsigned *>(pcr + c0)); \
+            break; \
+        } \
+        _Pragma("unroll") for (int i = 0; i < 4; i++) \
+            if (c0 + i < cw) { \
+                pcb[c0 + i] = (uint8_t)((ob >> (8 * i)) & 0xffu); \
+                pcr[c0 + i] = (uint8_t)((orr >> (8 * i)) & 0xffu); \
+            } \
     } while (0)
 
 } // namespace

@@ -673,4 +673,10 @@ int hvc_rgb_to_yuv(hvc_ctx *c, const uint8_t *rgb, size_t rgb_row_stride, size_t
     return HVC_OK;
 } HVC_ABI_CATCH
 
+// the same over images of different size and sampling in one launch (k_rgb_to_ycc_mixed): hvc_capi_mixed_encode.hip
+int hvc_rgb_to_yuv_mixed(hvc_ctx *c, uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos, int n_frames, const uint8_t *rgb,
+                         const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where) try {
+    return rgb_to_yuv_mixed_impl(c, yuv, yuv_offsets, infos, n_frames, rgb, rgb_offsets, rgb_row_strides, layout, where);
+} HVC_ABI_CATCH
+
 } // extern "C"

@@ -45,6 +45,8 @@ SYMBOLS = [
     "hvc_jpeg_mixed_scaled_rgb_layout", "hvc_jpeg_decode_batch_mixed_scaled_rgb",
     "hvc_jpeg_encoder_mixed_layout", "hvc_encode_frames_mixed", "hvc_jpeg_encode_batch_mixed",
     "hvc_huffman_encode_frames_mixed", "hvc_jpeg_encode_batch_mixed_gpu", "hvc_last_mixed_coder_files",
+    "hvc_jpeg_encoder_mixed_rgb_layout", "hvc_rgb_to_yuv_mixed", "hvc_encode_frames_mixed_rgb", "hvc_jpeg_encode_batch_mixed_rgb",
+    "hvc_jpeg_encode_batch_mixed_rgb_gpu",
 ]
 HVC_RGB = {"interleaved": 0, "planar": 1}  # enum hvc_rgb_layout: [H, W, 3] / [3, H, W]
 HVC_YUV_400 = 400   # luma only, beside 420 / 422 / 444
@@ -294,6 +296,14 @@ def lib():
                                                   C.POINTER(sz), C.POINTER(BatchStats)]
         L.hvc_huffman_encode_frames_mixed.argtypes = [vp, ip, vp, C.POINTER(sz), i, i, vp, sz, vp, C.POINTER(i), hs, i]
         L.hvc_jpeg_encode_batch_mixed_gpu.argtypes = L.hvc_jpeg_encode_batch_mixed.argtypes
+        L.hvc_jpeg_encoder_mixed_rgb_layout.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, i, sz, sz, ip,
+                                                        C.POINTER(i), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
+                                                        C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+        L.hvc_rgb_to_yuv_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), C.POINTER(sz), i, i]
+        L.hvc_encode_frames_mixed_rgb.argtypes = [vp, vp, C.POINTER(sz), C.POINTER(sz), i, ip, i, vp, C.POINTER(sz), i]
+        L.hvc_jpeg_encode_batch_mixed_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, ip, C.POINTER(i), i, i, sz, C.POINTER(vp),
+                                                      C.POINTER(sz), C.POINTER(sz), C.POINTER(BatchStats)]
+        L.hvc_jpeg_encode_batch_mixed_rgb_gpu.argtypes = L.hvc_jpeg_encode_batch_mixed_rgb.argtypes
         L.hvc_last_mixed_coder_files.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.hvc_checksum_records.argtypes = [vp, vp, sz, sz, i, vp, i]
         L.hvc_set_host_cpus.argtypes = [vp, C.c_char_p]
@@ -818,6 +828,37 @@ def jpeg_encoder_mixed_layout(frames, align=0):
     return EncoderMixedLayout(frames, align)
 
 
+class EncoderMixedRgbLayout(EncoderMixedLayout):
+    """what hvc_jpeg_encoder_mixed_rgb_layout makes of a list of (width, height, chroma, quality): EncoderMixedLayout's members
+    (status with the even-size rule of hvc_jpeg_encode_rgb on top), and where every good frame's RGB image goes: rgb_offsets,
+    rgb_row_strides, total_bytes (rgb_total), for one `layout` ("interleaved" / "planar")"""
+
+    def __init__(self, frames, layout="interleaved", align=0, row_align=0):
+        n = len(frames)
+        m = max(n, 1)
+        col = lambda k: (C.c_int * m)(*[int(f[k]) for f in frames])
+        self.n = n
+        self.layout = _rgb_layout(layout)
+        self.infos = (JpegInfo * m)()
+        self.status = (C.c_int * m)()
+        self.rgb_offsets = (C.c_size_t * m)()
+        self.rgb_row_strides = (C.c_size_t * m)()
+        self.pixel_offsets = (C.c_size_t * m)()
+        self.coef_offsets = (C.c_size_t * m)()
+        rt, pt, ct = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _chk(lib().hvc_jpeg_encoder_mixed_rgb_layout(col(0), col(1), col(2), col(3), n, self.layout, align, row_align, self.infos,
+                                                     self.status, self.rgb_offsets, self.rgb_row_strides, C.byref(rt),
+                                                     self.pixel_offsets, self.coef_offsets, C.byref(pt), C.byref(ct)),
+             "hvc_jpeg_encoder_mixed_rgb_layout")
+        self.total_bytes = self.rgb_total = rt.value
+        self.pixel_total, self.coef_total = pt.value, ct.value
+
+
+def jpeg_encoder_mixed_rgb_layout(frames, layout="interleaved", align=0, row_align=0):
+    """frames: (width, height, chroma, quality) each -> EncoderMixedRgbLayout"""
+    return EncoderMixedRgbLayout(frames, layout, align, row_align)
+
+
 def encoder_pixel_record(info, y, u, v, width, height, chroma):
     """the padded pixel record hvc_jpeg_encode hands its block stage (Plane.blit_available of the frame's planes into
     zero-filled planes of jpeg_encoder_layout's geometry, encoder.ml:514-516) -> uint8 array of info.pixel_bytes"""
@@ -1218,6 +1259,32 @@ class Context:
         arr = infos if isinstance(infos, C.Array) else (JpegInfo * n)(*infos)
         _chk(lib().hvc_yuv_to_rgb_mixed(self._h, ya, _size_array(yuv_offsets, n), arr, n, ra, _size_array(rgb_offsets, n),
                                         _size_array(rgb_row_strides, n), _rgb_layout(layout), w1), "hvc_yuv_to_rgb_mixed")
+
+    def rgb_to_yuv_mixed(self, yuv, yuv_offsets, infos, rgb, rgb_offsets, rgb_row_strides=None, layout="interleaved"):
+        """hvc_rgb_to_yuv_mixed: the way back of yuv_to_rgb_mixed, argument for argument: frame f's image at rgb[rgb_offsets[f]:]
+        is read, its planes at yuv[yuv_offsets[f]:] (laid out by infos[f].layout) are written -- the frame's own samples only.
+        Sizes are even where the sampling asks for it (hvc_rgb_to_yuv's rule)."""
+        ya, w1 = _addr(yuv)
+        ra, w2 = _addr(rgb)
+        assert w1 == w2, "yuv and rgb must live in the same memory space"
+        n = len(infos)
+        arr = infos if isinstance(infos, C.Array) else (JpegInfo * max(n, 1))(*infos)
+        _chk(lib().hvc_rgb_to_yuv_mixed(self._h, ya, _size_array(yuv_offsets, n), arr, n, ra, _size_array(rgb_offsets, n),
+                                        _size_array(rgb_row_strides, n), _rgb_layout(layout), w1), "hvc_rgb_to_yuv_mixed")
+
+    def encode_frames_mixed_rgb(self, rgb, rgb_offsets, infos, coefs, coef_offsets, rgb_row_strides=None, layout="interleaved"):
+        """hvc_encode_frames_mixed_rgb: frame f = infos[f] (JpegInfo), its RGB image at rgb[rgb_offsets[f]:] (bytes, rows
+        rgb_row_strides[f] apart, None: tight), its coefficient record written at coefs[coef_offsets[f]:] (int16 elements): the
+        mixed colour pass into zeroed padded planes in context scratch, then the mixed block stage.  rgb / coefs: numpy (host)
+        or torch cuda tensors, both in the same memory space."""
+        ra, w1 = _addr(rgb)
+        ca, w2 = _addr(coefs)
+        assert w1 == w2, "rgb and coefs must live in the same memory space"
+        n = len(infos)
+        arr = infos if isinstance(infos, C.Array) else (JpegInfo * max(n, 1))(*infos)
+        _chk(lib().hvc_encode_frames_mixed_rgb(self._h, ra, _size_array(rgb_offsets, n), _size_array(rgb_row_strides, n),
+                                               _rgb_layout(layout), arr, n, ca, _size_array(coef_offsets, n), w1),
+             "hvc_encode_frames_mixed_rgb")
 
     def decode_frames_mixed_rgb(self, coefs, coef_offsets, infos, rgb, rgb_offsets, rgb_row_strides=None, layout="interleaved"):
         """hvc_decode_frames_mixed_rgb: hvc_decode_frames_mixed into context scratch, then the mixed colour pass; arguments as
@@ -1766,6 +1833,47 @@ class Context:
         st = BatchStats()
         name = {"host": "hvc_jpeg_encode_batch_mixed", "gpu": "hvc_jpeg_encode_batch_mixed_gpu"}[coder]
         _chk(getattr(lib(), name)(self._h, fp, lay.infos, status, n, threads, chunk_bytes, op, cp, sizes, C.byref(st)), name)
+        self.last_batch_stats = st
+        return [(status[f], outs[f][:sizes[f]].tobytes() if status[f] == 0 else None, sizes[f]) for f in range(n)]
+
+    def jpeg_encode_batch_mixed_rgb(self, images, specs=None, threads=8, chunk_bytes=0, layout="interleaved", rgb_row_strides=None,
+                                    enc_layout=None, caps=None, outs=None, coder="host"):
+        """hvc_jpeg_encode_batch_mixed_rgb (coder="gpu": hvc_jpeg_encode_batch_mixed_rgb_gpu): RGB images (uint8 arrays, [H, W, 3]
+        interleaved or [3, H, W] planar, or flat bytes; rows rgb_row_strides[f] bytes apart, None: tight) of any sizes,
+        samplings and qualities -> files, in one call.  specs: (width, height, chroma, quality) per image, or enc_layout: an
+        EncoderMixedLayout / EncoderMixedRgbLayout made before.  Results, caps and outs as jpeg_encode_batch_mixed; every file
+        equals jpeg_encode_rgb's for that image alone."""
+        lay = enc_layout if enc_layout is not None else EncoderMixedRgbLayout(specs, layout)
+        n = len(lay)
+        m = max(n, 1)
+        code = _rgb_layout(layout)
+        arrs = [np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray)) else
+                np.ascontiguousarray(f, dtype=np.uint8).reshape(-1) for f in images]
+        assert len(arrs) == n
+        for f, a in enumerate(arrs):
+            if lay.status[f] == 0:
+                w, h = lay.infos[f].width, lay.infos[f].height
+                tight = w if code == 1 else 3 * w
+                rows = 3 * h if code == 1 else h
+                rs = (rgb_row_strides[f] if rgb_row_strides is not None else 0) or tight
+                if rs >= tight and a.size < (rows - 1) * rs + tight:
+                    raise ValueError("image %d shorter than %d bytes" % (f, (rows - 1) * rs + tight))
+        if outs is None:
+            ri = self.restart_interval
+            outs = [np.empty(8, dtype=np.uint8) if lay.status[f] else
+                    np.empty(4 * lay.infos[f].width * lay.infos[f].height + 65536 + restart_slack(lay.infos[f], ri), dtype=np.uint8)
+                    for f in range(n)]
+        if caps is None:
+            caps = [o.size for o in outs]
+        fp = (C.c_void_p * m)(*[a.ctypes.data for a in arrs])
+        op = (C.c_void_p * m)(*[o.ctypes.data for o in outs])
+        cp = (C.c_size_t * m)(*[int(x) for x in caps])
+        sizes = (C.c_size_t * m)()
+        status = (C.c_int * m)(*lay.status)
+        st = BatchStats()
+        name = {"host": "hvc_jpeg_encode_batch_mixed_rgb", "gpu": "hvc_jpeg_encode_batch_mixed_rgb_gpu"}[coder]
+        _chk(getattr(lib(), name)(self._h, fp, _size_array(rgb_row_strides, n), code, lay.infos, status, n, threads, chunk_bytes, op, cp,
+                                  sizes, C.byref(st)), name)
         self.last_batch_stats = st
         return [(status[f], outs[f][:sizes[f]].tobytes() if status[f] == 0 else None, sizes[f]) for f in range(n)]
 
