@@ -1108,6 +1108,65 @@ HVC_API int hvc_jpeg_encode_batch_mixed_rgb_gpu(hvc_ctx *ctx, const uint8_t *con
                                                 size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes,
                                                 hvc_batch_stats *stats);
 
+/* ------------------------------------------------------------------------- */
+/* Resizing: the step that takes the images of a mixed batch -- each of its own size -- to the size the caller names, usually one
+ * W x H for all, written as a uniform [n, H, W, 3] or [n, 3, H, W] tensor.  An extension with a named definition (the
+ * reference has no resampler): Pillow's Image.resize on 8-bit images, bit for bit, for the filters below; in numpy:
+ * tools/resize_reference.py.  Hamming and Lanczos are left out on purpose: they need cos / sin, whose last bit differs
+ * between C libraries, so their tables could not be held equal across numpy, the host C++ and Pillow.
+ *
+ * Filters f with support s:
+ *   box       s = 0.5   1 for -0.5 < x <= 0.5, else 0
+ *   bilinear  s = 1     1 - |x| for |x| < 1, else 0
+ *   bicubic   s = 2     a = -0.5: ((a + 2) |x| - (a + 3)) x^2 + 1 for |x| < 1, (((|x| - 5) |x| + 8) |x| - 4) a for |x| < 2, else 0
+ * The coefficients of one axis n_in -> n_out, in IEEE double, one rounding per operation, in exactly this order:
+ *   scale = n_in / n_out, fs = max(scale, 1.0), support = s * fs, ss = 1.0 / fs; for each output position xx:
+ *   center = (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), n_in),
+ *   count = xmax - xmin, w[i] = f((i + xmin - center + 0.5) * ss) for i < count, ww = the sum of w in index order, w[i] /= ww if
+ *   ww != 0, and the integer tap k[i] = (int)(w[i] * 4194304 + 0.5) for w[i] >= 0, (int)(w[i] * 4194304 - 0.5) otherwise ((int)
+ *   truncates towards zero; 22 bits).
+ * A pass computes, per output sample and channel, clip_0_255((2097152 + SUM k[i] * in[xmin + i]) >> 22) with an arithmetic
+ * shift and writes 8-bit samples.  The horizontal pass runs first, to an 8-bit intermediate of n_out_w x h_in; the vertical
+ * pass runs over that.  An axis with n_out == n_in is skipped (both: the image is copied).
+ *
+ * Bounds: a side of at most 2^24; at most HVC_RESIZE_MAX_TAPS = 2048 taps per output position of an axis (an 8192 -> 1 bicubic
+ * axis would have 8192); the tables of one call (one per distinct (n_in, n_out, filter): max count * n_out words each) at most
+ * 2^24 words together; every output position must satisfy 255 * SUM |k| + 2^21 < 2^31 and |k| < 2^23 (the kernels' int32
+ * accumulator and 24-bit multiply -- over sizes 1 .. 8192 to 1 .. 1000 the largest SUM |k| is 1.269 * 2^22, bicubic 69 -> 64,
+ * but the plan checks rather than trusts that); out_w * h * out_w < 2^32.  Beyond any of them: HVC_E_TOO_LARGE.
+ *
+ * hvc_rgb_resize_mixed: image i is widths[i] x heights[i] at src + src_offsets[i], rows src_row_strides[i] apart, and goes to
+ *   out_widths[i] x out_heights[i] at dst + dst_offsets[i], rows dst_row_strides[i] apart (a stride array of NULL, or an entry
+ *   of 0: tight rows; planar planes lie row stride * height apart, on both sides).  One `layout` (hvc_rgb_layout) and one
+ *   `filter` per call; src and dst both live where `where` says.  A uniform tensor is the case of equal output sizes and
+ *   dst_offsets[i] = i * frame_stride.  Under k_ycc_to_rgb_mixed's decomposition (csrc/hvc_resize.hip): one launch of
+ *   k_resize_h_mixed and one of k_resize_v_mixed per call, a pass no image needs launches nothing; the intermediate lives in
+ *   context scratch.  HVC_MEM_DEVICE: enqueued on ctx's stream, returns at once, honours hvc_set_profiling (the pair brackets
+ *   both passes); HVC_MEM_HOST: staged through context scratch, the call blocks, only the rows written are downloaded.  Bytes
+ *   between rows and between records are never written.  Does not depend on hvc_set_arithmetic.  HVC_E_INVALID_ARG: a size
+ *   below 1, a stride below the row, an unknown filter or layout; HVC_E_TOO_LARGE: the bounds above; either way for the whole
+ *   call, output untouched.
+ * hvc_jpeg_decode_batch_mixed_resized: hvc_jpeg_decode_batch_mixed_scaled_rgb's pipeline (any scale_denom, both readers, chunks,
+ *   per-file statuses, HVC_E_RANGE and restart markers as there) ending in the two passes: per chunk the block stage, then
+ *   k_ycc_to_rgb_mixed into a device RGB ring slot, then the passes into the output, so the images at decoded size never leave
+ *   the GPU.  infos / status: as hvc_jpeg_mixed_layout or any of its kin made them (full-size infos).  File f's image --
+ *   its decoded size at 1 / scale_denom -- goes to out_widths[f] x out_heights[f] at dst + dst_offsets[f], rows
+ *   dst_row_strides[f] apart (NULL or 0: tight).  A file whose resize is beyond the bounds gets HVC_E_TOO_LARGE (a size below 1
+ *   or a stride below the row: HVC_E_INVALID_ARG) as ITS status, and stops nobody; a file that fails leaves its record in dst
+ *   untouched.  dst_cap: every good file's record must lie inside (HVC_E_INVALID_ARG).  An unknown filter or layout, and
+ *   HVC_ARITH_HARDCAML / _LIBJPEG as the arithmetic: HVC_E_INVALID_ARG for the call, output untouched. */
+typedef enum { HVC_RESIZE_BOX = 0, HVC_RESIZE_BILINEAR = 1, HVC_RESIZE_BICUBIC = 2 } hvc_resize_filter;
+#define HVC_RESIZE_MAX_TAPS 2048
+HVC_API int hvc_rgb_resize_mixed(hvc_ctx *ctx, const uint8_t *src, const size_t *src_offsets, const size_t *src_row_strides,
+                                 const int *widths, const int *heights, int n_images, uint8_t *dst, const size_t *dst_offsets,
+                                 const size_t *dst_row_strides, const int *out_widths, const int *out_heights, int layout,
+                                 int filter, int where);
+HVC_API int hvc_jpeg_decode_batch_mixed_resized(hvc_ctx *ctx, const uint8_t *const *jpegs, const size_t *sizes, int n_files,
+                                                int threads, size_t chunk_bytes, int scale_denom, const hvc_jpeg_info *infos,
+                                                int *status, const int *out_widths, const int *out_heights,
+                                                const size_t *dst_offsets, const size_t *dst_row_strides, uint8_t *dst,
+                                                size_t dst_cap, int layout, int filter, int where, hvc_batch_stats *stats);
+
 /* K5 (no counterpart in the reference): what a benchmark or a pipeline produced, said in
  * 64 bits per record without bringing the records back.  For r < n_records
  *     sums[r] = SUM_i (byte_i + 1) * ((2 i + 1) * 0x9E3779B97F4A7C15)   mod 2^64,  i = byte index in record r

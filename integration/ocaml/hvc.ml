@@ -940,6 +940,29 @@ let jpeg_decode_batch_mixed_scaled_rgb =
     @-> ptr size_t @-> ptr char @-> size_t @-> int @-> int @-> ptr Batch_stats.t @-> returning int)
 ;;
 
+(* resizing a mixed set (bit-exact to Pillow's Image.resize; filter: 0 box, 1 bilinear, 2 bicubic).
+   int hvc_rgb_resize_mixed(ctx, src, src_offsets, src_row_strides, widths, heights, n_images, dst, dst_offsets,
+                            dst_row_strides, out_widths, out_heights, layout, filter, where) *)
+let rgb_resize_mixed =
+  foreign
+    "hvc_rgb_resize_mixed"
+    ~release_runtime_lock:true
+    (ctx @-> ptr char @-> ptr size_t @-> ptr size_t @-> ptr int @-> ptr int @-> int @-> ptr char @-> ptr size_t
+    @-> ptr size_t @-> ptr int @-> ptr int @-> int @-> int @-> int @-> returning int)
+;;
+
+(* int hvc_jpeg_decode_batch_mixed_resized(ctx, jpegs, sizes, n_files, threads, chunk_bytes, scale_denom, infos, status,
+                                           out_widths, out_heights, dst_offsets, dst_row_strides, dst, dst_cap, layout,
+                                           filter, where, stats) *)
+let jpeg_decode_batch_mixed_resized =
+  foreign
+    "hvc_jpeg_decode_batch_mixed_resized"
+    ~release_runtime_lock:true
+    (ctx @-> ptr string @-> ptr size_t @-> int @-> int @-> size_t @-> int @-> ptr Jpeg_info.t @-> ptr int @-> ptr int
+    @-> ptr int @-> ptr size_t @-> ptr size_t @-> ptr char @-> size_t @-> int @-> int @-> int @-> ptr Batch_stats.t
+    @-> returning int)
+;;
+
 (* mixed batches, encoding: frames of different sizes, samplings and qualities in one call.
    int hvc_jpeg_encoder_mixed_layout(widths, heights, chromas, qualities, n_frames, align, infos, status, pixel_offsets,
                                      coef_offsets, pixel_total, coef_total)                                     host only *)

@@ -20,6 +20,9 @@
                                                       -rgb (hvc_jpeg_decode_batch_mixed_rgb): OUT_DIR/<name>.ppm as `decode frame -rgb`
                                                       -scale (hvc_jpeg_decode_batch_mixed_scaled / _scaled_rgb): either as
                                                       `decode frame -scale` writes it
+    python -m video_coding_amd model decode frames OUT_DIR IN1.jpg ... -rgb -resize WxH [-filter box|bilinear|bicubic] [-scale N] [-reader gpu|host]
+                                                      every image resized to W x H on the GPU, bit-exact to Pillow's
+                                                      Image.resize (hvc_jpeg_decode_batch_mixed_resized): OUT_DIR/<name>.ppm
                                                       (an extension: JFIF colour conversion, hvc_jpeg_decode_rgb / _encode_rgb)
     python -m video_coding_amd oyuv compare {max-difference,mean-difference,mean-square-error,psnr}
                                             {y,u,v,yuv} FILE-1 FILE-2 WxH [-format 420]
@@ -145,7 +148,12 @@ def model_decode_frames_rgb(a, datas):
         if a.restart_markers:
             ctx.set_restart_markers(True)
         ctx.set_mixed_reader(a.reader)
-        if a.scale == 1:
+        if a.resize is not None:
+            # decoded (at 1 / -scale), converted and resized on the GPU in one hvc_jpeg_decode_batch_mixed_resized call
+            status, tensor = ctx.jpeg_decode_batch_mixed_resized(datas, size=a.resize, filter=a.filter, scale_denom=a.scale, threads=a.threads)
+            size = type("Size", (), dict(width=a.resize[0], height=a.resize[1]))
+            results = [(status[f], size, tensor[f]) for f in range(len(datas))]
+        elif a.scale == 1:
             results = ctx.jpeg_decode_batch_mixed_rgb(datas, threads=a.threads)
         else:
             results = ctx.jpeg_decode_batch_mixed_scaled_rgb(datas, a.scale, threads=a.threads)
@@ -171,6 +179,10 @@ def model_decode_frames(a):
     still written; the exit status says whether any failed"""
     import os
     datas = [open(p, "rb").read() for p in a.bits]
+    if a.resize is not None and not a.rgb:
+        raise SystemExit("-resize takes RGB images: give -rgb with it")
+    if a.resize is not None and (a.resize[0] < 1 or a.resize[1] < 1):
+        raise SystemExit("-resize WxH: sizes start at 1")
     if a.rgb:
         return model_decode_frames_rgb(a, datas)
     lay = hvc.jpeg_mixed_layout(datas) if a.scale == 1 else hvc.jpeg_mixed_scaled_layout(datas, a.scale)
@@ -548,6 +560,10 @@ def parser():
                    help="who reads the files' Huffman data (hvc_set_mixed_reader): host threads, or the mixed GPU reader; same files either way")
     p.add_argument("-scale", type=int, default=1, choices=[1, 2, 4, 8],
                    help="decode the set at 1/2, 1/4 or 1/8 size (hvc_jpeg_decode_batch_mixed_scaled / _scaled_rgb)")
+    p.add_argument("-resize", type=size_arg, default=None, metavar="WxH",
+                   help="with -rgb: every image resized to W x H on the GPU, bit-exact to Pillow's Image.resize "
+                        "(hvc_jpeg_decode_batch_mixed_resized; -scale: the cheap pre-shrink in front of it)")
+    p.add_argument("-filter", choices=["box", "bilinear", "bicubic"], default="bilinear", help="the filter of -resize")
     p.set_defaults(fn=model_decode_frames)
     enc = model.add_parser("encode").add_subparsers(dest="what", required=True)
     p = enc.add_parser("frame")

@@ -10,6 +10,7 @@
 #include "hvc_mixed.h"
 #include "hvc_mixed_rgb.h"
 #include "hvc_mixed_reader.h"
+#include "hvc_resize_plan.h"
 
 namespace {
 
@@ -385,6 +386,9 @@ int decode_frames_mixed_rgb_impl(hvc_ctx *c, const int16_t *coefs, const size_t 
 // form.rgb(): a file's record in `pixels` is its RGB image; the chunk's planes go to a device slot of their own ring and
 // k_ycc_to_rgb_mixed follows k_decode_mixed on the compute stream.  form.scale_denom = 2, 4, 8: the same pipeline with the
 // scaled infos describing every output and k_decode_mixed_scaled as the block stage; full-size planes exist nowhere.
+// form.resized(): a file's record in `pixels` is its image taken to the size the caller names; the colour pass writes the
+// chunk's images, tight, into a device slot of the RGB ring and the two resampling passes (hvc_capi_resize.hip) follow it on
+// the compute stream, through a slot of the intermediates' ring, into where the images would have gone.
 // hvc_set_mixed_reader(HVC_READER_GPU) (and not host_reader_only): the workers only unstuff the files' segments into the pinned
 // reader ring (MixedGpuReader::prepare), the copy stream uploads them with the chunk's descriptors and table records, and the
 // mixed GPU Huffman reader writes the coefficient records into d_ring[slot] in front of the block stage, which runs over the
@@ -412,6 +416,11 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
             if (status[f] == HVC_OK && infos[f].n_comp >= 0 && infos[f].n_comp <= 4) scaled_info(infos[f], N, scaled[(size_t)f]);
     }
     const hvc_jpeg_info *const oinfos = N != 8 ? scaled.data() : infos;
+    // the size of a file's record in `pixels`: its image's, or (resized) the size the caller names for it
+    auto out_w = [&](int f) { return form.resized() ? form.out_widths[f] : oinfos[f].width; };
+    auto out_h = [&](int f) { return form.resized() ? form.out_heights[f] : oinfos[f].height; };
+    if (form.resized() && (!form.out_heights || (form.filter != HVC_RESIZE_BOX && form.filter != HVC_RESIZE_BILINEAR && form.filter != HVC_RESIZE_BICUBIC)))
+        return HVC_E_INVALID_ARG;
     if (chunk_bytes == 0) chunk_bytes = (size_t)64 << 20;
     if (threads < 1) threads = 1;
     if (threads > 256) threads = 256;
@@ -423,7 +432,10 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
         size_t coef_bytes = 0;
         size_t pix_lo = 0, pix_hi = 0; // the bytes of `pixels` its files cover
         size_t plane_bytes = 0;        // (RGB form) its files' padded planes, each on 64 bytes
+        size_t rgb_bytes = 0, mid_bytes = 0; // (resized form) its files' tight RGB images at decoded size and the passes' intermediates
     };
+    std::vector<hvc::ResizeImage> rimg(form.resized() ? (size_t)n_files : 0); // (resized form) file f's image in its chunk's RGB slot, and where it goes
+    std::vector<size_t> rgb_rel(form.resized() ? (size_t)n_files : 0, 0);
     std::vector<int> take;
     std::vector<Chunk> chunks;
     std::vector<size_t> coef_rel((size_t)n_files, 0), pix_rel((size_t)n_files, 0);
@@ -442,10 +454,19 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
                 continue;
             }
             if (oi.width < 0 || oi.height < 0) return HVC_E_INVALID_ARG;
-            const size_t tight = hvc::mixed_rgb_row_bytes(form.layout, oi.width);
+            if (form.resized()) { // whether its image can be taken to its size is the file's own result too
+                const int rr = hvc::resize_image_status(oi.width, oi.height, form.out_widths[f], form.out_heights[f], form.filter);
+                const size_t otight = rr ? 0 : hvc::mixed_rgb_row_bytes(form.layout, form.out_widths[f]);
+                const bool narrow = !rr && form.rgb_row_strides && form.rgb_row_strides[f] && form.rgb_row_strides[f] < otight;
+                if (rr || narrow) {
+                    status[f] = rr ? rr : (int)HVC_E_INVALID_ARG;
+                    continue;
+                }
+            }
+            const size_t tight = hvc::mixed_rgb_row_bytes(form.layout, out_w(f));
             const size_t rs = form.rgb_row_strides && form.rgb_row_strides[f] ? form.rgb_row_strides[f] : tight;
             if (rs < tight) return HVC_E_INVALID_ARG;
-            ob = hvc::mixed_rgb_span(form.layout, oi.width, oi.height, rs);
+            ob = hvc::mixed_rgb_span(form.layout, out_w(f), out_h(f), rs);
         } else {
             ob = oi.pixel_bytes;
             if (N == 8 && ob && (pixel_offsets[f] & 7)) return HVC_E_ALIGNMENT; // (scaled planes: any offset)
@@ -471,6 +492,16 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
             plane_rel[(size_t)f] = k.plane_bytes;
             k.plane_bytes += (oinfos[f].pixel_bytes + 63) & ~(size_t)63;
         }
+        if (form.resized()) {
+            hvc::ResizeImage &im = rimg[(size_t)f];
+            im.w = oi.width, im.h = oi.height, im.out_w = out_w(f), im.out_h = out_h(f);
+            im.src_offset = rgb_rel[(size_t)f] = k.rgb_bytes, im.src_row_stride = 0;
+            im.dst_row_stride = form.rgb_row_strides ? form.rgb_row_strides[f] : 0;
+            const size_t planes = form.layout == HVC_RGB_PLANAR ? 3 : 1;
+            k.rgb_bytes += (hvc::mixed_rgb_span(form.layout, oi.width, oi.height, hvc::mixed_rgb_row_bytes(form.layout, oi.width)) + 63) & ~(size_t)63;
+            // (an upper bound of what resize_plan_build gives it: rows on 4 bytes, the image on 64)
+            k.mid_bytes += 64 + ((hvc::mixed_rgb_row_bytes(form.layout, im.out_w) + 3) & ~(size_t)3) * (size_t)im.h * planes;
+        }
         k.coef_bytes += cb;
         k.count++;
         take.push_back(f);
@@ -478,13 +509,15 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     if (need_pixels && !pixels) return HVC_E_INVALID_ARG;
     if (take.empty()) return HVC_OK;
     const int n_chunks = (int)chunks.size(), n_take = (int)take.size();
-    size_t ring_bytes = 0, oring_bytes = 0, pring_bytes = 0;
+    size_t ring_bytes = 0, oring_bytes = 0, pring_bytes = 0, rring_bytes = 0, mring_bytes = 0;
     int largest = 0;
     uint64_t coef_total = 0;
     for (const Chunk &k : chunks) {
         ring_bytes = std::max(ring_bytes, k.coef_bytes);
         if (where == HVC_MEM_HOST) oring_bytes = std::max(oring_bytes, k.pix_hi - k.pix_lo);
         pring_bytes = std::max(pring_bytes, k.plane_bytes);
+        rring_bytes = std::max(rring_bytes, k.rgb_bytes);
+        mring_bytes = std::max(mring_bytes, k.mid_bytes);
         largest = std::max(largest, k.count);
     }
     if (where == HVC_MEM_HOST)
@@ -497,6 +530,7 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     if ((r = ring_ensure(c, coef_rings(c), {ring_bytes, ring_bytes}))) return r; // (a single file larger than chunk_bytes: the ring grows)
     if ((r = ring_ensure(c, out_rings(c), {oring_bytes}))) return r;
     if ((r = ring_ensure(c, plane_rings(c), {pring_bytes}))) return r;
+    if (form.resized() && (r = ring_ensure(c, resize_rings(c), {rring_bytes, mring_bytes}))) return r;
     // the GPU reader: which files of a chunk it hands back (known once the chunk's verdict is read), how many it read
     const bool gpu = c->mixed_reader == HVC_READER_GPU && !host_reader_only;
     MixedGpuReader rd; // (before the feed: pool tasks use it)
@@ -552,6 +586,8 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     std::vector<int> ok; // the chunk's good files with blocks
     uint8_t *const out = where == HVC_MEM_DEVICE ? pixels : nullptr; // (host: the chunk's slot of d_oring)
     const size_t *dst_off = where == HVC_MEM_DEVICE ? pixel_offsets : pix_rel.data();
+    if (form.resized())
+        for (int f : take) rimg[(size_t)f].dst_offset = dst_off[f];
     r = host_reader_chunks(
         c, feed, n_chunks, threads, wall0, [&](int k) { return chunks[(size_t)k].count; },
         [&](int k) -> size_t {
@@ -586,6 +622,21 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
             // the planes into the slot of their own ring, the colour pass from there to where the planes would have gone
             uint8_t *planes = c->d_pring[slot].as<uint8_t>();
             hvc::MixedRgbPlan cplan;
+            if (form.resized()) {
+                // ... the colour pass into the slot of the RGB ring (tight images at decoded size), the two resampling passes from
+                // there to where the images would have gone; every plan is built before anything is enqueued
+                uint8_t *rgb = c->d_rring[slot].as<uint8_t>();
+                hvc::ResizePlan rplan;
+                int rc = hvc::mixed_rgb_plan_build(oinfos, plane_rel.data(), rgb_rel.data(), nullptr, form.layout, ok.data(), (int)ok.size(),
+                                                   (uintptr_t)planes, (uintptr_t)rgb, true, cplan, N);
+                if (!rc) rc = hvc::resize_plan_build(rimg.data(), ok.data(), (int)ok.size(), form.layout, form.filter, (uintptr_t)rgb, (uintptr_t)dst, rplan);
+                if (!rc && rplan.mid_bytes > c->d_mring[slot].cap) rc = HVC_E_INTERNAL;
+                if (!rc) rc = mixed_launch(c, c->d_ring[slot].as<const int16_t>(), coef_rel.data(), oinfos, ok.data(), (int)ok.size(), planes,
+                                           plane_rel.data(), c->profiling, N);
+                if (!rc) rc = mixed_rgb_launch_plan(c, cplan, form.layout, planes, rgb, false);
+                if (!rc) rc = resize_launch_plan(c, rplan, rgb, dst, c->d_mring[slot].as<uint8_t>(), false);
+                return rc;
+            }
             int rc = hvc::mixed_rgb_plan_build(oinfos, plane_rel.data(), dst_off, form.rgb_row_strides, form.layout, ok.data(), (int)ok.size(),
                                                (uintptr_t)planes, (uintptr_t)dst, true, cplan, N);
             if (!rc) rc = mixed_launch(c, c->d_ring[slot].as<const int16_t>(), coef_rel.data(), oinfos, ok.data(), (int)ok.size(), planes,
@@ -611,18 +662,18 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
                 const int f = take[(size_t)t];
                 if (status[f] != HVC_OK || !out_bytes[(size_t)f] || gone(f)) continue;
                 const size_t lo = pix_rel[(size_t)f], hi = lo + out_bytes[(size_t)f];
-                if (form.rgb() && form.rgb_row_strides && form.rgb_row_strides[f] > hvc::mixed_rgb_row_bytes(form.layout, oinfos[f].width)) {
+                if (form.rgb() && form.rgb_row_strides && form.rgb_row_strides[f] > hvc::mixed_rgb_row_bytes(form.layout, out_w(f))) {
                     flush(); // rows with room between them: the image row by row, the caller's bytes between rows stay
                     if (he == hipSuccess)
                         he = hipMemcpy2DAsync(pixels + ch.pix_lo + lo, form.rgb_row_strides[f], dst + lo, form.rgb_row_strides[f],
-                                              hvc::mixed_rgb_row_bytes(form.layout, oinfos[f].width),
-                                              hvc::mixed_rgb_rows(form.layout, oinfos[f].height), hipMemcpyDeviceToHost, c->stream);
+                                              hvc::mixed_rgb_row_bytes(form.layout, out_w(f)),
+                                              hvc::mixed_rgb_rows(form.layout, out_h(f)), hipMemcpyDeviceToHost, c->stream);
                     continue;
                 }
                 // (scaled records lie at any offset: there the runs join only where they touch, and no byte between records is written)
                 // (host_reader_only: the files masked out of this pass keep their room, so what lies between two of its files
                 // may be another file's record -- its runs join only where they touch)
-                const bool joins = run_hi > run_lo && t == prev_t + 1 && lo >= run_hi && lo - run_hi < (N == 8 && !host_reader_only ? (size_t)4096 : (size_t)1);
+                const bool joins = run_hi > run_lo && t == prev_t + 1 && lo >= run_hi && lo - run_hi < (N == 8 && !host_reader_only && !form.resized() ? (size_t)4096 : (size_t)1);
                 if (!joins) flush();
                 if (run_hi == run_lo) run_lo = lo;
                 run_hi = hi;

@@ -17,6 +17,8 @@
 //   hvc_capi_mixed_coder.hip   the mixed GPU Huffman coder alone and the file pipeline built on it (behind
 //                        hvc_huffman_encode_frames_mixed, hvc_jpeg_encode_batch_mixed_gpu)
 //   hvc_capi_mixed_reader.hip  the mixed GPU Huffman reader's driver (hvc_mixed_reader.h) and hvc_jpeg_entropy_decode_gpu_mixed
+//   hvc_capi_resize.hip  the resampling step over a mixed set (hvc_rgb_resize_mixed) and the launch of its two passes, which
+//                        hvc_jpeg_decode_batch_mixed_resized ends in
 //   hvc_capi_async.hip   pinned host memory and the slots of the asynchronous seam (hvc_decode_frames_submit / hvc_wait)
 #ifndef HVC_CTX_H
 #define HVC_CTX_H
@@ -211,6 +213,11 @@ struct hvc_ctx {
     // hvc_jpeg_decode_batch_mixed_rgb: the ring of device slots the chunks' decoded planes live in (they never leave the GPU)
     Buf d_pring[RING];
     size_t pring_bytes = 0;
+    // hvc_rgb_resize_mixed / hvc_jpeg_decode_batch_mixed_resized (hvc_capi_resize.hip): the plan of the two resampling passes, and
+    // the pipeline's rings of device slots for the chunks' RGB images at decoded size and for the passes' intermediates
+    PlanBuf resize_plan;
+    Buf d_rring[RING], d_mring[RING];
+    size_t rring_bytes = 0, mring_bytes = 0;
     // hvc_set_host_cpus: the CPUs the batch pipelines' host threads may run on (empty = no restriction)
     bool have_cpus = false;
     cpu_set_t cpus;
@@ -251,6 +258,7 @@ struct RingSet {
 inline RingSet coef_rings(hvc_ctx *c) { return {{{&c->h_ring, &c->ring_bytes, 0}, {&c->d_ring, &c->ring_bytes, 0}}, 2, true}; } // coefficient chunks of the decode pipelines
 inline RingSet out_rings(hvc_ctx *c) { return {{{&c->d_oring, &c->oring_bytes, 0}}, 1, false}; } // decoded chunks on their way to the host
 inline RingSet plane_rings(hvc_ctx *c) { return {{{&c->d_pring, &c->pring_bytes, 0}}, 1, false}; }
+inline RingSet resize_rings(hvc_ctx *c) { return {{{&c->d_rring, &c->rring_bytes, 0}, {&c->d_mring, &c->mring_bytes, 0}}, 2, false}; } // decoded-size RGB chunks and the passes' intermediates
 inline RingSet reader_rings(hvc_ctx *c) { // hvc_jpeg_decode_batch_gpu: segments, index arrays, per-frame tables
     return {{{&c->gp_h_ecs, &c->gp_ecs_bytes, 0}, {&c->gp_d_ecs, &c->gp_ecs_bytes, HVC_HD_ECS_SLACK}, {&c->gp_h_meta, &c->gp_meta_bytes, 0},
              {&c->gp_d_meta, &c->gp_meta_bytes, 0}, {&c->gp_h_ftabs, &c->gp_ftabs_bytes, 0}, {&c->gp_d_ftabs, &c->gp_ftabs_bytes, 0}},
@@ -581,11 +589,16 @@ int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coe
 // behind every chunk's block stage; the planes stay in a device ring.
 // scale_denom 2, 4, 8: the planes (or the planes the images are made of) are those of hvc_jpeg_scaled_info, through
 // k_decode_mixed_scaled; `infos` stay the FULL-size infos, the pipeline derives the scaled ones.
+// out_widths set (with rgb_offsets): the RGB images go to a device ring slot of their own, tight, and the two resampling passes
+// (hvc_capi_resize.hip) take image f from there to out_widths[f] x out_heights[f] at rgb_offsets[f], rows rgb_row_strides[f] apart.
 struct MixedForm {
     const size_t *rgb_offsets = nullptr, *rgb_row_strides = nullptr;
     int layout = 0;
     int scale_denom = 1;
+    const int *out_widths = nullptr, *out_heights = nullptr;
+    int filter = 0;
     bool rgb() const { return rgb_offsets != nullptr; }
+    bool resized() const { return rgb() && out_widths != nullptr; }
 };
 int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads, size_t chunk_bytes,
                             const hvc_jpeg_info *infos, int *status, const size_t *pixel_offsets, uint8_t *pixels, size_t pixel_cap,
@@ -625,6 +638,16 @@ struct MixedRgbPlan;
 int mixed_rgb_launch_plan(hvc_ctx *c, const hvc::MixedRgbPlan &plan, int layout, const uint8_t *d_yuv, uint8_t *d_rgb, bool profile,
                           bool to_ycc = false);
 size_t stage_offsets(const size_t *offsets, const std::vector<size_t> &spans, std::vector<size_t> &d_off);
+// hvc_capi_resize.hip: the two resampling passes of a plan on device memory, enqueued on c->stream (d_mid: the intermediate, at
+// least plan.mid_bytes, on 64 bytes)
+namespace hvc {
+struct ResizePlan;
+}
+int resize_launch_plan(hvc_ctx *c, const hvc::ResizePlan &plan, const uint8_t *d_src, uint8_t *d_dst, uint8_t *d_mid, bool profile);
+// ... and the resampling step alone (behind hvc_rgb_resize_mixed in hvc_yuv.hip)
+int rgb_resize_mixed_impl(hvc_ctx *c, const uint8_t *src, const size_t *src_offsets, const size_t *src_row_strides, const int *widths,
+                          const int *heights, int n_images, uint8_t *dst, const size_t *dst_offsets, const size_t *dst_row_strides,
+                          const int *out_widths, const int *out_heights, int layout, int filter, int where);
 // the colour pass alone / in front of the block stage (behind hvc_rgb_to_yuv_mixed in hvc_yuv.hip, hvc_encode_frames_mixed_rgb in
 // hvc_capi_files.hip)
 int rgb_to_yuv_mixed_impl(hvc_ctx *c, uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos, int n_frames, const uint8_t *rgb,

@@ -679,4 +679,12 @@ int hvc_rgb_to_yuv_mixed(hvc_ctx *c, uint8_t *yuv, const size_t *yuv_offsets, co
     return rgb_to_yuv_mixed_impl(c, yuv, yuv_offsets, infos, n_frames, rgb, rgb_offsets, rgb_row_strides, layout, where);
 } HVC_ABI_CATCH
 
+// RGB images of different sizes, each to a size of its own (k_resize_h_mixed / k_resize_v_mixed): hvc_capi_resize.hip
+int hvc_rgb_resize_mixed(hvc_ctx *c, const uint8_t *src, const size_t *src_offsets, const size_t *src_row_strides, const int *widths,
+                         const int *heights, int n_images, uint8_t *dst, const size_t *dst_offsets, const size_t *dst_row_strides,
+                         const int *out_widths, const int *out_heights, int layout, int filter, int where) try {
+    return rgb_resize_mixed_impl(c, src, src_offsets, src_row_strides, widths, heights, n_images, dst, dst_offsets, dst_row_strides, out_widths,
+                                 out_heights, layout, filter, where);
+} HVC_ABI_CATCH
+
 } // extern "C"

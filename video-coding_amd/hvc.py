@@ -47,7 +47,10 @@ SYMBOLS = [
     "hvc_huffman_encode_frames_mixed", "hvc_jpeg_encode_batch_mixed_gpu", "hvc_last_mixed_coder_files",
     "hvc_jpeg_encoder_mixed_rgb_layout", "hvc_rgb_to_yuv_mixed", "hvc_encode_frames_mixed_rgb", "hvc_jpeg_encode_batch_mixed_rgb",
     "hvc_jpeg_encode_batch_mixed_rgb_gpu",
+    "hvc_rgb_resize_mixed", "hvc_jpeg_decode_batch_mixed_resized",
 ]
+HVC_RESIZE = {"box": 0, "bilinear": 1, "bicubic": 2}  # enum hvc_resize_filter
+HVC_RESIZE_MAX_TAPS = 2048
 HVC_RGB = {"interleaved": 0, "planar": 1}  # enum hvc_rgb_layout: [H, W, 3] / [3, H, W]
 HVC_YUV_400 = 400   # luma only, beside 420 / 422 / 444
 HVC_HUFF = {"default": 0, "optimised": 1}  # enum hvc_huff_tables
@@ -289,6 +292,11 @@ def lib():
         L.hvc_decode_frames_mixed_rgb.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), C.POINTER(sz), i, i]
         L.hvc_jpeg_decode_batch_mixed_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, ip, C.POINTER(i), C.POINTER(sz),
                                                       C.POINTER(sz), vp, sz, i, i, C.POINTER(BatchStats)]
+        L.hvc_rgb_resize_mixed.argtypes = [vp, vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(i), C.POINTER(i), i, vp, C.POINTER(sz),
+                                           C.POINTER(sz), C.POINTER(i), C.POINTER(i), i, i, i]
+        L.hvc_jpeg_decode_batch_mixed_resized.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, i, ip, C.POINTER(i), C.POINTER(i),
+                                                          C.POINTER(i), C.POINTER(sz), C.POINTER(sz), vp, sz, i, i, i,
+                                                          C.POINTER(BatchStats)]
         L.hvc_jpeg_encoder_mixed_layout.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, sz, ip, C.POINTER(i),
                                                     C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
         L.hvc_encode_frames_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), i]
@@ -352,6 +360,10 @@ def kernel_source_id():
 
 def _rgb_layout(layout):
     return HVC_RGB[layout] if isinstance(layout, str) else int(layout)
+
+
+def _resize_filter(filter):
+    return HVC_RESIZE[filter] if isinstance(filter, str) else int(filter)
 
 
 def rgb_shape(layout, width, height):
@@ -1398,6 +1410,62 @@ class Context:
                 image = rgb_view(rgb, lay.rgb_offsets[f], lay.rgb_row_strides[f], info.width, info.height, lay.layout)
             out.append((status[f], info, image))
         return out
+
+    def rgb_resize_mixed(self, src, src_offsets, widths, heights, dst, dst_offsets, out_widths, out_heights, filter="bilinear",
+                         layout="interleaved", src_row_strides=None, dst_row_strides=None):
+        """hvc_rgb_resize_mixed: image i (widths[i] x heights[i] at src[src_offsets[i]:], rows src_row_strides[i] apart, None:
+        tight) to out_widths[i] x out_heights[i] at dst[dst_offsets[i]:] (rows dst_row_strides[i] apart), bit-exact to Pillow's
+        Image.resize for filter "box" / "bilinear" / "bicubic" (tools/resize_reference.py), one launch per pass for the whole
+        set.  src / dst: numpy (host) or torch cuda tensors of bytes, both in the same memory space."""
+        sa, w1 = _addr(src)
+        da, w2 = _addr(dst)
+        assert w1 == w2, "src and dst must live in the same memory space"
+        n = len(widths)
+        ints = lambda v: (C.c_int * max(n, 1))(*[int(x) for x in v])
+        _chk(lib().hvc_rgb_resize_mixed(self._h, sa, _size_array(src_offsets, n), _size_array(src_row_strides, n), ints(widths),
+                                        ints(heights), n, da, _size_array(dst_offsets, n), _size_array(dst_row_strides, n),
+                                        ints(out_widths), ints(out_heights), _rgb_layout(layout), _resize_filter(filter), w1),
+             "hvc_rgb_resize_mixed")
+
+    def jpeg_decode_batch_mixed_resized(self, jpegs, size=None, sizes=None, filter="bilinear", scale_denom=1, layout="interleaved",
+                                        device=False, threads=8, chunk_bytes=0, mixed_layout=None, out=None):
+        """Files of any sizes, samplings and tables decoded (at 1 / scale_denom), converted to RGB and resized on the GPU in one
+        call (hvc_jpeg_decode_batch_mixed_resized).  size=(W, H): every file to W x H; returns (status[], tensor) with tensor
+        [n, H, W, 3] (interleaved) or [n, 3, H, W] (planar) -- numpy, or a torch cuda tensor with device=True; the frame of a
+        file that failed keeps what `out` held (zeros when it is made here).  sizes=[(W, H), ...]: a size per file (aspect-
+        preserving thumbnails); returns (status[], views), one [H, W, 3] / [3, H, W] view into ONE buffer per file, None for a
+        file that failed.  mixed_layout: a MixedLayout made before (its headers are what is needed).  out: the buffer to write
+        (bytes; uniform: n * H * W * 3).  The call's hvc_batch_stats: self.last_batch_stats."""
+        assert (size is None) != (sizes is None), "one of size= and sizes="
+        lay = mixed_layout if mixed_layout is not None else MixedLayout(jpegs)
+        n = len(lay)
+        wh = [tuple(int(v) for v in size)] * n if size is not None else [tuple(int(v) for v in s) for s in sizes]
+        assert len(wh) == n
+        offs, total = (C.c_size_t * max(n, 1))(), 0
+        for f, (w, h) in enumerate(wh):
+            offs[f] = total
+            total += 3 * max(w, 0) * max(h, 0)
+        if out is None:
+            if device:
+                import torch
+                out = torch.zeros(max(total, 8), dtype=torch.uint8, device="cuda")
+            else:
+                out = np.zeros(max(total, 8), dtype=np.uint8)
+        oa, where = _addr(out)
+        cap = out.numel() if hasattr(out, "numel") else out.size
+        st = BatchStats()
+        status = (C.c_int * max(n, 1))(*lay.status)
+        ow, oh = (C.c_int * max(n, 1))(*[w for w, _ in wh]), (C.c_int * max(n, 1))(*[h for _, h in wh])
+        _chk(lib().hvc_jpeg_decode_batch_mixed_resized(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, scale_denom, lay.infos,
+                                                       status, ow, oh, offs, None, oa, cap, _rgb_layout(layout),
+                                                       _resize_filter(filter), where, C.byref(st)),
+             "hvc_jpeg_decode_batch_mixed_resized")
+        self.last_batch_stats = st
+        status = [status[f] for f in range(n)]
+        if size is not None:
+            w, h = wh[0] if n else (int(size[0]), int(size[1]))
+            return status, out[:n * 3 * w * h].reshape((n,) + rgb_shape(layout, w, h))
+        return status, [rgb_view(out, offs[f], 0, wh[f][0], wh[f][1], layout) if status[f] == 0 else None for f in range(n)]
 
     def decode_frames_yuv444(self, coefs, coef_frame_stride, qtabs, comps, n_frames, width, height, frames,
                              frame_stride=None):
