@@ -734,9 +734,27 @@ HVC_API int hvc_jpeg_encode_rgb(hvc_ctx *ctx, const uint8_t *rgb, size_t rgb_row
  * hvc_jpeg_decode, hvc_jpeg_decode_batch, hvc_jpeg_decode_batch_gpu, hvc_yuv_to_rgb, hvc_decode_frames_rgb,
  * hvc_jpeg_decode_rgb and hvc_jpeg_decode_batch_rgb; hvc_set_restart_markers is honoured as before.  A file with a block
  * whose absolute DC does not fit int16 is HVC_E_RANGE (as at the reduced scales: no side list of such blocks).  The fused
- * 4:4:4, scaled (scale_denom > 1) and mixed entry points refuse any arithmetic but MODEL with HVC_E_INVALID_ARG, output
- * untouched, as they do for HARDCAML: their libjpeg forms are not built yet.  hvc_decode_frames_divergence is unaffected,
- * and there is no encoder side: hvc_set_encode_arithmetic refuses the value. */
+ * 4:4:4 and scaled (scale_denom > 1) entry points refuse any arithmetic but MODEL with HVC_E_INVALID_ARG, output untouched,
+ * as they do for HARDCAML: their libjpeg forms are not built.  The mixed entry points refuse it under hvc_set_arithmetic in
+ * the same way, and have the libjpeg form at full size under a setting of their own (next paragraph).
+ * hvc_decode_frames_divergence is unaffected, and there is no encoder side: hvc_set_encode_arithmetic refuses the value.
+ *
+ * Mixed batches (csrc/hvc_mixed_libjpeg.hip): hvc_set_mixed_arithmetic(ctx, HVC_ARITH_LIBJPEG) gives the mixed decode calls --
+ * hvc_decode_frames_mixed, hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed, _mixed_rgb and
+ * _mixed_resized with scale_denom 1 -- the two definitions above: the block stage is k_islow_mixed, k_islow's block code under
+ * k_decode_mixed's decomposition with the int64 path in the same lane (hvc_last_wide_blocks counts it;
+ * hvc_set_decode_kernel(ctx, 2) sends every block there), and the colour pass is k_ycc_to_rgb_fancy_mixed.  Every record is
+ * what hvc_jpeg_decode / hvc_jpeg_decode_rgb write for that file alone under hvc_set_arithmetic(ctx, HVC_ARITH_LIBJPEG), with
+ * host or device memory and with either mixed reader; hvc_jpeg_decode_batch_mixed_resized then ends in the bytes of Pillow's
+ * Image.open(f).convert("RGB").resize((W, H), filter).  The setting is per context, HVC_ARITH_MODEL by default; any other
+ * value, HVC_ARITH_HARDCAML included, is HVC_E_INVALID_ARG and leaves the setting as it was.  At the default the mixed calls
+ * do what they do without it, refusing any hvc_set_arithmetic but MODEL included; under HVC_ARITH_LIBJPEG they do not look
+ * at hvc_set_arithmetic at all.  The reduced-size forms (hvc_decode_frames_mixed_scaled, hvc_jpeg_decode_batch_mixed_scaled,
+ * _mixed_scaled_rgb, and _mixed_resized with scale_denom > 1) return HVC_E_INVALID_ARG under it, output untouched: libjpeg
+ * decodes the chroma of a subsampled file at another size there, a different definition.  hvc_rgb_resize_mixed and the encode
+ * calls take no part in the setting. */
+HVC_API int hvc_set_mixed_arithmetic(hvc_ctx *ctx, int arith); /* HVC_ARITH_MODEL (default) | HVC_ARITH_LIBJPEG */
+HVC_API int hvc_get_mixed_arithmetic(const hvc_ctx *ctx, int *arith);
 
 /* ------------------------------------------------------------------------- */
 /* Decoding at reduced size: 1/2, 1/4, 1/8 (an EXTENSION; the model has no counterpart).  libjpeg's scale_denom: the inverse
@@ -806,7 +824,11 @@ HVC_API int hvc_jpeg_decode_batch_scaled(hvc_ctx *ctx, const uint8_t *const *jpe
  * there is no 4:4:4-planar form and no side list of DCs beyond int16; the files are read by the host Huffman reader or, with
  * hvc_set_mixed_reader(ctx, HVC_READER_GPU), by the mixed GPU Huffman reader (further below).  With
  * HVC_ARITH_HARDCAML set the ctx functions return HVC_E_INVALID_ARG; hvc_set_decode_kernel(ctx, 2) sends every block
- * through the int64 arithmetic, other selections are ignored; hvc_last_wide_blocks counts the blocks that took it. */
+ * through the int64 arithmetic, other selections are ignored; hvc_last_wide_blocks counts the blocks that took it.
+ * hvc_set_mixed_arithmetic(ctx, HVC_ARITH_LIBJPEG) ("Bit-exact to libjpeg" above) makes the full-size calls of this section
+ * and of the RGB and resized ones below compute libjpeg's pixels instead (k_islow_mixed, k_ycc_to_rgb_fancy_mixed) and the
+ * reduced-size ones return HVC_E_INVALID_ARG; it replaces what hvc_set_arithmetic says for these calls, which is otherwise
+ * honoured as stated here. */
 
 /* headers of n_files files -> infos[f], status[f] (what hvc_jpeg_read_header returns for file f),
  * pixel_offsets[f] (bytes; each record = the file's padded planes exactly as hvc_jpeg_decode lays them out,
@@ -1154,7 +1176,9 @@ HVC_API int hvc_jpeg_encode_batch_mixed_rgb_gpu(hvc_ctx *ctx, const uint8_t *con
  *   dst_row_strides[f] apart (NULL or 0: tight).  A file whose resize is beyond the bounds gets HVC_E_TOO_LARGE (a size below 1
  *   or a stride below the row: HVC_E_INVALID_ARG) as ITS status, and stops nobody; a file that fails leaves its record in dst
  *   untouched.  dst_cap: every good file's record must lie inside (HVC_E_INVALID_ARG).  An unknown filter or layout, and
- *   HVC_ARITH_HARDCAML / _LIBJPEG as the arithmetic: HVC_E_INVALID_ARG for the call, output untouched. */
+ *   HVC_ARITH_HARDCAML / _LIBJPEG as the arithmetic (hvc_set_arithmetic): HVC_E_INVALID_ARG for the call, output untouched.
+ *   Under hvc_set_mixed_arithmetic(ctx, HVC_ARITH_LIBJPEG) and scale_denom 1 the decode is libjpeg's and a record is Pillow's
+ *   Image.open(f).convert("RGB").resize((W, H), filter) byte for byte; scale_denom > 1 is then HVC_E_INVALID_ARG, output untouched. */
 typedef enum { HVC_RESIZE_BOX = 0, HVC_RESIZE_BILINEAR = 1, HVC_RESIZE_BICUBIC = 2 } hvc_resize_filter;
 #define HVC_RESIZE_MAX_TAPS 2048
 HVC_API int hvc_rgb_resize_mixed(hvc_ctx *ctx, const uint8_t *src, const size_t *src_offsets, const size_t *src_row_strides,

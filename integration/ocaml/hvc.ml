@@ -843,6 +843,12 @@ let last_mixed_reader_files =
   foreign "hvc_last_mixed_reader_files" (ctx @-> ptr uint64_t @-> ptr uint64_t @-> returning int)
 ;;
 
+(* the mixed decode calls' own arithmetic: 0 = the model (default), 3 = libjpeg's (k_islow_mixed + k_ycc_to_rgb_fancy_mixed);
+   under 3 they do not look at set_arithmetic, and the reduced-size forms are refused
+   int hvc_set_mixed_arithmetic(ctx, arith);  int hvc_get_mixed_arithmetic(ctx, arith) *)
+let set_mixed_arithmetic = foreign "hvc_set_mixed_arithmetic" (ctx @-> int @-> returning int)
+let get_mixed_arithmetic = foreign "hvc_get_mixed_arithmetic" (ctx @-> ptr int @-> returning int)
+
 (* int hvc_jpeg_entropy_decode_gpu_mixed(ctx, jpegs, sizes, n_files, infos, status, coefs, coef_offsets, coef_cap, where,
                                          used_gpu) *)
 let jpeg_entropy_decode_gpu_mixed =

@@ -23,6 +23,9 @@
     python -m video_coding_amd model decode frames OUT_DIR IN1.jpg ... -rgb -resize WxH [-filter box|bilinear|bicubic] [-scale N] [-reader gpu|host]
                                                       every image resized to W x H on the GPU, bit-exact to Pillow's
                                                       Image.resize (hvc_jpeg_decode_batch_mixed_resized): OUT_DIR/<name>.ppm
+    python -m video_coding_amd model decode frames OUT_DIR IN1.jpg ... [-rgb] [-resize WxH [-filter ...]] [-reader gpu|host] -arithmetic libjpeg
+                                                      the same calls in libjpeg's arithmetic (hvc_set_mixed_arithmetic): every file as
+                                                      `decode frame -arithmetic libjpeg` writes it; not with -scale above 1
                                                       (an extension: JFIF colour conversion, hvc_jpeg_decode_rgb / _encode_rgb)
     python -m video_coding_amd oyuv compare {max-difference,mean-difference,mean-square-error,psnr}
                                             {y,u,v,yuv} FILE-1 FILE-2 WxH [-format 420]
@@ -148,6 +151,7 @@ def model_decode_frames_rgb(a, datas):
         if a.restart_markers:
             ctx.set_restart_markers(True)
         ctx.set_mixed_reader(a.reader)
+        ctx.set_mixed_arithmetic(a.arithmetic)
         if a.resize is not None:
             # decoded (at 1 / -scale), converted and resized on the GPU in one hvc_jpeg_decode_batch_mixed_resized call
             status, tensor = ctx.jpeg_decode_batch_mixed_resized(datas, size=a.resize, filter=a.filter, scale_denom=a.scale, threads=a.threads)
@@ -178,6 +182,8 @@ def model_decode_frames(a):
     """every file through one hvc_jpeg_decode_batch_mixed call; a file that fails gets a line on stderr and the others are
     still written; the exit status says whether any failed"""
     import os
+    if a.arithmetic != "model" and a.scale != 1:   # (before a file is read or a context made, as `decode frame` refuses it)
+        raise SystemExit("-arithmetic %s decodes at full size (no -scale): libjpeg's reduced sizes are another definition" % a.arithmetic)
     datas = [open(p, "rb").read() for p in a.bits]
     if a.resize is not None and not a.rgb:
         raise SystemExit("-resize takes RGB images: give -rgb with it")
@@ -192,6 +198,7 @@ def model_decode_frames(a):
         if a.restart_markers:
             ctx.set_restart_markers(True)
         ctx.set_mixed_reader(a.reader)
+        ctx.set_mixed_arithmetic(a.arithmetic)
         if a.scale == 1:
             results = ctx.jpeg_decode_batch_mixed(datas, threads=a.threads, layout=lay, pixels=pixels)
         else:
@@ -564,6 +571,9 @@ def parser():
                    help="with -rgb: every image resized to W x H on the GPU, bit-exact to Pillow's Image.resize "
                         "(hvc_jpeg_decode_batch_mixed_resized; -scale: the cheap pre-shrink in front of it)")
     p.add_argument("-filter", choices=["box", "bilinear", "bicubic"], default="bilinear", help="the filter of -resize")
+    p.add_argument("-arithmetic", default="model", choices=["model", "libjpeg"],
+                   help="libjpeg: the set in libjpeg's arithmetic, every file as `decode frame -arithmetic libjpeg` writes it "
+                        "(hvc_set_mixed_arithmetic HVC_ARITH_LIBJPEG); full size only, no -scale")
     p.set_defaults(fn=model_decode_frames)
     enc = model.add_parser("encode").add_subparsers(dest="what", required=True)
     p = enc.add_parser("frame")

@@ -387,6 +387,19 @@ int hvc_get_arithmetic(const hvc_ctx *c, int *arith) try {
     return HVC_OK;
 } HVC_ABI_CATCH
 
+// the mixed decode calls' own setting (hvc_capi_mixed.hip; the rule: mixed_arith_of, hvc_ctx.h)
+int hvc_set_mixed_arithmetic(hvc_ctx *c, int arith) try {
+    if (!c || (arith != HVC_ARITH_MODEL && arith != HVC_ARITH_LIBJPEG)) return HVC_E_INVALID_ARG;
+    c->mixed_arith = arith;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_get_mixed_arithmetic(const hvc_ctx *c, int *arith) try {
+    if (!c || !arith) return HVC_E_INVALID_ARG;
+    *arith = c->mixed_arith;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
 int hvc_set_encode_arithmetic(hvc_ctx *c, int arith) try {
     if (!c || (arith != HVC_ARITH_MODEL && arith != HVC_ARITH_HARDCAML)) return HVC_E_INVALID_ARG;
     c->enc_arith = arith;

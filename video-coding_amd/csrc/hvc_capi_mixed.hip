@@ -8,23 +8,26 @@
 // plan built for N = 8 / scale_denom samples per block side and k_decode_mixed_scaled (hvc_mixed_scaled.hip) as the block stage.
 #include "hvc_batch.h"
 #include "hvc_mixed.h"
+#include "hvc_mixed_libjpeg.h"
 #include "hvc_mixed_rgb.h"
 #include "hvc_mixed_reader.h"
 #include "hvc_resize_plan.h"
 
 namespace {
 
-// the plan as one image: planes | tables | map, each part on 16 bytes
+// the plan as one image: planes | tables | map | pairs, each part on 16 bytes (pairs: the libjpeg-exact block stage's table
+// records, n_pairs words -- none under the model's arithmetic, whose image is the first three parts and nothing else)
 struct ImageParts {
-    size_t planes = 0, tables = 0, map = 0, total = 0;
+    size_t planes = 0, tables = 0, map = 0, pairs = 0, total = 0;
 };
-ImageParts image_parts(const hvc::MixedPlan &plan) {
+ImageParts image_parts(const hvc::MixedPlan &plan, size_t n_pairs) {
     ImageParts p;
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     p.planes = 0;
     p.tables = up(plan.planes.size() * sizeof(hvc::MixedPlaneK));
     p.map = p.tables + up(plan.tables.size() * sizeof(hvc::MixedTableK));
-    p.total = p.map + up(plan.map.size() * sizeof(unsigned));
+    p.pairs = p.map + up(plan.map.size() * sizeof(unsigned));
+    p.total = p.pairs + up(n_pairs * sizeof(unsigned));
     return p;
 }
 
@@ -54,10 +57,13 @@ int upload_image(hvc_ctx *c, PlanBuf &b, const std::vector<unsigned char> &img) 
 
 namespace {
 
-// the block stage's tables in c->mixed_plan
-int upload_plan(hvc_ctx *c, const hvc::MixedPlan &plan, hvc::MixedParams &P) {
-    const ImageParts ip = image_parts(plan);
+// the block stage's tables in c->mixed_plan; pairs (optional): the records of mixed_islow_pairs_build behind them, *d_pairs
+// = where they are on the device
+int upload_plan(hvc_ctx *c, const hvc::MixedPlan &plan, hvc::MixedParams &P, const std::vector<unsigned> *pairs = nullptr,
+                const unsigned **d_pairs = nullptr) {
+    const ImageParts ip = image_parts(plan, pairs ? pairs->size() : 0);
     std::vector<unsigned char> img(ip.total, 0);
+    if (pairs && !pairs->empty()) std::memcpy(img.data() + ip.pairs, pairs->data(), pairs->size() * sizeof(unsigned));
     std::memcpy(img.data() + ip.planes, plan.planes.data(), plan.planes.size() * sizeof(hvc::MixedPlaneK));
     std::memcpy(img.data() + ip.tables, plan.tables.data(), plan.tables.size() * sizeof(hvc::MixedTableK));
     std::memcpy(img.data() + ip.map, plan.map.data(), plan.map.size() * sizeof(unsigned));
@@ -68,6 +74,7 @@ int upload_plan(hvc_ctx *c, const hvc::MixedPlan &plan, hvc::MixedParams &P) {
     P.tables = reinterpret_cast<const hvc::MixedTableK *>(d + ip.tables);
     P.map = reinterpret_cast<const unsigned *>(d + ip.map);
     P.n_units = (unsigned)plan.map.size();
+    if (d_pairs) *d_pairs = reinterpret_cast<const unsigned *>(d + ip.pairs);
     return HVC_OK;
 }
 
@@ -95,7 +102,11 @@ int mixed_rgb_launch_plan(hvc_ctx *c, const hvc::MixedRgbPlan &plan, int layout,
     P.planar = layout == HVC_RGB_PLANAR;
     const int slot = (int)(c->k_calls % HVC_PROF_RING);
     const hipEvent_t k0 = profile ? (hipEvent_t)c->k0[slot] : nullptr, k1 = profile ? (hipEvent_t)c->k1[slot] : nullptr;
-    const hipError_t e = to_ycc ? hvc::launch_rgb_to_ycc_mixed(P, c->stream, k0, k1) : hvc::launch_ycc_to_rgb_mixed(P, c->stream, k0, k1);
+    // hvc_set_mixed_arithmetic(HVC_ARITH_LIBJPEG): the planes -> RGB direction with libjpeg's fancy upsampling
+    const bool fancy = !to_ycc && c->mixed_arith == HVC_ARITH_LIBJPEG;
+    const hipError_t e = to_ycc  ? hvc::launch_rgb_to_ycc_mixed(P, c->stream, k0, k1)
+                         : fancy ? hvc::launch_ycc_to_rgb_fancy_mixed(P, c->stream, k0, k1)
+                                 : hvc::launch_ycc_to_rgb_mixed(P, c->stream, k0, k1);
     if (e != hipSuccess) return fail_hip(c, e);
     if (profile) c->k_calls++;
     return HVC_OK;
@@ -113,6 +124,32 @@ int mixed_launch_plan(hvc_ctx *c, const hvc::MixedPlan &plan, const int16_t *d_c
     int r;
     if (plan.map.empty()) return HVC_OK; // no block at all: nothing to launch
     if (((uintptr_t)d_coefs & 15) || (n == 8 && ((uintptr_t)d_pixels & 7))) return HVC_E_ALIGNMENT;
+    if (n == 8 && c->mixed_arith == HVC_ARITH_LIBJPEG) {
+        // k_islow_mixed (hvc_mixed_libjpeg.hip): its int64 path runs in the same lane, so no fix-up list; the call's first launch
+        // clears the total it adds to, as the scaled stage below; hvc_set_decode_kernel(ctx, 2) sends every block there
+        std::vector<unsigned> pairs;
+        hvc::mixed_islow_pairs_build(plan, pairs);
+        hvc::MixedParams M;
+        std::memset(&M, 0, sizeof M);
+        hvc::MixedIslowParams P;
+        std::memset(&P, 0, sizeof P);
+        if ((r = upload_plan(c, plan, M, &pairs, &P.pairs))) return r;
+        P.coefs = d_coefs;
+        P.pixels = d_pixels;
+        P.planes = M.planes;
+        P.map = M.map;
+        P.n_units = M.n_units;
+        P.all_wide = c->decode_kernel == 2;
+        P.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count.as<unsigned>() + 2);
+        if (!c->wide_total_started) HIPCHK(c, hipMemsetAsync(P.wide_total, 0, sizeof *P.wide_total, c->stream));
+        c->wide_total_started = true;
+        if (P.all_wide) c->wide_host = (c->wide_host < 0 ? 0 : c->wide_host) + (long long)plan.blocks;
+        const int slot = (int)(c->k_calls % HVC_PROF_RING);
+        const hipError_t e = hvc::launch_islow_mixed(P, c->stream, profile ? c->k0[slot] : nullptr, profile ? c->k1[slot] : nullptr);
+        if (e != hipSuccess) return fail_hip(c, e);
+        if (profile) c->k_calls++;
+        return HVC_OK;
+    }
     if (n == 8 && (r = reserve_mixed_fix_list(c, plan.map.size() * HVC_MIXED_UNIT))) return r;
     hvc::MixedParams P;
     std::memset(&P, 0, sizeof P);
@@ -225,7 +262,8 @@ int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coe
                              uint8_t *pixels, const size_t *pixel_offsets, int where, int scale_denom) {
     const int N = scaled_side(scale_denom);
     if (!c || !N || n_frames < 0 || (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE)) return HVC_E_INVALID_ARG;
-    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (the RTL arithmetic has no mixed form, as it has no scaled one)
+    bool libjpeg;
+    if (mixed_arith_of(c, scale_denom, libjpeg)) return HVC_E_INVALID_ARG; // (hvc_ctx.h: the rule of hvc_set_mixed_arithmetic)
     if (n_frames == 0) return HVC_OK;
     if (!infos || !coef_offsets || !pixel_offsets) return HVC_E_INVALID_ARG;
     DeviceGuard g(c->device);
@@ -276,7 +314,8 @@ static int mixed_rgb_args(const hvc_ctx *c, const void *infos, const void *in_of
                           int where, bool &nothing) {
     if (!c || n_frames < 0 || (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE)) return HVC_E_INVALID_ARG;
     if (layout != HVC_RGB_INTERLEAVED && layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
-    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG; // (as the mixed block stage: no RTL form)
+    bool libjpeg;
+    if (mixed_arith_of(c, 1, libjpeg)) return HVC_E_INVALID_ARG; // (as the mixed block stage)
     nothing = n_frames == 0;
     if (!nothing && (!infos || !in_offsets || !rgb_offsets)) return HVC_E_INVALID_ARG;
     return HVC_OK;
@@ -402,7 +441,8 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     if (c && !host_reader_only) c->mixed_gpu_files = c->mixed_host_files = 0;
     if (!c || !jpegs || !sizes || !infos || !status || !pixel_offsets || n_files < 0) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
-    if (c->arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG;
+    bool libjpeg;
+    if (mixed_arith_of(c, form.scale_denom, libjpeg)) return HVC_E_INVALID_ARG; // (scaled forms under the libjpeg setting among them)
     const int N = scaled_side(form.scale_denom);
     if (!N) return HVC_E_INVALID_ARG;
     if (stats) std::memset(stats, 0, sizeof *stats);

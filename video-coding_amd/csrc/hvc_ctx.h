@@ -10,7 +10,8 @@
 //   hvc_rgb.hip          the RGB colour pass (kernels and launches; its entry points live with their families in the files above)
 //   hvc_capi_mixed.hip   batches of frames / files of different geometry and tables (hvc_decode_frames_mixed, hvc_jpeg_decode_batch_mixed,
 //                        their RGB forms: hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed_rgb, and the
-//                        reduced-size forms hvc_decode_frames_mixed_scaled, hvc_jpeg_decode_batch_mixed_scaled, _scaled_rgb)
+//                        reduced-size forms hvc_decode_frames_mixed_scaled, hvc_jpeg_decode_batch_mixed_scaled, _scaled_rgb); under
+//                        hvc_set_mixed_arithmetic(HVC_ARITH_LIBJPEG) the full-size ones launch the kernels of hvc_mixed_libjpeg.hip
 //   hvc_capi_mixed_encode.hip  the same in the other direction: raw frames of different geometry, sampling and quality to records
 //                        and files (behind hvc_encode_frames_mixed, hvc_jpeg_encode_batch_mixed), and the same from RGB images
 //                        (behind hvc_rgb_to_yuv_mixed, hvc_encode_frames_mixed_rgb, hvc_jpeg_encode_batch_mixed_rgb[_gpu])
@@ -153,6 +154,8 @@ struct hvc_ctx {
     int decode_kernel = 0; // hvc_set_decode_kernel: 0 packed (default), 1 unpacked int32, 2 int64 for every block, 3 q16
     int arith = HVC_ARITH_MODEL; // hvc_set_arithmetic: the block stage's arithmetic (HARDCAML: k_hardcaml, hvc_hardcaml.hip;
                                  // LIBJPEG: k_islow and, in the colour pass, k_ycc_to_rgb_fancy, hvc_libjpeg.hip)
+    int mixed_arith = HVC_ARITH_MODEL; // hvc_set_mixed_arithmetic: the mixed decode calls' own setting (LIBJPEG: k_islow_mixed and
+                                       // k_ycc_to_rgb_fancy_mixed, hvc_mixed_libjpeg.hip; they then do not look at `arith`)
     int enc_arith = HVC_ARITH_MODEL; // hvc_set_encode_arithmetic: the encoder's (HARDCAML: k_hardcaml_encode, hvc_hardcaml.hip)
     int huff_tables = HVC_HUFF_DEFAULT; // hvc_set_huffman_tables: the files' Huffman tables (OPTIMISED: k_huff_hist / k_huff_build)
     int restart_interval = 0; // hvc_set_restart_interval: MCUs per restart interval of the files written, 0 = no DRI / RSTn
@@ -591,6 +594,16 @@ int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coe
 // k_decode_mixed_scaled; `infos` stay the FULL-size infos, the pipeline derives the scaled ones.
 // out_widths set (with rgb_offsets): the RGB images go to a device ring slot of their own, tight, and the two resampling passes
 // (hvc_capi_resize.hip) take image f from there to out_widths[f] x out_heights[f] at rgb_offsets[f], rows rgb_row_strides[f] apart.
+// Which arithmetic a mixed decode call runs in, or that it is refused (the one rule of hvc_set_mixed_arithmetic).  At the
+// default the calls do what they did before there was such a setting: the model's arithmetic, and HVC_E_INVALID_ARG unless
+// hvc_set_arithmetic is the model's too (the RTL arithmetic has no mixed form, as it has no scaled one).  Under
+// HVC_ARITH_LIBJPEG hvc_set_arithmetic is not looked at; the reduced-size forms have no libjpeg form (libjpeg decodes the
+// chroma of a subsampled file at another size there) and are refused.
+inline int mixed_arith_of(const hvc_ctx *c, int scale_denom, bool &libjpeg) {
+    libjpeg = c->mixed_arith == HVC_ARITH_LIBJPEG;
+    if (libjpeg) return scale_denom == 1 ? HVC_OK : HVC_E_INVALID_ARG;
+    return c->arith != HVC_ARITH_MODEL ? HVC_E_INVALID_ARG : HVC_OK;
+}
 struct MixedForm {
     const size_t *rgb_offsets = nullptr, *rgb_row_strides = nullptr;
     int layout = 0;

@@ -93,6 +93,16 @@ int mixed_plan_build(const hvc_jpeg_info *infos, const size_t *coef_offsets, con
     return HVC_OK;
 }
 
+// the pair records of the libjpeg-exact block stage, from the entries MixedTableK::qt keeps whole
+void mixed_islow_pairs_build(const MixedPlan &plan, std::vector<unsigned> &pairs) {
+    pairs.assign(plan.tables.size() * HVC_ISLOW_PAIR_WORDS, 0u);
+    for (size_t t = 0; t < plan.tables.size(); t++)
+        for (int i = 0; i < HVC_ISLOW_PAIR_WORDS; i++) {
+            const int *q = plan.tables[t].qt;
+            pairs[t * HVC_ISLOW_PAIR_WORDS + i] = ((unsigned)q[2 * i] & 0xffffu) | ((unsigned)q[2 * i + 1] & 0xffffu) << 16;
+        }
+}
+
 // hvc_jpeg_mixed_layout (include/hvc_jpeg.h; the entry point itself stands in hvc_capi_jpeg.hip)
 int mixed_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, size_t align, hvc_jpeg_info *infos, int *status,
                  size_t *pixel_offsets, size_t *total_bytes) {

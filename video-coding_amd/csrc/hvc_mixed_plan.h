@@ -89,6 +89,13 @@ struct MixedPlan {
 int mixed_plan_build(const hvc_jpeg_info *infos, const size_t *coef_offsets, const size_t *pixel_offsets, const int *frames,
                      int n_list, MixedPlan &plan, int n = 8, uintptr_t pix_addr = 0);
 
+// The tables of a plan in the form the libjpeg-exact block stage wants (k_islow_mixed, hvc_mixed_libjpeg.hip; IslowParams::qq's
+// form): one record of HVC_ISLOW_PAIR_WORDS dwords per table of plan.tables, in that order, dword i = q[2i] | q[2i+1] << 16
+// in zig-zag order with all 16 bits of every entry.  An array of its own beside the plan's three: MixedTableK and
+// everything k_decode_mixed reads stay what they are.  An empty plan gives no record.
+#define HVC_ISLOW_PAIR_WORDS 32
+void mixed_islow_pairs_build(const MixedPlan &plan, std::vector<unsigned> &pairs);
+
 // hvc_jpeg_mixed_layout of include/hvc_jpeg.h
 int mixed_layout(const uint8_t *const *jpegs, const size_t *sizes, int n_files, size_t align, hvc_jpeg_info *infos, int *status,
                  size_t *pixel_offsets, size_t *total_bytes);

@@ -48,6 +48,7 @@ SYMBOLS = [
     "hvc_jpeg_encoder_mixed_rgb_layout", "hvc_rgb_to_yuv_mixed", "hvc_encode_frames_mixed_rgb", "hvc_jpeg_encode_batch_mixed_rgb",
     "hvc_jpeg_encode_batch_mixed_rgb_gpu",
     "hvc_rgb_resize_mixed", "hvc_jpeg_decode_batch_mixed_resized",
+    "hvc_set_mixed_arithmetic", "hvc_get_mixed_arithmetic",
 ]
 HVC_RESIZE = {"box": 0, "bilinear": 1, "bicubic": 2}  # enum hvc_resize_filter
 HVC_RESIZE_MAX_TAPS = 2048
@@ -215,6 +216,8 @@ def lib():
         L.hvc_jpeg_entropy_decode_gpu_mixed.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, vp, C.POINTER(i), vp, C.POINTER(sz), sz, i, C.POINTER(i)]
         L.hvc_set_arithmetic.argtypes = [vp, i]
         L.hvc_get_arithmetic.argtypes = [vp, C.POINTER(i)]
+        L.hvc_set_mixed_arithmetic.argtypes = [vp, i]
+        L.hvc_get_mixed_arithmetic.argtypes = [vp, C.POINTER(i)]
         L.hvc_decode_frames_divergence.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
         L.hvc_set_encode_arithmetic.argtypes = [vp, i]
         L.hvc_get_encode_arithmetic.argtypes = [vp, C.POINTER(i)]
@@ -990,6 +993,21 @@ class Context:
     def arithmetic(self):
         v = C.c_int()
         _chk(lib().hvc_get_arithmetic(self._h, C.byref(v)), "hvc_get_arithmetic")
+        return {b: a for a, b in HVC_ARITH.items()}.get(v.value, v.value)
+
+    def set_mixed_arithmetic(self, arith):
+        """hvc_set_mixed_arithmetic: "model" (default) | "libjpeg" -- the mixed decode calls' own setting.  Under "libjpeg"
+        decode_frames_mixed, yuv_to_rgb_mixed, decode_frames_mixed_rgb, jpeg_decode_batch_mixed, _mixed_rgb and _mixed_resized
+        at full size give libjpeg's pixels (what jpeg_decode / jpeg_decode_rgb give per file under set_arithmetic("libjpeg"))
+        whatever set_arithmetic says, and the reduced-size forms are refused.  Anything else ("hardcaml" included) is an error
+        and leaves the setting as it was."""
+        _chk(lib().hvc_set_mixed_arithmetic(self._h, HVC_ARITH[arith] if isinstance(arith, str) else int(arith)),
+             "hvc_set_mixed_arithmetic")
+
+    @property
+    def mixed_arithmetic(self):
+        v = C.c_int()
+        _chk(lib().hvc_get_mixed_arithmetic(self._h, C.byref(v)), "hvc_get_mixed_arithmetic")
         return {b: a for a, b in HVC_ARITH.items()}.get(v.value, v.value)
 
     def decode_divergence(self, coefs, coef_frame_stride, qtabs, comps, n_frames, max_diff=None, diff_frame_stride=None):
