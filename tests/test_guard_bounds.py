@@ -448,7 +448,8 @@ def test_xcd_work_is_a_permutation_of_the_grid():
     the whole groups of 8 R workgroups; frame = umulhi(linear, ceil(2^32 / tiles)).  Replayed here with the kernel's own
     integer steps: every (frame, tile) of the grid is taken exactly once, for the benches' grids and for awkward ones, and
     the reciprocal is exact wherever xcd_map_for lets the mapping on (tiles * tiles * frames < 2^32).  (That the kernels
-    really cover every tile is what the GPU parity tests at full size see: a tile nobody took would stay zero.)"""
+    really take their frame and tile from it everywhere is what tests/test_gpu_xcd_order.py sees, family by family, on grids
+    with a permuted part and a remainder over a sentinel fill; the table of tests/test_xcd_grids.py keeps those grids there.)"""
     import numpy as np
 
     def mapped(per, n, sh):
