@@ -1119,7 +1119,8 @@ int hvc_decode_frames_rgb(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, cons
 template <class Model, class Compare>
 static int divergence_chunks(hvc_ctx *c, const uint8_t *in, size_t in_fs, size_t in_span, size_t model_fs, int n_frames, uint8_t *max_diff,
                              size_t diff_fs, size_t blocks, int where, Model model, Compare compare) {
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)256 << 20) / model_fs));
+    // (at most 65535 frames too: the compare form is one launch per chunk, and its grid has a row per frame)
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_frames, 65535), ((size_t)256 << 20) / model_fs));
     int r = grow(c, c->d_div_px, (size_t)chunk * model_fs);
     if (r) return r;
     if (where == HVC_MEM_HOST) {
@@ -1540,8 +1541,13 @@ int hvc_encode_frames_recon(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, 
     if (error || where == HVC_MEM_HOST) {
         hvc::EncodeParams P;
         fill_geometry(P, L, 0, pixel_fs, n_frames);
-        P.pixels = d_pix;
-        HIPCHK(c, hvc::launch_abs_error(P, d_recon, d_error, c->stream));
+        // the grid's 65535 frames per launch (frames_per_launch_capped), as the two calls in front of it
+        HIPCHK(c, for_each_launch(0, n_frames, 65535, nullptr, nullptr, [&](int f, int n, hipEvent_t, hipEvent_t) {
+            hvc::EncodeParams Pk = P;
+            Pk.n_frames = n;
+            Pk.pixels = d_pix + (size_t)f * pixel_fs;
+            return hvc::launch_abs_error(Pk, d_recon + (size_t)f * pixel_fs, d_error + (size_t)f * pixel_fs, c->stream);
+        }));
     }
     if (where == HVC_MEM_DEVICE) return HVC_OK;
     for (int f = 0; f < n_frames; f++) // back to the caller: the component planes only (padding stays as it was)
