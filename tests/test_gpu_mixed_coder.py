@@ -79,6 +79,29 @@ def test_a_capacity_one_byte_short(ctx, raws):
     assert got[BAD][0] == -1
 
 
+def test_failing_files_across_ring_reuse(ctx, raws):
+    """one chunk per file -- more chunks than the ring has slots -- with a capacity one byte short and the refused frame in
+    the middle: both pipelines give the same results over the same chunks and leave the same bytes in every buffer"""
+    want = singles(ctx, raws)
+    short = 5
+    caps = [len(w) if w else 8 for w in want]
+    caps[short] -= 1
+    res, chunks, bufs = {}, {}, {}
+    for name, call in (("host", ctx.jpeg_encode_batch_mixed), ("gpu", ctx.jpeg_encode_batch_mixed_gpu)):
+        bufs[name] = [np.full(c + 8, 0xA5, dtype=np.uint8) for c in caps]
+        res[name] = call(raws, FRAMES, threads=4, chunk_bytes=64, caps=caps, outs=bufs[name])
+        chunks[name] = ctx.last_batch_stats.chunks
+    assert res["gpu"] == res["host"] and chunks["gpu"] == chunks["host"] == GOOD
+    assert ctx.last_mixed_coder_files() == (GOOD, 0)
+    for k, (status, jpg, size) in enumerate(res["gpu"]):
+        assert np.array_equal(bufs["gpu"][k], bufs["host"][k]), k
+        if k in (BAD, short):
+            assert status == -1 and (bufs["gpu"][k] == 0xA5).all(), k
+        else:
+            assert status == 0 and jpg == want[k] and (bufs["gpu"][k][size:] == 0xA5).all(), k
+    assert res["gpu"][short][2] == len(want[short])
+
+
 def test_hardcaml_arithmetic_is_refused(ctx, raws):
     import video_coding_amd as hvc
     ctx.set_encode_arithmetic("hardcaml")

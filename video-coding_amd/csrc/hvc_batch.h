@@ -1,6 +1,7 @@
 // hvc_batch.h -- what the batch decode pipelines share (internal): the streams and events of a pipeline call, and the
 // orchestrating loop of the two pipelines with the host reader (decode_batch_impl, decode_batch_mixed_impl):
 //   host Huffman threads (hvc_feed.h) || hipMemcpyAsync (copy stream) || block stage (compute stream)
+// and, at the end, the part the two mixed ENCODE file pipelines run in common (MixedEncodeFront, encode_mixed_chunks)
 #ifndef HVC_BATCH_H
 #define HVC_BATCH_H
 
@@ -88,5 +89,34 @@ inline int host_reader_chunks(hvc_ctx *c, hvc::ChunkFeed &feed, int n_chunks, in
     }
     return rc;
 }
+
+// The two mixed ENCODE file pipelines (host coder: hvc_capi_mixed_encode.hip; GPU coder: hvc_capi_mixed_coder.hip) are one
+// pipeline up to the coefficient slot.  encode_mixed_chunks (hvc_capi_mixed_encode.hip) runs that part: the chunk cut
+// (hvc_mixed_encode_chunks.h), streams, events and the rings of the pixel side, two feeds -- the padding workers fill pinned
+// pixel slots for the orchestrating thread, the orchestrating thread hands the slots behind the block stage to the pipeline's
+// own workers --, per chunk the upload and the block stage (RGB input: the colour stage in front of it) into ed_out[slot],
+// and the way out: both feeds ended, the streams drained, what it knows of `stats` filled (the pipeline adds entropy_ms_sum
+// and coef_bytes).  The pipeline fills in what stands behind the block stage before the call and reads the rest after it.
+struct MixedEncodeFront {
+    int max_files_per_chunk = 0; // a chunk closes at that many files (0: no cap)
+    bool down_stream = false;    // the pipeline also uses c->down_stream and ev_gpu[]
+    std::function<int()> setup;  // (optional) rings and tables of its own, sized by `plan`, before anything starts
+    std::function<void()> worker;             // body of a thread of the feed `codf`: items are positions in plan.take
+    std::function<int(int k, int slot)> stage; // enqueues what follows chunk k's block stage: an hvc_status
+    std::function<int(int k)> retire;         // chunk k is enqueued and its upload through: what it retires of the chunks before
+    std::function<int()> drain;               // behind the last chunk: what retire has left
+    // the call under way
+    hvc::MixedEncodeChunks plan;
+    hvc::ChunkFeed *codf = nullptr; // ring 0: chunk k may be read by the workers once release(k) says it has landed
+    int threads = 0;                // as clamped
+    bool ran = false;               // the pipeline started: `stats` are filled
+    std::chrono::steady_clock::time_point wall0;
+    double h2d_ms = 0, k_ms = 0, d2h_ms = 0; // retire / drain add the chunks' event times
+    static long long ns_since(std::chrono::steady_clock::time_point t0) {
+        return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    }
+};
+int encode_mixed_chunks(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
+                        size_t chunk_bytes, uint8_t *const *jpegs, const MixedEncodeInput &in, MixedEncodeFront &fr, hvc_batch_stats *stats);
 
 #endif

@@ -257,8 +257,6 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
     }
     if ((r = ring_ensure(c, enc_rings(c), {in_bytes, out_bytes, in_bytes, out_bytes}))) return r;
 
-    const int cw = chroma == 444 ? width : width / 2, ch = chroma == 420 ? height / 2 : height;
-    const int sw[3] = {width, cw, cw}, sh[3] = {height, ch, ch};
     struct Task {
         int kind, frame; // 0 = pad into the pinned pixel ring, 1 = entropy-code from the pinned coefficient ring
     };
@@ -285,24 +283,8 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
             int e = HVC_OK;
             if (error.load() == 0) try {
                 if (t.kind == 0) {
-                    uint8_t *rec = c->eh_in[slot].as<uint8_t>() + (size_t)(f - k * C) * pix_bytes;
-                    const uint8_t *src = frames[f];
-                    for (int i = 0; i < 3; i++) {
-                        const hvc_component &L = info.layout[i];
-                        const int pw = info.comp[i].decoded_width, ph = info.comp[i].decoded_height;
-                        const int bw = sw[i] < pw ? sw[i] : pw, bh = sh[i] < ph ? sh[i] : ph;
-                        uint8_t *dst = rec + L.plane_offset;
-                        for (int row = 0; row < ph; row++) {
-                            uint8_t *d = dst + (size_t)row * L.stride;
-                            if (row < bh) {
-                                std::memcpy(d, src + (size_t)row * sw[i], (size_t)bw);
-                                std::memset(d + bw, 0, (size_t)(pw - bw)); // Plane.create is zero-filled
-                            } else {
-                                std::memset(d, 0, (size_t)pw);
-                            }
-                        }
-                        src += (size_t)sw[i] * sh[i];
-                    }
+                    // (the info's actual plane sizes are width x height and the chroma's by `chroma`: tests/test_mixed_encode_chunks.py)
+                    pad_frame(info, frames[f], c->eh_in[slot].as<uint8_t>() + (size_t)(f - k * C) * pix_bytes);
                 } else if (!gpu_entropy) {
                     const int16_t *cf = c->eh_out[slot].as<const int16_t>() + (size_t)(f - k * C) * info.coef_count;
                     e = opt ? hvc::entropy_encode_optimised(&info, cf, jpegs[f], caps[f], &sizes[f], ri)

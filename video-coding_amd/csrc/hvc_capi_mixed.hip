@@ -13,26 +13,6 @@
 #include "hvc_mixed_reader.h"
 #include "hvc_resize_plan.h"
 
-namespace {
-
-// the plan as one image: planes | tables | map | pairs, each part on 16 bytes (pairs: the libjpeg-exact block stage's table
-// records, n_pairs words -- none under the model's arithmetic, whose image is the first three parts and nothing else)
-struct ImageParts {
-    size_t planes = 0, tables = 0, map = 0, pairs = 0, total = 0;
-};
-ImageParts image_parts(const hvc::MixedPlan &plan, size_t n_pairs) {
-    ImageParts p;
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    p.planes = 0;
-    p.tables = up(plan.planes.size() * sizeof(hvc::MixedPlaneK));
-    p.map = p.tables + up(plan.tables.size() * sizeof(hvc::MixedTableK));
-    p.pairs = p.map + up(plan.map.size() * sizeof(unsigned));
-    p.total = p.pairs + up(n_pairs * sizeof(unsigned));
-    return p;
-}
-
-} // namespace
-
 // A plan's image in a device buffer of the context, in stream order: uploaded from the pinned copy unless the device
 // already holds these bytes.  (hvc_ctx.h: the mixed encode plans use it too)
 int upload_image(hvc_ctx *c, PlanBuf &b, const std::vector<unsigned char> &img) {
@@ -55,26 +35,39 @@ int upload_image(hvc_ctx *c, PlanBuf &b, const std::vector<unsigned char> &img) 
     return HVC_OK;
 }
 
+// ... made of `parts` one after another, each on 16 bytes: at[i] = where part i starts in the image
+int upload_parts(hvc_ctx *c, PlanBuf &b, std::initializer_list<ImagePart> parts, size_t *at) {
+    size_t total = 0, i = 0;
+    for (const ImagePart &p : parts) at[i++] = total, total += (p.bytes + 15) & ~(size_t)15;
+    std::vector<unsigned char> img(total, 0);
+    i = 0;
+    for (const ImagePart &p : parts) {
+        if (p.bytes) std::memcpy(img.data() + at[i], p.p, p.bytes);
+        i++;
+    }
+    return upload_image(c, b, img);
+}
+
 namespace {
 
-// the block stage's tables in c->mixed_plan; pairs (optional): the records of mixed_islow_pairs_build behind them, *d_pairs
-// = where they are on the device
+// the block stage's tables in c->mixed_plan, planes | tables | map | pairs; pairs (optional): the libjpeg-exact block stage's
+// table records (mixed_islow_pairs_build) -- none under the model's arithmetic, whose image is the first three parts and
+// nothing else; *d_pairs = where they are on the device
 int upload_plan(hvc_ctx *c, const hvc::MixedPlan &plan, hvc::MixedParams &P, const std::vector<unsigned> *pairs = nullptr,
                 const unsigned **d_pairs = nullptr) {
-    const ImageParts ip = image_parts(plan, pairs ? pairs->size() : 0);
-    std::vector<unsigned char> img(ip.total, 0);
-    if (pairs && !pairs->empty()) std::memcpy(img.data() + ip.pairs, pairs->data(), pairs->size() * sizeof(unsigned));
-    std::memcpy(img.data() + ip.planes, plan.planes.data(), plan.planes.size() * sizeof(hvc::MixedPlaneK));
-    std::memcpy(img.data() + ip.tables, plan.tables.data(), plan.tables.size() * sizeof(hvc::MixedTableK));
-    std::memcpy(img.data() + ip.map, plan.map.data(), plan.map.size() * sizeof(unsigned));
-    const int r = upload_image(c, c->mixed_plan, img);
+    size_t at[4];
+    const int r = upload_parts(c, c->mixed_plan,
+                               {{plan.planes.data(), plan.planes.size() * sizeof(hvc::MixedPlaneK)},
+                                {plan.tables.data(), plan.tables.size() * sizeof(hvc::MixedTableK)},
+                                {plan.map.data(), plan.map.size() * sizeof(unsigned)},
+                                {pairs ? pairs->data() : nullptr, pairs ? pairs->size() * sizeof(unsigned) : 0}}, at);
     if (r) return r;
     const unsigned char *d = c->mixed_plan.d.as<const unsigned char>();
-    P.planes = reinterpret_cast<const hvc::MixedPlaneK *>(d + ip.planes);
-    P.tables = reinterpret_cast<const hvc::MixedTableK *>(d + ip.tables);
-    P.map = reinterpret_cast<const unsigned *>(d + ip.map);
+    P.planes = reinterpret_cast<const hvc::MixedPlaneK *>(d + at[0]);
+    P.tables = reinterpret_cast<const hvc::MixedTableK *>(d + at[1]);
+    P.map = reinterpret_cast<const unsigned *>(d + at[2]);
     P.n_units = (unsigned)plan.map.size();
-    if (d_pairs) *d_pairs = reinterpret_cast<const unsigned *>(d + ip.pairs);
+    if (d_pairs) *d_pairs = reinterpret_cast<const unsigned *>(d + at[3]);
     return HVC_OK;
 }
 
@@ -86,18 +79,16 @@ int upload_plan(hvc_ctx *c, const hvc::MixedPlan &plan, hvc::MixedParams &P, con
 int mixed_rgb_launch_plan(hvc_ctx *c, const hvc::MixedRgbPlan &plan, int layout, const uint8_t *d_yuv, uint8_t *d_rgb, bool profile,
                           bool to_ycc) {
     if (plan.map.empty()) return HVC_OK; // no pixel at all: nothing to launch
-    const size_t map_at = (plan.images.size() * sizeof(hvc::MixedRgbImageK) + 15) & ~(size_t)15;
-    std::vector<unsigned char> img(map_at + ((plan.map.size() * sizeof(unsigned) + 15) & ~(size_t)15), 0);
-    std::memcpy(img.data(), plan.images.data(), plan.images.size() * sizeof(hvc::MixedRgbImageK));
-    std::memcpy(img.data() + map_at, plan.map.data(), plan.map.size() * sizeof(unsigned));
-    const int r = upload_image(c, c->mixed_rgb_plan, img);
+    size_t at[2];
+    const int r = upload_parts(c, c->mixed_rgb_plan, {{plan.images.data(), plan.images.size() * sizeof(hvc::MixedRgbImageK)},
+                                                      {plan.map.data(), plan.map.size() * sizeof(unsigned)}}, at);
     if (r) return r;
     hvc::MixedRgbParams P;
     std::memset(&P, 0, sizeof P);
     P.yuv = d_yuv;
     P.rgb = d_rgb;
     P.images = c->mixed_rgb_plan.d.as<const hvc::MixedRgbImageK>();
-    P.map = reinterpret_cast<const unsigned *>(c->mixed_rgb_plan.d.as<const unsigned char>() + map_at);
+    P.map = reinterpret_cast<const unsigned *>(c->mixed_rgb_plan.d.as<const unsigned char>() + at[1]);
     P.n_units = (unsigned)plan.map.size();
     P.planar = layout == HVC_RGB_PLANAR;
     const int slot = (int)(c->k_calls % HVC_PROF_RING);

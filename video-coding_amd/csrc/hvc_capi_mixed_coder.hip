@@ -1,7 +1,8 @@
 // hvc_capi_mixed_coder.hip -- the MIXED GPU Huffman coder behind the C ABI (hvc_huff_mixed.hip, hvc_huff_mixed_plan.cpp):
 // the coder alone over a set of coefficient records (behind hvc_huffman_encode_frames_mixed) and the file pipeline built on it
 // (behind hvc_jpeg_encode_batch_mixed_gpu); the entry points themselves stand in hvc_capi_files.hip.
-// The pipeline is encode_batch_mixed_impl's (hvc_capi_mixed_encode.hip) with the coder stage of hvc_jpeg_encode_batch_gpu:
+// The pipeline is encode_batch_mixed_impl's up to the coefficient slot -- both run encode_mixed_chunks (MixedEncodeFront,
+// hvc_batch.h; hvc_capi_mixed_encode.hip) -- with the coder stage of hvc_jpeg_encode_batch_gpu behind it:
 //   host threads: Plane.blit_available into zero-padded planes (pinned ring)  [RGB input, MixedEncodeInput: the image's rows, tight]
 //   copy stream:  hipMemcpyAsync H2D           compute stream: [RGB input: the plane slot cleared, k_rgb_to_ycc_mixed into it,]
 //                                               k_encode_mixed into the device slot, the mixed coder over it,
@@ -21,20 +22,16 @@ namespace {
 int mixed_coder_prepare(hvc_ctx *c, const hvc::HuffMixedPlan &plan, const int16_t *d_coefs, uint8_t *d_out, size_t out_cap,
                         unsigned long long *d_offsets, bool optimised, bool partial, hvc::HuffMixedParams &P) {
     std::memset(&P, 0, sizeof P);
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t nf = plan.files.size();
-    const size_t planes_at = up(nf * sizeof(hvc::HuffMixedFileK));
-    const size_t map_at = planes_at + up(plan.planes.size() * sizeof(hvc::HuffMixedPlaneK));
-    std::vector<unsigned char> img(map_at + up(plan.map.size() * sizeof(unsigned)), 0);
-    std::memcpy(img.data(), plan.files.data(), nf * sizeof(hvc::HuffMixedFileK));
-    std::memcpy(img.data() + planes_at, plan.planes.data(), plan.planes.size() * sizeof(hvc::HuffMixedPlaneK));
-    std::memcpy(img.data() + map_at, plan.map.data(), plan.map.size() * sizeof(unsigned));
-    int r = upload_image(c, c->mixed_huff_plan, img);
+    size_t at[3];
+    int r = upload_parts(c, c->mixed_huff_plan, {{plan.files.data(), nf * sizeof(hvc::HuffMixedFileK)},
+                                                 {plan.planes.data(), plan.planes.size() * sizeof(hvc::HuffMixedPlaneK)},
+                                                 {plan.map.data(), plan.map.size() * sizeof(unsigned)}}, at);
     if (r) return r;
     const unsigned char *d = c->mixed_huff_plan.d.as<const unsigned char>();
     P.files = reinterpret_cast<const hvc::HuffMixedFileK *>(d);
-    P.planes = reinterpret_cast<const hvc::HuffMixedPlaneK *>(d + planes_at);
-    P.map = reinterpret_cast<const unsigned *>(d + map_at);
+    P.planes = reinterpret_cast<const hvc::HuffMixedPlaneK *>(d + at[1]);
+    P.map = reinterpret_cast<const unsigned *>(d + at[2]);
     P.n_files = (unsigned)nf;
     P.n_units = (unsigned)plan.map.size();
     P.coefs = d_coefs;
@@ -195,134 +192,48 @@ int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const 
         for (int f = 0; f < n_frames; f++) mine[(size_t)f] = status[f] == HVC_OK;
         return host_pass(mine, stats);
     }
-    if (chunk_bytes == 0) chunk_bytes = (size_t)64 << 20;
-    if (threads < 1) threads = 1;
-    if (threads > 256) threads = 256;
     constexpr int NB = hvc_ctx::RING;
-
-    // the frames that take part, cut into chunks as encode_batch_mixed_impl cuts them (+ the coder's cap on a chunk's files)
-    struct Chunk {
-        int first = 0, count = 0; // positions in `take`
-        size_t pix_bytes = 0, coef_elems = 0, rgb_bytes = 0;
-    };
-    std::vector<int> take, chunk_of((size_t)n_frames, -1);
-    std::vector<Chunk> chunks;
-    std::vector<size_t> pix_rel((size_t)n_frames, 0), coef_rel((size_t)n_frames, 0), rgb_rel(in.rgb ? (size_t)n_frames : 0, 0);
-    for (int f = 0; f < n_frames; f++) {
-        if (status[f] != HVC_OK) continue;
-        if (!frames[f] || !jpegs[f]) return HVC_E_INVALID_ARG;
-        const size_t zero = 0;
-        hvc::MixedEncodePlan own;
-        int e = hvc_jpeg_encoder_check(&infos[f]);
-        if (!e) e = hvc::mixed_encode_plan_build(&infos[f], &zero, &zero, nullptr, 1, own);
-        if (!e && (infos[f].pixel_bytes == 0 || infos[f].coef_count == 0)) e = HVC_E_INVALID_ARG;
-        for (int i = 0; i < 3 && !e; i++) { // what the padding workers go by
-            const hvc_jpeg_component &k = infos[f].comp[i];
-            if (k.decoded_width != 8 * infos[f].layout[i].blocks_w || k.decoded_height != 8 * infos[f].layout[i].blocks_h ||
-                k.actual_width < 0 || k.actual_height < 0)
-                e = HVC_E_INVALID_ARG;
-        }
-        if (!e && in.rgb) e = encode_rgb_frame_status(infos[f], in, f);
-        if (e) {
-            status[f] = e;
-            continue;
-        }
-        size_t ps, cs;
-        encode_frame_spans(infos[f], ps, cs);
-        if (ps > infos[f].pixel_bytes || cs > infos[f].coef_count) return HVC_E_INVALID_ARG; // (not a record of the layout call)
-        const size_t pb = (infos[f].pixel_bytes + 63) & ~(size_t)63;
-        if (chunks.empty() || (chunks.back().count > 0 && (chunks.back().pix_bytes + pb > chunk_bytes ||
-                                                           chunks.back().count >= HVC_HUFF_MIXED_MAX_FILES))) {
-            chunks.emplace_back();
-            chunks.back().first = (int)take.size();
-        }
-        Chunk &k = chunks.back();
-        pix_rel[(size_t)f] = k.pix_bytes;
-        coef_rel[(size_t)f] = k.coef_elems;
-        chunk_of[(size_t)f] = (int)chunks.size() - 1;
-        k.pix_bytes += pb;
-        k.coef_elems += (infos[f].coef_count + 31) & ~(size_t)31;
-        if (in.rgb) { // the tight image in the chunk's RGB slot, on 64 bytes
-            rgb_rel[(size_t)f] = k.rgb_bytes;
-            k.rgb_bytes += (encode_rgb_frame_bytes(infos[f], in) + 63) & ~(size_t)63;
-        }
-        k.count++;
-        take.push_back(f);
-    }
-    if (take.empty()) return HVC_OK;
-    const int n_chunks = (int)chunks.size(), n_take = (int)take.size();
-    size_t in_bytes = 0, out_bytes = 0, rgb_bytes = 0;
-    int largest = 0;
-    for (const Chunk &k : chunks) {
-        in_bytes = std::max(in_bytes, std::max(k.pix_bytes, k.rgb_bytes)); // (eh_in: the pinned images; ed_in: the planes)
-        rgb_bytes = std::max(rgb_bytes, k.rgb_bytes);
-        out_bytes = std::max(out_bytes, k.coef_elems * sizeof(int16_t));
-        largest = std::max(largest, k.count);
-    }
-
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    HIPCHK(c, c->copy_stream.ensure());
-    HIPCHK(c, c->down_stream.ensure());
-    for (int i = 0; i < NB; i++) {
-        HIPCHK(c, c->ev_up[i].ensure());
-        HIPCHK(c, c->ev_down[i].ensure());
-        for (int k = 0; k < 3; k++) HIPCHK(c, c->ev_et[i][k].ensure());
-        HIPCHK(c, c->ev_gpu[i].ensure());
-    }
     const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // each file its own tables (hvc_set_huffman_tables)
-    int r;
-    if (opt && (r = ring_ensure(c, enc_spec_rings(c), {(size_t)largest * 4 * sizeof(hvc_huff_spec)}))) return r;
-    // per slot: the packed segments on the device (capacity = the chunk's coefficient records, the uniform pipeline's rule),
-    // and (count + 1) offsets, the launch's status word and `count` file status words, on the device and pinned
-    const size_t words_at = ((size_t)largest + 2) * sizeof(unsigned long long);
-    const size_t off_bytes = words_at + (size_t)largest * sizeof(unsigned);
-    if ((r = ring_ensure(c, enc_seg_rings(c), {out_bytes, off_bytes, off_bytes}))) return r;
-    if ((r = ring_ensure(c, enc_rings(c), {in_bytes, out_bytes, in_bytes, out_bytes}))) return r;
-    if (in.rgb && (r = ring_ensure(c, enc_rgb_rings(c), {rgb_bytes}))) return r;
+    MixedEncodeFront fr; // the chunks are encode_batch_mixed_impl's but for the coder's cap on a chunk's files
+    fr.max_files_per_chunk = HVC_HUFF_MIXED_MAX_FILES;
+    fr.down_stream = true;
+    const hvc::MixedEncodeChunks &plan = fr.plan;
+    const std::vector<int> &take = plan.take;
 
     // what the orchestrating thread leaves for the assembling workers, per position in `take` (written before the chunk's
     // release, which the feed's mutex orders)
-    std::vector<char> by_gpu((size_t)n_take, 0), handed((size_t)n_frames, 0);
-    std::vector<unsigned long long> seg_at((size_t)n_take, 0), seg_len((size_t)n_take, 0);
-    std::vector<hvc_huff_spec> own_specs(opt ? 4 * (size_t)n_take : 0);
-    std::vector<std::vector<int>> chunk_files((size_t)n_chunks); // per chunk: the position in `take` of each file of its coder plan
-    std::vector<size_t> chunk_cap((size_t)n_chunks, 0);
+    std::vector<char> by_gpu, handed((size_t)n_frames, 0);
+    std::vector<unsigned long long> seg_at, seg_len;
+    std::vector<hvc_huff_spec> own_specs;
+    std::vector<std::vector<int>> chunk_files; // per chunk: the position in `take` of each file of its coder plan
+    std::vector<size_t> chunk_cap;
     unsigned long long seg_total = 0, gpu_done = 0, n_handed = 0;
-
-    std::atomic<long long> pad_ns{0}, ent_ns{0};
-    const auto wall0 = std::chrono::steady_clock::now();
-    const int pad_threads = (threads + 3) / 4;
-    if ((r = pool_ready(c, threads, pad_threads))) return r;
-    bool left = false;
-    hvc::ChunkFeed padf(c->pool, n_chunks, NB);
-    hvc::ChunkFeed codf(c->pool, n_chunks, 0, [&] { if (!left) padf.raise(HVC_E_INTERNAL); });
-    auto ns_since = [](std::chrono::steady_clock::time_point t0) {
-        return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    size_t words_at = 0;
+    std::atomic<long long> ent_ns{0};
+    fr.setup = [&]() {
+        int r;
+        if (opt && (r = ring_ensure(c, enc_spec_rings(c), {(size_t)plan.largest * 4 * sizeof(hvc_huff_spec)}))) return r;
+        // per slot: the packed segments on the device (capacity = the chunk's coefficient records, the uniform pipeline's rule),
+        // and (count + 1) offsets, the launch's status word and `count` file status words, on the device and pinned
+        words_at = ((size_t)plan.largest + 2) * sizeof(unsigned long long);
+        const size_t off_bytes = words_at + (size_t)plan.largest * sizeof(unsigned);
+        if ((r = ring_ensure(c, enc_seg_rings(c), {plan.out_bytes, off_bytes, off_bytes}))) return r;
+        by_gpu.assign(take.size(), 0);
+        seg_at.assign(take.size(), 0);
+        seg_len.assign(take.size(), 0);
+        own_specs.resize(opt ? 4 * take.size() : 0);
+        chunk_files.resize(plan.chunks.size());
+        chunk_cap.assign(plan.chunks.size(), 0);
+        return (int)HVC_OK;
     };
-    auto pad_worker = [&]() {
-        if (!pin_to_ctx_cpus(c)) padf.raise(HVC_E_INVALID_ARG); // hvc_set_host_cpus
-        for (;;) {
-            const int t = padf.claim();
-            if (t >= n_take || padf.error()) return;
-            const int f = take[(size_t)t], k = chunk_of[(size_t)f];
-            if (!padf.wait_slot(k)) return;
-            const auto t0 = std::chrono::steady_clock::now();
-            if (in.rgb)
-                encode_rgb_frame_copy(infos[f], in, f, frames[f], c->eh_in[k % NB].as<uint8_t>() + rgb_rel[(size_t)f]);
-            else
-                pad_frame(infos[f], frames[f], c->eh_in[k % NB].as<uint8_t>() + pix_rel[(size_t)f]);
-            pad_ns += ns_since(t0);
-            padf.report(k, 1, HVC_OK);
-        }
-    };
-    auto assemble_worker = [&]() { // header + the file's segment + EOI (complete_and_write_eoi, encoder.ml:507-510)
+    fr.worker = [&]() { // header + the file's segment + EOI (complete_and_write_eoi, encoder.ml:507-510)
+        hvc::ChunkFeed &codf = *fr.codf;
         if (!pin_to_ctx_cpus(c)) codf.raise(HVC_E_INVALID_ARG);
         std::vector<uint8_t> header;
         for (;;) {
             const int t = codf.claim();
-            if (t >= n_take || codf.error()) return;
-            const int f = take[(size_t)t], k = chunk_of[(size_t)f];
+            if (t >= (int)take.size() || codf.error()) return;
+            const int f = take[(size_t)t], k = plan.chunk_of[(size_t)f];
             if (!codf.wait_slot(k)) return;
             if (by_gpu[(size_t)t]) {
                 const auto t0 = std::chrono::steady_clock::now();
@@ -339,26 +250,59 @@ int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const 
                     jpegs[f][header.size() + seg + 1] = 0xd9;
                     status[f] = HVC_OK;
                 }
-                ent_ns += ns_since(t0);
+                ent_ns += MixedEncodeFront::ns_since(t0);
             }
             codf.report(k, 1, HVC_OK);
         }
     };
-    r = padf.start(pad_threads, pad_worker);
-    if (!r) r = codf.start(threads, assemble_worker);
-
-    int rc = r;
-    double h2d_ms = 0, k_ms = 0, d2h_ms = 0;
-    hipStream_t compute = c->stream;
-    std::vector<int> list, complete, back;
+    // behind the block stage: the coder over the chunk's records; a file its plan refuses is the host coder's
+    fr.stage = [&](int k, int slot) {
+        const hvc::MixedEncodeChunk &ch = plan.chunks[(size_t)k];
+        const int *list = take.data() + ch.first;
+        hipStream_t compute = c->stream;
+        int rc;
+        hvc::HuffMixedPlan hp;
+        if ((rc = hvc::huff_mixed_plan_build(infos, plan.coef_rel.data(), list, ch.count, opt, hp))) return rc;
+        std::vector<int> &files = chunk_files[(size_t)k];
+        for (int i = 0; i < ch.count; i++) {
+            if (hp.status[(size_t)i] == HVC_OK)
+                files.push_back(ch.first + i);
+            else
+                handed[(size_t)list[i]] = 1, n_handed++;
+        }
+        chunk_cap[(size_t)k] = ch.coef_elems * sizeof(int16_t);
+        const size_t nf = files.size();
+        unsigned long long *d_off = c->ed_off[slot].as<unsigned long long>();
+        hipError_t he;
+        if (nf) {
+            hvc::HuffMixedParams P;
+            if ((rc = mixed_coder_prepare(c, hp, c->ed_out[slot].as<const int16_t>(), c->ed_seg[slot].as<uint8_t>(), chunk_cap[(size_t)k], d_off,
+                                          opt, true, P)))
+                return rc;
+            he = hvc::launch_huffman_encode_mixed(P, compute);
+            if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][2], compute);
+            if (he == hipSuccess)
+                he = hipMemcpyAsync(c->eh_off[slot].p, d_off, (nf + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, compute);
+            if (he == hipSuccess) // (the context's scratch: copied before the next chunk's coder reuses it)
+                he = hipMemcpyAsync(c->eh_off[slot].as<unsigned char>() + words_at, P.file_status, nf * sizeof(unsigned),
+                                    hipMemcpyDeviceToHost, compute);
+            if (he == hipSuccess && opt)
+                he = hipMemcpyAsync(c->eh_specs[slot].p, P.specs, nf * 4 * sizeof(hvc_huff_spec), hipMemcpyDeviceToHost, compute);
+        } else {
+            he = hipEventRecord(c->ev_et[slot][2], compute);
+        }
+        if (he == hipSuccess) he = hipEventRecord(c->ev_gpu[slot], compute);
+        return he == hipSuccess ? (int)HVC_OK : fail_hip(c, he);
+    };
+    std::vector<int> complete, back;
     // chunk j's offsets and status words have landed: the hand-back decision, then exactly its segments on down_stream
     auto coded = [&](int j) {
         const int slot = j % NB;
         hipError_t he = wait_event(c->ev_gpu[slot]);
         if (he != hipSuccess) return fail_hip(c, he);
         float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev_et[slot][0], c->ev_up[slot]) == hipSuccess) h2d_ms += ms;
-        if (hipEventElapsedTime(&ms, c->ev_et[slot][1], c->ev_et[slot][2]) == hipSuccess) k_ms += ms;
+        if (hipEventElapsedTime(&ms, c->ev_et[slot][0], c->ev_up[slot]) == hipSuccess) fr.h2d_ms += ms;
+        if (hipEventElapsedTime(&ms, c->ev_et[slot][1], c->ev_et[slot][2]) == hipSuccess) fr.k_ms += ms;
         const std::vector<int> &files = chunk_files[(size_t)j];
         const int nf = (int)files.size();
         const unsigned long long *off = c->eh_off[slot].as<const unsigned long long>();
@@ -388,104 +332,38 @@ int encode_batch_mixed_gpu_impl(hvc_ctx *c, const uint8_t *const *frames, const 
         const hipError_t he = wait_event(c->ev_down[slot]);
         if (he != hipSuccess) return fail_hip(c, he);
         float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev_et[slot][0], c->ev_down[slot]) == hipSuccess) d2h_ms += ms;
-        codf.release(j);
+        if (hipEventElapsedTime(&ms, c->ev_et[slot][0], c->ev_down[slot]) == hipSuccess) fr.d2h_ms += ms;
+        fr.codf->release(j);
         return (int)HVC_OK;
     };
-    try {
-        for (int k = 0; k < n_chunks && rc == HVC_OK; k++) {
-            const Chunk &ch = chunks[(size_t)k];
-            const int slot = k % NB;
-            if ((rc = padf.wait_chunk(k, ch.count))) break;
-            // the slot's pinned segment buffer, its device segment buffer and its offsets are free again once chunk k - NB has
-            // been assembled (its downloads are behind it: ev_down[slot] was waited for before that chunk went to the workers)
-            if (k >= NB && (rc = codf.wait_chunk(k - NB, chunks[(size_t)(k - NB)].count))) break;
-            hipError_t he = hipEventRecord(c->ev_et[slot][0], c->copy_stream);
-            if (he == hipSuccess)
-                he = in.rgb ? hipMemcpyAsync(c->ed_rgb[slot].p, c->eh_in[slot].p, ch.rgb_bytes, hipMemcpyHostToDevice, c->copy_stream)
-                            : hipMemcpyAsync(c->ed_in[slot].p, c->eh_in[slot].p, ch.pix_bytes, hipMemcpyHostToDevice, c->copy_stream);
-            if (he == hipSuccess) he = hipEventRecord(c->ev_up[slot], c->copy_stream);
-            if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_up[slot], 0);
-            if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][1], compute);
-            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-            list.assign(take.begin() + ch.first, take.begin() + ch.first + ch.count);
-            if (in.rgb && (rc = encode_rgb_stage(c, in, infos, list.data(), ch.count, pix_rel.data(), rgb_rel.data(),
-                                                 c->ed_rgb[slot].as<const uint8_t>(), c->ed_in[slot].as<uint8_t>(), ch.pix_bytes)))
-                break;
-            hvc::MixedEncodePlan plan;
-            if ((rc = hvc::mixed_encode_plan_build(infos, coef_rel.data(), pix_rel.data(), list.data(), ch.count, plan))) break;
-            if ((rc = encode_mixed_launch_plan(c, plan, c->ed_in[slot].as<const uint8_t>(), c->ed_out[slot].as<int16_t>(), false))) break;
-            // the coder over the chunk's records; a file its plan refuses is the host coder's
-            hvc::HuffMixedPlan hp;
-            if ((rc = hvc::huff_mixed_plan_build(infos, coef_rel.data(), list.data(), ch.count, opt, hp))) break;
-            std::vector<int> &files = chunk_files[(size_t)k];
-            for (int i = 0; i < ch.count; i++) {
-                if (hp.status[(size_t)i] == HVC_OK)
-                    files.push_back(ch.first + i);
-                else
-                    handed[(size_t)list[(size_t)i]] = 1, n_handed++;
-            }
-            chunk_cap[(size_t)k] = ch.coef_elems * sizeof(int16_t);
-            const size_t nf = files.size();
-            unsigned long long *d_off = c->ed_off[slot].as<unsigned long long>();
-            if (nf) {
-                hvc::HuffMixedParams P;
-                if ((rc = mixed_coder_prepare(c, hp, c->ed_out[slot].as<const int16_t>(), c->ed_seg[slot].as<uint8_t>(), chunk_cap[(size_t)k],
-                                              d_off, opt, true, P)))
-                    break;
-                he = hvc::launch_huffman_encode_mixed(P, compute);
-                if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][2], compute);
-                if (he == hipSuccess)
-                    he = hipMemcpyAsync(c->eh_off[slot].p, d_off, (nf + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, compute);
-                if (he == hipSuccess) // (the context's scratch: copied before the next chunk's coder reuses it)
-                    he = hipMemcpyAsync(c->eh_off[slot].as<unsigned char>() + words_at, P.file_status, nf * sizeof(unsigned),
-                                        hipMemcpyDeviceToHost, compute);
-                if (he == hipSuccess && opt)
-                    he = hipMemcpyAsync(c->eh_specs[slot].p, P.specs, nf * 4 * sizeof(hvc_huff_spec), hipMemcpyDeviceToHost, compute);
-            } else {
-                he = hipEventRecord(c->ev_et[slot][2], compute);
-            }
-            if (he == hipSuccess) he = hipEventRecord(c->ev_gpu[slot], compute);
-            // wait for this chunk's upload, then hand the pinned pixel slot to chunk k + NB
-            if (he == hipSuccess) he = wait_event(c->ev_up[slot]);
-            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-            padf.release(k);
-            if (k > 1 && (rc = landed(k - 2))) break;
-            if (k > 0 && (rc = coded(k - 1))) break; // (while this chunk's kernels run)
-        }
-        if (rc == HVC_OK && n_chunks > 1) rc = landed(n_chunks - 2);
+    fr.retire = [&](int k) {
+        int rc = HVC_OK;
+        if (k > 1) rc = landed(k - 2);
+        if (rc == HVC_OK && k > 0) rc = coded(k - 1); // (while this chunk's kernels run)
+        return rc;
+    };
+    fr.drain = [&]() {
+        const int n_chunks = (int)plan.chunks.size();
+        int rc = HVC_OK;
+        if (n_chunks > 1) rc = landed(n_chunks - 2);
         if (rc == HVC_OK) rc = coded(n_chunks - 1);
         if (rc == HVC_OK) rc = landed(n_chunks - 1);
-        for (int k = std::max(0, n_chunks - NB); k < n_chunks && rc == HVC_OK; k++) rc = codf.wait_chunk(k, chunks[(size_t)k].count);
-    } catch (...) {
-        rc = hvc::exception_code();
-    }
-    if (rc != HVC_OK) { // both feeds end before either waits for the pool
-        padf.raise(rc);
-        codf.raise(rc);
-    }
-    left = true;
-    rc = padf.finish(rc);
-    rc = codf.finish(rc);
-    {
-        const hipError_t h1 = hipStreamSynchronize(compute), h2 = hipStreamSynchronize(c->copy_stream), h3 = hipStreamSynchronize(c->down_stream);
-        if (rc == HVC_OK && (h1 != hipSuccess || h2 != hipSuccess || h3 != hipSuccess))
-            rc = fail_hip(c, h1 != hipSuccess ? h1 : h2 != hipSuccess ? h2 : h3);
-    }
+        return rc;
+    };
+    int rc = encode_mixed_chunks(c, frames, infos, status, n_frames, threads, chunk_bytes, jpegs, in, fr, stats);
+    if (!fr.ran) return rc;
     c->mixed_coder_gpu_files = gpu_done;
     hvc_batch_stats host_stats;
     std::memset(&host_stats, 0, sizeof host_stats);
     if (rc == HVC_OK && n_handed) rc = host_pass(handed, &host_stats); // ONE pass behind the GPU chunks
-    if (stats) {
-        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    if (stats) { // (with the host pass's)
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - fr.wall0).count();
         stats->entropy_ms_sum = (double)ent_ns.load() * 1e-6 + host_stats.entropy_ms_sum;
-        stats->host_prep_ms_sum = (double)pad_ns.load() * 1e-6 + host_stats.host_prep_ms_sum;
-        stats->h2d_ms_sum = h2d_ms + host_stats.h2d_ms_sum;
-        stats->kernel_ms_sum = k_ms + host_stats.kernel_ms_sum;
-        stats->d2h_ms_sum = d2h_ms + host_stats.d2h_ms_sum;
-        stats->chunks = n_chunks + host_stats.chunks;
-        stats->threads = threads;
-        stats->frames_per_chunk = largest;
+        stats->host_prep_ms_sum += host_stats.host_prep_ms_sum;
+        stats->h2d_ms_sum += host_stats.h2d_ms_sum;
+        stats->kernel_ms_sum += host_stats.kernel_ms_sum;
+        stats->d2h_ms_sum += host_stats.d2h_ms_sum;
+        stats->chunks += host_stats.chunks;
         stats->coef_bytes = (uint64_t)seg_total + host_stats.coef_bytes; // bytes downloaded: the segments (+ the host pass's records)
     }
     return rc;

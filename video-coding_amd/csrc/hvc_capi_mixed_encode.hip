@@ -7,12 +7,15 @@
 //   host threads: Plane.blit_available into zero-padded planes (pinned ring)       encoder.ml:514-516
 //   copy stream:  hipMemcpyAsync H2D           compute stream: k_encode_mixed (a plan per chunk), D2H of the chunk's records
 //   host threads: write_headers + rle + write_bits + EOI per file, with its own info      encoder.ml:127-193, 371-418
-// With RGB images as input (MixedEncodeInput, hvc_ctx.h; behind hvc_jpeg_encode_batch_mixed_rgb) the host threads copy each
-// image's rows tight into the pinned ring, the copy stream uploads them into a device RGB slot, and on the compute stream a
-// hipMemsetAsync of the chunk's plane slot and k_rgb_to_ycc_mixed (hvc_mixed_rgb.hip) stand in front of k_encode_mixed.  The
-// colour pass alone is behind hvc_rgb_to_yuv_mixed, in front of one block stage behind hvc_encode_frames_mixed_rgb (below).
-// Two chunk feeds (hvc_feed.h) hand the chunks over: the padding workers fill pinned pixel slots for the orchestrating
-// thread, the orchestrating thread hands pinned coefficient slots to the coder workers.
+// With RGB images as input (MixedEncodeInput, hvc_mixed_encode_chunks.h; behind hvc_jpeg_encode_batch_mixed_rgb) the host
+// threads copy each image's rows tight into the pinned ring, the copy stream uploads them into a device RGB slot, and on the
+// compute stream a hipMemsetAsync of the chunk's plane slot and k_rgb_to_ycc_mixed (hvc_mixed_rgb.hip) stand in front of
+// k_encode_mixed.  The colour pass alone is behind hvc_rgb_to_yuv_mixed, in front of one block stage behind
+// hvc_encode_frames_mixed_rgb (below).
+// Everything up to the coefficient slot -- the chunk cut (hvc_mixed_encode_chunks.cpp, plain C++), the padding workers, the two
+// chunk feeds (hvc_feed.h), upload and block stage per chunk, the way out -- is encode_mixed_chunks (MixedEncodeFront,
+// hvc_batch.h), which the pipeline with the GPU coder (hvc_capi_mixed_coder.hip) runs too; encode_batch_mixed_impl adds the
+// download of the records and the coder workers.
 #include "hvc_batch.h"
 #include "hvc_mixed_encode.h"
 #include "hvc_mixed_rgb.h"
@@ -21,27 +24,22 @@ namespace {
 
 // the plan as one image: planes | tables | map, each part on 16 bytes, in c->mixed_enc_plan
 int upload_encode_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, hvc::MixedEncodeParams &P) {
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t tables_at = up(plan.planes.size() * sizeof(hvc::MixedPlaneK));
-    const size_t map_at = tables_at + up(plan.tables.size() * sizeof(hvc::MixedEncTableK));
-    std::vector<unsigned char> img(map_at + up(plan.map.size() * sizeof(unsigned)), 0);
-    std::memcpy(img.data(), plan.planes.data(), plan.planes.size() * sizeof(hvc::MixedPlaneK));
-    std::memcpy(img.data() + tables_at, plan.tables.data(), plan.tables.size() * sizeof(hvc::MixedEncTableK));
-    std::memcpy(img.data() + map_at, plan.map.data(), plan.map.size() * sizeof(unsigned));
-    const int r = upload_image(c, c->mixed_enc_plan, img);
+    size_t at[3];
+    const int r = upload_parts(c, c->mixed_enc_plan, {{plan.planes.data(), plan.planes.size() * sizeof(hvc::MixedPlaneK)},
+                                                      {plan.tables.data(), plan.tables.size() * sizeof(hvc::MixedEncTableK)},
+                                                      {plan.map.data(), plan.map.size() * sizeof(unsigned)}}, at);
     if (r) return r;
     const unsigned char *d = c->mixed_enc_plan.d.as<const unsigned char>();
     P.planes = reinterpret_cast<const hvc::MixedPlaneK *>(d);
-    P.tables = reinterpret_cast<const hvc::MixedEncTableK *>(d + tables_at);
-    P.map = reinterpret_cast<const unsigned *>(d + map_at);
+    P.tables = reinterpret_cast<const hvc::MixedEncTableK *>(d + at[1]);
+    P.map = reinterpret_cast<const unsigned *>(d + at[2]);
     P.n_units = (unsigned)plan.map.size();
     return HVC_OK;
 }
 
 } // namespace
 
-// The block stage of a plan on DEVICE memory, enqueued on c->stream (also the first stage of the pipeline with the GPU coder,
-// hvc_capi_mixed_coder.hip, as pad_frame and encode_frame_spans below)
+// The block stage of a plan on DEVICE memory, enqueued on c->stream
 int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const uint8_t *d_pixels, int16_t *d_coefs, bool profile) {
     if (plan.map.empty()) return HVC_OK; // no block at all: nothing to launch
     if (((uintptr_t)d_coefs & 15) || ((uintptr_t)d_pixels & 7)) return HVC_E_ALIGNMENT;
@@ -56,38 +54,6 @@ int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const
     if (e != hipSuccess) return fail_hip(c, e);
     if (profile) c->k_calls++;
     return HVC_OK;
-}
-
-// what a frame's records cover: bytes of pixels, elements of coefficients
-void encode_frame_spans(const hvc_jpeg_info &fi, size_t &pixel_span, size_t &coef_span) {
-    pixel_span = coef_span = 0;
-    for (int i = 0; i < fi.n_comp && i < 4; i++) {
-        const hvc_component &k = fi.layout[i];
-        if (k.blocks_w <= 0 || k.blocks_h <= 0) continue;
-        coef_span = std::max(coef_span, k.coef_offset + (size_t)k.blocks_w * k.blocks_h * 64);
-        pixel_span = std::max(pixel_span, k.plane_offset + ((size_t)k.blocks_h * 8 - 1) * k.stride + (size_t)k.blocks_w * 8);
-    }
-}
-
-// Plane.blit_available of a raw planar frame (tight Y, U, V of the info's actual sizes) into the zero-padded planes of `rec`
-void pad_frame(const hvc_jpeg_info &info, const uint8_t *src, uint8_t *rec) {
-    for (int i = 0; i < 3; i++) {
-        const hvc_component &L = info.layout[i];
-        const int sw = info.comp[i].actual_width, sh = info.comp[i].actual_height;
-        const int pw = info.comp[i].decoded_width, ph = info.comp[i].decoded_height;
-        const int bw = sw < pw ? sw : pw, bh = sh < ph ? sh : ph;
-        uint8_t *dst = rec + L.plane_offset;
-        for (int row = 0; row < ph; row++) {
-            uint8_t *d = dst + (size_t)row * L.stride;
-            if (row < bh) {
-                std::memcpy(d, src + (size_t)row * sw, (size_t)bw);
-                std::memset(d + bw, 0, (size_t)(pw - bw)); // Plane.create is zero-filled
-            } else {
-                std::memset(d, 0, (size_t)pw);
-            }
-        }
-        src += (size_t)sw * sh;
-    }
 }
 
 // behind hvc_encode_frames_mixed (hvc_capi_files.hip)
@@ -139,222 +105,6 @@ int encode_frames_mixed_impl(hvc_ctx *c, const uint8_t *pixels, const size_t *pi
     return HVC_OK;
 }
 
-// behind hvc_jpeg_encode_batch_mixed (hvc_capi_files.hip)
-int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
-                            size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats,
-                            const MixedEncodeInput &in) {
-    if (!c || !frames || !infos || !status || !jpegs || !caps || !sizes || n_frames < 0) return HVC_E_INVALID_ARG;
-    if (c->enc_arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG;
-    if (in.rgb && in.layout != HVC_RGB_INTERLEAVED && in.layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (n_frames == 0) return HVC_OK;
-    if (chunk_bytes == 0) chunk_bytes = (size_t)64 << 20;
-    if (threads < 1) threads = 1;
-    if (threads > 256) threads = 256;
-    constexpr int NB = hvc_ctx::RING;
-
-    // the frames that take part, cut into chunks by the bytes of their padded pixel records; a frame the block stage or the
-    // coder would refuse gets its own status here and is left out
-    struct Chunk {
-        int first = 0, count = 0; // positions in `take`
-        size_t pix_bytes = 0, coef_elems = 0, rgb_bytes = 0;
-    };
-    std::vector<int> take, chunk_of((size_t)n_frames, -1);
-    std::vector<Chunk> chunks;
-    std::vector<size_t> pix_rel((size_t)n_frames, 0), coef_rel((size_t)n_frames, 0), rgb_rel(in.rgb ? (size_t)n_frames : 0, 0);
-    for (int f = 0; f < n_frames; f++) {
-        if (status[f] != HVC_OK) continue;
-        if (!frames[f] || !jpegs[f]) return HVC_E_INVALID_ARG;
-        const size_t zero = 0;
-        hvc::MixedEncodePlan own;
-        int e = hvc_jpeg_encoder_check(&infos[f]);
-        if (!e) e = hvc::mixed_encode_plan_build(&infos[f], &zero, &zero, nullptr, 1, own);
-        if (!e && (infos[f].pixel_bytes == 0 || infos[f].coef_count == 0)) e = HVC_E_INVALID_ARG;
-        for (int i = 0; i < 3 && !e; i++) { // what the padding workers go by
-            const hvc_jpeg_component &k = infos[f].comp[i];
-            if (k.decoded_width != 8 * infos[f].layout[i].blocks_w || k.decoded_height != 8 * infos[f].layout[i].blocks_h ||
-                k.actual_width < 0 || k.actual_height < 0)
-                e = HVC_E_INVALID_ARG;
-        }
-        if (!e && in.rgb) e = encode_rgb_frame_status(infos[f], in, f);
-        if (e) {
-            status[f] = e;
-            continue;
-        }
-        size_t ps, cs;
-        encode_frame_spans(infos[f], ps, cs);
-        if (ps > infos[f].pixel_bytes || cs > infos[f].coef_count) return HVC_E_INVALID_ARG; // (not a record of the layout call)
-        const size_t pb = (infos[f].pixel_bytes + 63) & ~(size_t)63;
-        if (chunks.empty() || (chunks.back().count > 0 && chunks.back().pix_bytes + pb > chunk_bytes)) {
-            chunks.emplace_back();
-            chunks.back().first = (int)take.size();
-        }
-        Chunk &k = chunks.back();
-        pix_rel[(size_t)f] = k.pix_bytes;
-        coef_rel[(size_t)f] = k.coef_elems;
-        chunk_of[(size_t)f] = (int)chunks.size() - 1;
-        k.pix_bytes += pb;
-        k.coef_elems += (infos[f].coef_count + 31) & ~(size_t)31;
-        if (in.rgb) { // the tight image in the chunk's RGB slot, on 64 bytes
-            rgb_rel[(size_t)f] = k.rgb_bytes;
-            k.rgb_bytes += (encode_rgb_frame_bytes(infos[f], in) + 63) & ~(size_t)63;
-        }
-        k.count++;
-        take.push_back(f);
-    }
-    if (take.empty()) return HVC_OK;
-    const int n_chunks = (int)chunks.size(), n_take = (int)take.size();
-    size_t in_bytes = 0, out_bytes = 0, rgb_bytes = 0;
-    int largest = 0;
-    uint64_t coef_total = 0;
-    for (const Chunk &k : chunks) {
-        in_bytes = std::max(in_bytes, std::max(k.pix_bytes, k.rgb_bytes)); // (eh_in: the pinned images; ed_in: the planes)
-        rgb_bytes = std::max(rgb_bytes, k.rgb_bytes);
-        out_bytes = std::max(out_bytes, k.coef_elems * sizeof(int16_t));
-        largest = std::max(largest, k.count);
-        coef_total += k.coef_elems * sizeof(int16_t);
-    }
-
-    DeviceGuard g(c->device);
-    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    HIPCHK(c, c->copy_stream.ensure());
-    for (int i = 0; i < NB; i++) {
-        HIPCHK(c, c->ev_up[i].ensure());
-        HIPCHK(c, c->ev_down[i].ensure());
-        for (int k = 0; k < 3; k++) HIPCHK(c, c->ev_et[i][k].ensure());
-    }
-    int r = ring_ensure(c, enc_rings(c), {in_bytes, out_bytes, in_bytes, out_bytes}); // (a frame larger than chunk_bytes: the ring grows)
-    if (r) return r;
-    if (in.rgb && (r = ring_ensure(c, enc_rgb_rings(c), {rgb_bytes}))) return r;
-    const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // each file its own tables (hvc_set_huffman_tables)
-    const int ri = c->restart_interval;                    // DRI + RSTn every ri MCUs (hvc_set_restart_interval)
-
-    std::atomic<long long> pad_ns{0}, ent_ns{0};
-    const auto wall0 = std::chrono::steady_clock::now();
-    const int pad_threads = (threads + 3) / 4; // (padding is a copy: a quarter of the coder's threads keeps ahead of them)
-    if ((r = pool_ready(c, threads, pad_threads))) return r;
-    bool left = false; // the coder feed goes first when the call is left: it ends the padding workers with it
-    hvc::ChunkFeed padf(c->pool, n_chunks, NB);
-    // ring 0: chunk k may be read by the coder workers once release(k) says its records have landed
-    hvc::ChunkFeed codf(c->pool, n_chunks, 0, [&] { if (!left) padf.raise(HVC_E_INTERNAL); });
-    auto ns_since = [](std::chrono::steady_clock::time_point t0) {
-        return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-    };
-    auto pad_worker = [&]() {
-        if (!pin_to_ctx_cpus(c)) padf.raise(HVC_E_INVALID_ARG); // hvc_set_host_cpus
-        for (;;) {
-            const int t = padf.claim();
-            if (t >= n_take || padf.error()) return;
-            const int f = take[(size_t)t], k = chunk_of[(size_t)f];
-            if (!padf.wait_slot(k)) return;
-            const auto t0 = std::chrono::steady_clock::now();
-            if (in.rgb)
-                encode_rgb_frame_copy(infos[f], in, f, frames[f], c->eh_in[k % NB].as<uint8_t>() + rgb_rel[(size_t)f]);
-            else
-                pad_frame(infos[f], frames[f], c->eh_in[k % NB].as<uint8_t>() + pix_rel[(size_t)f]);
-            pad_ns += ns_since(t0);
-            padf.report(k, 1, HVC_OK);
-        }
-    };
-    auto code_worker = [&]() {
-        if (!pin_to_ctx_cpus(c)) codf.raise(HVC_E_INVALID_ARG);
-        for (;;) {
-            const int t = codf.claim();
-            if (t >= n_take || codf.error()) return;
-            const int f = take[(size_t)t], k = chunk_of[(size_t)f];
-            if (!codf.wait_slot(k)) return;
-            const auto t0 = std::chrono::steady_clock::now();
-            const int16_t *cf = c->eh_out[k % NB].as<const int16_t>() + coef_rel[(size_t)f];
-            const int e = opt ? hvc::entropy_encode_optimised(&infos[f], cf, jpegs[f], caps[f], &sizes[f], ri)
-                              : hvc::entropy_encode_file(&infos[f], nullptr, cf, jpegs[f], caps[f], &sizes[f], ri);
-            ent_ns += ns_since(t0);
-            status[f] = e; // the file's own result: it stops nobody else
-            codf.report(k, 1, HVC_OK);
-        }
-    };
-    r = padf.start(pad_threads, pad_worker);
-    if (!r) r = codf.start(threads, code_worker);
-
-    int rc = r;
-    double h2d_ms = 0, k_ms = 0, d2h_ms = 0;
-    hipStream_t compute = c->stream;
-    std::vector<int> list;
-    // chunk j's records have landed: its times are read, its pinned slot goes to the coder workers
-    auto landed = [&](int j) {
-        const int slot = j % NB;
-        const hipError_t he = wait_event(c->ev_down[slot]);
-        if (he != hipSuccess) return fail_hip(c, he);
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev_et[slot][0], c->ev_up[slot]) == hipSuccess) h2d_ms += ms;
-        if (hipEventElapsedTime(&ms, c->ev_et[slot][1], c->ev_et[slot][2]) == hipSuccess) k_ms += ms;
-        if (hipEventElapsedTime(&ms, c->ev_et[slot][2], c->ev_down[slot]) == hipSuccess) d2h_ms += ms;
-        codf.release(j);
-        return (int)HVC_OK;
-    };
-    try {
-        for (int k = 0; k < n_chunks && rc == HVC_OK; k++) {
-            const Chunk &ch = chunks[(size_t)k];
-            const int slot = k % NB;
-            if ((rc = padf.wait_chunk(k, ch.count))) break;
-            // the pinned coefficient slot is free again once chunk k - NB has been coded (its download and the kernel that
-            // read the device slots are behind it: ev_down[slot] was waited for before that chunk went to the coders)
-            if (k >= NB && (rc = codf.wait_chunk(k - NB, chunks[(size_t)(k - NB)].count))) break;
-            hipError_t he = hipEventRecord(c->ev_et[slot][0], c->copy_stream);
-            if (he == hipSuccess)
-                he = in.rgb ? hipMemcpyAsync(c->ed_rgb[slot].p, c->eh_in[slot].p, ch.rgb_bytes, hipMemcpyHostToDevice, c->copy_stream)
-                            : hipMemcpyAsync(c->ed_in[slot].p, c->eh_in[slot].p, ch.pix_bytes, hipMemcpyHostToDevice, c->copy_stream);
-            if (he == hipSuccess) he = hipEventRecord(c->ev_up[slot], c->copy_stream);
-            if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_up[slot], 0);
-            if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][1], compute);
-            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-            list.assign(take.begin() + ch.first, take.begin() + ch.first + ch.count);
-            if (in.rgb && (rc = encode_rgb_stage(c, in, infos, list.data(), ch.count, pix_rel.data(), rgb_rel.data(),
-                                                 c->ed_rgb[slot].as<const uint8_t>(), c->ed_in[slot].as<uint8_t>(), ch.pix_bytes)))
-                break;
-            hvc::MixedEncodePlan plan;
-            if ((rc = hvc::mixed_encode_plan_build(infos, coef_rel.data(), pix_rel.data(), list.data(), ch.count, plan))) break;
-            if ((rc = encode_mixed_launch_plan(c, plan, c->ed_in[slot].as<const uint8_t>(), c->ed_out[slot].as<int16_t>(), false))) break;
-            he = hipEventRecord(c->ev_et[slot][2], compute);
-            if (he == hipSuccess)
-                he = hipMemcpyAsync(c->eh_out[slot].p, c->ed_out[slot].p, ch.coef_elems * sizeof(int16_t), hipMemcpyDeviceToHost, compute);
-            if (he == hipSuccess) he = hipEventRecord(c->ev_down[slot], compute);
-            // wait for this chunk's upload, then hand the pinned pixel slot to chunk k + NB
-            if (he == hipSuccess) he = wait_event(c->ev_up[slot]);
-            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
-            padf.release(k);
-            if (k > 0 && (rc = landed(k - 1))) break; // (while this chunk's kernel runs)
-        }
-        if (rc == HVC_OK) rc = landed(n_chunks - 1);
-        for (int k = std::max(0, n_chunks - NB); k < n_chunks && rc == HVC_OK; k++) rc = codf.wait_chunk(k, chunks[(size_t)k].count);
-    } catch (...) {
-        rc = hvc::exception_code();
-    }
-    if (rc != HVC_OK) { // both feeds end before either waits for the pool
-        padf.raise(rc);
-        codf.raise(rc);
-    }
-    left = true;
-    rc = padf.finish(rc);
-    rc = codf.finish(rc);
-    {
-        const hipError_t h1 = hipStreamSynchronize(compute), h2 = hipStreamSynchronize(c->copy_stream);
-        if (rc == HVC_OK && (h1 != hipSuccess || h2 != hipSuccess)) rc = fail_hip(c, h1 != hipSuccess ? h1 : h2);
-    }
-    if (stats) {
-        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-        stats->entropy_ms_sum = (double)ent_ns.load() * 1e-6;
-        stats->host_prep_ms_sum = (double)pad_ns.load() * 1e-6;
-        stats->h2d_ms_sum = h2d_ms;
-        stats->kernel_ms_sum = k_ms;
-        stats->d2h_ms_sum = d2h_ms;
-        stats->chunks = n_chunks;
-        stats->threads = threads;
-        stats->frames_per_chunk = largest;
-        stats->coef_bytes = coef_total; // bytes downloaded
-    }
-    return rc;
-}
-
 // ---------------------------------------------------------------------------
 // RGB input: k_rgb_to_ycc_mixed (hvc_mixed_rgb.hip) from the host plan mixed_rgb_encode_plan_build (hvc_mixed_rgb_plan.cpp)
 
@@ -368,30 +118,7 @@ size_t rgb_image_span(const hvc_jpeg_info &fi, const size_t *rgb_row_strides, in
     return rs < tight ? 0 : hvc::mixed_rgb_span(layout, fi.width, fi.height, rs);
 }
 
-} // namespace
-
-int encode_rgb_frame_status(const hvc_jpeg_info &info, const MixedEncodeInput &in, int f) {
-    const int s = rgb_sampling_of(info);
-    if (s != HVC_YUV_420 && s != HVC_YUV_422 && s != HVC_YUV_444) return HVC_E_INVALID_ARG;
-    if ((s != HVC_YUV_444 && (info.width & 1)) || (s == HVC_YUV_420 && (info.height & 1))) return HVC_E_INVALID_ARG; // Yuv.assert_is_420 / _422
-    if (in.rgb_row_strides && in.rgb_row_strides[f] && in.rgb_row_strides[f] < hvc::mixed_rgb_row_bytes(in.layout, info.width)) return HVC_E_INVALID_ARG;
-    return HVC_OK;
-}
-
-size_t encode_rgb_frame_bytes(const hvc_jpeg_info &info, const MixedEncodeInput &in) {
-    return hvc::mixed_rgb_row_bytes(in.layout, info.width) * hvc::mixed_rgb_rows(in.layout, info.height);
-}
-
-void encode_rgb_frame_copy(const hvc_jpeg_info &info, const MixedEncodeInput &in, int f, const uint8_t *src, uint8_t *dst) {
-    const size_t row = hvc::mixed_rgb_row_bytes(in.layout, info.width), rows = hvc::mixed_rgb_rows(in.layout, info.height);
-    const size_t rs = in.rgb_row_strides && in.rgb_row_strides[f] ? in.rgb_row_strides[f] : row;
-    if (rs == row) {
-        std::memcpy(dst, src, row * rows);
-        return;
-    }
-    for (size_t y = 0; y < rows; y++) std::memcpy(dst + y * row, src + y * rs, row); // (planar: the planes are rs * height apart)
-}
-
+// a chunk's colour stage on c->stream: the plane slot cleared, then k_rgb_to_ycc_mixed over the listed frames
 int encode_rgb_stage(hvc_ctx *c, const MixedEncodeInput &in, const hvc_jpeg_info *infos, const int *list, int count, const size_t *pix_rel,
                      const size_t *rgb_rel, const uint8_t *d_rgb, uint8_t *d_planes, size_t plane_bytes) {
     hvc::MixedRgbPlan plan;
@@ -400,6 +127,8 @@ int encode_rgb_stage(hvc_ctx *c, const MixedEncodeInput &in, const hvc_jpeg_info
     HIPCHK(c, hipMemsetAsync(d_planes, 0, plane_bytes, c->stream)); // Plane.create is zero-filled: the kernel writes the frames' own samples only
     return mixed_rgb_launch_plan(c, plan, in.layout, d_planes, const_cast<uint8_t *>(d_rgb), false, true); // (d_rgb is read only)
 }
+
+} // namespace
 
 // behind hvc_rgb_to_yuv_mixed (hvc_yuv.hip)
 int rgb_to_yuv_mixed_impl(hvc_ctx *c, uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos, int n_frames, const uint8_t *rgb,
@@ -516,4 +245,192 @@ int encode_frames_mixed_rgb_impl(hvc_ctx *c, const uint8_t *rgb, const size_t *r
         }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HVC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The file pipelines: what both run (MixedEncodeFront, hvc_batch.h), then the one with the host coder
+
+int encode_mixed_chunks(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
+                        size_t chunk_bytes, uint8_t *const *jpegs, const MixedEncodeInput &in, MixedEncodeFront &fr, hvc_batch_stats *stats) {
+    if (threads < 1) threads = 1;
+    if (threads > 256) threads = 256;
+    constexpr int NB = hvc_ctx::RING;
+    // the frames that take part, cut into chunks by the bytes of their padded pixel records; a frame the block stage or the
+    // coder would refuse gets its own status here and is left out
+    const hvc::MixedEncodeChunks &plan = fr.plan;
+    int r = hvc::mixed_encode_chunks_build(infos, status, frames, jpegs, n_frames, chunk_bytes, in, fr.max_files_per_chunk, fr.plan);
+    if (r || plan.take.empty()) return r;
+    const int n_chunks = (int)plan.chunks.size(), n_take = (int)plan.take.size();
+
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
+    HIPCHK(c, c->copy_stream.ensure());
+    if (fr.down_stream) HIPCHK(c, c->down_stream.ensure());
+    for (int i = 0; i < NB; i++) {
+        HIPCHK(c, c->ev_up[i].ensure());
+        HIPCHK(c, c->ev_down[i].ensure());
+        for (int k = 0; k < 3; k++) HIPCHK(c, c->ev_et[i][k].ensure());
+        if (fr.down_stream) HIPCHK(c, c->ev_gpu[i].ensure());
+    }
+    // (a frame larger than chunk_bytes: the ring grows)
+    if ((r = ring_ensure(c, enc_rings(c), {plan.in_bytes, plan.out_bytes, plan.in_bytes, plan.out_bytes}))) return r;
+    if (in.rgb && (r = ring_ensure(c, enc_rgb_rings(c), {plan.rgb_bytes}))) return r;
+    if (fr.setup && (r = fr.setup())) return r;
+
+    std::atomic<long long> pad_ns{0};
+    fr.wall0 = std::chrono::steady_clock::now();
+    fr.threads = threads;
+    const int pad_threads = (threads + 3) / 4; // (padding is a copy: a quarter of the coder's threads keeps ahead of them)
+    if ((r = pool_ready(c, threads, pad_threads))) return r;
+    fr.ran = true;
+    bool left = false; // the coder feed goes first when the call is left: it ends the padding workers with it
+    hvc::ChunkFeed padf(c->pool, n_chunks, NB);
+    // ring 0: chunk k may be read by the pipeline's workers once release(k) says what they read has landed
+    hvc::ChunkFeed codf(c->pool, n_chunks, 0, [&] { if (!left) padf.raise(HVC_E_INTERNAL); });
+    fr.codf = &codf;
+    auto pad_worker = [&]() {
+        if (!pin_to_ctx_cpus(c)) padf.raise(HVC_E_INVALID_ARG); // hvc_set_host_cpus
+        for (;;) {
+            const int t = padf.claim();
+            if (t >= n_take || padf.error()) return;
+            const int f = plan.take[(size_t)t], k = plan.chunk_of[(size_t)f];
+            if (!padf.wait_slot(k)) return;
+            const auto t0 = std::chrono::steady_clock::now();
+            if (in.rgb)
+                encode_rgb_frame_copy(infos[f], in, f, frames[f], c->eh_in[k % NB].as<uint8_t>() + plan.rgb_rel[(size_t)f]);
+            else
+                pad_frame(infos[f], frames[f], c->eh_in[k % NB].as<uint8_t>() + plan.pix_rel[(size_t)f]);
+            pad_ns += MixedEncodeFront::ns_since(t0);
+            padf.report(k, 1, HVC_OK);
+        }
+    };
+    r = padf.start(pad_threads, pad_worker);
+    if (!r) r = codf.start(threads, fr.worker);
+
+    int rc = r;
+    hipStream_t compute = c->stream;
+    try {
+        for (int k = 0; k < n_chunks && rc == HVC_OK; k++) {
+            const hvc::MixedEncodeChunk &ch = plan.chunks[(size_t)k];
+            const int slot = k % NB;
+            const int *list = plan.take.data() + ch.first;
+            if ((rc = padf.wait_chunk(k, ch.count))) break;
+            // what the slot holds behind the block stage is free again once chunk k - NB has left the pipeline's workers (its
+            // downloads and the kernels that read the device slots are behind it: ev_down[slot] was waited for before that
+            // chunk went to them)
+            if (k >= NB && (rc = codf.wait_chunk(k - NB, plan.chunks[(size_t)(k - NB)].count))) break;
+            hipError_t he = hipEventRecord(c->ev_et[slot][0], c->copy_stream);
+            if (he == hipSuccess)
+                he = in.rgb ? hipMemcpyAsync(c->ed_rgb[slot].p, c->eh_in[slot].p, ch.rgb_bytes, hipMemcpyHostToDevice, c->copy_stream)
+                            : hipMemcpyAsync(c->ed_in[slot].p, c->eh_in[slot].p, ch.pix_bytes, hipMemcpyHostToDevice, c->copy_stream);
+            if (he == hipSuccess) he = hipEventRecord(c->ev_up[slot], c->copy_stream);
+            if (he == hipSuccess) he = hipStreamWaitEvent(compute, c->ev_up[slot], 0);
+            if (he == hipSuccess) he = hipEventRecord(c->ev_et[slot][1], compute);
+            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
+            if (in.rgb && (rc = encode_rgb_stage(c, in, infos, list, ch.count, plan.pix_rel.data(), plan.rgb_rel.data(),
+                                                 c->ed_rgb[slot].as<const uint8_t>(), c->ed_in[slot].as<uint8_t>(), ch.pix_bytes)))
+                break;
+            hvc::MixedEncodePlan bplan;
+            if ((rc = hvc::mixed_encode_plan_build(infos, plan.coef_rel.data(), plan.pix_rel.data(), list, ch.count, bplan))) break;
+            if ((rc = encode_mixed_launch_plan(c, bplan, c->ed_in[slot].as<const uint8_t>(), c->ed_out[slot].as<int16_t>(), false))) break;
+            if ((rc = fr.stage(k, slot))) break;
+            // wait for this chunk's upload, then hand the pinned pixel slot to chunk k + NB
+            he = wait_event(c->ev_up[slot]);
+            if (he != hipSuccess) { rc = fail_hip(c, he); break; }
+            padf.release(k);
+            if ((rc = fr.retire(k))) break; // (while this chunk's kernels run)
+        }
+        if (rc == HVC_OK) rc = fr.drain();
+        for (int k = std::max(0, n_chunks - NB); k < n_chunks && rc == HVC_OK; k++) rc = codf.wait_chunk(k, plan.chunks[(size_t)k].count);
+    } catch (...) {
+        rc = hvc::exception_code();
+    }
+    if (rc != HVC_OK) { // both feeds end before either waits for the pool
+        padf.raise(rc);
+        codf.raise(rc);
+    }
+    left = true;
+    rc = padf.finish(rc);
+    rc = codf.finish(rc);
+    fr.codf = nullptr;
+    {
+        const hipError_t h1 = hipStreamSynchronize(compute), h2 = hipStreamSynchronize(c->copy_stream),
+                         h3 = fr.down_stream ? hipStreamSynchronize(c->down_stream) : hipSuccess;
+        if (rc == HVC_OK && (h1 != hipSuccess || h2 != hipSuccess || h3 != hipSuccess))
+            rc = fail_hip(c, h1 != hipSuccess ? h1 : h2 != hipSuccess ? h2 : h3);
+    }
+    if (stats) {
+        stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - fr.wall0).count();
+        stats->host_prep_ms_sum = (double)pad_ns.load() * 1e-6;
+        stats->h2d_ms_sum = fr.h2d_ms;
+        stats->kernel_ms_sum = fr.k_ms;
+        stats->d2h_ms_sum = fr.d2h_ms;
+        stats->chunks = n_chunks;
+        stats->threads = threads;
+        stats->frames_per_chunk = plan.largest;
+    }
+    return rc;
+}
+
+// behind hvc_jpeg_encode_batch_mixed (hvc_capi_files.hip)
+int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
+                            size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats,
+                            const MixedEncodeInput &in) {
+    if (!c || !frames || !infos || !status || !jpegs || !caps || !sizes || n_frames < 0) return HVC_E_INVALID_ARG;
+    if (c->enc_arith != HVC_ARITH_MODEL) return HVC_E_INVALID_ARG;
+    if (in.rgb && in.layout != HVC_RGB_INTERLEAVED && in.layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_frames == 0) return HVC_OK;
+    constexpr int NB = hvc_ctx::RING;
+    const bool opt = c->huff_tables == HVC_HUFF_OPTIMISED; // each file its own tables (hvc_set_huffman_tables)
+    const int ri = c->restart_interval;                    // DRI + RSTn every ri MCUs (hvc_set_restart_interval)
+    std::atomic<long long> ent_ns{0};
+    MixedEncodeFront fr;
+    const hvc::MixedEncodeChunks &plan = fr.plan;
+    fr.worker = [&]() {
+        hvc::ChunkFeed &codf = *fr.codf;
+        if (!pin_to_ctx_cpus(c)) codf.raise(HVC_E_INVALID_ARG);
+        for (;;) {
+            const int t = codf.claim();
+            if (t >= (int)plan.take.size() || codf.error()) return;
+            const int f = plan.take[(size_t)t], k = plan.chunk_of[(size_t)f];
+            if (!codf.wait_slot(k)) return;
+            const auto t0 = std::chrono::steady_clock::now();
+            const int16_t *cf = c->eh_out[k % NB].as<const int16_t>() + plan.coef_rel[(size_t)f];
+            const int e = opt ? hvc::entropy_encode_optimised(&infos[f], cf, jpegs[f], caps[f], &sizes[f], ri)
+                              : hvc::entropy_encode_file(&infos[f], nullptr, cf, jpegs[f], caps[f], &sizes[f], ri);
+            ent_ns += MixedEncodeFront::ns_since(t0);
+            status[f] = e; // the file's own result: it stops nobody else
+            codf.report(k, 1, HVC_OK);
+        }
+    };
+    // behind the block stage: the chunk's records come down on the compute stream
+    fr.stage = [&](int k, int slot) {
+        hipError_t he = hipEventRecord(c->ev_et[slot][2], c->stream);
+        if (he == hipSuccess)
+            he = hipMemcpyAsync(c->eh_out[slot].p, c->ed_out[slot].p, plan.chunks[(size_t)k].coef_elems * sizeof(int16_t), hipMemcpyDeviceToHost,
+                                c->stream);
+        if (he == hipSuccess) he = hipEventRecord(c->ev_down[slot], c->stream);
+        return he == hipSuccess ? (int)HVC_OK : fail_hip(c, he);
+    };
+    // chunk j's records have landed: its times are read, its pinned slot goes to the coder workers
+    auto landed = [&](int j) {
+        const int slot = j % NB;
+        const hipError_t he = wait_event(c->ev_down[slot]);
+        if (he != hipSuccess) return fail_hip(c, he);
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c->ev_et[slot][0], c->ev_up[slot]) == hipSuccess) fr.h2d_ms += ms;
+        if (hipEventElapsedTime(&ms, c->ev_et[slot][1], c->ev_et[slot][2]) == hipSuccess) fr.k_ms += ms;
+        if (hipEventElapsedTime(&ms, c->ev_et[slot][2], c->ev_down[slot]) == hipSuccess) fr.d2h_ms += ms;
+        fr.codf->release(j);
+        return (int)HVC_OK;
+    };
+    fr.retire = [&](int k) { return k > 0 ? landed(k - 1) : (int)HVC_OK; };
+    fr.drain = [&]() { return landed((int)plan.chunks.size() - 1); };
+    const int rc = encode_mixed_chunks(c, frames, infos, status, n_frames, threads, chunk_bytes, jpegs, in, fr, stats);
+    if (stats && fr.ran) {
+        stats->entropy_ms_sum = (double)ent_ns.load() * 1e-6;
+        stats->coef_bytes = plan.coef_total; // bytes downloaded
+    }
+    return rc;
 }

@@ -14,9 +14,11 @@
 //                        hvc_set_mixed_arithmetic(HVC_ARITH_LIBJPEG) the full-size ones launch the kernels of hvc_mixed_libjpeg.hip
 //   hvc_capi_mixed_encode.hip  the same in the other direction: raw frames of different geometry, sampling and quality to records
 //                        and files (behind hvc_encode_frames_mixed, hvc_jpeg_encode_batch_mixed), and the same from RGB images
-//                        (behind hvc_rgb_to_yuv_mixed, hvc_encode_frames_mixed_rgb, hvc_jpeg_encode_batch_mixed_rgb[_gpu])
+//                        (behind hvc_rgb_to_yuv_mixed, hvc_encode_frames_mixed_rgb, hvc_jpeg_encode_batch_mixed_rgb[_gpu]); the part
+//                        of the file pipeline that the one with the GPU coder runs too (encode_mixed_chunks, hvc_batch.h; its
+//                        chunk cut and the padding workers' host parts: hvc_mixed_encode_chunks.h, plain C++)
 //   hvc_capi_mixed_coder.hip   the mixed GPU Huffman coder alone and the file pipeline built on it (behind
-//                        hvc_huffman_encode_frames_mixed, hvc_jpeg_encode_batch_mixed_gpu)
+//                        hvc_huffman_encode_frames_mixed, hvc_jpeg_encode_batch_mixed_gpu): what stands behind the block stage
 //   hvc_capi_mixed_reader.hip  the mixed GPU Huffman reader's driver (hvc_mixed_reader.h) and hvc_jpeg_entropy_decode_gpu_mixed
 //   hvc_capi_resize.hip  the resampling step over a mixed set (hvc_rgb_resize_mixed) and the launch of its two passes, which
 //                        hvc_jpeg_decode_batch_mixed_resized ends in
@@ -52,6 +54,7 @@
 #include "hvc_kernels.h"
 #include "hvc_mixed_plan.h"
 #include "hvc_mixed_encode_plan.h"
+#include "hvc_mixed_encode_chunks.h"
 #include "hvc_pool.h"
 #include "hvc_scaled_spec.h"
 
@@ -619,30 +622,21 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
 // A plan's image in a device buffer of the context, in stream order on c->stream: uploaded from the pinned copy unless the
 // device already holds these bytes (hvc_capi_mixed.hip; the mixed encode plans of hvc_capi_mixed_encode.hip go the same way)
 int upload_image(hvc_ctx *c, PlanBuf &b, const std::vector<unsigned char> &img);
+// ... made of parts one after another, each on 16 bytes; at[i] = where part i starts (a part of no bytes takes no room)
+struct ImagePart {
+    const void *p;
+    size_t bytes;
+};
+int upload_parts(hvc_ctx *c, PlanBuf &b, std::initializer_list<ImagePart> parts, size_t *at);
 // hvc_capi_mixed_encode.hip: frames of different geometry, sampling and quality ENCODED in one call (behind
 // hvc_encode_frames_mixed and hvc_jpeg_encode_batch_mixed in hvc_capi_files.hip)
 int encode_frames_mixed_impl(hvc_ctx *c, const uint8_t *pixels, const size_t *pixel_offsets, const hvc_jpeg_info *infos, int n_frames,
                              int16_t *coefs, const size_t *coef_offsets, int where);
-// What frames[f] of a mixed encode batch is.  Default: a raw planar frame (tight Y, U, V).  rgb: an RGB image of `layout`
-// with rows rgb_row_strides[f] apart (nullptr, or an entry of 0: tight); the padding workers copy its rows tight into the
-// pinned ring, the chunk goes up into a device RGB slot and k_rgb_to_ycc_mixed writes the chunk's zeroed plane slot from it in
-// front of k_encode_mixed.  Chunks, records and everything behind the block stage are the same.
-struct MixedEncodeInput {
-    bool rgb = false;
-    int layout = 0;
-    const size_t *rgb_row_strides = nullptr;
-};
+// (MixedEncodeInput -- what frames[f] of a mixed encode batch is -- and the host-only parts of the padding workers:
+// hvc_mixed_encode_chunks.h; what the pipeline shares with the one behind the GPU coder: MixedEncodeFront, hvc_batch.h)
 int encode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg_info *infos, int *status, int n_frames, int threads,
                             size_t chunk_bytes, uint8_t *const *jpegs, const size_t *caps, size_t *sizes, hvc_batch_stats *stats,
                             const MixedEncodeInput &in = MixedEncodeInput());
-// the RGB input form's parts, shared by the two pipelines: the frame's own status (HVC_E_INVALID_ARG: an odd size under its
-// sampling, a row stride below the row), the bytes of its tight image, its rows into the pinned slot, and the chunk's colour
-// stage on c->stream -- the plane slot cleared (Plane.create is zero-filled), then k_rgb_to_ycc_mixed over the listed frames
-int encode_rgb_frame_status(const hvc_jpeg_info &info, const MixedEncodeInput &in, int f);
-size_t encode_rgb_frame_bytes(const hvc_jpeg_info &info, const MixedEncodeInput &in);
-void encode_rgb_frame_copy(const hvc_jpeg_info &info, const MixedEncodeInput &in, int f, const uint8_t *src, uint8_t *dst);
-int encode_rgb_stage(hvc_ctx *c, const MixedEncodeInput &in, const hvc_jpeg_info *infos, const int *list, int count, const size_t *pix_rel,
-                     const size_t *rgb_rel, const uint8_t *d_rgb, uint8_t *d_planes, size_t plane_bytes);
 // hvc_capi_mixed.hip, for both directions: the mixed colour pass of a plan on device memory, enqueued on c->stream (to_ycc:
 // k_rgb_to_ycc_mixed, d_rgb read and the planes at d_yuv written); where the records of a host-memory call go in device scratch
 namespace hvc {
@@ -667,11 +661,8 @@ int rgb_to_yuv_mixed_impl(hvc_ctx *c, uint8_t *yuv, const size_t *yuv_offsets, c
                           const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout, int where);
 int encode_frames_mixed_rgb_impl(hvc_ctx *c, const uint8_t *rgb, const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout,
                                  const hvc_jpeg_info *infos, int n_frames, int16_t *coefs, const size_t *coef_offsets, int where);
-// hvc_capi_mixed_encode.hip, for the pipeline with the GPU coder: k_encode_mixed over a plan on device memory, enqueued on
-// c->stream; Plane.blit_available of a raw planar frame into its padded record; what a frame's records cover
+// hvc_capi_mixed_encode.hip: k_encode_mixed over a plan on device memory, enqueued on c->stream
 int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const uint8_t *d_pixels, int16_t *d_coefs, bool profile);
-void pad_frame(const hvc_jpeg_info &info, const uint8_t *src, uint8_t *rec);
-void encode_frame_spans(const hvc_jpeg_info &fi, size_t &pixel_span, size_t &coef_span);
 // hvc_capi_mixed_coder.hip: the mixed GPU Huffman coder alone and behind the block stage (behind
 // hvc_huffman_encode_frames_mixed and hvc_jpeg_encode_batch_mixed_gpu in hvc_capi_files.hip)
 int huffman_encode_frames_mixed_impl(hvc_ctx *c, const hvc_jpeg_info *infos, const int16_t *coefs, const size_t *coef_offsets, int n_frames,
