@@ -158,6 +158,30 @@ def test_file_cap(harness, tmp_path, lay):
     assert run_plan(harness, tmp_path, infos, status, 0, cap=1) == run_plan(harness, tmp_path, infos, status, 64)
 
 
+@pytest.mark.parametrize("chunk_bytes,cap,counts", [(0, 1, [1, 1, 1, 1, 1]), (0, 3, [3, 2]), (0, 5, [5]), (0, 6, [5]), (0, 4, [4, 1]),
+                                                    (600, 3, [2, 1, 1, 1]), (1300, 3, [3, 1, 1]), (1 << 20, 3, [3, 2])])
+def test_file_cap_values(harness, tmp_path, lay, chunk_bytes, cap, counts):
+    """max_files_per_chunk as hvc_jpeg_encode_batch_mixed_gpu sets it (there: HVC_HUFF_MIXED_MAX_FILES, which
+    tests/test_gpu_mixed_counts.py reaches with 65537 frames): 1, 3, exactly the files that take part (5) and the set's size (6),
+    one below; and with a byte limit that closes the chunk first (600: after two files) or with the same file (1300: the
+    third).  The rule restated (csrc/hvc_mixed_encode_chunks.h): a chunk that holds a file closes when the next record would
+    take it past chunk_bytes or when it holds `cap` files."""
+    infos, status = list(lay.infos), list(lay.status)
+    got = run_plan(harness, tmp_path, infos, status, chunk_bytes, cap=cap)
+    assert got == expected_plan(infos, status, chunk_bytes, cap=cap)
+    assert [k["count"] for k in got["chunks"]] == counts and got["take"] == GOOD
+    assert got["wants"]["largest"] == max(counts) <= cap
+    check_alignment(got, infos)
+    limit, first = chunk_bytes or 64 << 20, 0                                  # the rule once more, chunk by chunk
+    for j, k in enumerate(got["chunks"]):
+        assert 1 <= k["count"] <= cap and (k["count"] == 1 or k["pix_bytes"] <= limit)
+        if j + 1 < len(got["chunks"]):                                         # why it closed: full, or the next record did not fit
+            nxt = up(infos[GOOD[first + k["count"]]].pixel_bytes, 64)
+            assert k["count"] == cap or k["pix_bytes"] + nxt > limit
+        first += k["count"]
+    assert first == len(GOOD)
+
+
 @pytest.mark.parametrize("layout", [0, 1])
 def test_rgb_records_and_ring_wants(harness, tmp_path, lay, layout):
     """the tight images beside the planes, on 64 bytes; in_bytes is the larger of the two per chunk (the 4:2:0 frames' images are

@@ -6,6 +6,7 @@ shrinks below that, or a changed default run length, fails here."""
 import numpy as np
 import pytest
 
+import mixed_counts as mc
 import xcd_grids as xg
 
 TILE_GRID = dict(per=xg.tiles_per_frame(xg.TILE_PLANES), n=xg.TILE_FRAMES, parts=len(xg.TILE_PLANES))
@@ -28,7 +29,15 @@ B4_GRID_K2 = dict(per=xg.upsample_x8_tiles(264, 131), n=9, parts=9)
 PACKED_GRID = dict(per=xg.packed_op_tiles(1920, 1080), n=2, parts=3)
 CHROMA_GRID = dict(per=xg.plane_op_tiles(960, 540), n=2, parts=2)               # the u and the v plane, a launch each
 
+
+def count_grid(name, zero=True):
+    """a set of tests/mixed_counts.py: at 65535 groups the last permuted launch, at 65537 the launch as dispatched"""
+    s = mc.count_set(name, zero)
+    return dict(per=s.groups, n=1, units=s.units, frames=s.n, parts=3, edge=name)
+
+
 NEW = "test_gpu_xcd_order.py"
+COUNTS = "test_gpu_mixed_counts.py"
 # (kernel family, test module, test function, grid, text the test's source must hold: its geometry)
 TABLE = [
     ("k_decode_packed<false>", NEW, "test_decode_frames_model", TILE_GRID, ()),
@@ -59,6 +68,19 @@ TABLE = [
      ("((1920, 1080), (1920, 1080), (0, 0))", "(\"YVYU\", \"YUY2\")", "n_frames=2")),
     ("hvc_yuv.hip: k_chroma_420_to_422, k_chroma_422_to_420", "test_gpu_yuv_convert.py", "test_oconv_pipeline_every_format_pair", CHROMA_GRID,
      ("((1920, 1080), (1920, 1080), (0, 0))", "(420, \"UYVY\")", "(\"YUY2\", 420)", "n_frames=2")),
+    # the four mixed families at the counts where the order is switched off (tests/mixed_counts.py): 65535 groups, the last
+    # one full (ON) and ragged (ON_RAGGED), and 65537 groups (OFF)
+    ("k_decode_mixed", COUNTS, "test_decode_frames_mixed", count_grid("ON"), ('["ON", "ON_RAGGED", "OFF"]',)),
+    ("k_decode_mixed", COUNTS, "test_decode_frames_mixed", count_grid("ON_RAGGED"), ('["ON", "ON_RAGGED", "OFF"]',)),
+    ("k_decode_mixed", COUNTS, "test_decode_frames_mixed", count_grid("OFF"), ('["ON", "ON_RAGGED", "OFF"]',)),
+    ("k_decode_mixed + k_decode_mixed_wide (fix-up ids)", COUNTS, "test_decode_frames_mixed_fix_up_ids", count_grid("ON"), ()),
+    ("k_decode_mixed + k_decode_mixed_wide (fix-up ids)", COUNTS, "test_decode_frames_mixed_fix_up_ids", count_grid("OFF"), ()),
+    ("k_decode_mixed_scaled<N>", COUNTS, "test_decode_frames_mixed_scaled", count_grid("ON"), ()),
+    ("k_decode_mixed_scaled<N>", COUNTS, "test_decode_frames_mixed_scaled", count_grid("OFF"), ()),
+    ("k_encode_mixed", COUNTS, "test_encode_frames_mixed", count_grid("ON", False), ()),
+    ("k_encode_mixed", COUNTS, "test_encode_frames_mixed", count_grid("OFF", False), ()),
+    ("k_islow_mixed", COUNTS, "test_decode_frames_mixed_libjpeg", count_grid("ON", False), ()),
+    ("k_islow_mixed", COUNTS, "test_decode_frames_mixed_libjpeg", count_grid("OFF", False), ()),
 ]
 FAMILIES = ("k_decode_packed<false>", "k_decode_packed<true>", "k_decode_wide_all", "k_decode_444", "k_encode", "k_upsample420_x8",
             "k_hardcaml", "k_hardcaml_encode", "k_islow<false>", "k_islow<true>", "k_decode_scaled<N, false, DW>",
@@ -83,13 +105,25 @@ def test_every_family_runs_permuted_with_a_remainder_in_a_gpu_test():
         if module == NEW:                                  # the new tests take theirs from xcd_grids, by these names
             for name in ("xg.TILE_PLANES", "xg.TILE_FRAMES", "xg.MIXED_ORDER", "xg.MIXED_ORDER_NO_ZERO", "xg.READER_FILES", "xg.READER_SIZE"):
                 assert name in src, name
+        if module == COUNTS:                               # ... and these theirs from mixed_counts
+            assert "mc.count_set(name" in src and '@pytest.mark.parametrize("name", ["ON", "OFF"])' in src
         per, n, fused = grid["per"], grid["n"], grid.get("fused", False)
         s = xg.split(per, n, fused)
         report.append((family, per, n, s["full"], s["rest"]))
+        if grid.get("edge") == "OFF":                      # past the switch: nothing is permuted, every group runs once
+            assert per == 65537 and s["map"] == 0 and (s["full"], s["rest"]) == (0, per), family
+            frame, tile = xg.replay(per, n, fused)
+            assert not frame.any() and np.array_equal(tile, np.arange(per)), family
+            assert grid["units"] % xg.MIXED_GROUP != 0 and grid["frames"] > 1, family
+            continue
         assert s["map"] > 0, family                                                    # (a) the mapping is on
         assert s["full"] >= s["group"] > 0, family                                     # (b) a whole group is permuted
         assert s["rest"] > 0, family                                                   # (c) a remainder as dispatched
-        if "units" in grid:                                                            # (d) ragged against the run length
+        if "edge" in grid:                                                             # (d) the last count that is permuted
+            assert per == 65535 and xg.xcd_map_for(per + 1, 1) == 0, family
+            assert (grid["units"] % xg.MIXED_GROUP != 0) == (grid["edge"] == "ON_RAGGED"), family
+            assert grid["frames"] > 1 and grid["parts"] > 1, family                    # (e)
+        elif "units" in grid:                                                          # (d) ragged against the run length
             assert grid["units"] % xg.MIXED_GROUP != 0, family                         #     ... the last group has spare units
             assert 513 <= grid["units"] <= 1020, family
             assert grid["frames"] > 1 and grid["parts"] > 1, family                    # (e)
@@ -105,7 +139,7 @@ def test_every_family_runs_permuted_with_a_remainder_in_a_gpu_test():
         else:
             assert np.count_nonzero(frame[:s["full"]] != ids[:s["full"]] // per) > 0, family
     for line in report:
-        print("%-70s per %4d  n %3d  permuted %5d  remainder %4d" % line)
+        print("%-70s per %5d  n %3d  permuted %5d  remainder %5d" % line)
 
 
 def test_the_tile_geometry_is_the_one_the_issue_of_this_table_describes():
