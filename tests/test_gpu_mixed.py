@@ -255,6 +255,92 @@ def test_a_failing_file_stops_nobody_else(ctx, file_set, device):
     check_files(ctx.jpeg_decode_batch_mixed(good_files[:6], threads=2, device=device), good_models[:6])
 
 
+# the seam between the chunk plan (csrc/hvc_mixed_decode_chunks.cpp, tests/test_mixed_decode_chunks.py) and the pipeline: six small
+# files in three chunks, the third file's scan spoilt, host memory filled with a canary
+SEAM_SET = [(24, 18, [(2, 2), (1, 1), (1, 1)]), (8, 8, [(1, 1)] * 3), (16, 16, [(2, 2), (1, 1), (1, 1)]), (16, 8, [(2, 1), (1, 1), (1, 1)]),
+            (9, 9, [(1, 1)] * 3), (16, 16, [(2, 2), (1, 1), (1, 1)])]
+SEAM_BAD, SEAM_CHUNK_BYTES, SEAM_CHUNKS, CANARY = 2, 2400, [[0], [1, 2, 3], [4, 5]], 0xA5
+
+
+@pytest.fixture(scope="module")
+def seam_set():
+    """(files, the spoilt file's code, per form the bytes hvc_jpeg_decode / _rgb / _scaled give every good file)"""
+    import video_coding_amd as hvc
+    files = [jpeg_optimised_tables(w, h, s, QT, random_record(s, w, h, 7 + f)[0], table_sets=2) for f, (w, h, s) in enumerate(SEAM_SET)]
+    info = hvc.hvc.jpeg_read_header(files[SEAM_BAD])
+    files[SEAM_BAD] = files[SEAM_BAD][:info.ecs_offset] + b"\xff\x00" * 64 + b"\xff\xd9"   # one-bits: a code no table has
+    with pytest.raises(hvc.HvcError) as e:
+        hvc.hvc.jpeg_entropy_decode(files[SEAM_BAD])
+    cuts, limit = [[]], SEAM_CHUNK_BYTES                                      # the cut as the header words it
+    for f, data in enumerate(files):
+        cb = 2 * hvc.hvc.jpeg_read_header(data).coef_count
+        if cuts[-1] and sum(c for _, c in cuts[-1]) + cb > limit:
+            cuts.append([])
+        cuts[-1].append((f, cb))
+    assert [[f for f, _ in k] for k in cuts] == SEAM_CHUNKS
+    c = hvc.Context(0)
+    try:
+        want = {"planes": {}, "rgb": {}, "scale2": {}}
+        for f, data in enumerate(files):
+            if f != SEAM_BAD:
+                want["planes"][f] = c.jpeg_decode(data)[1].copy()
+                want["rgb"][f] = c.jpeg_decode_rgb(data)[1].copy()
+                want["scale2"][f] = c.jpeg_decode_scaled(data, 2)[1].copy()
+    finally:
+        c.close()
+    return files, e.value.code, want
+
+
+@pytest.mark.parametrize("reader", ["host", "gpu"])
+@pytest.mark.parametrize("form", ["planes", "rgb", "scale2"])
+def test_chunks_runs_and_a_failing_file_in_host_memory(ctx, seam_set, form, reader):
+    """Every good file's bytes are the single-file call's; the failing file's record, the 4096 bytes in front of it and behind it,
+    the five bytes behind every RGB row and every other byte that is no good file's still hold the canary; a status per file."""
+    import video_coding_amd as hvc
+    h = hvc.hvc
+    files, bad_code, want = seam_set
+    ctx.set_mixed_reader(reader)
+    lay = {"planes": lambda: h.MixedLayout(files, 8), "rgb": lambda: h.MixedRgbLayout(files, "interleaved", 0, 0),
+           "scale2": lambda: h.MixedScaledLayout(files, 2)}[form]()
+    assert list(lay.status) == [0] * 6
+    offsets = lay.rgb_offsets if form == "rgb" else lay.pixel_offsets
+    at, span = 8 if form == "planes" else 5, []                               # (full-size planes lie on 8 bytes, the others anywhere)
+    for f in range(6):
+        if form == "rgb":
+            lay.rgb_row_strides[f] = 3 * lay.infos[f].width + 5
+            span.append((lay.infos[f].height - 1) * lay.rgb_row_strides[f] + 3 * lay.infos[f].width)
+        else:
+            span.append((lay.infos if form == "planes" else lay.scaled)[f].pixel_bytes)
+        if f in (SEAM_BAD, SEAM_BAD + 1):
+            at += 4096
+        offsets[f] = at
+        at += span[f]
+    buf = np.full(at + 64, CANARY, dtype=np.uint8)
+    if form == "planes":
+        res = ctx.jpeg_decode_batch_mixed(files, threads=2, chunk_bytes=SEAM_CHUNK_BYTES, layout=lay, pixels=buf)
+    elif form == "rgb":
+        res = ctx.jpeg_decode_batch_mixed_rgb(files, threads=2, chunk_bytes=SEAM_CHUNK_BYTES, rgb_layout=lay, rgb=buf)
+    else:
+        res = ctx.jpeg_decode_batch_mixed_scaled(files, 2, threads=2, chunk_bytes=SEAM_CHUNK_BYTES, layout=lay, pixels=buf)
+    assert [r[0] for r in res] == [bad_code if f == SEAM_BAD else 0 for f in range(6)] and bad_code != 0
+    assert ctx.last_batch_stats.chunks >= 3                                   # (the GPU reader's hand-back pass adds its own)
+    theirs = np.zeros(buf.size, dtype=bool)                                   # the bytes that are a good file's
+    for f in range(6):
+        if f == SEAM_BAD:
+            continue
+        if form == "rgb":
+            w, hh, rs = lay.infos[f].width, lay.infos[f].height, lay.rgb_row_strides[f]
+            assert np.array_equal(h.rgb_view(buf, offsets[f], rs, w, hh, "interleaved"), want[form][f]), f
+            for y in range(hh):
+                theirs[offsets[f] + y * rs:offsets[f] + y * rs + 3 * w] = True
+        else:
+            assert np.array_equal(buf[offsets[f]:offsets[f] + span[f]], want[form][f]), f
+            theirs[offsets[f]:offsets[f] + span[f]] = True
+    lo, hi = offsets[SEAM_BAD], offsets[SEAM_BAD] + span[SEAM_BAD]
+    assert (buf[lo - 4096:hi + 4096] == CANARY).all() and not theirs[lo - 4096:hi + 4096].any()
+    assert (buf[~theirs] == CANARY).all() and theirs.sum() == sum(want[form][f].size for f in want[form])
+
+
 def test_restart_markers(ctx):
     """one file with DRI, hvc_set_restart_markers on and off, against hvc_jpeg_decode under the same setting.  Off is the model's
     reading: the scan ends at the first RSTn and zero bits follow.  The first file is built so that this reading stays inside

@@ -914,9 +914,7 @@ int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const u
         P.pixels = pixels;
         P.dc_plane = o.dc_plane;
         P.dc_fs = o.dc_fs;
-        const int slot = (int)(c->k_calls % HVC_PROF_RING);
-        HIPCHK(c, launch_range(coefs, pixels, 0, n_frames, o.profile ? c->k0[slot] : nullptr, o.profile ? c->k1[slot] : nullptr));
-        if (o.profile) c->k_calls++;
+        HIPCHK(c, profiled_launch(c, o.profile, [&](hipEvent_t k0, hipEvent_t k1) { return launch_range(coefs, pixels, 0, n_frames, k0, k1); }));
         if (has_wide) return apply_wide_dc(c, P, *o.wide, qtabs, n_qtabs, o.arith);
         return HVC_OK;
     }
@@ -1015,9 +1013,7 @@ int decode_frames_scaled_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
     if (where == HVC_MEM_DEVICE) {
         if ((uintptr_t)coefs & 15) return HVC_E_ALIGNMENT;
         HIPCHK(c, hipMemsetAsync(P.wide_total, 0, sizeof *P.wide_total, c->stream));
-        const int slot = (int)(c->k_calls % HVC_PROF_RING);
-        HIPCHK(c, launch_range(coefs, pixels, 0, n_frames, o.profile ? c->k0[slot] : nullptr, o.profile ? c->k1[slot] : nullptr));
-        if (o.profile) c->k_calls++;
+        HIPCHK(c, profiled_launch(c, o.profile, [&](hipEvent_t k0, hipEvent_t k1) { return launch_range(coefs, pixels, 0, n_frames, k0, k1); }));
         return HVC_OK;
     }
     if (o.dc_plane) return HVC_E_INVALID_ARG;
@@ -1366,9 +1362,7 @@ int decode_frames_yuv444_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, 
         P.dc_plane = o.dc_plane;
         P.dc_fs = o.dc_fs;
         const bool prof = o.profile && !wide_only;
-        const int slot = (int)(c->k_calls % HVC_PROF_RING);
-        HIPCHK(c, launch_range(coefs, frames, 0, n_frames, prof ? c->k0[slot] : nullptr, prof ? c->k1[slot] : nullptr));
-        if (prof) c->k_calls++;
+        HIPCHK(c, profiled_launch(c, prof, [&](hipEvent_t k0, hipEvent_t k1) { return launch_range(coefs, frames, 0, n_frames, k0, k1); }));
         if (has_wide) return apply_wide_dc_444(c, P, *o.wide);
         return HVC_OK;
     }
@@ -1469,9 +1463,7 @@ int encode_frames_impl(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const
     };
     if (where == HVC_MEM_DEVICE) {
         if (((uintptr_t)coefs & 15) || ((uintptr_t)pixels & 7)) return HVC_E_ALIGNMENT;
-        const int slot = (int)(c->k_calls % HVC_PROF_RING);
-        HIPCHK(c, launch_range(pixels, coefs, 0, n_frames, o.profile ? c->k0[slot] : nullptr, o.profile ? c->k1[slot] : nullptr));
-        if (o.profile) c->k_calls++;
+        HIPCHK(c, profiled_launch(c, o.profile, [&](hipEvent_t k0, hipEvent_t k1) { return launch_range(pixels, coefs, 0, n_frames, k0, k1); }));
         return HVC_OK;
     }
 

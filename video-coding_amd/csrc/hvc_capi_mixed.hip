@@ -91,15 +91,13 @@ int mixed_rgb_launch_plan(hvc_ctx *c, const hvc::MixedRgbPlan &plan, int layout,
     P.map = reinterpret_cast<const unsigned *>(c->mixed_rgb_plan.d.as<const unsigned char>() + at[1]);
     P.n_units = (unsigned)plan.map.size();
     P.planar = layout == HVC_RGB_PLANAR;
-    const int slot = (int)(c->k_calls % HVC_PROF_RING);
-    const hipEvent_t k0 = profile ? (hipEvent_t)c->k0[slot] : nullptr, k1 = profile ? (hipEvent_t)c->k1[slot] : nullptr;
     // hvc_set_mixed_arithmetic(HVC_ARITH_LIBJPEG): the planes -> RGB direction with libjpeg's fancy upsampling
     const bool fancy = !to_ycc && c->mixed_arith == HVC_ARITH_LIBJPEG;
-    const hipError_t e = to_ycc  ? hvc::launch_rgb_to_ycc_mixed(P, c->stream, k0, k1)
-                         : fancy ? hvc::launch_ycc_to_rgb_fancy_mixed(P, c->stream, k0, k1)
-                                 : hvc::launch_ycc_to_rgb_mixed(P, c->stream, k0, k1);
-    if (e != hipSuccess) return fail_hip(c, e);
-    if (profile) c->k_calls++;
+    HIPCHK(c, profiled_launch(c, profile, [&](hipEvent_t k0, hipEvent_t k1) {
+               return to_ycc  ? hvc::launch_rgb_to_ycc_mixed(P, c->stream, k0, k1)
+                      : fancy ? hvc::launch_ycc_to_rgb_fancy_mixed(P, c->stream, k0, k1)
+                              : hvc::launch_ycc_to_rgb_mixed(P, c->stream, k0, k1);
+           }));
     return HVC_OK;
 }
 
@@ -131,14 +129,9 @@ int mixed_launch_plan(hvc_ctx *c, const hvc::MixedPlan &plan, const int16_t *d_c
         P.map = M.map;
         P.n_units = M.n_units;
         P.all_wide = c->decode_kernel == 2;
-        P.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count.as<unsigned>() + 2);
-        if (!c->wide_total_started) HIPCHK(c, hipMemsetAsync(P.wide_total, 0, sizeof *P.wide_total, c->stream));
-        c->wide_total_started = true;
+        HIPCHK(c, wide_total_for_adding(c, P.wide_total));
         if (P.all_wide) c->wide_host = (c->wide_host < 0 ? 0 : c->wide_host) + (long long)plan.blocks;
-        const int slot = (int)(c->k_calls % HVC_PROF_RING);
-        const hipError_t e = hvc::launch_islow_mixed(P, c->stream, profile ? c->k0[slot] : nullptr, profile ? c->k1[slot] : nullptr);
-        if (e != hipSuccess) return fail_hip(c, e);
-        if (profile) c->k_calls++;
+        HIPCHK(c, profiled_launch(c, profile, [&](hipEvent_t k0, hipEvent_t k1) { return hvc::launch_islow_mixed(P, c->stream, k0, k1); }));
         return HVC_OK;
     }
     if (n == 8 && (r = reserve_mixed_fix_list(c, plan.map.size() * HVC_MIXED_UNIT))) return r;
@@ -147,26 +140,19 @@ int mixed_launch_plan(hvc_ctx *c, const hvc::MixedPlan &plan, const int16_t *d_c
     if ((r = upload_plan(c, plan, P))) return r;
     P.coefs = d_coefs;
     P.pixels = d_pixels;
-    if (n != 8) {
-        P.wide_total = reinterpret_cast<unsigned long long *>(c->d_fix_count.as<unsigned>() + 2);
-        if (!c->wide_total_started) HIPCHK(c, hipMemsetAsync(P.wide_total, 0, sizeof *P.wide_total, c->stream));
-        c->wide_total_started = true;
-        const int slot = (int)(c->k_calls % HVC_PROF_RING);
-        const hipError_t e = hvc::launch_decode_mixed_scaled(P, n, c->stream, profile ? c->k0[slot] : nullptr, profile ? c->k1[slot] : nullptr);
-        if (e != hipSuccess) return fail_hip(c, e);
-        if (profile) c->k_calls++;
+    if (n != 8) { // k_decode_mixed_scaled: the total alone
+        HIPCHK(c, wide_total_for_adding(c, P.wide_total));
+        HIPCHK(c, profiled_launch(c, profile, [&](hipEvent_t k0, hipEvent_t k1) { return hvc::launch_decode_mixed_scaled(P, n, c->stream, k0, k1); }));
         return HVC_OK;
     }
     P.all_wide = c->decode_kernel == 2;
     fix_assign(c, P);
-    const int slot = (int)(c->k_calls % HVC_PROF_RING);
-    const hipError_t e = hvc::launch_decode_mixed(P, c->stream, profile ? c->k0[slot] : nullptr, profile ? c->k1[slot] : nullptr);
+    const hipError_t e = profiled_launch(c, profile, [&](hipEvent_t k0, hipEvent_t k1) { return hvc::launch_decode_mixed(P, c->stream, k0, k1); });
     if (e != hipSuccess) {
         fix_reset(c);
         return fail_hip(c, e);
     }
     fix_commit(c);
-    if (profile) c->k_calls++;
     return HVC_OK;
 }
 
@@ -413,6 +399,8 @@ int decode_frames_mixed_rgb_impl(hvc_ctx *c, const int16_t *coefs, const size_t 
 // Files -> pixels: host Huffman reader || upload (copy stream) || k_decode_mixed of the previous chunk (compute stream), as
 // decode_batch_impl (hvc_capi_jpeg.hip) -- with chunks cut by the bytes of their coefficient records, a plan per chunk, and a
 // status per file: a file that fails keeps its slot in the chunk's ring buffer and is left out of the chunk's plan.
+// Which files take part, every offset into a ring slot, the ring sizes and the copies that take a chunk's output back to host
+// memory are hvc::MixedDecodeChunks (hvc_mixed_decode_chunks.cpp, plain C++): nothing below rounds, compares or bounds an offset.
 // form.rgb(): a file's record in `pixels` is its RGB image; the chunk's planes go to a device slot of their own ring and
 // k_ycc_to_rgb_mixed follows k_decode_mixed on the compute stream.  form.scale_denom = 2, 4, 8: the same pipeline with the
 // scaled infos describing every output and k_decode_mixed_scaled as the block stage; full-size planes exist nowhere.
@@ -434,149 +422,36 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     bool libjpeg;
     if (mixed_arith_of(c, form.scale_denom, libjpeg)) return HVC_E_INVALID_ARG; // (scaled forms under the libjpeg setting among them)
-    const int N = scaled_side(form.scale_denom);
-    if (!N) return HVC_E_INVALID_ARG;
+    const int N = scaled_side(form.scale_denom); // (0: the chunk plan refuses the form)
     if (stats) std::memset(stats, 0, sizeof *stats);
-    if (n_files == 0) return HVC_OK;
-    // what describes a file's OUTPUT (its planes, its image's size): its info, or the scaled form of it -- blocks, tables and
-    // coefficient offsets are the same in both
-    std::vector<hvc_jpeg_info> scaled;
-    if (N != 8) {
-        scaled.resize((size_t)n_files);
-        for (int f = 0; f < n_files; f++)
-            if (status[f] == HVC_OK && infos[f].n_comp >= 0 && infos[f].n_comp <= 4) scaled_info(infos[f], N, scaled[(size_t)f]);
-    }
-    const hvc_jpeg_info *const oinfos = N != 8 ? scaled.data() : infos;
-    // the size of a file's record in `pixels`: its image's, or (resized) the size the caller names for it
-    auto out_w = [&](int f) { return form.resized() ? form.out_widths[f] : oinfos[f].width; };
-    auto out_h = [&](int f) { return form.resized() ? form.out_heights[f] : oinfos[f].height; };
-    if (form.resized() && (!form.out_heights || (form.filter != HVC_RESIZE_BOX && form.filter != HVC_RESIZE_BILINEAR && form.filter != HVC_RESIZE_BICUBIC)))
-        return HVC_E_INVALID_ARG;
-    if (chunk_bytes == 0) chunk_bytes = (size_t)64 << 20;
     if (threads < 1) threads = 1;
     if (threads > 256) threads = 256;
     const int NB = hvc_ctx::RING;
-
     // the files that take part (their header was read), cut into chunks; everything else keeps the status it came with
-    struct Chunk {
-        int first = 0, count = 0;    // positions in `take`
-        size_t coef_bytes = 0;
-        size_t pix_lo = 0, pix_hi = 0; // the bytes of `pixels` its files cover
-        size_t plane_bytes = 0;        // (RGB form) its files' padded planes, each on 64 bytes
-        size_t rgb_bytes = 0, mid_bytes = 0; // (resized form) its files' tight RGB images at decoded size and the passes' intermediates
-    };
-    std::vector<hvc::ResizeImage> rimg(form.resized() ? (size_t)n_files : 0); // (resized form) file f's image in its chunk's RGB slot, and where it goes
-    std::vector<size_t> rgb_rel(form.resized() ? (size_t)n_files : 0, 0);
-    std::vector<int> take;
-    std::vector<Chunk> chunks;
-    std::vector<size_t> coef_rel((size_t)n_files, 0), pix_rel((size_t)n_files, 0);
-    std::vector<size_t> out_bytes((size_t)n_files, 0); // a file's record in `pixels`: its planes, or the span of its image
-    std::vector<size_t> plane_rel(form.rgb() ? (size_t)n_files : 0, 0);
-    std::vector<int> chunk_of((size_t)n_files, -1);
-    bool need_pixels = false;
-    for (int f = 0; f < n_files; f++) {
-        if (status[f] != HVC_OK) continue;
-        const hvc_jpeg_info &fi = infos[f], &oi = oinfos[f];
-        if (!jpegs[f] || fi.n_comp < 0 || fi.n_comp > 4) return HVC_E_INVALID_ARG;
-        size_t &ob = out_bytes[(size_t)f];
-        if (form.rgb()) {
-            if (!rgb_sampling_of(fi)) { // as hvc_jpeg_decode_rgb answers it: the file's own result
-                status[f] = HVC_E_INVALID_ARG;
-                continue;
-            }
-            if (oi.width < 0 || oi.height < 0) return HVC_E_INVALID_ARG;
-            if (form.resized()) { // whether its image can be taken to its size is the file's own result too
-                const int rr = hvc::resize_image_status(oi.width, oi.height, form.out_widths[f], form.out_heights[f], form.filter);
-                const size_t otight = rr ? 0 : hvc::mixed_rgb_row_bytes(form.layout, form.out_widths[f]);
-                const bool narrow = !rr && form.rgb_row_strides && form.rgb_row_strides[f] && form.rgb_row_strides[f] < otight;
-                if (rr || narrow) {
-                    status[f] = rr ? rr : (int)HVC_E_INVALID_ARG;
-                    continue;
-                }
-            }
-            const size_t tight = hvc::mixed_rgb_row_bytes(form.layout, out_w(f));
-            const size_t rs = form.rgb_row_strides && form.rgb_row_strides[f] ? form.rgb_row_strides[f] : tight;
-            if (rs < tight) return HVC_E_INVALID_ARG;
-            ob = hvc::mixed_rgb_span(form.layout, out_w(f), out_h(f), rs);
-        } else {
-            ob = oi.pixel_bytes;
-            if (N == 8 && ob && (pixel_offsets[f] & 7)) return HVC_E_ALIGNMENT; // (scaled planes: any offset)
-        }
-        if (ob) {
-            if (pixel_offsets[f] > pixel_cap || ob > pixel_cap - pixel_offsets[f]) return HVC_E_INVALID_ARG;
-            need_pixels = true;
-        }
-        const size_t cb = fi.coef_count * sizeof(int16_t);
-        if (chunks.empty() || (chunks.back().count > 0 && chunks.back().coef_bytes + cb > chunk_bytes)) {
-            chunks.emplace_back();
-            chunks.back().first = (int)take.size();
-        }
-        Chunk &k = chunks.back();
-        coef_rel[(size_t)f] = k.coef_bytes / sizeof(int16_t);
-        chunk_of[(size_t)f] = (int)chunks.size() - 1;
-        if (ob) {
-            if (k.pix_hi == 0) k.pix_lo = pixel_offsets[f] & ~(size_t)7; // (an image may start anywhere: the slot keeps its offset modulo 8)
-            k.pix_lo = std::min(k.pix_lo, pixel_offsets[f] & ~(size_t)7);
-            k.pix_hi = std::max(k.pix_hi, pixel_offsets[f] + ob);
-        }
-        if (form.rgb()) {
-            plane_rel[(size_t)f] = k.plane_bytes;
-            k.plane_bytes += (oinfos[f].pixel_bytes + 63) & ~(size_t)63;
-        }
-        if (form.resized()) {
-            hvc::ResizeImage &im = rimg[(size_t)f];
-            im.w = oi.width, im.h = oi.height, im.out_w = out_w(f), im.out_h = out_h(f);
-            im.src_offset = rgb_rel[(size_t)f] = k.rgb_bytes, im.src_row_stride = 0;
-            im.dst_row_stride = form.rgb_row_strides ? form.rgb_row_strides[f] : 0;
-            const size_t planes = form.layout == HVC_RGB_PLANAR ? 3 : 1;
-            k.rgb_bytes += (hvc::mixed_rgb_span(form.layout, oi.width, oi.height, hvc::mixed_rgb_row_bytes(form.layout, oi.width)) + 63) & ~(size_t)63;
-            // (an upper bound of what resize_plan_build gives it: rows on 4 bytes, the image on 64)
-            k.mid_bytes += 64 + ((hvc::mixed_rgb_row_bytes(form.layout, im.out_w) + 3) & ~(size_t)3) * (size_t)im.h * planes;
-        }
-        k.coef_bytes += cb;
-        k.count++;
-        take.push_back(f);
-    }
-    if (need_pixels && !pixels) return HVC_E_INVALID_ARG;
-    if (take.empty()) return HVC_OK;
+    hvc::MixedDecodeChunks plan;
+    int r = hvc::mixed_decode_chunks_build(infos, status, jpegs, pixel_offsets, pixel_cap, pixels != nullptr, n_files, chunk_bytes, where, form, plan);
+    if (r || plan.take.empty()) return r;
+    const std::vector<hvc::MixedDecodeChunk> &chunks = plan.chunks;
+    const std::vector<int> &take = plan.take, &chunk_of = plan.chunk_of;
+    const std::vector<size_t> &coef_rel = plan.coef_rel;
+    const hvc_jpeg_info *const oinfos = plan.out_infos(infos); // what describes a file's OUTPUT: its info, or the scaled form of it
     const int n_chunks = (int)chunks.size(), n_take = (int)take.size();
-    size_t ring_bytes = 0, oring_bytes = 0, pring_bytes = 0, rring_bytes = 0, mring_bytes = 0;
-    int largest = 0;
     uint64_t coef_total = 0;
-    for (const Chunk &k : chunks) {
-        ring_bytes = std::max(ring_bytes, k.coef_bytes);
-        if (where == HVC_MEM_HOST) oring_bytes = std::max(oring_bytes, k.pix_hi - k.pix_lo);
-        pring_bytes = std::max(pring_bytes, k.plane_bytes);
-        rring_bytes = std::max(rring_bytes, k.rgb_bytes);
-        mring_bytes = std::max(mring_bytes, k.mid_bytes);
-        largest = std::max(largest, k.count);
-    }
-    if (where == HVC_MEM_HOST)
-        for (int f : take) pix_rel[(size_t)f] = out_bytes[(size_t)f] ? pixel_offsets[f] - chunks[(size_t)chunk_of[(size_t)f]].pix_lo : 0;
 
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
-    int r = pipeline_events(c);
-    if (r) return r;
-    if ((r = ring_ensure(c, coef_rings(c), {ring_bytes, ring_bytes}))) return r; // (a single file larger than chunk_bytes: the ring grows)
-    if ((r = ring_ensure(c, out_rings(c), {oring_bytes}))) return r;
-    if ((r = ring_ensure(c, plane_rings(c), {pring_bytes}))) return r;
-    if (form.resized() && (r = ring_ensure(c, resize_rings(c), {rring_bytes, mring_bytes}))) return r;
+    if ((r = pipeline_events(c))) return r;
+    if ((r = ring_ensure(c, coef_rings(c), {plan.coef_ring, plan.coef_ring}))) return r; // (a single file larger than chunk_bytes: the ring grows)
+    if ((r = ring_ensure(c, out_rings(c), {plan.out_ring}))) return r;
+    if ((r = ring_ensure(c, plane_rings(c), {plan.plane_ring}))) return r;
+    if (form.resized() && (r = ring_ensure(c, resize_rings(c), {plan.rgb_ring, plan.mid_ring}))) return r;
     // the GPU reader: which files of a chunk it hands back (known once the chunk's verdict is read), how many it read
     const bool gpu = c->mixed_reader == HVC_READER_GPU && !host_reader_only;
     MixedGpuReader rd; // (before the feed: pool tasks use it)
     std::vector<char> back(gpu ? (size_t)n_files : 0, 0);
-    std::vector<int> chunk_first, chunk_count;
     unsigned long long gpu_files = 0;
     hipError_t gpu_upload_err = hipSuccess;
-    if (gpu) {
-        for (const Chunk &k : chunks) {
-            chunk_first.push_back(k.first);
-            chunk_count.push_back(k.count);
-        }
-        if ((r = rd.begin(c, jpegs, sizes, infos, coef_rel.data(), take, chunk_first, chunk_count))) return r;
-    }
-    auto gone = [&](int f) { return gpu && back[(size_t)f]; }; // the host reader has it: its record is not this pass's
+    if (gpu && (r = rd.begin(c, jpegs, sizes, infos, coef_rel.data(), take, plan.chunk_first, plan.chunk_count))) return r;
 
     std::atomic<long long> entropy_ns{0};
     const auto wall0 = std::chrono::steady_clock::now();
@@ -616,13 +491,12 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
     wide_total_begin(c);
     std::vector<int> ok; // the chunk's good files with blocks
     uint8_t *const out = where == HVC_MEM_DEVICE ? pixels : nullptr; // (host: the chunk's slot of d_oring)
-    const size_t *dst_off = where == HVC_MEM_DEVICE ? pixel_offsets : pix_rel.data();
-    if (form.resized())
-        for (int f : take) rimg[(size_t)f].dst_offset = dst_off[f];
+    const size_t *dst_off = where == HVC_MEM_DEVICE ? pixel_offsets : plan.pix_rel.data();
+    std::vector<hvc::MixedDecodeRun> runs; // the chunk's copies back to host memory
     r = host_reader_chunks(
         c, feed, n_chunks, threads, wall0, [&](int k) { return chunks[(size_t)k].count; },
         [&](int k) -> size_t {
-            const Chunk &ch = chunks[(size_t)k];
+            const hvc::MixedDecodeChunk &ch = chunks[(size_t)k];
             ok.clear();
             if (gpu) { // segments, descriptors, map and table records instead of coefficients (on the copy stream, as the copy would be)
                 gpu_upload_err = rd.upload(k, c->copy_stream);
@@ -638,7 +512,7 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
         [&](int k, int slot) {
             if (gpu) { // the reader in front of the block stage; the chunk's good files are known from its verdict
                 if (gpu_upload_err != hipSuccess) return fail_hip(c, gpu_upload_err);
-                const Chunk &ch = chunks[(size_t)k];
+                const hvc::MixedDecodeChunk &ch = chunks[(size_t)k];
                 int n_gpu = 0;
                 const int rc = rd.read(k, c->d_ring[slot].as<int16_t>(), c->stream, back, &n_gpu);
                 if (rc) return rc;
@@ -647,76 +521,46 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
                     if (!back[(size_t)take[(size_t)t]] && infos[take[(size_t)t]].coef_count) ok.push_back(take[(size_t)t]);
                 if (ok.empty()) return (int)HVC_OK;
             }
+            const int16_t *coefs = c->d_ring[slot].as<const int16_t>();
+            const int n_ok = (int)ok.size();
             uint8_t *dst = out ? out : c->d_oring[slot].as<uint8_t>();
-            if (!form.rgb())
-                return mixed_launch(c, c->d_ring[slot].as<const int16_t>(), coef_rel.data(), oinfos, ok.data(), (int)ok.size(), dst, dst_off, c->profiling, N);
-            // the planes into the slot of their own ring, the colour pass from there to where the planes would have gone
-            uint8_t *planes = c->d_pring[slot].as<uint8_t>();
+            if (!form.rgb()) return mixed_launch(c, coefs, coef_rel.data(), oinfos, ok.data(), n_ok, dst, dst_off, c->profiling, N);
+            // The planes into the slot of their own ring, the colour pass from there to where the planes would have gone.  Resized:
+            // the colour pass into the slot of the RGB ring instead (tight images at decoded size), the two resampling passes from
+            // there to where the images would have gone.  Every plan is built before anything is enqueued.
+            const bool resized = form.resized();
+            uint8_t *planes = c->d_pring[slot].as<uint8_t>(), *rgb = resized ? c->d_rring[slot].as<uint8_t>() : dst;
             hvc::MixedRgbPlan cplan;
-            if (form.resized()) {
-                // ... the colour pass into the slot of the RGB ring (tight images at decoded size), the two resampling passes from
-                // there to where the images would have gone; every plan is built before anything is enqueued
-                uint8_t *rgb = c->d_rring[slot].as<uint8_t>();
-                hvc::ResizePlan rplan;
-                int rc = hvc::mixed_rgb_plan_build(oinfos, plane_rel.data(), rgb_rel.data(), nullptr, form.layout, ok.data(), (int)ok.size(),
-                                                   (uintptr_t)planes, (uintptr_t)rgb, true, cplan, N);
-                if (!rc) rc = hvc::resize_plan_build(rimg.data(), ok.data(), (int)ok.size(), form.layout, form.filter, (uintptr_t)rgb, (uintptr_t)dst, rplan);
-                if (!rc && rplan.mid_bytes > c->d_mring[slot].cap) rc = HVC_E_INTERNAL;
-                if (!rc) rc = mixed_launch(c, c->d_ring[slot].as<const int16_t>(), coef_rel.data(), oinfos, ok.data(), (int)ok.size(), planes,
-                                           plane_rel.data(), c->profiling, N);
-                if (!rc) rc = mixed_rgb_launch_plan(c, cplan, form.layout, planes, rgb, false);
-                if (!rc) rc = resize_launch_plan(c, rplan, rgb, dst, c->d_mring[slot].as<uint8_t>(), false);
-                return rc;
-            }
-            int rc = hvc::mixed_rgb_plan_build(oinfos, plane_rel.data(), dst_off, form.rgb_row_strides, form.layout, ok.data(), (int)ok.size(),
-                                               (uintptr_t)planes, (uintptr_t)dst, true, cplan, N);
-            if (!rc) rc = mixed_launch(c, c->d_ring[slot].as<const int16_t>(), coef_rel.data(), oinfos, ok.data(), (int)ok.size(), planes,
-                                       plane_rel.data(), c->profiling, N);
-            if (!rc) rc = mixed_rgb_launch_plan(c, cplan, form.layout, planes, dst, false);
+            hvc::ResizePlan rplan;
+            int rc = hvc::mixed_rgb_plan_build(oinfos, plan.plane_rel.data(), resized ? plan.rgb_rel.data() : dst_off,
+                                               resized ? nullptr : form.rgb_row_strides, form.layout, ok.data(), n_ok, (uintptr_t)planes,
+                                               (uintptr_t)rgb, true, cplan, N);
+            if (!rc && resized) rc = hvc::resize_plan_build(plan.rimg.data(), ok.data(), n_ok, form.layout, form.filter, (uintptr_t)rgb, (uintptr_t)dst, rplan);
+            if (!rc && resized && rplan.mid_bytes > c->d_mring[slot].cap) rc = HVC_E_INTERNAL;
+            if (!rc) rc = mixed_launch(c, coefs, coef_rel.data(), oinfos, ok.data(), n_ok, planes, plan.plane_rel.data(), c->profiling, N);
+            if (!rc) rc = mixed_rgb_launch_plan(c, cplan, form.layout, planes, rgb, false);
+            if (!rc && resized) rc = resize_launch_plan(c, rplan, rgb, dst, c->d_mring[slot].as<uint8_t>(), false);
             return rc;
         },
         [&](int k, int slot) {
             hipError_t he = hipSuccess;
             if (where != HVC_MEM_HOST) return he;
-            const Chunk &ch = chunks[(size_t)k];
-            const uint8_t *dst = c->d_oring[slot].as<const uint8_t>();
-            // the records of consecutive good files go back in one copy where only alignment padding lies between them
-            // (the padding between records is nobody's; a failed file's record is never touched)
-            size_t run_lo = 0, run_hi = 0;
-            auto flush = [&]() {
-                if (run_hi > run_lo && he == hipSuccess)
-                    he = hipMemcpyAsync(pixels + ch.pix_lo + run_lo, dst + run_lo, run_hi - run_lo, hipMemcpyDeviceToHost, c->stream);
-                run_lo = run_hi = 0;
-            };
-            int prev_t = -2;
-            for (int t = ch.first; t < ch.first + ch.count; t++) {
-                const int f = take[(size_t)t];
-                if (status[f] != HVC_OK || !out_bytes[(size_t)f] || gone(f)) continue;
-                const size_t lo = pix_rel[(size_t)f], hi = lo + out_bytes[(size_t)f];
-                if (form.rgb() && form.rgb_row_strides && form.rgb_row_strides[f] > hvc::mixed_rgb_row_bytes(form.layout, out_w(f))) {
-                    flush(); // rows with room between them: the image row by row, the caller's bytes between rows stay
-                    if (he == hipSuccess)
-                        he = hipMemcpy2DAsync(pixels + ch.pix_lo + lo, form.rgb_row_strides[f], dst + lo, form.rgb_row_strides[f],
-                                              hvc::mixed_rgb_row_bytes(form.layout, out_w(f)),
-                                              hvc::mixed_rgb_rows(form.layout, out_h(f)), hipMemcpyDeviceToHost, c->stream);
-                    continue;
-                }
-                // (scaled records lie at any offset: there the runs join only where they touch, and no byte between records is written)
-                // (host_reader_only: the files masked out of this pass keep their room, so what lies between two of its files
-                // may be another file's record -- its runs join only where they touch)
-                const bool joins = run_hi > run_lo && t == prev_t + 1 && lo >= run_hi && lo - run_hi < (N == 8 && !host_reader_only && !form.resized() ? (size_t)4096 : (size_t)1);
-                if (!joins) flush();
-                if (run_hi == run_lo) run_lo = lo;
-                run_hi = hi;
-                prev_t = t;
+            // what the kernels wrote and nothing else: never a failed file's record, never the caller's row padding
+            hvc::mixed_decode_download_runs(plan, k, status, gpu ? back.data() : nullptr, form, N != 8, host_reader_only, runs);
+            uint8_t *to = pixels + chunks[(size_t)k].pix_lo;
+            const uint8_t *from = c->d_oring[slot].as<const uint8_t>();
+            for (const hvc::MixedDecodeRun &run : runs) {
+                if (he != hipSuccess) break;
+                he = run.rows ? hipMemcpy2DAsync(to + run.lo, run.row_stride, from + run.lo, run.row_stride, run.row_bytes, run.rows,
+                                                 hipMemcpyDeviceToHost, c->stream)
+                              : hipMemcpyAsync(to + run.lo, from + run.lo, run.bytes, hipMemcpyDeviceToHost, c->stream);
             }
-            flush();
             return he;
         },
         stats);
     if (stats) {
         stats->entropy_ms_sum = (double)entropy_ns.load() * 1e-6;
-        stats->frames_per_chunk = largest;
+        stats->frames_per_chunk = plan.largest;
         stats->coef_bytes = coef_total;
     }
     if (host_reader_only) return r;

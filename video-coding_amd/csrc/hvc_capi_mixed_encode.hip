@@ -49,10 +49,7 @@ int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const
     if (r) return r;
     P.pixels = d_pixels;
     P.coefs = d_coefs;
-    const int slot = (int)(c->k_calls % HVC_PROF_RING);
-    const hipError_t e = hvc::launch_encode_mixed(P, c->stream, profile ? c->k0[slot] : nullptr, profile ? c->k1[slot] : nullptr);
-    if (e != hipSuccess) return fail_hip(c, e);
-    if (profile) c->k_calls++;
+    HIPCHK(c, profiled_launch(c, profile, [&](hipEvent_t k0, hipEvent_t k1) { return hvc::launch_encode_mixed(P, c->stream, k0, k1); }));
     return HVC_OK;
 }
 

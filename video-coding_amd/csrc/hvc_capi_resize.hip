@@ -37,21 +37,20 @@ int resize_launch_plan(hvc_ctx *c, const hvc::ResizePlan &plan, const uint8_t *d
     P.dst[0] = d_dst, P.dst[1] = d_mid;
     P.recs = reinterpret_cast<const hvc::ResizeRecK *>(d + at[4]);
     P.taps = reinterpret_cast<const int *>(d + at[5]);
-    const int slot = (int)(c->k_calls % HVC_PROF_RING);
-    if (profile) HIPCHK(c, hipEventRecord(c->k0[slot], c->stream));
-    P.images = reinterpret_cast<const hvc::ResizeImageK *>(d + at[0]);
-    P.map = reinterpret_cast<const unsigned *>(d + at[1]);
-    P.n_units = (unsigned)plan.h.map.size();
-    hipError_t e = hvc::launch_resize_h_mixed(P, c->stream);
-    if (e != hipSuccess) return fail_hip(c, e);
-    P.images = reinterpret_cast<const hvc::ResizeImageK *>(d + at[2]);
-    P.map = reinterpret_cast<const unsigned *>(d + at[3]);
-    P.n_units = (unsigned)plan.v.map.size();
-    if ((e = hvc::launch_resize_v_mixed(P, c->stream)) != hipSuccess) return fail_hip(c, e);
-    if (profile) {
-        HIPCHK(c, hipEventRecord(c->k1[slot], c->stream));
-        c->k_calls++;
-    }
+    // (one entry of the profiling ring around the two passes)
+    HIPCHK(c, profiled_launch(c, profile, [&](hipEvent_t k0, hipEvent_t k1) {
+               hipError_t e = k0 ? hipEventRecord(k0, c->stream) : hipSuccess;
+               if (e != hipSuccess) return e;
+               P.images = reinterpret_cast<const hvc::ResizeImageK *>(d + at[0]);
+               P.map = reinterpret_cast<const unsigned *>(d + at[1]);
+               P.n_units = (unsigned)plan.h.map.size();
+               if ((e = hvc::launch_resize_h_mixed(P, c->stream)) != hipSuccess) return e;
+               P.images = reinterpret_cast<const hvc::ResizeImageK *>(d + at[2]);
+               P.map = reinterpret_cast<const unsigned *>(d + at[3]);
+               P.n_units = (unsigned)plan.v.map.size();
+               if ((e = hvc::launch_resize_v_mixed(P, c->stream)) != hipSuccess) return e;
+               return k1 ? hipEventRecord(k1, c->stream) : hipSuccess;
+           }));
     return HVC_OK;
 }
 

@@ -12,6 +12,7 @@
 //                        their RGB forms: hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed_rgb, and the
 //                        reduced-size forms hvc_decode_frames_mixed_scaled, hvc_jpeg_decode_batch_mixed_scaled, _scaled_rgb); under
 //                        hvc_set_mixed_arithmetic(HVC_ARITH_LIBJPEG) the full-size ones launch the kernels of hvc_mixed_libjpeg.hip
+//                        (the file pipeline's chunk cut and download runs: hvc_mixed_decode_chunks.h, plain C++)
 //   hvc_capi_mixed_encode.hip  the same in the other direction: raw frames of different geometry, sampling and quality to records
 //                        and files (behind hvc_encode_frames_mixed, hvc_jpeg_encode_batch_mixed), and the same from RGB images
 //                        (behind hvc_rgb_to_yuv_mixed, hvc_encode_frames_mixed_rgb, hvc_jpeg_encode_batch_mixed_rgb[_gpu]); the part
@@ -55,6 +56,7 @@
 #include "hvc_mixed_plan.h"
 #include "hvc_mixed_encode_plan.h"
 #include "hvc_mixed_encode_chunks.h"
+#include "hvc_mixed_decode_chunks.h"
 #include "hvc_pool.h"
 #include "hvc_scaled_spec.h"
 
@@ -360,6 +362,24 @@ inline void wide_total_begin(hvc_ctx *c) {
 inline void fix_reset(hvc_ctx *c) { // after a failed launch: all counters to zero, in stream order
     (void)hipMemsetAsync(c->d_fix_count.p, 0, HVC_FIX_WORDS * sizeof(unsigned), c->stream); // (and the total behind the first pair)
 }
+// The total for a block stage that only ADDS to it (k_decode_mixed_scaled, k_islow_mixed: no fix-up list): the call's first
+// launch has it cleared in front of it, in stream order
+inline hipError_t wide_total_for_adding(hvc_ctx *c, unsigned long long *&total) {
+    total = reinterpret_cast<unsigned long long *>(c->d_fix_count.as<unsigned>() + 2);
+    const hipError_t e = c->wide_total_started ? hipSuccess : hipMemsetAsync(total, 0, sizeof *total, c->stream);
+    if (e == hipSuccess) c->wide_total_started = true;
+    return e;
+}
+
+// A launch that takes the next entry of the profiling ring (hvc_kernel_ms_history) when `profile`: launch(k0, k1) is given the
+// entry's two events to record around its kernels, or two null events; the entry counts once the launch is enqueued.
+template <class Launch>
+inline hipError_t profiled_launch(hvc_ctx *c, bool profile, Launch launch) {
+    const int slot = (int)(c->k_calls % HVC_PROF_RING);
+    const hipError_t e = launch(profile ? (hipEvent_t)c->k0[slot] : nullptr, profile ? (hipEvent_t)c->k1[slot] : nullptr);
+    if (e == hipSuccess && profile) c->k_calls++;
+    return e;
+}
 
 // Launches longer than about 3 ms lose 2-3 % against back-to-back shorter ones (measured on MI355X: 1080p batches of
 // 2048 / 4096 frames per launch run at 71.9 / 71.6 % of the HBM peak, 1024-frame launches -- even 1900 of them back to
@@ -590,13 +610,7 @@ int decode_batch_gpu(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *size
 // and hvc_jpeg_decode_batch_mixed in hvc_capi_jpeg.hip)
 int decode_frames_mixed_impl(hvc_ctx *c, const int16_t *coefs, const size_t *coef_offsets, const hvc_jpeg_info *infos, int n_frames,
                              uint8_t *pixels, const size_t *pixel_offsets, int where, int scale_denom = 1);
-// What the files of a mixed batch become.  Default: their padded planes, at pixel_offsets.  rgb_offsets set: RGB images
-// there (`pixels` / `pixel_cap` are the RGB buffer), rows rgb_row_strides[f] apart (nullptr: tight), through k_ycc_to_rgb_mixed
-// behind every chunk's block stage; the planes stay in a device ring.
-// scale_denom 2, 4, 8: the planes (or the planes the images are made of) are those of hvc_jpeg_scaled_info, through
-// k_decode_mixed_scaled; `infos` stay the FULL-size infos, the pipeline derives the scaled ones.
-// out_widths set (with rgb_offsets): the RGB images go to a device ring slot of their own, tight, and the two resampling passes
-// (hvc_capi_resize.hip) take image f from there to out_widths[f] x out_heights[f] at rgb_offsets[f], rows rgb_row_strides[f] apart.
+// (MixedForm -- what the files of a mixed batch become -- and the pipeline's chunk cut: hvc_mixed_decode_chunks.h, plain C++)
 // Which arithmetic a mixed decode call runs in, or that it is refused (the one rule of hvc_set_mixed_arithmetic).  At the
 // default the calls do what they did before there was such a setting: the model's arithmetic, and HVC_E_INVALID_ARG unless
 // hvc_set_arithmetic is the model's too (the RTL arithmetic has no mixed form, as it has no scaled one).  Under
@@ -607,15 +621,6 @@ inline int mixed_arith_of(const hvc_ctx *c, int scale_denom, bool &libjpeg) {
     if (libjpeg) return scale_denom == 1 ? HVC_OK : HVC_E_INVALID_ARG;
     return c->arith != HVC_ARITH_MODEL ? HVC_E_INVALID_ARG : HVC_OK;
 }
-struct MixedForm {
-    const size_t *rgb_offsets = nullptr, *rgb_row_strides = nullptr;
-    int layout = 0;
-    int scale_denom = 1;
-    const int *out_widths = nullptr, *out_heights = nullptr;
-    int filter = 0;
-    bool rgb() const { return rgb_offsets != nullptr; }
-    bool resized() const { return rgb() && out_widths != nullptr; }
-};
 int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads, size_t chunk_bytes,
                             const hvc_jpeg_info *infos, int *status, const size_t *pixel_offsets, uint8_t *pixels, size_t pixel_cap,
                             int where, hvc_batch_stats *stats, const MixedForm &form = MixedForm(), bool host_reader_only = false);
