@@ -737,7 +737,8 @@ HVC_API int hvc_jpeg_encode_rgb(hvc_ctx *ctx, const uint8_t *rgb, size_t rgb_row
  * 4:4:4 and scaled (scale_denom > 1) entry points refuse any arithmetic but MODEL with HVC_E_INVALID_ARG, output untouched,
  * as they do for HARDCAML: their libjpeg forms are not built.  The mixed entry points refuse it under hvc_set_arithmetic in
  * the same way, and have the libjpeg form at full size under a setting of their own (next paragraph).
- * hvc_decode_frames_divergence is unaffected, and there is no encoder side: hvc_set_encode_arithmetic refuses the value.
+ * hvc_decode_frames_divergence is unaffected.  hvc_set_encode_arithmetic refuses the value: the encoder side is a setting of
+ * its own, hvc_set_encode_libjpeg ("Encoding bit-exact to libjpeg" below).
  *
  * Mixed batches (csrc/hvc_mixed_libjpeg.hip): hvc_set_mixed_arithmetic(ctx, HVC_ARITH_LIBJPEG) gives the mixed decode calls --
  * hvc_decode_frames_mixed, hvc_yuv_to_rgb_mixed, hvc_decode_frames_mixed_rgb, hvc_jpeg_decode_batch_mixed, _mixed_rgb and
@@ -755,6 +756,71 @@ HVC_API int hvc_jpeg_encode_rgb(hvc_ctx *ctx, const uint8_t *rgb, size_t rgb_row
  * calls take no part in the setting. */
 HVC_API int hvc_set_mixed_arithmetic(hvc_ctx *ctx, int arith); /* HVC_ARITH_MODEL (default) | HVC_ARITH_LIBJPEG */
 HVC_API int hvc_get_mixed_arithmetic(const hvc_ctx *ctx, int *arith);
+
+/* ------------------------------------------------------------------------- */
+/* Encoding bit-exact to libjpeg (an EXTENSION; csrc/hvc_libjpeg_encode.hip): hvc_set_encode_libjpeg(ctx, 1) makes the encode
+ * entry points produce the coefficients libjpeg-turbo's compressor writes at its defaults (JDCT_ISLOW, no smoothing,
+ * baseline), which is what Pillow, OpenCV and torchvision write.  The claim is about COEFFICIENTS, not file bytes: for the
+ * same component samples and the same quantiser tables the coefficient record equals, block for block and dummy blocks
+ * included, what libjpeg-turbo puts into its file.  Headers, Huffman tables and the quality-to-table mapping stay this
+ * library's (hvc_quant_table and the infos give the tables; a caller who wants Pillow's tables passes them).  The definition
+ * is restated in numpy in tools/libjpeg_encode_reference.py; tests/test_libjpeg_encode_reference.py holds that against Pillow
+ * (libjpeg-turbo) itself, 0 mismatching coefficients, and tests/golden/libjpeg_encode_pins.json pins Pillow's records.
+ *
+ * 1. Forward DCT: jfdctint.c's jpeg_fdct_islow on p - 128, CONST_BITS 13 and PASS1_BITS 2, rows first and then columns, the
+ *    output t scaled by 8.  The operation list is data, csrc/hvc_fdct_islow_spec.h: the kernel, the numpy form and the
+ *    overflow proof (tests/test_fdct_islow_bounds.py: int32 never wraps, every multiplicand fits 24 bits, |t| <= 8192) expand
+ *    that one list.
+ * 2. Quantiser: with q the table entry and d = 8 q, the value is sign(t) * ((|t| + d / 2) / d) in integer division
+ *    (jcdctmgr.c), stored at the entry's zig-zag position, the DC absolute as the records keep it.  Tables are validated as
+ *    before (1..255, else HVC_E_RANGE).  The division is one host-made multiplier per entry (csrc/hvc_libjpeg_encode_plan.cpp),
+ *    exhausted against C's / for every q and every |t| up to the proved bound (tests/test_libjpeg_encode_plan.py).
+ * 3. Edges, where a call knows the frame's size (the file-level calls, and hvc_encode_frames_mixed through its infos' comp[i]
+ *    .actual_width / .actual_height): every component, actual_width x actual_height of its info, is repeated to the right and
+ *    downward (last column, last row) where the model pads with zeros -- by the file-level calls, which pad; hvc_encode_frames_mixed
+ *    reads the padded pixel records it is given, so the samples of a ragged last block are the caller's.  Every block of
+ *    the padded layout past the component's own ceil(actual / 8) blocks in either direction is a DUMMY block: its AC
+ *    coefficients are 0 and its DC is that of the block before it in libjpeg's MCU buffer (jccoefct.c compress_data),
+ *    row-major inside the component's h x v blocks of the MCU -- a dummy in a real row takes the block on its left; every
+ *    block of a dummy row takes the LAST block of the row above it in the MCU; both chain through dummies to a real block.
+ *    hvc_fdct_quant, hvc_encode_frames and hvc_encode_frames_submit take a layout without sizes: they treat every block as
+ *    real and read the samples they are given; so does hvc_encode_frames_mixed for a component whose info states no size
+ *    (actual_width or actual_height <= 0).  A stated size whose blocks are not inside the plane is HVC_E_INVALID_ARG.
+ *    This library's 4:2:2 files carry the model's sampling factors 2x2 / 1x2 / 1x2 (Parameters.c422), libjpeg's own are
+ *    2x1 / 1x1 / 1x1: the same planes and, where the height is a whole number of 16-row MCUs, the same record; elsewhere the
+ *    model's layout has one more block row per plane, all dummies, which follow the rule above with the file's own factors.
+ *    In the calls that take planes the component planes are the caller's: this library's 4:2:0 / 4:2:2 frames carry chroma
+ *    planes of width / 2 (and height / 2), and those are the samples the claim is about.
+ * 4. From RGB (hvc_rgb_to_yuv, hvc_jpeg_encode_rgb and the mixed RGB calls): the colour step is the existing libjpeg form
+ *    (tools/rgb_reference.py), then jcsample.c's averaging of the full-size chroma -- h2v2: (a + b + c + d + bias) >> 2 with
+ *    bias 1, 2, 1, 2, ... along the output row; h2v1: (a + b + bias) >> 1 with bias 0, 1, 0, 1, ... .  Edges: the last column of
+ *    the full-size chroma is repeated to whole blocks of the sub-sampled plane BEFORE the averaging (the bias alternates, so a
+ *    padded chroma column is not always the copy of the last real one), and the last AVERAGED row is repeated downward
+ *    (jcprepct.c); luma is repeated as in 3.  Odd sizes under 4:2:0 / 4:2:2 stay refused as before.  k_rgb_to_ycc_libjpeg and
+ *    k_rgb_to_ycc_libjpeg_mixed expand one lane (csrc/hvc_rgb_libjpeg_dev.h) that works in the coordinates of the output planes
+ *    and clamps what it reads: in the encode pipelines (hvc_jpeg_encode_rgb, hvc_encode_frames_mixed_rgb,
+ *    hvc_jpeg_encode_batch_mixed_rgb[_gpu]) the colour pass itself writes every component up to ceil(actual / 8) * 8 both ways
+ *    -- the pipelines' clear of the plane slot stays, what lies beyond are dummy blocks -- while hvc_rgb_to_yuv and
+ *    hvc_rgb_to_yuv_mixed write the frame's own samples and nothing else, as without the setting.
+ *
+ * Where it applies.  The setting is per context, 0 by default, independent of every other setting; at 0 every entry point
+ * does byte for byte what it does without it.  At 1 hvc_set_encode_arithmetic is not consulted, except that HVC_ARITH_HARDCAML
+ * together with it is HVC_E_INVALID_ARG at the encode call, output untouched.  It applies to hvc_fdct_quant, hvc_encode_frames
+ * (host and device memory), hvc_encode_frames_submit, hvc_jpeg_encode, hvc_jpeg_encode_batch and hvc_jpeg_encode_batch_gpu:
+ * k_fdct_islow in k_encode's launch geometry and record layout, and behind it on the same stream k_dummy_blocks for the
+ * file-level calls; and to hvc_encode_frames_mixed, hvc_jpeg_encode_batch_mixed and hvc_jpeg_encode_batch_mixed_gpu:
+ * k_fdct_islow_mixed under k_encode_mixed's decomposition, its multipliers a record per distinct table and the dummy blocks a
+ * list of (record, source) pairs beside the plan image, uploaded only under the setting, k_dummy_blocks_mixed behind it.  Every
+ * file of a mixed call is what hvc_jpeg_encode writes for that frame alone under the setting; statuses are as before.  The
+ * Huffman coders sit behind the records and do not change; hvc_set_huffman_tables and hvc_set_restart_interval combine with it.
+ * From RGB it applies to hvc_rgb_to_yuv, hvc_jpeg_encode_rgb, hvc_rgb_to_yuv_mixed, hvc_encode_frames_mixed_rgb,
+ * hvc_jpeg_encode_batch_mixed_rgb and hvc_jpeg_encode_batch_mixed_rgb_gpu (4. above); every file of the mixed RGB calls is what
+ * hvc_jpeg_encode_rgb writes for that image alone under the setting.
+ * Refused under the setting with HVC_E_INVALID_ARG, output untouched, never computed the model's way in silence:
+ *   hvc_encode_frames_recon, hvc_encode_frames_divergence                         (no libjpeg form)
+ * hvc_set_encode_libjpeg: HVC_E_INVALID_ARG for anything but 0 and 1, the setting unchanged. */
+HVC_API int hvc_set_encode_libjpeg(hvc_ctx *ctx, int on);      /* 0 (default) | 1 */
+HVC_API int hvc_get_encode_libjpeg(const hvc_ctx *ctx, int *on);
 
 /* ------------------------------------------------------------------------- */
 /* Decoding at reduced size: 1/2, 1/4, 1/8 (an EXTENSION; the model has no counterpart).  libjpeg's scale_denom: the inverse

@@ -373,6 +373,10 @@ let decode_frames_divergence =
    int hvc_set_encode_arithmetic(ctx, arith);  int hvc_get_encode_arithmetic(ctx, arith) *)
 let set_encode_arithmetic = foreign "hvc_set_encode_arithmetic" (ctx @-> int @-> returning int)
 let get_encode_arithmetic = foreign "hvc_get_encode_arithmetic" (ctx @-> ptr int @-> returning int)
+(* the encoder bit-exact to libjpeg-turbo, a setting of its own:
+   int hvc_set_encode_libjpeg(ctx, on);  int hvc_get_encode_libjpeg(ctx, on) *)
+let set_encode_libjpeg = foreign "hvc_set_encode_libjpeg" (ctx @-> int @-> returning int)
+let get_encode_libjpeg = foreign "hvc_get_encode_libjpeg" (ctx @-> ptr int @-> returning int)
 
 (* int hvc_encode_frames_divergence(ctx, pixels, pixel_frame_stride, qtabs, n_qtabs, comps, n_comp, n_frames,
                                     max_diff, diff_frame_stride, where): max |model - hardcaml| coefficient per block *)

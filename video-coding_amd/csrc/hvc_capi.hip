@@ -406,6 +406,19 @@ int hvc_set_encode_arithmetic(hvc_ctx *c, int arith) try {
     return HVC_OK;
 } HVC_ABI_CATCH
 
+// the libjpeg-exact encoder: a setting of its own (hvc_set_encode_arithmetic's refusals are pinned by tests)
+int hvc_set_encode_libjpeg(hvc_ctx *c, int on) try {
+    if (!c || (on != 0 && on != 1)) return HVC_E_INVALID_ARG;
+    c->enc_libjpeg = on;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
+int hvc_get_encode_libjpeg(const hvc_ctx *c, int *on) try {
+    if (!c || !on) return HVC_E_INVALID_ARG;
+    *on = c->enc_libjpeg;
+    return HVC_OK;
+} HVC_ABI_CATCH
+
 int hvc_get_encode_arithmetic(const hvc_ctx *c, int *arith) try {
     if (!c || !arith) return HVC_E_INVALID_ARG;
     *arith = c->enc_arith;
@@ -1419,6 +1432,7 @@ int encode_frames_impl(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const
                        const EncodeOpts &o) {
     if (!c || !coefs || !pixels || n_frames < 0) return HVC_E_INVALID_ARG;
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
+    if (o.libjpeg && o.arith == HVC_ARITH_HARDCAML) return HVC_E_INVALID_ARG; // (hvc_set_encode_libjpeg: the two do not combine)
     int r = check_qtabs(qtabs, n_qtabs, true);
     if (r) return r;
     // Encoder tables are 8-bit (Markers.Dqt element_precision = 8, encoder.ml:224-229;
@@ -1440,13 +1454,48 @@ int encode_frames_impl(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, const
     for (int i = 0; i < n_qtabs * 64; i++) // fl((1 + 2^-16) / (4t)): see quant1 in hvc_kernels.hip
         P.qrcp[i] = hvc::encode_quant_reciprocal(qtabs[i]); // (hvc_mixed_encode_plan.h: k_encode_mixed's tables come from it too)
     // HVC_ARITH_HARDCAML (hvc_set_encode_arithmetic): the RTL encoder twin (hvc_hardcaml.hip) in place of k_encode
-    const bool twin = o.arith == HVC_ARITH_HARDCAML;
+    const bool twin = !o.libjpeg && o.arith == HVC_ARITH_HARDCAML;
     hvc::HardcamlEncodeParams H;
     if (twin) H = hardcaml_encode_params(P, qtabs, n_qtabs);
+    // hvc_set_encode_libjpeg: k_fdct_islow (hvc_libjpeg_encode.hip) in place of k_encode and, where the caller gave the frames'
+    // sizes, k_dummy_blocks behind it
+    hvc::FdctIslowParams J;
+    hvc::DummyBlocksParams D;
+    D.total = 0;
+    if (o.libjpeg) {
+        fill_geometry(J, P, P.coef_fs, P.pixel_fs, P.n_frames);
+        hvc::libjpeg_encode_tables(qtabs, n_qtabs, J.magic, J.half);
+        if (o.edges) {
+            int bw[HVC_MAX_COMP], bh[HVC_MAX_COMP], rw[HVC_MAX_COMP], rh[HVC_MAX_COMP], hs[HVC_MAX_COMP];
+            size_t off[HVC_MAX_COMP];
+            for (int i = 0; i < n_comp; i++) {
+                bw[i] = comps[i].blocks_w;
+                bh[i] = comps[i].blocks_h;
+                rw[i] = (o.edges->comp[i].actual_width + 7) / 8;
+                rh[i] = (o.edges->comp[i].actual_height + 7) / 8;
+                hs[i] = o.edges->comp[i].hscale;
+                off[i] = comps[i].coef_offset;
+            }
+            if (!hvc::dummy_blocks_geometry(D, n_comp, bw, bh, rw, rh, hs, off)) return HVC_E_INVALID_ARG;
+            D.coef_fs = coef_fs;
+        }
+    }
 
     // frames [f0, f0 + cnt) of the batch at d_pixels / d_coefs, in launches of `per` frames
     auto launch_range = [&](const uint8_t *d_pixels, int16_t *d_coefs, int f0, int cnt, hipEvent_t k0, hipEvent_t k1) {
         return for_each_launch(f0, cnt, per, k0, k1, [&](int f, int n, hipEvent_t e0, hipEvent_t e1) {
+            if (o.libjpeg) {
+                hvc::FdctIslowParams Jk = J;
+                Jk.n_frames = n;
+                Jk.coefs = d_coefs + (size_t)f * coef_fs;
+                Jk.pixels = d_pixels + (size_t)f * pixel_fs;
+                const hipError_t e = hvc::launch_fdct_islow(Jk, c->stream, e0, e1);
+                if (e != hipSuccess || D.total == 0) return e;
+                hvc::DummyBlocksParams Dk = D;
+                Dk.n_frames = n;
+                Dk.coefs = Jk.coefs;
+                return hvc::launch_dummy_blocks(Dk, c->stream);
+            }
             if (twin) {
                 hvc::HardcamlEncodeParams Hk = H;
                 Hk.n_frames = n;
@@ -1495,6 +1544,7 @@ int hvc_encode_frames_recon(hvc_ctx *c, const uint8_t *pixels, size_t pixel_fs, 
                             const hvc_component *comps, int n_comp, int n_frames, int16_t *coefs, size_t coef_fs,
                             uint8_t *recon, uint8_t *error, int where) try {
     if (!c || !coefs || !pixels || n_frames < 0) return HVC_E_INVALID_ARG;
+    if (encode_libjpeg_refused(c)) return HVC_E_INVALID_ARG; // (no libjpeg form of the debugging tail: hvc_set_encode_libjpeg)
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     Layout L;
     int r = check_qtabs(qtabs, n_qtabs, true);
@@ -1579,6 +1629,7 @@ int hvc_encode_frames_divergence(hvc_ctx *c, const uint8_t *pixels, size_t pixel
                                  const hvc_component *comps, int n_comp, int n_frames, uint8_t *max_diff, size_t diff_fs,
                                  int where) try {
     if (!c || !pixels || !max_diff || n_frames < 0) return HVC_E_INVALID_ARG;
+    if (encode_libjpeg_refused(c)) return HVC_E_INVALID_ARG; // (model against RTL: nothing of it is libjpeg's)
     if (where != HVC_MEM_HOST && where != HVC_MEM_DEVICE) return HVC_E_INVALID_ARG;
     int r = check_qtabs(qtabs, n_qtabs, true);
     if (r) return r;

@@ -284,7 +284,8 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
             if (error.load() == 0) try {
                 if (t.kind == 0) {
                     // (the info's actual plane sizes are width x height and the chroma's by `chroma`: tests/test_mixed_encode_chunks.py)
-                    pad_frame(info, frames[f], c->eh_in[slot].as<uint8_t>() + (size_t)(f - k * C) * pix_bytes);
+                    // (hvc_set_encode_libjpeg: the replicating sibling, hvc_libjpeg_encode_plan.h)
+                    (c->enc_libjpeg ? hvc::pad_frame_replicate : pad_frame)(info, frames[f], c->eh_in[slot].as<uint8_t>() + (size_t)(f - k * C) * pix_bytes);
                 } else if (!gpu_entropy) {
                     const int16_t *cf = c->eh_out[slot].as<const int16_t>() + (size_t)(f - k * C) * info.coef_count;
                     e = opt ? hvc::entropy_encode_optimised(&info, cf, jpegs[f], caps[f], &sizes[f], ri)
@@ -343,6 +344,7 @@ static int encode_batch_impl(hvc_ctx *c, const uint8_t *const *frames, int n_fra
     hipStream_t compute = c->stream;
     EncodeOpts block_stage(c); // (the chunks' launches take no entry of the profiling ring)
     block_stage.profile = false;
+    block_stage.edges = &info; // (hvc_set_encode_libjpeg: the files' dummy blocks)
     try {
     for (int it = 0; it < n_chunks + 3 && rc == HVC_OK; it++) {
         // stage 1: pad chunk `it` (its pinned slot was uploaded and synchronised two iterations ago)

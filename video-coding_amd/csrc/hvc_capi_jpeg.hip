@@ -306,6 +306,11 @@ int hvc_jpeg_encode(hvc_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_
     const int cw = chroma == 444 ? width : width / 2, ch = chroma == 420 ? height / 2 : height;
     const int sw[3] = {width, cw, cw}, sh[3] = {height, ch, ch};
     for (int i = 0; i < 3; i++) {
+        if (c->enc_libjpeg && sw[i] > 0 && sh[i] > 0) { // hvc_set_encode_libjpeg: libjpeg repeats the last column and row
+            hvc::pad_plane_replicate(src[i], sw[i], sh[i], planes.data() + info.layout[i].plane_offset, info.comp[i].decoded_width,
+                                     info.comp[i].decoded_height, info.layout[i].stride);
+            continue;
+        }
         const int bw = sw[i] < info.comp[i].decoded_width ? sw[i] : info.comp[i].decoded_width;
         const int bh = sh[i] < info.comp[i].decoded_height ? sh[i] : info.comp[i].decoded_height;
         for (int row = 0; row < bh; row++)
@@ -327,6 +332,7 @@ static int encode_padded_on_device(hvc_ctx *c, const hvc_jpeg_info &info, size_t
     const int ri = c->restart_interval;
     EncodeOpts o(c);
     o.profile = false;
+    o.edges = &info; // (hvc_set_encode_libjpeg: the file's dummy blocks)
     r = encode_frames_impl(c, c->d_in.as<const uint8_t>(), info.pixel_bytes, &info.qtabs[0][0], info.n_qtabs, info.layout, 3, 1,
                            c->d_out.as<int16_t>(), info.coef_count, HVC_MEM_DEVICE, o);
     if (r) return r;
@@ -355,6 +361,40 @@ static int encode_padded_on_device(hvc_ctx *c, const hvc_jpeg_info &info, size_t
     return HVC_OK;
 }
 
+hipError_t rgb_to_ycc_libjpeg_device(const uint8_t *d_rgb, const RgbImage &im, int width, int height, int sampling, int n_frames, uint8_t *d_yuv,
+                                     size_t yuv_fs, const hvc_component *comps, bool pad, hipStream_t s) {
+    if (n_frames <= 0 || width <= 0 || height <= 0) return hipSuccess;
+    const bool grey = sampling == HVC_YUV_400;
+    hvc::RgbLibjpegParams P;
+    std::memset(&P, 0, sizeof P);
+    P.rgb = d_rgb;
+    P.yuv = d_yuv;
+    P.rgb_fs = im.frame_stride;
+    P.yuv_fs = yuv_fs;
+    P.n_frames = n_frames;
+    P.planar = im.layout == HVC_RGB_PLANAR;
+    P.pad = pad;
+    hvc::MixedRgbImageK &K = P.image;
+    K.y_base = comps[0].plane_offset;
+    K.y_stride = comps[0].stride;
+    if (!grey) {
+        K.cb_base = comps[1].plane_offset, K.cr_base = comps[2].plane_offset;
+        K.cb_stride = comps[1].stride, K.cr_stride = comps[2].stride;
+    }
+    K.row_stride = im.row_stride;
+    K.plane_stride = im.row_stride * (size_t)height;
+    K.w = width, K.h = height;
+    K.cw = sampling == HVC_YUV_444 ? width : width / 2, K.ch = sampling == HVC_YUV_420 ? height / 2 : height;
+    K.sampling = sampling;
+    unsigned lx, ly;
+    hvc::libjpeg_rgb_lane_grid(width, height, sampling, pad, lx, ly);
+    if ((unsigned long long)lx * ly * lx >= (1ull << 32)) return hipErrorInvalidValue; // (the lane's row by a reciprocal; 65535 x 65535 stays far inside)
+    K.groups = lx;
+    K.magic = lx > 1 ? (unsigned)(((1ull << 32) + lx - 1) / lx) : 0u;
+    K.lanes = lx * ly;
+    return hvc::launch_rgb_to_ycc_libjpeg(P, s);
+}
+
 // hvc_jpeg_encode of the planes the colour pass makes of an RGB image: the image goes up as it is, k_rgb_to_ycc writes the
 // frame's samples into zeroed padded planes (Plane.create + blit_available), the rest is hvc_jpeg_encode's.
 int hvc_jpeg_encode_rgb(hvc_ctx *c, const uint8_t *rgb, size_t rgb_row_stride, int layout, int width, int height, int chroma, int quality,
@@ -375,8 +415,12 @@ int hvc_jpeg_encode_rgb(hvc_ctx *c, const uint8_t *rgb, size_t rgb_row_stride, i
     if ((r = grow(c, c->d_aux2, in_bytes))) return r;
     HIPCHK(c, hipMemcpyAsync(c->d_aux2.p, rgb, in_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_in.p, 0, info.pixel_bytes, c->stream));
-    HIPCHK(c, rgb_to_ycc_device(c->d_aux2.as<const uint8_t>(), im, width, height, chroma, 1, c->d_in.as<uint8_t>(), info.pixel_bytes, info.layout,
-                                c->stream));
+    // hvc_set_encode_libjpeg: libjpeg's averaging, and the replicated edge written by the colour pass itself (the clear stays: the
+    // samples of the dummy blocks are never looked at)
+    HIPCHK(c, c->enc_libjpeg ? rgb_to_ycc_libjpeg_device(c->d_aux2.as<const uint8_t>(), im, width, height, chroma, 1, c->d_in.as<uint8_t>(),
+                                                         info.pixel_bytes, info.layout, true, c->stream)
+                             : rgb_to_ycc_device(c->d_aux2.as<const uint8_t>(), im, width, height, chroma, 1, c->d_in.as<uint8_t>(),
+                                                 info.pixel_bytes, info.layout, c->stream));
     return encode_padded_on_device(c, info, seg_cap, out, cap, out_len);
 } HVC_ABI_CATCH
 

@@ -40,9 +40,35 @@ int upload_encode_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, hvc::MixedE
 } // namespace
 
 // The block stage of a plan on DEVICE memory, enqueued on c->stream
-int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const uint8_t *d_pixels, int16_t *d_coefs, bool profile) {
+int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const uint8_t *d_pixels, int16_t *d_coefs, bool profile,
+                             const MixedLibjpeg *lje) {
     if (plan.map.empty()) return HVC_OK; // no block at all: nothing to launch
     if (((uintptr_t)d_coefs & 15) || ((uintptr_t)d_pixels & 7)) return HVC_E_ALIGNMENT;
+    if (lje) { // the image: planes | multiplier records | map | dummy pairs -- the last two parts only under the setting
+        std::vector<hvc::FdctIslowTableK> tables;
+        std::vector<hvc::DummyPairK> pairs;
+        hvc::libjpeg_mixed_tables_build(plan.qt, tables);
+        int r = hvc::libjpeg_mixed_dummies_build(lje->infos, lje->coef_offsets, lje->frames, lje->n_list, pairs);
+        if (r) return r;
+        size_t at[4];
+        if ((r = upload_parts(c, c->mixed_enc_plan, {{plan.planes.data(), plan.planes.size() * sizeof(hvc::MixedPlaneK)},
+                                                     {tables.data(), tables.size() * sizeof(hvc::FdctIslowTableK)},
+                                                     {plan.map.data(), plan.map.size() * sizeof(unsigned)},
+                                                     {pairs.data(), pairs.size() * sizeof(hvc::DummyPairK)}}, at)))
+            return r;
+        const unsigned char *d = c->mixed_enc_plan.d.as<const unsigned char>();
+        hvc::FdctIslowMixedParams J;
+        std::memset(&J, 0, sizeof J);
+        J.planes = reinterpret_cast<const hvc::MixedPlaneK *>(d);
+        J.tables = reinterpret_cast<const hvc::FdctIslowTableK *>(d + at[1]);
+        J.map = reinterpret_cast<const unsigned *>(d + at[2]);
+        J.n_units = (unsigned)plan.map.size();
+        J.pixels = d_pixels;
+        J.coefs = d_coefs;
+        HIPCHK(c, profiled_launch(c, profile, [&](hipEvent_t k0, hipEvent_t k1) { return hvc::launch_fdct_islow_mixed(J, c->stream, k0, k1); }));
+        HIPCHK(c, hvc::launch_dummy_blocks_mixed(d_coefs, reinterpret_cast<const hvc::DummyPairK *>(d + at[3]), (unsigned)pairs.size(), c->stream));
+        return HVC_OK;
+    }
     hvc::MixedEncodeParams P;
     std::memset(&P, 0, sizeof P);
     const int r = upload_encode_plan(c, plan, P);
@@ -67,7 +93,8 @@ int encode_frames_mixed_impl(hvc_ctx *c, const uint8_t *pixels, const size_t *pi
     if ((r = hvc::mixed_encode_plan_build(infos, coef_offsets, pixel_offsets, nullptr, n_frames, plan))) return r;
     if (plan.map.empty()) return HVC_OK; // (a set without a block needs no memory)
     if (!coefs || !pixels) return HVC_E_INVALID_ARG;
-    if (where == HVC_MEM_DEVICE) return encode_mixed_launch_plan(c, plan, pixels, coefs, c->profiling);
+    const MixedLibjpeg own{infos, coef_offsets, nullptr, n_frames};
+    if (where == HVC_MEM_DEVICE) return encode_mixed_launch_plan(c, plan, pixels, coefs, c->profiling, c->enc_libjpeg ? &own : nullptr);
     // host memory: the frames' records one after another in c->d_in / c->d_out, each on 64 bytes; only the coefficient
     // planes come back (gaps in the caller's buffer stay untouched)
     std::vector<size_t> d_pix((size_t)n_frames, 0), d_coef((size_t)n_frames, 0), pspan((size_t)n_frames, 0);
@@ -87,7 +114,8 @@ int encode_frames_mixed_impl(hvc_ctx *c, const uint8_t *pixels, const size_t *pi
         if (pspan[(size_t)f])
             HIPCHK(c, hipMemcpyAsync(c->d_in.as<uint8_t>() + d_pix[(size_t)f], pixels + pixel_offsets[f], pspan[(size_t)f],
                                      hipMemcpyHostToDevice, c->stream));
-    if ((r = encode_mixed_launch_plan(c, plan, c->d_in.as<const uint8_t>(), c->d_out.as<int16_t>(), false))) {
+    const MixedLibjpeg staged{infos, d_coef.data(), nullptr, n_frames};
+    if ((r = encode_mixed_launch_plan(c, plan, c->d_in.as<const uint8_t>(), c->d_out.as<int16_t>(), false, c->enc_libjpeg ? &staged : nullptr))) {
         (void)hipStreamSynchronize(c->stream);
         return r;
     }
@@ -115,6 +143,33 @@ size_t rgb_image_span(const hvc_jpeg_info &fi, const size_t *rgb_row_strides, in
     return rs < tight ? 0 : hvc::mixed_rgb_span(layout, fi.width, fi.height, rs);
 }
 
+} // namespace
+
+int rgb_to_ycc_mixed_launch(hvc_ctx *c, hvc::MixedRgbPlan &plan, int layout, uint8_t *d_planes, const uint8_t *d_rgb, bool profile, bool pad,
+                            const hvc_jpeg_info *infos) {
+    if (!c->enc_libjpeg) return mixed_rgb_launch_plan(c, plan, layout, d_planes, const_cast<uint8_t *>(d_rgb), profile, true); // (d_rgb is read only)
+    if (plan.images.empty()) return HVC_OK;
+    int r = hvc::libjpeg_rgb_plan_lanes(plan, pad, infos);
+    if (r) return r;
+    size_t at[2];
+    if ((r = upload_parts(c, c->mixed_rgb_plan, {{plan.images.data(), plan.images.size() * sizeof(hvc::MixedRgbImageK)},
+                                                 {plan.map.data(), plan.map.size() * sizeof(unsigned)}}, at)))
+        return r;
+    hvc::RgbLibjpegMixedParams P;
+    std::memset(&P, 0, sizeof P);
+    P.rgb = d_rgb;
+    P.yuv = d_planes;
+    P.images = c->mixed_rgb_plan.d.as<const hvc::MixedRgbImageK>();
+    P.map = reinterpret_cast<const unsigned *>(c->mixed_rgb_plan.d.as<const unsigned char>() + at[1]);
+    P.n_units = (unsigned)plan.map.size();
+    P.planar = layout == HVC_RGB_PLANAR;
+    P.pad = pad;
+    HIPCHK(c, profiled_launch(c, profile, [&](hipEvent_t k0, hipEvent_t k1) { return hvc::launch_rgb_to_ycc_libjpeg_mixed(P, c->stream, k0, k1); }));
+    return HVC_OK;
+}
+
+namespace {
+
 // a chunk's colour stage on c->stream: the plane slot cleared, then k_rgb_to_ycc_mixed over the listed frames
 int encode_rgb_stage(hvc_ctx *c, const MixedEncodeInput &in, const hvc_jpeg_info *infos, const int *list, int count, const size_t *pix_rel,
                      const size_t *rgb_rel, const uint8_t *d_rgb, uint8_t *d_planes, size_t plane_bytes) {
@@ -122,7 +177,7 @@ int encode_rgb_stage(hvc_ctx *c, const MixedEncodeInput &in, const hvc_jpeg_info
     const int r = hvc::mixed_rgb_encode_plan_build(infos, pix_rel, rgb_rel, nullptr, in.layout, list, count, (uintptr_t)d_planes, (uintptr_t)d_rgb, plan);
     if (r) return r;
     HIPCHK(c, hipMemsetAsync(d_planes, 0, plane_bytes, c->stream)); // Plane.create is zero-filled: the kernel writes the frames' own samples only
-    return mixed_rgb_launch_plan(c, plan, in.layout, d_planes, const_cast<uint8_t *>(d_rgb), false, true); // (d_rgb is read only)
+    return rgb_to_ycc_mixed_launch(c, plan, in.layout, d_planes, d_rgb, false, true, infos); // (hvc_set_encode_libjpeg: with the replicated edge)
 }
 
 } // namespace
@@ -143,7 +198,7 @@ int rgb_to_yuv_mixed_impl(hvc_ctx *c, uint8_t *yuv, const size_t *yuv_offsets, c
         return r;
     if (plan.map.empty()) return HVC_OK; // (a set without a pixel needs no memory)
     if (!yuv || !rgb) return HVC_E_INVALID_ARG;
-    if (where == HVC_MEM_DEVICE) return mixed_rgb_launch_plan(c, plan, layout, yuv, const_cast<uint8_t *>(rgb), c->profiling, true);
+    if (where == HVC_MEM_DEVICE) return rgb_to_ycc_mixed_launch(c, plan, layout, yuv, rgb, c->profiling, false, infos);
     // host memory: the images and the plane records one after another in c->d_in / c->d_out; only each frame's own samples
     // come back (the padding of its planes stays the caller's)
     std::vector<size_t> yspan((size_t)n_frames, 0), rspan((size_t)n_frames, 0), d_yuv, d_rgb;
@@ -162,7 +217,7 @@ int rgb_to_yuv_mixed_impl(hvc_ctx *c, uint8_t *yuv, const size_t *yuv_offsets, c
     for (int f = 0; f < n_frames; f++)
         if (rspan[(size_t)f])
             HIPCHK(c, hipMemcpyAsync(c->d_in.as<uint8_t>() + d_rgb[(size_t)f], rgb + rgb_offsets[f], rspan[(size_t)f], hipMemcpyHostToDevice, c->stream));
-    if ((r = mixed_rgb_launch_plan(c, plan, layout, c->d_out.as<const uint8_t>(), c->d_in.as<uint8_t>(), false, true))) {
+    if ((r = rgb_to_ycc_mixed_launch(c, plan, layout, c->d_out.as<uint8_t>(), c->d_in.as<const uint8_t>(), false, false, infos))) {
         (void)hipStreamSynchronize(c->stream);
         return r;
     }
@@ -226,8 +281,10 @@ int encode_frames_mixed_rgb_impl(hvc_ctx *c, const uint8_t *rgb, const size_t *r
         if (rspan[(size_t)f])
             HIPCHK(c, hipMemcpyAsync(c->d_in.as<uint8_t>() + d_rgb[(size_t)f], rgb + rgb_offsets[f], rspan[(size_t)f], hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_aux.p, 0, ptot, c->stream)); // Plane.create is zero-filled
-    r = mixed_rgb_launch_plan(c, cplan, layout, c->d_aux.as<const uint8_t>(), const_cast<uint8_t *>(src), false, true);
-    if (!r) r = encode_mixed_launch_plan(c, bplan, c->d_aux.as<const uint8_t>(), host ? c->d_out.as<int16_t>() : coefs, !host && c->profiling);
+    r = rgb_to_ycc_mixed_launch(c, cplan, layout, c->d_aux.as<uint8_t>(), src, false, true, infos);
+    const MixedLibjpeg lje{infos, host ? d_coef.data() : coef_offsets, nullptr, n_frames};
+    if (!r) r = encode_mixed_launch_plan(c, bplan, c->d_aux.as<const uint8_t>(), host ? c->d_out.as<int16_t>() : coefs, !host && c->profiling,
+                                         c->enc_libjpeg ? &lje : nullptr);
     if (r) {
         (void)hipStreamSynchronize(c->stream);
         return r;
@@ -296,7 +353,7 @@ int encode_mixed_chunks(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg
             if (in.rgb)
                 encode_rgb_frame_copy(infos[f], in, f, frames[f], c->eh_in[k % NB].as<uint8_t>() + plan.rgb_rel[(size_t)f]);
             else
-                pad_frame(infos[f], frames[f], c->eh_in[k % NB].as<uint8_t>() + plan.pix_rel[(size_t)f]);
+                (c->enc_libjpeg ? hvc::pad_frame_replicate : pad_frame)(infos[f], frames[f], c->eh_in[k % NB].as<uint8_t>() + plan.pix_rel[(size_t)f]);
             pad_ns += MixedEncodeFront::ns_since(t0);
             padf.report(k, 1, HVC_OK);
         }
@@ -329,7 +386,10 @@ int encode_mixed_chunks(hvc_ctx *c, const uint8_t *const *frames, const hvc_jpeg
                 break;
             hvc::MixedEncodePlan bplan;
             if ((rc = hvc::mixed_encode_plan_build(infos, plan.coef_rel.data(), plan.pix_rel.data(), list, ch.count, bplan))) break;
-            if ((rc = encode_mixed_launch_plan(c, bplan, c->ed_in[slot].as<const uint8_t>(), c->ed_out[slot].as<int16_t>(), false))) break;
+            const MixedLibjpeg lje{infos, plan.coef_rel.data(), list, ch.count};
+            if ((rc = encode_mixed_launch_plan(c, bplan, c->ed_in[slot].as<const uint8_t>(), c->ed_out[slot].as<int16_t>(), false,
+                                               c->enc_libjpeg ? &lje : nullptr)))
+                break;
             if ((rc = fr.stage(k, slot))) break;
             // wait for this chunk's upload, then hand the pinned pixel slot to chunk k + NB
             he = wait_event(c->ev_up[slot]);

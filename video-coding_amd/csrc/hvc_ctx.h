@@ -51,6 +51,8 @@
 #include "hvc_hdec.h"
 #include "hvc_hardcaml.h"
 #include "hvc_libjpeg.h"
+#include "hvc_libjpeg_encode.h"
+#include "hvc_libjpeg_encode_plan.h"
 #include "hvc_huff.h"
 #include "hvc_kernels.h"
 #include "hvc_mixed_plan.h"
@@ -162,6 +164,8 @@ struct hvc_ctx {
     int mixed_arith = HVC_ARITH_MODEL; // hvc_set_mixed_arithmetic: the mixed decode calls' own setting (LIBJPEG: k_islow_mixed and
                                        // k_ycc_to_rgb_fancy_mixed, hvc_mixed_libjpeg.hip; they then do not look at `arith`)
     int enc_arith = HVC_ARITH_MODEL; // hvc_set_encode_arithmetic: the encoder's (HARDCAML: k_hardcaml_encode, hvc_hardcaml.hip)
+    int enc_libjpeg = 0; // hvc_set_encode_libjpeg: the encoder of "Encoding bit-exact to libjpeg" (k_fdct_islow and k_dummy_blocks,
+                         // hvc_libjpeg_encode.hip; replicated edges); enc_arith is then not consulted, HARDCAML beside it is refused
     int huff_tables = HVC_HUFF_DEFAULT; // hvc_set_huffman_tables: the files' Huffman tables (OPTIMISED: k_huff_hist / k_huff_build)
     int restart_interval = 0; // hvc_set_restart_interval: MCUs per restart interval of the files written, 0 = no DRI / RSTn
     Buf d_fix_count; // two counters, used alternately (see k_decode_wide); behind them (+ 8 bytes) the 64-bit
@@ -509,9 +513,18 @@ struct DecodeOpts {
 };
 struct EncodeOpts {
     int arith = HVC_ARITH_MODEL; // hvc_set_encode_arithmetic
+    bool libjpeg = false;        // hvc_set_encode_libjpeg: k_fdct_islow whatever `arith` (HARDCAML beside it: HVC_E_INVALID_ARG)
     bool profile = false;
-    explicit EncodeOpts(const hvc_ctx *c) : arith(c ? c->enc_arith : HVC_ARITH_MODEL), profile(c && c->profiling) {}
+    // (libjpeg only) the frames' sizes, where the caller knows them: comp[i].actual_width / actual_height and hscale of the
+    // components the records are laid out for -- blocks past ceil(actual / 8) are dummy blocks (k_dummy_blocks behind every
+    // launch, same stream).  nullptr: every block is real.
+    const hvc_jpeg_info *edges = nullptr;
+    explicit EncodeOpts(const hvc_ctx *c)
+        : arith(c ? c->enc_arith : HVC_ARITH_MODEL), libjpeg(c && c->enc_libjpeg), profile(c && c->profiling) {}
 };
+// the rule of hvc_set_encode_libjpeg for the entry points that have no libjpeg form (hvc_encode_frames_recon, _divergence): refused,
+// never the model's form in silence
+inline bool encode_libjpeg_refused(const hvc_ctx *c) { return c && c->enc_libjpeg; }
 
 // hvc_capi.hip: the block stage behind hvc_decode_frames / hvc_decode_frames_yuv444 / hvc_encode_frames
 int decode_frames_impl(hvc_ctx *c, const int16_t *coefs, size_t coef_fs, const uint16_t *qtabs, int n_qtabs,
@@ -667,7 +680,16 @@ int rgb_to_yuv_mixed_impl(hvc_ctx *c, uint8_t *yuv, const size_t *yuv_offsets, c
 int encode_frames_mixed_rgb_impl(hvc_ctx *c, const uint8_t *rgb, const size_t *rgb_offsets, const size_t *rgb_row_strides, int layout,
                                  const hvc_jpeg_info *infos, int n_frames, int16_t *coefs, const size_t *coef_offsets, int where);
 // hvc_capi_mixed_encode.hip: k_encode_mixed over a plan on device memory, enqueued on c->stream
-int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const uint8_t *d_pixels, int16_t *d_coefs, bool profile);
+// lje (hvc_set_encode_libjpeg; nullptr: the model's block stage): the frames the plan was built of -- k_fdct_islow_mixed in
+// place of k_encode_mixed and, from the infos' sizes, k_dummy_blocks_mixed behind it (hvc_libjpeg_encode.hip)
+struct MixedLibjpeg {
+    const hvc_jpeg_info *infos;
+    const size_t *coef_offsets; // as the plan was built with
+    const int *frames;          // the plan's list (nullptr: 0 .. n_list - 1)
+    int n_list;
+};
+int encode_mixed_launch_plan(hvc_ctx *c, const hvc::MixedEncodePlan &plan, const uint8_t *d_pixels, int16_t *d_coefs, bool profile,
+                             const MixedLibjpeg *lje = nullptr);
 // hvc_capi_mixed_coder.hip: the mixed GPU Huffman coder alone and behind the block stage (behind
 // hvc_huffman_encode_frames_mixed and hvc_jpeg_encode_batch_mixed_gpu in hvc_capi_files.hip)
 int huffman_encode_frames_mixed_impl(hvc_ctx *c, const hvc_jpeg_info *infos, const int16_t *coefs, const size_t *coef_offsets, int n_frames,
@@ -700,6 +722,14 @@ hipError_t ycc_to_rgb_device(const uint8_t *d_yuv, size_t yuv_fs, const hvc_comp
                              int ch, int n_frames, uint8_t *d_rgb, const RgbImage &im, hipStream_t s, int arith);
 hipError_t ycc_to_rgb_fancy_device(const uint8_t *d_yuv, size_t yuv_fs, const hvc_component *comps, int sampling, int width, int height,
                                    int cw, int ch, int n_frames, uint8_t *d_rgb, const RgbImage &im, hipStream_t s);
+// hvc_set_encode_libjpeg: k_rgb_to_ycc_libjpeg (hvc_libjpeg_encode.hip) -- libjpeg's chroma averaging; pad: every component written up to
+// ceil(actual / 8) * 8 both ways (the encode pipelines' replicated edge; the planes must be whole blocks), else the frame's own samples
+hipError_t rgb_to_ycc_libjpeg_device(const uint8_t *d_rgb, const RgbImage &im, int width, int height, int sampling, int n_frames, uint8_t *d_yuv,
+                                     size_t yuv_fs, const hvc_component *comps, bool pad, hipStream_t s);
+// the mixed colour pass RGB -> planes over a plan of mixed_rgb_encode_plan_build: k_rgb_to_ycc_mixed, or under hvc_set_encode_libjpeg
+// k_rgb_to_ycc_libjpeg_mixed on the plan's images with libjpeg_rgb_plan_lanes' lane grid (pad, infos: as there)
+int rgb_to_ycc_mixed_launch(hvc_ctx *c, hvc::MixedRgbPlan &plan, int layout, uint8_t *d_planes, const uint8_t *d_rgb, bool profile, bool pad,
+                            const hvc_jpeg_info *infos);
 hipError_t rgb_to_ycc_device(const uint8_t *d_rgb, const RgbImage &im, int width, int height, int sampling, int n_frames, uint8_t *d_yuv,
                              size_t yuv_fs, const hvc_component *comps, hipStream_t s);
 size_t rgb_yuv_span(const hvc_component *comps, int sampling, int w, int h, int cw, int ch); // bytes of a frame record the pass touches

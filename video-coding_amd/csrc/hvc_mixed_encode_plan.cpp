@@ -9,6 +9,7 @@ int mixed_encode_plan_build(const hvc_jpeg_info *infos, const size_t *coef_offse
                             int n_list, MixedEncodePlan &plan) {
     plan.planes.clear();
     plan.tables.clear();
+    plan.qt.clear();
     plan.map.clear();
     plan.blocks = 0;
     if (n_list < 0 || (n_list > 0 && (!infos || !coef_offsets || !pixel_offsets))) return HVC_E_INVALID_ARG;
@@ -24,14 +25,17 @@ int mixed_encode_plan_build(const hvc_jpeg_info *infos, const size_t *coef_offse
     const int r = mixed_plan_build(infos, coef_offsets, pixel_offsets, frames, n_list, d);
     if (r) return r;
     plan.tables.resize(d.tables.size());
+    plan.qt.resize(d.tables.size() * 64);
     for (size_t k = 0; k < d.tables.size(); k++)
         for (int i = 0; i < 64; i++) {
             const int t = d.tables[k].qt[i];
             if (t < 1 || t > 255) { // (Markers.Dqt element_precision = 8; a zero does not divide)
                 plan.tables.clear();
+                plan.qt.clear();
                 return HVC_E_RANGE;
             }
             plan.tables[k].qrcp[i] = encode_quant_reciprocal((unsigned)t);
+            plan.qt[k * 64 + (size_t)i] = t;
         }
     plan.planes.swap(d.planes);
     plan.map.swap(d.map);

@@ -26,6 +26,8 @@ struct MixedEncTableK { // 256 bytes
 struct MixedEncodePlan {
     std::vector<MixedPlaneK> planes;
     std::vector<MixedEncTableK> tables;
+    std::vector<int> qt;       // the entries themselves, 64 per table in zig-zag order (the libjpeg-exact block stage's multipliers
+                               // are made from them: libjpeg_mixed_tables_build, hvc_libjpeg_encode_plan.h)
     std::vector<unsigned> map; // unit -> plane
     unsigned long long blocks = 0;
 };

@@ -655,14 +655,19 @@ int hvc_rgb_to_yuv(hvc_ctx *c, const uint8_t *rgb, size_t rgb_row_stride, size_t
     DeviceGuard g(c->device);
     if (!g.ok) return fail_hip(c, hipErrorInvalidDevice);
     if (where == HVC_MEM_DEVICE) {
-        HIPCHK(c, rgb_to_ycc_device(rgb, im, width, height, sampling, n_frames, yuv, yuv_fs, comps, c->stream));
+        // (hvc_set_encode_libjpeg: libjpeg's averaging; the frame's own samples only, as without it)
+        HIPCHK(c, c->enc_libjpeg ? rgb_to_ycc_libjpeg_device(rgb, im, width, height, sampling, n_frames, yuv, yuv_fs, comps, false, c->stream)
+                                 : rgb_to_ycc_device(rgb, im, width, height, sampling, n_frames, yuv, yuv_fs, comps, c->stream));
         return HVC_OK;
     }
     const size_t in_bytes = rgb_bytes(im, n_frames), out_bytes = (size_t)(n_frames - 1) * yuv_fs + span;
     if ((r = grow(c, c->d_in, in_bytes))) return r;
     if ((r = grow(c, c->d_out, out_bytes))) return r;
     HIPCHK(c, hipMemcpyAsync(c->d_in.p, rgb, in_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, rgb_to_ycc_device(c->d_in.as<const uint8_t>(), im, width, height, sampling, n_frames, c->d_out.as<uint8_t>(), yuv_fs, comps, c->stream));
+    HIPCHK(c, c->enc_libjpeg ? rgb_to_ycc_libjpeg_device(c->d_in.as<const uint8_t>(), im, width, height, sampling, n_frames, c->d_out.as<uint8_t>(),
+                                                         yuv_fs, comps, false, c->stream)
+                             : rgb_to_ycc_device(c->d_in.as<const uint8_t>(), im, width, height, sampling, n_frames, c->d_out.as<uint8_t>(), yuv_fs,
+                                                 comps, c->stream));
     for (int f = 0; f < n_frames; f++) // (only the frame's own samples: padding stays the caller's)
         for (int k = 0; k < (grey ? 1 : 3); k++) {
             const size_t at = (size_t)f * yuv_fs + comps[k].plane_offset;

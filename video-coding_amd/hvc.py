@@ -29,6 +29,7 @@ SYMBOLS = [
     "hvc_encode_frames_submit", "hvc_wait", "hvc_slot_query", "hvc_slot_last_stats", "hvc_huffman_code_tables",
     "hvc_set_arithmetic", "hvc_get_arithmetic", "hvc_decode_frames_divergence",
     "hvc_set_encode_arithmetic", "hvc_get_encode_arithmetic", "hvc_encode_frames_divergence",
+    "hvc_set_encode_libjpeg", "hvc_get_encode_libjpeg",
     "hvc_dct_rom", "hvc_dct_matrix", "hvc_dct_blocks", "hvc_dct_fixed", "hvc_dct_reference", "hvc_dct_error_search",
     "hvc_set_huffman_tables", "hvc_get_huffman_tables", "hvc_huffman_spec_from_counts", "hvc_huffman_optimal_tables",
     "hvc_jpeg_header_tables", "hvc_jpeg_entropy_encode_tables", "hvc_huffman_encode_frames_optimised",
@@ -221,6 +222,8 @@ def lib():
         L.hvc_decode_frames_divergence.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
         L.hvc_set_encode_arithmetic.argtypes = [vp, i]
         L.hvc_get_encode_arithmetic.argtypes = [vp, C.POINTER(i)]
+        L.hvc_set_encode_libjpeg.argtypes = [vp, i]
+        L.hvc_get_encode_libjpeg.argtypes = [vp, C.POINTER(i)]
         L.hvc_encode_frames_divergence.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
         u64 = C.c_uint64
         L.hvc_dct_rom.argtypes = [i, vp]
@@ -1074,6 +1077,21 @@ class Context:
         v = C.c_int()
         _chk(lib().hvc_get_encode_arithmetic(self._h, C.byref(v)), "hvc_get_encode_arithmetic")
         return {b: a for a, b in HVC_ARITH.items()}.get(v.value, v.value)
+
+    def set_encode_libjpeg(self, on=True):
+        """hvc_set_encode_libjpeg: the encoder bit-exact to libjpeg-turbo (jfdctint.c's forward DCT, its rounded division,
+        replicated edges and dummy blocks; from RGB its biased chroma averaging) for fdct_quant, encode_frames,
+        encode_frames_submit, jpeg_encode, jpeg_encode_batch, rgb_to_yuv, jpeg_encode_rgb and the mixed encode calls, from planes
+        and from RGB, with either coder.  A setting of its own: set_encode_arithmetic is then not consulted, except that
+        "hardcaml" beside it is refused at the encode call.  encode_frames_recon and encode_divergence have no libjpeg form and
+        are refused under it."""
+        _chk(lib().hvc_set_encode_libjpeg(self._h, int(on) if isinstance(on, (bool, np.bool_)) else on), "hvc_set_encode_libjpeg")
+
+    @property
+    def encode_libjpeg(self):
+        v = C.c_int()
+        _chk(lib().hvc_get_encode_libjpeg(self._h, C.byref(v)), "hvc_get_encode_libjpeg")
+        return bool(v.value)
 
     def set_huffman_tables(self, which):
         """"default" (the Annex K tables, every byte as before) | "optimised" (each file's own Annex K.2 tables): the files of
