@@ -1244,8 +1244,59 @@ HVC_API int hvc_jpeg_encode_batch_mixed_rgb_gpu(hvc_ctx *ctx, const uint8_t *con
  *   untouched.  dst_cap: every good file's record must lie inside (HVC_E_INVALID_ARG).  An unknown filter or layout, and
  *   HVC_ARITH_HARDCAML / _LIBJPEG as the arithmetic (hvc_set_arithmetic): HVC_E_INVALID_ARG for the call, output untouched.
  *   Under hvc_set_mixed_arithmetic(ctx, HVC_ARITH_LIBJPEG) and scale_denom 1 the decode is libjpeg's and a record is Pillow's
- *   Image.open(f).convert("RGB").resize((W, H), filter) byte for byte; scale_denom > 1 is then HVC_E_INVALID_ARG, output untouched. */
+ *   Image.open(f).convert("RGB").resize((W, H), filter) byte for byte; scale_denom > 1 is then HVC_E_INVALID_ARG, output untouched.
+ *
+ * The option block (hvc_resize_opts, the _opts forms of the two calls): what takes the batch to the tensor a model reads.  Every
+ * piece has a definition of its own; a NULL or all-zero block is, byte for byte, the call without it.  In numpy:
+ * tools/resize_reference.py coefficients_box / resize_box / apply_lut.
+ *
+ * Box.  Per image box = (x0, y0, x1, y1), four IEEE SINGLE values in the coordinates of the image being resized (file pipeline:
+ *   the decoded image at 1 / scale_denom): Pillow's Image.resize(size, resample, box=box), fractional values allowed.  One axis
+ *   of n_in samples with the window [in0, in1) to n_out is computed as above except for these two lines:
+ *     scale  = (double)(float)(in1 - in0) / n_out      -- the span is subtracted in SINGLE precision, then widened
+ *     center = (double)in0 + (xx + 0.5) * scale
+ *   fs, support, ss, xmin (clamped at 0), xmax (clamped at n_in), the weights, their normalisation and the 22-bit taps are
+ *   unchanged.  Taps may reach outside the box but never outside the image: that is Pillow's behaviour, and why an integer box is
+ *   NOT crop().resize().  (With the span taken in double a few results in a thousand differ from Pillow's by one.)
+ *   An axis is skipped iff n_out == n_in && in0 == 0 && in1 == n_in.  When both axes run, the horizontal pass covers only the
+ *   source rows the vertical pass reads, [ymin[0], ymin[H - 1] + count[H - 1]), and the vertical records are shifted by ymin[0]
+ *   (Pillow does the same): the result is identical, the intermediate and the work shrink.
+ *   Refused with HVC_E_INVALID_ARG (hvc_rgb_resize_mixed_opts: for the call, output untouched; the file call: as that file's own
+ *   status, stopping nobody): a non-finite value; x0 < 0, y0 < 0, x1 > w or y1 > h; a span (float)(in1 - in0) <= 0 (Pillow lets a
+ *   zero span through; this library does not).
+ * Mirror.  Per image a flag (any non-zero byte).  The output is the unmirrored result with every row reversed left to right
+ *   (.transpose(FLIP_LEFT_RIGHT) after the resize).  A mirror makes the horizontal axis run even where it would be skipped, with
+ *   the identity table; the host plan emits that axis' records in reverse output order, and no kernel knows about it.
+ * Typed output.  out_elem = 0: 8-bit samples, as without the block.  out_elem = 2 or 4: bytes per output element, and `lut` is
+ *   HOST memory of 3 * 256 elements of out_elem bytes, indexed [channel][sample]: sample v of channel c is written as lut[c][v]
+ *   -- raw bits; the kernel (k_resize_v_mixed_lut, csrc/hvc_resize.hip) does not know what they mean, so the output is exact by
+ *   construction for any element type and any formula.  Every image then ends in the vertical pass (the identity table where
+ *   that axis is skipped).  Strides, offsets and dst_cap stay in BYTES: a row is out_w * 3 * out_elem bytes interleaved and
+ *   out_w * out_elem bytes planar; bytes between rows and records are never written.  out_elem outside {0, 2, 4}, or out_elem
+ *   != 0 with lut == NULL: HVC_E_INVALID_ARG for the call, output untouched.
+ *   hvc_normalize_lut(mean, std, elem, lut) is the library's own table maker (host only, no context; csrc/hvc_normalize_lut.cpp,
+ *   a plain C++ translation unit compiled with -ffp-contract=off): for c < 3, v < 256, in IEEE single with one rounding per
+ *   operation, lut[c][v] = ((float)v / 255.0f - mean[c]) / std[c], and for HVC_ELEM_F16 / HVC_ELEM_BF16 one round-to-nearest-
+ *   even conversion of that -- torchvision's ToTensor() followed by Normalize(mean, std) on the CPU, bit for bit.  mean, std: 3
+ *   values each; lut: 3 * 256 elements of 4 (HVC_ELEM_F32) or 2 bytes.  std[c] == 0, a non-finite mean or std, an unknown elem or
+ *   a NULL argument: HVC_E_INVALID_ARG.
+ * Bounds under a box: the table key grows to (n_in, n_out, filter, bits of in0, bits of in1, mirrored), so with a box of its own
+ *   every image has tables of its own, and a large direct hvc_rgb_resize_mixed_opts call can meet the 2^24 table words
+ *   (HVC_E_TOO_LARGE) where the call without boxes would not; the bound is not raised.  The file pipeline plans per chunk and
+ *   does not meet it.  The taps and accumulator bounds hold per position as before; out_w * rows * out_w < 2^32 counts the rows
+ *   of the horizontal pass's window.
+ * hvc_jpeg_decode_batch_mixed_resized_opts keeps the whole matrix of hvc_jpeg_decode_batch_mixed_resized (chunks, per-file
+ *   statuses, both readers, restart markers, any scale_denom, hvc_set_mixed_arithmetic(ctx, HVC_ARITH_LIBJPEG) at scale 1, under
+ *   which an 8-bit record is Image.open(f).convert("RGB").resize((W, H), filter, box=box) byte for byte).  The block stage and
+ *   the colour pass still produce the WHOLE image at decoded size; stages that decode and convert only the box are a later step. */
 typedef enum { HVC_RESIZE_BOX = 0, HVC_RESIZE_BILINEAR = 1, HVC_RESIZE_BICUBIC = 2 } hvc_resize_filter;
+typedef enum { HVC_ELEM_F32 = 1, HVC_ELEM_F16 = 2, HVC_ELEM_BF16 = 3 } hvc_elem; /* hvc_normalize_lut's element types */
+typedef struct hvc_resize_opts {
+    const float *boxes;      /* NULL, or 4 per image: x0, y0, x1, y1 */
+    const uint8_t *mirror;   /* NULL, or 1 per image */
+    int out_elem;            /* 0, 2, 4: bytes per output element */
+    const void *lut;         /* host, 3 * 256 elements of out_elem bytes, when out_elem != 0 */
+} hvc_resize_opts;
 #define HVC_RESIZE_MAX_TAPS 2048
 HVC_API int hvc_rgb_resize_mixed(hvc_ctx *ctx, const uint8_t *src, const size_t *src_offsets, const size_t *src_row_strides,
                                  const int *widths, const int *heights, int n_images, uint8_t *dst, const size_t *dst_offsets,
@@ -1256,6 +1307,17 @@ HVC_API int hvc_jpeg_decode_batch_mixed_resized(hvc_ctx *ctx, const uint8_t *con
                                                 int *status, const int *out_widths, const int *out_heights,
                                                 const size_t *dst_offsets, const size_t *dst_row_strides, uint8_t *dst,
                                                 size_t dst_cap, int layout, int filter, int where, hvc_batch_stats *stats);
+HVC_API int hvc_rgb_resize_mixed_opts(hvc_ctx *ctx, const uint8_t *src, const size_t *src_offsets, const size_t *src_row_strides,
+                                      const int *widths, const int *heights, int n_images, uint8_t *dst, const size_t *dst_offsets,
+                                      const size_t *dst_row_strides, const int *out_widths, const int *out_heights, int layout,
+                                      int filter, int where, const hvc_resize_opts *opts);
+HVC_API int hvc_jpeg_decode_batch_mixed_resized_opts(hvc_ctx *ctx, const uint8_t *const *jpegs, const size_t *sizes, int n_files,
+                                                     int threads, size_t chunk_bytes, int scale_denom, const hvc_jpeg_info *infos,
+                                                     int *status, const int *out_widths, const int *out_heights,
+                                                     const size_t *dst_offsets, const size_t *dst_row_strides, uint8_t *dst,
+                                                     size_t dst_cap, int layout, int filter, int where, hvc_batch_stats *stats,
+                                                     const hvc_resize_opts *opts);
+HVC_API int hvc_normalize_lut(const float *mean, const float *std, int elem, void *lut);
 
 /* K5 (no counterpart in the reference): what a benchmark or a pipeline produced, said in
  * 64 bits per record without bringing the records back.  For r < n_records

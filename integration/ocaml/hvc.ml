@@ -973,6 +973,43 @@ let jpeg_decode_batch_mixed_resized =
     @-> returning int)
 ;;
 
+(* the option block of the resizing calls: a box (4 singles: x0, y0, x1, y1) and a mirror flag per image, and a typed output
+   looked up in a host table of 3 * 256 elements of out_elem bytes (0: 8-bit samples).  A null pointer or an all-zero block is
+   the call without it.
+   typedef struct hvc_resize_opts { const float *boxes; const uint8_t *mirror; int out_elem; const void *lut; } *)
+module Resize_opts = struct
+  type t
+
+  let t : t structure typ = structure "hvc_resize_opts"
+  let boxes = field t "boxes" (ptr float)
+  let mirror = field t "mirror" (ptr uint8_t)
+  let out_elem = field t "out_elem" int
+  let lut = field t "lut" (ptr void)
+  let () = seal t
+end
+
+(* int hvc_rgb_resize_mixed_opts(... hvc_rgb_resize_mixed's arguments ..., opts) *)
+let rgb_resize_mixed_opts =
+  foreign
+    "hvc_rgb_resize_mixed_opts"
+    ~release_runtime_lock:true
+    (ctx @-> ptr char @-> ptr size_t @-> ptr size_t @-> ptr int @-> ptr int @-> int @-> ptr char @-> ptr size_t
+    @-> ptr size_t @-> ptr int @-> ptr int @-> int @-> int @-> int @-> ptr Resize_opts.t @-> returning int)
+;;
+
+(* int hvc_jpeg_decode_batch_mixed_resized_opts(... hvc_jpeg_decode_batch_mixed_resized's arguments ..., opts) *)
+let jpeg_decode_batch_mixed_resized_opts =
+  foreign
+    "hvc_jpeg_decode_batch_mixed_resized_opts"
+    ~release_runtime_lock:true
+    (ctx @-> ptr string @-> ptr size_t @-> int @-> int @-> size_t @-> int @-> ptr Jpeg_info.t @-> ptr int @-> ptr int
+    @-> ptr int @-> ptr size_t @-> ptr size_t @-> ptr char @-> size_t @-> int @-> int @-> int @-> ptr Batch_stats.t
+    @-> ptr Resize_opts.t @-> returning int)
+;;
+
+(* host only: int hvc_normalize_lut(mean, std, elem, lut): elem 1 float32, 2 float16, 3 bfloat16; lut: 3 * 256 elements *)
+let normalize_lut = foreign "hvc_normalize_lut" (ptr float @-> ptr float @-> int @-> ptr void @-> returning int)
+
 (* mixed batches, encoding: frames of different sizes, samplings and qualities in one call.
    int hvc_jpeg_encoder_mixed_layout(widths, heights, chromas, qualities, n_frames, align, infos, status, pixel_offsets,
                                      coef_offsets, pixel_total, coef_total)                                     host only *)

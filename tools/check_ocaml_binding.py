@@ -34,10 +34,12 @@ C_TO_ML = {
     "void*": {"ptr void"}, "void**": {"ptr (ptr void)"},
     "hvc_component*": {"ptr Component.t"}, "hvc_jpeg_info*": {"ptr Jpeg_info.t"},
     "hvc_batch_stats*": {"ptr Batch_stats.t"}, "hvc_slot_stats*": {"ptr Slot_stats.t"},
+    "hvc_resize_opts*": {"ptr Resize_opts.t"},
     "uint8_t**": {"ptr (ptr char)", "ptr string"},  # const uint8_t *const *: an array of byte strings
 }
 FIELD_TO_ML = {"int": "int", "size_t": "size_t", "uint16_t": "uint16_t", "uint8_t": "uint8_t", "double": "double", "uint64_t": "uint64_t",
-               "hvc_jpeg_component": "Jpeg_component.t", "hvc_component": "Component.t"}
+               "hvc_jpeg_component": "Jpeg_component.t", "hvc_component": "Component.t",
+               "float*": "(ptr float)", "uint8_t*": "(ptr uint8_t)", "void*": "(ptr void)"}  # pointer fields (hvc_resize_opts)
 
 
 def strip_comments(text, ml=False):
@@ -73,7 +75,8 @@ def header_structs(text):
             decl = decl.strip()
             if not decl:
                 continue
-            mm = re.match(r"([\w\s]+?)\s+([\w\s,\[\]]+)$", decl)
+            decl = re.sub(r"\s*\*\s*", "* ", decl)   # `const float *boxes`: the star belongs to the type
+            mm = re.match(r"([\w\s\*]+?)\s+([\w\s,\[\]]+)$", decl)
             ctype = norm_ctype(mm.group(1))
             for name in mm.group(2).split(","):
                 name = name.strip()
@@ -123,7 +126,7 @@ def binding_structs(text):
     out = {}
     for m in re.finditer(r'structure\s+"(\w+)"(.*?)let \(\) = seal t', text, flags=re.S):
         fields = []
-        for f in re.finditer(r'field t "(\w+)"\s+(\(array (\d+) ([\w.]+)\)|[\w.]+)', m.group(2)):
+        for f in re.finditer(r'field t "(\w+)"\s+(\(array (\d+) ([\w.]+)\)|\(ptr \w+\)|[\w.]+)', m.group(2)):
             fields.append((f.group(1), f.group(4) or f.group(2), int(f.group(3)) if f.group(3) else 0))
         out[m.group(1)] = fields
     return out

@@ -12,3 +12,4 @@ hvc.Context() raises when no gfx950 GPU is usable.
 from . import hvc  # noqa: F401
 from .hvc import YUV_FORMATS, Component, Context, HvcError, build, lib, yuv_frame_bytes  # noqa: F401
 from .hvc import dct_blocks, dct_matrix, dct_rom  # noqa: F401
+from .hvc import normalize_lut  # noqa: F401

@@ -23,6 +23,10 @@
     python -m video_coding_amd model decode frames OUT_DIR IN1.jpg ... -rgb -resize WxH [-filter box|bilinear|bicubic] [-scale N] [-reader gpu|host]
                                                       every image resized to W x H on the GPU, bit-exact to Pillow's
                                                       Image.resize (hvc_jpeg_decode_batch_mixed_resized): OUT_DIR/<name>.ppm
+    python -m video_coding_amd model decode frames OUT_DIR IN1.jpg ... -rgb -resize WxH [-box X0,Y0,X1,Y1] [-mirror]
+                                                      the window X0,Y0,X1,Y1 of every image (fractions allowed; coordinates of the
+                                                      image at 1 / -scale) resized to W x H as Pillow's resize(box=...), -mirror: then
+                                                      flipped left to right (hvc_jpeg_decode_batch_mixed_resized_opts)
     python -m video_coding_amd model decode frames OUT_DIR IN1.jpg ... [-rgb] [-resize WxH [-filter ...]] [-reader gpu|host] -arithmetic libjpeg
                                                       the same calls in libjpeg's arithmetic (hvc_set_mixed_arithmetic): every file as
                                                       `decode frame -arithmetic libjpeg` writes it; not with -scale above 1
@@ -75,6 +79,13 @@ from . import hvc, yuv
 def size_arg(s):
     w, h = s.lower().split("x")
     return int(w), int(h)
+
+
+def box_arg(s):
+    v = tuple(float(x) for x in s.split(","))
+    if len(v) != 4:
+        raise ValueError("X0,Y0,X1,Y1")
+    return v
 
 
 def read_ppm(path, size):
@@ -154,7 +165,9 @@ def model_decode_frames_rgb(a, datas):
         ctx.set_mixed_arithmetic(a.arithmetic)
         if a.resize is not None:
             # decoded (at 1 / -scale), converted and resized on the GPU in one hvc_jpeg_decode_batch_mixed_resized call
-            status, tensor = ctx.jpeg_decode_batch_mixed_resized(datas, size=a.resize, filter=a.filter, scale_denom=a.scale, threads=a.threads)
+            # (-box / -mirror: the same window and flip for every file, hvc_jpeg_decode_batch_mixed_resized_opts)
+            status, tensor = ctx.jpeg_decode_batch_mixed_resized(datas, size=a.resize, filter=a.filter, scale_denom=a.scale, threads=a.threads,
+                                                                 boxes=a.box, mirror=True if a.mirror else None)
             size = type("Size", (), dict(width=a.resize[0], height=a.resize[1]))
             results = [(status[f], size, tensor[f]) for f in range(len(datas))]
         elif a.scale == 1:
@@ -189,6 +202,8 @@ def model_decode_frames(a):
         raise SystemExit("-resize takes RGB images: give -rgb with it")
     if a.resize is not None and (a.resize[0] < 1 or a.resize[1] < 1):
         raise SystemExit("-resize WxH: sizes start at 1")
+    if (a.box is not None or a.mirror) and a.resize is None:
+        raise SystemExit("-box and -mirror belong to -resize WxH")
     if a.rgb:
         return model_decode_frames_rgb(a, datas)
     lay = hvc.jpeg_mixed_layout(datas) if a.scale == 1 else hvc.jpeg_mixed_scaled_layout(datas, a.scale)
@@ -575,6 +590,10 @@ def parser():
                    help="with -rgb: every image resized to W x H on the GPU, bit-exact to Pillow's Image.resize "
                         "(hvc_jpeg_decode_batch_mixed_resized; -scale: the cheap pre-shrink in front of it)")
     p.add_argument("-filter", choices=["box", "bilinear", "bicubic"], default="bilinear", help="the filter of -resize")
+    p.add_argument("-box", type=box_arg, default=None, metavar="X0,Y0,X1,Y1",
+                   help="with -resize: the window of every image that is resized, as Pillow's resize(box=...); fractions allowed, "
+                        "coordinates of the image at 1 / -scale (hvc_jpeg_decode_batch_mixed_resized_opts)")
+    p.add_argument("-mirror", action="store_true", help="with -resize: every resized image flipped left to right")
     p.add_argument("-arithmetic", default="model", choices=["model", "libjpeg"],
                    help="libjpeg: the set in libjpeg's arithmetic, every file as `decode frame -arithmetic libjpeg` writes it "
                         "(hvc_set_mixed_arithmetic HVC_ARITH_LIBJPEG); full size only, no -scale")

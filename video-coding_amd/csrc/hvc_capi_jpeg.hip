@@ -655,18 +655,29 @@ int hvc_jpeg_decode_batch_mixed_rgb(hvc_ctx *c, const uint8_t *const *jpegs, con
     return decode_batch_mixed_impl(c, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, rgb_offsets, rgb, rgb_cap, where, stats, form);
 } HVC_ABI_CATCH
 
-// ... ending in the two resampling passes: every image to the size the caller names for it (hvc_capi_resize.hip)
+// ... ending in the two resampling passes: every image to the size the caller names for it (hvc_capi_resize.hip); opts: a box
+// and a mirror flag per file, a typed output (NULL or all zero: none of them)
+int hvc_jpeg_decode_batch_mixed_resized_opts(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads,
+                                             size_t chunk_bytes, int scale_denom, const hvc_jpeg_info *infos, int *status, const int *out_widths,
+                                             const int *out_heights, const size_t *dst_offsets, const size_t *dst_row_strides, uint8_t *dst,
+                                             size_t dst_cap, int layout, int filter, int where, hvc_batch_stats *stats,
+                                             const hvc_resize_opts *opts) try {
+    if (!scaled_side(scale_denom) || !dst_offsets || !out_widths || !out_heights) return HVC_E_INVALID_ARG;
+    if (layout != HVC_RGB_INTERLEAVED && layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
+    if (filter != HVC_RESIZE_BOX && filter != HVC_RESIZE_BILINEAR && filter != HVC_RESIZE_BICUBIC) return HVC_E_INVALID_ARG;
+    if (resize_opts_check(opts)) return HVC_E_INVALID_ARG;
+    MixedForm form;
+    form.rgb_offsets = dst_offsets, form.rgb_row_strides = dst_row_strides, form.layout = layout, form.scale_denom = scale_denom;
+    form.out_widths = out_widths, form.out_heights = out_heights, form.filter = filter;
+    if (opts) form.boxes = opts->boxes, form.mirror = opts->mirror, form.out_elem = opts->out_elem, form.lut = opts->lut;
+    return decode_batch_mixed_impl(c, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, dst_offsets, dst, dst_cap, where, stats, form);
+} HVC_ABI_CATCH
 int hvc_jpeg_decode_batch_mixed_resized(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_files, int threads,
                                         size_t chunk_bytes, int scale_denom, const hvc_jpeg_info *infos, int *status, const int *out_widths,
                                         const int *out_heights, const size_t *dst_offsets, const size_t *dst_row_strides, uint8_t *dst,
                                         size_t dst_cap, int layout, int filter, int where, hvc_batch_stats *stats) try {
-    if (!scaled_side(scale_denom) || !dst_offsets || !out_widths || !out_heights) return HVC_E_INVALID_ARG;
-    if (layout != HVC_RGB_INTERLEAVED && layout != HVC_RGB_PLANAR) return HVC_E_INVALID_ARG;
-    if (filter != HVC_RESIZE_BOX && filter != HVC_RESIZE_BILINEAR && filter != HVC_RESIZE_BICUBIC) return HVC_E_INVALID_ARG;
-    MixedForm form;
-    form.rgb_offsets = dst_offsets, form.rgb_row_strides = dst_row_strides, form.layout = layout, form.scale_denom = scale_denom;
-    form.out_widths = out_widths, form.out_heights = out_heights, form.filter = filter;
-    return decode_batch_mixed_impl(c, jpegs, sizes, n_files, threads, chunk_bytes, infos, status, dst_offsets, dst, dst_cap, where, stats, form);
+    return hvc_jpeg_decode_batch_mixed_resized_opts(c, jpegs, sizes, n_files, threads, chunk_bytes, scale_denom, infos, status, out_widths,
+                                                    out_heights, dst_offsets, dst_row_strides, dst, dst_cap, layout, filter, where, stats, nullptr);
 } HVC_ABI_CATCH
 
 int hvc_jpeg_decode_batch_yuv444(hvc_ctx *c, const uint8_t *const *jpegs, const size_t *sizes, int n_frames,

@@ -535,11 +535,15 @@ int decode_batch_mixed_impl(hvc_ctx *c, const uint8_t *const *jpegs, const size_
             int rc = hvc::mixed_rgb_plan_build(oinfos, plan.plane_rel.data(), resized ? plan.rgb_rel.data() : dst_off,
                                                resized ? nullptr : form.rgb_row_strides, form.layout, ok.data(), n_ok, (uintptr_t)planes,
                                                (uintptr_t)rgb, true, cplan, N);
-            if (!rc && resized) rc = hvc::resize_plan_build(plan.rimg.data(), ok.data(), n_ok, form.layout, form.filter, (uintptr_t)rgb, (uintptr_t)dst, rplan);
+            if (!rc && resized) {
+                hvc::ResizePlanOpts po;
+                po.boxes = form.boxes, po.mirror = form.mirror, po.out_elem = form.out_elem;
+                rc = hvc::resize_plan_build_opts(plan.rimg.data(), ok.data(), n_ok, form.layout, form.filter, (uintptr_t)rgb, (uintptr_t)dst, po, rplan);
+            }
             if (!rc && resized && rplan.mid_bytes > c->d_mring[slot].cap) rc = HVC_E_INTERNAL;
             if (!rc) rc = mixed_launch(c, coefs, coef_rel.data(), oinfos, ok.data(), n_ok, planes, plan.plane_rel.data(), c->profiling, N);
             if (!rc) rc = mixed_rgb_launch_plan(c, cplan, form.layout, planes, rgb, false);
-            if (!rc && resized) rc = resize_launch_plan(c, rplan, rgb, dst, c->d_mring[slot].as<uint8_t>(), false);
+            if (!rc && resized) rc = resize_launch_plan(c, rplan, rgb, dst, c->d_mring[slot].as<uint8_t>(), false, form.lut);
             return rc;
         },
         [&](int k, int slot) {

@@ -668,11 +668,24 @@ size_t stage_offsets(const size_t *offsets, const std::vector<size_t> &spans, st
 namespace hvc {
 struct ResizePlan;
 }
-int resize_launch_plan(hvc_ctx *c, const hvc::ResizePlan &plan, const uint8_t *d_src, uint8_t *d_dst, uint8_t *d_mid, bool profile);
-// ... and the resampling step alone (behind hvc_rgb_resize_mixed in hvc_yuv.hip)
+// lut: a plan with out_elem 2 / 4 (typed output): the caller's table, HOST memory, 3 * 256 elements
+int resize_launch_plan(hvc_ctx *c, const hvc::ResizePlan &plan, const uint8_t *d_src, uint8_t *d_dst, uint8_t *d_mid, bool profile,
+                       const void *lut = nullptr);
+// what every call reads of an hvc_resize_opts before anything else (NULL: all zero): out_elem is 0, 2 or 4, and a table comes with 2 / 4
+inline int resize_opts_check(const hvc_resize_opts *o) {
+    if (!o) return HVC_OK;
+    if (o->out_elem != 0 && o->out_elem != 2 && o->out_elem != 4) return HVC_E_INVALID_ARG;
+    return o->out_elem && !o->lut ? (int)HVC_E_INVALID_ARG : (int)HVC_OK;
+}
+// ... and the resampling step alone (behind hvc_rgb_resize_mixed and hvc_rgb_resize_mixed_opts in hvc_yuv.hip)
 int rgb_resize_mixed_impl(hvc_ctx *c, const uint8_t *src, const size_t *src_offsets, const size_t *src_row_strides, const int *widths,
                           const int *heights, int n_images, uint8_t *dst, const size_t *dst_offsets, const size_t *dst_row_strides,
-                          const int *out_widths, const int *out_heights, int layout, int filter, int where);
+                          const int *out_widths, const int *out_heights, int layout, int filter, int where,
+                          const hvc_resize_opts *opts = nullptr);
+// hvc_normalize_lut.cpp (plain C++, -ffp-contract=off): the table behind hvc_normalize_lut (hvc_yuv.hip)
+namespace hvc {
+int normalize_lut(const float *mean, const float *std, int elem, void *lut);
+}
 // the colour pass alone / in front of the block stage (behind hvc_rgb_to_yuv_mixed in hvc_yuv.hip, hvc_encode_frames_mixed_rgb in
 // hvc_capi_files.hip)
 int rgb_to_yuv_mixed_impl(hvc_ctx *c, uint8_t *yuv, const size_t *yuv_offsets, const hvc_jpeg_info *infos, int n_frames, const uint8_t *rgb,

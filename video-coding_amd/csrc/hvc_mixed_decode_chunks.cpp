@@ -54,17 +54,19 @@ int mixed_decode_chunks_build(const hvc_jpeg_info *infos, int *status, const uin
             const int ow = form.resized() ? form.out_widths[f] : oi.width, oh = form.resized() ? form.out_heights[f] : oi.height;
             const size_t stride = form.rgb_row_strides ? form.rgb_row_strides[f] : 0;
             if (form.resized()) { // whether its image can be taken to its size is the file's own result too
-                const int rr = resize_image_status(oi.width, oi.height, ow, oh, form.filter);
-                if (rr || (stride && stride < mixed_rgb_row_bytes(form.layout, ow))) {
+                const int rr = resize_image_status_box(oi.width, oi.height, ow, oh, form.filter, form.boxes ? form.boxes + 4 * (size_t)f : nullptr,
+                                                       form.mirror ? form.mirror[f] : 0);
+                if (rr || (stride && stride < mixed_rgb_row_bytes(form.layout, ow) * form.elem())) {
                     status[f] = rr ? rr : (int)HVC_E_INVALID_ARG;
                     continue;
                 }
             }
-            const size_t tight = mixed_rgb_row_bytes(form.layout, ow);
+            const size_t tight = mixed_rgb_row_bytes(form.layout, ow) * (form.resized() ? form.elem() : 1);
             if (stride && stride < tight) return HVC_E_INVALID_ARG;
             plan.row_bytes[(size_t)f] = tight;
             plan.rows[(size_t)f] = mixed_rgb_rows(form.layout, oh);
             ob = mixed_rgb_span(form.layout, ow, oh, stride ? stride : tight);
+            if (ob && form.resized() && form.out_elem) ob = (plan.rows[(size_t)f] - 1) * (stride ? stride : tight) + tight; // (typed rows)
         } else {
             ob = oi.pixel_bytes;
             if (N == 8 && ob && (pixel_offsets[f] & 7)) return HVC_E_ALIGNMENT; // (scaled planes: any offset)

@@ -26,6 +26,13 @@ struct MixedForm {
     int scale_denom = 1;
     const int *out_widths = nullptr, *out_heights = nullptr;
     int filter = 0;
+    // (resized form) hvc_resize_opts: a box (4 singles) and a mirror flag per file, nullptr: none; out_elem 2 / 4: a file's record
+    // is its image in elements of that many bytes, looked up in `lut` (host memory, 3 * 256 elements) by the vertical pass
+    const float *boxes = nullptr;
+    const uint8_t *mirror = nullptr;
+    int out_elem = 0;
+    const void *lut = nullptr;
+    size_t elem() const { return out_elem ? (size_t)out_elem : 1; }
     bool rgb() const { return rgb_offsets != nullptr; }
     bool resized() const { return rgb() && out_widths != nullptr; }
 };
@@ -75,8 +82,10 @@ struct MixedDecodeChunks {
 // mixed_rgb_span of its image -- the decoded (scaled) size, or under the resized form the size the caller names -- with rows
 // rgb_row_strides[f] apart (nullptr, or an entry of 0: tight).
 // The file's own result, written to status[f] (it is left out and stops nobody else): under an RGB form a sampling that
-// rgb_sampling_of does not know (HVC_E_INVALID_ARG); under the resized form what resize_image_status answers for its image,
-// and a row stride below the tight output row (HVC_E_INVALID_ARG).
+// rgb_sampling_of does not know (HVC_E_INVALID_ARG); under the resized form what resize_image_status_box answers for its image,
+// its box (in the coordinates of the image at decoded size) and its mirror flag, and a row stride below the tight output row
+// (HVC_E_INVALID_ARG).  Under a typed output (out_elem 2 / 4) the tight row, the record and the copies back are those of
+// out_elem bytes per sample.
 // HVC_E_INVALID_ARG for the call: a null jpegs[f] or an n_comp outside 0 .. 4 of a file that takes part; under an RGB form a
 // negative image size or (not resized) a row stride below the tight row; a record of bytes that starts beyond pixel_cap or
 // ends beyond it (ending exactly at pixel_cap is fine); after the loop, a record of bytes anywhere and have_pixels false.

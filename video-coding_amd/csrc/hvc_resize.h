@@ -1,5 +1,5 @@
 // hvc_resize.h -- parameter block and launchers of the resampling passes over a mixed set (internal): k_resize_h_mixed and
-// k_resize_v_mixed, hvc_resize.hip.  The tables come from hvc_resize_plan.h, in device memory.
+// k_resize_v_mixed (and its typed form k_resize_v_mixed_lut), hvc_resize.hip.  The tables come from hvc_resize_plan.h, in device memory.
 #ifndef HVC_RESIZE_H
 #define HVC_RESIZE_H
 
@@ -22,6 +22,9 @@ struct ResizeParams {
 // one launch over all units of the pass; n_units == 0 (no image needs the pass) launches nothing
 hipError_t launch_resize_h_mixed(const ResizeParams &P, hipStream_t s);
 hipError_t launch_resize_v_mixed(const ResizeParams &P, hipStream_t s);
+// the vertical pass of a plan made with out_elem = elem (2 or 4): k_resize_v_mixed_lut<elem>; lut: device memory, 3 * 256
+// elements of elem bytes, [channel][sample], on elem bytes
+hipError_t launch_resize_v_mixed_lut(const ResizeParams &P, const void *lut, int elem, hipStream_t s);
 
 } // namespace hvc
 #endif

@@ -691,5 +691,17 @@ int hvc_rgb_resize_mixed(hvc_ctx *c, const uint8_t *src, const size_t *src_offse
     return rgb_resize_mixed_impl(c, src, src_offsets, src_row_strides, widths, heights, n_images, dst, dst_offsets, dst_row_strides, out_widths,
                                  out_heights, layout, filter, where);
 } HVC_ABI_CATCH
+// ... under a box and a mirror flag per image and a typed output (opts NULL or all zero: the call above)
+int hvc_rgb_resize_mixed_opts(hvc_ctx *c, const uint8_t *src, const size_t *src_offsets, const size_t *src_row_strides, const int *widths,
+                              const int *heights, int n_images, uint8_t *dst, const size_t *dst_offsets, const size_t *dst_row_strides,
+                              const int *out_widths, const int *out_heights, int layout, int filter, int where,
+                              const hvc_resize_opts *opts) try {
+    return rgb_resize_mixed_impl(c, src, src_offsets, src_row_strides, widths, heights, n_images, dst, dst_offsets, dst_row_strides, out_widths,
+                                 out_heights, layout, filter, where, opts);
+} HVC_ABI_CATCH
+// the table of a typed output that normalises per channel (host only: hvc_normalize_lut.cpp)
+int hvc_normalize_lut(const float *mean, const float *std, int elem, void *lut) try {
+    return hvc::normalize_lut(mean, std, elem, lut);
+} HVC_ABI_CATCH
 
 } // extern "C"

@@ -49,10 +49,13 @@ SYMBOLS = [
     "hvc_jpeg_encoder_mixed_rgb_layout", "hvc_rgb_to_yuv_mixed", "hvc_encode_frames_mixed_rgb", "hvc_jpeg_encode_batch_mixed_rgb",
     "hvc_jpeg_encode_batch_mixed_rgb_gpu",
     "hvc_rgb_resize_mixed", "hvc_jpeg_decode_batch_mixed_resized",
+    "hvc_rgb_resize_mixed_opts", "hvc_jpeg_decode_batch_mixed_resized_opts", "hvc_normalize_lut",
     "hvc_set_mixed_arithmetic", "hvc_get_mixed_arithmetic",
 ]
 HVC_RESIZE = {"box": 0, "bilinear": 1, "bicubic": 2}  # enum hvc_resize_filter
 HVC_RESIZE_MAX_TAPS = 2048
+HVC_ELEM = {"float32": 1, "float16": 2, "bfloat16": 3}  # enum hvc_elem: what hvc_normalize_lut makes a table of
+ELEM_BYTES = {"float32": 4, "float16": 2, "bfloat16": 2}
 HVC_RGB = {"interleaved": 0, "planar": 1}  # enum hvc_rgb_layout: [H, W, 3] / [3, H, W]
 HVC_YUV_400 = 400   # luma only, beside 420 / 422 / 444
 HVC_HUFF = {"default": 0, "optimised": 1}  # enum hvc_huff_tables
@@ -303,6 +306,9 @@ def lib():
         L.hvc_jpeg_decode_batch_mixed_resized.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, i, ip, C.POINTER(i), C.POINTER(i),
                                                           C.POINTER(i), C.POINTER(sz), C.POINTER(sz), vp, sz, i, i, i,
                                                           C.POINTER(BatchStats)]
+        L.hvc_rgb_resize_mixed_opts.argtypes = L.hvc_rgb_resize_mixed.argtypes + [C.POINTER(ResizeOpts)]
+        L.hvc_jpeg_decode_batch_mixed_resized_opts.argtypes = L.hvc_jpeg_decode_batch_mixed_resized.argtypes + [C.POINTER(ResizeOpts)]
+        L.hvc_normalize_lut.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), i, vp]
         L.hvc_jpeg_encoder_mixed_layout.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, sz, ip, C.POINTER(i),
                                                     C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
         L.hvc_encode_frames_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), i]
@@ -370,6 +376,77 @@ def _rgb_layout(layout):
 
 def _resize_filter(filter):
     return HVC_RESIZE[filter] if isinstance(filter, str) else int(filter)
+
+
+class ResizeOpts(C.Structure):
+    """hvc_resize_opts: a box and a mirror flag per image, a typed output through a table"""
+    _fields_ = [("boxes", C.POINTER(C.c_float)), ("mirror", C.POINTER(C.c_uint8)), ("out_elem", C.c_int), ("lut", C.c_void_p)]
+
+
+def elem_name(dtype):
+    """"float32" / "float16" / "bfloat16" of a name, a numpy dtype or a torch dtype"""
+    name = str(dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
+    name = {"half": "float16", "float": "float32"}.get(name, name)
+    if name not in HVC_ELEM:
+        raise ValueError("dtype %r: one of float32, float16, bfloat16" % (dtype,))
+    return name
+
+
+def normalize_lut(mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), dtype="float32"):
+    """hvc_normalize_lut: the [3, 256] table ((float)v / 255.0f - mean[c]) / std[c] in IEEE single, rounded once to dtype --
+    torchvision's ToTensor() + Normalize(mean, std) on the CPU, bit for bit.  numpy float32 / float16; bfloat16: the raw bits as
+    uint16 (numpy has no such type; torch.from_numpy(lut).view(torch.bfloat16) reads them)."""
+    name = elem_name(dtype)
+    out = np.zeros((3, 256), dtype={"float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}[name])
+    m, s = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    _chk(lib().hvc_normalize_lut(m, s, HVC_ELEM[name], out.ctypes.data), "hvc_normalize_lut")
+    return out
+
+
+def resize_opts(n, boxes=None, mirror=None, dtype=None, mean=None, std=None, lut=None):
+    """(ResizeOpts or None, what must stay alive during the call, bytes per output element, dtype name or None) of the keyword
+    arguments the resizing calls share.  boxes: n x (x0, y0, x1, y1), or one box for every image; mirror: n flags, or one;
+    dtype with mean / std (defaults 0 and 1): a table made by normalize_lut; lut: a [3, 256] array of 2- or 4-byte elements of
+    the caller's own (dtype then only names what the result is viewed as).  Nothing given: (None, [], 1, None)."""
+    if boxes is None and mirror is None and dtype is None and lut is None:
+        assert mean is None and std is None, "mean= / std= come with dtype="
+        return None, [], 1, None
+    o, keep, name = ResizeOpts(), [], None
+    if boxes is not None:
+        b = np.asarray(boxes, dtype=np.float32)
+        b = np.tile(b.reshape(1, 4), (max(n, 1), 1)) if b.ndim == 1 else np.ascontiguousarray(b.reshape(n, 4))
+        keep.append(b)
+        o.boxes = b.ctypes.data_as(C.POINTER(C.c_float))
+    if mirror is not None:
+        m = np.ascontiguousarray(np.broadcast_to(np.asarray(mirror).astype(bool).astype(np.uint8).reshape(-1), (max(n, 1),)))
+        keep.append(m)
+        o.mirror = m.ctypes.data_as(C.POINTER(C.c_uint8))
+    if lut is not None:
+        assert mean is None and std is None, "lut= is the table itself: no mean= / std="
+        t = np.ascontiguousarray(lut)
+        assert t.shape == (3, 256) and t.dtype.itemsize in (2, 4), "lut: [3, 256] of 2- or 4-byte elements"
+        name = elem_name(dtype) if dtype is not None else None
+        assert name is None or ELEM_BYTES[name] == t.dtype.itemsize
+    elif dtype is not None:
+        name = elem_name(dtype)
+        t = normalize_lut(mean if mean is not None else (0.0,) * 3, std if std is not None else (1.0,) * 3, name)
+    else:
+        assert mean is None and std is None, "mean= / std= come with dtype="
+        return o, keep, 1, None
+    keep.append(t)
+    o.out_elem, o.lut = t.dtype.itemsize, t.ctypes.data
+    return o, keep, t.dtype.itemsize, name
+
+
+def typed_view(buf, name, itemsize):
+    """a byte buffer (numpy / torch) seen as elements of dtype `name` (None: unsigned integers of itemsize bytes; bfloat16 in
+    numpy: uint16)"""
+    if hasattr(buf, "data_ptr"):
+        import torch
+        return buf.view({None: {1: torch.uint8, 2: torch.int16, 4: torch.int32}[itemsize], "float32": torch.float32,
+                         "float16": torch.float16, "bfloat16": torch.bfloat16}[name])
+    return buf.view({None: {1: np.uint8, 2: np.uint16, 4: np.uint32}[itemsize], "float32": np.float32, "float16": np.float16,
+                     "bfloat16": np.uint16}[name])
 
 
 def rgb_shape(layout, width, height):
@@ -1448,39 +1525,58 @@ class Context:
         return out
 
     def rgb_resize_mixed(self, src, src_offsets, widths, heights, dst, dst_offsets, out_widths, out_heights, filter="bilinear",
-                         layout="interleaved", src_row_strides=None, dst_row_strides=None):
+                         layout="interleaved", src_row_strides=None, dst_row_strides=None, boxes=None, mirror=None, dtype=None,
+                         mean=None, std=None, lut=None):
         """hvc_rgb_resize_mixed: image i (widths[i] x heights[i] at src[src_offsets[i]:], rows src_row_strides[i] apart, None:
         tight) to out_widths[i] x out_heights[i] at dst[dst_offsets[i]:] (rows dst_row_strides[i] apart), bit-exact to Pillow's
         Image.resize for filter "box" / "bilinear" / "bicubic" (tools/resize_reference.py), one launch per pass for the whole
-        set.  src / dst: numpy (host) or torch cuda tensors of bytes, both in the same memory space."""
+        set.  src / dst: numpy (host) or torch cuda tensors of bytes, both in the same memory space.
+        boxes / mirror / dtype with mean, std / lut (resize_opts): hvc_rgb_resize_mixed_opts -- Pillow's resize(box=...), a
+        left-right flip, and elements of dtype looked up in a table instead of bytes; dst offsets and strides stay in BYTES."""
         sa, w1 = _addr(src)
         da, w2 = _addr(dst)
         assert w1 == w2, "src and dst must live in the same memory space"
         n = len(widths)
         ints = lambda v: (C.c_int * max(n, 1))(*[int(x) for x in v])
+        opts, keep, _, _ = resize_opts(n, boxes, mirror, dtype, mean, std, lut)
+        if opts is not None:
+            _chk(lib().hvc_rgb_resize_mixed_opts(self._h, sa, _size_array(src_offsets, n), _size_array(src_row_strides, n),
+                                                 ints(widths), ints(heights), n, da, _size_array(dst_offsets, n),
+                                                 _size_array(dst_row_strides, n), ints(out_widths), ints(out_heights),
+                                                 _rgb_layout(layout), _resize_filter(filter), w1, C.byref(opts)),
+                 "hvc_rgb_resize_mixed_opts")
+            del keep
+            return
         _chk(lib().hvc_rgb_resize_mixed(self._h, sa, _size_array(src_offsets, n), _size_array(src_row_strides, n), ints(widths),
                                         ints(heights), n, da, _size_array(dst_offsets, n), _size_array(dst_row_strides, n),
                                         ints(out_widths), ints(out_heights), _rgb_layout(layout), _resize_filter(filter), w1),
              "hvc_rgb_resize_mixed")
 
     def jpeg_decode_batch_mixed_resized(self, jpegs, size=None, sizes=None, filter="bilinear", scale_denom=1, layout="interleaved",
-                                        device=False, threads=8, chunk_bytes=0, mixed_layout=None, out=None):
+                                        device=False, threads=8, chunk_bytes=0, mixed_layout=None, out=None, boxes=None, mirror=None,
+                                        dtype=None, mean=None, std=None, lut=None):
         """Files of any sizes, samplings and tables decoded (at 1 / scale_denom), converted to RGB and resized on the GPU in one
         call (hvc_jpeg_decode_batch_mixed_resized).  size=(W, H): every file to W x H; returns (status[], tensor) with tensor
         [n, H, W, 3] (interleaved) or [n, 3, H, W] (planar) -- numpy, or a torch cuda tensor with device=True; the frame of a
         file that failed keeps what `out` held (zeros when it is made here).  sizes=[(W, H), ...]: a size per file (aspect-
         preserving thumbnails); returns (status[], views), one [H, W, 3] / [3, H, W] view into ONE buffer per file, None for a
         file that failed.  mixed_layout: a MixedLayout made before (its headers are what is needed).  out: the buffer to write
-        (bytes; uniform: n * H * W * 3).  The call's hvc_batch_stats: self.last_batch_stats."""
+        (bytes; uniform: n * H * W * 3).  The call's hvc_batch_stats: self.last_batch_stats.
+        boxes / mirror / dtype with mean, std / lut (resize_opts): hvc_jpeg_decode_batch_mixed_resized_opts -- a box per file in
+        the coordinates of its image at 1 / scale_denom (RandomResizedCrop, a centre crop), a left-right flip per file, and a
+        tensor of dtype ("float32" / "float16" / "bfloat16", or a torch / numpy dtype) normalised per channel as torchvision's
+        ToTensor() + Normalize(mean, std), or looked up in a table of the caller's own (lut, [3, 256]); `out` stays a buffer of
+        BYTES (elements * itemsize), the tensor returned is a view of it in dtype."""
         assert (size is None) != (sizes is None), "one of size= and sizes="
         lay = mixed_layout if mixed_layout is not None else MixedLayout(jpegs)
         n = len(lay)
+        opts, keep, esz, ename = resize_opts(n, boxes, mirror, dtype, mean, std, lut)
         wh = [tuple(int(v) for v in size)] * n if size is not None else [tuple(int(v) for v in s) for s in sizes]
         assert len(wh) == n
         offs, total = (C.c_size_t * max(n, 1))(), 0
         for f, (w, h) in enumerate(wh):
             offs[f] = total
-            total += 3 * max(w, 0) * max(h, 0)
+            total += 3 * max(w, 0) * max(h, 0) * esz
         if out is None:
             if device:
                 import torch
@@ -1492,15 +1588,26 @@ class Context:
         st = BatchStats()
         status = (C.c_int * max(n, 1))(*lay.status)
         ow, oh = (C.c_int * max(n, 1))(*[w for w, _ in wh]), (C.c_int * max(n, 1))(*[h for _, h in wh])
-        _chk(lib().hvc_jpeg_decode_batch_mixed_resized(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, scale_denom, lay.infos,
-                                                       status, ow, oh, offs, None, oa, cap, _rgb_layout(layout),
-                                                       _resize_filter(filter), where, C.byref(st)),
-             "hvc_jpeg_decode_batch_mixed_resized")
+        if opts is None:
+            _chk(lib().hvc_jpeg_decode_batch_mixed_resized(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, scale_denom, lay.infos,
+                                                           status, ow, oh, offs, None, oa, cap, _rgb_layout(layout),
+                                                           _resize_filter(filter), where, C.byref(st)),
+                 "hvc_jpeg_decode_batch_mixed_resized")
+        else:
+            _chk(lib().hvc_jpeg_decode_batch_mixed_resized_opts(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, scale_denom,
+                                                                lay.infos, status, ow, oh, offs, None, oa, cap, _rgb_layout(layout),
+                                                                _resize_filter(filter), where, C.byref(st), C.byref(opts)),
+                 "hvc_jpeg_decode_batch_mixed_resized_opts")
+        del keep
         self.last_batch_stats = st
         status = [status[f] for f in range(n)]
         if size is not None:
             w, h = wh[0] if n else (int(size[0]), int(size[1]))
-            return status, out[:n * 3 * w * h].reshape((n,) + rgb_shape(layout, w, h))
+            flat = out[:n * 3 * w * h * esz]
+            return status, typed_view(flat, ename, esz).reshape((n,) + rgb_shape(layout, w, h))
+        if esz > 1:   # views in elements: offsets counted in elements of the typed buffer
+            typed = typed_view(out[:total], ename, esz)
+            return status, [rgb_view(typed, offs[f] // esz, 0, wh[f][0], wh[f][1], layout) if status[f] == 0 else None for f in range(n)]
         return status, [rgb_view(out, offs[f], 0, wh[f][0], wh[f][1], layout) if status[f] == 0 else None for f in range(n)]
 
     def decode_frames_yuv444(self, coefs, coef_frame_stride, qtabs, comps, n_frames, width, height, frames,
