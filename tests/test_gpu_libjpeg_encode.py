@@ -519,18 +519,41 @@ def test_mixed_rgb_batch_equals_the_single_file_call(ctx, mixed_rgb_set, coder, 
     assert [r[1] for r in res] == alone
 
 
+# The smallest set with, in ONE launch of k_rgb_to_ycc_libjpeg_mixed, a last workgroup with spare units, a unit with a single
+# active lane and an image with one lane per row (groups == 1): the single-block image, the 40 x 104 4:4:4 image (520 lanes: 9
+# units) and two images of 65 lanes, 8 x 65 with one lane per row.  The lane grid is libjpeg_rgb_lane_grid's without padding
+# (hvc_rgb_to_yuv_mixed): ceil(w / 8) x h here; under padding (hvc_encode_frames_mixed_rgb) a grid's height is a multiple of
+# 8, so a unit of one lane cannot occur there -- that call has the spare units (1 + 9 + 2 + 2) and the one-lane rows.
+EDGE_RGB = [("edge_rgb_%dx%d_%d" % c,) + c + ("noise", "q75") for c in ((8, 8, 444), (40, 104, 444), (8, 65, 422), (40, 13, 444))]
+
+
+def test_the_edge_rgb_set_is_what_it_claims():
+    lanes = [-(-w // 8) * h for _, w, h, s, _, _ in EDGE_RGB]
+    padded = [-(-w // 8) * (-(-h // 8) * 8) for _, w, h, s, _, _ in EDGE_RGB]
+    assert sum(-(-n // 64) for n in lanes) % 4 and sum(-(-n // 64) for n in padded) % 4
+    assert sum(n % 64 == 1 for n in lanes) == 2 and any(w <= 8 and h > 64 for _, w, h, _, _, _ in EDGE_RGB)
+
+
 @pytest.mark.parametrize("where", ["host", "device"])
 def test_encode_frames_mixed_rgb_and_rgb_to_yuv_mixed(hvc, ctx, where):
     """records straight from RGB images of mixed geometry = the records of hvc_jpeg_encode_rgb's files; the planes of
     hvc_rgb_to_yuv_mixed = hvc_rgb_to_yuv's, the padding of the plane records untouched"""
+    mixed_rgb_records_and_planes(hvc, ctx, where, [c for c in RGB_CASES if c[4] == "noise"], 0)
+
+
+def test_mixed_rgb_spare_units_a_single_active_lane_and_one_lane_per_row(hvc, ctx):
+    """EDGE_RGB in one launch, whole buffers over the fill with a guard region behind the last record"""
+    mixed_rgb_records_and_planes(hvc, ctx, "device", EDGE_RGB, 4096)
+
+
+def mixed_rgb_records_and_planes(hvc, ctx, where, cases, guard):
     import torch
-    cases = [c for c in RGB_CASES if c[4] == "noise"]
     specs = [(w, h, s, quality_of(tab)) for _, w, h, s, _, tab in cases]
     lay = hvc.hvc.jpeg_encoder_mixed_rgb_layout(specs)
     assert not any(lay.status)
     rgb = np.full(lay.rgb_total, FILL, dtype=np.uint8)
-    want = np.full(lay.coef_total, FILL16, dtype=np.int16)
-    planes_want = np.full(lay.pixel_total, FILL, dtype=np.uint8)
+    want = np.full(lay.coef_total + guard, FILL16, dtype=np.int16)
+    planes_want = np.full(lay.pixel_total + guard, FILL, dtype=np.uint8)
     for f, case in enumerate(cases):
         name, w, h, s, kind, tab = case
         im = lc.rgb_image(w, h, s, kind)
@@ -545,8 +568,8 @@ def test_encode_frames_mixed_rgb_and_rgb_to_yuv_mixed(hvc, ctx, where):
             for y in range(ah):
                 at = lay.pixel_offsets[f] + L.plane_offset + y * L.stride
                 planes_want[at:at + aw] = p[y, :aw]
-    got = np.full(lay.coef_total, FILL16, dtype=np.int16)
-    planes = np.full(lay.pixel_total, FILL, dtype=np.uint8)
+    got = np.full(lay.coef_total + guard, FILL16, dtype=np.int16)
+    planes = np.full(lay.pixel_total + guard, FILL, dtype=np.uint8)
     if where == "host":
         ctx.encode_frames_mixed_rgb(rgb, lay.rgb_offsets, lay.infos, got, lay.coef_offsets, rgb_row_strides=lay.rgb_row_strides)
         ctx.rgb_to_yuv_mixed(planes, lay.pixel_offsets, lay.infos, rgb, lay.rgb_offsets, rgb_row_strides=lay.rgb_row_strides)

@@ -17,7 +17,7 @@ import pytest
 import libjpeg_files as lf
 from conftest import GOLDEN, golden_bytes
 from test_gpu_libjpeg import extreme_record, guard_record
-from test_gpu_mixed_rgb import image_list, up, view
+from test_gpu_mixed_rgb import edge_image_list, image_list, up, view
 from test_host_entropy import unusual_sampling_file
 from test_mixed_rgb_plan import UNCONVERTIBLE, make_image
 
@@ -291,9 +291,9 @@ class Planes:
     """seeded random planes of the images, decoded-style (whole blocks, strides on 8) or raw (stride = width + 1), the records
     `align` apart, with the numpy definition's image of each (as the class of that name in tests/test_gpu_mixed_rgb.py)"""
 
-    def __init__(self, hvc, decoded, align):
+    def __init__(self, hvc, decoded, align, images=None):
         rng = np.random.Generator(np.random.PCG64(20261020 + decoded))
-        self.images = fancy_image_list()
+        self.images = images or fancy_image_list()
         self.infos, self.offsets, self.want = [], [], {}
         off, parts = 3 if align == 1 else 0, []
         for k, (w, h, s) in enumerate(self.images):
@@ -320,11 +320,11 @@ class Planes:
 _PLANES = {}
 
 
-def planes_of(decoded, align):
+def planes_of(decoded, align, edge=False):
     import video_coding_amd
-    if (decoded, align) not in _PLANES:
-        _PLANES[decoded, align] = Planes(video_coding_amd, decoded, align)
-    return _PLANES[decoded, align]
+    if (decoded, align, edge) not in _PLANES:
+        _PLANES[decoded, align, edge] = Planes(video_coding_amd, decoded, align, edge_image_list() if edge else None)
+    return _PLANES[decoded, align, edge]
 
 
 @pytest.mark.parametrize("reverse", [False, True], ids=["forward", "reversed"])
@@ -334,9 +334,21 @@ def planes_of(decoded, align):
 def test_colour_pass_with_fancy_upsampling(ctx, form, device, layout, reverse):
     """form bytes: raw planes at odd strides, records and images packed at align 1 (the byte paths); form vector: decoded planes,
     images at align 256 with rows on 8 (the 8-byte paths)"""
+    fancy_colour_pass(ctx, form, device, layout, reverse, False, 16)
+
+
+@pytest.mark.parametrize("layout", ["interleaved", "planar"])
+@pytest.mark.parametrize("form", ["bytes", "vector"])
+def test_fancy_colour_pass_spare_units_single_lane_one_lane_per_row(ctx, form, layout):
+    """edge_image_list() of tests/test_gpu_mixed_rgb.py in one launch: spare units in the last workgroup, a unit with a single
+    active lane, images with one lane per row; whole buffer over the fill with a guard region behind the last image"""
+    fancy_colour_pass(ctx, form, True, layout, False, True, 4096)
+
+
+def fancy_colour_pass(ctx, form, device, layout, reverse, edge, guard):
     import torch
     decoded, align, row_align = (False, 1, 1) if form == "bytes" else (True, 256, 8)
-    P = planes_of(decoded, align)
+    P = planes_of(decoded, align, edge)
     order = list(range(len(P.images)))[::-1] if reverse else list(range(len(P.images)))
     infos = [P.infos[k] for k in order]
     yoffs = [P.offsets[k] for k in order]
@@ -348,7 +360,7 @@ def test_colour_pass_with_fancy_upsampling(ctx, form, device, layout, reverse):
         roffs.append(off)
         strides.append(stride)
         off += stride * h * (3 if layout == "planar" else 1)
-    rgb = np.full(off + 16, FILL, dtype=np.uint8)
+    rgb = np.full(off + guard, FILL, dtype=np.uint8)
     expect = rgb.copy()
     for j, k in enumerate(order):
         w, h, s = P.images[k]

@@ -67,13 +67,23 @@ def image_list():
     return out
 
 
+def edge_image_list():
+    """The smallest set with, in ONE launch, a last workgroup with spare units, a unit with a single active lane and images
+    with one lane per row (groups == 1): the single-block image and the 40 x 104 4:4:4 image (9 units, 8 lanes in the last),
+    and two images of 65 lanes, one of them with one lane per row."""
+    out = [(8, 8, 444), (40, 104, 444), (8, 65, 400), (40, 13, 444)]
+    lanes = [-(-w // 8) * (-(-h // 2) if s == 420 else h) for w, h, s in out]
+    assert sum(-(-n // 64) for n in lanes) % 4 != 0 and any(n % 64 == 1 for n in lanes) and any(w <= 8 for w, _, _ in out)
+    return out
+
+
 class Planes:
     """seeded random planes of the images, decoded-style (whole blocks, strides on 8) or raw (stride = width + 1), the
     records `align` apart, with the numpy definition's image of each"""
 
-    def __init__(self, hvc, decoded, align):
+    def __init__(self, hvc, decoded, align, images=None):
         rng = np.random.Generator(np.random.PCG64(20261018 + decoded))
-        self.images = image_list()
+        self.images = images or image_list()
         self.infos, self.offsets, self.want = [], [], {}
         off, parts = 3 if align == 1 else 0, []
         for k, (w, h, s) in enumerate(self.images):
@@ -113,11 +123,11 @@ class Planes:
 _PLANES = {}
 
 
-def planes_of(decoded, align):
+def planes_of(decoded, align, edge=False):
     import video_coding_amd as hvc
-    if (decoded, align) not in _PLANES:
-        _PLANES[decoded, align] = Planes(hvc, decoded, align)
-    return _PLANES[decoded, align]
+    if (decoded, align, edge) not in _PLANES:
+        _PLANES[decoded, align, edge] = Planes(hvc, decoded, align, edge_image_list() if edge else None)
+    return _PLANES[decoded, align, edge]
 
 
 def flags_by_rule(info, s, yoff, roff, stride, layout):
@@ -137,9 +147,20 @@ def flags_by_rule(info, s, yoff, roff, stride, layout):
 def test_colour_pass_over_images_of_any_geometry(ctx, form, device, layout, reverse):
     """form bytes: raw planes at odd strides, records and images packed at align 1 (off 8 bytes: the byte paths); form vector:
     decoded planes, images at align 256 with rows on 8 (the 8-byte paths)"""
+    colour_pass(ctx, form, device, layout, reverse, False, FILL, 16)
+
+
+@pytest.mark.parametrize("layout", ["interleaved", "planar"])
+@pytest.mark.parametrize("form", ["bytes", "vector"])
+def test_colour_pass_spare_units_single_lane_one_lane_per_row(ctx, form, layout):
+    """edge_image_list() in one launch, whole buffer over a 0xA5 fill with a guard region behind the last image"""
+    colour_pass(ctx, form, True, layout, False, True, 0xA5, 4096)
+
+
+def colour_pass(ctx, form, device, layout, reverse, edge, FILL, guard):
     import torch
     decoded, align, row_align = (False, 1, 1) if form == "bytes" else (True, 256, 8)
-    P = planes_of(decoded, align)
+    P = planes_of(decoded, align, edge)
     order = list(range(len(P.images)))[::-1] if reverse else list(range(len(P.images)))
     infos = [P.infos[k] for k in order]
     yoffs = [P.offsets[k] for k in order]
@@ -151,7 +172,7 @@ def test_colour_pass_over_images_of_any_geometry(ctx, form, device, layout, reve
         roffs.append(off)
         strides.append(stride)
         off += image_bytes(layout, w, h, stride)
-    rgb = np.full(off + 16, FILL, dtype=np.uint8)
+    rgb = np.full(off + guard, FILL, dtype=np.uint8)
     give_strides = None if row_align == 1 else strides          # (NULL = tight rows)
     if device:
         d_y, d_r = torch.from_numpy(P.yuv).cuda(), torch.from_numpy(rgb).cuda()
@@ -174,7 +195,7 @@ def test_colour_pass_over_images_of_any_geometry(ctx, form, device, layout, reve
         assert np.array_equal(got, P.want[k, layout]), (k, P.images[k])                  # the definition
         assert np.array_equal(got, P.image_alone(ctx, k, layout)), (k, P.images[k])      # hvc_yuv_to_rgb on it alone
         seen.setdefault(s, set()).add(flags_by_rule(P.infos[k], s, yoffs[j], roffs[j], strides[j], layout))
-    for s in (420, 422, 444, 400):                              # each path ran for each sampling
+    for s in () if edge else (420, 422, 444, 400):              # each path ran for each sampling
         want = form == "vector"
         assert any(f[0] == want for f in seen[s]) and any(f[2] == want for f in seen[s]), (s, seen[s])
         if s != 400:

@@ -141,6 +141,50 @@ def test_a_set_of_images_each_to_its_own_size(ctx, filt, layout, rows, align, de
     assert bad.size == 0, (bad.size, bad[:8].tolist(), [k for k in range(n) if d_off[k] <= bad[0]][-1])
 
 
+# The smallest set that has, in ONE launch of each pass and in both layouts, a last workgroup with spare units, a unit with a
+# single active lane and one unit per row of lanes (groups == 1).  Every image runs one pass only, so the unit counts below
+# are exact: horizontal (H == h) 65 lanes of one sample per row and 64 lanes; vertical (W == w) rows of 1, 65 and 3 / 1 lanes.
+EDGE_SET = [(5, 65, 1, 65), (10, 8, 8, 8), (1, 5, 1, 2), (86, 7, 86, 3), (258, 3, 258, 2), (4, 3, 4, 2)]
+GUARD = 4096
+
+
+def edge_units(layout):
+    """(units of the horizontal pass, units of the vertical pass, lane counts of a horizontal image / of a vertical row)"""
+    planes = 3 if layout == "planar" else 1
+    hu = vu = 0
+    lanes = set()
+    for w, h, W, H in EDGE_SET:
+        assert (W != w) != (H != h)
+        if W != w:
+            hu += planes * -(-(W * h) // 64)
+            lanes.add(W * h)
+        else:
+            row = -(-(W if layout == "planar" else 3 * W) // 4)
+            vu += planes * H * -(-row // 64)
+            lanes.add(row)
+    return hu, vu, lanes
+
+
+@pytest.mark.parametrize("align", ["odd", "8"])
+@pytest.mark.parametrize("layout", ["interleaved", "planar"])
+def test_spare_units_a_single_active_lane_and_one_unit_per_row(ctx, layout, align):
+    hu, vu, lanes = edge_units(layout)
+    assert hu % 4 and vu % 4 and {1, 65} <= lanes, (hu, vu, lanes)
+    s_off, _, s_len = place([(w, h) for w, h, _, _ in EDGE_SET], layout, "tight", align)
+    d_off, _, d_len = place([(W, H) for _, _, W, H in EDGE_SET], layout, "tight", align)
+    src = np.full(s_len, 0x3C, dtype=np.uint8)
+    dst = np.full(d_len + GUARD, FILL, dtype=np.uint8)
+    expect = dst.copy()
+    for k, (w, h, W, H) in enumerate(EDGE_SET):
+        img = np.random.default_rng(4001 + k).integers(0, 256, size=(h, w, 3), dtype=np.uint8)
+        view(src, s_off[k], w if layout == "planar" else 3 * w, w, h, layout)[...] = as_layout(img, layout)
+        view(expect, d_off[k], W if layout == "planar" else 3 * W, W, H, layout)[...] = as_layout(rr.resize(img, W, H, "bilinear"), layout)
+    run(ctx, True, src, dst, s_off, [s[0] for s in EDGE_SET], [s[1] for s in EDGE_SET], d_off, [s[2] for s in EDGE_SET],
+        [s[3] for s in EDGE_SET], filter="bilinear", layout=layout)
+    bad = np.flatnonzero(dst != expect)
+    assert bad.size == 0, (bad.size, bad[:8].tolist())
+
+
 @pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
 def test_constant_images_and_the_checkerboard_under_bicubic(ctx, device):
     imgs = [np.zeros((9, 17, 3), np.uint8), np.full((9, 17, 3), 255, np.uint8), rc.checkerboard(53, 45), rc.checkerboard(53, 45),

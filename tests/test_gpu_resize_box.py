@@ -151,6 +151,9 @@ def test_the_typed_set_is_what_it_claims():
     assert typed_units("interleaved") % 4 != 0 and typed_units("planar") % 4 != 0     # the last workgroup has spare units
     assert {(3 * s[2]) % 4 for s in TYPED} == {0, 1, 2, 3} and {s[2] % 4 for s in TYPED} == {0, 1, 2, 3}
     assert -(-3 * 86 // 4) == 65 and -(-3 * 171 // 4) == 129
+    # in the same launch: a unit with a single active lane (1 x 1 in both layouts, the 65th lane of W = 86 interleaved) and rows
+    # of one unit (groups == 1)
+    assert any(s[2] == 1 for s in TYPED) and any(-(-3 * s[2] // 4) <= 64 for s in TYPED)
 
 
 _TSRC, _TWANT = {}, {}

@@ -16,11 +16,12 @@
 // row of MCUs' worth of dummies, so the pass is small.
 //
 // k_rgb_to_ycc_libjpeg: the colour pass in front of the block stage with libjpeg's chroma averaging; its lane, the edges it
-// writes and why are in hvc_rgb_libjpeg_dev.h.  The three kernels' mixed twins expand the same device code under
-// k_encode_mixed's / k_rgb_to_ycc_mixed's decomposition (a wavefront is 64 blocks of one plane, or 64 lanes of one image).
+// writes and why are in hvc_rgb_libjpeg_dev.h.  The three kernels' mixed twins expand the same device code under the
+// decomposition of hvc_mixed_dev.h.
 #include "hvc_libjpeg_encode.h"
 
 #include "hvc_fdct_islow_dev.h"
+#include "hvc_mixed_dev.h"
 #include "hvc_rgb_libjpeg_dev.h"
 
 namespace hvc {
@@ -112,10 +113,8 @@ __global__ __launch_bounds__(DUMMY_LANES) void k_dummy_blocks(DummyBlocksParams 
 }
 
 // ---------------------------------------------------------------------------
-// The mixed twins: k_encode_mixed's decomposition (hvc_mixed_encode.hip), the block of hvc_fdct_islow_dev.h
-#define HVC_LJE_MIXED_LANES (HVC_MIXED_UNIT * HVC_MIXED_GROUP)
-
-__global__ __launch_bounds__(HVC_LJE_MIXED_LANES) void k_fdct_islow_mixed(FdctIslowMixedParams P) {
+// The mixed twins: the decomposition of hvc_mixed_dev.h, the block of hvc_fdct_islow_dev.h
+__global__ __launch_bounds__(HVC_MIXED_LANES) void k_fdct_islow_mixed(FdctIslowMixedParams P) {
     unsigned wf, wt;
     xcd_work(P.xcd_map, P.xcd_magic, wf, wt); // gridDim.y == 1: a permutation of the groups (or the plain order)
     const unsigned group = wf * gridDim.x + wt;
@@ -160,16 +159,7 @@ __global__ __launch_bounds__(HVC_LJE_MIXED_LANES) void k_fdct_islow_mixed(FdctIs
 }
 
 hipError_t launch_fdct_islow_mixed(const FdctIslowMixedParams &P, hipStream_t s, hipEvent_t k0, hipEvent_t k1) {
-    if (P.n_units == 0) return hipSuccess;
-    hipError_t e;
-    const unsigned groups = (P.n_units + HVC_MIXED_GROUP - 1) / HVC_MIXED_GROUP;
-    FdctIslowMixedParams Q = P;
-    Q.xcd_map = xcd_map_for(groups, 1, Q.xcd_magic); // (0 beyond 65535 groups: the plain order)
-    if (k0 && (e = hipEventRecord(k0, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fdct_islow_mixed, dim3(groups), dim3(HVC_LJE_MIXED_LANES), 0, s, Q);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (k1 && (e = hipEventRecord(k1, s)) != hipSuccess) return e;
-    return hipSuccess;
+    return mixed_launch_xcd(k_fdct_islow_mixed, P, s, k0, k1);
 }
 
 __global__ __launch_bounds__(DUMMY_LANES) void k_dummy_blocks_mixed(int16_t *coefs, const DummyPairK *pairs, unsigned n) {
@@ -213,23 +203,17 @@ hipError_t launch_rgb_to_ycc_libjpeg(const RgbLibjpegParams &P, hipStream_t s) {
     return hipSuccess;
 }
 
-__global__ __launch_bounds__(HVC_LJE_MIXED_LANES) void k_rgb_to_ycc_libjpeg_mixed(RgbLibjpegMixedParams P) {
-    const unsigned unit = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * HVC_MIXED_GROUP + (threadIdx.x >> 6)));
-    if (unit >= P.n_units) return;
-    const MixedRgbImageK &K = P.images[P.map[unit]];
-    const unsigned lane = (unit - K.unit0) * 64u + (threadIdx.x & 63u);
-    if (lane >= K.lanes) return;
-    rgb_to_ycc_libjpeg_lane(K, lane, P.rgb, P.yuv, P.planar != 0, P.pad != 0);
+__global__ __launch_bounds__(HVC_MIXED_LANES) void k_rgb_to_ycc_libjpeg_mixed(RgbLibjpegMixedParams P) {
+    const MixedWave W = mixed_wave_plain();
+    if (W.unit >= P.n_units) return;
+    const MixedRgbImageK &K = P.images[P.map[W.unit]];
+    MixedImageLane L;
+    if (!mixed_image_lane(K, W.unit, W.lane, L)) return;
+    rgb_to_ycc_libjpeg_lane(K, L.t, P.rgb, P.yuv, P.planar != 0, P.pad != 0); // (it splits t into row and group itself)
 }
 
 hipError_t launch_rgb_to_ycc_libjpeg_mixed(const RgbLibjpegMixedParams &P, hipStream_t s, hipEvent_t k0, hipEvent_t k1) {
-    if (P.n_units == 0) return hipSuccess;
-    hipError_t e;
-    if (k0 && (e = hipEventRecord(k0, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rgb_to_ycc_libjpeg_mixed, dim3((P.n_units + HVC_MIXED_GROUP - 1) / HVC_MIXED_GROUP), dim3(HVC_LJE_MIXED_LANES), 0, s, P);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (k1 && (e = hipEventRecord(k1, s)) != hipSuccess) return e;
-    return hipSuccess;
+    return mixed_launch(k_rgb_to_ycc_libjpeg_mixed, P, s, k0, k1);
 }
 
 bool dummy_blocks_geometry(DummyBlocksParams &P, int n_comp, const int *bw, const int *bh, const int *real_w, const int *real_h,

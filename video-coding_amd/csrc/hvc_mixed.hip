@@ -1,11 +1,8 @@
 // hvc_mixed.hip -- the block stage over frames of DIFFERENT geometry and quantiser tables in one launch.
 //
 // k_decode_packed takes one DecodeParams: up to four planes and four tables in the kernarg segment, grid = tiles x frames.
-// Here the decomposition comes from device memory (hvc_mixed_plan.h): a work map names the plane of every work unit, a
-// plane descriptor says where its records and pixels are, a table entry holds its quantiser in the forms the arithmetic
-// wants.  A work unit is 64 consecutive blocks of ONE plane = one wavefront, so the map entry, the descriptor and the table
-// are wave-uniform: they come through scalar loads and live in SGPRs, exactly where k_decode_packed finds its kernarg
-// copies.  A workgroup is four consecutive units (256 lanes); its wavefronts share nothing (no LDS, no barrier).
+// Here the decomposition comes from device memory: hvc_mixed_dev.h says how (work map, plane descriptor, one wavefront per
+// work unit); a table entry (hvc_mixed_plan.h) holds the plane's quantiser in the forms the arithmetic wants.  No LDS.
 //
 // Per lane: K1's block -- eight 16-byte loads of the 128-byte record, the Chen-Wang row and column passes as the operation
 // list of hvc_idct_spec.h (HVC_IDCT_PASS, expanded with this file's own primitives: operation for operation the form
@@ -20,13 +17,11 @@
 #include <stdint.h>
 
 #include "hvc_idct_spec.h"
-#include "hvc_kernels.h" /* xcd_work, xcd_map_for */
 #include "hvc_mixed.h"
+#include "hvc_mixed_dev.h"
 
 namespace hvc {
 namespace {
-
-#define HVC_MIXED_LANES (HVC_MIXED_UNIT * HVC_MIXED_GROUP)
 
 // natural position -> zig-zag position (zigzag.ml:71-137)
 __device__ constexpr int MZF[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30,
@@ -165,64 +160,33 @@ __device__ __forceinline__ void m_store_row(uint8_t *p, unsigned lo, unsigned hi
         }                                                                                                  \
     } while (0)
 
-// unit -> its plane's descriptor; block b of the plane -> record and first pixel.  Everything but b is wave-uniform.
-struct MixedRef {
-    const int16_t *coef;
-    uint8_t *pix;
-    size_t stride;
-};
-__device__ __forceinline__ MixedRef mixed_block(const MixedParams &P, const MixedPlaneK &K, int b) {
-    const unsigned by = K.bw == 1 ? (unsigned)b : __umulhi((unsigned)b, K.magic);
-    const unsigned bx = (unsigned)b - by * (unsigned)K.bw;
-    MixedRef r;
-    r.stride = (size_t)K.stride;
-    r.coef = P.coefs + (size_t)K.coef_base + (size_t)b * 64;
-    r.pix = P.pixels + (size_t)K.pix_base + (size_t)by * 8 * r.stride + (size_t)bx * 8;
-    return r;
-}
-
 __global__ __launch_bounds__(HVC_MIXED_LANES, 4) void k_decode_mixed(MixedParams P) {
-    unsigned wf, wt;
-    xcd_work(P.xcd_map, P.xcd_magic, wf, wt); // gridDim.y == 1: a permutation of the groups (or the plain order)
-    const unsigned group = wf * gridDim.x + wt;
-    const int lane = threadIdx.x & (HVC_MIXED_UNIT - 1);
-    const unsigned unit = (unsigned)__builtin_amdgcn_readfirstlane((int)(group * HVC_MIXED_GROUP + (threadIdx.x >> 6)));
-    if (unit >= P.n_units) return; // (the whole wavefront: the last group's spare units)
-    const MixedPlaneK &K = P.planes[P.map[unit]];
+    const MixedWave W = mixed_wave_xcd(P.xcd_map, P.xcd_magic);
+    if (W.unit >= P.n_units) return;
+    const MixedPlaneK &K = P.planes[P.map[W.unit]];
     const MixedTableK &T = P.tables[K.table];
-    int b = (int)(unit - K.unit0) * HVC_MIXED_UNIT + lane;
-    const bool active = b < K.nblk;
-    b = active ? b : K.nblk - 1;
-    const MixedRef br = mixed_block(P, K, b);
-    bool flag = active;
+    const auto B = mixed_block<8>(K, W.unit, W.lane, P.coefs, P.pixels);
+    bool flag = B.active;
     if (!(P.all_wide | T.wide)) { // wave-uniform
-        const uint4 *src = reinterpret_cast<const uint4 *>(br.coef);
         unsigned w[32];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint4 t = src[j];
-            w[4 * j + 0] = t.x;
-            w[4 * j + 1] = t.y;
-            w[4 * j + 2] = t.z;
-            w[4 * j + 3] = t.w;
-        }
+        mixed_load_record(B.rec, w);
         MGuard g;
         unsigned out[8][2];
         const unsigned *__restrict__ qp = T.qpair;
         HVC_MX_DECODE_BLOCK(w, qp, out, g);
         const bool bad = g.failed(T.ethr_packed);
-        if (active && !bad) {
+        if (B.active && !bad) {
 #pragma unroll
-            for (int j = 0; j < 8; j++) m_store_row(br.pix + (size_t)j * br.stride, out[j][0], out[j][1]);
+            for (int j = 0; j < 8; j++) m_store_row(B.pix + (size_t)j * B.stride, out[j][0], out[j][1]);
         }
-        flag = active && bad;
+        flag = B.active && bad;
     }
     const unsigned long long m = __ballot(flag);
     if (m) {
         unsigned base = 0;
-        if (lane == 0) base = atomicAdd(P.fix_count, (unsigned)__popcll(m));
+        if (W.lane == 0) base = atomicAdd(P.fix_count, (unsigned)__popcll(m));
         base = __shfl(base, 0);
-        if (flag) P.fix_list[base + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = unit * HVC_MIXED_UNIT + (unsigned)lane;
+        if (flag) P.fix_list[base + (unsigned)__popcll(m & ((1ull << W.lane) - 1ull))] = W.unit * HVC_MIXED_UNIT + (unsigned)W.lane;
     }
 }
 
@@ -325,17 +289,9 @@ __global__ __launch_bounds__(HVC_MIXED_WIDE_LANES) void k_decode_mixed_wide(Mixe
         if (unit < K.unit0) continue;
         const unsigned long long b = (unsigned long long)(unit - K.unit0) * HVC_MIXED_UNIT + lane;
         if (b >= (unsigned long long)K.nblk) continue;
-        const MixedRef br = mixed_block(P, K, (int)b);
-        const uint4 *src = reinterpret_cast<const uint4 *>(br.coef);
+        const auto br = mixed_block_at<8>(K, (int)b, P.coefs, P.pixels);
         unsigned w[32], out[8][2];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint4 t = src[j];
-            w[4 * j + 0] = t.x;
-            w[4 * j + 1] = t.y;
-            w[4 * j + 2] = t.z;
-            w[4 * j + 3] = t.w;
-        }
+        mixed_load_record(br.rec, w);
         m_block_wide(w, P.tables[K.table].qt, out);
 #pragma unroll
         for (int j = 0; j < 8; j++) m_store_row(br.pix + (size_t)j * br.stride, out[j][0], out[j][1]);
@@ -346,15 +302,9 @@ __global__ __launch_bounds__(HVC_MIXED_WIDE_LANES) void k_decode_mixed_wide(Mixe
 
 hipError_t launch_decode_mixed(const MixedParams &P, hipStream_t s, hipEvent_t k0, hipEvent_t k1) {
     if (P.n_units == 0) return hipSuccess;
-    hipError_t e;
-    const unsigned groups = (P.n_units + HVC_MIXED_GROUP - 1) / HVC_MIXED_GROUP;
-    MixedParams Q = P;
-    Q.xcd_map = xcd_map_for(groups, 1, Q.xcd_magic); // (0 beyond 65535 groups: the plain order)
-    if (k0 && (e = hipEventRecord(k0, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_decode_mixed, dim3(groups), dim3(HVC_MIXED_LANES), 0, s, Q);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (k1 && (e = hipEventRecord(k1, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_decode_mixed_wide, dim3(HVC_MIXED_WIDE_WGS), dim3(HVC_MIXED_WIDE_LANES), 0, s, Q);
+    const hipError_t e = mixed_launch_xcd(k_decode_mixed, P, s, k0, k1);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_decode_mixed_wide, dim3(HVC_MIXED_WIDE_WGS), dim3(HVC_MIXED_WIDE_LANES), 0, s, P);
     return hipGetLastError();
 }
 

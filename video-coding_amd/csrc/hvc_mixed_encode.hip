@@ -1,22 +1,16 @@
 // hvc_mixed_encode.hip -- the FORWARD block stage over frames of DIFFERENT geometry and quantiser tables in one launch.
 //
 // k_encode (hvc_kernels.hip) takes one EncodeParams: up to four planes and four tables in the kernarg segment, grid = tiles x
-// frames.  Here the decomposition comes from device memory, and it is k_decode_mixed's (hvc_mixed.hip, hvc_mixed_plan.h): a
-// work map names the plane of every work unit, a plane descriptor says where its pixels and records are, a table entry
-// (hvc_mixed_encode_plan.h) holds the 64 reciprocals of its quantiser.  A work unit is 64 consecutive blocks of ONE plane =
-// one wavefront, so the map entry, the descriptor and the table are wave-uniform: they come through scalar loads and live
-// in SGPRs, where k_encode finds its kernarg copies.  A workgroup is HVC_MIXED_GROUP consecutive units (256 lanes); a unit
-// beyond n_units returns as a whole wavefront.
+// frames.  Here the decomposition comes from device memory: hvc_mixed_dev.h says how (the block stage's, and the forward
+// tail); a table entry (hvc_mixed_encode_plan.h) holds the 64 reciprocals of the plane's quantiser.
 //
 // Per lane: k_encode's block in its shipped form (its HVC_ENCODE_MULHI = 1, HVC_ENCODE_QMAGIC = 1, non-temporal loads and
 // stores; none of its experiment switches exists here) -- eight 8-byte row loads at the descriptor's stride, the column
 // pass from the bytes with the level shift riding in fdct_tail<true>, the row pass, the quantiser as one v_fma_f32 per
 // coefficient against fl((1 + 2^-16) / (4 t)) with v_perm_b32 packing the pairs (tests/test_quant_division.py proves the
-// quotient; the host makes the reciprocals with the expression k_encode's are made with, encode_quant_reciprocal).  The
-// wavefront then transposes its 8 KiB through its own XOR-swizzled LDS region (wave-private: no barrier) and stores the
-// unit's coefficient run -- the 64 blocks of a unit are contiguous in the plane's record -- as 1 KiB pieces.  Blocks at or
-// beyond nblk are not stored; an inactive lane computes the plane's last block and stores nothing.
-// LDS per workgroup: 32 KiB, as k_encode with HVC_TILE 256.  No scratch (profiles/mixed_encode_rocprofv3.txt).
+// quotient; the host makes the reciprocals with the expression k_encode's are made with, encode_quant_reciprocal), then
+// the forward tail.  LDS per workgroup: 32 KiB, as k_encode with HVC_TILE 256.  No scratch
+// (profiles/mixed_encode_rocprofv3.txt).
 //
 // (The Huffman coder on the GPU for mixed sets is hvc_huff_mixed.hip, behind hvc_jpeg_encode_batch_mixed_gpu; RGB input for
 // mixed sets is k_rgb_to_ycc_mixed, hvc_mixed_rgb.hip, in front of this block stage, behind hvc_jpeg_encode_batch_mixed_rgb.)
@@ -26,13 +20,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "hvc_kernels.h" /* xcd_work, xcd_map_for */
+#include "hvc_mixed_dev.h"
 #include "hvc_mixed_encode.h"
 
 namespace hvc {
 namespace {
-
-#define HVC_MIXED_ENC_LANES (HVC_MIXED_UNIT * HVC_MIXED_GROUP)
 
 // zig-zag position -> natural position (zigzag.ml:5-69)
 __device__ constexpr int EZI[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -123,7 +115,7 @@ __device__ __forceinline__ void fdct_col_bytes(const unsigned (&px)[8][2], int (
                     v[56 + C]);
 }
 
-__global__ __launch_bounds__(HVC_MIXED_ENC_LANES) void k_encode_mixed(MixedEncodeParams P) {
+__global__ __launch_bounds__(HVC_MIXED_LANES) void k_encode_mixed(MixedEncodeParams P) {
     unsigned wf, wt;
     xcd_work(P.xcd_map, P.xcd_magic, wf, wt); // gridDim.y == 1: a permutation of the groups (or the plain order)
     const unsigned group = wf * gridDim.x + wt;
@@ -198,16 +190,7 @@ __global__ __launch_bounds__(HVC_MIXED_ENC_LANES) void k_encode_mixed(MixedEncod
 } // namespace
 
 hipError_t launch_encode_mixed(const MixedEncodeParams &P, hipStream_t s, hipEvent_t k0, hipEvent_t k1) {
-    if (P.n_units == 0) return hipSuccess;
-    hipError_t e;
-    const unsigned groups = (P.n_units + HVC_MIXED_GROUP - 1) / HVC_MIXED_GROUP;
-    MixedEncodeParams Q = P;
-    Q.xcd_map = xcd_map_for(groups, 1, Q.xcd_magic); // (0 beyond 65535 groups: the plain order)
-    if (k0 && (e = hipEventRecord(k0, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_encode_mixed, dim3(groups), dim3(HVC_MIXED_ENC_LANES), 0, s, Q);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (k1 && (e = hipEventRecord(k1, s)) != hipSuccess) return e;
-    return hipSuccess;
+    return mixed_launch_xcd(k_encode_mixed, P, s, k0, k1);
 }
 
 } // namespace hvc

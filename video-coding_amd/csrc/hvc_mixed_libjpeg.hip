@@ -2,9 +2,7 @@
 // ("Bit-exact to libjpeg") over frames and images of DIFFERENT geometry, sampling and quantiser tables in one launch.
 //
 // k_islow_mixed: k_islow's block (hvc_islow_dev.h: guard sum, int path, int64 path in the same lane -- the same expansion of
-// hvc_islow_spec.h, no second spelling) under k_decode_mixed's decomposition (hvc_mixed.hip, hvc_mixed_plan.h): a work unit is
-// 64 consecutive blocks of ONE plane = one wavefront, the map entry and the MixedPlaneK descriptor are wave-uniform and come
-// through scalar loads, four units make a workgroup whose wavefronts share nothing.  No LDS, no barrier, no scratch.
+// hvc_islow_spec.h, no second spelling) under the block stage's decomposition of hvc_mixed_dev.h.  No LDS, no scratch.
 //   table       32 dwords q[2i] | q[2i+1] << 16 per distinct table of the plan (mixed_islow_pairs_build: IslowParams::qq's form,
 //               all 16 bits of every entry), beside the plan image; read through a wave-uniform const pointer, so that the
 //               words arrive in SGPRs, where k_islow finds its kernarg copy
@@ -13,24 +11,23 @@
 //   DC          the record's coefficient 0: the mixed pipelines keep absolute DCs in the records
 //
 // k_ycc_to_rgb_fancy_mixed: k_ycc_to_rgb_fancy's lane (HVC_YCC_LANE_TO_RGB_FANCY, hvc_fancy_dev.h) in k_ycc_to_rgb_mixed's frame
-// (hvc_mixed_rgb.hip): unit map, MixedRgbImageK through scalar loads, an RgbOp filled per image, a wave-uniform switch on the
-// sampling.  The descriptor's cw x ch is the chroma window the triangle filter clamps to.
+// (hvc_mixed_rgb.hip; the image passes of hvc_mixed_dev.h).  The descriptor's cw x ch is the chroma window the triangle
+// filter clamps to.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/hvc_jpeg.h"
 #include "hvc_fancy_dev.h"
 #include "hvc_islow_dev.h"
-#include "hvc_kernels.h" /* xcd_work, xcd_map_for */
+#include "hvc_mixed_dev.h"
 #include "hvc_mixed_libjpeg.h"
 
 namespace hvc {
 namespace {
 
-#define HVC_MIXED_LJ_LANES (HVC_MIXED_UNIT * HVC_MIXED_GROUP)
 static_assert(HVC_ISLOW_PAIR_WORDS == 32, "a lane's table: one pair word per record dword");
 
-__global__ __launch_bounds__(HVC_MIXED_LJ_LANES) void k_islow_mixed(MixedIslowParams P) {
+__global__ __launch_bounds__(HVC_MIXED_LANES) void k_islow_mixed(MixedIslowParams P) {
     unsigned wf, wt;
     xcd_work(P.xcd_map, P.xcd_magic, wf, wt); // gridDim.y == 1: a permutation of the groups (or the plain order)
     const unsigned group = wf * gridDim.x + wt;
@@ -77,63 +74,32 @@ __global__ __launch_bounds__(HVC_MIXED_LJ_LANES) void k_islow_mixed(MixedIslowPa
     }
 }
 
-template <int S, int PLANAR>
-__device__ __forceinline__ void mixed_fancy_lane(const RgbOp &P, unsigned lr, unsigned g) {
-    const size_t f = 0; // one image per RgbOp
-    HVC_YCC_LANE_TO_RGB_FANCY(P, f, lr, g);
-}
+struct FancyLane {
+    template <int S, int PLANAR>
+    static __device__ __forceinline__ void lane(const RgbOp &P, unsigned lr, unsigned g) {
+        const size_t f = 0; // one image per RgbOp
+        HVC_YCC_LANE_TO_RGB_FANCY(P, f, lr, g);
+    }
+};
 
 template <int PLANAR>
-__global__ __launch_bounds__(HVC_MIXED_LJ_LANES) void k_ycc_to_rgb_fancy_mixed(MixedRgbParams P) {
-    const unsigned lane = threadIdx.x & (HVC_MIXED_UNIT - 1);
-    const unsigned unit = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * HVC_MIXED_GROUP + (threadIdx.x >> 6)));
-    if (unit >= P.n_units) return; // (the whole wavefront: the last group's spare units)
-    const MixedRgbImageK K = P.images[P.map[unit]]; // wave-uniform: read once, before any store
-    const unsigned t = (unit - K.unit0) * HVC_MIXED_UNIT + lane;
-    if (t >= K.lanes) return;
-    const unsigned lr = K.groups == 1 ? t : __umulhi(t, K.magic), g = t - lr * K.groups;
-    RgbOp R; // the image as k_ycc_to_rgb_fancy's parameter block: one frame, its own bases
-    R.y = const_cast<uint8_t *>(P.yuv) + K.y_base;
-    R.cb = const_cast<uint8_t *>(P.yuv) + K.cb_base;
-    R.cr = const_cast<uint8_t *>(P.yuv) + K.cr_base;
-    R.rgb = P.rgb + K.rgb_base;
-    R.y_stride = K.y_stride, R.cb_stride = K.cb_stride, R.cr_stride = K.cr_stride, R.yuv_fs = 0;
-    R.row_stride = K.row_stride, R.plane_stride = K.plane_stride, R.frame_stride = 0;
-    R.w = K.w, R.h = K.h, R.cw = K.cw, R.ch = K.ch;
-    R.vec_y = K.vec_y, R.vec_c = K.vec_c, R.vec_rgb = K.vec_rgb;
-    switch (K.sampling) { // wave-uniform
-    case HVC_YUV_420: mixed_fancy_lane<420, PLANAR>(R, lr, g); break;
-    case HVC_YUV_422: mixed_fancy_lane<422, PLANAR>(R, lr, g); break;
-    case HVC_YUV_444: mixed_fancy_lane<444, PLANAR>(R, lr, g); break;
-    default: mixed_fancy_lane<400, PLANAR>(R, lr, g); break;
-    }
+__global__ __launch_bounds__(HVC_MIXED_LANES) void k_ycc_to_rgb_fancy_mixed(MixedRgbParams P) {
+    const MixedWave W = mixed_wave_plain();
+    if (W.unit >= P.n_units) return;
+    const MixedRgbImageK K = P.images[P.map[W.unit]]; // wave-uniform: read once, before any store
+    MixedImageLane L;
+    if (!mixed_image_lane(K, W.unit, W.lane, L)) return;
+    mixed_rgb_dispatch<FancyLane, PLANAR>(K.sampling, mixed_rgb_op(P, K), L.row, L.group);
 }
 
 } // namespace
 
 hipError_t launch_islow_mixed(const MixedIslowParams &P, hipStream_t s, hipEvent_t k0, hipEvent_t k1) {
-    if (P.n_units == 0) return hipSuccess;
-    hipError_t e;
-    const unsigned groups = (P.n_units + HVC_MIXED_GROUP - 1) / HVC_MIXED_GROUP;
-    MixedIslowParams Q = P;
-    Q.xcd_map = xcd_map_for(groups, 1, Q.xcd_magic); // (0 beyond 65535 groups: the plain order)
-    if (k0 && (e = hipEventRecord(k0, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_islow_mixed, dim3(groups), dim3(HVC_MIXED_LJ_LANES), 0, s, Q);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (k1 && (e = hipEventRecord(k1, s)) != hipSuccess) return e;
-    return hipSuccess;
+    return mixed_launch_xcd(k_islow_mixed, P, s, k0, k1);
 }
 
 hipError_t launch_ycc_to_rgb_fancy_mixed(const MixedRgbParams &P, hipStream_t s, hipEvent_t k0, hipEvent_t k1) {
-    if (P.n_units == 0) return hipSuccess;
-    hipError_t e;
-    const unsigned groups = (P.n_units + HVC_MIXED_GROUP - 1) / HVC_MIXED_GROUP;
-    if (k0 && (e = hipEventRecord(k0, s)) != hipSuccess) return e;
-    if (P.planar) hipLaunchKernelGGL(k_ycc_to_rgb_fancy_mixed<1>, dim3(groups), dim3(HVC_MIXED_LJ_LANES), 0, s, P);
-    else hipLaunchKernelGGL(k_ycc_to_rgb_fancy_mixed<0>, dim3(groups), dim3(HVC_MIXED_LJ_LANES), 0, s, P);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (k1 && (e = hipEventRecord(k1, s)) != hipSuccess) return e;
-    return hipSuccess;
+    return mixed_launch(P.planar ? k_ycc_to_rgb_fancy_mixed<1> : k_ycc_to_rgb_fancy_mixed<0>, P, s, k0, k1);
 }
 
 } // namespace hvc

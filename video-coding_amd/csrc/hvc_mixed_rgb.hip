@@ -2,11 +2,8 @@
 // (k_ycc_to_rgb_mixed) and, under the same decomposition, RGB -> the encoder's planes (k_rgb_to_ycc_mixed, below it).
 //
 // k_ycc_to_rgb (hvc_rgb.hip) takes one RgbOp: one w, h and sampling in the kernarg segment, frames on blockIdx.y.  Here the
-// decomposition comes from device memory (hvc_mixed_rgb_plan.h), as the block stage's does in hvc_mixed.hip: a work map names
-// the image of every work unit, an image descriptor says where its planes and its RGB image are.  A work unit is 64
-// consecutive lanes of ONE image = one wavefront, so the map entry and the descriptor are wave-uniform: they come through
-// scalar loads and live in SGPRs, exactly where k_ycc_to_rgb finds its kernarg copies; the branch on the sampling is
-// wave-uniform too.  A workgroup is four consecutive units (256 lanes); its wavefronts share nothing (no LDS, no barrier).
+// decomposition comes from device memory (hvc_mixed_rgb_plan.h): hvc_mixed_dev.h says how (the image passes: work map, image
+// descriptor, one wavefront per work unit, a wave-uniform branch on the sampling).  No LDS.
 //
 // Per lane: what a lane of k_ycc_to_rgb does, by the same code (HVC_YCC_LANE_TO_RGB, hvc_rgb_dev.h): 8 columns of one image
 // row (4:2:0: two), chroma supersampled in registers with the ceil-window clamping, ycc4_to_rgb, 8-byte stores where the
@@ -15,44 +12,29 @@
 #include <stdint.h>
 
 #include "../../include/hvc_jpeg.h"
+#include "hvc_mixed_dev.h"
 #include "hvc_mixed_rgb.h"
 #include "hvc_rgb_dev.h"
 
 namespace hvc {
 namespace {
 
-#define HVC_MIXED_RGB_LANES (HVC_MIXED_UNIT * HVC_MIXED_GROUP)
-
-template <int S, int PLANAR>
-__device__ __forceinline__ void mixed_rgb_lane(const RgbOp &P, unsigned lr, unsigned g) {
-    const size_t f = 0; // one image per RgbOp
-    HVC_YCC_LANE_TO_RGB(P, f, lr, g);
-}
+struct YccToRgbLane {
+    template <int S, int PLANAR>
+    static __device__ __forceinline__ void lane(const RgbOp &P, unsigned lr, unsigned g) {
+        const size_t f = 0; // one image per RgbOp
+        HVC_YCC_LANE_TO_RGB(P, f, lr, g);
+    }
+};
 
 template <int PLANAR>
-__global__ __launch_bounds__(HVC_MIXED_RGB_LANES) void k_ycc_to_rgb_mixed(MixedRgbParams P) {
-    const unsigned lane = threadIdx.x & (HVC_MIXED_UNIT - 1);
-    const unsigned unit = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * HVC_MIXED_GROUP + (threadIdx.x >> 6)));
-    if (unit >= P.n_units) return; // (the whole wavefront: the last group's spare units)
-    const MixedRgbImageK K = P.images[P.map[unit]]; // wave-uniform: read once, before any store
-    const unsigned t = (unit - K.unit0) * HVC_MIXED_UNIT + lane;
-    if (t >= K.lanes) return;
-    const unsigned lr = K.groups == 1 ? t : __umulhi(t, K.magic), g = t - lr * K.groups;
-    RgbOp R; // the image as k_ycc_to_rgb's parameter block: one frame, its own bases
-    R.y = const_cast<uint8_t *>(P.yuv) + K.y_base;
-    R.cb = const_cast<uint8_t *>(P.yuv) + K.cb_base;
-    R.cr = const_cast<uint8_t *>(P.yuv) + K.cr_base;
-    R.rgb = P.rgb + K.rgb_base;
-    R.y_stride = K.y_stride, R.cb_stride = K.cb_stride, R.cr_stride = K.cr_stride, R.yuv_fs = 0;
-    R.row_stride = K.row_stride, R.plane_stride = K.plane_stride, R.frame_stride = 0;
-    R.w = K.w, R.h = K.h, R.cw = K.cw, R.ch = K.ch;
-    R.vec_y = K.vec_y, R.vec_c = K.vec_c, R.vec_rgb = K.vec_rgb;
-    switch (K.sampling) { // wave-uniform
-    case HVC_YUV_420: mixed_rgb_lane<420, PLANAR>(R, lr, g); break;
-    case HVC_YUV_422: mixed_rgb_lane<422, PLANAR>(R, lr, g); break;
-    case HVC_YUV_444: mixed_rgb_lane<444, PLANAR>(R, lr, g); break;
-    default: mixed_rgb_lane<400, PLANAR>(R, lr, g); break;
-    }
+__global__ __launch_bounds__(HVC_MIXED_LANES) void k_ycc_to_rgb_mixed(MixedRgbParams P) {
+    const MixedWave W = mixed_wave_plain();
+    if (W.unit >= P.n_units) return;
+    const MixedRgbImageK K = P.images[P.map[W.unit]]; // wave-uniform: read once, before any store
+    MixedImageLane L;
+    if (!mixed_image_lane(K, W.unit, W.lane, L)) return;
+    mixed_rgb_dispatch<YccToRgbLane, PLANAR>(K.sampling, mixed_rgb_op(P, K), L.row, L.group);
 }
 
 // The way back (RGB -> the encoder's planes), under the same decomposition: P.rgb is read, the planes at P.yuv are written.
@@ -66,7 +48,7 @@ __device__ __forceinline__ void mixed_ycc_lane(const RgbOp &P, unsigned lr, unsi
 }
 
 template <int PLANAR>
-__global__ __launch_bounds__(HVC_MIXED_RGB_LANES) void k_rgb_to_ycc_mixed(MixedRgbParams P) {
+__global__ __launch_bounds__(HVC_MIXED_LANES) void k_rgb_to_ycc_mixed(MixedRgbParams P) {
     const unsigned lane = threadIdx.x & (HVC_MIXED_UNIT - 1);
     const unsigned unit = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * HVC_MIXED_GROUP + (threadIdx.x >> 6)));
     if (unit >= P.n_units) return; // (the whole wavefront: the last group's spare units)
@@ -94,27 +76,11 @@ __global__ __launch_bounds__(HVC_MIXED_RGB_LANES) void k_rgb_to_ycc_mixed(MixedR
 } // namespace
 
 hipError_t launch_rgb_to_ycc_mixed(const MixedRgbParams &P, hipStream_t s, hipEvent_t k0, hipEvent_t k1) {
-    if (P.n_units == 0) return hipSuccess;
-    hipError_t e;
-    const unsigned groups = (P.n_units + HVC_MIXED_GROUP - 1) / HVC_MIXED_GROUP;
-    if (k0 && (e = hipEventRecord(k0, s)) != hipSuccess) return e;
-    if (P.planar) hipLaunchKernelGGL(k_rgb_to_ycc_mixed<1>, dim3(groups), dim3(HVC_MIXED_RGB_LANES), 0, s, P);
-    else hipLaunchKernelGGL(k_rgb_to_ycc_mixed<0>, dim3(groups), dim3(HVC_MIXED_RGB_LANES), 0, s, P);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (k1 && (e = hipEventRecord(k1, s)) != hipSuccess) return e;
-    return hipSuccess;
+    return mixed_launch(P.planar ? k_rgb_to_ycc_mixed<1> : k_rgb_to_ycc_mixed<0>, P, s, k0, k1);
 }
 
 hipError_t launch_ycc_to_rgb_mixed(const MixedRgbParams &P, hipStream_t s, hipEvent_t k0, hipEvent_t k1) {
-    if (P.n_units == 0) return hipSuccess;
-    hipError_t e;
-    const unsigned groups = (P.n_units + HVC_MIXED_GROUP - 1) / HVC_MIXED_GROUP;
-    if (k0 && (e = hipEventRecord(k0, s)) != hipSuccess) return e;
-    if (P.planar) hipLaunchKernelGGL(k_ycc_to_rgb_mixed<1>, dim3(groups), dim3(HVC_MIXED_RGB_LANES), 0, s, P);
-    else hipLaunchKernelGGL(k_ycc_to_rgb_mixed<0>, dim3(groups), dim3(HVC_MIXED_RGB_LANES), 0, s, P);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (k1 && (e = hipEventRecord(k1, s)) != hipSuccess) return e;
-    return hipSuccess;
+    return mixed_launch(P.planar ? k_ycc_to_rgb_mixed<1> : k_ycc_to_rgb_mixed<0>, P, s, k0, k1);
 }
 
 } // namespace hvc

@@ -3,10 +3,8 @@
 // destination).  The definition is include/hvc_jpeg.h, Resizing -- Pillow's Image.resize on 8-bit images, bit for bit: 22-bit
 // integer taps made on the host (hvc_resize_plan.cpp), clip_0_255((2^21 + SUM k[i] * in[xmin + i]) >> 22) per sample here.
 //
-// Both kernels work under k_ycc_to_rgb_mixed's decomposition (hvc_mixed_rgb.hip): a work map in device memory names the image
-// of every work unit, an image descriptor says where it reads and writes and which axis table it uses.  A work unit is one
-// wavefront of ONE image, so the map entry and the descriptor are wave-uniform: they come through scalar loads and live in
-// SGPRs.  A workgroup is four consecutive units (256 lanes); its wavefronts share nothing (no LDS, no barrier).
+// Both kernels work under the image passes' decomposition of hvc_mixed_dev.h; an image descriptor says where the pass reads and
+// writes and which axis table it uses.  No LDS.
 //
 // k_resize_h_mixed: a unit = 64 consecutive lanes of one image; a lane makes one output sample position of one source row
 // in all its channels (3 interleaved, 1 for a plane of a planar image: the plan emits a planar image as three one-channel
@@ -30,12 +28,12 @@
 #include <stdint.h>
 
 #include "../../include/hvc_jpeg.h"
+#include "hvc_mixed_dev.h"
 #include "hvc_resize.h"
 
 namespace hvc {
 namespace {
 
-#define HVC_RESIZE_LANES (HVC_MIXED_UNIT * HVC_MIXED_GROUP)
 #define HVC_RESIZE_ROUND (1 << (HVC_RESIZE_PRECISION_BITS - 1))
 
 __device__ __forceinline__ unsigned clip8(int acc) {
@@ -61,27 +59,23 @@ __device__ __forceinline__ void resize_h_lane(const ResizeImageK &K, const Resiz
     for (int c = 0; c < CH; c++) d[c] = (uint8_t)clip8(acc[c]);
 }
 
-__global__ __launch_bounds__(HVC_RESIZE_LANES) void k_resize_h_mixed(ResizeParams P) {
-    const unsigned lane = threadIdx.x & (HVC_MIXED_UNIT - 1);
-    const unsigned unit = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * HVC_MIXED_GROUP + (threadIdx.x >> 6)));
-    if (unit >= P.n_units) return; // (the whole wavefront: the last group's spare units)
-    const ResizeImageK K = P.images[P.map[unit]]; // wave-uniform: read once, before any store
-    const unsigned t = (unit - K.unit0) * HVC_MIXED_UNIT + lane;
-    if (t >= K.lanes) return;
-    const unsigned row = K.groups == 1 ? t : __umulhi(t, K.magic), xx = t - row * K.groups;
-    if (K.ch == 3) resize_h_lane<3>(K, P, row, xx); // wave-uniform
-    else resize_h_lane<1>(K, P, row, xx);
+__global__ __launch_bounds__(HVC_MIXED_LANES) void k_resize_h_mixed(ResizeParams P) {
+    const MixedWave W = mixed_wave_plain();
+    if (W.unit >= P.n_units) return;
+    const ResizeImageK K = P.images[P.map[W.unit]]; // wave-uniform: read once, before any store
+    MixedImageLane L;
+    if (!mixed_image_lane(K, W.unit, W.lane, L)) return;
+    if (K.ch == 3) resize_h_lane<3>(K, P, L.row, L.group); // wave-uniform
+    else resize_h_lane<1>(K, P, L.row, L.group);
 }
 
-__global__ __launch_bounds__(HVC_RESIZE_LANES) void k_resize_v_mixed(ResizeParams P) {
-    const unsigned lane = threadIdx.x & (HVC_MIXED_UNIT - 1);
-    const unsigned unit = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * HVC_MIXED_GROUP + (threadIdx.x >> 6)));
-    if (unit >= P.n_units) return;
-    const ResizeImageK K = P.images[P.map[unit]]; // wave-uniform
-    const unsigned u = unit - K.unit0;
-    const unsigned row = K.groups == 1 ? u : __umulhi(u, K.magic), seg = u - row * K.groups; // wave-uniform
-    const unsigned l = seg * HVC_MIXED_UNIT + lane;
-    if (l >= K.lanes) return;
+__global__ __launch_bounds__(HVC_MIXED_LANES) void k_resize_v_mixed(ResizeParams P) {
+    const MixedWave W = mixed_wave_plain();
+    if (W.unit >= P.n_units) return;
+    const ResizeImageK K = P.images[P.map[W.unit]]; // wave-uniform
+    MixedImageLane L;
+    if (!mixed_image_row_lane(K, W.unit, W.lane, L)) return;
+    const unsigned l = L.t, row = L.row;
     const unsigned b = l * 4;                                   // the lane's first byte of the row
     const unsigned nb = min(4u, K.row_bytes - b);               // (l < lanes: b < row_bytes)
     const ResizeRecK rec = P.recs[K.rec0 + row];                // wave-uniform: the row's record and taps are scalar loads
@@ -136,16 +130,14 @@ template <> struct LutElem<2> { typedef uint16_t type; };
 template <> struct LutElem<4> { typedef uint32_t type; };
 
 template <int ELEM>
-__global__ __launch_bounds__(HVC_RESIZE_LANES) void k_resize_v_mixed_lut(ResizeParams P, const typename LutElem<ELEM>::type *__restrict__ lut) {
+__global__ __launch_bounds__(HVC_MIXED_LANES) void k_resize_v_mixed_lut(ResizeParams P, const typename LutElem<ELEM>::type *__restrict__ lut) {
     typedef typename LutElem<ELEM>::type E;
-    const unsigned lane = threadIdx.x & (HVC_MIXED_UNIT - 1);
-    const unsigned unit = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * HVC_MIXED_GROUP + (threadIdx.x >> 6)));
-    if (unit >= P.n_units) return;
-    const ResizeImageK K = P.images[P.map[unit]]; // wave-uniform
-    const unsigned u = unit - K.unit0;
-    const unsigned row = K.groups == 1 ? u : __umulhi(u, K.magic), seg = u - row * K.groups; // wave-uniform
-    const unsigned l = seg * HVC_MIXED_UNIT + lane;
-    if (l >= K.lanes) return;
+    const MixedWave W = mixed_wave_plain();
+    if (W.unit >= P.n_units) return;
+    const ResizeImageK K = P.images[P.map[W.unit]]; // wave-uniform
+    MixedImageLane L;
+    if (!mixed_image_row_lane(K, W.unit, W.lane, L)) return;
+    const unsigned l = L.t, row = L.row;
     const unsigned b = l * 4;                                   // the lane's first sample of the row
     const unsigned nb = min(4u, K.row_bytes - b);               // (l < lanes: b < row_bytes)
     const ResizeRecK rec = P.recs[K.rec0 + row];                // wave-uniform
@@ -197,29 +189,14 @@ __global__ __launch_bounds__(HVC_RESIZE_LANES) void k_resize_v_mixed_lut(ResizeP
 
 } // namespace
 
-hipError_t launch_resize_h_mixed(const ResizeParams &P, hipStream_t s) {
-    if (P.n_units == 0) return hipSuccess;
-    const unsigned groups = (P.n_units + HVC_MIXED_GROUP - 1) / HVC_MIXED_GROUP;
-    hipLaunchKernelGGL(k_resize_h_mixed, dim3(groups), dim3(HVC_RESIZE_LANES), 0, s, P);
-    return hipGetLastError();
-}
+hipError_t launch_resize_h_mixed(const ResizeParams &P, hipStream_t s) { return mixed_launch(k_resize_h_mixed, P, s, nullptr, nullptr); }
 
-hipError_t launch_resize_v_mixed(const ResizeParams &P, hipStream_t s) {
-    if (P.n_units == 0) return hipSuccess;
-    const unsigned groups = (P.n_units + HVC_MIXED_GROUP - 1) / HVC_MIXED_GROUP;
-    hipLaunchKernelGGL(k_resize_v_mixed, dim3(groups), dim3(HVC_RESIZE_LANES), 0, s, P);
-    return hipGetLastError();
-}
+hipError_t launch_resize_v_mixed(const ResizeParams &P, hipStream_t s) { return mixed_launch(k_resize_v_mixed, P, s, nullptr, nullptr); }
 
 hipError_t launch_resize_v_mixed_lut(const ResizeParams &P, const void *lut, int elem, hipStream_t s) {
     if ((elem != 2 && elem != 4) || !lut) return hipErrorInvalidValue;
-    if (P.n_units == 0) return hipSuccess;
-    const unsigned groups = (P.n_units + HVC_MIXED_GROUP - 1) / HVC_MIXED_GROUP;
-    if (elem == 2)
-        hipLaunchKernelGGL(k_resize_v_mixed_lut<2>, dim3(groups), dim3(HVC_RESIZE_LANES), 0, s, P, static_cast<const uint16_t *>(lut));
-    else
-        hipLaunchKernelGGL(k_resize_v_mixed_lut<4>, dim3(groups), dim3(HVC_RESIZE_LANES), 0, s, P, static_cast<const uint32_t *>(lut));
-    return hipGetLastError();
+    if (elem == 2) return mixed_launch(k_resize_v_mixed_lut<2>, P, s, nullptr, nullptr, static_cast<const uint16_t *>(lut));
+    return mixed_launch(k_resize_v_mixed_lut<4>, P, s, nullptr, nullptr, static_cast<const uint32_t *>(lut));
 }
 
 } // namespace hvc
