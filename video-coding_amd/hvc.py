@@ -12,46 +12,6 @@ _LIB = None
 
 HVC_MEM_HOST, HVC_MEM_DEVICE = 0, 1
 
-# every symbol include/hvc_jpeg.h declares
-SYMBOLS = [
-    "hvc_create", "hvc_destroy", "hvc_strerror", "hvc_last_hip_error", "hvc_version", "hvc_set_stream",
-    "hvc_synchronize", "hvc_timer_begin", "hvc_timer_end", "hvc_set_profiling", "hvc_last_kernel_ms", "hvc_kernel_ms_history", "hvc_dequant_idct_recon", "hvc_decode_frames",
-    "hvc_last_wide_blocks", "hvc_fdct_quant", "hvc_encode_frames", "hvc_upsample420", "hvc_device_alloc",
-    "hvc_device_free", "hvc_memcpy_h2d", "hvc_memcpy_d2h",
-    "hvc_jpeg_read_header", "hvc_jpeg_entropy_decode", "hvc_jpeg_get_yuv_frame", "hvc_jpeg_decode",
-    "hvc_jpeg_decode_batch", "hvc_quant_table", "hvc_jpeg_encoder_layout", "hvc_jpeg_entropy_encode",
-    "hvc_jpeg_encode", "hvc_set_decode_kernel", "hvc_reset_stream", "hvc_decode_frames_yuv444", "hvc_jpeg_decode_yuv444", "hvc_compare_planes", "hvc_jpeg_encode_batch", "hvc_jpeg_decode_batch_yuv444", "hvc_jpeg_encoder_check", "hvc_huffman_encode_frames", "hvc_jpeg_header", "hvc_jpeg_encode_batch_gpu", "hvc_jpeg_entropy_decode_gpu", "hvc_jpeg_decode_batch_gpu",
-    "hvc_checksum_records", "hvc_encode_frames_recon", "hvc_set_host_cpus", "hvc_get_host_cpus",
-    "hvc_host_threads", "hvc_host_threads_probe", "hvc_jpeg_entropy_decode2", "hvc_jpeg_get_cropped_planes",
-    "hvc_jpeg_entropy_decode_restart", "hvc_set_restart_markers",
-    "hvc_subsample420", "hvc_subsample422", "hvc_upsample422", "hvc_crop_planes", "hvc_yuv_frame_bytes", "hvc_yuv_convert",
-    "hvc_host_alloc", "hvc_host_free", "hvc_host_register", "hvc_host_unregister", "hvc_decode_frames_submit",
-    "hvc_encode_frames_submit", "hvc_wait", "hvc_slot_query", "hvc_slot_last_stats", "hvc_huffman_code_tables",
-    "hvc_set_arithmetic", "hvc_get_arithmetic", "hvc_decode_frames_divergence",
-    "hvc_set_encode_arithmetic", "hvc_get_encode_arithmetic", "hvc_encode_frames_divergence",
-    "hvc_set_encode_libjpeg", "hvc_get_encode_libjpeg",
-    "hvc_dct_rom", "hvc_dct_matrix", "hvc_dct_blocks", "hvc_dct_fixed", "hvc_dct_reference", "hvc_dct_error_search",
-    "hvc_set_huffman_tables", "hvc_get_huffman_tables", "hvc_huffman_spec_from_counts", "hvc_huffman_optimal_tables",
-    "hvc_jpeg_header_tables", "hvc_jpeg_entropy_encode_tables", "hvc_huffman_encode_frames_optimised",
-    "hvc_set_restart_interval", "hvc_get_restart_interval", "hvc_jpeg_header_restart", "hvc_jpeg_entropy_encode_restart",
-    "hvc_huffman_optimal_tables_restart", "hvc_huffman_encode_frames_restart",
-    "hvc_yuv_to_rgb", "hvc_rgb_to_yuv", "hvc_decode_frames_rgb", "hvc_jpeg_decode_rgb", "hvc_jpeg_decode_batch_rgb",
-    "hvc_jpeg_encode_rgb",
-    "hvc_jpeg_scaled_info", "hvc_decode_frames_scaled", "hvc_jpeg_decode_scaled", "hvc_jpeg_decode_scaled_rgb",
-    "hvc_jpeg_decode_batch_scaled",
-    "hvc_jpeg_mixed_layout", "hvc_decode_frames_mixed", "hvc_jpeg_decode_batch_mixed",
-    "hvc_set_mixed_reader", "hvc_get_mixed_reader", "hvc_last_mixed_reader_files", "hvc_jpeg_entropy_decode_gpu_mixed",
-    "hvc_jpeg_mixed_rgb_layout", "hvc_yuv_to_rgb_mixed", "hvc_decode_frames_mixed_rgb", "hvc_jpeg_decode_batch_mixed_rgb",
-    "hvc_jpeg_mixed_scaled_layout", "hvc_decode_frames_mixed_scaled", "hvc_jpeg_decode_batch_mixed_scaled",
-    "hvc_jpeg_mixed_scaled_rgb_layout", "hvc_jpeg_decode_batch_mixed_scaled_rgb",
-    "hvc_jpeg_encoder_mixed_layout", "hvc_encode_frames_mixed", "hvc_jpeg_encode_batch_mixed",
-    "hvc_huffman_encode_frames_mixed", "hvc_jpeg_encode_batch_mixed_gpu", "hvc_last_mixed_coder_files",
-    "hvc_jpeg_encoder_mixed_rgb_layout", "hvc_rgb_to_yuv_mixed", "hvc_encode_frames_mixed_rgb", "hvc_jpeg_encode_batch_mixed_rgb",
-    "hvc_jpeg_encode_batch_mixed_rgb_gpu",
-    "hvc_rgb_resize_mixed", "hvc_jpeg_decode_batch_mixed_resized",
-    "hvc_rgb_resize_mixed_opts", "hvc_jpeg_decode_batch_mixed_resized_opts", "hvc_normalize_lut",
-    "hvc_set_mixed_arithmetic", "hvc_get_mixed_arithmetic",
-]
 HVC_RESIZE = {"box": 0, "bilinear": 1, "bicubic": 2}  # enum hvc_resize_filter
 HVC_RESIZE_MAX_TAPS = 2048
 HVC_ELEM = {"float32": 1, "float16": 2, "bfloat16": 3}  # enum hvc_elem: what hvc_normalize_lut makes a table of
@@ -124,6 +84,14 @@ class HuffSpec(C.Structure):
         return s
 
 
+def _spec_pairs(specs, n, status=None):
+    """the 4 * n hvc_huff_spec a GPU coder call filled -> per frame its [(bits, vals)] x 4, None for a frame whose status is
+    not 0; None where the call had no specs to fill (the default tables)"""
+    if specs is None:
+        return None
+    return [[specs[4 * f + t].to_pair() for t in range(4)] if status is None or status[f] == 0 else None for f in range(n)]
+
+
 def huff_specs(specs):
     """four (bits, vals) pairs or HuffSpec -> ctypes array of 4 hvc_huff_spec (DC0, DC1, AC0, AC1)"""
     if isinstance(specs, C.Array):
@@ -155,6 +123,183 @@ class SlotStats(C.Structure):
                 ("d2h_bytes", C.c_uint64)]
 
 
+class ResizeOpts(C.Structure):
+    """hvc_resize_opts: a box and a mirror flag per image, a typed output through a table"""
+    _fields_ = [("boxes", C.POINTER(C.c_float)), ("mirror", C.POINTER(C.c_uint8)), ("out_elem", C.c_int), ("lut", C.c_void_p)]
+
+
+class DctConfig(C.Structure):
+    _fields_ = [("mode", C.c_int), ("fwd_rom_prec", C.c_int), ("fwd_transpose_prec", C.c_int), ("inv_rom_prec", C.c_int),
+                ("inv_transpose_prec", C.c_int)]
+
+
+class DctError(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("worst_block", C.c_uint64)]
+
+
+# -- the ABI: every function include/hvc_jpeg.h declares, name -> (argtypes[, restype]); restype is int (an hvc_status)
+#    where it is not given.  lib() applies the table and SYMBOLS lists it; tests/test_binding_prototypes.py holds it to the header.
+_vp, _sz, _i, _u64 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint64
+_vpp, _szp, _intp, _u64p, _fp = C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_i), C.POINTER(_u64), C.POINTER(C.c_float)
+_ip, _hs, _cs, _st = C.POINTER(JpegInfo), C.POINTER(HuffSpec), C.POINTER(Component), C.POINTER(BatchStats)
+_FRAMES = [_vp, _vp, _sz, _vp, _i, _cs, _i, _i, _vp, _sz, _i]       # ctx, records in, stride, qtabs, n, comps, n, frames, records out, stride, where
+_PLANE_OP = [_vp, _vp, _i, _i, _sz, _vp, _sz, _i, _sz, _sz, _i]    # ctx, src, w, h, stride, dst, stride, planes, plane strides, where
+_FILES = [_vpp, _szp, _i]                                          # jpegs, sizes, n_files
+_DECODE_BATCH = [_vp] + _FILES + [_i, _i, _vp, _sz, _i, _st]
+_ENCODE_BATCH = [_vp, _vpp, _i, _i, _i, _i, _i, _i, _i, _vpp, _szp, _szp, _st]
+_ENCODE_BATCH_MIXED = [_vp, _vpp, _ip, _intp, _i, _i, _sz, _vpp, _szp, _szp, _st]
+_ENCODE_BATCH_MIXED_RGB = [_vp, _vpp, _szp, _i, _ip, _intp, _i, _i, _sz, _vpp, _szp, _szp, _st]
+_COLOUR_MIXED = [_vp, _vp, _szp, _ip, _i, _vp, _szp, _szp, _i, _i]  # ctx, records, offsets, infos, n, rgb, offsets, row strides, layout, where
+_RESIZE_MIXED = [_vp, _vp, _szp, _szp, _intp, _intp, _i, _vp, _szp, _szp, _intp, _intp, _i, _i, _i]
+_DECODE_BATCH_RESIZED = [_vp] + _FILES + [_i, _sz, _i, _ip, _intp, _intp, _intp, _szp, _szp, _vp, _sz, _i, _i, _i, _st]
+_ENCODER_COLUMNS = [_intp, _intp, _intp, _intp, _i]                 # widths, heights, chromas, qualities, n_frames
+PROTOTYPES = {
+    "hvc_create": ([_vpp, _i],),
+    "hvc_destroy": ([_vp], None),
+    "hvc_strerror": ([_i], C.c_char_p),
+    "hvc_last_hip_error": ([_vp],),
+    "hvc_version": ([], C.c_char_p),
+    "hvc_host_threads": ([_vp, _intp, _u64p],),
+    "hvc_host_threads_probe": ([_i],),
+    "hvc_set_host_cpus": ([_vp, C.c_char_p],),
+    "hvc_get_host_cpus": ([_vp, C.c_char_p, _sz, _intp],),
+    "hvc_set_stream": ([_vp, _vp],),
+    "hvc_reset_stream": ([_vp],),
+    "hvc_synchronize": ([_vp],),
+    "hvc_timer_begin": ([_vp],),
+    "hvc_timer_end": ([_vp, _fp],),
+    "hvc_set_profiling": ([_vp, _i],),
+    "hvc_last_kernel_ms": ([_vp, _fp],),
+    "hvc_kernel_ms_history": ([_vp, _fp, _i],),
+    "hvc_dequant_idct_recon": ([_vp, _vp, _sz, _vp, _i, _i, _i, _vp, _sz, _sz, _i],),
+    "hvc_decode_frames": (_FRAMES,),
+    "hvc_decode_frames_yuv444": ([_vp, _vp, _sz, _vp, _i, _cs, _i, _i, _i, _i, _vp, _sz, _i],),
+    "hvc_set_decode_kernel": ([_vp, _i],),
+    "hvc_set_arithmetic": ([_vp, _i],),
+    "hvc_get_arithmetic": ([_vp, _intp],),
+    "hvc_decode_frames_divergence": (_FRAMES,),
+    "hvc_set_encode_arithmetic": ([_vp, _i],),
+    "hvc_get_encode_arithmetic": ([_vp, _intp],),
+    "hvc_encode_frames_divergence": (_FRAMES,),
+    "hvc_last_wide_blocks": ([_vp, _u64p],),
+    "hvc_fdct_quant": ([_vp, _vp, _sz, _sz, _vp, _i, _i, _i, _vp, _sz, _i],),
+    "hvc_encode_frames": (_FRAMES,),
+    "hvc_encode_frames_recon": (_FRAMES[:-1] + [_vp, _vp, _i],),
+    "hvc_upsample420": (_PLANE_OP,),
+    "hvc_subsample420": (_PLANE_OP,),
+    "hvc_subsample422": (_PLANE_OP,),
+    "hvc_upsample422": (_PLANE_OP,),
+    "hvc_crop_planes": ([_vp, _vp, _i, _i, _sz, _i, _i, _vp, _i, _i, _sz, _i, _sz, _sz, _i],),
+    "hvc_yuv_frame_bytes": ([_i, _i, _i, _szp],),
+    "hvc_yuv_convert": ([_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i],),
+    "hvc_jpeg_read_header": ([_vp, _sz, _ip],),
+    "hvc_jpeg_entropy_decode": ([_vp, _sz, _ip, _vp],),
+    "hvc_jpeg_entropy_decode_restart": ([_vp, _sz, _ip, _vp],),
+    "hvc_set_restart_markers": ([_vp, _i],),
+    "hvc_jpeg_entropy_decode2": ([_vp, _sz, _ip, _vp, _intp, _vp, _sz, _ip, _vp, _intp],),
+    "hvc_jpeg_get_yuv_frame": ([_ip, _vp, _vp, _sz, _szp],),
+    "hvc_jpeg_get_cropped_planes": ([_ip, _vp, _vp, _sz, _szp],),
+    "hvc_jpeg_decode": ([_vp, _vp, _sz, _ip, _vp, _sz],),
+    "hvc_jpeg_decode_yuv444": ([_vp, _vp, _sz, _ip, _vp, _sz],),
+    "hvc_jpeg_decode_batch": (_DECODE_BATCH,),
+    "hvc_jpeg_decode_batch_yuv444": (_DECODE_BATCH,),
+    "hvc_quant_table": ([_i, _i, _vp],),
+    "hvc_compare_planes": ([_vp, _vp, _sz, _intp, _u64p, _u64p],),
+    "hvc_jpeg_encoder_layout": ([_i, _i, _i, _i, _ip],),
+    "hvc_jpeg_decode_batch_gpu": (_DECODE_BATCH[:-1] + [_i, _st],),
+    "hvc_jpeg_entropy_decode_gpu": ([_vp] + _FILES + [_vp, _sz, _i, _ip, _intp],),
+    "hvc_huffman_encode_frames": ([_vp, _ip, _vp, _sz, _i, _vp, _sz, _vp, _i],),
+    "hvc_jpeg_header": ([_ip, _vp, _sz, _szp],),
+    "hvc_huffman_code_tables": ([_vp, _i, _i, _vp],),
+    "hvc_jpeg_encoder_check": ([_ip],),
+    "hvc_jpeg_entropy_encode": ([_ip, _vp, _vp, _sz, _szp],),
+    "hvc_jpeg_encode": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _szp],),
+    "hvc_set_huffman_tables": ([_vp, _i],),
+    "hvc_get_huffman_tables": ([_vp, _intp],),
+    "hvc_huffman_spec_from_counts": ([_vp, _hs],),
+    "hvc_huffman_optimal_tables": ([_ip, _vp, _hs],),
+    "hvc_jpeg_header_tables": ([_ip, _hs, _vp, _sz, _szp],),
+    "hvc_jpeg_entropy_encode_tables": ([_ip, _hs, _vp, _vp, _sz, _szp],),
+    "hvc_huffman_encode_frames_optimised": ([_vp, _ip, _vp, _sz, _i, _vp, _sz, _vp, _hs, _i],),
+    "hvc_set_restart_interval": ([_vp, _i],),
+    "hvc_get_restart_interval": ([_vp, _intp],),
+    "hvc_jpeg_header_restart": ([_ip, _hs, _i, _vp, _sz, _szp],),
+    "hvc_jpeg_entropy_encode_restart": ([_ip, _hs, _i, _vp, _vp, _sz, _szp],),
+    "hvc_huffman_optimal_tables_restart": ([_ip, _vp, _i, _hs],),
+    "hvc_huffman_encode_frames_restart": ([_vp, _ip, _vp, _sz, _i, _i, _i, _vp, _sz, _vp, _hs, _i],),
+    "hvc_jpeg_encode_batch": (_ENCODE_BATCH,),
+    "hvc_jpeg_encode_batch_gpu": (_ENCODE_BATCH,),
+    "hvc_yuv_to_rgb": ([_vp, _vp, _sz, _cs, _i, _i, _i, _i, _i, _i, _vp, _sz, _sz, _i, _i],),
+    "hvc_rgb_to_yuv": ([_vp, _vp, _sz, _sz, _i, _i, _i, _i, _i, _vp, _sz, _cs, _i],),
+    "hvc_decode_frames_rgb": ([_vp, _vp, _sz, _vp, _i, _cs, _i, _i, _i, _i, _i, _vp, _sz, _sz, _i, _i],),
+    "hvc_jpeg_decode_rgb": ([_vp, _vp, _sz, _ip, _vp, _sz, _sz, _i],),
+    "hvc_jpeg_decode_batch_rgb": ([_vp] + _FILES + [_i, _i, _i, _vp, _sz, _sz, _i, _i, _st],),
+    "hvc_jpeg_encode_rgb": ([_vp, _vp, _sz, _i, _i, _i, _i, _i, _vp, _sz, _szp],),
+    "hvc_set_mixed_arithmetic": ([_vp, _i],),
+    "hvc_get_mixed_arithmetic": ([_vp, _intp],),
+    "hvc_set_encode_libjpeg": ([_vp, _i],),
+    "hvc_get_encode_libjpeg": ([_vp, _intp],),
+    "hvc_jpeg_scaled_info": ([_ip, _i, _ip],),
+    "hvc_decode_frames_scaled": ([_vp, _vp, _sz, _vp, _i, _cs, _i, _i, _i, _vp, _sz, _i],),
+    "hvc_jpeg_decode_scaled": ([_vp, _vp, _sz, _i, _ip, _vp, _sz],),
+    "hvc_jpeg_decode_scaled_rgb": ([_vp, _vp, _sz, _i, _ip, _vp, _sz, _sz, _i],),
+    "hvc_jpeg_decode_batch_scaled": ([_vp] + _FILES + [_i, _i, _i, _i, _vp, _sz, _i, _st],),
+    "hvc_jpeg_mixed_layout": (_FILES + [_sz, _ip, _intp, _szp, _szp],),
+    "hvc_decode_frames_mixed": ([_vp, _vp, _szp, _ip, _i, _vp, _szp, _i],),
+    "hvc_jpeg_decode_batch_mixed": ([_vp] + _FILES + [_i, _sz, _ip, _intp, _szp, _vp, _sz, _i, _st],),
+    "hvc_set_mixed_reader": ([_vp, _i],),
+    "hvc_get_mixed_reader": ([_vp, _intp],),
+    "hvc_last_mixed_reader_files": ([_vp, _u64p, _u64p],),
+    "hvc_jpeg_entropy_decode_gpu_mixed": ([_vp] + _FILES + [_vp, _intp, _vp, _szp, _sz, _i, _intp],),
+    "hvc_jpeg_mixed_rgb_layout": (_FILES + [_i, _sz, _sz, _ip, _intp, _szp, _szp, _szp],),
+    "hvc_yuv_to_rgb_mixed": (_COLOUR_MIXED,),
+    "hvc_decode_frames_mixed_rgb": (_COLOUR_MIXED,),
+    "hvc_jpeg_decode_batch_mixed_rgb": ([_vp] + _FILES + [_i, _sz, _ip, _intp, _szp, _szp, _vp, _sz, _i, _i, _st],),
+    "hvc_jpeg_mixed_scaled_layout": (_FILES + [_i, _sz, _ip, _ip, _intp, _szp, _szp],),
+    "hvc_decode_frames_mixed_scaled": ([_vp, _vp, _szp, _ip, _i, _i, _vp, _szp, _i],),
+    "hvc_jpeg_decode_batch_mixed_scaled": ([_vp] + _FILES + [_i, _sz, _i, _ip, _intp, _szp, _vp, _sz, _i, _st],),
+    "hvc_jpeg_mixed_scaled_rgb_layout": (_FILES + [_i, _i, _sz, _sz, _ip, _ip, _intp, _szp, _szp, _szp],),
+    "hvc_jpeg_decode_batch_mixed_scaled_rgb": ([_vp] + _FILES + [_i, _sz, _i, _ip, _intp, _szp, _szp, _vp, _sz, _i, _i, _st],),
+    "hvc_jpeg_encoder_mixed_layout": (_ENCODER_COLUMNS + [_sz, _ip, _intp, _szp, _szp, _szp, _szp],),
+    "hvc_encode_frames_mixed": ([_vp, _vp, _szp, _ip, _i, _vp, _szp, _i],),
+    "hvc_jpeg_encode_batch_mixed": (_ENCODE_BATCH_MIXED,),
+    "hvc_huffman_encode_frames_mixed": ([_vp, _ip, _vp, _szp, _i, _i, _vp, _sz, _vp, _intp, _hs, _i],),
+    "hvc_jpeg_encode_batch_mixed_gpu": (_ENCODE_BATCH_MIXED,),
+    "hvc_last_mixed_coder_files": ([_vp, _u64p, _u64p],),
+    "hvc_jpeg_encoder_mixed_rgb_layout": (_ENCODER_COLUMNS + [_i, _sz, _sz, _ip, _intp, _szp, _szp, _szp, _szp, _szp, _szp, _szp],),
+    "hvc_rgb_to_yuv_mixed": (_COLOUR_MIXED,),
+    "hvc_encode_frames_mixed_rgb": ([_vp, _vp, _szp, _szp, _i, _ip, _i, _vp, _szp, _i],),
+    "hvc_jpeg_encode_batch_mixed_rgb": (_ENCODE_BATCH_MIXED_RGB,),
+    "hvc_jpeg_encode_batch_mixed_rgb_gpu": (_ENCODE_BATCH_MIXED_RGB,),
+    "hvc_rgb_resize_mixed": (_RESIZE_MIXED,),
+    "hvc_jpeg_decode_batch_mixed_resized": (_DECODE_BATCH_RESIZED,),
+    "hvc_rgb_resize_mixed_opts": (_RESIZE_MIXED + [C.POINTER(ResizeOpts)],),
+    "hvc_jpeg_decode_batch_mixed_resized_opts": (_DECODE_BATCH_RESIZED + [C.POINTER(ResizeOpts)],),
+    "hvc_normalize_lut": ([_fp, _fp, _i, _vp],),
+    "hvc_checksum_records": ([_vp, _vp, _sz, _sz, _i, _vp, _i],),
+    "hvc_host_alloc": ([_vp, _sz, _vpp],),
+    "hvc_host_free": ([_vp, _vp],),
+    "hvc_host_register": ([_vp, _vp, _sz],),
+    "hvc_host_unregister": ([_vp, _vp],),
+    "hvc_decode_frames_submit": ([_vp, _i] + _FRAMES[1:],),
+    "hvc_encode_frames_submit": ([_vp, _i] + _FRAMES[1:],),
+    "hvc_wait": ([_vp, _i],),
+    "hvc_slot_query": ([_vp, _i, _intp],),
+    "hvc_slot_last_stats": ([_vp, _i, C.POINTER(SlotStats)],),
+    "hvc_dct_rom": ([_i, _vp],),
+    "hvc_dct_matrix": ([_vp],),
+    "hvc_dct_blocks": ([_u64, _i, _u64, _sz, _vp],),
+    "hvc_dct_fixed": ([_vp, _i, _i, _i, _vp, _vp, _sz, _i],),
+    "hvc_dct_reference": ([_vp, _i, _vp, _vp, _sz, _i],),
+    "hvc_dct_error_search": ([_vp, C.POINTER(DctConfig), _sz, _u64, _i, _u64, _u64, C.POINTER(DctError)],),
+    "hvc_device_alloc": ([_vp, _sz, _vpp],),
+    "hvc_device_free": ([_vp, _vp],),
+    "hvc_memcpy_h2d": ([_vp, _vp, _vp, _sz],),
+    "hvc_memcpy_d2h": ([_vp, _vp, _vp, _sz],),
+}
+SYMBOLS = list(PROTOTYPES)
+
+
 def build(force=False):
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_DIR, "csrc", f) for f in os.listdir(os.path.join(_DIR, "csrc"))]
@@ -181,170 +326,14 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(_SO)
-        vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
-        L.hvc_strerror.restype = C.c_char_p
-        L.hvc_strerror.argtypes = [i]
-        L.hvc_version.restype = C.c_char_p
-        L.hvc_create.argtypes = [C.POINTER(vp), i]
-        L.hvc_destroy.argtypes = [vp]
-        L.hvc_destroy.restype = None
-        L.hvc_last_hip_error.argtypes = [vp]
-        L.hvc_set_stream.argtypes = [vp, vp]
-        L.hvc_synchronize.argtypes = [vp]
-        L.hvc_timer_begin.argtypes = [vp]
-        L.hvc_timer_end.argtypes = [vp, C.POINTER(C.c_float)]
-        L.hvc_set_profiling.argtypes = [vp, i]
-        L.hvc_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.hvc_kernel_ms_history.argtypes = [vp, C.POINTER(C.c_float), i]
-        L.hvc_dequant_idct_recon.argtypes = [vp, vp, sz, vp, i, i, i, vp, sz, sz, i]
-        L.hvc_decode_frames.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
-        L.hvc_decode_frames_yuv444.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, i, i, vp, sz, i]
-        L.hvc_last_wide_blocks.argtypes = [vp, C.POINTER(C.c_uint64)]
-        if hasattr(L, "hvc_fdct_quant"):
-            L.hvc_fdct_quant.argtypes = [vp, vp, sz, sz, vp, i, i, i, vp, sz, i]
-            L.hvc_encode_frames.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
-            L.hvc_upsample420.argtypes = [vp, vp, i, i, sz, vp, sz, i, sz, sz, i]
-            for f in ("hvc_subsample420", "hvc_subsample422", "hvc_upsample422"):
-                getattr(L, f).argtypes = [vp, vp, i, i, sz, vp, sz, i, sz, sz, i]
-            L.hvc_crop_planes.argtypes = [vp, vp, i, i, sz, i, i, vp, i, i, sz, i, sz, sz, i]
-            L.hvc_yuv_frame_bytes.argtypes = [i, i, i, C.POINTER(sz)]
-            L.hvc_yuv_convert.argtypes = [vp, vp, i, i, i, i, i, vp, i, i, i, i, i]
-        ip = C.POINTER(JpegInfo)
-        L.hvc_jpeg_read_header.argtypes = [vp, sz, ip]
-        L.hvc_jpeg_entropy_decode.argtypes = [vp, sz, ip, vp]
-        L.hvc_jpeg_entropy_decode_restart.argtypes = [vp, sz, ip, vp]
-        L.hvc_set_restart_markers.argtypes = [vp, i]
-        L.hvc_set_mixed_reader.argtypes = [vp, i]
-        L.hvc_get_mixed_reader.argtypes = [vp, C.POINTER(i)]
-        L.hvc_last_mixed_reader_files.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        L.hvc_jpeg_entropy_decode_gpu_mixed.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, vp, C.POINTER(i), vp, C.POINTER(sz), sz, i, C.POINTER(i)]
-        L.hvc_set_arithmetic.argtypes = [vp, i]
-        L.hvc_get_arithmetic.argtypes = [vp, C.POINTER(i)]
-        L.hvc_set_mixed_arithmetic.argtypes = [vp, i]
-        L.hvc_get_mixed_arithmetic.argtypes = [vp, C.POINTER(i)]
-        L.hvc_decode_frames_divergence.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
-        L.hvc_set_encode_arithmetic.argtypes = [vp, i]
-        L.hvc_get_encode_arithmetic.argtypes = [vp, C.POINTER(i)]
-        L.hvc_set_encode_libjpeg.argtypes = [vp, i]
-        L.hvc_get_encode_libjpeg.argtypes = [vp, C.POINTER(i)]
-        L.hvc_encode_frames_divergence.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
-        u64 = C.c_uint64
-        L.hvc_dct_rom.argtypes = [i, vp]
-        L.hvc_dct_matrix.argtypes = [vp]
-        L.hvc_dct_blocks.argtypes = [u64, i, u64, sz, vp]
-        L.hvc_dct_fixed.argtypes = [vp, i, i, i, vp, vp, sz, i]
-        L.hvc_dct_reference.argtypes = [vp, i, vp, vp, sz, i]
-        L.hvc_dct_error_search.argtypes = [vp, C.POINTER(DctConfig), sz, u64, i, u64, u64, C.POINTER(DctError)]
-        L.hvc_jpeg_get_yuv_frame.argtypes = [ip, vp, vp, sz, C.POINTER(sz)]
-        L.hvc_jpeg_get_cropped_planes.argtypes = [ip, vp, vp, sz, C.POINTER(sz)]
-        L.hvc_jpeg_entropy_decode2.argtypes = [vp, sz, ip, vp, C.POINTER(i), vp, sz, ip, vp, C.POINTER(i)]
-        L.hvc_jpeg_decode.argtypes = [vp, vp, sz, ip, vp, sz]
-        L.hvc_jpeg_decode_yuv444.argtypes = [vp, vp, sz, ip, vp, sz]
-        L.hvc_jpeg_decode_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, i, vp, sz, i,
-                                            C.POINTER(BatchStats)]
-        L.hvc_quant_table.argtypes = [i, i, vp]
-        L.hvc_jpeg_decode_batch_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, i, vp, sz, i, i, C.POINTER(BatchStats)]
-        L.hvc_jpeg_entropy_decode_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, vp, sz, i, ip, C.POINTER(i)]
-        L.hvc_huffman_encode_frames.argtypes = [vp, ip, vp, sz, i, vp, sz, vp, i]
-        L.hvc_jpeg_header.argtypes = [ip, vp, sz, C.POINTER(sz)]
-        L.hvc_jpeg_decode_batch_yuv444.argtypes = L.hvc_jpeg_decode_batch.argtypes
-        L.hvc_jpeg_encode_batch.argtypes = [vp, C.POINTER(vp), i, i, i, i, i, i, i, C.POINTER(vp), C.POINTER(sz),
-                                            C.POINTER(sz), C.POINTER(BatchStats)]
-        L.hvc_jpeg_encode_batch_gpu.argtypes = L.hvc_jpeg_encode_batch.argtypes
-        L.hvc_compare_planes.argtypes = [vp, vp, sz, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        L.hvc_jpeg_encoder_layout.argtypes = [i, i, i, i, ip]
-        L.hvc_jpeg_entropy_encode.argtypes = [ip, vp, vp, sz, C.POINTER(sz)]
-        hs = C.POINTER(HuffSpec)
-        L.hvc_set_huffman_tables.argtypes = [vp, i]
-        L.hvc_get_huffman_tables.argtypes = [vp, C.POINTER(i)]
-        L.hvc_huffman_spec_from_counts.argtypes = [vp, hs]
-        L.hvc_huffman_optimal_tables.argtypes = [ip, vp, hs]
-        L.hvc_jpeg_header_tables.argtypes = [ip, hs, vp, sz, C.POINTER(sz)]
-        L.hvc_jpeg_entropy_encode_tables.argtypes = [ip, hs, vp, vp, sz, C.POINTER(sz)]
-        L.hvc_huffman_encode_frames_optimised.argtypes = [vp, ip, vp, sz, i, vp, sz, vp, hs, i]
-        L.hvc_set_restart_interval.argtypes = [vp, i]
-        L.hvc_get_restart_interval.argtypes = [vp, C.POINTER(i)]
-        L.hvc_jpeg_header_restart.argtypes = [ip, hs, i, vp, sz, C.POINTER(sz)]
-        L.hvc_jpeg_entropy_encode_restart.argtypes = [ip, hs, i, vp, vp, sz, C.POINTER(sz)]
-        L.hvc_huffman_optimal_tables_restart.argtypes = [ip, vp, i, hs]
-        L.hvc_huffman_encode_frames_restart.argtypes = [vp, ip, vp, sz, i, i, i, vp, sz, vp, hs, i]
-        L.hvc_jpeg_encode.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, sz, C.POINTER(sz)]
-        L.hvc_yuv_to_rgb.argtypes = [vp, vp, sz, C.POINTER(Component), i, i, i, i, i, i, vp, sz, sz, i, i]
-        L.hvc_rgb_to_yuv.argtypes = [vp, vp, sz, sz, i, i, i, i, i, vp, sz, C.POINTER(Component), i]
-        L.hvc_decode_frames_rgb.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, i, i, i, vp, sz, sz, i, i]
-        L.hvc_jpeg_decode_rgb.argtypes = [vp, vp, sz, ip, vp, sz, sz, i]
-        L.hvc_jpeg_decode_batch_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, i, i, vp, sz, sz, i, i,
-                                                C.POINTER(BatchStats)]
-        L.hvc_jpeg_encode_rgb.argtypes = [vp, vp, sz, i, i, i, i, i, vp, sz, C.POINTER(sz)]
-        L.hvc_jpeg_scaled_info.argtypes = [ip, i, ip]
-        L.hvc_decode_frames_scaled.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, i, vp, sz, i]
-        L.hvc_jpeg_decode_scaled.argtypes = [vp, vp, sz, i, ip, vp, sz]
-        L.hvc_jpeg_decode_scaled_rgb.argtypes = [vp, vp, sz, i, ip, vp, sz, sz, i]
-        L.hvc_jpeg_decode_batch_scaled.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, i, i, i, vp, sz, i,
-                                                   C.POINTER(BatchStats)]
-        L.hvc_jpeg_mixed_layout.argtypes = [C.POINTER(vp), C.POINTER(sz), i, sz, ip, C.POINTER(i), C.POINTER(sz), C.POINTER(sz)]
-        L.hvc_decode_frames_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), i]
-        L.hvc_jpeg_decode_batch_mixed.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, ip, C.POINTER(i), C.POINTER(sz), vp, sz, i,
-                                                  C.POINTER(BatchStats)]
-        L.hvc_jpeg_mixed_rgb_layout.argtypes = [C.POINTER(vp), C.POINTER(sz), i, i, sz, sz, ip, C.POINTER(i), C.POINTER(sz), C.POINTER(sz),
-                                                C.POINTER(sz)]
-        L.hvc_jpeg_mixed_scaled_layout.argtypes = [C.POINTER(vp), C.POINTER(sz), i, i, sz, ip, ip, C.POINTER(i), C.POINTER(sz),
-                                                   C.POINTER(sz)]
-        L.hvc_decode_frames_mixed_scaled.argtypes = [vp, vp, C.POINTER(sz), ip, i, i, vp, C.POINTER(sz), i]
-        L.hvc_jpeg_decode_batch_mixed_scaled.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, i, ip, C.POINTER(i), C.POINTER(sz),
-                                                         vp, sz, i, C.POINTER(BatchStats)]
-        L.hvc_jpeg_mixed_scaled_rgb_layout.argtypes = [C.POINTER(vp), C.POINTER(sz), i, i, i, sz, sz, ip, ip, C.POINTER(i),
-                                                       C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
-        L.hvc_jpeg_decode_batch_mixed_scaled_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, i, ip, C.POINTER(i),
-                                                             C.POINTER(sz), C.POINTER(sz), vp, sz, i, i, C.POINTER(BatchStats)]
-        L.hvc_yuv_to_rgb_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), C.POINTER(sz), i, i]
-        L.hvc_decode_frames_mixed_rgb.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), C.POINTER(sz), i, i]
-        L.hvc_jpeg_decode_batch_mixed_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, ip, C.POINTER(i), C.POINTER(sz),
-                                                      C.POINTER(sz), vp, sz, i, i, C.POINTER(BatchStats)]
-        L.hvc_rgb_resize_mixed.argtypes = [vp, vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(i), C.POINTER(i), i, vp, C.POINTER(sz),
-                                           C.POINTER(sz), C.POINTER(i), C.POINTER(i), i, i, i]
-        L.hvc_jpeg_decode_batch_mixed_resized.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, i, sz, i, ip, C.POINTER(i), C.POINTER(i),
-                                                          C.POINTER(i), C.POINTER(sz), C.POINTER(sz), vp, sz, i, i, i,
-                                                          C.POINTER(BatchStats)]
-        L.hvc_rgb_resize_mixed_opts.argtypes = L.hvc_rgb_resize_mixed.argtypes + [C.POINTER(ResizeOpts)]
-        L.hvc_jpeg_decode_batch_mixed_resized_opts.argtypes = L.hvc_jpeg_decode_batch_mixed_resized.argtypes + [C.POINTER(ResizeOpts)]
-        L.hvc_normalize_lut.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), i, vp]
-        L.hvc_jpeg_encoder_mixed_layout.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, sz, ip, C.POINTER(i),
-                                                    C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
-        L.hvc_encode_frames_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), i]
-        L.hvc_jpeg_encode_batch_mixed.argtypes = [vp, C.POINTER(vp), ip, C.POINTER(i), i, i, sz, C.POINTER(vp), C.POINTER(sz),
-                                                  C.POINTER(sz), C.POINTER(BatchStats)]
-        L.hvc_huffman_encode_frames_mixed.argtypes = [vp, ip, vp, C.POINTER(sz), i, i, vp, sz, vp, C.POINTER(i), hs, i]
-        L.hvc_jpeg_encode_batch_mixed_gpu.argtypes = L.hvc_jpeg_encode_batch_mixed.argtypes
-        L.hvc_jpeg_encoder_mixed_rgb_layout.argtypes = [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, i, sz, sz, ip,
-                                                        C.POINTER(i), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
-                                                        C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
-        L.hvc_rgb_to_yuv_mixed.argtypes = [vp, vp, C.POINTER(sz), ip, i, vp, C.POINTER(sz), C.POINTER(sz), i, i]
-        L.hvc_encode_frames_mixed_rgb.argtypes = [vp, vp, C.POINTER(sz), C.POINTER(sz), i, ip, i, vp, C.POINTER(sz), i]
-        L.hvc_jpeg_encode_batch_mixed_rgb.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i, ip, C.POINTER(i), i, i, sz, C.POINTER(vp),
-                                                      C.POINTER(sz), C.POINTER(sz), C.POINTER(BatchStats)]
-        L.hvc_jpeg_encode_batch_mixed_rgb_gpu.argtypes = L.hvc_jpeg_encode_batch_mixed_rgb.argtypes
-        L.hvc_last_mixed_coder_files.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        L.hvc_checksum_records.argtypes = [vp, vp, sz, sz, i, vp, i]
-        L.hvc_set_host_cpus.argtypes = [vp, C.c_char_p]
-        L.hvc_get_host_cpus.argtypes = [vp, C.c_char_p, sz, C.POINTER(i)]
-        L.hvc_host_threads.argtypes = [vp, C.POINTER(i), C.POINTER(C.c_uint64)]
-        L.hvc_host_threads_probe.argtypes = [i]
-        L.hvc_encode_frames_recon.argtypes = [vp, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, vp, vp, i]
-        L.hvc_host_alloc.argtypes = [vp, sz, C.POINTER(vp)]
-        L.hvc_host_free.argtypes = [vp, vp]
-        L.hvc_host_register.argtypes = [vp, vp, sz]
-        L.hvc_host_unregister.argtypes = [vp, vp]
-        L.hvc_decode_frames_submit.argtypes = [vp, i, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
-        L.hvc_encode_frames_submit.argtypes = [vp, i, vp, sz, vp, i, C.POINTER(Component), i, i, vp, sz, i]
-        L.hvc_wait.argtypes = [vp, i]
-        L.hvc_slot_query.argtypes = [vp, i, C.POINTER(i)]
-        L.hvc_slot_last_stats.argtypes = [vp, i, C.POINTER(SlotStats)]
-        L.hvc_huffman_code_tables.argtypes = [vp, i, i, vp]
-        L.hvc_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
-        L.hvc_device_free.argtypes = [vp, vp]
-        L.hvc_memcpy_h2d.argtypes = [vp, vp, vp, sz]
-        L.hvc_memcpy_d2h.argtypes = [vp, vp, vp, sz]
+        for name, proto in PROTOTYPES.items():
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                raise ImportError("%s lacks %s, which include/hvc_jpeg.h declares: rebuild it from this tree" % (_SO, name))
+            fn.argtypes = proto[0]
+            if len(proto) > 1:
+                fn.restype = proto[1]
         _LIB = L
     return _LIB
 
@@ -370,17 +359,21 @@ def kernel_source_id():
     return h.hexdigest()[:12]
 
 
+def _enum(table, v):
+    """a name of `table`, or the number itself"""
+    return table[v] if isinstance(v, str) else int(v)
+
+
 def _rgb_layout(layout):
-    return HVC_RGB[layout] if isinstance(layout, str) else int(layout)
+    return _enum(HVC_RGB, layout)
 
 
 def _resize_filter(filter):
-    return HVC_RESIZE[filter] if isinstance(filter, str) else int(filter)
+    return _enum(HVC_RESIZE, filter)
 
 
-class ResizeOpts(C.Structure):
-    """hvc_resize_opts: a box and a mirror flag per image, a typed output through a table"""
-    _fields_ = [("boxes", C.POINTER(C.c_float)), ("mirror", C.POINTER(C.c_uint8)), ("out_elem", C.c_int), ("lut", C.c_void_p)]
+ARITH_NAMES = {v: k for k, v in HVC_ARITH.items()}   # what the getters answer: the name, or the number where it has none
+HUFF_NAMES = {v: k for k, v in HVC_HUFF.items()}
 
 
 def elem_name(dtype):
@@ -475,22 +468,46 @@ def _addr(x):
     raise TypeError(type(x))
 
 
+def _same_space(a, a_name, b, b_name):
+    """(address of a, address of b, where) of two buffers a call takes in ONE memory space"""
+    aa, w1 = _addr(a)
+    ba, w2 = _addr(b)
+    assert w1 == w2, "%s and %s must live in the same memory space" % (a_name, b_name)
+    return aa, ba, w1
+
+
+def _infos_array(infos):
+    """a list of JpegInfo as the ctypes array a call takes (never of length 0: the array of an empty set is one unused entry)"""
+    return infos if isinstance(infos, C.Array) else (JpegInfo * max(len(infos), 1))(*infos)
+
+
+def _zeroed_bytes(n, device):
+    """the zero-filled buffer a batch call decodes into when the caller brings none: n bytes (8 at least), a torch cuda tensor
+    with `device`, a numpy array without"""
+    if device:
+        import torch
+        return torch.zeros(max(n, 8), dtype=torch.uint8, device="cuda")
+    return np.zeros(max(n, 8), dtype=np.uint8)
+
+
+def _flat_bytes(frames):
+    """raw frames (bytes / bytearray / uint8 arrays of any shape) as flat uint8 arrays, without a copy where none is needed"""
+    return [np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray)) else
+            np.ascontiguousarray(f, dtype=np.uint8).reshape(-1) for f in frames]
+
+
+def _capacity(buf):
+    """the elements of a numpy array or a torch tensor"""
+    return buf.numel() if hasattr(buf, "numel") else buf.size
+
+
 HVC_DCT = {"forward": 0, "inverse": 1, "round_trip": 2}   # HVC_DCT_FORWARD / _INVERSE / _ROUND_TRIP
 DCT_ROM_PREC_MAX, DCT_TP_MAX = 16, 8                      # hvc_dct_spec.h
 DCT_FWD_IN_MAX, DCT_INV_IN_MAX = 2048, 32768
 
 
-class DctConfig(C.Structure):
-    _fields_ = [("mode", C.c_int), ("fwd_rom_prec", C.c_int), ("fwd_transpose_prec", C.c_int), ("inv_rom_prec", C.c_int),
-                ("inv_transpose_prec", C.c_int)]
-
-
-class DctError(C.Structure):
-    _fields_ = [("max_error", C.c_double), ("worst_block", C.c_uint64)]
-
-
 def _dct_direction(d):
-    return HVC_DCT[d] if isinstance(d, str) else int(d)
+    return _enum(HVC_DCT, d)
 
 
 def dct_rom(rom_prec):
@@ -611,25 +628,41 @@ def jpeg_read_header(data: bytes):
     return info
 
 
-class MixedLayout:
-    """what hvc_jpeg_mixed_layout makes of a list of files: infos (ctypes array of JpegInfo), status and pixel_offsets (ctypes
-    arrays, one entry per file) and total_bytes -- the size of the buffer that holds every good file's pixel record"""
+class _FileSetLayout:
+    """what the four hvc_jpeg_mixed*_layout calls make of a list of files, the part they share: jpegs (the files), ptrs and
+    sizes (ctypes arrays: what the batch calls take), infos (ctypes array of JpegInfo), status (ctypes array, one hvc_status
+    per file) and total_bytes; len() = the number of files.  Each class names its call, the arguments between n_files and
+    infos, and the size_t arrays the call fills behind status."""
 
-    def __init__(self, jpegs, align=0):
+    def _lay_out(self, name, jpegs, middle, arrays, scaled=False):
+        """name(ptrs, sizes, n, *middle, infos, [scaled,] status, *arrays, &total_bytes)"""
         n = len(jpegs)
         self.jpegs = list(jpegs)
         self.ptrs = (C.c_void_p * n)(*[C.cast(C.c_char_p(j), C.c_void_p) for j in self.jpegs])
         self.sizes = (C.c_size_t * n)(*[len(j) for j in self.jpegs])
         self.infos = (JpegInfo * n)()
+        out_infos = [self.infos]
+        if scaled:
+            self.scaled = (JpegInfo * n)()
+            out_infos.append(self.scaled)
         self.status = (C.c_int * n)()
-        self.pixel_offsets = (C.c_size_t * n)()
+        for a in arrays:
+            setattr(self, a, (C.c_size_t * n)())
         total = C.c_size_t(0)
-        _chk(lib().hvc_jpeg_mixed_layout(self.ptrs, self.sizes, n, align, self.infos, self.status, self.pixel_offsets,
-                                         C.byref(total)), "hvc_jpeg_mixed_layout")
+        _chk(getattr(lib(), name)(self.ptrs, self.sizes, n, *middle, *out_infos, self.status, *[getattr(self, a) for a in arrays],
+                                  C.byref(total)), name)
         self.total_bytes = total.value
 
     def __len__(self):
         return len(self.jpegs)
+
+
+class MixedLayout(_FileSetLayout):
+    """what hvc_jpeg_mixed_layout makes of a list of files: infos (ctypes array of JpegInfo), status and pixel_offsets (ctypes
+    arrays, one entry per file) and total_bytes -- the size of the buffer that holds every good file's pixel record"""
+
+    def __init__(self, jpegs, align=0):
+        self._lay_out("hvc_jpeg_mixed_layout", jpegs, (align,), ("pixel_offsets",))
 
 
 def mixed_coef_offsets(layout):
@@ -649,28 +682,14 @@ def jpeg_mixed_layout(jpegs, align=0):
     return MixedLayout(jpegs, align)
 
 
-class MixedRgbLayout:
+class MixedRgbLayout(_FileSetLayout):
     """what hvc_jpeg_mixed_rgb_layout makes of a list of files: infos, status (nonzero also for a sampling without an RGB
     image), rgb_offsets and rgb_row_strides (ctypes arrays, one entry per file) and total_bytes -- the size of the buffer
     that holds every good file's RGB image"""
 
     def __init__(self, jpegs, layout="interleaved", align=0, row_align=0):
-        n = len(jpegs)
-        self.jpegs = list(jpegs)
         self.layout = _rgb_layout(layout)
-        self.ptrs = (C.c_void_p * n)(*[C.cast(C.c_char_p(j), C.c_void_p) for j in self.jpegs])
-        self.sizes = (C.c_size_t * n)(*[len(j) for j in self.jpegs])
-        self.infos = (JpegInfo * n)()
-        self.status = (C.c_int * n)()
-        self.rgb_offsets = (C.c_size_t * n)()
-        self.rgb_row_strides = (C.c_size_t * n)()
-        total = C.c_size_t(0)
-        _chk(lib().hvc_jpeg_mixed_rgb_layout(self.ptrs, self.sizes, n, self.layout, align, row_align, self.infos, self.status,
-                                             self.rgb_offsets, self.rgb_row_strides, C.byref(total)), "hvc_jpeg_mixed_rgb_layout")
-        self.total_bytes = total.value
-
-    def __len__(self):
-        return len(self.jpegs)
+        self._lay_out("hvc_jpeg_mixed_rgb_layout", jpegs, (self.layout, align, row_align), ("rgb_offsets", "rgb_row_strides"))
 
 
 def jpeg_mixed_rgb_layout(jpegs, layout="interleaved", align=0, row_align=0):
@@ -678,28 +697,14 @@ def jpeg_mixed_rgb_layout(jpegs, layout="interleaved", align=0, row_align=0):
     return MixedRgbLayout(jpegs, layout, align, row_align)
 
 
-class MixedScaledLayout:
+class MixedScaledLayout(_FileSetLayout):
     """what hvc_jpeg_mixed_scaled_layout makes of a list of files: infos (FULL-size: the batch call's input), scaled (the infos
     of the output records), status, pixel_offsets and total_bytes -- the size of the buffer that holds every good file's
     scaled pixel record"""
 
     def __init__(self, jpegs, scale_denom, align=0):
-        n = len(jpegs)
-        self.jpegs = list(jpegs)
         self.scale_denom = int(scale_denom)
-        self.ptrs = (C.c_void_p * n)(*[C.cast(C.c_char_p(j), C.c_void_p) for j in self.jpegs])
-        self.sizes = (C.c_size_t * n)(*[len(j) for j in self.jpegs])
-        self.infos = (JpegInfo * n)()
-        self.scaled = (JpegInfo * n)()
-        self.status = (C.c_int * n)()
-        self.pixel_offsets = (C.c_size_t * n)()
-        total = C.c_size_t(0)
-        _chk(lib().hvc_jpeg_mixed_scaled_layout(self.ptrs, self.sizes, n, self.scale_denom, align, self.infos, self.scaled, self.status,
-                                                self.pixel_offsets, C.byref(total)), "hvc_jpeg_mixed_scaled_layout")
-        self.total_bytes = total.value
-
-    def __len__(self):
-        return len(self.jpegs)
+        self._lay_out("hvc_jpeg_mixed_scaled_layout", jpegs, (self.scale_denom, align), ("pixel_offsets",), scaled=True)
 
 
 def jpeg_mixed_scaled_layout(jpegs, scale_denom, align=0):
@@ -707,30 +712,15 @@ def jpeg_mixed_scaled_layout(jpegs, scale_denom, align=0):
     return MixedScaledLayout(jpegs, scale_denom, align)
 
 
-class MixedScaledRgbLayout:
+class MixedScaledRgbLayout(_FileSetLayout):
     """what hvc_jpeg_mixed_scaled_rgb_layout makes of a list of files: infos (FULL-size), scaled (image f is scaled[f].width x
     .height), status, rgb_offsets, rgb_row_strides and total_bytes"""
 
     def __init__(self, jpegs, scale_denom, layout="interleaved", align=0, row_align=0):
-        n = len(jpegs)
-        self.jpegs = list(jpegs)
         self.scale_denom = int(scale_denom)
         self.layout = _rgb_layout(layout)
-        self.ptrs = (C.c_void_p * n)(*[C.cast(C.c_char_p(j), C.c_void_p) for j in self.jpegs])
-        self.sizes = (C.c_size_t * n)(*[len(j) for j in self.jpegs])
-        self.infos = (JpegInfo * n)()
-        self.scaled = (JpegInfo * n)()
-        self.status = (C.c_int * n)()
-        self.rgb_offsets = (C.c_size_t * n)()
-        self.rgb_row_strides = (C.c_size_t * n)()
-        total = C.c_size_t(0)
-        _chk(lib().hvc_jpeg_mixed_scaled_rgb_layout(self.ptrs, self.sizes, n, self.scale_denom, self.layout, align, row_align, self.infos,
-                                                    self.scaled, self.status, self.rgb_offsets, self.rgb_row_strides, C.byref(total)),
-             "hvc_jpeg_mixed_scaled_rgb_layout")
-        self.total_bytes = total.value
-
-    def __len__(self):
-        return len(self.jpegs)
+        self._lay_out("hvc_jpeg_mixed_scaled_rgb_layout", jpegs, (self.scale_denom, self.layout, align, row_align),
+                      ("rgb_offsets", "rgb_row_strides"), scaled=True)
 
 
 def jpeg_mixed_scaled_rgb_layout(jpegs, scale_denom, layout="interleaved", align=0, row_align=0):
@@ -901,18 +891,22 @@ class EncoderMixedLayout:
     elements) of the good frames' records, pixel_total and coef_total"""
 
     def __init__(self, frames, align=0):
-        n = len(frames)
-        m = max(n, 1)
-        col = lambda k: (C.c_int * m)(*[int(f[k]) for f in frames])
-        self.n = n
-        self.infos = (JpegInfo * m)()
-        self.status = (C.c_int * m)()
-        self.pixel_offsets = (C.c_size_t * m)()
-        self.coef_offsets = (C.c_size_t * m)()
+        cols = self._columns(frames, ("pixel_offsets", "coef_offsets"))
         pt, ct = C.c_size_t(), C.c_size_t()
-        _chk(lib().hvc_jpeg_encoder_mixed_layout(col(0), col(1), col(2), col(3), n, align, self.infos, self.status, self.pixel_offsets,
+        _chk(lib().hvc_jpeg_encoder_mixed_layout(*cols, self.n, align, self.infos, self.status, self.pixel_offsets,
                                                  self.coef_offsets, C.byref(pt), C.byref(ct)), "hvc_jpeg_encoder_mixed_layout")
         self.pixel_total, self.coef_total = pt.value, ct.value
+
+    def _columns(self, frames, arrays):
+        """widths, heights, chromas, qualities of `frames` as int arrays; sets n, infos, status and the size_t `arrays`, every
+        array max(n, 1) long"""
+        self.n = len(frames)
+        m = max(self.n, 1)
+        self.infos = (JpegInfo * m)()
+        self.status = (C.c_int * m)()
+        for a in arrays:
+            setattr(self, a, (C.c_size_t * m)())
+        return [(C.c_int * m)(*[int(f[k]) for f in frames]) for k in range(4)]
 
     def __len__(self):
         return self.n
@@ -929,21 +923,12 @@ class EncoderMixedRgbLayout(EncoderMixedLayout):
     rgb_row_strides, total_bytes (rgb_total), for one `layout` ("interleaved" / "planar")"""
 
     def __init__(self, frames, layout="interleaved", align=0, row_align=0):
-        n = len(frames)
-        m = max(n, 1)
-        col = lambda k: (C.c_int * m)(*[int(f[k]) for f in frames])
-        self.n = n
+        cols = self._columns(frames, ("rgb_offsets", "rgb_row_strides", "pixel_offsets", "coef_offsets"))
         self.layout = _rgb_layout(layout)
-        self.infos = (JpegInfo * m)()
-        self.status = (C.c_int * m)()
-        self.rgb_offsets = (C.c_size_t * m)()
-        self.rgb_row_strides = (C.c_size_t * m)()
-        self.pixel_offsets = (C.c_size_t * m)()
-        self.coef_offsets = (C.c_size_t * m)()
         rt, pt, ct = C.c_size_t(), C.c_size_t(), C.c_size_t()
-        _chk(lib().hvc_jpeg_encoder_mixed_rgb_layout(col(0), col(1), col(2), col(3), n, self.layout, align, row_align, self.infos,
-                                                     self.status, self.rgb_offsets, self.rgb_row_strides, C.byref(rt),
-                                                     self.pixel_offsets, self.coef_offsets, C.byref(pt), C.byref(ct)),
+        _chk(lib().hvc_jpeg_encoder_mixed_rgb_layout(*cols, self.n, self.layout, align, row_align, self.infos, self.status,
+                                                     self.rgb_offsets, self.rgb_row_strides, C.byref(rt), self.pixel_offsets,
+                                                     self.coef_offsets, C.byref(pt), C.byref(ct)),
              "hvc_jpeg_encoder_mixed_rgb_layout")
         self.total_bytes = self.rgb_total = rt.value
         self.pixel_total, self.coef_total = pt.value, ct.value
@@ -970,11 +955,13 @@ def encoder_pixel_record(info, y, u, v, width, height, chroma):
 
 def restart_slack(info, restart_interval):
     """bytes a restart interval adds to a file at most: 3 per interval (pad byte + marker) and the 6 of DRI"""
-    if not restart_interval:
-        return 0
     c0 = info.comp[0]
-    mcus = (c0.decoded_width // (8 * max(c0.hscale, 1))) * (c0.decoded_height // (8 * max(c0.vscale, 1)))
-    return 3 * -(-mcus // int(restart_interval)) + 6
+    return _interval_slack((c0.decoded_width // (8 * max(c0.hscale, 1))) * (c0.decoded_height // (8 * max(c0.vscale, 1))),
+                           restart_interval)
+
+
+def _interval_slack(mcus, restart_interval):
+    return 3 * -(-mcus // int(restart_interval)) + 6 if restart_interval else 0
 
 
 def jpeg_entropy_encode(info, coefs, specs=None, restart_interval=0):
@@ -1029,7 +1016,6 @@ class Context:
 
     def reset_stream(self):
         """back to the context's own (non-blocking) stream"""
-        lib().hvc_reset_stream.argtypes = [C.c_void_p]
         _chk(lib().hvc_reset_stream(self._h))
 
     def synchronize(self):
@@ -1062,18 +1048,26 @@ class Context:
         """the extension: the context's file-level entry points honour DRI / RSTn (default off = the model's behaviour)"""
         _chk(lib().hvc_set_restart_markers(self._h, 1 if honour else 0), "hvc_set_restart_markers")
 
+    def _set(self, name, table, v):
+        """hvc_set_*(ctx, a name of `table` or the number itself)"""
+        _chk(getattr(lib(), name)(self._h, _enum(table, v)), name)
+
+    def _get(self, name, start=0):
+        """hvc_get_*(ctx, &int) -> the int"""
+        v = C.c_int(start)
+        _chk(getattr(lib(), name)(self._h, C.byref(v)), name)
+        return v.value
+
     def set_arithmetic(self, arith):
         """"model" (default: the OCaml model's decoder) | "hardcaml" (the reference's RTL decoder datapath, bit for bit) |
         "libjpeg" (libjpeg's islow inverse DCT and, in the RGB forms, its fancy upsampling, bit for bit): the block stage
         of every decode entry point except the fused 4:4:4, scaled and mixed ones, which refuse anything but "model"."""
-        _chk(lib().hvc_set_arithmetic(self._h, HVC_ARITH[arith] if isinstance(arith, str) else int(arith)),
-             "hvc_set_arithmetic")
+        self._set("hvc_set_arithmetic", HVC_ARITH, arith)
 
     @property
     def arithmetic(self):
-        v = C.c_int()
-        _chk(lib().hvc_get_arithmetic(self._h, C.byref(v)), "hvc_get_arithmetic")
-        return {b: a for a, b in HVC_ARITH.items()}.get(v.value, v.value)
+        v = self._get("hvc_get_arithmetic")
+        return ARITH_NAMES.get(v, v)
 
     def set_mixed_arithmetic(self, arith):
         """hvc_set_mixed_arithmetic: "model" (default) | "libjpeg" -- the mixed decode calls' own setting.  Under "libjpeg"
@@ -1081,14 +1075,12 @@ class Context:
         at full size give libjpeg's pixels (what jpeg_decode / jpeg_decode_rgb give per file under set_arithmetic("libjpeg"))
         whatever set_arithmetic says, and the reduced-size forms are refused.  Anything else ("hardcaml" included) is an error
         and leaves the setting as it was."""
-        _chk(lib().hvc_set_mixed_arithmetic(self._h, HVC_ARITH[arith] if isinstance(arith, str) else int(arith)),
-             "hvc_set_mixed_arithmetic")
+        self._set("hvc_set_mixed_arithmetic", HVC_ARITH, arith)
 
     @property
     def mixed_arithmetic(self):
-        v = C.c_int()
-        _chk(lib().hvc_get_mixed_arithmetic(self._h, C.byref(v)), "hvc_get_mixed_arithmetic")
-        return {b: a for a, b in HVC_ARITH.items()}.get(v.value, v.value)
+        v = self._get("hvc_get_mixed_arithmetic")
+        return ARITH_NAMES.get(v, v)
 
     def decode_divergence(self, coefs, coef_frame_stride, qtabs, comps, n_frames, max_diff=None, diff_frame_stride=None):
         """max |model - hardcaml| per block (hvc_decode_frames_divergence) -> uint8 array [n_frames, blocks per frame]
@@ -1146,14 +1138,12 @@ class Context:
     def set_encode_arithmetic(self, arith):
         """"model" (default: the OCaml model's encoder) | "hardcaml" (the reference's RTL encoder DCT and quantiser, bit
         for bit): the block stage of every encode entry point.  Independent of set_arithmetic."""
-        _chk(lib().hvc_set_encode_arithmetic(self._h, HVC_ARITH[arith] if isinstance(arith, str) else int(arith)),
-             "hvc_set_encode_arithmetic")
+        self._set("hvc_set_encode_arithmetic", HVC_ARITH, arith)
 
     @property
     def encode_arithmetic(self):
-        v = C.c_int()
-        _chk(lib().hvc_get_encode_arithmetic(self._h, C.byref(v)), "hvc_get_encode_arithmetic")
-        return {b: a for a, b in HVC_ARITH.items()}.get(v.value, v.value)
+        v = self._get("hvc_get_encode_arithmetic")
+        return ARITH_NAMES.get(v, v)
 
     def set_encode_libjpeg(self, on=True):
         """hvc_set_encode_libjpeg: the encoder bit-exact to libjpeg-turbo (jfdctint.c's forward DCT, its rounded division,
@@ -1166,15 +1156,12 @@ class Context:
 
     @property
     def encode_libjpeg(self):
-        v = C.c_int()
-        _chk(lib().hvc_get_encode_libjpeg(self._h, C.byref(v)), "hvc_get_encode_libjpeg")
-        return bool(v.value)
+        return bool(self._get("hvc_get_encode_libjpeg"))
 
     def set_huffman_tables(self, which):
         """"default" (the Annex K tables, every byte as before) | "optimised" (each file's own Annex K.2 tables): the files of
         jpeg_encode and jpeg_encode_batch (both coders).  Independent of set_encode_arithmetic."""
-        _chk(lib().hvc_set_huffman_tables(self._h, HVC_HUFF[which] if isinstance(which, str) else int(which)),
-             "hvc_set_huffman_tables")
+        self._set("hvc_set_huffman_tables", HVC_HUFF, which)
 
     def set_restart_interval(self, mcus):
         """0 (default: no DRI, no RSTn, every byte as before) | 1 .. 65535: the files of jpeg_encode and jpeg_encode_batch
@@ -1184,15 +1171,12 @@ class Context:
 
     @property
     def restart_interval(self):
-        v = C.c_int()
-        _chk(lib().hvc_get_restart_interval(self._h, C.byref(v)), "hvc_get_restart_interval")
-        return v.value
+        return self._get("hvc_get_restart_interval")
 
     @property
     def huffman_tables(self):
-        v = C.c_int()
-        _chk(lib().hvc_get_huffman_tables(self._h, C.byref(v)), "hvc_get_huffman_tables")
-        return {b: a for a, b in HVC_HUFF.items()}.get(v.value, v.value)
+        v = self._get("hvc_get_huffman_tables")
+        return HUFF_NAMES.get(v, v)
 
     def encode_divergence(self, pixels, pixel_frame_stride, qtabs, comps, n_frames, max_diff=None, diff_frame_stride=None):
         """min(255, max |q_model - q_hardcaml|) per block (hvc_encode_frames_divergence) -> uint8 array [n_frames, blocks
@@ -1213,7 +1197,6 @@ class Context:
 
     def set_decode_kernel(self, which):
         """0 packed (default) | 1 unpacked int32 | 2 int64 for every block -- identical output"""
-        lib().hvc_set_decode_kernel.argtypes = [C.c_void_p, C.c_int]
         _chk(lib().hvc_set_decode_kernel(self._h, which))
 
     def set_profiling(self, on=True):
@@ -1313,9 +1296,7 @@ class Context:
     # -- decode -------------------------------------------------------------
     def dequant_idct_recon(self, coefs, qtab, blocks_w, blocks_h, n_planes, plane, stride=None,
                            coef_plane_stride=0, plane_stride=0):
-        ca, w1 = _addr(coefs)
-        pa, w2 = _addr(plane)
-        assert w1 == w2, "coefs and plane must live in the same memory space"
+        ca, pa, w1 = _same_space(coefs, "coefs", plane, "plane")
         q = np.ascontiguousarray(qtab, dtype=np.uint16)
         assert q.size == 64
         _chk(lib().hvc_dequant_idct_recon(self._h, ca, coef_plane_stride, q.ctypes.data, blocks_w, blocks_h,
@@ -1334,14 +1315,37 @@ class Context:
         """hvc_decode_frames_mixed: frame f = infos[f] (JpegInfo: layout and tables), its coefficient record at
         coefs[coef_offsets[f]:] (int16 elements), its pixel record at pixels[pixel_offsets[f]:] (bytes).  coefs / pixels:
         numpy (host) or torch cuda tensors, both in the same memory space."""
-        ca, w1 = _addr(coefs)
-        pa, w2 = _addr(pixels)
-        assert w1 == w2, "coefs and pixels must live in the same memory space"
+        ca, pa, w1 = _same_space(coefs, "coefs", pixels, "pixels")
         n = len(infos)
-        arr = infos if isinstance(infos, C.Array) else (JpegInfo * n)(*infos)
-        co = coef_offsets if isinstance(coef_offsets, C.Array) else (C.c_size_t * n)(*[int(x) for x in coef_offsets])
-        po = pixel_offsets if isinstance(pixel_offsets, C.Array) else (C.c_size_t * n)(*[int(x) for x in pixel_offsets])
-        _chk(lib().hvc_decode_frames_mixed(self._h, ca, co, arr, n, pa, po, w1), "hvc_decode_frames_mixed")
+        _chk(lib().hvc_decode_frames_mixed(self._h, ca, _size_array(coef_offsets, n), _infos_array(infos), n, pa,
+                                           _size_array(pixel_offsets, n), w1), "hvc_decode_frames_mixed")
+
+    def _decode_batch_mixed(self, name, lay, buf, device, middle, out_infos, image):
+        """the tail of the four mixed batch decode calls: name(ctx, files, n, *middle, infos, status, offsets, buf, capacity,
+        [layout,] where, stats) into buf (None: made here, zero-filled, on the device with `device`), the stats into
+        self.last_batch_stats, and one (status, info, view) per file -- info = out_infos[f] (lay.infos or lay.scaled), None for a
+        file the layout refused; view = the planes of info (a file the layout took), or, with `image`, the RGB image (a file that
+        decoded and has a size), else None"""
+        n = len(lay)
+        if buf is None:
+            buf = _zeroed_bytes(lay.total_bytes, device)
+        addr, where = _addr(buf)
+        st = BatchStats()
+        status = (C.c_int * n)(*lay.status)
+        tail = (lay.rgb_offsets, lay.rgb_row_strides, addr, _capacity(buf), lay.layout) if image else \
+               (lay.pixel_offsets, addr, _capacity(buf))
+        _chk(getattr(lib(), name)(self._h, lay.ptrs, lay.sizes, n, *middle, lay.infos, status, *tail, where, C.byref(st)), name)
+        self.last_batch_stats = st
+        out = []
+        for f in range(n):
+            info, view = (out_infos[f] if lay.status[f] == 0 else None), None
+            if info is not None and not image:
+                off = lay.pixel_offsets[f]
+                view = info.planes(buf[off:off + info.pixel_bytes])
+            elif info is not None and status[f] == 0 and info.width > 0 and info.height > 0:
+                view = rgb_view(buf, lay.rgb_offsets[f], lay.rgb_row_strides[f], info.width, info.height, lay.layout)
+            out.append((status[f], info, view))
+        return out
 
     def jpeg_decode_batch_mixed(self, jpegs, threads=8, chunk_bytes=0, device=False, layout=None, pixels=None):
         """Files of any sizes, samplings and tables in one call.  Returns one (status, info, planes) per file: status = the file's
@@ -1349,52 +1353,25 @@ class Context:
         device=True), None for a file whose header could not be read.  layout / pixels: a MixedLayout made before and a buffer of
         layout.total_bytes to decode into (default: made here, zero-filled).  The call's hvc_batch_stats: self.last_batch_stats."""
         lay = layout if layout is not None else MixedLayout(jpegs)
-        n = len(lay)
-        if pixels is None:
-            if device:
-                import torch
-                pixels = torch.zeros(max(lay.total_bytes, 8), dtype=torch.uint8, device="cuda")
-            else:
-                pixels = np.zeros(max(lay.total_bytes, 8), dtype=np.uint8)
-        pa, where = _addr(pixels)
-        cap = pixels.numel() if hasattr(pixels, "numel") else pixels.size
-        st = BatchStats()
-        status = (C.c_int * n)(*lay.status)
-        _chk(lib().hvc_jpeg_decode_batch_mixed(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, lay.infos, status,
-                                               lay.pixel_offsets, pa, cap, where, C.byref(st)), "hvc_jpeg_decode_batch_mixed")
-        self.last_batch_stats = st
-        out = []
-        for f in range(n):
-            if lay.status[f] != 0:
-                out.append((status[f], None, None))
-                continue
-            info, off = lay.infos[f], lay.pixel_offsets[f]
-            out.append((status[f], info, info.planes(pixels[off:off + info.pixel_bytes])))
-        return out
+        return self._decode_batch_mixed("hvc_jpeg_decode_batch_mixed", lay, pixels, device, (threads, chunk_bytes), lay.infos, False)
 
     def yuv_to_rgb_mixed(self, yuv, yuv_offsets, infos, rgb, rgb_offsets, rgb_row_strides=None, layout="interleaved"):
         """hvc_yuv_to_rgb_mixed: the colour pass over images of any size and sampling in one launch.  Frame f = infos[f]
         (JpegInfo: width, height, sampling factors, layout), its planes at yuv[yuv_offsets[f]:], its image at
         rgb[rgb_offsets[f]:] with rows rgb_row_strides[f] apart (None: tight).  yuv / rgb: numpy (host) or torch cuda
         tensors of bytes, both in the same memory space."""
-        ya, w1 = _addr(yuv)
-        ra, w2 = _addr(rgb)
-        assert w1 == w2, "yuv and rgb must live in the same memory space"
+        ya, ra, w1 = _same_space(yuv, "yuv", rgb, "rgb")
         n = len(infos)
-        arr = infos if isinstance(infos, C.Array) else (JpegInfo * n)(*infos)
-        _chk(lib().hvc_yuv_to_rgb_mixed(self._h, ya, _size_array(yuv_offsets, n), arr, n, ra, _size_array(rgb_offsets, n),
+        _chk(lib().hvc_yuv_to_rgb_mixed(self._h, ya, _size_array(yuv_offsets, n), _infos_array(infos), n, ra, _size_array(rgb_offsets, n),
                                         _size_array(rgb_row_strides, n), _rgb_layout(layout), w1), "hvc_yuv_to_rgb_mixed")
 
     def rgb_to_yuv_mixed(self, yuv, yuv_offsets, infos, rgb, rgb_offsets, rgb_row_strides=None, layout="interleaved"):
         """hvc_rgb_to_yuv_mixed: the way back of yuv_to_rgb_mixed, argument for argument: frame f's image at rgb[rgb_offsets[f]:]
         is read, its planes at yuv[yuv_offsets[f]:] (laid out by infos[f].layout) are written -- the frame's own samples only.
         Sizes are even where the sampling asks for it (hvc_rgb_to_yuv's rule)."""
-        ya, w1 = _addr(yuv)
-        ra, w2 = _addr(rgb)
-        assert w1 == w2, "yuv and rgb must live in the same memory space"
+        ya, ra, w1 = _same_space(yuv, "yuv", rgb, "rgb")
         n = len(infos)
-        arr = infos if isinstance(infos, C.Array) else (JpegInfo * max(n, 1))(*infos)
-        _chk(lib().hvc_rgb_to_yuv_mixed(self._h, ya, _size_array(yuv_offsets, n), arr, n, ra, _size_array(rgb_offsets, n),
+        _chk(lib().hvc_rgb_to_yuv_mixed(self._h, ya, _size_array(yuv_offsets, n), _infos_array(infos), n, ra, _size_array(rgb_offsets, n),
                                         _size_array(rgb_row_strides, n), _rgb_layout(layout), w1), "hvc_rgb_to_yuv_mixed")
 
     def encode_frames_mixed_rgb(self, rgb, rgb_offsets, infos, coefs, coef_offsets, rgb_row_strides=None, layout="interleaved"):
@@ -1402,24 +1379,18 @@ class Context:
         rgb_row_strides[f] apart, None: tight), its coefficient record written at coefs[coef_offsets[f]:] (int16 elements): the
         mixed colour pass into zeroed padded planes in context scratch, then the mixed block stage.  rgb / coefs: numpy (host)
         or torch cuda tensors, both in the same memory space."""
-        ra, w1 = _addr(rgb)
-        ca, w2 = _addr(coefs)
-        assert w1 == w2, "rgb and coefs must live in the same memory space"
+        ra, ca, w1 = _same_space(rgb, "rgb", coefs, "coefs")
         n = len(infos)
-        arr = infos if isinstance(infos, C.Array) else (JpegInfo * max(n, 1))(*infos)
         _chk(lib().hvc_encode_frames_mixed_rgb(self._h, ra, _size_array(rgb_offsets, n), _size_array(rgb_row_strides, n),
-                                               _rgb_layout(layout), arr, n, ca, _size_array(coef_offsets, n), w1),
+                                               _rgb_layout(layout), _infos_array(infos), n, ca, _size_array(coef_offsets, n), w1),
              "hvc_encode_frames_mixed_rgb")
 
     def decode_frames_mixed_rgb(self, coefs, coef_offsets, infos, rgb, rgb_offsets, rgb_row_strides=None, layout="interleaved"):
         """hvc_decode_frames_mixed_rgb: hvc_decode_frames_mixed into context scratch, then the mixed colour pass; arguments as
         decode_frames_mixed and yuv_to_rgb_mixed."""
-        ca, w1 = _addr(coefs)
-        ra, w2 = _addr(rgb)
-        assert w1 == w2, "coefs and rgb must live in the same memory space"
+        ca, ra, w1 = _same_space(coefs, "coefs", rgb, "rgb")
         n = len(infos)
-        arr = infos if isinstance(infos, C.Array) else (JpegInfo * n)(*infos)
-        _chk(lib().hvc_decode_frames_mixed_rgb(self._h, ca, _size_array(coef_offsets, n), arr, n, ra, _size_array(rgb_offsets, n),
+        _chk(lib().hvc_decode_frames_mixed_rgb(self._h, ca, _size_array(coef_offsets, n), _infos_array(infos), n, ra, _size_array(rgb_offsets, n),
                                                _size_array(rgb_row_strides, n), _rgb_layout(layout), w1), "hvc_decode_frames_mixed_rgb")
 
     def jpeg_decode_batch_mixed_rgb(self, jpegs, threads=8, chunk_bytes=0, device=False, layout="interleaved", row_align=0,
@@ -1430,39 +1401,14 @@ class Context:
         MixedRgbLayout made before and a buffer of rgb_layout.total_bytes to decode into (default: made here, zero-filled).
         The call's hvc_batch_stats: self.last_batch_stats."""
         lay = rgb_layout if rgb_layout is not None else MixedRgbLayout(jpegs, layout, 0, row_align)
-        n = len(lay)
-        if rgb is None:
-            if device:
-                import torch
-                rgb = torch.zeros(max(lay.total_bytes, 8), dtype=torch.uint8, device="cuda")
-            else:
-                rgb = np.zeros(max(lay.total_bytes, 8), dtype=np.uint8)
-        ra, where = _addr(rgb)
-        cap = rgb.numel() if hasattr(rgb, "numel") else rgb.size
-        st = BatchStats()
-        status = (C.c_int * n)(*lay.status)
-        _chk(lib().hvc_jpeg_decode_batch_mixed_rgb(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, lay.infos, status,
-                                                   lay.rgb_offsets, lay.rgb_row_strides, ra, cap, lay.layout, where, C.byref(st)),
-             "hvc_jpeg_decode_batch_mixed_rgb")
-        self.last_batch_stats = st
-        out = []
-        for f in range(n):
-            info = lay.infos[f] if lay.status[f] == 0 else None
-            image = None
-            if status[f] == 0 and info is not None and info.width > 0 and info.height > 0:
-                image = rgb_view(rgb, lay.rgb_offsets[f], lay.rgb_row_strides[f], info.width, info.height, lay.layout)
-            out.append((status[f], info, image))
-        return out
+        return self._decode_batch_mixed("hvc_jpeg_decode_batch_mixed_rgb", lay, rgb, device, (threads, chunk_bytes), lay.infos, True)
 
     def decode_frames_mixed_scaled(self, coefs, coef_offsets, infos, scale_denom, pixels, pixel_offsets):
         """hvc_decode_frames_mixed_scaled: decode_frames_mixed at 1 / scale_denom; infos[f].layout's plane_offset / stride place
         planes of blocks_w * N x blocks_h * N samples, N = 8 / scale_denom (any offset, any stride >= blocks_w * N)."""
-        ca, w1 = _addr(coefs)
-        pa, w2 = _addr(pixels)
-        assert w1 == w2, "coefs and pixels must live in the same memory space"
+        ca, pa, w1 = _same_space(coefs, "coefs", pixels, "pixels")
         n = len(infos)
-        arr = infos if isinstance(infos, C.Array) else (JpegInfo * n)(*infos)
-        _chk(lib().hvc_decode_frames_mixed_scaled(self._h, ca, _size_array(coef_offsets, n), arr, n, scale_denom, pa,
+        _chk(lib().hvc_decode_frames_mixed_scaled(self._h, ca, _size_array(coef_offsets, n), _infos_array(infos), n, scale_denom, pa,
                                                   _size_array(pixel_offsets, n), w1), "hvc_decode_frames_mixed_scaled")
 
     def jpeg_decode_batch_mixed_scaled(self, jpegs, scale_denom, threads=8, chunk_bytes=0, device=False, layout=None, pixels=None):
@@ -1470,29 +1416,8 @@ class Context:
         file, as jpeg_decode_batch_mixed does at full size; planes = views of the scaled padded planes inside ONE buffer.
         layout / pixels: a MixedScaledLayout made before and a buffer of layout.total_bytes (default: made here, zero-filled)."""
         lay = layout if layout is not None else MixedScaledLayout(jpegs, scale_denom)
-        n = len(lay)
-        if pixels is None:
-            if device:
-                import torch
-                pixels = torch.zeros(max(lay.total_bytes, 8), dtype=torch.uint8, device="cuda")
-            else:
-                pixels = np.zeros(max(lay.total_bytes, 8), dtype=np.uint8)
-        pa, where = _addr(pixels)
-        cap = pixels.numel() if hasattr(pixels, "numel") else pixels.size
-        st = BatchStats()
-        status = (C.c_int * n)(*lay.status)
-        _chk(lib().hvc_jpeg_decode_batch_mixed_scaled(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, scale_denom, lay.infos,
-                                                      status, lay.pixel_offsets, pa, cap, where, C.byref(st)),
-             "hvc_jpeg_decode_batch_mixed_scaled")
-        self.last_batch_stats = st
-        out = []
-        for f in range(n):
-            if lay.status[f] != 0:
-                out.append((status[f], None, None))
-                continue
-            info, off = lay.scaled[f], lay.pixel_offsets[f]
-            out.append((status[f], info, info.planes(pixels[off:off + info.pixel_bytes])))
-        return out
+        return self._decode_batch_mixed("hvc_jpeg_decode_batch_mixed_scaled", lay, pixels, device, (threads, chunk_bytes, scale_denom),
+                                        lay.scaled, False)
 
     def jpeg_decode_batch_mixed_scaled_rgb(self, jpegs, scale_denom, threads=8, chunk_bytes=0, device=False, layout="interleaved",
                                            row_align=0, rgb_layout=None, rgb=None):
@@ -1500,29 +1425,8 @@ class Context:
         info, image) per file, as jpeg_decode_batch_mixed_rgb does at full size.  rgb_layout / rgb: a MixedScaledRgbLayout made
         before and a buffer of rgb_layout.total_bytes (default: made here, zero-filled)."""
         lay = rgb_layout if rgb_layout is not None else MixedScaledRgbLayout(jpegs, scale_denom, layout, 0, row_align)
-        n = len(lay)
-        if rgb is None:
-            if device:
-                import torch
-                rgb = torch.zeros(max(lay.total_bytes, 8), dtype=torch.uint8, device="cuda")
-            else:
-                rgb = np.zeros(max(lay.total_bytes, 8), dtype=np.uint8)
-        ra, where = _addr(rgb)
-        cap = rgb.numel() if hasattr(rgb, "numel") else rgb.size
-        st = BatchStats()
-        status = (C.c_int * n)(*lay.status)
-        _chk(lib().hvc_jpeg_decode_batch_mixed_scaled_rgb(self._h, lay.ptrs, lay.sizes, n, threads, chunk_bytes, scale_denom, lay.infos,
-                                                          status, lay.rgb_offsets, lay.rgb_row_strides, ra, cap, lay.layout, where,
-                                                          C.byref(st)), "hvc_jpeg_decode_batch_mixed_scaled_rgb")
-        self.last_batch_stats = st
-        out = []
-        for f in range(n):
-            info = lay.scaled[f] if lay.status[f] == 0 else None
-            image = None
-            if status[f] == 0 and info is not None and info.width > 0 and info.height > 0:
-                image = rgb_view(rgb, lay.rgb_offsets[f], lay.rgb_row_strides[f], info.width, info.height, lay.layout)
-            out.append((status[f], info, image))
-        return out
+        return self._decode_batch_mixed("hvc_jpeg_decode_batch_mixed_scaled_rgb", lay, rgb, device, (threads, chunk_bytes, scale_denom),
+                                        lay.scaled, True)
 
     def rgb_resize_mixed(self, src, src_offsets, widths, heights, dst, dst_offsets, out_widths, out_heights, filter="bilinear",
                          layout="interleaved", src_row_strides=None, dst_row_strides=None, boxes=None, mirror=None, dtype=None,
@@ -1533,9 +1437,7 @@ class Context:
         set.  src / dst: numpy (host) or torch cuda tensors of bytes, both in the same memory space.
         boxes / mirror / dtype with mean, std / lut (resize_opts): hvc_rgb_resize_mixed_opts -- Pillow's resize(box=...), a
         left-right flip, and elements of dtype looked up in a table instead of bytes; dst offsets and strides stay in BYTES."""
-        sa, w1 = _addr(src)
-        da, w2 = _addr(dst)
-        assert w1 == w2, "src and dst must live in the same memory space"
+        sa, da, w1 = _same_space(src, "src", dst, "dst")
         n = len(widths)
         ints = lambda v: (C.c_int * max(n, 1))(*[int(x) for x in v])
         opts, keep, _, _ = resize_opts(n, boxes, mirror, dtype, mean, std, lut)
@@ -1578,13 +1480,9 @@ class Context:
             offs[f] = total
             total += 3 * max(w, 0) * max(h, 0) * esz
         if out is None:
-            if device:
-                import torch
-                out = torch.zeros(max(total, 8), dtype=torch.uint8, device="cuda")
-            else:
-                out = np.zeros(max(total, 8), dtype=np.uint8)
+            out = _zeroed_bytes(total, device)
         oa, where = _addr(out)
-        cap = out.numel() if hasattr(out, "numel") else out.size
+        cap = _capacity(out)
         st = BatchStats()
         status = (C.c_int * max(n, 1))(*lay.status)
         ow, oh = (C.c_int * max(n, 1))(*[w for w, _ in wh]), (C.c_int * max(n, 1))(*[h for _, h in wh])
@@ -1809,13 +1707,10 @@ class Context:
     def set_mixed_reader(self, which="gpu"):
         """hvc_set_mixed_reader: who reads the files of the mixed batch calls, "host" (the default) or "gpu" -- the mixed GPU
         Huffman reader; which one ran never changes a result"""
-        _chk(lib().hvc_set_mixed_reader(self._h, self.MIXED_READERS[which] if isinstance(which, str) else int(which)),
-             "hvc_set_mixed_reader")
+        self._set("hvc_set_mixed_reader", self.MIXED_READERS, which)
 
     def get_mixed_reader(self):
-        v = C.c_int(-1)
-        _chk(lib().hvc_get_mixed_reader(self._h, C.byref(v)), "hvc_get_mixed_reader")
-        return {0: "host", 1: "gpu"}[v.value]
+        return {0: "host", 1: "gpu"}[self._get("hvc_get_mixed_reader", -1)]
 
     def last_mixed_reader_files(self):
         """(gpu_files, host_files) of the last mixed batch call: the files that reached a reader, by the reader that read them"""
@@ -1852,9 +1747,32 @@ class Context:
         return out
 
     def _restart_slack(self, width, height):
-        """what the context's restart interval adds to a file of this size at most (see restart_slack)"""
-        ri = self.restart_interval
-        return 3 * -(-(-(-width // 8) * -(-height // 8)) // ri) + 6 if ri else 0
+        """what the context's restart interval adds to a file of this size at most.  Not restart_slack(info, ...): the callers
+        size their buffers before any JpegInfo of the frame exists, so the 8 x 8 blocks of the luma plane stand in for the MCUs
+        (never fewer)."""
+        return _interval_slack(-(-width // 8) * -(-height // 8), self.restart_interval)
+
+    def _huffman_coder(self, name, head, n, cap, tail, where, out=None):
+        """the tail of the GPU Huffman coder wrappers: name(*head, out, cap, offsets, *tail, where) with an output of cap bytes
+        (out: the caller's) and n + 1 offsets in the memory space `where` -- on the device after torch.cuda.synchronize(), what
+        was written read back -- cut into the n per-frame segments as bytes"""
+        fn = getattr(lib(), name)
+        if where == HVC_MEM_DEVICE:
+            import torch
+            if out is None:
+                out = torch.empty(max(cap, 1), dtype=torch.uint8, device="cuda")
+            offs = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            _chk(fn(*head, out.data_ptr(), cap, offs.data_ptr(), *tail, where), name)
+            o = offs.cpu().numpy()
+            data = out[:int(o[-1])].cpu().numpy()
+        else:
+            if out is None:
+                out = np.empty(max(cap, 1), dtype=np.uint8)
+            o = np.zeros(n + 1, dtype=np.uint64)
+            _chk(fn(*head, out.ctypes.data, cap, o.ctypes.data, *tail, where), name)
+            data = out
+        return [data[int(o[f]):int(o[f + 1])].tobytes() for f in range(n)]
 
     def huffman_encode_frames(self, info, coefs, coef_frame_stride, n_frames, out_cap=None, restart_interval=0):
         """Encoder back end on the GPU: (list of per-frame entropy-coded segments as bytes).  coefs: host
@@ -1864,48 +1782,18 @@ class Context:
             return self._huffman_encode_frames_restart(info, coefs, coef_frame_stride, n_frames, out_cap, restart_interval, False)[0]
         ca, where = _addr(coefs)
         cap = out_cap or (n_frames * (info.coef_count // 64) * 243 + 4096)
-        if where == 1:
-            import torch
-            out = torch.empty(cap, dtype=torch.uint8, device="cuda")
-            offs = torch.zeros(n_frames + 1, dtype=torch.int64, device="cuda")
-            torch.cuda.synchronize()
-            _chk(lib().hvc_huffman_encode_frames(self._h, C.byref(info), ca, coef_frame_stride, n_frames, out.data_ptr(),
-                                                 cap, offs.data_ptr(), 1), "hvc_huffman_encode_frames")
-            o = offs.cpu().numpy()
-            data = out[:int(o[-1])].cpu().numpy()
-        else:
-            out = np.empty(cap, dtype=np.uint8)
-            offs = np.zeros(n_frames + 1, dtype=np.uint64)
-            _chk(lib().hvc_huffman_encode_frames(self._h, C.byref(info), ca, coef_frame_stride, n_frames, out.ctypes.data,
-                                                 cap, offs.ctypes.data, 0), "hvc_huffman_encode_frames")
-            o, data = offs, out
-        return [data[int(o[f]):int(o[f + 1])].tobytes() for f in range(n_frames)]
+        return self._huffman_coder("hvc_huffman_encode_frames", (self._h, C.byref(info), ca, coef_frame_stride, n_frames), n_frames,
+                                   cap, (), where)
 
     def _huffman_encode_frames_restart(self, info, coefs, coef_frame_stride, n_frames, out_cap, restart_interval, optimised):
         """hvc_huffman_encode_frames_restart -> (segments, per-frame specs or None)"""
         ca, where = _addr(coefs)
         cap = out_cap or (n_frames * ((info.coef_count // 64) * 243 + restart_slack(info, restart_interval)) + 4096)
         specs = (HuffSpec * max(4 * n_frames, 1))() if optimised else None
-        tables = HVC_HUFF["optimised" if optimised else "default"]
-        if where == 1:
-            import torch
-            out = torch.empty(cap, dtype=torch.uint8, device="cuda")
-            offs = torch.zeros(n_frames + 1, dtype=torch.int64, device="cuda")
-            torch.cuda.synchronize()
-            _chk(lib().hvc_huffman_encode_frames_restart(self._h, C.byref(info), ca, coef_frame_stride, n_frames,
-                                                         int(restart_interval), tables, out.data_ptr(), cap, offs.data_ptr(),
-                                                         specs, 1), "hvc_huffman_encode_frames_restart")
-            o = offs.cpu().numpy()
-            data = out[:int(o[-1])].cpu().numpy()
-        else:
-            out = np.empty(cap, dtype=np.uint8)
-            offs = np.zeros(n_frames + 1, dtype=np.uint64)
-            _chk(lib().hvc_huffman_encode_frames_restart(self._h, C.byref(info), ca, coef_frame_stride, n_frames,
-                                                         int(restart_interval), tables, out.ctypes.data, cap, offs.ctypes.data,
-                                                         specs, 0), "hvc_huffman_encode_frames_restart")
-            o, data = offs, out
-        return ([data[int(o[f]):int(o[f + 1])].tobytes() for f in range(n_frames)],
-                [[specs[4 * f + t].to_pair() for t in range(4)] for f in range(n_frames)] if optimised else None)
+        segs = self._huffman_coder("hvc_huffman_encode_frames_restart",
+                                   (self._h, C.byref(info), ca, coef_frame_stride, n_frames, int(restart_interval),
+                                    HVC_HUFF["optimised" if optimised else "default"]), n_frames, cap, (specs,), where)
+        return segs, _spec_pairs(specs, n_frames)
 
     def huffman_encode_frames_optimised(self, info, coefs, coef_frame_stride, n_frames, out_cap=None, restart_interval=0):
         """hvc_huffman_encode_frames with each frame's own optimal tables, counted and built on the GPU: (list of per-frame
@@ -1916,33 +1804,16 @@ class Context:
         ca, where = _addr(coefs)
         cap = out_cap or (n_frames * (info.coef_count // 64) * 243 + 4096)
         specs = (HuffSpec * max(4 * n_frames, 1))()
-        if where == 1:
-            import torch
-            out = torch.empty(cap, dtype=torch.uint8, device="cuda")
-            offs = torch.zeros(n_frames + 1, dtype=torch.int64, device="cuda")
-            torch.cuda.synchronize()
-            _chk(lib().hvc_huffman_encode_frames_optimised(self._h, C.byref(info), ca, coef_frame_stride, n_frames,
-                                                           out.data_ptr(), cap, offs.data_ptr(), specs, 1),
-                 "hvc_huffman_encode_frames_optimised")
-            o = offs.cpu().numpy()
-            data = out[:int(o[-1])].cpu().numpy()
-        else:
-            out = np.empty(cap, dtype=np.uint8)
-            offs = np.zeros(n_frames + 1, dtype=np.uint64)
-            _chk(lib().hvc_huffman_encode_frames_optimised(self._h, C.byref(info), ca, coef_frame_stride, n_frames,
-                                                           out.ctypes.data, cap, offs.ctypes.data, specs, 0),
-                 "hvc_huffman_encode_frames_optimised")
-            o, data = offs, out
-        return ([data[int(o[f]):int(o[f + 1])].tobytes() for f in range(n_frames)],
-                [[specs[4 * f + t].to_pair() for t in range(4)] for f in range(n_frames)])
+        segs = self._huffman_coder("hvc_huffman_encode_frames_optimised", (self._h, C.byref(info), ca, coef_frame_stride, n_frames),
+                                   n_frames, cap, (specs,), where)
+        return segs, _spec_pairs(specs, n_frames)
 
     def jpeg_encode_batch(self, frames, width, height, chroma=420, quality=75, threads=8, frames_per_chunk=16,
                           gpu_entropy=False):
         """Encoder.encode_4xx over a batch of raw planar frames (bytes / uint8 arrays in Frame.input layout).
         Returns (list of jpeg byte strings, BatchStats).  gpu_entropy: Huffman coding on the GPU as well."""
         n = len(frames)
-        arrs = [np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray)) else
-                np.ascontiguousarray(f, dtype=np.uint8).reshape(-1) for f in frames]
+        arrs = _flat_bytes(frames)
         cw = width if chroma == 444 else width // 2
         ch = height // 2 if chroma == 420 else height
         need = width * height + 2 * cw * ch
@@ -1981,34 +1852,16 @@ class Context:
         here)."""
         n = len(infos)
         m = max(n, 1)
-        arr = infos if isinstance(infos, C.Array) else (JpegInfo * m)(*infos)
+        arr = _infos_array(infos)
         ca, where = _addr(coefs) if coefs is not None else (None, HVC_MEM_HOST)
         cap = out_cap if out_cap is not None else sum((arr[f].coef_count // 64) * 243 for f in range(n)) + 4096
         status = (C.c_int * m)(*([77] * m))
         specs = (HuffSpec * (4 * m))() if optimised else None
-        tables = HVC_HUFF["optimised" if optimised else "default"]
-        co = _size_array(coef_offsets, n)
-        if where == 1:
-            import torch
-            if out is None:
-                out = torch.empty(max(cap, 1), dtype=torch.uint8, device="cuda")
-            offs = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
-            torch.cuda.synchronize()
-            _chk(lib().hvc_huffman_encode_frames_mixed(self._h, arr, ca, co, n, tables, out.data_ptr(), cap, offs.data_ptr(), status,
-                                                       specs, 1), "hvc_huffman_encode_frames_mixed")
-            o = offs.cpu().numpy()
-            data = out[:int(o[-1])].cpu().numpy()
-        else:
-            if out is None:
-                out = np.empty(max(cap, 1), dtype=np.uint8)
-            offs = np.zeros(n + 1, dtype=np.uint64)
-            _chk(lib().hvc_huffman_encode_frames_mixed(self._h, arr, ca, co, n, tables, out.ctypes.data, cap, offs.ctypes.data, status,
-                                                       specs, 0), "hvc_huffman_encode_frames_mixed")
-            o, data = offs, out
-        segs = [data[int(o[f]):int(o[f + 1])].tobytes() for f in range(n)]
+        segs = self._huffman_coder("hvc_huffman_encode_frames_mixed",
+                                   (self._h, arr, ca, _size_array(coef_offsets, n), n, HVC_HUFF["optimised" if optimised else "default"]),
+                                   n, cap, (status, specs), where, out)
         st = [status[f] for f in range(n)]
-        sp = [[specs[4 * f + t].to_pair() for t in range(4)] if st[f] == 0 else None for f in range(n)] if optimised else None
-        return segs, st, sp
+        return segs, st, _spec_pairs(specs, n, st)
 
     def jpeg_encode_batch_mixed(self, frames, specs=None, threads=8, chunk_bytes=0, layout=None, caps=None, outs=None, coder="host"):
         """hvc_jpeg_encode_batch_mixed (coder="gpu": hvc_jpeg_encode_batch_mixed_gpu, the Huffman coder on the GPU too): raw planar frames (bytes / uint8 arrays, tight Y, U, V) of any sizes, samplings and
@@ -2018,17 +1871,24 @@ class Context:
         capacity and the uint8 output array of every frame (default: made here, large enough).  The call's hvc_batch_stats:
         self.last_batch_stats."""
         lay = layout if layout is not None else EncoderMixedLayout(specs)
-        n = len(lay)
-        m = max(n, 1)
-        arrs = [np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray)) else
-                np.ascontiguousarray(f, dtype=np.uint8).reshape(-1) for f in frames]
-        assert len(arrs) == n
+        arrs = _flat_bytes(frames)
+        assert len(arrs) == len(lay)
         for f, a in enumerate(arrs):
             if lay.status[f] == 0:
                 k = lay.infos[f].comp
                 need = sum(k[i].actual_width * k[i].actual_height for i in range(3))
                 if a.size < need:
                     raise ValueError("frame %d shorter than %d bytes" % (f, need))
+        return self._encode_batch_mixed("hvc_jpeg_encode_batch_mixed", coder, lay, arrs, (), threads, chunk_bytes, caps, outs)
+
+    def _encode_batch_mixed(self, name, coder, lay, arrs, front, threads, chunk_bytes, caps, outs):
+        """the tail of the two mixed encode batch calls: name (coder "gpu": name_gpu) (ctx, frames, *front, infos, status, n,
+        threads, chunk_bytes, jpegs, caps, sizes, stats) over the flat uint8 arrays `arrs`, into outs / caps (None: made here,
+        large enough for any file of the frame's size under the context's restart interval; 8 bytes for a frame the layout
+        refused), the stats into self.last_batch_stats -> one (status, jpeg bytes or None, size) per frame"""
+        name += {"host": "", "gpu": "_gpu"}[coder]
+        n = len(lay)
+        m = max(n, 1)
         if outs is None:
             ri = self.restart_interval
             outs = [np.empty(8, dtype=np.uint8) if lay.status[f] else
@@ -2042,8 +1902,7 @@ class Context:
         sizes = (C.c_size_t * m)()
         status = (C.c_int * m)(*lay.status)
         st = BatchStats()
-        name = {"host": "hvc_jpeg_encode_batch_mixed", "gpu": "hvc_jpeg_encode_batch_mixed_gpu"}[coder]
-        _chk(getattr(lib(), name)(self._h, fp, lay.infos, status, n, threads, chunk_bytes, op, cp, sizes, C.byref(st)), name)
+        _chk(getattr(lib(), name)(self._h, fp, *front, lay.infos, status, n, threads, chunk_bytes, op, cp, sizes, C.byref(st)), name)
         self.last_batch_stats = st
         return [(status[f], outs[f][:sizes[f]].tobytes() if status[f] == 0 else None, sizes[f]) for f in range(n)]
 
@@ -2055,12 +1914,9 @@ class Context:
         EncoderMixedLayout / EncoderMixedRgbLayout made before.  Results, caps and outs as jpeg_encode_batch_mixed; every file
         equals jpeg_encode_rgb's for that image alone."""
         lay = enc_layout if enc_layout is not None else EncoderMixedRgbLayout(specs, layout)
-        n = len(lay)
-        m = max(n, 1)
         code = _rgb_layout(layout)
-        arrs = [np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray)) else
-                np.ascontiguousarray(f, dtype=np.uint8).reshape(-1) for f in images]
-        assert len(arrs) == n
+        arrs = _flat_bytes(images)
+        assert len(arrs) == len(lay)
         for f, a in enumerate(arrs):
             if lay.status[f] == 0:
                 w, h = lay.infos[f].width, lay.infos[f].height
@@ -2069,37 +1925,18 @@ class Context:
                 rs = (rgb_row_strides[f] if rgb_row_strides is not None else 0) or tight
                 if rs >= tight and a.size < (rows - 1) * rs + tight:
                     raise ValueError("image %d shorter than %d bytes" % (f, (rows - 1) * rs + tight))
-        if outs is None:
-            ri = self.restart_interval
-            outs = [np.empty(8, dtype=np.uint8) if lay.status[f] else
-                    np.empty(4 * lay.infos[f].width * lay.infos[f].height + 65536 + restart_slack(lay.infos[f], ri), dtype=np.uint8)
-                    for f in range(n)]
-        if caps is None:
-            caps = [o.size for o in outs]
-        fp = (C.c_void_p * m)(*[a.ctypes.data for a in arrs])
-        op = (C.c_void_p * m)(*[o.ctypes.data for o in outs])
-        cp = (C.c_size_t * m)(*[int(x) for x in caps])
-        sizes = (C.c_size_t * m)()
-        status = (C.c_int * m)(*lay.status)
-        st = BatchStats()
-        name = {"host": "hvc_jpeg_encode_batch_mixed_rgb", "gpu": "hvc_jpeg_encode_batch_mixed_rgb_gpu"}[coder]
-        _chk(getattr(lib(), name)(self._h, fp, _size_array(rgb_row_strides, n), code, lay.infos, status, n, threads, chunk_bytes, op, cp,
-                                  sizes, C.byref(st)), name)
-        self.last_batch_stats = st
-        return [(status[f], outs[f][:sizes[f]].tobytes() if status[f] == 0 else None, sizes[f]) for f in range(n)]
+        return self._encode_batch_mixed("hvc_jpeg_encode_batch_mixed_rgb", coder, lay, arrs, (_size_array(rgb_row_strides, len(lay)), code),
+                                        threads, chunk_bytes, caps, outs)
 
     # -- encode -------------------------------------------------------------
     def encode_frames_mixed(self, pixels, pixel_offsets, infos, coefs, coef_offsets):
         """hvc_encode_frames_mixed: frame f = infos[f] (JpegInfo: layout and tables), its padded pixel record at
         pixels[pixel_offsets[f]:] (bytes), its coefficient record written at coefs[coef_offsets[f]:] (int16 elements).
         pixels / coefs: numpy (host) or torch cuda tensors, both in the same memory space."""
-        pa, w1 = _addr(pixels)
-        ca, w2 = _addr(coefs)
-        assert w1 == w2, "pixels and coefs must live in the same memory space"
+        pa, ca, w1 = _same_space(pixels, "pixels", coefs, "coefs")
         n = len(infos)
-        arr = infos if isinstance(infos, C.Array) else (JpegInfo * max(n, 1))(*infos)
-        _chk(lib().hvc_encode_frames_mixed(self._h, pa, _size_array(pixel_offsets, n), arr, n, ca, _size_array(coef_offsets, n), w1),
-             "hvc_encode_frames_mixed")
+        _chk(lib().hvc_encode_frames_mixed(self._h, pa, _size_array(pixel_offsets, n), _infos_array(infos), n, ca,
+                                           _size_array(coef_offsets, n), w1), "hvc_encode_frames_mixed")
 
     def fdct_quant(self, plane, qtab, blocks_w, blocks_h, n_planes, coefs, stride=None, plane_stride=0,
                    coef_plane_stride=0):
